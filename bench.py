@@ -12,12 +12,14 @@ extras   : the AE half of the metric (configs[1]: encode / decode ms + `roofline
            training step with the RCCL gradient exchange are appended to the same JSON line.
 guard    : every RALD_* environment variable is recorded in config.env; the run exits non-zero if the loaded library is a
            PROBE build (the only build with work-skipping switches) or if a probe-only / library-override variable is set.
+outputs  : --dump-outputs DIR writes what the last timed NFE returned (rank 0's shard) as DIR/denoised.npy, float32; inputs
+           and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 Multi-GPU (driver launches torchrun, one rank per GPU): samples are independent, so the batch
 is sharded across ranks with NO data-path collective ("weak" scaling: B per GPU is fixed);
 the only communication is the barrier + MAX-reduce of the elapsed time (RCCL).
 
-  python bench.py --gpus N --steps K --warmup W [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -33,6 +35,7 @@ sys.path.insert(0, ROOT)
 GFLOP_PER_NFE = 132.18          # SURVEY.md §8d / BASELINE.md §3 (multiply-add = 2 FLOP)
 PEAK_BF16_TFLOPS = 2500.0       # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip table)
 PEAK_HBM_GBS = 8000.0           # MI355X HBM3E (same table; ~6.3 TB/s is what a streaming copy reaches)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together
 
 
 def source_fingerprint():
@@ -131,6 +134,25 @@ def max_over_ranks(val, world):
     return float(t.item())
 
 
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes each tensor as dirname/<name>.npy in float32.  A tensor larger than its even share of `limit` keeps a fixed subset of
+    its dim-0 rows (samples): rows i * n // keep for i < keep, the same for every run of the same arguments.  Returns the files."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(len(arrays), 1) - 4096           # room for the .npy header
+    files = {}
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        n = t.shape[0]
+        keep = min(n, max(share // max(t[0].numel() * 4, 1), 1))
+        if keep < n:
+            t = t[torch.arange(keep) * n // keep]
+        path = os.path.join(dirname, f"{name}.npy")
+        np.save(path, t.contiguous().numpy())
+        files[name] = {"path": path, "shape": list(t.shape), "rows_of": n}
+    return files
+
+
 def build_denoiser(depth=24):
     from rald_amd import models_radar_generation as G, weights
     m = G.LatentArrayTransformer(in_channels=32, t_channels=256, n_heads=8, d_head=64, depth=depth)
@@ -196,7 +218,11 @@ def main():
     ap.add_argument("--batch", type=int, default=128, help="samples per GPU per NFE")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed NFE's output as DIR/denoised.npy (float32, at most 64 MB: a fixed subset of samples beyond)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env = env_guard()
     world, rank, local = dist_setup(args.gpus)
@@ -219,16 +245,22 @@ def main():
         h.denoise(x, cache, 0)
     barrier(world)
     h.profile_begin()
+    y = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         # the dominant kernel (FF1) is bracketed by HIP events on every launch of the timed region; the three residual + LayerNorm GEMMs on its
         # first three NFEs only: an event pair costs ~2.5 us of stream time and 96 pairs per NFE took 0.5 ms (2.5 %) off the rate being measured
         if i == 3:
             h.profile_set_kinds(0x1)
-        h.denoise(x, cache, 0)
+        del y           # the previous output returns to the allocator before the next is made: every step reuses one block
+        y = h.denoise(x, cache, 0)
     barrier(world)
     elapsed = time.perf_counter() - t0
     kinds = h.profile_end_kinds()
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"denoised": y})
+        log(f"outputs of the last timed step: {dumped}")
+    del y
     ff1_ms, ff1_launches = kinds[0]
     elapsed = max_over_ranks(elapsed, world)
 

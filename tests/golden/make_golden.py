@@ -249,6 +249,7 @@ def main():
         golden_long_horizon(only)
     if want("g18"):
         golden_stress_ae()
+        golden_stress_ae_f64()
     if want("g19"):
         golden_stress_dit()
     if want("g20"):
@@ -482,6 +483,27 @@ def golden_stress_ae():
         torch.manual_seed(99)
         out["eps"] = torch.randn(2, 512, 32)
         save("g18_ae_stress.npz", **out)
+
+
+def golden_stress_ae_f64():
+    """G18 b) encode in float64: with peaked attentions logvar reaches ~23 and z = mean + exp(logvar / 2) * eps multiplies logvar's
+    rounding by ~11, so the float32 vectors hold only as far as float32 sums happen to round alike on the host CPU (the float32
+    moments are 1.4e-5 from exact).  The same reference run in float64 (eps still float32 randn, as the reference draws it) pins
+    the encode independently of the CPU."""
+    G, A, R = import_reference()
+    with torch.no_grad():
+        ae = A.kl_d512_m512_l32_mix(N=10000)
+        sd = weights.stress_ae_state_dict(weights.make_state_dict(seed_module(ae, 0), 0))
+        ae.load_state_dict(sd, strict=True)
+        ae.double()
+        hooks = {}
+        h1 = ae.mean_fc.register_forward_hook(lambda m_, i, o: hooks.setdefault("mean", o))
+        h2 = ae.logvar_fc.register_forward_hook(lambda m_, i, o: hooks.setdefault("logvar", o))
+        torch.manual_seed(99)
+        kl, z = ae.encode(synth.structured_cloud(2, 10000).double())
+        h1.remove(); h2.remove()
+        assert z.dtype == torch.float64
+        save("g18_ae_stress_f64.npz", peaked_kl=kl, peaked_z=z, peaked_mean=hooks["mean"], peaked_logvar=hooks["logvar"])
 
 
 def golden_stress_dit():

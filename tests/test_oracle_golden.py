@@ -204,9 +204,16 @@ def test_g18_autoencoder_on_structured_cloud(tag):
     sd = weights.make_state_dict(weights.ae_spec(), seed=0)
     if tag == "peaked":
         sd = weights.stress_ae_state_dict(sd, out_bias=float(g["peaked_out_bias"]))
-    kl, z, mean, logvar = O.ae_encode(sd, synth.structured_cloud(2, 10000), g["eps"])
-    assert rel_l2(mean, g[f"{tag}_mean"]) < TOL and rel_l2(logvar, g[f"{tag}_logvar"]) < TOL
-    assert rel_l2(z, g[f"{tag}_z"]) < TOL and rel_l2(kl, g[f"{tag}_kl"]) < TOL
+    pc, enc = synth.structured_cloud(2, 10000), g
+    if tag == "peaked":
+        # logvar reaches ~23 and exp(logvar / 2) multiplies its float32 rounding ~11x in z (the float32 moments are themselves 1.4e-5
+        # from exact): the encode is compared in float64 with the reference run in float64, which holds on any host CPU
+        enc = load_golden("g18_ae_stress_f64.npz")
+        kl, z, mean, logvar = O.ae_encode({k: v.double() for k, v in sd.items()}, pc.double(), g["eps"].double())
+    else:
+        kl, z, mean, logvar = O.ae_encode(sd, pc, g["eps"])
+    assert rel_l2(mean, enc[f"{tag}_mean"]) < TOL and rel_l2(logvar, enc[f"{tag}_logvar"]) < TOL
+    assert rel_l2(z, enc[f"{tag}_z"]) < TOL and rel_l2(kl, enc[f"{tag}_kl"]) < TOL
     logits = O.ae_decode(sd, g[f"{tag}_z"], synth.structured_queries(2, 4096), depth=24).squeeze(-1)
     ref = g[f"{tag}_logits"]
     assert float((logits - ref).abs().max()) < 2e-4 * max(1.0, float(ref.abs().max()))      # (peaked logits straddle 0: absolute bound)
