@@ -26,9 +26,8 @@ extern "C" {
 
 const char* rald_last_error(void);
 int rald_version(void);
-/* bit 0: PROBE build (`make PROBE=1`): the only build whose kernels honour the RALD_* A/B and ablation environment
- * switches, some of which skip work (no DMA in a main loop, no epilogue stores).  0 for the shipped library, which reads no
- * environment variable at all; bench.py refuses to measure a library that reports anything else. */
+/* Always 0: the library reads no environment variable and has no work-skipping build.  bench.py refuses to measure a
+ * library that reports anything else. */
 int rald_build_flags(void);
 /* Diagnostic (synchronises the device): how many times a lane clamped a value while writing an fp16 partial-sum slab since the last
  * reset.  The small-batch paths (<= 2 samples) pass per-head / split-K partial sums between kernels as fp16 x 2^-6, saturating at
@@ -446,10 +445,11 @@ int rald_op_layernorm_mx8(const float* x, void* out_e4m3, void* out_scales_e8m0,
 /* out_bf16 = LayerNorm(x_f32[M][D]) * (add_one + g[row/rows_per_group*gstride + c]) + b[...] */
 int rald_op_layernorm(const float* x, void* out_bf16, int32_t M, int32_t D, const float* g, const float* b,
                       int64_t gstride, int32_t rows_per_group, float add_one, float eps, void* stream);
-/* multi-head attention, head dim 64; Q[b][i][h*64+d], K[b][j][h*64+d], Vt[b][h*64+d][j] bf16 */
+/* multi-head attention, head dim 64; Q[b][i][h*64+d], K[b][j][h*64+d], Vt[b][h*64+d][j] bf16.  q_prescaled != 0: Q is already
+ * multiplied by scale*log2(e) (as the denoiser's projections produce it) and `scale` is ignored. */
 int rald_op_attention(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
                       const void* Vt, int64_t ldvt, int64_t strideVt, void* O, int64_t ldo, int64_t strideO,
-                      int32_t nq, int32_t nk, int32_t k_rows, int32_t heads, int32_t batch, float scale, void* stream);
+                      int32_t nq, int32_t nk, int32_t k_rows, int32_t heads, int32_t batch, float scale, int32_t q_prescaled, void* stream);
 /* rald_op_attention with the keys split over `ksplit` workgroups per query block (few queries x many keys, e.g. 512
  * latents x 10 000 points at batch 1): partial results go through `scratch` (rald_op_attention_split_scratch_bytes)
  * and a combine pass.  ksplit <= 0 picks a value from the shape. */

@@ -310,13 +310,14 @@ def op_layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, gstride: int
     return out
 
 
-def op_attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, nk: int, heads: int, scale: float) -> torch.Tensor:
-    """Q [B,nq,H*64], K [B,k_rows,H*64], Vt [B,H*64,ldvt] (bf16) -> O [B,nq,H*64] bf16."""
+def op_attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, nk: int, heads: int, scale: float, prescaled: bool = False) -> torch.Tensor:
+    """Q [B,nq,H*64], K [B,k_rows,H*64], Vt [B,H*64,ldvt] (bf16) -> O [B,nq,H*64] bf16.  prescaled: Q is already multiplied by
+    scale*log2(e) and `scale` is ignored."""
     Bn, nq, HD = Q.shape
     O = torch.empty(Bn, nq, HD, device=Q.device, dtype=torch.bfloat16)
     check(lib().rald_op_attention(C.c_void_p(_ptr(Q)), Q.stride(1), Q.stride(0), C.c_void_p(_ptr(K)), K.stride(1), K.stride(0),
                                   C.c_void_p(_ptr(Vt)), Vt.stride(1), Vt.stride(0), C.c_void_p(_ptr(O)), O.stride(1), O.stride(0),
-                                  nq, nk, K.shape[1], heads, Bn, scale, C.c_void_p(_stream())))
+                                  nq, nk, K.shape[1], heads, Bn, scale, int(prescaled), C.c_void_p(_stream())))
     return O
 
 

@@ -14,13 +14,7 @@ extern "C" {
 
 const char* rald_last_error(void) { return rald::last_error(); }
 int rald_version(void) { return 2; }
-int rald_build_flags(void) {
-#ifdef RALD_PROBE
-    return 1;
-#else
-    return 0;
-#endif
-}
+int rald_build_flags(void) { return 0; }
 
 int64_t rald_debug_f16_saturation_count(int32_t reset) {
     unsigned a = 0, b = 0;
@@ -301,8 +295,7 @@ int rald_op_gemm_nt(const void* A, int64_t lda, int64_t strideA, const void* B, 
     RALD_CHECK(A && B && C, "rald_op_gemm_nt: null pointer");
     GemmArgs g;
     g.A = (const bf16*)A; g.lda = lda; g.strideA = strideA; g.B = (const bf16*)B; g.ldb = ldb; g.strideB = strideB;
-    g.C = C; g.ldc = ldc; g.strideC = strideC; g.bias = bias; g.M = M; g.N = N; g.K = K; g.batch = batch; g.alpha = alpha; g.alpha_ncols = 1 << 30; g.ablate = 0;
-    g.ablate = RALD_PROBE_ENV("RALD_GEMM_ABLATE", 0);
+    g.C = C; g.ldc = ldc; g.strideC = strideC; g.bias = bias; g.M = M; g.N = N; g.K = K; g.batch = batch; g.alpha = alpha; g.alpha_ncols = 1 << 30; g.flags = 0;
     return gemm_nt(g, epilogue, (hipStream_t)stream);
 }
 int rald_op_gemm_nt2(const void* A, int64_t lda, int64_t strideA, int64_t strideA2, const void* B, int64_t ldb, int64_t strideB, int64_t strideB2,
@@ -460,7 +453,7 @@ int rald_op_gemm_mx8(const void* A8, const void* scaleA, int64_t lda, int64_t st
     a.strideSA = strideSA; a.strideSB = strideSB;
     GemmArgs& g = a.g;
     g.A = nullptr; g.lda = lda; g.strideA = strideA; g.B = nullptr; g.ldb = ldb; g.strideB = strideB;
-    g.C = C; g.ldc = ldc; g.strideC = strideC; g.bias = bias; g.M = M; g.N = N; g.K = K; g.batch = batch; g.alpha = alpha; g.alpha_ncols = 1 << 30; g.ablate = 0;
+    g.C = C; g.ldc = ldc; g.strideC = strideC; g.bias = bias; g.M = M; g.N = N; g.K = K; g.batch = batch; g.alpha = alpha; g.alpha_ncols = 1 << 30; g.flags = 0;
     return gemm_mx8(a, epilogue, (hipStream_t)stream);
 }
 int rald_op_quantize_mx8(const void* in, int32_t in_is_bf16, int64_t ld_in, void* out_e4m3, int64_t ld_out, void* out_scales_e8m0, int64_t rows,
@@ -481,13 +474,12 @@ int rald_op_layernorm(const float* x, void* out_bf16, int32_t M, int32_t D, cons
 }
 int rald_op_attention(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
                       const void* Vt, int64_t ldvt, int64_t strideVt, void* O, int64_t ldo, int64_t strideO,
-                      int32_t nq, int32_t nk, int32_t k_rows, int32_t heads, int32_t batch, float scale, void* stream) {
+                      int32_t nq, int32_t nk, int32_t k_rows, int32_t heads, int32_t batch, float scale, int32_t q_prescaled, void* stream) {
     RALD_CHECK(Q && K && Vt && O, "rald_op_attention: null pointer");
     AttnArgs a;
     a.Q = (const bf16*)Q; a.ldq = ldq; a.strideQ = strideQ; a.K = (const bf16*)K; a.ldk = ldk; a.strideK = strideK;
     a.Vt = (const bf16*)Vt; a.ldvt = ldvt; a.strideVt = strideVt; a.O = (bf16*)O; a.ldo = ldo; a.strideO = strideO;
-    a.nq = nq; a.nk = nk; a.k_rows = k_rows; a.heads = heads; a.batch = batch; a.scale = scale; a.q_prescaled = 0;
-    a.q_prescaled = RALD_PROBE_ENV("RALD_ATTN_PRESCALED", a.q_prescaled);   // timing experiments (probe builds)
+    a.nq = nq; a.nk = nk; a.k_rows = k_rows; a.heads = heads; a.batch = batch; a.scale = scale; a.q_prescaled = q_prescaled != 0;
     return attention_d64(a, (hipStream_t)stream);
 }
 int64_t rald_op_attention_split_scratch_bytes(int32_t ksplit, int32_t nq, int32_t heads, int32_t batch) {

@@ -387,8 +387,7 @@ int Dit::build_table(SigmaTable& t, const float* sig, int n, hipStream_t st) {
 int Dit::set_sigmas(const float* sig, int n, hipStream_t st) { return build_table(tables[0], sig, n, st); }
 
 bool Dit::cond_fold(int B) const {
-    static const bool on = RALD_PROBE_ENV("RALD_COND_FOLD", 1) != 0;
-    return on && cfg.qkv_dtype == 0 && cfg.n_cond_tokens == 64 && cfg.d_head == 64 && cfg.n_heads * 64 == D && cfg.n_latents % 128 == 0 &&
+    return cfg.qkv_dtype == 0 && cfg.n_cond_tokens == 64 && cfg.d_head == 64 && cfg.n_heads * 64 == D && cfg.n_latents % 128 == 0 &&
            !small_m_fused(B * cfg.n_latents, cfg.n_latents, cfg.n_heads, D, cfg.n_cond_tokens);
 }
 
@@ -564,14 +563,12 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
         if (timed) { RALD_HIP(hipEventRecord(prof_ev[prof_used + 1], st)); prof_kind[prof_used / 2] = kind; prof_used += 2; }
         return 0;
     };
-    // probe builds: RALD_FUSE_LN=0 falls back to separate LayerNorm launches (A/B and debugging)
-    static const bool fuse_ln = RALD_PROBE_ENV("RALD_FUSE_LN", 1) != 0;
     auto resid_ln = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* mnext) -> int {
         // x += A.W^T + bias, then (if mnext) h = AdaLN(x; mnext) for the next sub-block
         if (splitk_for(M, K))
             return resid_splitk_ln(A, lda, W, ldw, bias, ws_x, mnext ? ws_h : nullptr, mnext, mnext ? mnext + D : nullptr, gstride, NL, 1.0f, 1e-5f,
                                    M, K, splitk_for(M, K), ws_part, st);
-        if (fuse_ln && mnext && gemm_resid_ln_pays(M, K)) {
+        if (mnext && gemm_resid_ln_pays(M, K)) {
             GemmLnArgs g;
             g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = ws_x; g.h = ws_h;
             g.g = mnext; g.b = mnext + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f;
@@ -585,7 +582,7 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
     };
     // the same with one weight matrix per sample (W + sample * strideW): the folded cross-attention's output projection
     auto resid_ln_w = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* mnext, int64_t strideW) -> int {
-        if (fuse_ln && mnext && gemm_resid_ln_pays(M, K)) {
+        if (mnext && gemm_resid_ln_pays(M, K)) {
             GemmLnArgs g;
             g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = ws_x; g.h = ws_h;
             g.g = mnext; g.b = mnext + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f;
@@ -620,7 +617,7 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
         };
         // x += A.W^T + bias (bf16 GEMM), then the next AdaLN as MXFP8 into ws_h8 / ws_hs
         auto resid_ln8 = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* mnext) -> int {
-            if (fuse_ln && gemm_resid_ln_pays(M, K)) {
+            if (gemm_resid_ln_pays(M, K)) {
                 GemmLnArgs g;
                 g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = ws_x; g.h = nullptr; g.h8 = ws_h8; g.hs = ws_hs;
                 g.g = mnext; g.b = mnext + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f;
@@ -672,7 +669,7 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
             RALD_TRY(attention_d64(a2, st));
             // qkv_dtype 3: the GEGLU output leaves the FF1 epilogue as MXFP8 and ff.net.2 (+ residual + next AdaLN) consumes it
             if (fork_pending && timed_ok) { RALD_HIP(hipEventRecord(ev_fork, st)); fork_pending = false; }   // two-stream schedule: the other half starts here
-            const bool ff2_mx = cfg.qkv_dtype == 3 && M % 256 == 0 && M >= 4096 && fuse_ln && gemm_resid_ln_pays(M, 4 * D);
+            const bool ff2_mx = cfg.qkv_dtype == 3 && M % 256 == 0 && M >= 4096 && gemm_resid_ln_pays(M, 4 * D);
             if (cfg.qkv_dtype >= 2) {
                 RALD_TRY(resid_ln8(ws_o, D, l.w_o2, D, l.b_o2, D, m3));                  // + norm3 (MXFP8)
                 Mx8Args f1 = mx(ws_h8, ws_hs, l.q8_ff1, l.s8_ff1, ws_g, 4 * D, l.b_ff1, M, 8 * D);
@@ -708,9 +705,8 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
         // (norm1(x) is already in ws_h: produced by the previous block's FF2 epilogue / the prologue)
         (void)m1;
         // one projection for q | k | v (N = 1536); the attention kernel reads V row-major through ds_read_b64_tr_b16, so no
-        // transposed copy of V and no separate V^T GEMM (RALD_ATTN_VROW=0: the two-GEMM form, for A/B runs)
-        static const bool vrow_env = RALD_PROBE_ENV("RALD_ATTN_VROW", 1) != 0;
-        const bool vrow = vrow_env && NL % 64 == 0;
+        // transposed copy of V and no separate V^T GEMM (NL % 64 != 0: the two-GEMM form)
+        const bool vrow = NL % 64 == 0;
         AttnArgs a1;
         if (vrow) {
             GemmArgs qkv = gemm_args(ws_h, D, l.w_qk, D, ws_qk, 3 * D, nullptr, M, 3 * D, D);

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
 #ifdef RALD_GN16               // A/B builds (tools/build_variant.sh): strips of 16 n-tiles (A panels fetched once at N = 4096)
     const int GN = 16;
 #else
-    const int GN = RALD_ABLATED(a.ablate, 128) ? 16 : 8;       // probe builds: bit 128 = strips of 16 n-tiles
+    const int GN = 8;
 #endif
     int tm, tn;
     if (ntn % GN == 0) {
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
 #ifndef RALD_KOFF            // off in the shipped build: see below (A/B builds: tools/build_variant.sh koff -DRALD_KOFF)
     const int koff = 0;
 #else
-    const int koff = (NSTAGE == 2 && !RALD_ABLATED(a.ablate, 2048)) ? (int)((unsigned)(tm + tn + bz) % (unsigned)nk_) : 0;
+    const int koff = NSTAGE == 2 ? (int)((unsigned)(tm + tn + bz) % (unsigned)nk_) : 0;
 #endif
     int64_t oa, ob, coff;
     gemm_batch_offsets(a, bz, oa, ob, coff);
@@ -301,19 +301,17 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         unsigned char* base = smem + buf * STAGE_BYTES;
         int ks = kt + koff;
         ks = ks >= nk_ ? ks - nk_ : ks;
-        // probe builds (timing only, wrong results): bits 4096 / 8192 drop the B / A pieces of every stage after the first two - is a k-step
-        // paced by the BYTES of its stage or by the latency of a stage, whatever its size?
-        // (the probe library's main loop is ~2 x slower than the shipped one - its run-time switches sit between the MFMAs - so the same question
-        // is asked of the shipped loop with compile-time variants: tools/build_variant.sh ska -DRALD_SKIP_A, skb -DRALD_SKIP_B, skab with both)
+        // A/B builds (timing only, wrong results): -DRALD_SKIP_A / -DRALD_SKIP_B drop the A / B pieces of every stage after the first two -
+        // is a k-step paced by the BYTES of its stage or by the latency of a stage, whatever its size?  (tools/build_variant.sh ska, skb, skab)
 #if defined(RALD_SKIP_A)
         const bool skip_a = kt >= 2;
 #else
-        const bool skip_a = RALD_ABLATED(a.ablate, 8192) && kt >= 2;
+        const bool skip_a = false;
 #endif
 #if defined(RALD_SKIP_B)
         const bool skip_b = kt >= 2;
 #else
-        const bool skip_b = RALD_ABLATED(a.ablate, 4096) && kt >= 2;
+        const bool skip_b = false;
 #endif
 #pragma unroll
         for (int p = 0; p < CA; ++p)
@@ -374,7 +372,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         constexpr int W_ALL = 0x0070;                                                  // vmcnt(0) lgkmcnt(0), expcnt untouched
         constexpr int W_ST1 = ((CA + CB) & 15) | (((CA + CB) >> 4) << 14) | 0x0f70;    // vmcnt(CA+CB): the older stage has landed
         stage(0, 0);
-        if (nk > 1 && !RALD_ABLATED(a.ablate, 1)) { stage(1, 1); __builtin_amdgcn_s_waitcnt(W_ST1); }
+        if (nk > 1) { stage(1, 1); __builtin_amdgcn_s_waitcnt(W_ST1); }
         else __builtin_amdgcn_s_waitcnt(W_ALL);
         __builtin_amdgcn_s_barrier();
         RALD_GSTAMP(1);
@@ -424,12 +422,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
             __builtin_amdgcn_s_waitcnt(W_ALL);                   // tile kt+1 landed; my reads of tile kt are done
             __builtin_amdgcn_s_barrier();
         };
-        if (RALD_ABLATED(a.ablate, 1)) {
-            for (int kt = 1; kt < nk; ++kt) body(kt, std::false_type{});
-        } else {
-            for (int kt = 1; kt + 1 < nk; ++kt) body(kt, std::true_type{});
-            if (nk > 1) body(nk - 1, std::false_type{});
-        }
+        for (int kt = 1; kt + 1 < nk; ++kt) body(kt, std::true_type{});
+        if (nk > 1) body(nk - 1, std::false_type{});
         mfma_all(fa1, fb1);                                      // sub-step 1 of the last tile
     } else {
 #pragma unroll
@@ -442,7 +436,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();          // everyone's pieces of tile kt are in LDS; buffer (kt-1)%NSTAGE is free
             asm volatile("" ::: "memory");
-            if (kt + NSTAGE - 1 < nk && !RALD_ABLATED(a.ablate, 1)) stage(kt + NSTAGE - 1, (kt + NSTAGE - 1) % NSTAGE);
+            if (kt + NSTAGE - 1 < nk) stage(kt + NSTAGE - 1, (kt + NSTAGE - 1) % NSTAGE);
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 bf16x8 fa[MT], fb[NT];
@@ -450,15 +444,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
                 mfma_all(fa, fb);
             }
         }
-    }
-    if (RALD_ABLATED(a.ablate, 2)) {          // probe builds: keep the accumulators live, store (almost) nothing
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) s += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if (s == 1234.5678f) reinterpret_cast<float*>(a.C)[0] = s;
-        return;
     }
     if constexpr (NSTAGE != 2) {              // (the 2-stage loop ends on a barrier behind its last fragment reads)
         asm volatile("" ::: "memory");
@@ -476,181 +461,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
     if (tid == 0 && lin == nt / 2) { g_gemm_clk[0] = clock64() - clk0; g_gemm_clk[1] = wall_clock64() - wall0; }
 #endif
 }
-
-#ifdef RALD_PROBE
-// =================================================================================================
-// Persistent form of the 256x256 engine for the GEGLU projection (FF1: the dominant kernel of an NFE).  PROBE builds only
-// (RALD_GEMM_PERSIST=1): measured on MI355X against the plain launch of the same tiles, interleaved in one process
-// (tools/ab_persist.py): FF1 alone 155.1 vs 151.6 us, whole NFE at B = 64 12.75 vs 12.60 ms, with the stagger 12.86 ms - the
-// hardware dispatcher already starts the next workgroup of a CU while the previous one drains its stores, and the tile loop
-// costs the double-buffered fragment registers of the plain kernel's main loop.  Kept as a measured dead end.
-// Round 3 rebuilt it on the rotated main loop WITH the double-buffered fragments (scalar base + 32-bit lane offsets for the DMA sources,
-// one code path for the last tile, bias through LDS-DMA; clean k-loop, 52 spilled registers at the tile boundaries): correct, and 7 % SLOWER
-// per NFE (FF1 143 -> ~176 us at B = 64).  The reason is structural: vmcnt is per wave and in order, so the next tile's second hand-over
-// (its stage 2 was issued behind the epilogue's stores) waits for this wave's own stores - and those are part of a chip-wide burst
-// (16.8 MB per round of tiles, all CUs at once) that takes ~4 us to drain.  In the plain launch the next workgroup's waves start with
-// empty counters and never wait for the previous workgroup's stores.  A persistent GEMM with an HBM-write-through epilogue pays its own
-// store latency; the plain launch does not.
-// =================================================================================================
-// One workgroup per CU walks its tiles (virtual block id v = blockIdx.x + j * gridDim.x through the same XCD-aware strip order
-// as above: v % 8 == blockIdx.x % 8, so a workgroup's tiles stay on its XCD's L2).  What the plain launch cannot do:
-//   * the k-loop runs on ACROSS tile boundaries: the first two k-steps of the next tile are issued (LDS-DMA) during the last
-//     two k-steps of the current one and land under its epilogue, so a tile starts with its operands in LDS instead of one
-//     exposed HBM/L2 latency + a workgroup launch;
-//   * the epilogue's transpose patches live in their own 18 KiB of LDS (GEGLU rows are 128 B: 16 x 144 B per wave), so the
-//     two staging buffers stay untouched while the epilogue runs;
-//   * its 8 output stores per wave stay in flight behind counted waits (vmcnt counts stores too): the next tile's first two
-//     hand-overs wait for "all but the youngest 16 / 8" operations, i.e. for their DMA pieces only;
-//   * STAGGER: the workgroups with an odd slot on their XCD start half a tile late, so that from then on half of the CUs
-//     are in their HBM-heavy epilogue while the other half are in the MFMA loop (in a plain launch all 256 CUs run the same
-//     phase at the same time; two independent streams gained 5-7 % from the same effect).
-template <bool STAGGER>
-__global__ __launch_bounds__(512) void gemm_geglu_persist_kernel(GemmArgs a, int ntn, int ntm) {
-    constexpr int BM = 256, BN = 256, BK = 64, WM = 4, WN = 2, WAVES = 8;
-    constexpr int MT = BM / (16 * WM), NT = BN / (16 * WN);
-    constexpr int CA = BM / 8 / WAVES, CB = BN / 8 / WAVES;          // 4 + 4 DMA pieces per wave and stage
-    constexpr int STAGE_BYTES = (BM + BN) * BK * 2;                  // 64 KiB
-    constexpr int PATCH = 16 * (NT * 8 * 2 + 16);                    // 2304 B: one 16-row m-tile of GEGLU output per wave
-    constexpr int NSTORE = MT * 2;                                   // output store instructions per wave and tile (8 rows each)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][A tile | B tile] | 8 patches | [2 tiles][8 waves] 512 B of bias
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int nt = ntn * ntm;
-    const int nk = a.K / BK;
-    const int lr = lane >> 3;
-    const int lc = (lane & 7) ^ lr;
-    const int fr = lane & 15, fq = lane >> 4;
-    constexpr int GN = 8;
-    auto tile_origin = [&](int v, int& m0, int& n0) {
-        const int xcd = v & 7, q = nt >> 3, rr = nt & 7;
-        const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (v >> 3);
-        int tm, tn;
-        if (ntn % GN == 0) {
-            const int strip = tile / (ntm * GN), within = tile % (ntm * GN);
-            tm = within / GN;
-            tn = strip * GN + within % GN;
-        } else {
-            tm = tile / ntn;
-            tn = tile % ntn;
-        }
-        m0 = tm * BM; n0 = tn * BN;
-    };
-    // one DMA stage: k-step kt of the tile at (m0, n0) into buffer buf.  Full tiles only (host contract: M, N multiples of 256), so
-    // the per-lane part of every source address is a 32-bit element offset fixed for the whole launch (8 VGPRs) and the tile /
-    // k-step part is scalar - the register file has no room for eight 64-bit pointers next to 128 accumulators and 96 fragment
-    // registers (a first version spilled 99 VGPRs to scratch and ran at half the speed of the plain launch).
-    unsigned offA[CA], offB[CB];
-#pragma unroll
-    for (int p = 0; p < CA; ++p) offA[p] = (unsigned)((8 * (wave + WAVES * p) + lr) * (int)a.lda + lc * 8);
-#pragma unroll
-    for (int p = 0; p < CB; ++p) offB[p] = (unsigned)((8 * (wave + WAVES * p) + lr) * (int)a.ldb + lc * 8);
-    auto stage = [&](int m0, int n0, int kt, int buf) {
-        unsigned char* base = smem + buf * STAGE_BYTES;
-        const bf16* sa = a.A + (int64_t)m0 * a.lda + kt * BK;       // scalar
-        const bf16* sb = a.B + (int64_t)n0 * a.ldb + kt * BK;
-#pragma unroll
-        for (int p = 0; p < CA; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(sa + offA[p]), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int p = 0; p < CB; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(sb + offB[p]), (lds_void*)(base + BM * 128 + (wave + WAVES * p) * 1024), 16, 0, 0);
-    };
-    // the wave's 128 bias values of the tile at n0 -> its LDS slot of parity `par` (two 256-byte DMA pieces, 4 bytes per lane)
-    float* const s_bias = reinterpret_cast<float*>(smem + 2 * STAGE_BYTES + WAVES * PATCH);
-    auto stage_bias = [&](int n0, int par) {
-        const float* src = a.bias + n0 + wn * (BN / WN) + lane;
-        float* dst = s_bias + (par * WAVES + wave) * 128;
-        __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 4, 0, 0);
-        __builtin_amdgcn_global_load_lds((glb_void*)(src + 64), (lds_void*)(dst + 64), 4, 0, 0);
-    };
-    int v = blockIdx.x;
-    if (v >= nt) return;
-    if (STAGGER && ((blockIdx.x >> 3) & 1)) {
-        // about half a tile of head start for the even slots: a tile is ~5 000 clocks per k-step, s_sleep 127 = 8 128 clocks
-        for (int i = 0; i < (5 * nk + 8) / 16; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-    int m0, n0;
-    tile_origin(v, m0, n0);
-    stage_bias(n0, 0);
-    stage(m0, n0, 0, 0);
-    if (nk > 1) stage(m0, n0, 1, 1);
-    bool first = true;
-    int par = 0;
-    for (;;) {
-        const int vn = v + gridDim.x;
-        int m1 = 0, n1 = 0;
-        const bool more = vn < nt;
-        if (more) tile_origin(vn, m1, n1);
-        f32x4 acc[MT][NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // k-step 0 of this tile (and its bias) must have landed.  Outstanding, oldest first: [bias][stage 0] [stage 1] [the previous
-        // tile's NSTORE stores]
-        if (first) { if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA + CB) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA + CB + NSTORE) : "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        for (int kt = 0; kt < nk; ++kt) {
-            const int cur = kt & 1;
-            // one 32-deep sub-step: the 4 A fragments at once, the B fragments one n-tile ahead of their 4 MFMAs (24 fragment
-            // registers instead of the 96 of the plain kernel's double-buffered sets: the tile loop needs the difference)
-            auto substep = [&](int kk) {
-                const bf16x8* sA = reinterpret_cast<const bf16x8*>(smem + cur * STAGE_BYTES);
-                const bf16x8* sB = sA + BM * 8;
-                const int chunk = kk * 4 + fq;
-                bf16x8 fa[MT];
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    const int r = wm * (BM / WM) + i * 16 + fr;
-                    fa[i] = sA[r * 8 + (chunk ^ (r & 7))];
-                }
-                const int rb0 = wn * (BN / WN) + fr;
-                bf16x8 fb = sB[rb0 * 8 + (chunk ^ (rb0 & 7))];
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    bf16x8 fbn = fb;
-                    if (j + 1 < NT) {
-                        const int r = rb0 + (j + 1) * 16;
-                        fbn = sB[r * 8 + (chunk ^ (r & 7))];
-                    }
-#pragma unroll
-                    for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb, fa[i], acc[i][j], 0, 0, 0);
-                    fb = fbn;
-                }
-            };
-            substep(0);
-            substep(1);
-            if (kt + 1 < nk) {
-                // k-step kt+1 landed; my reads of buffer `cur` are done.  After the first hand-over of a tile the stores of the
-                // previous tile may still be in flight BEHIND the stage waited for (kt == 0: [stage 1][stores]); later the
-                // only younger operations are DMA pieces issued after them, so everything is waited for.
-                if (kt == 0 && !first) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NSTORE) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                if (kt + 2 < nk) stage(m0, n0, kt + 2, cur);
-                else if (more) { stage_bias(n1, par ^ 1); stage(m1, n1, kt + 2 - nk, cur); }     // the next tile's bias and k-step 0 (nk even: buffer 0)
-            }
-        }
-        // every wave is done reading the last buffer (nk - 1) & 1 = 1: the next tile's k-step 1 goes there
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (more && nk > 1) stage(m1, n1, 1, 1);
-        gemm_epilogue_lds<MT, NT, EPI_GEGLU>(acc, a, m0 + wm * (BM / WM), n0 + wn * (BN / WN), 0, lane, smem + 2 * STAGE_BYTES + wave * PATCH,
-                                             s_bias + (par * WAVES + wave) * 128);
-        if (!more) break;
-        v = vn; m0 = m1; n0 = n1;
-        first = false;
-        par ^= 1;
-    }
-}
-
-#endif  // RALD_PROBE
 
 // -------------------------------------------------------------------------------------------------
 template <int BM, int BN>
@@ -700,33 +510,6 @@ static int launch_glds(const GemmArgs& a, int epi, hipStream_t st) {
     }
 }
 
-#ifdef RALD_PROBE
-static int launch_geglu_persist(const GemmArgs& a, hipStream_t st) {
-    constexpr int smem = 2 * (256 + 256) * 64 * 2 + 8 * 2304 + 2 * 8 * 512;
-    static int n_cu = 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        RALD_HIP(hipFuncSetAttribute((const void*)gemm_geglu_persist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        RALD_HIP(hipFuncSetAttribute((const void*)gemm_geglu_persist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        RALD_HIP(hipGetDevice(&dev));
-        RALD_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount;
-        attr_set = true;
-    }
-    const int ntn = a.N / 256, ntm = a.M / 256;
-    int grid = n_cu - n_cu % 8;                               // a multiple of 8: a workgroup's tiles share its XCD (speed only)
-    if (grid > ntn * ntm) grid = ntn * ntm;
-    if (grid < 8) grid = ntn * ntm < 8 ? ntn * ntm : 8;
-    const bool stagger = RALD_PROBE_ENV("RALD_GEMM_STAGGER", 1) != 0;
-    if (stagger) hipLaunchKernelGGL(gemm_geglu_persist_kernel<true>, dim3(grid), dim3(512), smem, st, a, ntn, ntm);
-    else hipLaunchKernelGGL(gemm_geglu_persist_kernel<false>, dim3(grid), dim3(512), smem, st, a, ntn, ntm);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-#endif
-
 int f16_saturation_gemm(unsigned* count, bool reset) {
     RALD_HIP(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_f16_sat_gemm), sizeof(unsigned)));
     if (reset) { const unsigned z = 0; RALD_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_f16_sat_gemm), &z, sizeof(unsigned))); }
@@ -735,21 +518,11 @@ int f16_saturation_gemm(unsigned* count, bool reset) {
 
 // Host-side shape contract is checked here, before any launch (an out-of-bounds MFMA tile
 // can take the whole node down, so nothing is left to the kernel).
-static int gemm_nt_impl(const GemmArgs& a, int epi, hipStream_t st);
 int gemm_nt(const GemmArgs& a0, int epi, hipStream_t st) {
     // bf16 outputs are streamed (written once, read by the next kernel after the whole tensor has
     // passed through): non-temporal stores keep them from evicting the weight panels out of L2.
-    static const int nt_store = RALD_PROBE_ENV("RALD_NT_STORE", 1);
     GemmArgs a = a0;
-    if (nt_store) a.ablate |= 64;
-    static const int st_flavour = RALD_PROBE_ENV("RALD_GEMM_STORE", 0);     // probe builds: 1 = sc0 sc1 (no nt), 2 = sc1
-    if (st_flavour == 1) a.ablate |= 512;
-    if (st_flavour == 2) a.ablate |= 1024;
-    static const int diag = RALD_PROBE_ENV("RALD_GEMM_ABLATE", 0);   // probe builds (PMC runs): OR-ed into GemmArgs::ablate
-    a.ablate |= diag;
-    return gemm_nt_impl(a, epi, st);
-}
-static int gemm_nt_impl(const GemmArgs& a, int epi, hipStream_t st) {
+    a.flags |= GEMM_NT_STORE;
     RALD_CHECK(a.M > 0 && a.N > 0 && a.K > 0 && a.batch > 0 && a.batch2 > 0, "gemm: empty problem");
     const int64_t nbatch = (int64_t)a.batch * a.batch2;
     RALD_CHECK(nbatch <= 65535, "gemm: batch * batch2 exceeds the grid z limit");
@@ -783,50 +556,24 @@ static int gemm_nt_impl(const GemmArgs& a, int epi, hipStream_t st) {
                    (int64_t)(a.M / 256) * (a.N / 256) >= 256, "gemm: the MXFP8 output form needs the GEGLU epilogue on full 256x256 tiles");
         return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
     }
-    // engine selection.  Default (-1): LDS-DMA 256x256 tiles (8 waves) when they give every CU at
-    // least one tile, LDS-DMA 128x128 (4 waves, 2 workgroups/CU) otherwise, register-staged 64x64 for
-    // the small-M (batch-1) regime.  RALD_GEMM_IMPL forces a variant for A/B microbenchmarks:
-    // 0 register-staged 128x128, 1 LDS-DMA 128x128 2 stages, 2 ... 3 stages, 3 LDS-DMA 256x128 2 stages,
-    // 4 256x128 3 stages, 5 256x256 2 stages.
-    int impl = -1;
-    impl = RALD_PROBE_ENV("RALD_GEMM_IMPL", -1);
+    // engine selection: register-staged 64x64 tiles or the 64x64 LDS-DMA ring for the small-M (batch-1) regime, LDS-DMA 256x256 tiles
+    // (8 waves) when they give every CU at least one tile, LDS-DMA 64x128 (3 stages) for 192-320 tiles of 128x128, LDS-DMA 128x128
+    // (4 waves, 2 workgroups/CU) otherwise.
     const int64_t wg128 = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 128) * nbatch;
-    if (wg128 < RALD_PROBE_ENV("RALD_GEMM_SMALL_MAX", 192)) {
+    if (wg128 < 192) {
         // small-M (batch-1) regime: too few tiles to hide memory latency behind other workgroups, so put
         // (up to) the whole K extent in flight at once: 64x64 tiles, 8-stage LDS-DMA ring (128 KB).
         const int64_t wg64 = (int64_t)cdiv(a.M, 64) * cdiv(a.N, 64) * nbatch;
-        static const int mid = RALD_PROBE_ENV("RALD_GEMM_MID", 0);   // A/B: 1 = LDS-DMA 128x128 from 96 tiles up, 2 = LDS-DMA 64x64 ring always
-        if (mid == 1 && wg128 >= 96) return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
-        if (mid == 2) return launch_glds<64, 64, 2, 2, 8>(a, epi, st);
-        if (impl == 0 || wg64 > 256) return launch_tile<64, 64>(a, epi, st);   // more than one tile per CU: 5 small workgroups/CU hide latency
+        if (wg64 > 256) return launch_tile<64, 64>(a, epi, st);   // more than one tile per CU: 5 small workgroups/CU hide latency
         return launch_glds<64, 64, 2, 2, 8>(a, epi, st);
     }
-    if (impl < 0) {
-        const int64_t wg256 = (int64_t)(a.M / 256) * (a.N / 256) * nbatch;
-#ifdef RALD_PROBE
-        // probe builds, RALD_GEMM_PERSIST=1: the persistent engine (one workgroup per CU) for GEGLU projections of >= 2 rounds of tiles
-        if (epi == EPI_GEGLU && nbatch == 1 && a.M % 256 == 0 && a.N % 256 == 0 && wg256 >= 512 && a.K % 128 == 0 && !a.out8 &&
-            RALD_PROBE_ENV("RALD_GEMM_PERSIST", 0) != 0)
-            return launch_geglu_persist(a, st);
-#endif
-        if (a.M % 256 == 0 && a.N % 256 == 0 && wg256 >= 256) return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
-        // 192-320 tiles of 128 x 128 = about one 4-wave workgroup per CU, walking its k-steps as a latency chain (N = 512 projections at
-        // M = 8192: 19-21 us for 4.3 GFLOP).  64 x 128 tiles with 3 stages give two workgroups per CU and a deeper prefetch: NFE at
-        // B = 16 4.63 -> 4.36 ms, B = 8 2.94 -> 2.90 ms (RALD_GEMM_64x128=0 in probe builds: the old choice).
-        if (epi != EPI_SOFTMAX64 && epi != EPI_GEGLU && wg128 <= RALD_PROBE_ENV("RALD_GEMM_64x128_MAX", 320) && a.M % 64 == 0 && RALD_PROBE_ENV("RALD_GEMM_64x128", 1)) return launch_glds<64, 128, 2, 2, 3>(a, epi, st);
-        return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
-    }
-    switch (impl) {
-        case 0: return launch_tile<128, 128>(a, epi, st);
-        case 2: return launch_glds<128, 128, 2, 2, 3>(a, epi, st);
-        case 3: if (a.M % 256 == 0 && wg128 >= 512) return launch_glds<256, 128, 4, 2, 2>(a, epi, st);
-                return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
-        case 4: if (a.M % 256 == 0 && wg128 >= 512) return launch_glds<256, 128, 4, 2, 3>(a, epi, st);
-                return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
-        case 5: if (a.M % 256 == 0 && a.N % 256 == 0 && wg128 >= 1024) return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
-                return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
-        default: return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
-    }
+    const int64_t wg256 = (int64_t)(a.M / 256) * (a.N / 256) * nbatch;
+    if (a.M % 256 == 0 && a.N % 256 == 0 && wg256 >= 256) return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
+    // 192-320 tiles of 128 x 128 = about one 4-wave workgroup per CU, walking its k-steps as a latency chain (N = 512 projections at
+    // M = 8192: 19-21 us for 4.3 GFLOP).  64 x 128 tiles with 3 stages give two workgroups per CU and a deeper prefetch: NFE at
+    // B = 16 4.63 -> 4.36 ms, B = 8 2.94 -> 2.90 ms against 128 x 128 tiles.
+    if (epi != EPI_GEGLU && wg128 <= 320 && a.M % 64 == 0) return launch_glds<64, 128, 2, 2, 3>(a, epi, st);
+    return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
 }
 
 }  // namespace rald

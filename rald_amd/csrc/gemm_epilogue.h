@@ -121,7 +121,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(f32x4 (&acc)[MT][NT], const Ge
                     continue;
                 }
             }
-            if (m < a.M && c < ncols && !RALD_ABLATED(a.ablate, 16)) {      // 16: probe builds, no global stores
+            if (m < a.M && c < ncols) {
                 if constexpr (EPI == EPI_RESID) {
                     float* C = reinterpret_cast<float*>(a.C) + coff + (int64_t)m * a.ldc + c;
                     float4 x = *reinterpret_cast<float4*>(C);
@@ -140,12 +140,11 @@ __device__ __forceinline__ void gemm_epilogue_lds(f32x4 (&acc)[MT][NT], const Ge
                         // lines displace the weight / activation panels: FETCH_SIZE of the FF1 GEMM in situ 193 MB per launch
                         // against 80 MB with this policy (= with no stores at all; profiles/traffic.json)
                         const u32x4 vv = u32x4{v.x, v.y, v.z, v.w};
-                        if (RALD_ABLATED(a.ablate, 512)) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(C), "v"(vv) : "memory");     // probe: write-through without the nt hint
-                        else if (RALD_ABLATED(a.ablate, 1024)) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(C), "v"(vv) : "memory");   // probe: sc1 only
 #ifdef RALD_STORE_SC01        // A/B builds (tools/build_variant.sh): write-through without the nt hint
-                        else if (a.ablate & 64) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(C), "v"(vv) : "memory");
+                        if (a.flags & GEMM_NT_STORE) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(C), "v"(vv) : "memory");
+#else
+                        if (a.flags & GEMM_NT_STORE) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(C), "v"(vv) : "memory");
 #endif
-                        else if (a.ablate & 64) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(C), "v"(vv) : "memory");
                         else *reinterpret_cast<uint4*>(C) = v;
                     } else *reinterpret_cast<uint2*>(C) = make_uint2(v.x, v.y);   // N % 8 == 4 tail
                 }

@@ -205,7 +205,7 @@ int gemm_mx8(const Mx8Args& a0, int epi, hipStream_t st) {
     if (epi == EPI_GEGLU) RALD_CHECK(g.N % 128 == 0 && g.bias != nullptr && g.ldc % 4 == 0 && g.ldc >= g.N / 2, "gemm_mx8: GEGLU needs N % 128 == 0, a packed bias and ldc >= N/2");
     else RALD_CHECK(g.ldc % 4 == 0 && g.ldc >= g.N, "gemm_mx8: ldc must be >= N and a multiple of 4");
     RALD_CHECK((int64_t)g.M * (g.K / 32) < ((int64_t)1 << 31) && (int64_t)g.N * (g.K / 32) < ((int64_t)1 << 31), "gemm_mx8: scale index overflow");
-    a.g.ablate = 64;                           // streamed (non-temporal) bf16 output, as in gemm_nt
+    a.g.flags = GEMM_NT_STORE;                 // streamed (non-temporal) bf16 output, as in gemm_nt
     if (g.out8) RALD_CHECK(epi == EPI_GEGLU && g.outs && g.batch == 1 && g.M % 256 == 0 && g.N % 256 == 0 && (int64_t)(g.M / 256) * (g.N / 256) >= 256,
                            "gemm_mx8: the MXFP8 output form needs the GEGLU epilogue on full 256x256 tiles");
     const int64_t wg256 = (int64_t)(g.M / 256) * (g.N / 256) * g.batch;

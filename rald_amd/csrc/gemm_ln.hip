@@ -31,7 +31,7 @@ __device__ long long g_ln_stamps[1024][4];
 
 // ---- epilogue shared by the main-loop forms: acc (+ x_old already inside unless XEPI) -> x_new, h ---------------------------------
 template <int BM, int WM, int WN, bool XEPI>
-__device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&acc)[BM / (16 * WM)][512 / (16 * WN)], unsigned char* smem, int lds_bytes, int m0) {
+__device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&acc)[BM / (16 * WM)][512 / (16 * WN)], unsigned char* smem, int m0) {
     constexpr int BN = 512;
     constexpr int WAVES = WM * WN;
     constexpr int MT = BM / (16 * WM);
@@ -40,7 +40,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
     constexpr int PATCH = 16 * STRIDE_F;
     constexpr int RED_OFF = WAVES * PATCH;                            // float2 red[BM][WN]
-    (void)lds_bytes; (void)ROWB_H;
+    (void)ROWB_H;
     typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -48,7 +48,6 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     const int wm = wave / WN, wn = wave % WN;
     const int fr = lane & 15, fq = lane >> 4;
     const bool nt_io = (a.nt_io & 1) != 0;
-    const bool skip_x = RALD_ABLATED(a.nt_io, 2), skip_h = RALD_ABLATED(a.nt_io, 4);   // probe builds, RALD_NT_STORE bits 1 / 2: timing ablations
     // ---- 1. v = acc + bias + x_old (accumulator layout), row partial sums -------------------------
     const int mb = m0 + wm * (BM / WM);
     const int nb = wn * (BN / WN);
@@ -117,7 +116,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
                 const int r = r0 + lane / LPR, pc = lane % LPR;
                 const int m = mb + i * 16 + r;
                 const uint4 v = *reinterpret_cast<const uint4*>(patch + r * STRIDE_F + pc * 16);
-                if (m < a.M && !skip_x) {
+                if (m < a.M) {
                     typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
                     if (nt_io) __builtin_nontemporal_store(nt_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_u32x4*>(a.x + (int64_t)m * BN + nb + pc * 4));
                     else *reinterpret_cast<uint4*>(a.x + (int64_t)m * BN + nb + pc * 4) = v;
@@ -161,7 +160,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
                         *reinterpret_cast<uint2*>(a.h8 + mc * BN + col) = *reinterpret_cast<const uint2*>(q8);
                         if ((pc & 3) == 0) a.hs[mc * (BN / 32) + col / 32] = sc;
                     }
-                } else if (mm < a.M && !skip_h) {
+                } else if (mm < a.M) {
                     typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
                     if (nt_io) __builtin_nontemporal_store(nt_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_u32x4*>(a.h + (int64_t)mm * BN + nb + pc * 8));
                     else *reinterpret_cast<uint4*>(a.h + (int64_t)mm * BN + nb + pc * 8) = v;
@@ -171,24 +170,20 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     }
 }
 
-// BK = 64: LDS rows of 128 bytes, 8 chunks, chunk ^ (row & 7).  BK = 32 (bf16 only): rows of 64 bytes, 4 chunks, chunk ^ ((row >> 2) & 3) -
-// rows r, r+4, r+8, r+12 share a 256-byte bank row, so a ds_read_b128 lane group (16 rows at one logical chunk) touches all 16 slots of it.
-// With 64-row tiles the BK = 32 form needs 72 KiB of LDS: TWO workgroups per CU, so one streams its epilogue (196 KB of stores) while
-// the other runs its k-loop, and a k-step that waits for HBM leaves the MFMAs to the other workgroup.
-template <int BM, int WM, int WN, bool MX, int BK, bool XLOOP = true>
+// LDS rows of 128 bytes (64 bf16 or 128 e4m3 of one k-step), 8 chunks of 16 bytes, chunk ^ (row & 7).
+template <int BM, int WM, int WN, bool MX>
 __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
-    constexpr int BN = 512, NSTAGE = 2;
-    static_assert(BK == 64 || (BK == 32 && !MX), "k-step: 64, or 32 for bf16 operands");
+    constexpr int BN = 512, NSTAGE = 2, BK = 64;
     constexpr int WAVES = WM * WN;
     constexpr int MT = BM / (16 * WM);
     constexpr int NT = BN / (16 * WN);
-    constexpr int ROWB = MX ? 128 : BK * 2;                      // bytes per LDS row
+    constexpr int ROWB = 128;                                    // bytes per LDS row
     constexpr int CPR = ROWB / 16;                               // 16-byte chunks per row
     constexpr int RPP = 1024 / ROWB;                             // rows per DMA piece (one wave instruction = 1 KiB)
     constexpr int PA = BM / RPP, PB = BN / RPP;                  // pieces per stage
-    constexpr int CA = (PA + WAVES - 1) / WAVES;
+    constexpr int CA = PA / WAVES;
     constexpr int CB = PB / WAVES;
-    static_assert(CB >= 1 && PB % WAVES == 0 && MT >= 1 && NT >= 1 && (PA % WAVES == 0 || PA < WAVES), "tile/wave split");
+    static_assert(CA >= 1 && CB >= 1 && PA % WAVES == 0 && PB % WAVES == 0 && MT >= 1 && NT >= 1, "tile/wave split");
     constexpr int STAGE_BYTES = (BM + BN) * ROWB;
     constexpr int ROWB_F = NT * 16 * 4, STRIDE_F = ROWB_F + 16;      // fp32 patch row (x_new)
     constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
@@ -212,8 +207,8 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     }
     const int m0 = mtile * BM;
     const int lr = lane / CPR;                                    // row inside a DMA piece
-    const int lc = CPR == 8 ? ((lane & 7) ^ lr) : ((lane & 3) ^ ((lr >> 2) & 3));     // source chunk that lands in physical chunk lane % CPR
-    // operand rows per k-step: 128 bytes = 64 bf16 or 128 e4m3 (MX: e4m3 + e8m0 per 32, see gemm_fp8.hip); 64 bytes = 32 bf16
+    const int lc = (lane & 7) ^ lr;                               // source chunk that lands in physical chunk lane % CPR
+    // operand rows per k-step: 128 bytes = 64 bf16 or 128 e4m3 (MX: e4m3 + e8m0 per 32, see gemm_fp8.hip)
     constexpr int ESZ = MX ? 1 : 2;
     const unsigned char* A0 = MX ? a.A8 : reinterpret_cast<const unsigned char*>(a.A);
     const unsigned char* W0 = MX ? a.W8 : reinterpret_cast<const unsigned char*>(a.W + (int64_t)(m0 / a.w_rows) * a.strideW);
@@ -231,8 +226,7 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         unsigned char* base = smem + buf * STAGE_BYTES;
 #pragma unroll
         for (int p = 0; p < CA; ++p)
-            if (PA >= WAVES || wave < PA)                           // fewer A pieces than waves (64 rows x 64-byte rows): the first PA waves stage them
-                __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + kt * ROWB), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + kt * ROWB), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
 #pragma unroll
         for (int p = 0; p < CB; ++p)
             __builtin_amdgcn_global_load_lds((glb_void*)(gB[p] + kt * ROWB), (lds_void*)(base + BM * ROWB + (wave + WAVES * p) * 1024), 16, 0, 0);
@@ -357,12 +351,12 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int r = wm * (BM / WM) + i * 16 + fr;
-                fa[i] = sA[r * CPR + (chunk ^ (CPR == 8 ? (r & 7) : ((r >> 2) & 3)))];
+                fa[i] = sA[r * CPR + (chunk ^ (r & 7))];
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int r = wn * (BN / WN) + j * 16 + fr;
-                fb[j] = sB[r * CPR + (chunk ^ (CPR == 8 ? (r & 7) : ((r >> 2) & 3)))];
+                fb[j] = sB[r * CPR + (chunk ^ (r & 7))];
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -371,7 +365,7 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
         }
     };
-    if constexpr (XLOOP && BK == 64 && MT == 4 && NT == 8 && CA + CB == 10) {
+    if constexpr (MT == 4 && NT == 8 && CA + CB == 10) {
         // ---- pipelined main loop of the 128-row form (round 3) ----------------------------------------------------------------------
         // An iteration starts right AFTER a tile hand-over (barrier), so no LDS read is pending at the loop head and the compiler's
         // waits inside are exact counts.  Fragments: the A side (4 m-tiles) is double-buffered per 32-deep sub-step, the B side (8
@@ -407,7 +401,7 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
 #ifndef RALD_KOFF            // off in the shipped build: see below (A/B builds: tools/build_variant.sh koff -DRALD_KOFF)
         const int koff = 0;
 #else
-        const int koff = RALD_ABLATED(a.nt_io, 8) ? 0 : (int)((unsigned)(((mtile & 255) >> 3) + (mtile & 7)) % (unsigned)nk);
+        const int koff = (int)((unsigned)(((mtile & 255) >> 3) + (mtile & 7)) % (unsigned)nk);
 #endif
         auto ksrc = [&](int kt) { const int k = kt + koff; return k >= nk ? k - nk : k; };
         auto stage2 = [&](int kt, int buf) {
@@ -526,9 +520,7 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
 #endif
     } else {
     stage(0, 0);
-    if constexpr (!XLOOP) {                                           // two workgroups per CU: the other one covers this one's epilogue reads
-        for (int kt = 0; kt < nk; ++kt) kstep(kt, std::integral_constant<int, 9>{});
-    } else if (nk >= 9) {                                             // K >= 576: pieces over the first eight k-steps
+    if (nk >= 9) {                                             // K >= 576: pieces over the first eight k-steps
         kstep(0, std::integral_constant<int, 0>{}); kstep(1, std::integral_constant<int, 1>{});
         kstep(2, std::integral_constant<int, 2>{}); kstep(3, std::integral_constant<int, 3>{});
         kstep(4, std::integral_constant<int, 4>{}); kstep(5, std::integral_constant<int, 5>{});
@@ -555,177 +547,15 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     }
 
     }
-    constexpr bool PIPE = XLOOP && !MX && BK == 64 && MT == 4 && NT == 8 && CA + CB == 10;     // the pipelined loop adds x_old in the epilogue
-    resid_ln_epilogue<BM, WM, WN, (MX || !XLOOP || PIPE)>(a, acc, smem, NSTAGE * STAGE_BYTES, m0);
+    constexpr bool PIPE = !MX && MT == 4 && NT == 8 && CA + CB == 10;     // the pipelined loop adds x_old in the epilogue
+    resid_ln_epilogue<BM, WM, WN, (MX || PIPE)>(a, acc, smem, m0);
 #ifdef RALD_LN_STAMPS
     if (threadIdx.x == 0) g_ln_stamps[blockIdx.x & 1023][3] = wall_clock64();
 #endif
 }
 
-#ifdef RALD_PROBE
-// ---- MEASURED DEAD END, probe builds only (tools/ab_ln_ring.py): 128-row form with two operand rings (bf16) ---------------------------
-// Hypothesis: with one 80-KiB stage of A and W in flight (the kernel above) every k-step of a workgroup waits one HBM latency for the A
-// panel (2.4 us per k-step measured for 0.9 us of MFMA work at the datasheet rate).  Result at B = 64: 51 vs 44.5 us (K = 512), 100 vs 88 us
-// (K = 2048), NFE 12.10 vs 11.91 ms, same numbers out (x 1e-7, h 2e-5): with three A stages ahead the k-step takes just as long, so the
-// A latency is not what the loop waits for - it runs at the pace of its LDS traffic (276 KB per k-step and CU) plus the MFMAs at the clock
-// the chip sustains in such loops - and twice the barriers plus the up-front x_old read cost 6-12 us.
-// The two operands have their own rings in the same 160 KiB:
-//   A: 4 stages of 128 rows x 64 k (16 KiB each) - three stages (2.6 us of work) ahead of the MFMAs;
-//   W: 3 stages of 512 rows x 32 k (32 KiB each) - two 32-deep steps ahead (L2 latency);
-// one barrier per 32-deep step, counted vmcnt (the only vector-memory instructions inside the loop are the DMA pieces, issued in a fixed
-// order, so "all but the pieces of the previous step" is a compile-time count).  The residual x_old is loaded STRAIGHT INTO the accumulators
-// before the loop (its latency overlaps the first stages' DMA; no ordinary load sits beside the DMA stream inside the loop, which would make
-// hipcc wait vmcnt(0) there).
-template <int WM, int WN>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_resid_ln_ring_kernel(GemmLnArgs a) {
-    constexpr int BM = 128, BN = 512, WAVES = WM * WN;
-    static_assert(WAVES == 8, "8 waves");
-    constexpr int MT = BM / (16 * WM), NT = BN / (16 * WN);
-    constexpr int NA = 4, A_STAGE = BM * 128, NWS = 3, W_STAGE = BN * 64;
-    constexpr int W_OFF = NA * A_STAGE;
-    static_assert(W_OFF + NWS * W_STAGE == 160 * 1024, "the two rings fill the CU's LDS");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int m0 = blockIdx.x * BM;
-    const int fr = lane & 15, fq = lane >> 4;
-    // DMA sources.  A: pieces of 8 rows x 128 B (2 per wave and stage); W: pieces of 16 rows x 64 B (4 per wave and stage)
-    const unsigned char* gA[2];
-    {
-        const int lr = lane >> 3, lc = (lane & 7) ^ lr;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            int r = m0 + 8 * (wave + WAVES * p) + lr;
-            r = r < a.M ? r : a.M - 1;
-            gA[p] = reinterpret_cast<const unsigned char*>(a.A) + (int64_t)r * a.lda * 2 + lc * 16;
-        }
-    }
-    const unsigned char* gW0;
-    const int64_t w_piece = (int64_t)16 * WAVES * a.ldw * 2;               // bytes between this wave's pieces
-    {
-        const int lr = lane >> 2, lc = (lane & 3) ^ ((lr >> 2) & 3);
-        gW0 = reinterpret_cast<const unsigned char*>(a.W) + (int64_t)(16 * wave + lr) * a.ldw * 2 + lc * 16;
-    }
-    auto stage_a = [&](int ka) {
-        unsigned char* base = smem + (ka & (NA - 1)) * A_STAGE;
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + ka * 128), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
-    };
-    auto stage_w = [&](int t) {
-        unsigned char* base = smem + W_OFF + (t % NWS) * W_STAGE;
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(gW0 + p * w_piece + t * 64), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
-    };
-    const int nk64 = a.K / 64, nk32 = a.K / 32;
-    stage_a(0);
-    if (nk64 > 1) stage_a(1);
-    if (nk64 > 2) stage_a(2);
-    stage_w(0);
-    stage_w(1);                                                         // nk32 >= 2
-    // accumulators start as x_old
-    typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-    f32x4 acc[MT][NT];
-    {
-        const int mb = m0 + wm * (BM / WM), nb = wn * (BN / WN);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            int m = mb + i * 16 + fr;
-            m = m < a.M ? m : a.M - 1;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const nt_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f32x4*>(a.x + (int64_t)m * BN + nb + j * 16 + 4 * fq));
-                acc[i][j] = f32x4{v[0], v[1], v[2], v[3]};
-            }
-        }
-    }
-    auto compute = [&](int t) {
-        const unsigned char* sA = smem + ((t >> 1) & (NA - 1)) * A_STAGE;
-        const unsigned char* sW = smem + W_OFF + (t % NWS) * W_STAGE;
-        bf16x8 fa[MT], fb[NT];
-        const int chunk = (t & 1) * 4 + fq;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int r = wm * (BM / WM) + i * 16 + fr;
-            fa[i] = *reinterpret_cast<const bf16x8*>(sA + r * 128 + ((chunk ^ (r & 7)) << 4));
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int r = wn * (BN / WN) + j * 16 + fr;
-            fb[j] = *reinterpret_cast<const bf16x8*>(sW + r * 64 + ((fq ^ ((r >> 2) & 3)) << 4));
-        }
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-    };
-    auto issue = [&](int t) -> int {                                     // the loads issued during step t; returns their instruction count
-        int n = 0;
-        if (t + 2 < nk32) { stage_w(t + 2); n += 4; }
-        if ((t & 1) == 0 && (t >> 1) + 3 < nk64) { stage_a((t >> 1) + 3); n += 2; }
-        return n;
-    };
-    // step 0: everything issued so far (and x_old) has to be there
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    compute(0);                                                         // (hipcc waits vmcnt(0) for x_old before the first MFMA: nothing may be in flight yet)
-    int pend = issue(0);
-    for (int t = 1; t < nk32; ++t) {
-        // all but the pieces issued during step t-1 have landed: stage t of W (issued at step t-2) and its A stage (earlier still)
-        if (pend == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (pend == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (pend == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                                    // ... for every wave; the slots overwritten below were read in step t-1
-        asm volatile("" ::: "memory");
-        pend = issue(t);
-        compute(t);
-    }
-    asm volatile("" ::: "memory");
-    resid_ln_epilogue<BM, WM, WN, false>(a, acc, smem, 160 * 1024, m0);
-}
-
-static int launch_ln_ring(const GemmLnArgs& a, hipStream_t st) {
-    constexpr int smem = 160 * 1024;
-    static bool attr_set = false;
-    auto kern = gemm_resid_ln_ring_kernel<2, 4>;
-    if (!attr_set) {
-        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(cdiv(a.M, 128)), dim3(512), smem, st, a);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-#endif
-
 template <int BM, int WM, int WN, bool MX>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_resid_ln_kernel(GemmLnArgs a) { gemm_resid_ln_body<BM, WM, WN, MX, 64>(a); }
-#ifdef RALD_PROBE
-// MEASURED DEAD END, probe builds only (tools/ab_ln_pair.py): 64-row tiles, 32-deep k-steps, two workgroups per CU (4 waves per SIMD, 128
-// registers) so that one workgroup's epilogue streams while the other runs its k-loop.  Same results (x 1e-7, h 2e-5), but 67 vs 46 us at
-// K = 512 and 140 vs 88 us at K = 2048 (B = 64), NFE 13.87 vs 12.41 ms: a 64-row tile re-reads W once per 64 rows - 1 GB of L2 -> LDS
-// traffic per launch at K = 2048 (7.6 TB/s: the L2 is the bound) - and takes twice the barriers per FLOP.  The 128-row tile stays.
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_resid_ln_pair_kernel(GemmLnArgs a) {
-    gemm_resid_ln_body<64, 1, 8, false, 32, false>(a);
-}
-
-static int launch_ln_pair(const GemmLnArgs& a, hipStream_t st) {
-    constexpr int smem = 2 * (64 + 512) * 32 * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        RALD_HIP(hipFuncSetAttribute((const void*)gemm_resid_ln_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(gemm_resid_ln_pair_kernel, dim3(cdiv(a.M, 64)), dim3(512), smem, st, a);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-#endif
+__global__ __launch_bounds__(WM * WN * 64) void gemm_resid_ln_kernel(GemmLnArgs a) { gemm_resid_ln_body<BM, WM, WN, MX>(a); }
 
 template <int BM, int WM, int WN, bool MX>
 static int launch_ln(const GemmLnArgs& a, hipStream_t st) {
@@ -741,10 +571,7 @@ static int launch_ln(const GemmLnArgs& a, hipStream_t st) {
     return 0;
 }
 
-int gemm_resid_ln(const GemmLnArgs& a0, hipStream_t st) {
-    static const int nt_env = RALD_PROBE_ENV("RALD_NT_STORE", 1);
-    GemmLnArgs a = a0;
-    a.nt_io = nt_env;
+int gemm_resid_ln(const GemmLnArgs& a, hipStream_t st) {
     const bool mx = a.A8 != nullptr;                         // MXFP8 operands: A8/SA and W8/SW instead of A and W
     RALD_CHECK(a.M > 0 && a.K > 0 && a.K % (mx ? 128 : 64) == 0, "gemm_resid_ln: bad shape");
     RALD_CHECK(a.lda % 16 == 0 && a.ldw % 16 == 0 && a.lda >= a.K && a.ldw >= a.K, "gemm_resid_ln: leading dimensions");
@@ -756,12 +583,6 @@ int gemm_resid_ln(const GemmLnArgs& a0, hipStream_t st) {
     RALD_CHECK(!mx || (int64_t)a.M * (a.K / 32) < ((int64_t)1 << 31), "gemm_resid_ln: scale index overflow");
     RALD_CHECK(a.strideW == 0 || (!mx && a.w_rows % 128 == 0 && a.strideW % 8 == 0), "gemm_resid_ln: per-group weights need bf16 operands and groups of whole 128-row tiles");
     // 128-row tiles (all 160 KiB of LDS) when they cover the chip, 64-row tiles for smaller M
-#ifdef RALD_PROBE
-    if (!mx && RALD_PROBE_ENV("RALD_LN_PAIR", 0) && cdiv(a.M, 64) >= 384) return launch_ln_pair(a, st);
-#endif
-#ifdef RALD_PROBE
-    if (!mx && cdiv(a.M, 128) >= 192 && a.K >= 64 && RALD_PROBE_ENV("RALD_LN_RING", 0)) return launch_ln_ring(a, st);
-#endif
     if (cdiv(a.M, 128) >= 192) return mx ? launch_ln<128, 2, 4, true>(a, st) : launch_ln<128, 2, 4, false>(a, st);
     return mx ? launch_ln<64, 1, 8, true>(a, st) : launch_ln<64, 1, 8, false>(a, st);
 }

@@ -206,7 +206,6 @@ struct WgradLineArgs {
     int D, H, W, lw, lh, ld, Cin, Cout, lines, steps_per_split, nsteps;   // OUTPUT dims; lines = B*D*H; a step = 64 / W lines; lh / ld = log2(H), log2(D) or -1
     int tiles;                                                            // 64 x 64 blocks of the parameter
     float* slab; float* slab_b;                                           // slab form (see GemmTnArgs): slab[range][Cout][27][Cin], slab_b[range][Cout]
-    int ablate;                                                           // probe builds (RALD_WGRAD_ABLATE): 1 no MFMA, 2 no LDS reads, 4 no DMA after the first stage, 8 no atomics
 };
 
 // 8-row DMA pieces sit 1152 bytes apart (1024 + 128): rows 8 apart - the row blocks of neighbouring lane groups of one transposed read -
@@ -335,19 +334,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_line_kernel(WgradLineArgs a) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (s + NST - 1 < nst && !RALD_ABLATED(a.ablate, 4)) stage(s + NST - 1, buf >= 1 ? buf - 1 : NST - 1);          // (s + NST - 1) % NST
+        if (s + NST - 1 < nst) stage(s + NST - 1, buf >= 1 ? buf - 1 : NST - 1);          // (s + NST - 1) % NST
         const unsigned char* tS = smem + buf * STAGE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 fa[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = RALD_ABLATED(a.ablate, 2) ? ones : wl_read(tS, oa[ks][i][0], oa[ks][i][1]);
+            for (int i = 0; i < 2; ++i) fa[i] = wl_read(tS, oa[ks][i][0], oa[ks][i][1]);
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const bf16x8 fb = RALD_ABLATED(a.ablate, 2) ? ones : wl_read(tS, ob[ks][t][j][0], ob[ks][t][j][1]);
-                    if (RALD_ABLATED(a.ablate, 1)) { acc[t][0][j][0] += (float)fb[0] * (float)fa[0][1]; acc[t][1][j][1] += (float)fb[2] * (float)fa[1][3]; continue; }
+                    const bf16x8 fb = wl_read(tS, ob[ks][t][j][0], ob[ks][t][j][1]);
 #pragma unroll
                     for (int i = 0; i < 2; ++i) acc[t][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[t][i][j], 0, 0, 0);
                 }
@@ -360,7 +358,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_line_kernel(WgradLineArgs a) {
         buf = buf + 1 < NST ? buf + 1 : 0;
     }
     // acc[t][i][j][e] = dW[co0 + 32 wa + 16 i + 4 (lane >> 4) + e][ci0 + 32 wb + 16 j + (lane & 15)][tap (kd, kh, t)]
-    if (RALD_ABLATED(a.ablate, 8) && acc[0][0][0][0] != 12345.f) return;
     const int cl = lane & 15;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -417,13 +414,12 @@ static int tn_reduce(const float* slab, const float* slab_b, int ranges, int N1,
 }
 
 // row ranges of the generic kernel: a multiple of 8 (one per XCD), at least 256 rows (4 k-steps) per range.  Atomic form: ~1024 workgroups.
-// Slab form: one range per XCD once there are 32 tiles (measured at 4 096 rows, tools/bench_tn_target.py: 512 x 2048 39.8 -> 29.6 us,
+// Slab form: one range per XCD once there are 32 tiles (measured at 4 096 rows: 512 x 2048 39.8 -> 29.6 us,
 // 1536 x 512 34.5 -> 28.9 us against the atomic form's count; 4096 x 512 is 8 ranges either way) - every further range is another slab to
 // write and to sum.
 static void tn_ranges(int M, int N1, int N2, int& rows, int& used, int& launched, bool slab) {
     const int t1 = cdiv(N1, 128), t2 = cdiv(N2, 128);
-    int splits = cdiv(RALD_PROBE_ENV("RALD_TN_TARGET", 1024), t1 * t2);
-    if (slab && RALD_PROBE_ENV("RALD_TN_TARGET", 0) == 0) splits = t1 * t2 >= 32 ? 8 : (int)round_up(cdiv(256, t1 * t2), 8);
+    int splits = !slab ? cdiv(1024, t1 * t2) : t1 * t2 >= 32 ? 8 : (int)round_up(cdiv(256, t1 * t2), 8);
     const int max_splits = cdiv(M, 256);
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
@@ -479,7 +475,7 @@ int gemm_tn(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, float* C, in
 // workspace (conv3d_wgrad_workspace_floats floats, or null): the voxel ranges leave their partial gradients there with plain stores and a
 // second launch adds them, in order, into dW / dbias - bit-reproducible, and 4-13 x faster below full resolution: the atomic form ends every
 // workgroup in 12 288 atomics whose 64 lanes hit 64 different cache lines (the parameter layout puts the 27 taps innermost), which at
-// 32 x 16 x 8 voxels was 93 % of the launch (928 -> 70 us without them, tools/bench_wgrad_levels.py).  null = the atomic form.
+// 32 x 16 x 8 voxels was 93 % of the launch (928 -> 70 us without them).  null = the atomic form.
 namespace {
 struct WgradPlan { bool line; int splits, used, steps_per_split, nsteps, tiles, lw, lh, ld; };
 int lg2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
@@ -498,7 +494,6 @@ WgradPlan wgrad_plan(int B, int ID, int IH, int IW, int Cin, int Cout, int strid
         // 64 x 64 x 3 block of partial sums per workgroup)
         int splits = 8;
         double best = -1.0;
-        const int forced = RALD_PROBE_ENV("RALD_WGRAD_SPLITS", 0);
         for (int r = 1; r <= 4; ++r) {
             int sp = 8 * ((512 * r) / (72 * p.tiles));
             if (sp < 8) sp = 8;
@@ -507,7 +502,6 @@ WgradPlan wgrad_plan(int B, int ID, int IH, int IW, int Cin, int Cout, int strid
             const double eff = (double)wgs / (double)(cdiv(wgs, 512) * 512);
             if (eff > best + 0.05) { best = eff; splits = sp; }
         }
-        if (forced > 0) splits = (int)round_up(forced, 8);
         p.steps_per_split = cdiv(p.nsteps, splits);
         p.used = cdiv(p.nsteps, p.steps_per_split);
         p.splits = (int)round_up(p.used, 8);                     // (ranges past the last step return at once)
@@ -549,7 +543,6 @@ int conv3d_wgrad_tn(const bf16* dy, const bf16* x, float* dW, float* dbias, int 
         w.steps_per_split = p.steps_per_split;
         w.tiles = p.tiles;
         w.slab = workspace; w.slab_b = workspace ? workspace + (int64_t)p.used * Cout * 27 * Cin : nullptr;
-        w.ablate = RALD_PROBE_ENV("RALD_WGRAD_ABLATE", 0);
         RALD_CHECK((int64_t)9 * p.tiles * p.splits < ((int64_t)1 << 31), "conv3d_wgrad_tn: grid too large");
         constexpr int LDS1 = 3 * 20 * WL_PIECE, LDS2 = 2 * 28 * WL_PIECE;
         static bool attr_set = false;

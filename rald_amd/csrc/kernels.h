@@ -8,6 +8,7 @@
 namespace rald {
 
 // ---------------------------------------------------------------- gemm.hip
+enum { GEMM_NT_STORE = 64 };  // GemmArgs::flags: streamed (system-scope, non-temporal) bf16 output stores of the LDS-DMA engines
 enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_RESID = 2, EPI_GEGLU = 3,
        EPI_SOFTMAX64 = 4,
        EPI_F16S = 5 };        // C_fp16 = 2^-6 (alpha*acc + bias), saturating: split-K slabs for reduce_resid_ln(part_f16) (norm.hip)   // C_bf16 = softmax over every aligned group of 64 output columns of alpha*acc, in exp2 units (folded cross-attention, dit.hip)
@@ -19,7 +20,7 @@ struct GemmArgs {
     int M, N, K, batch;
     float alpha;
     int alpha_ncols;                               // alpha applies to output columns n < alpha_ncols only (others use 1)
-    int ablate;                                    // bit 64: non-temporal output stores.  Probe builds only (RALD_ABLATED): 1 = no DMA in the loop, 2 = no epilogue, 16 = no stores
+    int flags;                                     // GEMM_NT_STORE or 0 (gemm_nt and the MXFP8 GEMM set it on every launch)
     // optional inner batch (attention heads): grid z = batch * batch2, blockIdx.z = b1 * batch2 + b2,
     // operand offset = b1 * stride + b2 * stride2
     int batch2 = 1;
@@ -48,7 +49,7 @@ inline GemmArgs gemm_args(const bf16* A, int64_t lda, const bf16* B, int64_t ldb
                           const float* bias, int M, int N, int K) {
     GemmArgs g;
     g.A = A; g.lda = lda; g.strideA = 0; g.B = B; g.ldb = ldb; g.strideB = 0;
-    g.C = C; g.ldc = ldc; g.strideC = 0; g.bias = bias; g.M = M; g.N = N; g.K = K; g.batch = 1; g.alpha = 1.f; g.alpha_ncols = 1 << 30; g.ablate = 0;
+    g.C = C; g.ldc = ldc; g.strideC = 0; g.bias = bias; g.M = M; g.N = N; g.K = K; g.batch = 1; g.alpha = 1.f; g.alpha_ncols = 1 << 30; g.flags = 0;
     return g;
 }
 
@@ -62,7 +63,7 @@ struct GemmLnArgs {
     bf16* h;                  // [M][512] bf16 out (skipped when h8 is set)
     unsigned char* h8 = nullptr;   // optional MXFP8 form of h instead: e4m3 [M][512] ...
     unsigned char* hs = nullptr;   // ... + e8m0 scales [M][16]
-    int nt_io = 1;                 // non-temporal residual / output traffic (RALD_NT_STORE=0 turns it off for A/B runs)
+    int nt_io = 1;                 // non-temporal residual / output traffic
     // MXFP8 operands instead of A / W when A8 is set: e4m3 [M][K], [512][K] + e8m0 scales [..][K/32]; lda/ldw in elements
     const unsigned char *A8 = nullptr, *SA = nullptr, *W8 = nullptr, *SW = nullptr;
     const float* g; const float* b; int64_t gstride; int rows_per_group; float add_one, eps;
@@ -263,10 +264,7 @@ int quantize_mx8(const void* in, int in_is_bf16, int64_t ld_in, unsigned char* q
 // small-M split-K residual GEMM + (optional) LayerNorm: see norm.hip.  splitk_for() = 0 when it does not pay.
 int resid_splitk_ln(const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, float* x, bf16* h, const float* g, const float* b,
                     int64_t gstride, int rows_per_group, float add_one, float eps, int M, int K, int splits, float* scratch, hipStream_t st);
-inline int splitk_max_rows() {                      // RALD_SPLITK_MAXM: A/B switch for the row count up to which split-K pays
-    static const int v = RALD_PROBE_ENV("RALD_SPLITK_MAXM", 4096);
-    return v;
-}
+constexpr int splitk_max_rows() { return 4096; }   // the row count up to which split-K pays
 inline int splitk_for(int M, int K) { return (K >= 2048 && M <= splitk_max_rows()) ? 4 : 0; }   // [M,512] outputs: few 128x128 tiles
 int layernorm_mod_mx8(const float* x, unsigned char* q, unsigned char* scales, int64_t rows, int D, const float* gam, const float* bet,
                       int64_t gstride, int rows_per_group, float add_one, float eps, hipStream_t st);

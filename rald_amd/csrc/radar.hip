@@ -882,25 +882,23 @@ __global__ __launch_bounds__(512) void conv3d_pplane_kernel(ConvArgs a, int lw, 
     }
 }
 
-// engine choice for one convolution (RALD_CONV_LINE=0 keeps the per-tap gather kernel everywhere: A/B switch)
+// engine choice for one convolution
 static void launch_conv(const ConvArgs& a, hipStream_t st) {
-    static const bool line = RALD_PROBE_ENV("RALD_CONV_LINE", 1) != 0;
     const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
     const dim3 grid(cdiv(a.Cout, 64), (unsigned)((M + 127) / 128));
     const bool pow2 = a.OW == 8 || a.OW == 16 || a.OW == 32;
-    if (line && a.stride == 1 && a.pad == 1 && pow2 && M % 128 == 0 && a.Cin % 64 == 0 && a.OD == a.ID && a.OH == a.IH && a.OW == a.IW) {
+    if (a.stride == 1 && a.pad == 1 && pow2 && M % 128 == 0 && a.Cin % 64 == 0 && a.OD == a.ID && a.OH == a.IH && a.OW == a.IW) {
         const int lw = a.OW == 8 ? 3 : a.OW == 16 ? 4 : 5;
-        static const bool plane = RALD_PROBE_ENV("RALD_CONV_PLANE", 1) != 0;
-        static const int pds = RALD_PROBE_ENV("RALD_CONV_PPLANE_DS", 8);      // planes per persistent workgroup (0 = the one-tile kernel)
+        constexpr int pds = 8;                                                // planes per persistent workgroup
         const int Lp = 256 >> lw;
-        if (plane && pds > 0 && a.Cin == 64 && a.Cout % 64 == 0 && lw >= 4 && a.OH % Lp == 0 && a.OD % pds == 0 && 3 * (Lp + 2) * (a.OW + 2) <= 1024 &&
+        if (a.Cin == 64 && a.Cout % 64 == 0 && lw >= 4 && a.OH % Lp == 0 && a.OD % pds == 0 && 3 * (Lp + 2) * (a.OW + 2) <= 1024 &&
             (int64_t)a.B * (a.OH / Lp) * (a.OD / pds) >= 256) {
             constexpr int LDSP = 1024 * 128 + 3 * 64 * 128;
             static bool attr_set = false;
             if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3d_pplane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSP); attr_set = true; }
             hipLaunchKernelGGL(conv3d_pplane_kernel, dim3(cdiv(a.Cout, 64), (unsigned)(a.B * (a.OH / Lp) * (a.OD / pds))), dim3(512), LDSP, st, a, lw, pds);
         } else
-        if (plane && a.Cin == 64 && a.Cout % 64 == 0 && lw >= 4 && a.OH % Lp == 0 && M % 256 == 0 && M / 256 >= 256 && 3 * (Lp + 2) * (a.OW + 2) <= 1024) {
+        if (a.Cin == 64 && a.Cout % 64 == 0 && lw >= 4 && a.OH % Lp == 0 && M % 256 == 0 && M / 256 >= 256 && 3 * (Lp + 2) * (a.OW + 2) <= 1024) {
             constexpr int LDSP = 1024 * 128 + 3 * 64 * 128;                  // the tile's input image staged once + one (kd, kh) pair of weights
             static bool attr_set = false;
             if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3d_plane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSP); attr_set = true; }
@@ -1183,8 +1181,7 @@ int RadarEncoder::Impl::ensure_ws(int nsub) {
 
 int RadarEncoder::Impl::gn(const float* x, const std::string& name, bf16* y, int B, int S, int C, bool swish, hipStream_t st) {
     RALD_CHECK(gn_blocks(S) <= gn_part_blocks, "radar encoder: GroupNorm partial buffer too small");
-    static const bool fuse = RALD_PROBE_ENV("RALD_GN_FUSE", 1) != 0;   // A/B switch
-    if (fuse && x == fused_src && B == fused_B && S == fused_S && C == fused_C) {
+    if (x == fused_src && B == fused_B && S == fused_S && C == fused_C) {
         // the convolution that produced x left per-tile partials: no statistics pass over x
         hipLaunchKernelGGL(gn_finish_kernel, dim3(B), dim3(1024), 0, st, cpart, stats, S / 128);
     } else {
@@ -1210,11 +1207,10 @@ int RadarEncoder::Impl::run_conv(const bf16* in, const std::string& name, const 
     const int64_t M = (int64_t)B * a.OD * a.OH * a.OW;
     const int So = a.OD * a.OH * a.OW;
     // few tiles x long K (the 512- and 64-voxel levels: 8-64 workgroups looping over 54-108 k-steps): split K over gridDim.z
-    static const bool split_ok = RALD_PROBE_ENV("RALD_CONV_SPLITK", 1) != 0;   // A/B switch
     const int64_t tiles = (int64_t)cdiv(cout, 64) * ((M + 127) / 128);
     const int nk = 27 * (cin / 64);
     const bool line_engine = stride == 1 && pad == 1 && (a.OW == 8 || a.OW == 16 || a.OW == 32) && M % 128 == 0;
-    if (split_ok && !line_engine && tiles <= 64 && nk >= 12 && cout % 4 == 0) {
+    if (!line_engine && tiles <= 64 && nk >= 12 && cout % 4 == 0) {
         int splits = (int)(256 / tiles);
         if (splits > 16) splits = 16;
         if (splits > nk / 3) splits = nk / 3;

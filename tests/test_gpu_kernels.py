@@ -170,7 +170,7 @@ def test_attention_key_split_equals_unsplit(H):
         assert rel_l2(out, base) < 4e-3, ks                         # P is rounded to bf16 against a different running max
 
 
-def test_attention_reference_max_moves_lazily(H, monkeypatch):
+def test_attention_reference_max_moves_lazily(H):
     """The running max only moves when a tile's scores exceed it by more than 2^8 (attention.hip, RALD_ATTN_LAZY).  Scores that
     climb tile after tile - by less than the threshold, by far more, and falling - must still give the exact softmax, in
     the kernel's own-scale path and in the prescaled-q path (q already times scale*log2 e, what the denoiser feeds it)."""
@@ -184,13 +184,11 @@ def test_attention_reference_max_moves_lazily(H, monkeypatch):
     v = torch.randn(B, nk, 64, generator=g)
     qb, kb, vb = q.cuda().bfloat16(), k.cuda().bfloat16(), v.cuda().bfloat16()
     vt = vb.transpose(1, 2).contiguous()
-    for prescaled, scale in ((0, 1.0), (1, math.log(2.0))):
-        monkeypatch.setenv("RALD_ATTN_PRESCALED", str(prescaled))
-        out = H.op_attention(qb, kb, vt, nk, heads, scale)
+    for prescaled, scale in ((False, 1.0), (True, math.log(2.0))):
+        out = H.op_attention(qb, kb, vt, nk, heads, scale, prescaled=prescaled)
         ref = _attn_ref(qb, kb, vb, heads, scale)
         assert torch.isfinite(out.float()).all()
         assert rel_l2(out, ref) < 6e-3, prescaled
-    monkeypatch.delenv("RALD_ATTN_PRESCALED")
     out = H.op_attention_vrow(qb, kb, vb, heads, 1.0)
     assert rel_l2(out, _attn_ref(qb, kb, vb, heads, 1.0)) < 6e-3
 

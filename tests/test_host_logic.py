@@ -1,5 +1,6 @@
 """CPU tests of the host logic: sharding, the world_size-2 gloo collectives, the C-ABI symbol
 table, the oracle/product separation, and loud failure without a GPU."""
+import glob
 import os
 import re
 import socket
@@ -208,13 +209,23 @@ def test_documented_import_swap_resolves():
 
 
 def test_shipped_library_reads_no_environment_variable():
-    """Every A/B and ablation switch lives in the PROBE build only (csrc/common.h): the shipped library must not even import
-    getenv, and must report build flags 0."""
+    """The library has no run-time A/B or ablation switches: it must not even import getenv, its sources must not name it,
+    and it must report build flags 0."""
     import subprocess
     from rald_amd import _lib
     und = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     assert "getenv" not in und
     assert _lib.lib().rald_build_flags() == 0
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "rald_amd", "csrc")
+    srcs = [os.path.join(csrc, "Makefile")] + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + \
+        glob.glob(os.path.join(root, "include", "*.h"))
+    assert srcs
+    for path in srcs:
+        with open(path) as f:
+            text = f.read()
+        for word in ("getenv", "RALD_PROBE", "RALD_ABLATED"):
+            assert word not in text, (path, word)
 
 
 def test_module_forward_checks_batch_sizes_before_touching_the_gpu():

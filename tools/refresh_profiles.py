@@ -1,4 +1,4 @@
-"""Copy the round's evidence from gpurun_out/ (tools/r3_final_a.sh, r3_final_b.sh) into profiles/ and rebuild the in-situ HBM traffic entries of
+"""Copy the round's evidence (the outputs of the final round-3 profiling scripts, last in tree 44dcc59) into profiles/ and rebuild the in-situ HBM traffic entries of
 profiles/traffic.json from the FETCH_SIZE / WRITE_SIZE passes (KB -> bytes; FETCH_SIZE doubled: the gfx950 correction of MI355X_MICROARCH.md's
 HBM section for wide loads; WRITE_SIZE exact; median per launch).  The three uses of gemm_resid_ln per block (to_out, folded cross-attention
 output, ff.net.2) are told apart by launch order.  usage: python tools/refresh_profiles.py [tag, default r03]"""
