@@ -374,7 +374,6 @@ int Ae::reserve_decode(int B) {
     }
     x_h = (bf16*)arena.alloc(b * M * d * 2, true);
     x_qk = (bf16*)arena.alloc(b * M * 3 * I * 2, true);       // q | k | v
-    x_vt = (bf16*)arena.alloc(b * I * M * 2, true);
     x_o = (bf16*)arena.alloc(b * M * I * 2, true);
     x_g = (bf16*)arena.alloc(b * M * 4 * d * 2, true);
     x_y = (float*)arena.alloc(b * M * 64 * 4 + b * 4 + 16, true);        // projection [B*M][64] + one |max| word per sample
@@ -404,54 +403,24 @@ int Ae::decode_latents(const float* z, int B, void* ctx, hipStream_t st) {
     const int M = cfg.num_latents, L = cfg.latent_dim, BM = B * M;
     const float scale = 1.0f / sqrtf((float)cfg.dim_head);
     RALD_TRY(small_k_linear(z, w_proj, b_proj, x_x, BM, L, d, st));                     // x = proj(z)  (:410)
-    const bool fuse_ok = d == 512;                              // the fused epilogue owns whole 512-wide rows
-    auto resid_ln = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* ng, const float* nb) -> int {
-        if (d == 512 && splitk_for(BM, K))
-            return resid_splitk_ln(A, lda, W, ldw, bias, x_x, x_h, ng, nb, 0, 1 << 30, 0.f, 1e-5f, BM, K, splitk_for(BM, K), x_part, st);
-        if (fuse_ok && gemm_resid_ln_pays(BM, K)) {
-            GemmLnArgs g;
-            g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = x_x; g.h = x_h;
-            g.g = ng; g.b = nb; g.gstride = 0; g.rows_per_group = 1 << 30; g.add_one = 0.f; g.eps = 1e-5f; g.M = BM; g.K = K;
-            return gemm_resid_ln(g, st);
-        }
-        GemmArgs o = gemm_args(A, lda, W, ldw, x_x, d, bias, BM, d, K);
-        RALD_TRY(gemm_nt(o, EPI_RESID, st));
-        return layernorm_mod(x_x, x_h, BM, d, ng, nb, 0, 1 << 30, 0.f, 1e-5f, st);
+    auto resid_ln = [&](const bf16* A, int64_t ld, const bf16* W, const float* bias, int K, const float* ng, const float* nb) {
+        return resid_gemm_ln(gemm_ln_args(A, ld, W, ld, bias, x_x, x_h, ng, nb, 0, 1 << 30, 0.f, BM, K), d, x_part, st);
     };
     RALD_TRY(layernorm_mod(x_x, x_h, BM, d, layers[0].ng, layers[0].nb, 0, 1 << 30, 0.f, 1e-5f, st));
     for (size_t li = 0; li < layers.size(); ++li) {
         const Layer& l = layers[li];
         // x = self_attn(x) + x   (:413); LN(x) is already in x_h (prologue / previous layer's FF2 epilogue)
         // q | k | v in one projection; V stays row-major and is transposed on the attention kernel's LDS read
-        AttnArgs a;
-        if (M % 64 == 0) {
-            GemmArgs qkv = gemm_args(x_h, d, l.w_qk, d, x_qk, 3 * I, nullptr, BM, 3 * I, d);
-            qkv.alpha = scale * 1.4426950408889634f; qkv.alpha_ncols = I;
-            RALD_TRY(gemm_nt(qkv, EPI_BF16, st));
-            a.Q = x_qk; a.ldq = 3 * I; a.strideQ = (int64_t)M * 3 * I;
-            a.K = x_qk + I; a.ldk = 3 * I; a.strideK = (int64_t)M * 3 * I;
-            a.Vt = nullptr; a.ldvt = 0; a.strideVt = 0;
-            a.V = x_qk + 2 * I; a.ldv = 3 * I; a.strideV = (int64_t)M * 3 * I;
-        } else {
-            GemmArgs qk = gemm_args(x_h, d, l.w_qk, d, x_qk, 2 * I, nullptr, BM, 2 * I, d);
-            qk.alpha = scale * 1.4426950408889634f; qk.alpha_ncols = I;
-            RALD_TRY(gemm_nt(qk, EPI_BF16, st));
-            GemmArgs vt = gemm_args(l.w_v, d, x_h, d, x_vt, M, nullptr, I, M, d);
-            vt.batch = B; vt.strideB = (int64_t)M * d; vt.strideC = (int64_t)I * M;
-            RALD_TRY(gemm_nt(vt, EPI_BF16, st));
-            a.Q = x_qk; a.ldq = 2 * I; a.strideQ = (int64_t)M * 2 * I;
-            a.K = x_qk + I; a.ldk = 2 * I; a.strideK = (int64_t)M * 2 * I;
-            a.Vt = x_vt; a.ldvt = M; a.strideVt = (int64_t)I * M;
-        }
-        if (d == 512 && M % 64 == 0 && small_m_fused(BM, M, cfg.heads, I, 64)) {
+        GemmArgs qkv = gemm_args(x_h, d, l.w_qk, d, x_qk, 3 * I, nullptr, BM, 3 * I, d);
+        qkv.alpha = scale * 1.4426950408889634f; qkv.alpha_ncols = I;
+        RALD_TRY(gemm_nt(qkv, EPI_BF16, st));
+        if (d == 512 && small_m_fused(BM, M, cfg.heads, I, 64)) {
             // small batches: attention + per-head slice of to_out in one kernel, partials summed with the residual + the FF's PreNorm
             RALD_TRY(attn_self_proj(x_qk, 3 * I, l.w_o, x_part, M, cfg.heads, B, st, true));
             RALD_TRY(reduce_resid_ln(x_part, cfg.heads, (int64_t)BM * d, l.b_o, x_x, x_h, BM, l.ff.ng, l.ff.nb, 0, 1 << 30, 0.f, 1e-5f, st, true));
         } else {
-        a.O = x_o; a.ldo = I; a.strideO = (int64_t)M * I;
-        a.nq = M; a.nk = M; a.k_rows = M; a.heads = cfg.heads; a.batch = B; a.scale = scale; a.q_prescaled = 1;
-        RALD_TRY(attention_d64(a, st));
-        RALD_TRY(resid_ln(x_o, I, l.w_o, I, l.b_o, I, l.ff.ng, l.ff.nb));             // + the FF's PreNorm
+            RALD_TRY(attention_d64(self_attn_args(x_qk, x_o, M, I, cfg.heads, B, scale), st));
+            RALD_TRY(resid_ln(x_o, I, l.w_o, l.b_o, I, l.ff.ng, l.ff.nb));                // + the FF's PreNorm
         }
         // x = self_ff(x) + x                                                            (:414)
         GemmArgs f1 = gemm_args(x_h, d, l.ff.w1, d, x_g, 4 * d, l.ff.b1, BM, 8 * d, d);
@@ -459,7 +428,7 @@ int Ae::decode_latents(const float* z, int B, void* ctx, hipStream_t st) {
         // FF2 + the next consumer's LayerNorm: next layer's attention PreNorm, or the decoder's norm_context
         const float* ng = (li + 1 < layers.size()) ? layers[li + 1].ng : dec.cg;
         const float* nb = (li + 1 < layers.size()) ? layers[li + 1].nb : dec.cb;
-        RALD_TRY(resid_ln(x_g, 4 * d, l.ff.w2, 4 * d, l.ff.b2, 4 * d, ng, nb));
+        RALD_TRY(resid_ln(x_g, 4 * d, l.ff.w2, l.ff.b2, 4 * d, ng, nb));
     }
     // decoder context (ae_decode.hip): LN_ctx(x) . t2aug -> per-latent score coefficients, h0, hb, u; one fp16 image per sample.
     // (x_h holds LN_ctx(x) in bf16 from the last epilogue; the context is projected from the fp32 residual stream instead.)

@@ -77,7 +77,7 @@ struct Dit {
         bf16* w_q2t = nullptr;                                // attn2.to_q transposed [k][h*64+d]: operand of the folded condition keys (cond_fold)
         float *b_o, *b_o2, *b_ff1, *b_ff2;
         // MXFP8 copies of the attention projections (cfg.qkv_dtype == 1): e4m3 elements [rows][D] + e8m0 scales [rows][D/32]
-        unsigned char *q8_qk = nullptr, *s8_qk = nullptr, *q8_v = nullptr, *s8_v = nullptr, *q8_q2 = nullptr, *s8_q2 = nullptr;
+        unsigned char *q8_qk = nullptr, *s8_qk = nullptr, *q8_q2 = nullptr, *s8_q2 = nullptr;
         unsigned char *q8_ff1 = nullptr, *s8_ff1 = nullptr;   // qkv_dtype >= 2: the GEGLU projection too (packed row order)
         unsigned char *q8_ff2 = nullptr, *s8_ff2 = nullptr;   // qkv_dtype == 3: and the feed-forward's output projection
     };
@@ -111,7 +111,7 @@ struct Dit {
     struct Work {
         float* x = nullptr;                 // residual stream [M][D] fp32
         float* part = nullptr;              // split-K partial sums of the small-batch FF2 (norm.hip resid_splitk_ln) / per-head slabs
-        bf16 *h = nullptr, *qk = nullptr, *vt = nullptr, *o = nullptr, *q2 = nullptr, *g = nullptr;
+        bf16 *h = nullptr, *qk = nullptr, *o = nullptr, *q2 = nullptr, *g = nullptr;
         unsigned char *h8 = nullptr, *hs = nullptr;   // MXFP8 AdaLN outputs feeding q/k/v (qkv_dtype >= 1)
         unsigned char *g8 = nullptr, *gs = nullptr;   // MXFP8 GEGLU output feeding ff.net.2 (qkv_dtype == 3)
         int rows = 0;

@@ -128,12 +128,10 @@ int Dit::create() {
         if (c.qkv_dtype >= 1) {
             auto U8 = [&](size_t n) { return (unsigned char*)arena.alloc(n, true); };
             l.q8_qk = U8((size_t)3 * D * D); l.s8_qk = U8((size_t)3 * D * D / 32);   // q | k | v stacked like the bf16 weights
-            l.q8_v = l.q8_qk + (size_t)2 * D * D; l.s8_v = l.s8_qk + (size_t)2 * D * D / 32;
             l.q8_q2 = U8((size_t)D * D);     l.s8_q2 = U8((size_t)D * D / 32);
             if (c.qkv_dtype >= 2) { l.q8_ff1 = U8((size_t)8 * D * D); l.s8_ff1 = U8((size_t)8 * D * D / 32); RALD_CHECK(l.q8_ff1 && l.s8_ff1, "dit: device allocation failed"); }
             if (c.qkv_dtype == 3) { l.q8_ff2 = U8((size_t)4 * D * D); l.s8_ff2 = U8((size_t)4 * D * D / 32); RALD_CHECK(l.q8_ff2 && l.s8_ff2, "dit: device allocation failed"); }
-            RALD_CHECK(l.q8_qk && l.s8_qk && l.q8_v && l.s8_v && l.q8_q2 && l.s8_q2,
-                       "dit: device allocation failed");
+            RALD_CHECK(l.q8_qk && l.s8_qk && l.q8_q2 && l.s8_q2, "dit: device allocation failed");
         }
     }
     w_k2_all = B16((size_t)L * D * c.context_dim);
@@ -253,7 +251,7 @@ int Dit::finalize() {
     for (const auto& k : expected) RALD_CHECK(loaded.count(k), "dit: missing key '" + k + "' (strict load)");
     if (cfg.qkv_dtype >= 1) {                  // MXFP8 copies of the attention projections, from the bf16 weights
         for (auto& l : layers) {
-            RALD_TRY(quantize_mx8(l.w_qk, 1, D, l.q8_qk, D, l.s8_qk, 3 * D, D, nullptr));      // q | k | v (q8_v / s8_v alias its last third)
+            RALD_TRY(quantize_mx8(l.w_qk, 1, D, l.q8_qk, D, l.s8_qk, 3 * D, D, nullptr));      // q | k | v
             RALD_TRY(quantize_mx8(l.w_q2, 1, D, l.q8_q2, D, l.s8_q2, D, D, nullptr));
             if (cfg.qkv_dtype >= 2) RALD_TRY(quantize_mx8(l.w_ff1, 1, D, l.q8_ff1, D, l.s8_ff1, 8 * D, D, nullptr));
             if (cfg.qkv_dtype == 3) RALD_TRY(quantize_mx8(l.w_ff2, 1, 4 * D, l.q8_ff2, 4 * D, l.s8_ff2, D, 4 * D, nullptr));
@@ -267,17 +265,15 @@ int Dit::finalize() {
 }
 
 void Dit::free_work(Work& w) {
-    for (void* p : {(void*)w.x, (void*)w.part, (void*)w.h, (void*)w.qk, (void*)w.vt, (void*)w.o, (void*)w.q2, (void*)w.g, (void*)w.h8, (void*)w.hs,
+    for (void* p : {(void*)w.x, (void*)w.part, (void*)w.h, (void*)w.qk, (void*)w.o, (void*)w.q2, (void*)w.g, (void*)w.h8, (void*)w.hs,
                     (void*)w.g8, (void*)w.gs})
         if (p) arena.release(p);
     w = Work();
 }
 int Dit::alloc_work(Work& w, size_t M) {
-    const size_t B = M / cfg.n_latents;
     w.x = (float*)arena.alloc(M * D * 4, true);
     w.h = (bf16*)arena.alloc(M * D * 2, true);
     w.qk = (bf16*)arena.alloc(M * 3 * D * 2, true);       // q | k | v rows of 3*D
-    w.vt = (bf16*)arena.alloc(B * D * cfg.n_latents * 2, true);
     w.o = (bf16*)arena.alloc(M * D * 2, true);
     w.q2 = (bf16*)arena.alloc(M * D * 2, true);
     w.g = (bf16*)arena.alloc(M * 4 * D * 2, true);
@@ -289,7 +285,7 @@ int Dit::alloc_work(Work& w, size_t M) {
         const size_t slabs_rows = 4 * r4 > (size_t)cfg.n_heads * r8 ? 4 * r4 : (size_t)cfg.n_heads * r8;
         w.part = (float*)arena.alloc(slabs_rows * 512 * 4, true);
     }
-    RALD_CHECK(w.x && w.h && w.qk && w.vt && w.o && w.q2 && w.g && w.part, "dit: workspace allocation failed");
+    RALD_CHECK(w.x && w.h && w.qk && w.o && w.q2 && w.g && w.part, "dit: workspace allocation failed");
     if (cfg.qkv_dtype >= 1) {
         w.h8 = (unsigned char*)arena.alloc(M * D, true);
         w.hs = (unsigned char*)arena.alloc(M * D / 32, true);
@@ -537,7 +533,7 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
     const int M = B * NL;
     RALD_CHECK(w.rows >= M, "dit: workspace smaller than the batch (internal)");
     float* const ws_x = w.x; float* const ws_part = w.part;
-    bf16 *const ws_h = w.h, *const ws_qk = w.qk, *const ws_vt = w.vt, *const ws_o = w.o, *const ws_q2 = w.q2, *const ws_g = w.g;
+    bf16 *const ws_h = w.h, *const ws_qk = w.qk, *const ws_o = w.o, *const ws_q2 = w.q2, *const ws_g = w.g;
     unsigned char *const ws_h8 = w.h8, *const ws_hs = w.hs, *const ws_g8 = w.g8, *const ws_gs = w.gs;
     x += (size_t)b0 * NL * C;
     out += (size_t)b0 * NL * C;
@@ -554,180 +550,58 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
     const bf16* Vtc = Vtc0 + (size_t)b0 * L * D * T;
     const float scale = 1.0f / sqrtf((float)cfg.d_head);
     const float qscale = scale * 1.4426950408889634f;     // softmax scale and log2(e) folded into q by the projection epilogue
+    // MXFP8 (BASELINE config #5): the AdaLN outputs that feed to_q / to_k / to_v (norm1, norm2; qkv_dtype >= 2 also norm3 for the GEGLU
+    // projection) are produced directly in e4m3 + e8m0/32 by the residual+LayerNorm step and multiplied on
+    // v_mfma_scale_f32_16x16x128_f8f6f4; to_out stays bf16, and so does ff.net.2 below qkv_dtype 3 (its A operand, the GEGLU output, needs
+    // the quantising FF1 epilogue of ff2_mx).
+    const bool mx1 = cfg.qkv_dtype >= 1, mx2 = cfg.qkv_dtype >= 2;
 
-    // live timing (rald_dit_profile_begin / _end): events around the launches of one kind on the launch stream
+    // live timing (rald_dit_profile_begin / _end, bf16 only): events around the launches of one kind on the launch stream
     auto timed_launch = [&](int kind, auto&& launch) -> int {
-        const bool timed = timed_ok && prof_on && ((prof_mask >> kind) & 1u) && prof_used + 2 <= (int)prof_ev.size();
+        const bool timed = timed_ok && !mx1 && prof_on && ((prof_mask >> kind) & 1u) && prof_used + 2 <= (int)prof_ev.size();
         if (timed) RALD_HIP(hipEventRecord(prof_ev[prof_used], st));
         RALD_TRY(launch());
         if (timed) { RALD_HIP(hipEventRecord(prof_ev[prof_used + 1], st)); prof_kind[prof_used / 2] = kind; prof_used += 2; }
         return 0;
     };
-    auto resid_ln = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* mnext) -> int {
-        // x += A.W^T + bias, then (if mnext) h = AdaLN(x; mnext) for the next sub-block
-        if (splitk_for(M, K))
-            return resid_splitk_ln(A, lda, W, ldw, bias, ws_x, mnext ? ws_h : nullptr, mnext, mnext ? mnext + D : nullptr, gstride, NL, 1.0f, 1e-5f,
-                                   M, K, splitk_for(M, K), ws_part, st);
-        if (mnext && gemm_resid_ln_pays(M, K)) {
-            GemmLnArgs g;
-            g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = ws_x; g.h = ws_h;
-            g.g = mnext; g.b = mnext + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f;
-            g.M = M; g.K = K;
-            return gemm_resid_ln(g, st);
-        }
-        GemmArgs o = gemm_args(A, lda, W, ldw, ws_x, D, bias, M, D, K);
-        RALD_TRY(gemm_nt(o, EPI_RESID, st));
-        if (mnext) RALD_TRY(layernorm_mod(ws_x, ws_h, M, D, mnext, mnext + D, gstride, NL, 1.0f, 1e-5f, st));
-        return 0;
+    // a projection of the AdaLN output: bf16 from ws_h, or (mx8) MXFP8 from ws_h8 / ws_hs against the weight's e4m3 copy W8 / SW
+    auto proj = [&](bool mx8, GemmArgs g, const unsigned char* W8, const unsigned char* SW, int epi) -> int {
+        if (!mx8) return gemm_nt(g, epi, st);
+        Mx8Args a;
+        a.g = g; a.g.A = nullptr; a.g.B = nullptr;
+        a.A8 = ws_h8; a.SA = ws_hs; a.B8 = W8; a.SB = SW; a.strideSA = 0; a.strideSB = 0;
+        return gemm_mx8(a, epi, st);
     };
-    // the same with one weight matrix per sample (W + sample * strideW): the folded cross-attention's output projection
-    auto resid_ln_w = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* mnext, int64_t strideW) -> int {
-        if (mnext && gemm_resid_ln_pays(M, K)) {
-            GemmLnArgs g;
-            g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = ws_x; g.h = ws_h;
-            g.g = mnext; g.b = mnext + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f;
-            g.M = M; g.K = K; g.strideW = strideW; g.w_rows = NL;
-            return gemm_resid_ln(g, st);
-        }
-        GemmArgs o = gemm_args(A, lda, W, ldw, ws_x, D, bias, NL, D, K);
-        o.batch = B; o.strideA = (int64_t)NL * lda; o.strideB = strideW; o.strideC = (int64_t)NL * D;
-        RALD_TRY(gemm_nt(o, EPI_RESID, st));
-        if (mnext) RALD_TRY(layernorm_mod(ws_x, ws_h, M, D, mnext, mnext + D, gstride, NL, 1.0f, 1e-5f, st));
-        return 0;
+    // x += A.W^T + bias, then (mnext set) the AdaLN of the next sub-block into ws_h, or into ws_h8 / ws_hs when mx8
+    auto resid_args = [&](const bf16* A, int64_t ld, const bf16* W, const float* bias, int K, const float* mnext, bool mx8) {
+        GemmLnArgs g = gemm_ln_args(A, ld, W, ld, bias, ws_x, mx8 ? nullptr : ws_h, mnext, mnext ? mnext + D : nullptr, gstride, NL, 1.0f, M, K);
+        if (mx8 && mnext) { g.h8 = ws_h8; g.hs = ws_hs; }
+        return g;
+    };
+    auto resid_ln = [&](const bf16* A, int64_t ld, const bf16* W, const float* bias, int K, const float* mnext, bool mx8) {
+        return resid_gemm_ln(resid_args(A, ld, W, bias, K, mnext, mx8), D, ws_part, st);
     };
     const bool fold = cond_fold(Bfull);
-    RALD_CHECK(!fold || !small_m_fused(M, NL, cfg.n_heads, D, T), "dit: a folded condition cache cannot feed the small-batch kernels (internal)");
+    const bool small = !mx1 && small_m_fused(M, NL, cfg.n_heads, D, T);
+    RALD_CHECK(!fold || !small, "dit: a folded condition cache cannot feed the small-batch kernels (internal)");
     const bf16* Gt0 = Vtc0 + (size_t)2 * Bfull * T * L * D;         // (behind Vc; only there when fold)
     const bf16* Gt = Gt0 + (size_t)b0 * L * D * D;
     const bf16* Ut = Gt0 + (size_t)Bfull * L * D * D + (size_t)b0 * L * D * D;
     RALD_TRY(proj_in(x, w_in, ws_x, M, C, D, coef, cstride, NL, st));
-    if (cfg.qkv_dtype >= 1) {
-        // ---- MXFP8 q/k/v projections (BASELINE config #5; qkv_dtype 2 adds the GEGLU projection of the feed-forward).  The AdaLN outputs that feed to_q / to_k / to_v (norm1,
-        // norm2) are produced directly in e4m3 + e8m0/32 by the fused residual+LayerNorm GEMM epilogue (or by
-        // layernorm_mod_mx8 where that kernel does not pay) and multiplied on v_mfma_scale_f32_16x16x128_f8f6f4;
-        // to_out and the feed-forward stay bf16 (their A operands - attention output, GEGLU output - would need
-        // quantising epilogues of their own before fp8 pays there).
-        auto ln8 = [&](const float* m) { return layernorm_mod_mx8(ws_x, ws_h8, ws_hs, M, D, m, m + D, gstride, NL, 1.0f, 1e-5f, st); };
-        auto mx = [&](const unsigned char* A8, const unsigned char* SA, const unsigned char* B8, const unsigned char* SB, void* Cp, int64_t ldc,
-                      const float* bias, int m, int n) {
-            Mx8Args a;
-            a.A8 = A8; a.SA = SA; a.B8 = B8; a.SB = SB; a.strideSA = 0; a.strideSB = 0;
-            a.g = gemm_args(nullptr, D, nullptr, D, Cp, ldc, bias, m, n, D);
-            return a;
-        };
-        // x += A.W^T + bias (bf16 GEMM), then the next AdaLN as MXFP8 into ws_h8 / ws_hs
-        auto resid_ln8 = [&](const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, int K, const float* mnext) -> int {
-            if (gemm_resid_ln_pays(M, K)) {
-                GemmLnArgs g;
-                g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.x = ws_x; g.h = nullptr; g.h8 = ws_h8; g.hs = ws_hs;
-                g.g = mnext; g.b = mnext + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f;
-                g.M = M; g.K = K;
-                return gemm_resid_ln(g, st);
-            }
-            GemmArgs o = gemm_args(A, lda, W, ldw, ws_x, D, bias, M, D, K);
-            RALD_TRY(gemm_nt(o, EPI_RESID, st));
-            return ln8(mnext);
-        };
-        RALD_TRY(ln8(mod));                                                               // norm1 of block 0
-        for (int li = 0; li < L; ++li) {
-            const Layer& l = layers[li];
-            const float* m2 = mod + (int64_t)(li * 3 + 1) * 2 * D;
-            const float* m3 = mod + (int64_t)(li * 3 + 2) * 2 * D;
-            AttnArgs a1;
-            if (NL % 64 == 0) {                                                            // fused q|k|v projection, row-major V (see the bf16 path)
-                Mx8Args qkv = mx(ws_h8, ws_hs, l.q8_qk, l.s8_qk, ws_qk, 3 * D, nullptr, M, 3 * D);
-                qkv.g.alpha = qscale; qkv.g.alpha_ncols = D;
-                RALD_TRY(gemm_mx8(qkv, EPI_BF16, st));
-                a1.Q = ws_qk; a1.ldq = 3 * D; a1.strideQ = (int64_t)NL * 3 * D;
-                a1.K = ws_qk + D; a1.ldk = 3 * D; a1.strideK = (int64_t)NL * 3 * D;
-                a1.Vt = nullptr; a1.ldvt = 0; a1.strideVt = 0;
-                a1.V = ws_qk + 2 * D; a1.ldv = 3 * D; a1.strideV = (int64_t)NL * 3 * D;
-            } else {
-                Mx8Args qk = mx(ws_h8, ws_hs, l.q8_qk, l.s8_qk, ws_qk, 2 * D, nullptr, M, 2 * D);
-                qk.g.alpha = qscale; qk.g.alpha_ncols = D;
-                RALD_TRY(gemm_mx8(qk, EPI_BF16, st));
-                Mx8Args vt = mx(l.q8_v, l.s8_v, ws_h8, ws_hs, ws_vt, NL, nullptr, D, NL);    // V^T = Wv . h^T per sample
-                vt.g.batch = B; vt.g.strideB = (int64_t)NL * D; vt.strideSB = (int64_t)NL * D / 32; vt.g.strideC = (int64_t)D * NL;
-                RALD_TRY(gemm_mx8(vt, EPI_BF16, st));
-                a1.Q = ws_qk; a1.ldq = 2 * D; a1.strideQ = (int64_t)NL * 2 * D;
-                a1.K = ws_qk + D; a1.ldk = 2 * D; a1.strideK = (int64_t)NL * 2 * D;
-                a1.Vt = ws_vt; a1.ldvt = NL; a1.strideVt = (int64_t)D * NL;
-            }
-            a1.O = ws_o; a1.ldo = D; a1.strideO = (int64_t)NL * D;
-            a1.nq = NL; a1.nk = NL; a1.k_rows = NL; a1.heads = cfg.n_heads; a1.batch = B; a1.scale = scale; a1.q_prescaled = 1;
-            RALD_TRY(attention_d64(a1, st));
-            RALD_TRY(resid_ln8(ws_o, D, l.w_o, D, l.b_o, D, m2));                        // + norm2 (MXFP8) for to_q of attn2
-            Mx8Args q2 = mx(ws_h8, ws_hs, l.q8_q2, l.s8_q2, ws_q2, D, nullptr, M, D);
-            q2.g.alpha = qscale;
-            RALD_TRY(gemm_mx8(q2, EPI_BF16, st));
-            AttnArgs a2;
-            a2.Q = ws_q2; a2.ldq = D; a2.strideQ = (int64_t)NL * D;
-            a2.K = Kc + (size_t)li * D; a2.ldk = (int64_t)L * D; a2.strideK = (int64_t)T * L * D;
-            a2.Vt = Vtc + (size_t)li * D * T; a2.ldvt = T; a2.strideVt = (int64_t)L * D * T;
-            a2.O = ws_o; a2.ldo = D; a2.strideO = (int64_t)NL * D;
-            a2.nq = NL; a2.nk = T; a2.k_rows = T; a2.heads = cfg.n_heads; a2.batch = B; a2.scale = scale; a2.q_prescaled = 1;
-            RALD_TRY(attention_d64(a2, st));
-            // qkv_dtype 3: the GEGLU output leaves the FF1 epilogue as MXFP8 and ff.net.2 (+ residual + next AdaLN) consumes it
-            if (fork_pending && timed_ok) { RALD_HIP(hipEventRecord(ev_fork, st)); fork_pending = false; }   // two-stream schedule: the other half starts here
-            const bool ff2_mx = cfg.qkv_dtype == 3 && M % 256 == 0 && M >= 4096 && gemm_resid_ln_pays(M, 4 * D);
-            if (cfg.qkv_dtype >= 2) {
-                RALD_TRY(resid_ln8(ws_o, D, l.w_o2, D, l.b_o2, D, m3));                  // + norm3 (MXFP8)
-                Mx8Args f1 = mx(ws_h8, ws_hs, l.q8_ff1, l.s8_ff1, ws_g, 4 * D, l.b_ff1, M, 8 * D);
-                if (ff2_mx) { f1.g.out8 = ws_g8; f1.g.outs = ws_gs; }
-                RALD_TRY(gemm_mx8(f1, EPI_GEGLU, st));
-                if (ff2_mx) {
-                    const float* mn = (li + 1 < L) ? mod + (int64_t)((li + 1) * 3) * 2 * D : m3;      // last block: the LN output is unused
-                    GemmLnArgs g;
-                    g.A = nullptr; g.W = nullptr; g.A8 = ws_g8; g.SA = ws_gs; g.W8 = l.q8_ff2; g.SW = l.s8_ff2; g.lda = 4 * D; g.ldw = 4 * D;
-                    g.bias = l.b_ff2; g.x = ws_x; g.h = nullptr; g.h8 = ws_h8; g.hs = ws_hs;
-                    g.g = mn; g.b = mn + D; g.gstride = gstride; g.rows_per_group = NL; g.add_one = 1.0f; g.eps = 1e-5f; g.M = M; g.K = 4 * D;
-                    RALD_TRY(gemm_resid_ln(g, st));
-                    continue;
-                }
-            } else {
-                RALD_TRY(resid_ln(ws_o, D, l.w_o2, D, l.b_o2, D, m3));                   // + norm3 (bf16) for the feed-forward
-                GemmArgs f1 = gemm_args(ws_h, D, l.w_ff1, D, ws_g, 4 * D, l.b_ff1, M, 8 * D, D);
-                RALD_TRY(gemm_nt(f1, EPI_GEGLU, st));
-            }
-            if (li + 1 < L) RALD_TRY(resid_ln8(ws_g, 4 * D, l.w_ff2, 4 * D, l.b_ff2, 4 * D, mod + (int64_t)((li + 1) * 3) * 2 * D));
-            else RALD_TRY(resid_ln(ws_g, 4 * D, l.w_ff2, 4 * D, l.b_ff2, 4 * D, nullptr));
-        }
-        RALD_TRY(final_norm_proj(ws_x, norm_g, norm_b, w_out, x, out, M, D, C, coef, cstride, NL, st, w_out_hl));
-        return 0;
-    }
-    RALD_TRY(layernorm_mod(ws_x, ws_h, M, D, mod, mod + D, gstride, NL, 1.0f, 1e-5f, st));      // norm1 of block 0
+    RALD_TRY(mx1 ? layernorm_mod_mx8(ws_x, ws_h8, ws_hs, M, D, mod, mod + D, gstride, NL, 1.0f, 1e-5f, st)
+                 : layernorm_mod(ws_x, ws_h, M, D, mod, mod + D, gstride, NL, 1.0f, 1e-5f, st));      // norm1 of block 0
     for (int li = 0; li < L; ++li) {
         const Layer& l = layers[li];
-        const float* m1 = mod + (int64_t)(li * 3 + 0) * 2 * D;
         const float* m2 = mod + (int64_t)(li * 3 + 1) * 2 * D;
         const float* m3 = mod + (int64_t)(li * 3 + 2) * 2 * D;
         // ---- x += attn1(norm1(x, t))                                               (:166)
-        // (norm1(x) is already in ws_h: produced by the previous block's FF2 epilogue / the prologue)
-        (void)m1;
+        // (norm1(x) is already in ws_h / ws_h8: produced by the previous block's FF2 epilogue / the prologue)
         // one projection for q | k | v (N = 1536); the attention kernel reads V row-major through ds_read_b64_tr_b16, so no
-        // transposed copy of V and no separate V^T GEMM (NL % 64 != 0: the two-GEMM form)
-        const bool vrow = NL % 64 == 0;
-        AttnArgs a1;
-        if (vrow) {
-            GemmArgs qkv = gemm_args(ws_h, D, l.w_qk, D, ws_qk, 3 * D, nullptr, M, 3 * D, D);
-            qkv.alpha = qscale; qkv.alpha_ncols = D;                                // q columns only
-            RALD_TRY(gemm_nt(qkv, EPI_BF16, st));
-            a1.Q = ws_qk; a1.ldq = 3 * D; a1.strideQ = (int64_t)NL * 3 * D;
-            a1.K = ws_qk + D; a1.ldk = 3 * D; a1.strideK = (int64_t)NL * 3 * D;
-            a1.Vt = nullptr; a1.ldvt = 0; a1.strideVt = 0;
-            a1.V = ws_qk + 2 * D; a1.ldv = 3 * D; a1.strideV = (int64_t)NL * 3 * D;
-        } else {
-            GemmArgs qk = gemm_args(ws_h, D, l.w_qk, D, ws_qk, 2 * D, nullptr, M, 2 * D, D);
-            qk.alpha = qscale; qk.alpha_ncols = D;
-            RALD_TRY(gemm_nt(qk, EPI_BF16, st));
-            GemmArgs vt = gemm_args(l.w_v, D, ws_h, D, ws_vt, NL, nullptr, D, NL, D);   // V^T = Wv . h^T per sample
-            vt.batch = B; vt.strideB = (int64_t)NL * D; vt.strideC = (int64_t)D * NL;
-            RALD_TRY(gemm_nt(vt, EPI_BF16, st));
-            a1.Q = ws_qk; a1.ldq = 2 * D; a1.strideQ = (int64_t)NL * 2 * D;
-            a1.K = ws_qk + D; a1.ldk = 2 * D; a1.strideK = (int64_t)NL * 2 * D;
-            a1.Vt = ws_vt; a1.ldvt = NL; a1.strideVt = (int64_t)D * NL;
-        }
-        if (vrow && small_m_fused(M, NL, cfg.n_heads, D, T)) {
+        // transposed copy of V and no separate V^T GEMM
+        GemmArgs qkv = gemm_args(ws_h, D, l.w_qk, D, ws_qk, 3 * D, nullptr, M, 3 * D, D);
+        qkv.alpha = qscale; qkv.alpha_ncols = D;                                // q columns only
+        RALD_TRY(proj(mx1, qkv, l.q8_qk, l.s8_qk, EPI_BF16));
+        if (small) {
             // small batches (attn_small.hip): attention + that head's slice of to_out in one kernel per (head, 32-query block),
             // the 8 per-head partials summed into the residual stream together with the next AdaLN; then to_q + the 64-key
             // radar cross-attention + to_out slice likewise.  8 launches per block instead of 12.
@@ -737,37 +611,48 @@ int Dit::denoise_range(const float* x, int Bfull, int b0, int B, int sigma_row, 
                                    l.w_o2, ws_part, M, NL, cfg.n_heads, T, qscale, st, true));
             RALD_TRY(reduce_resid_ln(ws_part, cfg.n_heads, (int64_t)M * D, l.b_o2, ws_x, ws_h, M, m3, m3 + D, gstride, NL, 1.0f, 1e-5f, st, true));
         } else {
-        a1.O = ws_o; a1.ldo = D; a1.strideO = (int64_t)NL * D;
-        a1.nq = NL; a1.nk = NL; a1.k_rows = NL; a1.heads = cfg.n_heads; a1.batch = B; a1.scale = scale; a1.q_prescaled = 1;
-        RALD_TRY(attention_d64(a1, st));
-        RALD_TRY(timed_launch(1, [&] { return resid_ln(ws_o, D, l.w_o, D, l.b_o, D, m2); }));   // + norm2 for the next sub-block
-        // ---- x += attn2(norm2(x, t), context)                                      (:167)
-        if (fold) {
-            // folded form (see cond_fold in dit.h): P = softmax over each head's 64 keys of h.Gt^T, then x += P.Ut^T + b_o (+ norm3)
-            GemmArgs p1 = gemm_args(ws_h, D, Gt + (size_t)li * D * D, D, ws_q2, D, nullptr, NL, D, D);
-            p1.batch = B; p1.strideA = (int64_t)NL * D; p1.strideB = (int64_t)L * D * D; p1.strideC = (int64_t)NL * D;
-            RALD_TRY(gemm_nt(p1, EPI_SOFTMAX64, st));
-            RALD_TRY(timed_launch(2, [&] { return resid_ln_w(ws_q2, D, Ut + (size_t)li * D * D, D, l.b_o2, D, m3, (int64_t)L * D * D); }));
-        } else {
-        GemmArgs q2 = gemm_args(ws_h, D, l.w_q2, D, ws_q2, D, nullptr, M, D, D);
-        q2.alpha = qscale;
-        RALD_TRY(gemm_nt(q2, EPI_BF16, st));
-        AttnArgs a2;
-        a2.Q = ws_q2; a2.ldq = D; a2.strideQ = (int64_t)NL * D;
-        a2.K = Kc + (size_t)li * D; a2.ldk = (int64_t)L * D; a2.strideK = (int64_t)T * L * D;
-        a2.Vt = Vtc + (size_t)li * D * T; a2.ldvt = T; a2.strideVt = (int64_t)L * D * T;
-        a2.O = ws_o; a2.ldo = D; a2.strideO = (int64_t)NL * D;
-        a2.nq = NL; a2.nk = T; a2.k_rows = T; a2.heads = cfg.n_heads; a2.batch = B; a2.scale = scale; a2.q_prescaled = 1;
-        RALD_TRY(attention_d64(a2, st));
-        RALD_TRY(resid_ln(ws_o, D, l.w_o2, D, l.b_o2, D, m3));                     // + norm3
-        }
+            RALD_TRY(attention_d64(self_attn_args(ws_qk, ws_o, NL, D, cfg.n_heads, B, scale), st));
+            RALD_TRY(timed_launch(1, [&] { return resid_ln(ws_o, D, l.w_o, l.b_o, D, m2, mx1); }));   // + norm2 for the next sub-block
+            // ---- x += attn2(norm2(x, t), context)                                  (:167)
+            if (fold) {
+                // folded form (see cond_fold in dit.h): P = softmax over each head's 64 keys of h.Gt^T, then x += P.Ut^T + b_o (+ norm3),
+                // one Ut per sample
+                GemmArgs p1 = gemm_args(ws_h, D, Gt + (size_t)li * D * D, D, ws_q2, D, nullptr, NL, D, D);
+                p1.batch = B; p1.strideA = (int64_t)NL * D; p1.strideB = (int64_t)L * D * D; p1.strideC = (int64_t)NL * D;
+                RALD_TRY(gemm_nt(p1, EPI_SOFTMAX64, st));
+                GemmLnArgs g = resid_args(ws_q2, D, Ut + (size_t)li * D * D, l.b_o2, D, m3, false);
+                g.strideW = (int64_t)L * D * D; g.w_rows = NL;
+                RALD_TRY(timed_launch(2, [&] { return resid_gemm_ln(g, D, ws_part, st); }));
+            } else {
+                GemmArgs q2 = gemm_args(ws_h, D, l.w_q2, D, ws_q2, D, nullptr, M, D, D);
+                q2.alpha = qscale;
+                RALD_TRY(proj(mx1, q2, l.q8_q2, l.s8_q2, EPI_BF16));
+                AttnArgs a2;
+                a2.Q = ws_q2; a2.ldq = D; a2.strideQ = (int64_t)NL * D;
+                a2.K = Kc + (size_t)li * D; a2.ldk = (int64_t)L * D; a2.strideK = (int64_t)T * L * D;
+                a2.Vt = Vtc + (size_t)li * D * T; a2.ldvt = T; a2.strideVt = (int64_t)L * D * T;
+                a2.O = ws_o; a2.ldo = D; a2.strideO = (int64_t)NL * D;
+                a2.nq = NL; a2.nk = T; a2.k_rows = T; a2.heads = cfg.n_heads; a2.batch = B; a2.scale = scale; a2.q_prescaled = 1;
+                RALD_TRY(attention_d64(a2, st));
+                if (mx1 && fork_pending && timed_ok) { RALD_HIP(hipEventRecord(ev_fork, st)); fork_pending = false; }   // MXFP8: the other half starts here
+                RALD_TRY(resid_ln(ws_o, D, l.w_o2, l.b_o2, D, m3, mx2));                // + norm3
+            }
         }
         // ---- x += ff(norm3(x, t))                                                   (:168)
-        if (fork_pending && timed_ok) { RALD_HIP(hipEventRecord(ev_fork, st)); fork_pending = false; }   // two-stream schedule: the other half starts here
+        if (fork_pending && timed_ok) { RALD_HIP(hipEventRecord(ev_fork, st)); fork_pending = false; }   // two-stream schedule: the other half starts here (bf16)
+        // qkv_dtype 3: the GEGLU output leaves the FF1 epilogue as MXFP8 and ff.net.2 (+ residual + next AdaLN) consumes it
+        const bool ff2_mx = cfg.qkv_dtype == 3 && M % 256 == 0 && M >= 4096 && gemm_resid_ln_pays(M, 4 * D);
         GemmArgs f1 = gemm_args(ws_h, D, l.w_ff1, D, ws_g, 4 * D, l.b_ff1, M, 8 * D, D);
-        RALD_TRY(timed_launch(0, [&] { return gemm_nt(f1, EPI_GEGLU, st); }));
+        if (ff2_mx) { f1.out8 = ws_g8; f1.outs = ws_gs; }
+        RALD_TRY(timed_launch(0, [&] { return proj(mx2, f1, l.q8_ff1, l.s8_ff1, EPI_GEGLU); }));
         const float* m1_next = (li + 1 < L) ? mod + (int64_t)((li + 1) * 3) * 2 * D : nullptr;   // norm1 of the next block
-        RALD_TRY(timed_launch(3, [&] { return resid_ln(ws_g, 4 * D, l.w_ff2, 4 * D, l.b_ff2, 4 * D, m1_next); }));
+        if (ff2_mx) {
+            GemmLnArgs g = resid_args(nullptr, 4 * D, nullptr, l.b_ff2, 4 * D, m1_next ? m1_next : m3, true);   // last block: the LN output is unused
+            g.A8 = ws_g8; g.SA = ws_gs; g.W8 = l.q8_ff2; g.SW = l.s8_ff2;
+            RALD_TRY(resid_gemm_ln(g, D, ws_part, st));
+        } else {
+            RALD_TRY(timed_launch(3, [&] { return resid_ln(ws_g, 4 * D, l.w_ff2, l.b_ff2, 4 * D, m1_next, mx1); }));
+        }
     }
     RALD_TRY(final_norm_proj(ws_x, norm_g, norm_b, w_out, x, out, M, D, C, coef, cstride, NL, st, w_out_hl));
     return 0;

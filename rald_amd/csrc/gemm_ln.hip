@@ -587,4 +587,19 @@ int gemm_resid_ln(const GemmLnArgs& a, hipStream_t st) {
     return mx ? launch_ln<64, 1, 8, true>(a, st) : launch_ln<64, 1, 8, false>(a, st);
 }
 
+int resid_gemm_ln(const GemmLnArgs& a, int n, float* scratch, hipStream_t st) {
+    const int splits = splitk_for(a.M, a.K);
+    if (n == 512 && splits && !a.A8 && !a.h8 && a.strideW == 0)
+        return resid_splitk_ln(a.A, a.lda, a.W, a.ldw, a.bias, a.x, a.g ? a.h : nullptr, a.g, a.b, a.gstride, a.rows_per_group, a.add_one, a.eps,
+                               a.M, a.K, splits, scratch, st);
+    if (n == 512 && a.g && gemm_resid_ln_pays(a.M, a.K)) return gemm_resid_ln(a, st);
+    RALD_CHECK(!a.A8, "resid_gemm_ln: MXFP8 operands need the fused kernel");
+    GemmArgs o = gemm_args(a.A, a.lda, a.W, a.ldw, a.x, n, a.bias, a.M, n, a.K);
+    if (a.strideW) { o.M = a.w_rows; o.batch = a.M / a.w_rows; o.strideA = a.w_rows * a.lda; o.strideB = a.strideW; o.strideC = (int64_t)a.w_rows * n; }
+    RALD_TRY(gemm_nt(o, EPI_RESID, st));
+    if (!a.g) return 0;
+    if (a.h8) return layernorm_mod_mx8(a.x, a.h8, a.hs, a.M, n, a.g, a.b, a.gstride, a.rows_per_group, a.add_one, a.eps, st);
+    return layernorm_mod(a.x, a.h, a.M, n, a.g, a.b, a.gstride, a.rows_per_group, a.add_one, a.eps, st);
+}
+
 }  // namespace rald

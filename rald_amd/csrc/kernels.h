@@ -75,6 +75,19 @@ int gemm_resid_ln(const GemmLnArgs& a, hipStream_t st);
 // true when the fused kernel beats GEMM + separate LayerNorm (measured on MI355X, tools/bench_resid_ln.py and
 // whole-NFE sweeps: wins from M = 16384 on for K = 512 and K = 2048, +1 % per NFE at B = 32; at M = 8192 it loses)
 inline bool gemm_resid_ln_pays(int M, int K = 512) { (void)K; return M >= 16384; }
+// bf16 operands, h in bf16 (set h8 / hs for MXFP8, A8 / SA / W8 / SW for MXFP8 operands); eps = 1e-5 (nn.LayerNorm's default)
+inline GemmLnArgs gemm_ln_args(const bf16* A, int64_t lda, const bf16* W, int64_t ldw, const float* bias, float* x, bf16* h,
+                               const float* g, const float* b, int64_t gstride, int rows_per_group, float add_one, int M, int K) {
+    GemmLnArgs a;
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.x = x; a.h = h;
+    a.g = g; a.b = b; a.gstride = gstride; a.rows_per_group = rows_per_group; a.add_one = add_one; a.eps = 1e-5f; a.M = M; a.K = K;
+    return a;
+}
+// x[M][n] += A.W^T + bias, then (a.g set) the LayerNorm of GemmLnArgs: the engine choice of every residual projection of the latent stacks.
+// Split-K (resid_splitk_ln through `scratch`, splitk_for) when the operands are bf16 and the LN output is not MXFP8; else the fused
+// gemm_resid_ln where it pays; else gemm_nt (EPI_RESID; batched over the weight groups of a.strideW) + a separate LayerNorm.  The first
+// two own whole 512-wide rows (n = 512 only); MXFP8 operands need the fused kernel.
+int resid_gemm_ln(const GemmLnArgs& a, int n, float* scratch, hipStream_t st);
 
 // radar_train.hip: out [B*D*H*W][32] bf16 = the 27-neighbourhood (zero outside the volume) of channel 0 of cube [B][D][H][W][cube_ch], 5 zero pads
 int patches27(const float* cube, int cube_ch, bf16* out, int B, int D, int H, int Wd, hipStream_t st);
@@ -126,6 +139,18 @@ struct AttnArgs {
     int v_padded = 0;                          // row-major V: rows nk .. k_rows-1 are finite (zero), so nk need not be a multiple of 64
 };
 int attention_d64(const AttnArgs& a, hipStream_t st);
+// self-attention of n tokens per sample over a fused projection qkv [batch][n][q | k | v of `inner` columns each] (q prescaled,
+// V row-major) into O [batch][n][inner]
+inline AttnArgs self_attn_args(const bf16* qkv, bf16* O, int n, int inner, int heads, int batch, float scale) {
+    AttnArgs a;
+    a.Q = qkv; a.ldq = 3 * inner; a.strideQ = (int64_t)n * 3 * inner;
+    a.K = qkv + inner; a.ldk = 3 * inner; a.strideK = (int64_t)n * 3 * inner;
+    a.Vt = nullptr; a.ldvt = 0; a.strideVt = 0;
+    a.V = qkv + 2 * inner; a.ldv = 3 * inner; a.strideV = (int64_t)n * 3 * inner;
+    a.O = O; a.ldo = inner; a.strideO = (int64_t)n * inner;
+    a.nq = n; a.nk = n; a.k_rows = n; a.heads = heads; a.batch = batch; a.scale = scale; a.q_prescaled = 1;
+    return a;
+}
 int attention_pick_ksplit(int nq, int nk, int heads, int batch);
 inline int64_t attention_split_scratch_bytes(int ksplit, int nq, int heads, int batch) { return (int64_t)ksplit * batch * heads * nq * 66 * 4; }
 
