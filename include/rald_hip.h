@@ -269,6 +269,31 @@ int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t 
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Radar front end (dataset_preprocessor/radar.py:64-76 load_radar_data + utils/radar_preprocessing.py:6-62 RAEIVVmap):
+ * raw ADC frames -> RAEIVV cubes [R = range_fft][A = angle_fft][E = elevation_fft][3] (intensity dB, velocity, validity 0/1).
+ * range_fft / doppler_fft: powers of two in [2, 256]; angle_fft / elevation_fft: [1, 64].  crop_low / crop_high are the
+ * fractions of range bins zeroed at the head / tail; int(range_fft * crop_high) must be >= 1 (the reference's [-0:] slice
+ * would zero every bin).  Everything is checked, and the host tables built, at create.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t ntx, nrx, n_chirps, n_samples;
+    int32_t range_fft, doppler_fft, angle_fft, elevation_fft;
+    double crop_low, crop_high;
+} rald_radar_dsp_config;
+typedef struct rald_radar_dsp rald_radar_dsp;
+/* tx_layout [ntx][3], rx_layout [nrx][3] int32 rows {data index, azimuth, elevation} in half wavelengths (config/antenna_array.txt);
+ * vbins [n_vbins] = the velocity reported for Doppler bin d (the reference's vbins; n_vbins >= doppler_fft). */
+int rald_radar_dsp_create(const rald_radar_dsp_config* cfg, const int32_t* tx_layout, const int32_t* rx_layout, const double* vbins,
+                          int32_t n_vbins, rald_radar_dsp** out);
+void rald_radar_dsp_destroy(rald_radar_dsp* h);
+/* device workspace rald_radar_dsp_run needs for `batch` frames (host arithmetic; -1 on a bad configuration) */
+int64_t rald_radar_dsp_workspace_bytes(const rald_radar_dsp_config* cfg, int32_t batch);
+/* frames [batch][ntx][nrx][n_chirps][n_samples][2] (I, Q): input_kind 0 = int16, the frame's complex mean removed (radar.py:75);
+ * input_kind 1 = fp32, used as given.  out: fp32 [batch][R][A][E][3].  A frame's result does not depend on the batch. */
+int rald_radar_dsp_run(const rald_radar_dsp* h, const void* frames, int32_t input_kind, int32_t batch, float* out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel-level entry points (what the parity tests and microbenchmarks drive directly)
  * ---------------------------------------------------------------------------------------- */
 /* C[b][m][n] = alpha * sum_k A[b][m][k]*B[b][n][k] (+bias[n]); A,B bf16 (K contiguous).

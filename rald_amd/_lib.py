@@ -32,6 +32,12 @@ class AeConfig(C.Structure):
                 ("heads", c_int), ("dim_head", c_int), ("num_inputs", c_int), ("query_type", c_int)]
 
 
+class RadarDspConfig(C.Structure):
+    _fields_ = [("ntx", c_int), ("nrx", c_int), ("n_chirps", c_int), ("n_samples", c_int), ("range_fft", c_int),
+                ("doppler_fft", c_int), ("angle_fft", c_int), ("elevation_fft", c_int), ("crop_low", C.c_double),
+                ("crop_high", C.c_double)]
+
+
 # name -> (restype, argtypes); everything include/rald_hip.h declares
 SIGNATURES = {
     "rald_last_error": (c_char_p, []),
@@ -92,6 +98,11 @@ SIGNATURES = {
     "rald_optim_ema": (c_int, [c_void_p, c_void_p, c_i64, C.c_double, c_void_p]),
     "rald_radar_cube_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_void_p,
                                         c_void_p]),
+    "rald_radar_dsp_create": (c_int, [C.POINTER(RadarDspConfig), C.POINTER(c_int), C.POINTER(c_int), C.POINTER(C.c_double), c_int,
+                                      C.POINTER(c_void_p)]),
+    "rald_radar_dsp_destroy": (None, [c_void_p]),
+    "rald_radar_dsp_workspace_bytes": (c_i64, [C.POINTER(RadarDspConfig), c_int]),
+    "rald_radar_dsp_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
     "rald_op_gemm_nt": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
                                 c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "rald_op_gemm_nt2": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,

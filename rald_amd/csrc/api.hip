@@ -4,6 +4,7 @@
 
 #include "ae.h"
 #include "dit.h"
+#include "radar_dsp.h"
 
 using namespace rald;
 
@@ -238,6 +239,32 @@ int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t 
                             void* stream) {
     return radar_cube_prepare(raw, batch, R, A, E, raw_channels, tgt_A, tgt_E, norm_intensity, max_intensity, norm_dopp, max_dopp, out,
                               (hipStream_t)stream);
+}
+
+// ---- radar front end: ADC frames -> RAEIVV cubes (radar_dsp.hip) ---------------------------------
+struct rald_radar_dsp { RadarDsp* impl; };
+int rald_radar_dsp_create(const rald_radar_dsp_config* cfg, const int32_t* tx_layout, const int32_t* rx_layout, const double* vbins,
+                          int32_t n_vbins, rald_radar_dsp** out) {
+    RALD_CHECK(cfg && out, "rald_radar_dsp_create: null argument");
+    RadarDsp* impl = nullptr;
+    RALD_TRY(radar_dsp_create(*cfg, tx_layout, rx_layout, vbins, n_vbins, &impl));
+    *out = new rald_radar_dsp{impl};
+    return 0;
+}
+void rald_radar_dsp_destroy(rald_radar_dsp* h) {
+    if (!h) return;
+    (void)hipDeviceSynchronize();
+    delete h->impl;
+    delete h;
+}
+int64_t rald_radar_dsp_workspace_bytes(const rald_radar_dsp_config* cfg, int32_t batch) {
+    if (!cfg || batch < 1 || radar_dsp_check_sizes(*cfg)) return -1;
+    return radar_dsp_workspace_bytes(*cfg, batch);
+}
+int rald_radar_dsp_run(const rald_radar_dsp* h, const void* frames, int32_t input_kind, int32_t batch, float* out, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+    RALD_CHECK(h, "rald_radar_dsp_run: null handle");
+    return radar_dsp_run(*h->impl, frames, input_kind, batch, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- query generation + refine --------------------------------------------------

@@ -87,3 +87,36 @@ def structured_queries(batch: int, n_queries: int, seed: int = 3032) -> torch.Te
         q[b, n4 + n4 // 3:n4 + 2 * (n4 // 3), 1] = -0.5
         q[b, n4 + 2 * (n4 // 3):2 * n4, 2] = 1.0
     return q
+
+
+# AWR1843 layout of the reference's config/antenna_array.txt: rows {data index, azimuth, elevation} in half wavelengths
+AWR1843_TX = ((0, 0, 0), (2, 2, 1), (1, 4, 0))
+AWR1843_RX = ((0, 0, 0), (1, 1, 0), (2, 2, 0), (3, 3, 0))
+
+
+def radar_adc(batch: int, seed: int = 5151, ntx: int = 3, nrx: int = 4, n_chirps: int = 128, n_samples: int = 128, n_targets: int = 4,
+              tx=AWR1843_TX, rx=AWR1843_RX) -> torch.Tensor:
+    """Raw ADC frames int16 [B, ntx, nrx, n_chirps, n_samples, 2] (I, Q; dataset_preprocessor/radar.py:64-70): complex Gaussian
+    noise (sigma 40 counts) on a DC offset, plus `n_targets` point targets per frame.  A target is a complex tone with a range beat
+    (cycles per sample), a Doppler phase per chirp (including the TDM slot of its transmitter) and the phase of each virtual
+    element, exp(i pi (az sin(theta) cos(phi) + el sin(phi))), at amplitudes of 150-1500 counts."""
+    g = torch.Generator("cpu").manual_seed(seed)
+    s = torch.arange(n_samples, dtype=torch.float64)
+    c = torch.arange(n_chirps, dtype=torch.float64)
+    frames = []
+    for _ in range(batch):
+        dc = (torch.rand(2, generator=g, dtype=torch.float64) - 0.5) * 120
+        x = torch.randn([ntx, nrx, n_chirps, n_samples, 2], generator=g, dtype=torch.float64) * 40 + dc
+        for _ in range(n_targets):
+            fr, fd, amp, th, ph = torch.rand(5, generator=g, dtype=torch.float64).tolist()
+            fr, fd = 0.08 + 0.35 * fr, fd - 0.5                     # range beat in the uncropped bins; Doppler anywhere
+            amp, th, ph = 150 + 1350 * amp, (th - 0.5) * 2.4, (ph - 0.5) * 0.6
+            for t_idx, taz, tel in tx:
+                for r_idx, raz, rel in rx:
+                    ang = torch.pi * ((taz + raz) * torch.sin(torch.tensor(th)) * torch.cos(torch.tensor(ph)) +
+                                      (tel + rel) * torch.sin(torch.tensor(ph)))
+                    phase = 2 * torch.pi * (fr * s[None, :] + fd * (c[:, None] + t_idx / ntx)) + ang
+                    x[t_idx, r_idx, ..., 0] += amp * torch.cos(phase)
+                    x[t_idx, r_idx, ..., 1] += amp * torch.sin(phase)
+        frames.append(x.round().clamp(-32768, 32767).to(torch.int16))
+    return torch.stack(frames)
