@@ -294,6 +294,34 @@ int rald_radar_dsp_run(const rald_radar_dsp* h, const void* frames, int32_t inpu
                        int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Helper points: RAEIVV intensity cubes -> CFAR query points (dataset_preprocessor/cache_test_cfar.py:68-93:
+ * rae_interpo, weighted_allocation, RA2DDetectorTensor, cube_idx2coord, filter_points_polar)
+ * ---------------------------------------------------------------------------------------- */
+typedef struct rald_radar_points_config {
+    int32_t in_r, in_a, in_e, in_channels;   /* source cube; channel 0 is read */
+    int32_t tgt_r, tgt_a, tgt_e;             /* trilinear target (align_corners=False); tgt_a * tgt_e <= 32768 */
+    int64_t num_points;                      /* 1 .. tgt_r*tgt_a*tgt_e (and <= INT32_MAX) */
+} rald_radar_points_config;
+typedef struct rald_radar_points rald_radar_points;
+/* axis_r / axis_a / axis_e: float32 coordinate of each target index (tgt_r / tgt_a / tgt_e entries: range in m, azimuth and
+ * elevation in degrees); keep_r / keep_a / keep_e: nonzero where that coordinate passes the FOV filter. */
+int rald_radar_points_create(const rald_radar_points_config* cfg, const float* axis_r, const float* axis_a, const float* axis_e,
+                             const uint8_t* keep_r, const uint8_t* keep_a, const uint8_t* keep_e, rald_radar_points** out);
+void rald_radar_points_destroy(rald_radar_points* h);
+/* device workspace rald_radar_points_run needs for `batch` frames (host arithmetic; -1 on a bad configuration) */
+int64_t rald_radar_points_workspace_bytes(const rald_radar_points_config* cfg, int32_t batch);
+/* cubes fp32 [batch][in_r][in_a][in_e][in_channels].  Per frame, num_points voxels of the upsampled intensity are chosen: slice r
+ * gets floor(num * s_r / sum s) (in double; the surplus to the first slice of largest sum s_r), and takes its largest values, ties
+ * at the k-th value by lowest flat index a * tgt_e + e.  Output order: slices ascending, then value descending, then flat index
+ * ascending.  points [batch][num_points][3] polar (r, az deg, el deg) of the chosen voxels the keep masks pass, compacted: the
+ * first counts[b] rows are valid.  counts[b] = -1 when the frame's total is not positive and finite, -2 when a slice would need
+ * more points than it has voxels; the other frames are still written.  peaks [batch][num_points][3] int32 (r, a, e) and
+ * intensities [batch][num_points], before the filter and in output order, are optional (NULL).  A frame's output does not depend
+ * on the batch. */
+int rald_radar_points_run(const rald_radar_points* h, const float* cubes, int32_t batch, float* points, int32_t* counts, int32_t* peaks,
+                          float* intensities, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel-level entry points (what the parity tests and microbenchmarks drive directly)
  * ---------------------------------------------------------------------------------------- */
 /* C[b][m][n] = alpha * sum_k A[b][m][k]*B[b][n][k] (+bias[n]); A,B bf16 (K contiguous).

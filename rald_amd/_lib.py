@@ -38,6 +38,11 @@ class RadarDspConfig(C.Structure):
                 ("crop_high", C.c_double)]
 
 
+class RadarPointsConfig(C.Structure):
+    _fields_ = [("in_r", c_int), ("in_a", c_int), ("in_e", c_int), ("in_channels", c_int), ("tgt_r", c_int), ("tgt_a", c_int),
+                ("tgt_e", c_int), ("num_points", C.c_int64)]
+
+
 # name -> (restype, argtypes); everything include/rald_hip.h declares
 SIGNATURES = {
     "rald_last_error": (c_char_p, []),
@@ -103,6 +108,11 @@ SIGNATURES = {
     "rald_radar_dsp_destroy": (None, [c_void_p]),
     "rald_radar_dsp_workspace_bytes": (c_i64, [C.POINTER(RadarDspConfig), c_int]),
     "rald_radar_dsp_run": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_radar_points_create": (c_int, [C.POINTER(RadarPointsConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         C.POINTER(c_void_p)]),
+    "rald_radar_points_destroy": (None, [c_void_p]),
+    "rald_radar_points_workspace_bytes": (c_i64, [C.POINTER(RadarPointsConfig), c_int]),
+    "rald_radar_points_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "rald_op_gemm_nt": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
                                 c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "rald_op_gemm_nt2": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,

@@ -5,6 +5,7 @@
 #include "ae.h"
 #include "dit.h"
 #include "radar_dsp.h"
+#include "radar_points.h"
 
 using namespace rald;
 
@@ -265,6 +266,32 @@ int rald_radar_dsp_run(const rald_radar_dsp* h, const void* frames, int32_t inpu
                        int64_t workspace_bytes, void* stream) {
     RALD_CHECK(h, "rald_radar_dsp_run: null handle");
     return radar_dsp_run(*h->impl, frames, input_kind, batch, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- helper points: intensity cubes -> CFAR query points (radar_points.hip) -----------------------
+struct rald_radar_points { RadarPoints* impl; };
+int rald_radar_points_create(const rald_radar_points_config* cfg, const float* axis_r, const float* axis_a, const float* axis_e,
+                             const uint8_t* keep_r, const uint8_t* keep_a, const uint8_t* keep_e, rald_radar_points** out) {
+    RALD_CHECK(cfg && out, "rald_radar_points_create: null argument");
+    RadarPoints* impl = nullptr;
+    RALD_TRY(radar_points_create(*cfg, axis_r, axis_a, axis_e, keep_r, keep_a, keep_e, &impl));
+    *out = new rald_radar_points{impl};
+    return 0;
+}
+void rald_radar_points_destroy(rald_radar_points* h) {
+    if (!h) return;
+    (void)hipDeviceSynchronize();
+    delete h->impl;
+    delete h;
+}
+int64_t rald_radar_points_workspace_bytes(const rald_radar_points_config* cfg, int32_t batch) {
+    if (!cfg || batch < 1 || radar_points_check_config(*cfg)) return -1;
+    return radar_points_workspace_bytes(*cfg, batch);
+}
+int rald_radar_points_run(const rald_radar_points* h, const float* cubes, int32_t batch, float* points, int32_t* counts, int32_t* peaks,
+                          float* intensities, void* workspace, int64_t workspace_bytes, void* stream) {
+    RALD_CHECK(h, "rald_radar_points_run: null handle");
+    return radar_points_run(*h->impl, cubes, batch, points, counts, peaks, intensities, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- query generation + refine --------------------------------------------------
