@@ -322,6 +322,54 @@ int rald_radar_points_run(const rald_radar_points* h, const float* cubes, int32_
                           float* intensities, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LiDAR front end: raw scans -> cropped points (dataset_preprocessor/lidar.py:123-194), voxels (datasets/utils/voxelize.py, spconv
+ * Point2VoxelCPU3d) and occupancy queries (datasets/aligned_coloradar/Coloradar_dataset.py:70-135, :237-418).  Frames are packed
+ * [total][F] float32 with HOST int64 offsets [batch + 1] (offsets[0] = 0, non-decreasing, frames below 2^31 points), checked before
+ * any launch.  A frame's outputs do not depend on the batch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct rald_lidar_config {
+    double pc_range[6];                      /* lo x y z, hi x y z (dataset.lidar.pc_range; r / az / el in view-cone mode) */
+    double voxel_size[3];                    /* > 0; grid = round((hi - lo) / voxel_size), at most 2^31 - 1 cells in all */
+    int32_t max_points_per_voxel, max_voxels, num_point_features;
+    int32_t view_cone_mode, norm_anisotropy, norm_isotropy;
+    double extrinsic[16];                    /* T_RADAR_TO_LIDAR, row-major (dataset_preprocessor/constants.py:602) */
+    double fov[6];                           /* r lo, r hi, az lo, az hi, el lo, el hi in degrees, inclusive (lidar.py:172-177) */
+} rald_lidar_config;
+typedef struct rald_lidar rald_lidar;
+/* rejects non-positive voxel sizes, empty axes and grids over 2^31 cells */
+int rald_lidar_create(const rald_lidar_config* cfg, rald_lidar** out);
+void rald_lidar_destroy(rald_lidar* h);
+/* device workspace any of the three calls below needs for `batch` frames of `total_points` points (host arithmetic; -1 on a bad
+ * configuration) */
+int64_t rald_lidar_workspace_bytes(const rald_lidar_config* cfg, int32_t batch, int64_t total_points);
+/* lidar.py:170-182 per point, in float64: remove_empty_points, [x y z 1] @ T.T, cartesian2polar, filter_points_polar, polar2cartesian,
+ * rounded once to float32.  points [total][in_stride] (x, y, z first); out [total][3]: frame b's survivors, in input order, at rows
+ * offsets[b] .. offsets[b] + counts[b]. */
+int rald_lidar_crop(const rald_lidar* h, const float* points, int32_t in_stride, const int64_t* offsets, int32_t batch, float* out,
+                    int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+/* Point2VoxelCPU3d (voxelize.py:559-576): cell c = floor((p - lo) / v) in float32, outside when c < 0 or c >= grid; voxels are numbered
+ * by their first point; a new voxel beyond max_voxels is dropped, points of kept voxels still count; a voxel keeps its first
+ * max_points_per_voxel points in input order.  points [total][F]; counts [batch] (nullable): frame b is its first
+ * min(counts[b], offsets[b+1] - offsets[b]) rows.  to_polar: first convert the points to float32 polar as numpy's cartesian2polar
+ * does on float32 (Coloradar_dataset.py:87-88; F must be 3) into polar_out [total][3].  Outputs per frame b, rows past
+ * voxel_counts[b] unspecified: voxels [batch][max_voxels][max_points_per_voxel][F] zero-filled (nullable), coords
+ * [batch][max_voxels][3] int32 in z, y, x order, num_points [batch][max_voxels], kept_keys [batch][max_voxels] the linear cells
+ * (x * Gy + y) * Gz + z of the kept voxels in ascending order (the input of rald_lidar_queries). */
+int rald_lidar_voxelize(const rald_lidar* h, const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch,
+                        int32_t to_polar, float* polar_out, float* voxels, int32_t* coords, int32_t* num_points, int32_t* kept_keys,
+                        int32_t* voxel_counts, void* workspace, int64_t workspace_bytes, void* stream);
+/* transform_voxels_to_query_points + get_empty_voxel_centers + norm_points (Coloradar_dataset.py:237-294, :335-418) from drawn inputs.
+ * points [total][3] (what the samples index), sample_idx [batch][S]; in-voxel rows s < in_num: centre(coords[voxel_idx]) +
+ * float32(u_in), label 1; the other rows: centre of the empty_rank-th empty cell in row-major (x, y, z) order + float32(u_out),
+ * label 0.  u_in [batch][in_num][3], voxel_idx [batch][in_num], u_out [batch][S - in_num][3], empty_rank [batch][S - in_num].  Out:
+ * lidar_points, query_points [batch][S][3] normalised, query_labels [batch][S] float32.  An index out of range gives NaN rows. */
+int rald_lidar_queries(const rald_lidar* h, const float* points, const int64_t* offsets, int32_t batch, int32_t num_samples,
+                       int32_t in_num, const int64_t* sample_idx, const double* u_in, const int64_t* voxel_idx, const double* u_out,
+                       const int64_t* empty_rank, const int32_t* coords, const int32_t* kept_keys, const int32_t* voxel_counts,
+                       float* lidar_points, float* query_points, float* query_labels, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel-level entry points (what the parity tests and microbenchmarks drive directly)
  * ---------------------------------------------------------------------------------------- */
 /* C[b][m][n] = alpha * sum_k A[b][m][k]*B[b][n][k] (+bias[n]); A,B bf16 (K contiguous).

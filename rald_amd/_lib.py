@@ -43,6 +43,12 @@ class RadarPointsConfig(C.Structure):
                 ("tgt_e", c_int), ("num_points", C.c_int64)]
 
 
+class LidarConfig(C.Structure):
+    _fields_ = [("pc_range", C.c_double * 6), ("voxel_size", C.c_double * 3), ("max_points_per_voxel", c_int), ("max_voxels", c_int),
+                ("num_point_features", c_int), ("view_cone_mode", c_int), ("norm_anisotropy", c_int), ("norm_isotropy", c_int),
+                ("extrinsic", C.c_double * 16), ("fov", C.c_double * 6)]
+
+
 # name -> (restype, argtypes); everything include/rald_hip.h declares
 SIGNATURES = {
     "rald_last_error": (c_char_p, []),
@@ -113,6 +119,14 @@ SIGNATURES = {
     "rald_radar_points_destroy": (None, [c_void_p]),
     "rald_radar_points_workspace_bytes": (c_i64, [C.POINTER(RadarPointsConfig), c_int]),
     "rald_radar_points_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_lidar_create": (c_int, [C.POINTER(LidarConfig), C.POINTER(c_void_p)]),
+    "rald_lidar_destroy": (None, [c_void_p]),
+    "rald_lidar_workspace_bytes": (c_i64, [C.POINTER(LidarConfig), c_int, c_i64]),
+    "rald_lidar_crop": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_lidar_voxelize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_lidar_queries": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "rald_op_gemm_nt": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
                                 c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "rald_op_gemm_nt2": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,

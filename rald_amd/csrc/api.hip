@@ -4,6 +4,7 @@
 
 #include "ae.h"
 #include "dit.h"
+#include "lidar.h"
 #include "radar_dsp.h"
 #include "radar_points.h"
 
@@ -292,6 +293,47 @@ int rald_radar_points_run(const rald_radar_points* h, const float* cubes, int32_
                           float* intensities, void* workspace, int64_t workspace_bytes, void* stream) {
     RALD_CHECK(h, "rald_radar_points_run: null handle");
     return radar_points_run(*h->impl, cubes, batch, points, counts, peaks, intensities, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- LiDAR front end: scans -> voxels -> occupancy queries (lidar.hip) ----------------------------
+struct rald_lidar { Lidar impl; };
+int rald_lidar_create(const rald_lidar_config* cfg, rald_lidar** out) {
+    RALD_CHECK(cfg && out, "rald_lidar_create: null argument");
+    Lidar impl;
+    RALD_TRY(lidar_check_config(*cfg, &impl));
+    *out = new rald_lidar{impl};
+    return 0;
+}
+void rald_lidar_destroy(rald_lidar* h) {
+    if (!h) return;
+    (void)hipDeviceSynchronize();
+    delete h;
+}
+int64_t rald_lidar_workspace_bytes(const rald_lidar_config* cfg, int32_t batch, int64_t total_points) {
+    Lidar impl;
+    if (!cfg || batch < 1 || total_points < 0 || lidar_check_config(*cfg, &impl)) return -1;
+    return lidar_workspace_bytes(impl, batch, total_points);
+}
+int rald_lidar_crop(const rald_lidar* h, const float* points, int32_t in_stride, const int64_t* offsets, int32_t batch, float* out,
+                    int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+    RALD_CHECK(h, "rald_lidar_crop: null handle");
+    return lidar_crop(h->impl, points, in_stride, offsets, batch, out, counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int rald_lidar_voxelize(const rald_lidar* h, const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch,
+                        int32_t to_polar, float* polar_out, float* voxels, int32_t* coords, int32_t* num_points, int32_t* kept_keys,
+                        int32_t* voxel_counts, void* workspace, int64_t workspace_bytes, void* stream) {
+    RALD_CHECK(h, "rald_lidar_voxelize: null handle");
+    return lidar_voxelize(h->impl, points, offsets, counts, batch, to_polar, polar_out, voxels, coords, num_points, kept_keys, voxel_counts,
+                          workspace, workspace_bytes, (hipStream_t)stream);
+}
+int rald_lidar_queries(const rald_lidar* h, const float* points, const int64_t* offsets, int32_t batch, int32_t num_samples,
+                       int32_t in_num, const int64_t* sample_idx, const double* u_in, const int64_t* voxel_idx, const double* u_out,
+                       const int64_t* empty_rank, const int32_t* coords, const int32_t* kept_keys, const int32_t* voxel_counts,
+                       float* lidar_points, float* query_points, float* query_labels, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+    RALD_CHECK(h, "rald_lidar_queries: null handle");
+    return lidar_queries(h->impl, points, offsets, batch, num_samples, in_num, sample_idx, u_in, voxel_idx, u_out, empty_rank, coords,
+                         kept_keys, voxel_counts, lidar_points, query_points, query_labels, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- query generation + refine --------------------------------------------------

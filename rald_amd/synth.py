@@ -4,6 +4,7 @@ the oracle tests, the GPU parity tests and bench.py see identical tensors.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -120,3 +121,39 @@ def radar_adc(batch: int, seed: int = 5151, ntx: int = 3, nrx: int = 4, n_chirps
                     x[t_idx, r_idx, ..., 1] += amp * torch.sin(phase)
         frames.append(x.round().clamp(-32768, 32767).to(torch.int16))
     return torch.stack(frames)
+
+
+def lidar_scan(batch: int, seed: int = 2301, n: int = 65536) -> list:
+    """Raw LiDAR scans, float32 [n, 4] (x, y, z, intensity in the sensor frame; the layout of lidar/pointclouds/*.bin) per frame,
+    a list of `batch` numpy arrays.  Rays from the sensor hit a room (walls, floor, ceiling) with boxes in it; the room reaches past
+    the crop range along one axis.  Mixed in, so that every branch of the crop is taken: 6 % all-zero points, rays in every azimuth
+    (a third of them behind the radar once the extrinsic turns the frame about z) and elevations up to +-35 degrees (outside the
+    +-20 degree FOV)."""
+    rng = np.random.default_rng(seed)
+    lo = np.array([-22.0, -7.0, -1.3])          # room box around the sensor; -x is the radar's forward direction
+    hi = np.array([9.0, 6.0, 2.1])
+    out = []
+    for _ in range(batch):
+        boxes = []
+        for _ in range(4):
+            c = np.array([rng.uniform(-14, -2), rng.uniform(-5, 4), -1.3])
+            s = rng.uniform([0.4, 0.4, 0.5], [1.5, 1.5, 1.6])
+            boxes.append((c - s * [1, 1, 0], c + s * [1, 1, 2]))
+        az = rng.uniform(-np.pi, np.pi, n)
+        az = np.where(rng.random(n) < 0.7, rng.uniform(np.pi - 1.4, np.pi + 1.4, n), az)   # more rays toward -x
+        el = np.deg2rad(np.where(rng.random(n) < 0.8, rng.uniform(-19, 19, n), rng.uniform(-35, 35, n)))
+        d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(d > 0, (hi - 0) / d, np.where(d < 0, (lo - 0) / d, np.inf)).min(axis=1)   # exit of the room
+            for bl, bh in boxes:
+                t1, t2 = (bl - 0) / d, (bh - 0) / d
+                tn = np.minimum(t1, t2).max(axis=1)
+                tf = np.maximum(t1, t2).min(axis=1)
+                hit = (tn <= tf) & (tn > 0)
+                t = np.where(hit & (tn < t), tn, t)
+        p = d * (t * (1 + rng.normal(0, 0.003, n)))[:, None]
+        inten = rng.uniform(0, 60, n)
+        pts = np.concatenate([p, inten[:, None]], axis=1).astype(np.float32)
+        pts[rng.random(n) < 0.06] = 0.0
+        out.append(pts)
+    return out
