@@ -566,7 +566,8 @@ int rald_op_attention_vrow(const void* Q, int64_t ldq, int64_t strideQ, const vo
 /* gradients of rald_op_attention_vrow's O = softmax(Q K^T scale) V per head (torch autograd of CrossAttention,
  * model/models_radar_generation.py:66-75, in the training step engine_generation.py:74-98): dQ, dK, dV bf16 in the layouts of Q, K, V
  * (own leading dimensions and batch strides: column slices of fused buffers are fine).  Two launches, nothing score-shaped in memory.
- * lse_scratch / delta_scratch: fp32 [batch*heads*nq] each.  nq % 128 == 0, nk % 64 == 0. */
+ * lse_scratch / delta_scratch: fp32 [batch*heads*nq] each.  nq % 128 == 0; nk any >= 32 (a last key tile that is not full is masked:
+ * nothing past key nk - 1 is read or written). */
 int rald_op_attention_bwd(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK, const void* V, int64_t ldv,
                           int64_t strideV, const void* O, int64_t ldo, int64_t strideO, const void* dO, int64_t lddo, int64_t strideDO,
                           void* dQ, int64_t lddq, int64_t strideDQ, void* dK, int64_t lddk, int64_t strideDK, void* dV, int64_t lddv, int64_t strideDV,
@@ -577,6 +578,33 @@ int rald_op_gemm_resid_ln(const void* A, int64_t lda, const void* W, int64_t ldw
                           const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps,
                           int32_t M, int32_t K, void* stream);
 int rald_op_cast_bf16(const float* in, void* out_bf16, int64_t n, void* stream);
+/* Set-latent autoencoder training (KLAutoEncoder under autograd, engine_ae.py:33-104; rald_amd/csrc/ae_train.hip).  No float atomics:
+ * reductions over rows go through a caller-owned scratch (16-byte aligned, _scratch_bytes(rows) bytes - pure host arithmetic) and are
+ * summed in a fixed order by a second launch, so results are bit-reproducible.
+ * _ln_affine_bwd: nn.LayerNorm(512) backward, x [rows][512] fp32 (the LN input), dh [rows][512] fp32 (gradient w.r.t. the LN output):
+ *   dx_accum += dx; dx_bf16_out (nullable) = the updated dx_accum as bf16; dgamma_accum / dbeta_accum [512] += sum dh*xhat / sum dh.
+ * _pe_wgrad: PointEmbed.mlp gradient from dY [rows][512] fp32 and the raw points [rows][3] (basis [3][24]): dW_accum [512][51] +=
+ *   dY^T . [sin(p.basis) | cos(p.basis) | p], db_accum [512] += column sums of dY.
+ * _point_features: feat bf16 [n][64] = [sin(p.basis) (24) | cos (24) | p (3) | 0 ...].
+ * _posterior: ml [B*rows][2L] = raw [mean | logvar] -> z [B*rows][L] = mean + exp(0.5 clamp(logvar, -30, 20)) eps, kl [B].
+ * _posterior_bwd: dml [B*rows][2L] = gradient of (z, kl) w.r.t. [mean | logvar] given dz (nullable) and dkl [B] (nullable).
+ * _scale_rows: drop-path residual; exactly one of x_accum (x += s[r / rows_per_sample] * in[r]) and out_bf16 (= s[...] * in[r]).
+ * _softmax_bwd_rows: S [rows][ld] fp32 (already times the softmax scale), dP [rows][ld], delta [rows]: P = softmax of S[r][0..n),
+ *   dS = P (dP - delta[r]) * scale; P (nullable) and dS bf16 [rows][ld], columns n .. ld - 1 zero. */
+int64_t rald_op_ln_affine_bwd_scratch_bytes(int64_t rows);
+int rald_op_ln_affine_bwd(const float* x, const float* dh, const float* gamma, float eps, int64_t rows, float* dx_accum, void* dx_bf16_out,
+                          float* dgamma_accum, float* dbeta_accum, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t rald_op_pe_wgrad_scratch_bytes(int64_t rows);
+int rald_op_pe_wgrad(const float* dY, const float* pts, const float* basis, int64_t rows, float* dW_accum, float* db_accum, void* scratch,
+                     int64_t scratch_bytes, void* stream);
+int rald_op_point_features(const float* pts, const float* basis, void* feat_bf16, int64_t n, void* stream);
+int rald_op_posterior(const float* ml, const float* eps, float* z, float* kl, int32_t B, int32_t rows, int32_t L, void* stream);
+int rald_op_posterior_bwd(const float* dz, const float* dkl, const float* ml, const float* eps, float* dml, int32_t B, int32_t rows, int32_t L,
+                          void* stream);
+int rald_op_scale_rows(const float* in, const float* s, float* x_accum, void* out_bf16, int64_t rows, int32_t cols, int64_t rows_per_sample,
+                       void* stream);
+int rald_op_softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_t rows, int64_t ld, int32_t n, float scale, void* P_bf16,
+                             void* dS_bf16, void* stream);
 
 #ifdef __cplusplus
 }

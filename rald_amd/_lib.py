@@ -203,6 +203,15 @@ SIGNATURES = {
     "rald_op_gemm_resid_ln": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int,
                                       c_float, c_float, c_int, c_int, c_void_p]),
     "rald_op_cast_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_op_ln_affine_bwd_scratch_bytes": (c_i64, [c_i64]),
+    "rald_op_ln_affine_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_op_pe_wgrad_scratch_bytes": (c_i64, [c_i64]),
+    "rald_op_pe_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_op_point_features": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "rald_op_posterior": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "rald_op_posterior_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "rald_op_scale_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p]),
+    "rald_op_softmax_bwd_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -678,6 +678,40 @@ int rald_op_gemm_resid_ln(const void* A, int64_t lda, const void* W, int64_t ldw
     a.g = g; a.b = b; a.gstride = gstride; a.rows_per_group = rows_per_group; a.add_one = add_one; a.eps = eps; a.M = M; a.K = K;
     return gemm_resid_ln(a, (hipStream_t)stream);
 }
+int64_t rald_op_ln_affine_bwd_scratch_bytes(int64_t rows) { return ln_affine_bwd_scratch_bytes(rows); }
+int rald_op_ln_affine_bwd(const float* x, const float* dh, const float* gamma, float eps, int64_t rows, float* dx_accum, void* dx_bf16_out,
+                          float* dgamma_accum, float* dbeta_accum, void* scratch, int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(x && dh && gamma && dx_accum && dgamma_accum && dbeta_accum, "rald_op_ln_affine_bwd: null pointer");
+    return ln_affine_bwd(x, dh, gamma, eps, rows, dx_accum, (bf16*)dx_bf16_out, dgamma_accum, dbeta_accum, (float*)scratch, scratch_bytes,
+                         (hipStream_t)stream);
+}
+int64_t rald_op_pe_wgrad_scratch_bytes(int64_t rows) { return pe_wgrad_scratch_bytes(rows); }
+int rald_op_pe_wgrad(const float* dY, const float* pts, const float* basis, int64_t rows, float* dW_accum, float* db_accum, void* scratch,
+                     int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(dY && pts && basis && dW_accum && db_accum, "rald_op_pe_wgrad: null pointer");
+    return pe_wgrad(dY, pts, basis, rows, dW_accum, db_accum, (float*)scratch, scratch_bytes, (hipStream_t)stream);
+}
+int rald_op_point_features(const float* pts, const float* basis, void* feat_bf16, int64_t n, void* stream) {
+    RALD_CHECK(pts && basis && feat_bf16, "rald_op_point_features: null pointer");
+    return point_features(pts, basis, (bf16*)feat_bf16, n, (hipStream_t)stream);
+}
+int rald_op_posterior(const float* ml, const float* eps, float* z, float* kl, int32_t B, int32_t rows, int32_t L, void* stream) {
+    RALD_CHECK(ml && eps && z && kl && B > 0 && rows > 0 && L > 0, "rald_op_posterior: bad arguments");
+    return posterior(ml, eps, nullptr, nullptr, z, kl, B, rows, L, (hipStream_t)stream);
+}
+int rald_op_posterior_bwd(const float* dz, const float* dkl, const float* ml, const float* eps, float* dml, int32_t B, int32_t rows, int32_t L,
+                          void* stream) {
+    return posterior_bwd(dz, dkl, ml, eps, dml, B, rows, L, (hipStream_t)stream);
+}
+int rald_op_scale_rows(const float* in, const float* s, float* x_accum, void* out_bf16, int64_t rows, int32_t cols, int64_t rows_per_sample,
+                       void* stream) {
+    RALD_CHECK(!x_accum != !out_bf16, "rald_op_scale_rows: exactly one of x_accum / out_bf16");
+    return scale_rows(in, s, x_accum, (bf16*)out_bf16, rows, cols, rows_per_sample, (hipStream_t)stream);
+}
+int rald_op_softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_t rows, int64_t ld, int32_t n, float scale, void* P_bf16,
+                             void* dS_bf16, void* stream) {
+    return softmax_bwd_rows(S, dP, delta, rows, ld, n, scale, (bf16*)P_bf16, (bf16*)dS_bf16, (hipStream_t)stream);
+}
 int rald_op_cast_bf16(const float* in, void* out_bf16, int64_t n, void* stream) {
     RALD_CHECK(in && out_bf16, "rald_op_cast_bf16: null pointer");
     return cast_f32_bf16(in, (bf16*)out_bf16, n, (hipStream_t)stream);

@@ -14,6 +14,11 @@
 // address; row fragments (A operand = tile rows) from a "natural" image, column gathers (A operand = the tile transposed) through
 // ds_read_b64_tr_b16 from a second image of the same tile with the transposed-read swizzle.  P and dS are rounded to bf16 for the
 // MFMAs, as the unfused form stored them.  Gradient parity: tests/test_gpu_train_ops.py against autograd in fp32.
+//
+// Key tail (TAIL = nk % 64 != 0, e.g. the autoencoder's mix attention over 10 000 points): staged key rows are clamped to nk - 1
+// (nothing past the last key is read), the scores of keys >= nk in the last tile are set to -1e30 before the softmax (their
+// probabilities and score gradients are exactly 0), and the key side writes only rows < nk.  nk % 64 == 0 launches TAIL = false:
+// the code those shapes ran before, unchanged.
 #include "common.h"
 #include "kernels.h"
 
@@ -55,6 +60,7 @@ __device__ __forceinline__ bf16x8 cut8(const f32x16& v, int s) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------- query side
+template <bool TAIL>
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnBwdArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 3 * TB];     // [buf][K natural | K transposed-read | V natural]
     const int lane = threadIdx.x & 63;
@@ -79,12 +85,14 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnBwdArgs a) {
         unsigned char* base = smem + buf * 3 * TB;
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            __builtin_amdgcn_global_load_lds((glb_void*)(gKn[p] + (int64_t)j0 * a.ldk), (lds_void*)(base + (wave + 4 * p) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_void*)(gKt[p] + (int64_t)j0 * a.ldk), (lds_void*)(base + TB + (wave + 4 * p) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_void*)(gVn[p] + (int64_t)j0 * a.ldv), (lds_void*)(base + 2 * TB + (wave + 4 * p) * 1024), 16, 0, 0);
+            const int row = 8 * (wave + 4 * p) + lr;
+            const int64_t j = TAIL ? (int64_t)(min(j0 + row, a.nk - 1) - row) : (int64_t)j0;      // clamp past-the-end key rows
+            __builtin_amdgcn_global_load_lds((glb_void*)(gKn[p] + j * a.ldk), (lds_void*)(base + (wave + 4 * p) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_void*)(gKt[p] + j * a.ldk), (lds_void*)(base + TB + (wave + 4 * p) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_void*)(gVn[p] + j * a.ldv), (lds_void*)(base + 2 * TB + (wave + 4 * p) * 1024), 16, 0, 0);
         }
     };
-    const int ntiles = a.nk >> 6;
+    const int ntiles = TAIL ? (a.nk + 63) >> 6 : a.nk >> 6;
     stage(0, 0);
 
     bf16x8 qf[4], dof[4];
@@ -125,6 +133,14 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnBwdArgs a) {
             for (int i = 0; i < 16; ++i) st[u][i] = 0.f;
 #pragma unroll
             for (int s = 0; s < 4; ++s) st[u] = mfma32(frag_row(sKn, 32 * u + r, s, hf), qf[s], st[u]);
+        }
+        if (TAIL && (it == ntiles - 1 || it == 2 * ntiles - 1)) {      // last key tile: element i of st[u] <-> key 32u + 8(i>>2) + 4hf + (i&3)
+            const int kb = (ntiles - 1) * 64 + 4 * hf;
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if (kb + 32 * u + 8 * (i >> 2) + (i & 3) >= a.nk) st[u][i] = -1e30f;
         }
         if (it < ntiles) {                                      // pass 1: log-sum-exp of this lane's query (exp2 units)
             float mx = st[0][0];
@@ -187,6 +203,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnBwdArgs a) {
 
 // ------------------------------------------------------------------------------------------------- key side
 constexpr int KV_STAGE = 4 * TB + 512;                          // Q natural | Q transposed-read | dO natural | dO transposed-read | lse[64] | delta[64]
+template <bool TAIL>
 __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_kv[];
     unsigned char* smem = smem_kv;
@@ -197,8 +214,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnBwdArgs a) {
     const int bh = blockIdx.x / nx, kblk = blockIdx.x - bh * nx;
     const int h = bh % a.heads, b = bh / a.heads;
     int key0 = (kblk * 4 + wave) * 32;
-    const bool active = key0 < a.nk;
-    if (!active) key0 = a.nk - 32;
+    const bool active = TAIL ? key0 + r < a.nk : key0 < a.nk;        // TAIL: per lane (key key0 + r); rows past nk read row nk - 1
+    if (!TAIL && !active) key0 = a.nk - 32;
+    const int krow = TAIL ? min(key0 + r, a.nk - 1) : key0 + r;
     const float c = a.scale * 1.4426950408889634f;
 
     const bf16 *gQn[2], *gQt[2], *gDn[2], *gDt[2];
@@ -228,8 +246,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnBwdArgs a) {
 
     bf16x8 kf[4], vf[4];
     {
-        const bf16* kp = a.K + (int64_t)b * a.sk + (int64_t)(key0 + r) * a.ldk + h * 64 + 8 * hf;
-        const bf16* vp = a.V + (int64_t)b * a.sv + (int64_t)(key0 + r) * a.ldv + h * 64 + 8 * hf;
+        const bf16* kp = a.K + (int64_t)b * a.sk + (int64_t)krow * a.ldk + h * 64 + 8 * hf;
+        const bf16* vp = a.V + (int64_t)b * a.sv + (int64_t)krow * a.ldv + h * 64 + 8 * hf;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             kf[s] = *reinterpret_cast<const bf16x8*>(kp + 16 * s);
@@ -302,7 +320,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnBwdArgs a) {
 int attention_bwd_d64(const AttnBwdArgs& a, hipStream_t st) {
     RALD_CHECK(a.Q && a.K && a.V && a.O && a.dO && a.dQ && a.dK && a.dV && a.lse && a.delta, "attention_bwd: null argument");
     RALD_CHECK(a.nq > 0 && a.nk > 0 && a.heads > 0 && a.batch > 0, "attention_bwd: empty problem");
-    RALD_CHECK(a.nq % 128 == 0 && a.nk % 64 == 0, "attention_bwd: nq must be a multiple of 128 and nk of 64");
+    RALD_CHECK(a.nq % 128 == 0, "attention_bwd: nq must be a multiple of 128");
+    RALD_CHECK(a.nk % 64 == 0 || a.nk >= 32, "attention_bwd: a key count that is not a multiple of 64 must be at least 32");
     RALD_CHECK(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.lddo % 8 == 0 && a.lddq % 4 == 0 && a.lddk % 4 == 0 && a.lddv % 4 == 0,
                "attention_bwd: leading dimensions must be multiples of 8 elements (inputs) / 4 elements (outputs)");
     RALD_CHECK(a.ldq >= a.heads * 64 && a.ldk >= a.heads * 64 && a.ldv >= a.heads * 64 && a.ldo >= a.heads * 64 && a.lddo >= a.heads * 64 &&
@@ -315,11 +334,17 @@ int attention_bwd_d64(const AttnBwdArgs& a, hipStream_t st) {
     RALD_CHECK((int64_t)a.batch * a.heads * (a.nq / 128) < (1ll << 31) && (int64_t)a.batch * a.heads * cdiv(a.nk, 128) < (1ll << 31), "attention_bwd: too many workgroups");
     static bool attr_set = false;
     if (!attr_set) {
-        RALD_HIP(hipFuncSetAttribute((const void*)attn_bwd_kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KV_STAGE));
+        RALD_HIP(hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KV_STAGE));
+        RALD_HIP(hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KV_STAGE));
         attr_set = true;
     }
-    hipLaunchKernelGGL(attn_bwd_q_kernel, dim3(a.batch * a.heads * (a.nq / 128)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(attn_bwd_kv_kernel, dim3(a.batch * a.heads * cdiv(a.nk, 128)), dim3(256), 2 * KV_STAGE, st, a);
+    if (a.nk % 64 == 0) {
+        hipLaunchKernelGGL(attn_bwd_q_kernel<false>, dim3(a.batch * a.heads * (a.nq / 128)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, dim3(a.batch * a.heads * cdiv(a.nk, 128)), dim3(256), 2 * KV_STAGE, st, a);
+    } else {
+        hipLaunchKernelGGL(attn_bwd_q_kernel<true>, dim3(a.batch * a.heads * (a.nq / 128)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(attn_bwd_kv_kernel<true>, dim3(a.batch * a.heads * cdiv(a.nk, 128)), dim3(256), 2 * KV_STAGE, st, a);
+    }
     RALD_HIP(hipGetLastError());
     return 0;
 }

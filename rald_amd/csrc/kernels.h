@@ -168,6 +168,18 @@ struct AttnBwdArgs {
 };
 int attention_bwd_d64(const AttnBwdArgs& a, hipStream_t st);
 
+// ---------------------------------------------------------------- ae_train.hip (autoencoder training: no float atomics)
+int64_t ln_affine_bwd_scratch_bytes(int64_t rows);
+int ln_affine_bwd(const float* x, const float* dh, const float* g, float eps, int64_t rows, float* dx, bf16* dx_bf16, float* dgamma, float* dbeta,
+                  float* scratch, int64_t scratch_bytes, hipStream_t st);
+int64_t pe_wgrad_scratch_bytes(int64_t rows);
+int pe_wgrad(const float* dY, const float* pts, const float* basis, int64_t rows, float* dW, float* db, float* scratch, int64_t scratch_bytes,
+             hipStream_t st);
+int posterior_bwd(const float* dz, const float* dkl, const float* ml, const float* eps, float* dml, int B, int rows, int L, hipStream_t st);
+int scale_rows(const float* in, const float* s, float* x_accum, bf16* out_bf16, int64_t rows, int cols, int64_t rows_per_sample, hipStream_t st);
+int softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_t rows, int64_t ld, int n, float scale, bf16* P, bf16* dS,
+                     hipStream_t st);
+
 // ---------------------------------------------------------------- attn_small.hip (<= 2048 rows: fused per-head sub-blocks)
 // part[h][row][512] = (softmax(q_h k_h^T) v_h) . Wo[:, 64h:64h+64]^T  for the fused q|k|v buffer of a self-attention
 int attn_self_proj(const bf16* qkv, int64_t ld, const bf16* Wo, float* part, int NL, int heads, int batch, hipStream_t st, bool part_f16 = false);

@@ -2,7 +2,8 @@
 ..., looked up via ``models_ae.__dict__[name](N=...)``, main_generation.py:110), same
 ``KLAutoEncoder.encode / decode / forward`` signatures and return values (:351-432) and the same
 ``state_dict`` keys.  Arithmetic runs in librald_hip.so (include/rald_hip.h); no PyTorch compute
-path exists.
+path exists.  Under ``train()`` + grad mode ``forward`` is differentiable (``_AeForwardFn`` over rald_amd.train_ae), so the
+reference's stage-1 loop (engine_ae.py:33-104) trains the module as written.
 
 Scope: query_type='mix' (the shipped config, configs/ae/*cone.yml:85) and 'learnable' (:325-326,
 :378-379); query_type='point' needs torch_cluster.fps (a CUDA extension that is neither vendored
@@ -86,9 +87,86 @@ class KLAutoEncoder(_HipBacked):
         return h.decode_queries(self._context(x), queries).unsqueeze(-1)
 
     def forward(self, pc, queries):
+        # Route like EDMPrecond.forward: model.train() + grad mode + trainable parameters = the stage-1 training step
+        # (engine_ae.py:51, :73-104); eval() / no_grad = the inference path below, unchanged.
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._train_forward(pc, queries)
         kl, x = self.encode(pc)
         o = self.decode(x, queries).squeeze(-1)
         return {'logits': o, 'kl': kl}
+
+    def _train_forward(self, pc, queries, masks=None, eps=None):
+        """The differentiable forward (_AeForwardFn).  ``masks`` (1 + 2*depth drop-path scales [B] for 'mix', 2*depth for 'learnable')
+        and ``eps`` [B, M, latent_dim] default to the reference's draws: timm's DropPath on the device RNG in forward order, then
+        torch.randn on the CPU global RNG (:153)."""
+        if pc.requires_grad or queries.requires_grad:
+            raise NotImplementedError("gradients with respect to the points / the query points are not built (the reference trains the "
+                                      "parameters only)")
+        if self.dim != 512 or self.heads * self.dim_head != 512 or self.dim_head != 64 or self.num_latents != 512 \
+                or self.latent_dim < 32 or self.latent_dim % 32:
+            raise NotImplementedError("the differentiable autoencoder covers dim 512, 8 x 64 heads, 512 latents and latent_dim a multiple "
+                                      "of 32 (kl_d512_m512_l32_mix and its 'learnable' twin); use eval() / no_grad for the others")
+        if pc.dim() != 3 or queries.dim() != 3 or pc.shape[0] != queries.shape[0] or pc.shape[-1] != 3 or queries.shape[-1] != 3:
+            raise RuntimeError(f"pc must be [B,N,3] and queries [B,Q,3]; got {tuple(pc.shape)} and {tuple(queries.shape)}")
+        tr = self._autograd_trainers()
+        B = pc.shape[0]
+        dev = self._device()
+        if masks is None:
+            from .train_ae import drop_path_masks
+            masks = drop_path_masks(B, tr["ae"].n_masks, dev)
+        if eps is None:
+            eps = torch.randn(B, self.num_latents, self.latent_dim)
+        self._last_drop_path_masks = masks
+        params = [p for _, p in self.named_parameters()]
+        logits, kl = _AeForwardFn.apply(self, pc.to(device=dev, dtype=torch.float32), queries.to(device=dev, dtype=torch.float32), eps,
+                                        masks, *params)
+        return {'logits': logits, 'kl': kl}
+
+    def _autograd_trainers(self):
+        """As EDMPrecond._autograd_trainers: shadow Parameters sharing the real parameters' storage (the trainer accumulates into
+        their `.grad`; the real `.grad`s belong to autograd), rebuilt when a parameter's storage moved, bf16 copies refreshed when a
+        parameter's version changed (an optimizer step)."""
+        from .train_ae import AeTrainer
+        named = list(self.named_parameters())
+        ptrs = tuple(p.data_ptr() for _, p in named)
+        vers = tuple(p._version for _, p in named)
+        tr = self.__dict__.get("_ag_trainers")
+        if tr is None or tr["ptrs"] != ptrs:
+            shadow = {n: nn.Parameter(p.detach(), requires_grad=True) for n, p in named}
+            tr = dict(shadow=shadow, names=[n for n, _ in named], ptrs=ptrs, vers=vers,
+                      ae=AeTrainer(shadow, self.point_embed.basis, self.depth, self.latent_dim, self.query_type, heads=self.heads))
+            self.__dict__["_ag_trainers"] = tr
+        elif tr["vers"] != vers:
+            tr["ae"].refresh_weights()
+            tr["vers"] = vers
+        return tr
+
+
+class _AeForwardFn(torch.autograd.Function):
+    """KLAutoEncoder.forward as an autograd node: forward = rald_amd.train_ae.AeTrainer.forward (HIP kernels, activations kept),
+    backward = its hand-written backward.  The parameters are inputs of the node, so ``loss.backward()`` fills ``p.grad`` the
+    ordinary way (GradScaler, clip_grad_norm_, torch.optim and DDP hooks see ordinary gradients)."""
+
+    @staticmethod
+    def forward(ctx, module, pc, queries, eps, masks, *params):
+        tr = module._autograd_trainers()
+        logits, kl, st = tr["ae"].forward(pc, queries, eps, masks)
+        ctx.module, ctx.st = module, st
+        return logits, kl
+
+    @staticmethod
+    def backward(ctx, dlogits, dkl):
+        if ctx.st is None:
+            raise RuntimeError("KLAutoEncoder.forward: backward through the same forward a second time - the saved activations are "
+                               "released by the first backward; retain_graph is not supported")
+        tr = ctx.module._autograd_trainers()
+        for sh in tr["shadow"].values():
+            sh.grad = None
+        tr["ae"].backward(ctx.st, dlogits.contiguous() if dlogits is not None else None, dkl.contiguous() if dkl is not None else None)
+        ctx.st = None
+        grads = tuple(tr["shadow"][n].grad if tr["shadow"][n].grad is not None else torch.zeros_like(tr["shadow"][n])
+                      for n in tr["names"])
+        return (None, None, None, None, None) + grads
 
 
 class AutoEncoder(nn.Module):
