@@ -1,10 +1,13 @@
 """Python owners of the C handles: device-memory plumbing (torch tensors -> raw pointers, the
-current torch stream -> hipStream_t) around librald_hip.so.  No arithmetic happens here."""
+current torch stream -> hipStream_t) around librald_hip.so.  No arithmetic happens here.
+
+Calls into the library pass `t.data_ptr()` for a tensor, None for NULL (`_opt` for an optional tensor), a numpy array's
+`.ctypes.data` for host memory and `_stream()` for the stream: the binding (_lib.py) declares every pointer as c_void_p."""
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Iterable, Optional, Tuple
+from typing import Dict, Iterable, Optional, Sequence, Tuple
 
 import torch
 
@@ -16,8 +19,9 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _ptr(t: torch.Tensor) -> int:
-    return t.data_ptr()
+def _opt(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Pointer argument of an optional tensor: None (NULL) when it is absent."""
+    return t.data_ptr() if t is not None else None
 
 
 def _need_cuda(t: torch.Tensor, what: str) -> None:
@@ -27,6 +31,60 @@ def _need_cuda(t: torch.Tensor, what: str) -> None:
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
+
+
+def _nbytes(n: int) -> int:
+    """A size from a rald_*_workspace_bytes query; a negative one means the library refused the configuration."""
+    if n < 0:
+        check(1)
+    return n
+
+
+def _cached_workspace(cache: Dict[torch.device, torch.Tensor], nbytes: int, device) -> torch.Tensor:
+    """The uint8 workspace of `device` in `cache`, kept between calls and grown to `nbytes` on demand."""
+    ws = cache.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = cache[device] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    """A uint8 scratch buffer for one call, at least 16 bytes, so its pointer is never NULL."""
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def _doubles(vals: Sequence[float], n: int, what: str, layout: str = "") -> C.Array:
+    """A host double[n] argument (Python floats of the reference's YAML -> doubles)."""
+    if len(vals) != n:
+        raise ValueError(f"{what} must have {n} elements{layout}")
+    return (C.c_double * n)(*[float(v) for v in vals])
+
+
+class _Handle:
+    """Owner of one rald_<kind>* handle: created from `args` by rald_<kind>_create, destroyed by rald_<kind>_destroy when the owner
+    drops it.  `_h` is the handle itself (a c_void_p) for the calls."""
+
+    def __init__(self, kind: str, *args):
+        self._kind = kind
+        self._h = C.c_void_p()
+        check(getattr(lib(), f"rald_{kind}_create")(*args, C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                getattr(lib(), f"rald_{self._kind}_destroy")(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def load(self, named: Iterable[Tuple[str, torch.Tensor]], fn: str = "load_weight", finalize: bool = True) -> None:
+        """rald_<kind>_<fn>(name, fp32 data, nelem) for every (name, tensor), then rald_<kind>_finalize."""
+        put = getattr(lib(), f"rald_{self._kind}_{fn}")
+        for name, t in named:
+            t = _f32c(t)                       # host or device fp32; the library stages either
+            check(put(self._h, name.encode(), t.data_ptr(), t.numel()))
+        if finalize:
+            check(getattr(lib(), f"rald_{self._kind}_finalize")(self._h))
 
 
 # Launch-bound regime (small batches): one sampler run is ~10 000 kernel launches of a few
@@ -81,13 +139,12 @@ class _GraphCache:
         return [o.clone() for o in outs]
 
 
-class DitHandle:
+class DitHandle(_Handle):
     """rald_dit* + its condition cache.  One handle per module per device."""
 
     def __init__(self, cfg: DitConfig):
         self.cfg = cfg
-        self._h = C.c_void_p()
-        check(lib().rald_dit_create(C.byref(cfg), C.byref(self._h)))
+        super().__init__("dit", C.byref(cfg))
         self._graphs = _GraphCache(lambda: lib().rald_dit_workspace_generation(self._h))
         self._reserved = 0
         self._sched = None
@@ -99,24 +156,10 @@ class DitHandle:
         self.autotune_two_stream = False
         self._two_stream_tuned = {}
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().rald_dit_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def load(self, named: Iterable[Tuple[str, torch.Tensor]]) -> None:
-        for name, t in named:
-            t = _f32c(t)                       # host or device fp32; the library stages either
-            check(lib().rald_dit_load_weight(self._h, name.encode(), C.c_void_p(_ptr(t)), t.numel()))
-        check(lib().rald_dit_finalize(self._h))
-
     def set_sigmas(self, sigmas) -> None:
         s = [float(v) for v in sigmas]
         arr = (C.c_float * len(s))(*s)
-        check(lib().rald_dit_set_sigmas(self._h, arr, len(s), C.c_void_p(_stream())))
+        check(lib().rald_dit_set_sigmas(self._h, arr, len(s), _stream()))
 
     def new_cache(self, batch: int, device) -> torch.Tensor:
         nbytes = lib().rald_dit_cond_cache_bytes(self._h, batch)
@@ -129,7 +172,7 @@ class DitHandle:
         if T != self.cfg.n_cond_tokens or Cd != self.cfg.context_dim:
             raise RuntimeError(f"condition tokens must be [B,{self.cfg.n_cond_tokens},{self.cfg.context_dim}], got {tuple(tokens.shape)}")
         cache = self.new_cache(B, tokens.device)
-        check(lib().rald_dit_encode_cond_tokens(self._h, C.c_void_p(_ptr(tokens)), B, C.c_void_p(_ptr(cache)), C.c_void_p(_stream())))
+        check(lib().rald_dit_encode_cond_tokens(self._h, tokens.data_ptr(), B, cache.data_ptr(), _stream()))
         return cache
 
     def encode_cond(self, cube: torch.Tensor, want_tokens: bool = True):
@@ -138,11 +181,9 @@ class DitHandle:
         B = cube.shape[0]
         cache = self.new_cache(B, cube.device)
         tokens = None
-        tp = C.c_void_p(0)
         if want_tokens:
             tokens = torch.empty(B, self.cfg.n_cond_tokens, self.cfg.n_heads * self.cfg.d_head, device=cube.device, dtype=torch.float32)
-            tp = C.c_void_p(_ptr(tokens))
-        check(lib().rald_dit_encode_cond(self._h, C.c_void_p(_ptr(cube)), B, tp, C.c_void_p(_ptr(cache)), C.c_void_p(_stream())))
+        check(lib().rald_dit_encode_cond(self._h, cube.data_ptr(), B, _opt(tokens), cache.data_ptr(), _stream()))
         return tokens, cache
 
     def denoise(self, x: torch.Tensor, cache: torch.Tensor, sigma_row: int = 0, per_sample: bool = False,
@@ -158,8 +199,8 @@ class DitHandle:
         B = x.shape[0]
         if self.autotune_two_stream and 128 <= B < 256 and B not in self._two_stream_tuned and not torch.cuda.is_current_stream_capturing():
             self._tune_two_stream(x, cache, sigma_row, per_sample, raw_F, out)
-        check(lib().rald_dit_denoise(self._h, C.c_void_p(_ptr(x)), B, sigma_row, int(per_sample),
-                                     C.c_void_p(_ptr(cache)), C.c_void_p(_ptr(out)), int(raw_F), C.c_void_p(_stream())))
+        check(lib().rald_dit_denoise(self._h, x.data_ptr(), B, sigma_row, int(per_sample),
+                                     cache.data_ptr(), out.data_ptr(), int(raw_F), _stream()))
         return out
 
     def _tune_two_stream(self, x, cache, sigma_row, per_sample, raw_F, out) -> None:
@@ -169,8 +210,8 @@ class DitHandle:
 
         def run(n):
             for _ in range(n):
-                check(lib().rald_dit_denoise(self._h, C.c_void_p(_ptr(x)), B, sigma_row, int(per_sample), C.c_void_p(_ptr(cache)),
-                                             C.c_void_p(_ptr(out)), int(raw_F), C.c_void_p(_stream())))
+                check(lib().rald_dit_denoise(self._h, x.data_ptr(), B, sigma_row, int(per_sample), cache.data_ptr(),
+                                             out.data_ptr(), int(raw_F), _stream()))
         ms = {}
         for mode, mb in (("whole", 0), ("split", B)):
             self._set_two_stream(mb)
@@ -220,8 +261,8 @@ class DitHandle:
             self._reserved = batch
 
     def _sample_eager(self, latents, cache, out, num_steps, sigma_min, sigma_max, rho):
-        check(lib().rald_dit_sample(self._h, C.c_void_p(_ptr(latents)), latents.shape[0], C.c_void_p(_ptr(cache)), num_steps,
-                                    sigma_min, sigma_max, rho, C.c_void_p(_ptr(out)), C.c_void_p(_stream())))
+        check(lib().rald_dit_sample(self._h, latents.data_ptr(), latents.shape[0], cache.data_ptr(), num_steps,
+                                    sigma_min, sigma_max, rho, out.data_ptr(), _stream()))
 
     def sample(self, latents: torch.Tensor, cache: torch.Tensor, num_steps: int = 18, sigma_min: float = 0.002,
                sigma_max: float = 80.0, rho: float = 7.0, use_graph: Optional[bool] = None) -> torch.Tensor:
@@ -265,10 +306,8 @@ def op_gemm_nt(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = 
         shape = (batch, M, nc) if batched else (M, nc)
         out = torch.empty(shape, device=A.device, dtype=torch.float16 if epilogue == 5 else (torch.bfloat16 if epilogue in (0, 3, 4) else torch.float32))
     sC = out.stride(0) if out.dim() == 3 else 0
-    check(lib().rald_op_gemm_nt(C.c_void_p(_ptr(A)), A.stride(-2), sA, C.c_void_p(_ptr(B)), B.stride(-2), sB,
-                                C.c_void_p(_ptr(out)), out.stride(-2), sC,
-                                C.c_void_p(_ptr(bias) if bias is not None else 0), M, N, K, batch, alpha, epilogue,
-                                C.c_void_p(_stream())))
+    check(lib().rald_op_gemm_nt(A.data_ptr(), A.stride(-2), sA, B.data_ptr(), B.stride(-2), sB, out.data_ptr(), out.stride(-2), sC, _opt(bias), M, N,
+                                K, batch, alpha, epilogue, _stream()))
     return out
 
 
@@ -280,13 +319,13 @@ def op_gemm_tn(A: torch.Tensor, B: torch.Tensor, C_inout: torch.Tensor, colsum: 
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and C_inout.dtype == torch.float32 and B.shape[0] == M
     assert A.stride(1) == 1 and B.stride(1) == 1 and C_inout.stride(1) == 1 and C_inout.shape == (N1, N2)
     if atomics:
-        check(lib().rald_op_gemm_tn(C.c_void_p(_ptr(A)), A.stride(0), C.c_void_p(_ptr(B)), B.stride(0), C.c_void_p(_ptr(C_inout)), C_inout.stride(0),
-                                    C.c_void_p(_ptr(colsum) if colsum is not None else 0), M, N1, N2, C.c_void_p(_stream())))
+        check(lib().rald_op_gemm_tn(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C_inout.data_ptr(), C_inout.stride(0),
+                                    _opt(colsum), M, N1, N2, _stream()))
         return C_inout
     nbytes = lib().rald_op_gemm_tn_workspace_bytes(M, N1, N2)
-    ws = torch.empty(max(nbytes, 16), device=A.device, dtype=torch.uint8)
-    check(lib().rald_op_gemm_tn_ws(C.c_void_p(_ptr(A)), A.stride(0), C.c_void_p(_ptr(B)), B.stride(0), C.c_void_p(_ptr(C_inout)), C_inout.stride(0),
-                                   C.c_void_p(_ptr(colsum) if colsum is not None else 0), M, N1, N2, C.c_void_p(_ptr(ws)), nbytes, C.c_void_p(_stream())))
+    ws = _scratch(nbytes, A.device)
+    check(lib().rald_op_gemm_tn_ws(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C_inout.data_ptr(), C_inout.stride(0),
+                                   _opt(colsum), M, N1, N2, ws.data_ptr(), nbytes, _stream()))
     return C_inout
 
 
@@ -295,9 +334,9 @@ def op_gemm_resid_ln(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, x: to
     """x [M,512] f32 += A [M,K] bf16 @ W [512,K]^T + bias (in place); returns h = LN(x)*(add_one+g)+b as bf16."""
     M, K = A.shape
     h = torch.empty(M, 512, device=A.device, dtype=torch.bfloat16)
-    check(lib().rald_op_gemm_resid_ln(C.c_void_p(_ptr(A)), A.stride(0), C.c_void_p(_ptr(W)), W.stride(0), C.c_void_p(_ptr(bias)),
-                                      C.c_void_p(_ptr(x)), C.c_void_p(_ptr(h)), C.c_void_p(_ptr(g)), C.c_void_p(_ptr(b)), gstride,
-                                      rows_per_group, add_one, eps, M, K, C.c_void_p(_stream())))
+    check(lib().rald_op_gemm_resid_ln(A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr(),
+                                      x.data_ptr(), h.data_ptr(), g.data_ptr(), b.data_ptr(), gstride,
+                                      rows_per_group, add_one, eps, M, K, _stream()))
     return h
 
 
@@ -305,8 +344,8 @@ def op_layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, gstride: int
                  add_one: float = 0.0, eps: float = 1e-5) -> torch.Tensor:
     M, D = x.shape
     out = torch.empty(M, D, device=x.device, dtype=torch.bfloat16)
-    check(lib().rald_op_layernorm(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(out)), M, D, C.c_void_p(_ptr(g)), C.c_void_p(_ptr(b)),
-                                  gstride, rows_per_group, add_one, eps, C.c_void_p(_stream())))
+    check(lib().rald_op_layernorm(x.data_ptr(), out.data_ptr(), M, D, g.data_ptr(), b.data_ptr(),
+                                  gstride, rows_per_group, add_one, eps, _stream()))
     return out
 
 
@@ -315,9 +354,9 @@ def op_attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, nk: int, he
     scale*log2(e) and `scale` is ignored."""
     Bn, nq, HD = Q.shape
     O = torch.empty(Bn, nq, HD, device=Q.device, dtype=torch.bfloat16)
-    check(lib().rald_op_attention(C.c_void_p(_ptr(Q)), Q.stride(1), Q.stride(0), C.c_void_p(_ptr(K)), K.stride(1), K.stride(0),
-                                  C.c_void_p(_ptr(Vt)), Vt.stride(1), Vt.stride(0), C.c_void_p(_ptr(O)), O.stride(1), O.stride(0),
-                                  nq, nk, K.shape[1], heads, Bn, scale, int(prescaled), C.c_void_p(_stream())))
+    check(lib().rald_op_attention(Q.data_ptr(), Q.stride(1), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0),
+                                  Vt.data_ptr(), Vt.stride(1), Vt.stride(0), O.data_ptr(), O.stride(1), O.stride(0),
+                                  nq, nk, K.shape[1], heads, Bn, scale, int(prescaled), _stream()))
     return O
 
 
@@ -325,10 +364,10 @@ def op_attention_split(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, nk: i
     """op_attention with the keys split over `ksplit` workgroups per query block (+ combine pass)."""
     Bn, nq, HD = Q.shape
     O = torch.empty(Bn, nq, HD, device=Q.device, dtype=torch.bfloat16)
-    scratch = torch.empty(max(8, lib().rald_op_attention_split_scratch_bytes(max(ksplit, 32), nq, heads, Bn)), device=Q.device, dtype=torch.uint8)
-    check(lib().rald_op_attention_split(C.c_void_p(_ptr(Q)), Q.stride(1), Q.stride(0), C.c_void_p(_ptr(K)), K.stride(1), K.stride(0),
-                                        C.c_void_p(_ptr(Vt)), Vt.stride(1), Vt.stride(0), C.c_void_p(_ptr(O)), O.stride(1), O.stride(0),
-                                        nq, nk, K.shape[1], heads, Bn, scale, ksplit, C.c_void_p(_ptr(scratch)), C.c_void_p(_stream())))
+    scratch = _scratch(lib().rald_op_attention_split_scratch_bytes(max(ksplit, 32), nq, heads, Bn), Q.device)
+    check(lib().rald_op_attention_split(Q.data_ptr(), Q.stride(1), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0),
+                                        Vt.data_ptr(), Vt.stride(1), Vt.stride(0), O.data_ptr(), O.stride(1), O.stride(0),
+                                        nq, nk, K.shape[1], heads, Bn, scale, ksplit, scratch.data_ptr(), _stream()))
     return O
 
 
@@ -336,9 +375,9 @@ def op_attention_vrow(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: 
     """Q [B,nq,H*64], K / V [B,nk,H*64] (bf16, possibly column slices of one fused buffer) -> O [B,nq,H*64] bf16."""
     Bn, nq, HD = Q.shape
     O = torch.empty(Bn, nq, HD, device=Q.device, dtype=torch.bfloat16)
-    check(lib().rald_op_attention_vrow(C.c_void_p(_ptr(Q)), Q.stride(1), Q.stride(0), C.c_void_p(_ptr(K)), K.stride(1), K.stride(0),
-                                       C.c_void_p(_ptr(V)), V.stride(1), V.stride(0), C.c_void_p(_ptr(O)), O.stride(1), O.stride(0),
-                                       nq, K.shape[1], heads, Bn, scale, C.c_void_p(_stream())))
+    check(lib().rald_op_attention_vrow(Q.data_ptr(), Q.stride(1), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0),
+                                       V.data_ptr(), V.stride(1), V.stride(0), O.data_ptr(), O.stride(1), O.stride(0),
+                                       nq, K.shape[1], heads, Bn, scale, _stream()))
     return O
 
 
@@ -349,9 +388,9 @@ def op_attention_f16kv(Q: torch.Tensor, KV: torch.Tensor, nk: int, heads: int, k
     nq, HD = Q.shape[-2], Q.shape[-1]
     assert Q.dtype == torch.float32 and KV.dtype == torch.float16 and Q.is_contiguous() and KV.is_contiguous() and HD == heads * 64
     O = torch.empty(Bn, nq, HD, device=KV.device, dtype=torch.bfloat16)
-    scratch = torch.empty(lib().rald_op_attention_split_scratch_bytes(max(ksplit, 32), nq, heads, Bn) // 4, device=KV.device, dtype=torch.float32)
-    check(lib().rald_op_attention_f16kv(C.c_void_p(_ptr(Q)), HD, 0 if shared_q else nq * HD, C.c_void_p(_ptr(KV)), C.c_void_p(_ptr(O)), HD, nq * HD,
-                                        nq, nk, k_rows, heads, Bn, ksplit, C.c_void_p(_ptr(scratch)), C.c_void_p(_stream())))
+    scratch = _scratch(lib().rald_op_attention_split_scratch_bytes(max(ksplit, 32), nq, heads, Bn), KV.device)
+    check(lib().rald_op_attention_f16kv(Q.data_ptr(), HD, 0 if shared_q else nq * HD, KV.data_ptr(), O.data_ptr(), HD, nq * HD,
+                                        nq, nk, k_rows, heads, Bn, ksplit, scratch.data_ptr(), _stream()))
     return O
 
 
@@ -361,34 +400,19 @@ def op_ae_enc_features(pc: torch.Tensor, basis: torch.Tensor, var_factor: torch.
     Pp = (P + 63) // 64 * 64
     F = torch.empty(Bn, Pp, 64, device=pc.device, dtype=torch.float16)
     G = torch.empty_like(F)
-    check(lib().rald_op_ae_enc_features(C.c_void_p(_ptr(_f32c(pc))), C.c_void_p(_ptr(_f32c(basis))), C.c_void_p(_ptr(_f32c(var_factor))),
-                                        C.c_void_p(_ptr(F)), C.c_void_p(_ptr(G)), Bn, P, Pp, C.c_void_p(_stream())))
+    check(lib().rald_op_ae_enc_features(_f32c(pc).data_ptr(), _f32c(basis).data_ptr(), _f32c(var_factor).data_ptr(),
+                                        F.data_ptr(), G.data_ptr(), Bn, P, Pp, _stream()))
     return F, G
 
 
-class AeHandle:
+class AeHandle(_Handle):
     """rald_ae*: encode / decode_latents / decode_queries of the set-latent autoencoder."""
 
     def __init__(self, cfg):
         self.cfg = cfg
-        self._h = C.c_void_p()
-        check(lib().rald_ae_create(C.byref(cfg), C.byref(self._h)))
+        super().__init__("ae", C.byref(cfg))
         self._graphs = _GraphCache(lambda: lib().rald_ae_workspace_generation(self._h))
         self._dec_batch = 0
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().rald_ae_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def load(self, named) -> None:
-        for name, t in named:
-            t = _f32c(t)
-            check(lib().rald_ae_load_weight(self._h, name.encode(), C.c_void_p(_ptr(t)), t.numel()))
-        check(lib().rald_ae_finalize(self._h))
 
     def encode(self, pc: torch.Tensor, eps: torch.Tensor, want_moments: bool = False):
         _need_cuda(pc, "point cloud")
@@ -401,13 +425,13 @@ class AeHandle:
         kl = torch.empty(B, device=pc.device, dtype=torch.float32)
         mean = torch.empty_like(z) if want_moments else None
         logvar = torch.empty_like(z) if want_moments else None
-        check(lib().rald_ae_encode(self._h, C.c_void_p(_ptr(pc)), B, C.c_void_p(_ptr(eps)),
-                                   C.c_void_p(_ptr(mean) if want_moments else 0), C.c_void_p(_ptr(logvar) if want_moments else 0),
-                                   C.c_void_p(_ptr(z)), C.c_void_p(_ptr(kl)), C.c_void_p(_stream())))
+        check(lib().rald_ae_encode(self._h, pc.data_ptr(), B, eps.data_ptr(),
+                                   _opt(mean), _opt(logvar),
+                                   z.data_ptr(), kl.data_ptr(), _stream()))
         return (kl, z, mean, logvar) if want_moments else (kl, z)
 
     def _decode_latents_eager(self, z, ctx):
-        check(lib().rald_ae_decode_latents(self._h, C.c_void_p(_ptr(z)), z.shape[0], C.c_void_p(_ptr(ctx)), C.c_void_p(_stream())))
+        check(lib().rald_ae_decode_latents(self._h, z.data_ptr(), z.shape[0], ctx.data_ptr(), _stream()))
 
     def decode_latents(self, z: torch.Tensor, use_graph: Optional[bool] = None) -> torch.Tensor:
         _need_cuda(z, "latents")
@@ -435,8 +459,7 @@ class AeHandle:
             raise RuntimeError(f"decoder context of {ctx.numel()} bytes does not belong to a batch of {B}: decode_latents(z) and the queries "
                                "must have the same batch size")
         out = torch.empty(B, Q, device=queries.device, dtype=torch.float32)
-        check(lib().rald_ae_decode_queries(self._h, C.c_void_p(_ptr(ctx)), C.c_void_p(_ptr(queries)), B, Q, C.c_void_p(_ptr(out)),
-                                           C.c_void_p(_stream())))
+        check(lib().rald_ae_decode_queries(self._h, ctx.data_ptr(), queries.data_ptr(), B, Q, out.data_ptr(), _stream()))
         return out
 
 
@@ -453,8 +476,8 @@ def op_quantize_mx8(x: torch.Tensor):
     rows = x2.shape[0]
     q = torch.empty(rows, K, device=x.device, dtype=torch.uint8)
     s = torch.empty(rows, K // 32, device=x.device, dtype=torch.uint8)
-    check(lib().rald_op_quantize_mx8(C.c_void_p(_ptr(x2)), int(x.dtype == torch.bfloat16), x2.stride(0), C.c_void_p(_ptr(q)), K,
-                                     C.c_void_p(_ptr(s)), rows, K, C.c_void_p(_stream())))
+    check(lib().rald_op_quantize_mx8(x2.data_ptr(), int(x.dtype == torch.bfloat16), x2.stride(0), q.data_ptr(), K,
+                                     s.data_ptr(), rows, K, _stream()))
     return q.reshape(*x.shape), s.reshape(*x.shape[:-1], K // 32)
 
 
@@ -473,11 +496,11 @@ def op_gemm_mx8(A8: torch.Tensor, sA: torch.Tensor, B8: torch.Tensor, sB: torch.
     else:
         shape = (batch, M, N) if batched else (M, N)
         out = torch.empty(shape, device=A8.device, dtype=torch.bfloat16 if epilogue == 0 else torch.float32)
-    check(lib().rald_op_gemm_mx8(C.c_void_p(_ptr(A8)), C.c_void_p(_ptr(sA)), A8.stride(-2), A8.stride(0) if A8.dim() == 3 else 0,
-                                 sA.stride(0) if sA.dim() == 3 else 0, C.c_void_p(_ptr(B8)), C.c_void_p(_ptr(sB)), B8.stride(-2),
-                                 B8.stride(0) if B8.dim() == 3 else 0, sB.stride(0) if sB.dim() == 3 else 0, C.c_void_p(_ptr(out)),
-                                 out.stride(-2), out.stride(0) if out.dim() == 3 else 0, C.c_void_p(_ptr(bias) if bias is not None else 0),
-                                 M, N, K, batch, alpha, epilogue, C.c_void_p(_stream())))
+    check(lib().rald_op_gemm_mx8(A8.data_ptr(), sA.data_ptr(), A8.stride(-2), A8.stride(0) if A8.dim() == 3 else 0,
+                                 sA.stride(0) if sA.dim() == 3 else 0, B8.data_ptr(), sB.data_ptr(), B8.stride(-2),
+                                 B8.stride(0) if B8.dim() == 3 else 0, sB.stride(0) if sB.dim() == 3 else 0, out.data_ptr(),
+                                 out.stride(-2), out.stride(0) if out.dim() == 3 else 0, _opt(bias),
+                                 M, N, K, batch, alpha, epilogue, _stream()))
     return out
 
 
@@ -486,6 +509,6 @@ def op_layernorm_mx8(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, gstride:
     M, D = x.shape
     q = torch.empty(M, D, device=x.device, dtype=torch.uint8)
     s = torch.empty(M, D // 32, device=x.device, dtype=torch.uint8)
-    check(lib().rald_op_layernorm_mx8(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(q)), C.c_void_p(_ptr(s)), M, D, C.c_void_p(_ptr(g)),
-                                      C.c_void_p(_ptr(b)), gstride, rows_per_group, add_one, eps, C.c_void_p(_stream())))
+    check(lib().rald_op_layernorm_mx8(x.data_ptr(), q.data_ptr(), s.data_ptr(), M, D, g.data_ptr(),
+                                      b.data_ptr(), gstride, rows_per_group, add_one, eps, _stream()))
     return q, s

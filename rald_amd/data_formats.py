@@ -14,14 +14,13 @@ Only loaders that execute nothing from the file are used (``np.load(allow_pickle
 """
 from __future__ import annotations
 
-import ctypes as C
 from pathlib import Path
 from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from ._handles import _f32c, _ptr, _stream
+from ._handles import _f32c, _stream
 from ._lib import check, lib
 
 
@@ -46,8 +45,8 @@ def process_radar_data(radar_cube, *, norm_intensity: bool = True, max_intensity
     B, R, A, E, Cr = t.shape
     tA, tE = (tgt_a_dim, tgt_e_dim) if upsample else (A, E)
     out = torch.empty(B, R, tA, tE, 2, device=t.device, dtype=torch.float32)
-    check(lib().rald_radar_cube_prepare(C.c_void_p(_ptr(t)), B, R, A, E, Cr, tA, tE, int(norm_intensity), float(max_intensity),
-                                        int(norm_dopp), float(max_dopp), C.c_void_p(_ptr(out)), C.c_void_p(_stream())))
+    check(lib().rald_radar_cube_prepare(t.data_ptr(), B, R, A, E, Cr, tA, tE, int(norm_intensity), float(max_intensity),
+                                        int(norm_dopp), float(max_dopp), out.data_ptr(), _stream()))
     return out[0] if squeeze else out
 
 

@@ -29,7 +29,7 @@ from typing import Dict, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from ._handles import _need_cuda, _ptr, _stream
+from ._handles import _Handle, _cached_workspace, _nbytes, _need_cuda, _opt, _stream
 from ._lib import LidarConfig, check, lib
 from .config import Config
 
@@ -130,10 +130,7 @@ def grid_size(cfg) -> np.ndarray:
 
 def workspace_bytes(cfg, batch: int, total_points: int) -> int:
     """Device workspace of one crop / voxelize / queries call over `batch` frames of `total_points` points (host arithmetic)."""
-    n = lib().rald_lidar_workspace_bytes(C.byref(lidar_config_struct(cfg)), int(batch), int(total_points))
-    if n < 0:
-        check(1)
-    return n
+    return _nbytes(lib().rald_lidar_workspace_bytes(C.byref(lidar_config_struct(cfg)), int(batch), int(total_points)))
 
 
 def empty_cell(kept_keys: np.ndarray, r) -> np.ndarray:
@@ -202,7 +199,7 @@ def _pack(scans: Sequence, cols: int) -> tuple:
     return flat, offs, width
 
 
-class LidarFrames:
+class LidarFrames(_Handle):
     """rald_lidar*: the configuration is checked at creation (positive voxel sizes, a grid below 2^31 cells).  Frames are packed
     [total, F] float32 CUDA tensors with host int64 offsets [B + 1]; the workspace is owned here and grows on demand."""
 
@@ -214,27 +211,11 @@ class LidarFrames:
         self.maxv = int(self.cfg.max_voxels)
         self.maxp = int(self.cfg.max_points_per_voxel)
         self.F = int(self.cfg.num_point_features)
-        self._h = C.c_void_p()
-        check(lib().rald_lidar_create(C.byref(self.cfg), C.byref(self._h)))
+        super().__init__("lidar", C.byref(self.cfg))
         self._ws: Dict[torch.device, torch.Tensor] = {}
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().rald_lidar_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     def _workspace(self, batch: int, total: int, device) -> torch.Tensor:
-        need = lib().rald_lidar_workspace_bytes(C.byref(self.cfg), int(batch), int(total))
-        if need < 0:
-            check(1)
-        ws = self._ws.get(device)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[device] = ws
-        return ws
+        return _cached_workspace(self._ws, _nbytes(lib().rald_lidar_workspace_bytes(C.byref(self.cfg), int(batch), int(total))), device)
 
     @staticmethod
     def _offs(offsets) -> np.ndarray:
@@ -261,8 +242,8 @@ class LidarFrames:
         out = torch.empty((max(points.shape[0], 1), 3), dtype=torch.float32, device=dev)
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
         ws = self._workspace(B, points.shape[0], dev)
-        check(lib().rald_lidar_crop(self._h, C.c_void_p(_ptr(points)), points.shape[1], C.c_void_p(o.ctypes.data), B, C.c_void_p(_ptr(out)),
-                                    C.c_void_p(_ptr(counts)), C.c_void_p(_ptr(ws)), ws.numel(), C.c_void_p(_stream())))
+        check(lib().rald_lidar_crop(self._h, points.data_ptr(), points.shape[1], o.ctypes.data, B, out.data_ptr(),
+                                    counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return out, counts
 
     def voxelize(self, points: torch.Tensor, offsets, counts: Optional[torch.Tensor] = None, to_polar: bool = False,
@@ -287,10 +268,9 @@ class LidarFrames:
             _need_cuda(counts, "counts")
             counts = counts.to(torch.int32).contiguous()
         ws = self._workspace(B, T, dev)
-        p = lambda t: C.c_void_p(_ptr(t) if t is not None else 0)
-        check(lib().rald_lidar_voxelize(self._h, p(points), C.c_void_p(o.ctypes.data), p(counts), B, int(bool(to_polar)), p(res["polar"]),
-                                        p(voxels), p(res["coords"]), p(res["num_points"]), p(res["kept_keys"]), p(res["voxel_counts"]),
-                                        p(ws), ws.numel(), C.c_void_p(_stream())))
+        check(lib().rald_lidar_voxelize(self._h, points.data_ptr(), o.ctypes.data, _opt(counts), B, int(bool(to_polar)), _opt(res["polar"]),
+                                        _opt(voxels), res["coords"].data_ptr(), res["num_points"].data_ptr(), res["kept_keys"].data_ptr(),
+                                        res["voxel_counts"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return res
 
     def queries(self, points: torch.Tensor, offsets, num_samples: int, in_num: int, sample_idx, u_in, voxel_idx, u_out, empty_rank,
@@ -307,10 +287,9 @@ class LidarFrames:
         qp = torch.empty((B, S, 3), dtype=torch.float32, device=dev)
         lab = torch.empty((B, S), dtype=torch.float32, device=dev)
         ws = self._workspace(B, 0, dev)
-        p = lambda t: C.c_void_p(_ptr(t) if t is not None else 0)
-        check(lib().rald_lidar_queries(self._h, p(points.contiguous()), C.c_void_p(o.ctypes.data), B, S, int(in_num), p(sample_idx), p(u_in),
-                                       p(voxel_idx), p(u_out), p(empty_rank), p(vox["coords"]), p(vox["kept_keys"]), p(vox["voxel_counts"]),
-                                       p(lp), p(qp), p(lab), p(ws), ws.numel(), C.c_void_p(_stream())))
+        check(lib().rald_lidar_queries(self._h, points.contiguous().data_ptr(), o.ctypes.data, B, S, int(in_num), _opt(sample_idx), _opt(u_in),
+                                       _opt(voxel_idx), _opt(u_out), _opt(empty_rank), _opt(vox["coords"]), _opt(vox["kept_keys"]),
+                                       _opt(vox["voxel_counts"]), lp.data_ptr(), qp.data_ptr(), lab.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return lp, qp, lab
 
     def batch(self, scans: Sequence, loader_type: str = "train", load_query: bool = True,

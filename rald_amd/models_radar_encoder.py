@@ -9,12 +9,10 @@ with a nearest-neighbour up-sampling kernel between the levels.  Inference only 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import weights as _w
-from ._handles import _f32c, _need_cuda, _ptr, _stream
+from ._handles import _Handle, _f32c, _need_cuda, _stream
 from ._lib import check, lib
 from .models_radar_generation import _HipBacked, build_param_tree
 
@@ -34,26 +32,13 @@ class RadarAutoencoder(_HipBacked):
     def _handle(self):
         fp = self._state_fingerprint()
         if self._hip is None or self._hip_fp != fp:
-            if self._hip is not None:
-                lib().rald_radar_destroy(self._hip)
-            h = C.c_void_p()
-            check(lib().rald_radar_create(self.basic_channel, self.embed_dim, 2, 128, 64, 32, C.byref(h)))
-            for k, v in self.state_dict().items():
-                t = _f32c(v)
-                if k.startswith("encoder."):
-                    check(lib().rald_radar_load_weight(h, k[len("encoder."):].encode(), C.c_void_p(_ptr(t)), t.numel()))
-                elif k.startswith("decoder."):
-                    check(lib().rald_radar_load_decoder_weight(h, k[len("decoder."):].encode(), C.c_void_p(_ptr(t)), t.numel()))
-            check(lib().rald_radar_finalize(h))
+            self._hip = None                   # the old handle's device memory is freed before the new one allocates
+            h = _Handle("radar", self.basic_channel, self.embed_dim, 2, 128, 64, 32)
+            sd = self.state_dict()             # encoder.* then decoder.*: the two halves load in state-dict order
+            h.load(((k[len("encoder."):], v) for k, v in sd.items() if k.startswith("encoder.")), finalize=False)
+            h.load(((k[len("decoder."):], v) for k, v in sd.items() if k.startswith("decoder.")), fn="load_decoder_weight")
             self._hip, self._hip_fp = h, fp
-        return self._hip
-
-    def __del__(self):
-        try:
-            if self._hip is not None:
-                lib().rald_radar_destroy(self._hip)
-        except Exception:
-            pass
+        return self._hip._h
 
     def _encode(self, x: torch.Tensor) -> torch.Tensor:
         """cube [B,R,A,E,2] -> [B,R/16,A/16,E/16,embed_dim]  (:390-393)."""
@@ -63,7 +48,7 @@ class RadarAutoencoder(_HipBacked):
             raise RuntimeError(f"radar cube must be [B,128,64,32,2], got {tuple(x.shape)}")
         B = x.shape[0]
         z = torch.empty(B, 8, 4, 2, self.embed_dim, device=x.device, dtype=torch.float32)
-        check(lib().rald_radar_encode(self._handle(), C.c_void_p(_ptr(x)), B, C.c_void_p(_ptr(z)), C.c_void_p(_stream())))
+        check(lib().rald_radar_encode(self._handle(), x.data_ptr(), B, z.data_ptr(), _stream()))
         return z
 
     def encode(self, x: torch.Tensor) -> torch.Tensor:
@@ -78,7 +63,7 @@ class RadarAutoencoder(_HipBacked):
             raise RuntimeError(f"radar latent must be [B,8,4,2,{self.embed_dim}] (channels last), got {tuple(z_cl.shape)}")
         B = z_cl.shape[0]
         out4 = torch.empty(B, 128, 64, 32, 4, device=z_cl.device, dtype=torch.float32)      # 2 channels + the kernel's zero padding
-        check(lib().rald_radar_decode(self._handle(), C.c_void_p(_ptr(z_cl)), B, C.c_void_p(_ptr(out4)), C.c_void_p(_stream())))
+        check(lib().rald_radar_decode(self._handle(), z_cl.data_ptr(), B, out4.data_ptr(), _stream()))
         return out4[..., :2].contiguous()
 
     @torch.no_grad()

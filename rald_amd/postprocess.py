@@ -7,19 +7,15 @@
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Sequence, Tuple
+from typing import Tuple
 
 import torch
 
-from ._handles import _f32c, _need_cuda, _ptr, _stream
+from ._handles import _doubles, _f32c, _need_cuda, _opt, _stream
 from ._lib import check, lib
 
 
-def _range(pc_range: Sequence[float]):
-    if len(pc_range) != 6:
-        raise ValueError("pc_range must have 6 elements [min0,min1,min2,max0,max1,max2]")
-    return (C.c_double * 6)(*[float(v) for v in pc_range])      # Python floats in the reference's YAML -> doubles
+_PC_RANGE = " [min0,min1,min2,max0,max1,max2]"          # the layout named when a pc_range has the wrong length
 
 
 def occupied_points(logits: torch.Tensor, queries: torch.Tensor, lidar_pc_range, norm_anisotropy: bool, norm_isotropy: bool,
@@ -35,10 +31,10 @@ def occupied_points(logits: torch.Tensor, queries: torch.Tensor, lidar_pc_range,
     idx = torch.empty(Q, device=logits.device, dtype=torch.int64) if return_index else None
     cnt = torch.zeros(1, device=logits.device, dtype=torch.int64)
     scratch = torch.empty(lib().rald_post_scratch_bytes(Q), device=logits.device, dtype=torch.uint8)
-    check(lib().rald_post_occupied_points(C.c_void_p(_ptr(logits)), C.c_void_p(_ptr(queries)), Q, _range(lidar_pc_range),
+    check(lib().rald_post_occupied_points(logits.data_ptr(), queries.data_ptr(), Q, _doubles(lidar_pc_range, 6, "pc_range", _PC_RANGE),
                                           int(norm_anisotropy), int(norm_isotropy), int(view_cone_mode), float(threshold),
-                                          C.c_void_p(_ptr(pts)), C.c_void_p(_ptr(idx) if return_index else 0), C.c_void_p(_ptr(cnt)),
-                                          C.c_void_p(_ptr(scratch)), C.c_void_p(_stream())))
+                                          pts.data_ptr(), _opt(idx), cnt.data_ptr(),
+                                          scratch.data_ptr(), _stream()))
     n = int(cnt.item())                                   # the only host sync: the reference syncs on the full D2H here
     return (pts[:n], idx[:n]) if return_index else pts[:n]
 
@@ -48,8 +44,8 @@ def _transform(points: torch.Tensor, lidar_pc_range, aniso: bool, iso: bool, vie
     points = _f32c(points).reshape(-1, 3)
     out = torch.empty_like(points)
     if points.shape[0]:
-        check(lib().rald_post_transform_points(C.c_void_p(_ptr(points)), points.shape[0], _range(lidar_pc_range), int(aniso), int(iso),
-                                               int(view_cone), C.c_void_p(_ptr(out)), C.c_void_p(_stream())))
+        check(lib().rald_post_transform_points(points.data_ptr(), points.shape[0], _doubles(lidar_pc_range, 6, "pc_range", _PC_RANGE), int(aniso),
+                                               int(iso), int(view_cone), out.data_ptr(), _stream()))
     return out
 
 
@@ -71,8 +67,8 @@ def cal_metrics(y_pred: torch.Tensor, y_gt: torch.Tensor) -> float:
     _need_cuda(y_pred, "y_pred")
     y_pred, y_gt = _f32c(y_pred).reshape(-1, 3), _f32c(y_gt).reshape(-1, 3).to(y_pred.device)
     sums = torch.zeros(2, device=y_pred.device, dtype=torch.float64)
-    check(lib().rald_post_chamfer_sums(C.c_void_p(_ptr(y_pred)), y_pred.shape[0], C.c_void_p(_ptr(y_gt)), y_gt.shape[0],
-                                       C.c_void_p(_ptr(sums)), C.c_void_p(_stream())))
+    check(lib().rald_post_chamfer_sums(y_pred.data_ptr(), y_pred.shape[0], y_gt.data_ptr(), y_gt.shape[0],
+                                       sums.data_ptr(), _stream()))
     s = sums.cpu()
     return float(0.5 * s[1] / y_gt.shape[0] + 0.5 * s[0] / y_pred.shape[0])
 
@@ -84,6 +80,5 @@ def accuracy_iou(outputs: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Ten
     B, Q = outputs.shape
     acc = torch.empty(B, device=outputs.device, dtype=torch.float32)
     iou = torch.empty(B, device=outputs.device, dtype=torch.float32)
-    check(lib().rald_post_iou(C.c_void_p(_ptr(outputs)), C.c_void_p(_ptr(labels)), B, Q, C.c_void_p(_ptr(acc)), C.c_void_p(_ptr(iou)),
-                              C.c_void_p(_stream())))
+    check(lib().rald_post_iou(outputs.data_ptr(), labels.data_ptr(), B, Q, acc.data_ptr(), iou.data_ptr(), _stream()))
     return acc, iou

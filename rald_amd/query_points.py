@@ -11,22 +11,15 @@ different stream, no host work).
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
 
-from ._handles import _f32c, _need_cuda, _ptr, _stream
+from ._handles import _doubles, _f32c, _need_cuda, _opt, _stream
 from ._lib import check, lib
 
 Rng = Optional[torch.Generator]
-
-
-def _d(vals: Sequence[float], n: int, what: str):
-    if len(vals) != n:
-        raise ValueError(f"{what} must have {n} elements")
-    return (C.c_double * n)(*[float(v) for v in vals])
 
 
 def _uniform(shape, device, rng: Rng) -> torch.Tensor:
@@ -65,8 +58,8 @@ def uniform_queries(n: int, pc_range, norm_anisotropy: bool, norm_isotropy: bool
         raise ValueError("one of norm_anisotropy / norm_isotropy is required")
     u = _uniform((3, n), device, rng)                          # x draws, then y, then z - numpy's order
     out = torch.empty(n, 3, device=device, dtype=torch.float32)
-    check(lib().rald_query_uniform(C.c_void_p(_ptr(u)), n, _d(pc_range, 6, "pc_range"), int(norm_anisotropy), int(norm_isotropy),
-                                   C.c_void_p(_ptr(out)), C.c_void_p(_stream())))
+    check(lib().rald_query_uniform(u.data_ptr(), n, _doubles(pc_range, 6, "pc_range"), int(norm_anisotropy), int(norm_isotropy),
+                                   out.data_ptr(), _stream()))
     return out
 
 
@@ -82,9 +75,9 @@ def generate_cart_query_points(args, device=None, rng: Rng = None) -> torch.Tens
     out = torch.empty(n, 3, device=device, dtype=torch.float32)
     cnt = torch.zeros(1, device=device, dtype=torch.int64)
     scratch = torch.empty(lib().rald_post_scratch_bytes(n), device=device, dtype=torch.uint8)
-    check(lib().rald_query_uniform_cart(C.c_void_p(_ptr(u)), n, _d(lidar.pc_range_cart, 6, "pc_range_cart"), _d(lidar.pc_range, 6, "pc_range"),
-                                        int(lidar.norm_anisotropy), int(lidar.norm_isotropy), C.c_void_p(_ptr(out)), C.c_void_p(_ptr(cnt)),
-                                        C.c_void_p(_ptr(scratch)), C.c_void_p(_stream())))
+    check(lib().rald_query_uniform_cart(u.data_ptr(), n, _doubles(lidar.pc_range_cart, 6, "pc_range_cart"), _doubles(lidar.pc_range, 6, "pc_range"),
+                                        int(lidar.norm_anisotropy), int(lidar.norm_isotropy), out.data_ptr(), cnt.data_ptr(),
+                                        scratch.data_ptr(), _stream()))
     return out[:int(cnt.item())]
 
 
@@ -93,8 +86,8 @@ def norm_points(points: torch.Tensor, lidar_pc_range, norm_anisotropy: bool, nor
     _need_cuda(points, "points")
     points = _f32c(points).reshape(-1, 3)
     out = torch.empty_like(points)
-    check(lib().rald_query_norm_points(C.c_void_p(_ptr(points)), points.shape[0], _d(lidar_pc_range, 6, "pc_range"), int(norm_anisotropy),
-                                       int(norm_isotropy), C.c_void_p(_ptr(out)), C.c_void_p(_stream())))
+    check(lib().rald_query_norm_points(points.data_ptr(), points.shape[0], _doubles(lidar_pc_range, 6, "pc_range"), int(norm_anisotropy),
+                                       int(norm_isotropy), out.data_ptr(), _stream()))
     return out
 
 
@@ -128,9 +121,8 @@ def aug_query_helper(helper_points: torch.Tensor, aug_num: int, pc_range, voxel_
             u = torch.rand((gen, 3), dtype=torch.float64, device=dev, generator=rng)
     out = torch.empty(aug_num, 3, device=dev, dtype=torch.float32)
     aniso, iso = (bool(norm[0]), bool(norm[1])) if norm is not None else (False, False)
-    p = lambda t: C.c_void_p(_ptr(t) if t is not None else 0)
-    check(lib().rald_query_refine(p(helper_points), N, aug_num, p(sel), p(scales), p(u), _d(pc_range, 6, "pc_range"), _d(voxel_size, 3, "voxel_size"),
-                                  int(aniso), int(iso), int(norm is not None), p(out), C.c_void_p(_stream())))
+    check(lib().rald_query_refine(helper_points.data_ptr(), N, aug_num, _opt(sel), _opt(scales), _opt(u), _doubles(pc_range, 6, "pc_range"),
+                                  _doubles(voxel_size, 3, "voxel_size"), int(aniso), int(iso), int(norm is not None), out.data_ptr(), _stream()))
     return out
 
 

@@ -20,7 +20,7 @@ from typing import Dict, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._handles import _need_cuda, _ptr, _stream
+from ._handles import _Handle, _cached_workspace, _nbytes, _need_cuda, _stream
 from ._lib import RadarDspConfig, check, lib
 
 class RadarConfig(dict):
@@ -86,13 +86,10 @@ def dsp_config(radar_config) -> RadarDspConfig:
 
 def workspace_bytes(radar_config, batch: int) -> int:
     """Device workspace of one run over `batch` frames (host arithmetic, no device call)."""
-    n = lib().rald_radar_dsp_workspace_bytes(C.byref(dsp_config(radar_config)), int(batch))
-    if n < 0:
-        check(1)
-    return n
+    return _nbytes(lib().rald_radar_dsp_workspace_bytes(C.byref(dsp_config(radar_config)), int(batch)))
 
 
-class RadarDSP:
+class RadarDSP(_Handle):
     """rald_radar_dsp*: every size, the crop and the antenna layout are checked, and the tables built, here."""
 
     def __init__(self, radar_config, tx_array, rx_array):
@@ -106,27 +103,8 @@ class RadarDSP:
         if tx.shape[0] != c.ntx or rx.shape[0] != c.nrx:
             raise ValueError(f"antenna layout has {tx.shape[0]} tx / {rx.shape[0]} rx rows, the config {c.ntx} / {c.nrx}")
         self.vbins = np.ascontiguousarray(velocity_bins(radar_config), dtype=np.float64)
-        ip = C.POINTER(C.c_int32)
-        self._h = C.c_void_p()
-        check(lib().rald_radar_dsp_create(C.byref(c), tx.ctypes.data_as(ip), rx.ctypes.data_as(ip),
-                                          self.vbins.ctypes.data_as(C.POINTER(C.c_double)), len(self.vbins), C.byref(self._h)))
+        super().__init__("radar_dsp", C.byref(c), tx.ctypes.data, rx.ctypes.data, self.vbins.ctypes.data, len(self.vbins))
         self._ws: Dict[torch.device, torch.Tensor] = {}
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().rald_radar_dsp_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def _workspace(self, batch: int, device) -> torch.Tensor:
-        need = lib().rald_radar_dsp_workspace_bytes(C.byref(self.cfg), batch)
-        ws = self._ws.get(device)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[device] = ws
-        return ws
 
     def _run(self, frames: torch.Tensor, kind: int) -> torch.Tensor:
         _need_cuda(frames, "the ADC frames")
@@ -137,9 +115,8 @@ class RadarDSP:
         x = x.contiguous()
         B = x.shape[0]
         out = torch.empty((B, *self.shape_out), dtype=torch.float32, device=x.device)
-        ws = self._workspace(B, x.device)
-        check(lib().rald_radar_dsp_run(self._h, C.c_void_p(_ptr(x)), kind, B, C.c_void_p(_ptr(out)), C.c_void_p(_ptr(ws)), ws.numel(),
-                                       C.c_void_p(_stream())))
+        ws = _cached_workspace(self._ws, _nbytes(lib().rald_radar_dsp_workspace_bytes(C.byref(self.cfg), B)), x.device)
+        check(lib().rald_radar_dsp_run(self._h, x.data_ptr(), kind, B, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return out[0] if squeeze else out
 
     def cubes(self, adc: torch.Tensor) -> torch.Tensor:

@@ -24,7 +24,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._handles import _need_cuda, _ptr, _stream
+from ._handles import _Handle, _cached_workspace, _nbytes, _need_cuda, _opt, _stream
 from ._lib import RadarPointsConfig, check, lib
 from .radar_dsp import RadarConfig, load_radar_config
 
@@ -80,10 +80,7 @@ def points_config(cfg, in_channels: int = 1) -> RadarPointsConfig:
 
 def workspace_bytes(cfg, batch: int) -> int:
     """Device workspace of one run over `batch` frames (host arithmetic, no device call)."""
-    n = lib().rald_radar_points_workspace_bytes(C.byref(points_config(cfg)), int(batch))
-    if n < 0:
-        check(1)
-    return n
+    return _nbytes(lib().rald_radar_points_workspace_bytes(C.byref(points_config(cfg)), int(batch)))
 
 
 def _raise_rejected(counts: torch.Tensor) -> None:
@@ -97,7 +94,7 @@ def _raise_rejected(counts: torch.Tensor) -> None:
     raise AssertionError(f"radar_points: frame {b} needs more points in one range slice than the slice has voxels")
 
 
-class RadarPoints:
+class RadarPoints(_Handle):
     """rald_radar_points*: the sizes are checked, and the interpolation tables built, at creation.  `in_channels` is the channel
     count of the cubes given to it (channel 0, the intensity, is read): 3 for RadarDSP.cubes() output, 1 for intensity only."""
 
@@ -114,26 +111,8 @@ class RadarPoints:
         for name, t, m, n in zip("rae", self._axes, self._masks, (c.tgt_r, c.tgt_a, c.tgt_e)):
             if t.ndim != 1 or len(t) < n or m.ndim != 1 or len(m) < n:
                 raise ValueError(f"the {name} axis table and keep mask need {n} entries (tgt_{name}), got {t.shape} and {m.shape}")
-        self._h = C.c_void_p()
-        check(lib().rald_radar_points_create(C.byref(c), *[C.c_void_p(t.ctypes.data) for t in self._axes],
-                                             *[C.c_void_p(m.ctypes.data) for m in self._masks], C.byref(self._h)))
+        super().__init__("radar_points", C.byref(c), *[t.ctypes.data for t in self._axes], *[m.ctypes.data for m in self._masks])
         self._ws: Dict[torch.device, torch.Tensor] = {}
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().rald_radar_points_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def _workspace(self, batch: int, device) -> torch.Tensor:
-        need = lib().rald_radar_points_workspace_bytes(C.byref(self.cfg), batch)
-        ws = self._ws.get(device)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[device] = ws
-        return ws
 
     def _frames(self, cubes: torch.Tensor) -> torch.Tensor:
         _need_cuda(cubes, "the radar cubes")
@@ -158,10 +137,10 @@ class RadarPoints:
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
         peaks = torch.empty((B, self.num, 3), dtype=torch.int32, device=dev) if with_peaks else None
         inten = torch.empty((B, self.num), dtype=torch.float32, device=dev) if with_peaks else None
-        ws = self._workspace(B, dev)
-        check(lib().rald_radar_points_run(self._h, C.c_void_p(_ptr(x)), B, C.c_void_p(_ptr(points)), C.c_void_p(_ptr(counts)),
-                                          C.c_void_p(_ptr(peaks) if with_peaks else 0), C.c_void_p(_ptr(inten) if with_peaks else 0),
-                                          C.c_void_p(_ptr(ws)), ws.numel(), C.c_void_p(_stream())))
+        ws = _cached_workspace(self._ws, _nbytes(lib().rald_radar_points_workspace_bytes(C.byref(self.cfg), B)), dev)
+        check(lib().rald_radar_points_run(self._h, x.data_ptr(), B, points.data_ptr(), counts.data_ptr(),
+                                          _opt(peaks), _opt(inten),
+                                          ws.data_ptr(), ws.numel(), _stream()))
         if check_frames:
             _raise_rejected(counts)
         return points, counts, peaks, inten

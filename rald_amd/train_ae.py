@@ -20,16 +20,14 @@ softmax backward) are in csrc/ae_train.hip.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional
 
 import torch
 
 from . import train_ops as TO
-from ._handles import _stream, op_attention, op_attention_vrow, op_gemm_nt, op_gemm_tn, op_layernorm
+from ._handles import _opt, _scratch, _stream, op_attention, op_attention_vrow, op_gemm_nt, op_gemm_tn, op_layernorm
 from ._lib import check, lib
 
-_p = TO._p
 HEAD = 64
 DROP_PATH_RATE = 0.1
 LN_EPS = 1e-5
@@ -64,27 +62,28 @@ def ln_affine_bwd(x: torch.Tensor, dh: torch.Tensor, gamma: torch.Tensor, dx: to
     fixed order; dx_bf16 (optional) receives the updated dx as bf16."""
     rows = x.shape[0]
     nbytes = lib().rald_op_ln_affine_bwd_scratch_bytes(rows)
-    scratch = torch.empty(max(nbytes, 16) // 4, device=x.device, dtype=torch.float32)
-    check(lib().rald_op_ln_affine_bwd(_p(x), _p(dh), _p(gamma), LN_EPS, rows, _p(dx), _p(dx_bf16), _p(dgamma), _p(dbeta), _p(scratch), nbytes,
-                                      C.c_void_p(_stream())))
+    scratch = _scratch(nbytes, x.device)
+    check(lib().rald_op_ln_affine_bwd(x.data_ptr(), dh.data_ptr(), gamma.data_ptr(), LN_EPS, rows, dx.data_ptr(), _opt(dx_bf16), dgamma.data_ptr(),
+                                      dbeta.data_ptr(), scratch.data_ptr(), nbytes, _stream()))
 
 
 def pe_wgrad(dY: torch.Tensor, pts: torch.Tensor, basis: torch.Tensor, dW: torch.Tensor, db: torch.Tensor) -> None:
     """PointEmbed.mlp gradient: dW [512, 51] += dY^T . features(pts), db += column sums of dY (fixed order; features recomputed)."""
     rows = dY.shape[0]
     nbytes = lib().rald_op_pe_wgrad_scratch_bytes(rows)
-    scratch = torch.empty(max(nbytes, 16) // 4, device=dY.device, dtype=torch.float32)
-    check(lib().rald_op_pe_wgrad(_p(dY), _p(pts), _p(basis), rows, _p(dW), _p(db), _p(scratch), nbytes, C.c_void_p(_stream())))
+    scratch = _scratch(nbytes, dY.device)
+    check(lib().rald_op_pe_wgrad(dY.data_ptr(), pts.data_ptr(), basis.data_ptr(), rows, dW.data_ptr(), db.data_ptr(), scratch.data_ptr(), nbytes,
+                                 _stream()))
 
 
 def scale_rows_add(y: torch.Tensor, s: torch.Tensor, x: torch.Tensor, rows_per_sample: int) -> None:
     """x += s[row // rows_per_sample] * y (the drop-path residual)."""
-    check(lib().rald_op_scale_rows(_p(y), _p(s), _p(x), _p(None), y.shape[0], y.shape[1], rows_per_sample, C.c_void_p(_stream())))
+    check(lib().rald_op_scale_rows(y.data_ptr(), s.data_ptr(), x.data_ptr(), None, y.shape[0], y.shape[1], rows_per_sample, _stream()))
 
 
 def scale_rows_bf16(dx: torch.Tensor, s: torch.Tensor, rows_per_sample: int) -> torch.Tensor:
     out = torch.empty(dx.shape, device=dx.device, dtype=torch.bfloat16)
-    check(lib().rald_op_scale_rows(_p(dx), _p(s), _p(None), _p(out), dx.shape[0], dx.shape[1], rows_per_sample, C.c_void_p(_stream())))
+    check(lib().rald_op_scale_rows(dx.data_ptr(), s.data_ptr(), None, out.data_ptr(), dx.shape[0], dx.shape[1], rows_per_sample, _stream()))
     return out
 
 
@@ -109,7 +108,7 @@ def wgrad_narrow(dy: torch.Tensor, x: torch.Tensor, n: int):
 def pad_bf16(x: torch.Tensor, cols: int) -> torch.Tensor:
     """fp32 [M, C] -> bf16 [M, cols] with zero columns C .. cols-1."""
     out = torch.empty(x.shape[0], cols, device=x.device, dtype=torch.bfloat16)
-    check(lib().rald_op_pad_channels(_p(x), _p(out), x.shape[0], x.shape[1], cols, C.c_void_p(_stream())))
+    check(lib().rald_op_pad_channels(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], cols, _stream()))
     return out
 
 
@@ -189,7 +188,7 @@ class AeTrainer:
         """pts [R, 3] fp32 -> PointEmbed [R, 512] fp32 (features in bf16, one K = 64 GEMM)."""
         R = pts.shape[0]
         feat = torch.empty(R, 64, device=self.dev, dtype=torch.bfloat16)
-        check(lib().rald_op_point_features(_p(pts), _p(self.basis), _p(feat), R, C.c_void_p(_stream())))
+        check(lib().rald_op_point_features(pts.data_ptr(), self.basis.data_ptr(), feat.data_ptr(), R, _stream()))
         return op_gemm_nt(feat, self.W["pe"], bias=self.P["point_embed.mlp.bias"].data, epilogue=1)
 
     def _ln(self, x: torch.Tensor, p: str) -> torch.Tensor:
@@ -208,7 +207,7 @@ class AeTrainer:
         kv3 = kv.view(Bn, kp, 2 * D)
         S = op_gemm_nt(q.view(Bn, nq, D), kv3[:, :, :D], epilogue=1, alpha=D ** -0.5)
         P = torch.empty(Bn, nq, kp, device=self.dev, dtype=torch.bfloat16)
-        check(lib().rald_op_softmax_rows(_p(S), kp, _p(P), kp, Bn * nq, nk, C.c_void_p(_stream())))
+        check(lib().rald_op_softmax_rows(S.data_ptr(), kp, P.data_ptr(), kp, Bn * nq, nk, _stream()))
         vT = TO.transpose(kv[:, D:], kp, D, 2 * D, Bn, kp * 2 * D).view(Bn, D, kp)
         O = op_gemm_nt(P, vT, epilogue=0)
         return O.view(Bn * nq, D), S
@@ -219,10 +218,11 @@ class AeTrainer:
         kv3 = kv.view(Bn, kp, 2 * D)
         dP = op_gemm_nt(dO.view(Bn, nq, D), kv3[:, :, D:], epilogue=1)
         delta = _f32(Bn * nq, device=self.dev)
-        check(lib().rald_op_rowdot(_p(dO), _p(O), Bn * nq, D, _p(delta), C.c_void_p(_stream())))
+        check(lib().rald_op_rowdot(dO.data_ptr(), O.data_ptr(), Bn * nq, D, delta.data_ptr(), _stream()))
         P = torch.empty(Bn, nq, kp, device=self.dev, dtype=torch.bfloat16)
         dS = torch.empty(Bn, nq, kp, device=self.dev, dtype=torch.bfloat16)
-        check(lib().rald_op_softmax_bwd_rows(_p(S), _p(dP), _p(delta), Bn * nq, kp, nk, D ** -0.5, _p(P), _p(dS), C.c_void_p(_stream())))
+        check(lib().rald_op_softmax_bwd_rows(S.data_ptr(), dP.data_ptr(), delta.data_ptr(), Bn * nq, kp, nk, D ** -0.5, P.data_ptr(), dS.data_ptr(),
+                                             _stream()))
         del dP
         kT = TO.transpose(kv[:, :D], kp, D, 2 * D, Bn, kp * 2 * D).view(Bn, D, kp)
         dq = op_gemm_nt(dS, kT, epilogue=0).view(Bn * nq, D)
@@ -354,7 +354,7 @@ class AeTrainer:
         eps_d = eps.to(device=dev, dtype=torch.float32).reshape(Bn * M, L).contiguous()
         z = _f32(Bn * M, L, device=dev)
         kl = _f32(Bn, device=dev)
-        check(lib().rald_op_posterior(_p(ml), _p(eps_d), _p(z), _p(kl), Bn, M, L, C.c_void_p(_stream())))
+        check(lib().rald_op_posterior(ml.data_ptr(), eps_d.data_ptr(), z.data_ptr(), kl.data_ptr(), Bn, M, L, _stream()))
         st.update(x3b=x3b, ml=ml, eps=eps_d)
         # ---- decoder: proj, latent stack ---------------------------------------------------------------------------------------------
         zb = pad_bf16(z, _round_up(L, 64))
@@ -414,7 +414,8 @@ class AeTrainer:
         self._grad("proj.weight").add_(gp[:, :L])
         dz = op_gemm_nt(dxb, W["projT"], epilogue=1)                                        # [B*M, L]
         dml = _f32(Bn * M, 2 * L, device=dev)
-        check(lib().rald_op_posterior_bwd(_p(dz), _p(dkl_d), _p(st["ml"]), _p(st["eps"]), _p(dml), Bn, M, L, C.c_void_p(_stream())))
+        check(lib().rald_op_posterior_bwd(dz.data_ptr(), dkl_d.data_ptr(), st["ml"].data_ptr(), st["eps"].data_ptr(), dml.data_ptr(), Bn, M, L,
+                                          _stream()))
         dmlb = TO.cast_bf16(dml)
         gmv, gmb = wgrad_narrow(dml, st["x3b"], 2 * L)
         self._grad("mean_fc.weight").add_(gmv[:L])
@@ -458,8 +459,8 @@ def st_off(mix: bool) -> int:
 
 def TO_sgemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> None:
     """out[m, n] += a[m, 0] * w[0, n] (a K = 1 product: the fp32 FMA kernel runs it without a split over K)."""
-    check(lib().rald_op_sgemm_acc(_p(a), a.stride(0), 0, _p(w), w.stride(0), 1, _p(out), out.stride(0), out.shape[0], out.shape[1], 1, 1.0,
-                                  C.c_void_p(_stream())))
+    check(lib().rald_op_sgemm_acc(a.data_ptr(), a.stride(0), 0, w.data_ptr(), w.stride(0), 1, out.data_ptr(), out.stride(0), out.shape[0],
+                                  out.shape[1], 1, 1.0, _stream()))
 
 
 def attention_bwd_rows(q, kv, O, dO, dq, dkv, Bn: int, H: int, nq: int, k_rows: int, nk: int) -> None:
@@ -467,6 +468,7 @@ def attention_bwd_rows(q, kv, O, dO, dq, dkv, Bn: int, H: int, nq: int, k_rows: 
     first nk rows per sample are keys (nk need not be a multiple of 64: the last tile is masked)."""
     D = H * HEAD
     scratch = torch.empty(2, Bn * H * nq, device=O.device, dtype=torch.float32)
-    check(lib().rald_op_attention_bwd(_p(q), D, nq * D, _p(kv), 2 * D, k_rows * 2 * D, _p(kv[:, D:]), 2 * D, k_rows * 2 * D, _p(O), D, nq * D,
-                                      _p(dO), D, nq * D, _p(dq), D, nq * D, _p(dkv), 2 * D, k_rows * 2 * D, _p(dkv[:, D:]), 2 * D, k_rows * 2 * D,
-                                      _p(scratch[0]), _p(scratch[1]), nq, nk, H, Bn, HEAD ** -0.5, C.c_void_p(_stream())))
+    check(lib().rald_op_attention_bwd(q.data_ptr(), D, nq * D, kv.data_ptr(), 2 * D, k_rows * 2 * D, kv[:, D:].data_ptr(), 2 * D, k_rows * 2 * D,
+                                      O.data_ptr(), D, nq * D, dO.data_ptr(), D, nq * D, dq.data_ptr(), D, nq * D, dkv.data_ptr(), 2 * D,
+                                      k_rows * 2 * D, dkv[:, D:].data_ptr(), 2 * D, k_rows * 2 * D, scratch[0].data_ptr(), scratch[1].data_ptr(), nq,
+                                      nk, H, Bn, HEAD ** -0.5, _stream()))

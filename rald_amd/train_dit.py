@@ -17,7 +17,6 @@ shipped config trains jointly (``unfreeze_radar_enc``), and the optimizer step: 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional
 
@@ -27,16 +26,13 @@ from . import train_ops as TO
 from ._handles import _stream, op_gemm_nt, op_layernorm
 from ._lib import check, lib
 
-_p = TO._p
-
-
 def sgemm_acc(A, B, out, trans_a=False, trans_b=False, alpha=1.0, M=None, N=None, K=None):
     """out[m, n] += alpha * sum_k A(m, k) B(n, k) in fp32 (see rald_op_sgemm_acc)."""
     M = M if M is not None else (A.shape[1] if trans_a else A.shape[0])
     K = K if K is not None else (A.shape[0] if trans_a else A.shape[1])
     N = N if N is not None else (B.shape[1] if trans_b else B.shape[0])
-    check(lib().rald_op_sgemm_acc(_p(A), A.stride(0), int(trans_a), _p(B), B.stride(0), int(trans_b), _p(out), out.stride(0), M, N, K, alpha,
-                                  C.c_void_p(_stream())))
+    check(lib().rald_op_sgemm_acc(A.data_ptr(), A.stride(0), int(trans_a), B.data_ptr(), B.stride(0), int(trans_b), out.data_ptr(), out.stride(0), M,
+                                  N, K, alpha, _stream()))
     return out
 
 
@@ -48,13 +44,13 @@ def linear_f32(x, W, b=None):
 
 def silu(x):
     y = torch.empty_like(x)
-    check(lib().rald_op_silu_fwd(_p(x), _p(y), x.numel(), C.c_void_p(_stream())))
+    check(lib().rald_op_silu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()))
     return y
 
 
 def silu_bwd(x_pre, dy):
     dx = torch.empty_like(x_pre)
-    check(lib().rald_op_silu_bwd(_p(x_pre), _p(dy), _p(dx), x_pre.numel(), C.c_void_p(_stream())))
+    check(lib().rald_op_silu_bwd(x_pre.data_ptr(), dy.data_ptr(), dx.data_ptr(), x_pre.numel(), _stream()))
     return dx
 
 
@@ -177,7 +173,8 @@ class DitTrainer:
         coef3 = scal[:, 3:6].contiguous()
         loss = torch.zeros(1, device=self.dev, dtype=torch.float64)
         dF = torch.empty_like(st["F"])
-        check(lib().rald_op_edm_loss_grad(_p(st["F"]), _p(xn), _p(y2), _p(coef3), NL * Cc, M * Cc, _p(dF), _p(None), _p(loss), C.c_void_p(_stream())))
+        check(lib().rald_op_edm_loss_grad(st["F"].data_ptr(), xn.data_ptr(), y2.data_ptr(), coef3.data_ptr(), NL * Cc, M * Cc, dF.data_ptr(), None,
+                                          loss.data_ptr(), _stream()))
         dcond = self.backward_core(st, dF)
         return loss[0], dcond
 
@@ -210,7 +207,7 @@ class DitTrainer:
         xin = (xn.view(Bn, NL * Cc) * c_in[:, None]).view(M, Cc).contiguous()
         # ---- timestep embedding (:217-219) and the 72 AdaLN modulations (:127-131) ---------------------------
         pe = torch.empty(Bn, P["map_layer0.weight"].shape[1], **f32)
-        check(lib().rald_op_posemb(_p(c_noise), _p(pe), Bn, pe.shape[1], C.c_void_p(_stream())))
+        check(lib().rald_op_posemb(c_noise.data_ptr(), pe.data_ptr(), Bn, pe.shape[1], _stream()))
         a0 = linear_f32(pe, P["map_layer0.weight"].data, P["map_layer0.bias"].data)
         e0 = silu(a0)
         a1 = linear_f32(e0, P["map_layer1.weight"].data, P["map_layer1.bias"].data)

@@ -16,21 +16,15 @@ PyTorch owns the buffers only.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import train_ops as TO
-from ._handles import _stream, op_gemm_nt
+from ._handles import _opt, _scratch, _stream, op_gemm_nt
 from ._lib import check, lib
 
-_p = TO._p
 CH_MULT = (1, 1, 2, 2, 4)            # models_radar_encoder.py factories (ch_mult of ae_ch64_mult5_*)
-
-
-def _st():
-    return C.c_void_p(_stream())
 
 
 def pack_conv(W: torch.Tensor, dgrad: bool = False, pad_to: Optional[int] = None) -> torch.Tensor:
@@ -39,7 +33,7 @@ def pack_conv(W: torch.Tensor, dgrad: bool = False, pad_to: Optional[int] = None
     inner = Cout if dgrad else Cin
     pad_to = pad_to or inner
     out = torch.empty((Cin if dgrad else Cout), 27, pad_to, device=W.device, dtype=torch.bfloat16)
-    check(lib().rald_op_conv_pack_weights(_p(W.contiguous()), _p(out), Cout, Cin, pad_to, int(dgrad), _st()))
+    check(lib().rald_op_conv_pack_weights(W.contiguous().data_ptr(), out.data_ptr(), Cout, Cin, pad_to, int(dgrad), _stream()))
     return out
 
 
@@ -51,10 +45,11 @@ def conv3d(x16: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, resid: Optio
     if out_bf16:
         assert resid is None
         out = torch.empty(B, D // stride, H // stride, W // stride, Cout, device=x16.device, dtype=torch.bfloat16)
-        check(lib().rald_op_conv3d_bf16(_p(x16), _p(wp), _p(bias), _p(out), B, D, H, W, Cin, Cout, stride, pad, _st()))
+        check(lib().rald_op_conv3d_bf16(x16.data_ptr(), wp.data_ptr(), _opt(bias), out.data_ptr(), B, D, H, W, Cin, Cout, stride, pad, _stream()))
         return out
     out = torch.empty(B, D // stride, H // stride, W // stride, Cout, device=x16.device, dtype=torch.float32)
-    check(lib().rald_op_conv3d(_p(x16), _p(wp), _p(bias), _p(resid), _p(out), B, D, H, W, Cin, Cout, stride, pad, _st()))
+    check(lib().rald_op_conv3d(x16.data_ptr(), wp.data_ptr(), _opt(bias), _opt(resid), out.data_ptr(), B, D, H, W, Cin, Cout, stride, pad,
+                               _stream()))
     return out
 
 
@@ -64,7 +59,7 @@ def groupnorm(x: torch.Tensor, gamma, beta, swish: bool):
     S = x.numel() // (B * Cc)
     y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
     buf = torch.empty(B * 64 * (1 + (S + 511) // 512), device=x.device, dtype=torch.float64)   # stats + per-block partials
-    check(lib().rald_op_groupnorm(_p(x), _p(gamma), _p(beta), _p(y), _p(buf), B, S, Cc, int(swish), _st()))
+    check(lib().rald_op_groupnorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), buf.data_ptr(), B, S, Cc, int(swish), _stream()))
     return y, buf[:B * 64].view(B, 32, 2)
 
 
@@ -73,7 +68,8 @@ def groupnorm_apply(x: torch.Tensor, stats: torch.Tensor, gamma, beta, swish: bo
     B, Cc = x.shape[0], x.shape[-1]
     S = x.numel() // (B * Cc)
     y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    check(lib().rald_op_groupnorm_apply(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), B, S, Cc, int(swish), _st()))
+    check(lib().rald_op_groupnorm_apply(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), B, S, Cc, int(swish),
+                                        _stream()))
     return y
 
 
@@ -84,11 +80,12 @@ def groupnorm_bwd(x, stats, gamma, beta, da, dx, dgamma, dbeta, swish: bool, acc
     scratch = torch.empty((lib().rald_op_groupnorm_bwd_scratch_bytes(B, S, Cc) + 7) // 8, device=x.device, dtype=torch.float64)
     if dx_bf16 is None:
         assert da.dtype == torch.float32
-        check(lib().rald_op_groupnorm_bwd(_p(x), _p(stats), _p(gamma), _p(beta), _p(da), _p(dx), _p(dgamma), _p(dbeta), _p(scratch), B, S, Cc,
-                                          int(swish), int(accumulate), _st()))
+        check(lib().rald_op_groupnorm_bwd(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), da.data_ptr(), _opt(dx),
+                                          dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), B, S, Cc, int(swish), int(accumulate), _stream()))
     else:
-        check(lib().rald_op_groupnorm_bwd_cast(_p(x), _p(stats), _p(gamma), _p(beta), _p(da), int(da.dtype == torch.bfloat16), _p(dx), _p(dx_bf16),
-                                               _p(dgamma), _p(dbeta), _p(scratch), B, S, Cc, int(swish), int(accumulate), _st()))
+        check(lib().rald_op_groupnorm_bwd_cast(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), da.data_ptr(),
+                                               int(da.dtype == torch.bfloat16), _opt(dx), dx_bf16.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                               scratch.data_ptr(), B, S, Cc, int(swish), int(accumulate), _stream()))
 
 
 def _zero_bias(n, dev):
@@ -105,7 +102,7 @@ def conv_dgrad(dy: torch.Tensor, W: torch.Tensor, out_bf16: bool = False) -> tor
         dy16 = dy.contiguous()                               # already what the convolution reads (the caller's one bf16 copy of dy)
     else:
         dy16 = torch.empty(*dy.shape[:-1], cpad, device=dy.device, dtype=torch.bfloat16)
-        check(lib().rald_op_pad_channels(_p(dy.float() if dy.dtype != torch.float32 else dy), _p(dy16), M, Cout, cpad, _st()))
+        check(lib().rald_op_pad_channels((dy.float() if dy.dtype != torch.float32 else dy).data_ptr(), dy16.data_ptr(), M, Cout, cpad, _stream()))
     return conv3d(dy16, pack_conv(W, dgrad=True, pad_to=cpad), _zero_bias(Cin, dy.device), None, 1, 1, out_bf16=out_bf16)
 
 
@@ -113,7 +110,7 @@ def down_dgrad(dy: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     """Gradient w.r.t. the input of Downsample (:37-41, F.pad(0,1) + k3 s2 p0): dy [B, OD, OH, OW, C] -> [B, 2OD, 2OH, 2OW, C]."""
     B, OD, OH, OW, Cc = dy.shape
     up = torch.empty(B, 2 * OD, 2 * OH, 2 * OW, Cc, device=dy.device, dtype=torch.bfloat16)
-    check(lib().rald_op_zero_insert2(_p(dy), _p(up), B, OD, OH, OW, Cc, _st()))
+    check(lib().rald_op_zero_insert2(dy.data_ptr(), up.data_ptr(), B, OD, OH, OW, Cc, _stream()))
     return conv3d(up, pack_conv(W, dgrad=True), _zero_bias(W.shape[1], dy.device), None, 1, 2)
 
 
@@ -132,8 +129,9 @@ def conv_wgrad(dy: torch.Tensor, x16: torch.Tensor, dW: torch.Tensor, dbias: Opt
     # the voxel ranges meet in a workspace and are summed in order by a second launch (no atomics: bit-reproducible, and 4-13 x faster below
     # full resolution - csrc/gemm_tn.hip)
     nbytes = lib().rald_op_conv3d_wgrad_workspace_bytes(B, ID, IH, IW, Cin, Cout, stride, pad)
-    ws = torch.empty(max(nbytes, 16), device=dy16.device, dtype=torch.uint8)
-    check(lib().rald_op_conv3d_wgrad_ws(_p(dy16), _p(x16), _p(dW), _p(dbias), B, ID, IH, IW, Cin, Cout, stride, pad, _p(ws), nbytes, _st()))
+    ws = _scratch(nbytes, dy16.device)
+    check(lib().rald_op_conv3d_wgrad_ws(dy16.data_ptr(), x16.data_ptr(), dW.data_ptr(), _opt(dbias), B, ID, IH, IW, Cin, Cout, stride, pad,
+                                        ws.data_ptr(), nbytes, _stream()))
 
 
 def _g(p: torch.nn.Parameter) -> torch.Tensor:
@@ -146,7 +144,8 @@ def _sgemm(A, B, out, trans_a=False, trans_b=False):
     M = A.shape[1] if trans_a else A.shape[0]
     K = A.shape[0] if trans_a else A.shape[1]
     N = B.shape[1] if trans_b else B.shape[0]
-    check(lib().rald_op_sgemm_acc(_p(A), A.stride(0), int(trans_a), _p(B), B.stride(0), int(trans_b), _p(out), out.stride(0), M, N, K, 1.0, _st()))
+    check(lib().rald_op_sgemm_acc(A.data_ptr(), A.stride(0), int(trans_a), B.data_ptr(), B.stride(0), int(trans_b), out.data_ptr(), out.stride(0), M,
+                                  N, K, 1.0, _stream()))
     return out
 
 
@@ -229,10 +228,10 @@ class EncoderTrainer:
         Sm = torch.empty(B, S, S, device=x.device, dtype=torch.float32)
         TO.gemm2(q, Cc, S * Cc, 0, k, Cc, S * Cc, 0, Sm, S, S * S, 0, S, S, Cc, B, 1, epilogue=1)
         lse = torch.empty(B, S, device=x.device, dtype=torch.float32)
-        check(lib().rald_op_row_lse(_p(Sm), B * S, S, scale, _p(lse), _st()))
+        check(lib().rald_op_row_lse(Sm.data_ptr(), B * S, S, scale, lse.data_ptr(), _stream()))
         Pm = torch.empty(B, S, S, device=x.device, dtype=torch.bfloat16)
         Ssc = Sm * scale                                                # [B,64,64]: tiny
-        check(lib().rald_op_softmax_rows(_p(Ssc), S, _p(Pm), S, B * S, S, _st()))
+        check(lib().rald_op_softmax_rows(Ssc.data_ptr(), S, Pm.data_ptr(), S, B * S, S, _stream()))
         vT = TO.transpose(v, S, Cc, Cc, B, S * Cc).view(B, Cc, S)
         o = torch.empty(B * S, Cc, device=x.device, dtype=torch.bfloat16)
         TO.gemm2(Pm, S, S * S, 0, vT, S, Cc * S, 0, o, Cc, S * Cc, 0, S, Cc, S, B, 1)
@@ -256,9 +255,10 @@ class EncoderTrainer:
         dP = torch.empty(B, S, S, device=x.device, dtype=torch.float32)
         TO.gemm2(do, Cc, S * Cc, 0, v, Cc, S * Cc, 0, dP, S, S * S, 0, S, S, Cc, B, 1, epilogue=1)
         delta = torch.empty(B, S, device=x.device, dtype=torch.float32)
-        check(lib().rald_op_rowdot(_p(do), _p(o), B * S, Cc, _p(delta), _st()))
+        check(lib().rald_op_rowdot(do.data_ptr(), o.data_ptr(), B * S, Cc, delta.data_ptr(), _stream()))
         dS = torch.empty(B, S, S, device=x.device, dtype=torch.bfloat16)
-        check(lib().rald_op_attn_bwd_elem(_p(Sm), _p(dP), _p(lse), _p(delta), B, S, S, S, 1, scale, 0, _p(None), _p(dS), _st()))
+        check(lib().rald_op_attn_bwd_elem(Sm.data_ptr(), dP.data_ptr(), lse.data_ptr(), delta.data_ptr(), B, S, S, S, 1, scale, 0, None,
+                                          dS.data_ptr(), _stream()))
         tb = lambda t, r, c: TO.transpose(t, r, c, c, B, r * c).view(B, c, r)                  # per-sample transpose
         dq = torch.empty(B * S, Cc, device=x.device, dtype=torch.bfloat16)
         dk, dv = torch.empty_like(dq), torch.empty_like(dq)
@@ -283,7 +283,8 @@ class EncoderTrainer:
         ch = self.ch
         cube = cube.contiguous()
         x = torch.empty(B, R, A, E, ch, device=self.dev, dtype=torch.float32)
-        check(lib().rald_op_conv_in(_p(cube), cch, 1, _p(self.w("conv_in.weight")), _p(self.w("conv_in.bias")), _p(x), B, R, A, E, ch, _st()))
+        check(lib().rald_op_conv_in(cube.data_ptr(), cch, 1, self.w("conv_in.weight").data_ptr(), self.w("conv_in.bias").data_ptr(), x.data_ptr(), B,
+                                    R, A, E, ch, _stream()))
         self.saved.append(("conv_in", cube))
         cin = ch
         for l in range(5):
@@ -352,7 +353,7 @@ class EncoderTrainer:
                 Bc, R, A, E, cch = cube.shape
                 # dW [ch][1][27] = dy^T . patches (27-neighbourhoods of the one input channel as bf16 rows of 32), dbias from the same launch
                 pat = torch.empty(Bc * R * A * E, 32, device=cube.device, dtype=torch.bfloat16)
-                check(lib().rald_op_patches27(_p(cube), cch, _p(pat), Bc, R, A, E, _st()))
+                check(lib().rald_op_patches27(cube.data_ptr(), cch, pat.data_ptr(), Bc, R, A, E, _stream()))
                 dw32 = torch.zeros(self.ch, 32, device=cube.device, dtype=torch.float32)
                 TO.lin_wgrad(dx.view(-1, self.ch), pat, dw32, _g(self.p("conv_in.bias")))
                 _g(self.p("conv_in.weight")).view(self.ch, 27).add_(dw32[:, :27])

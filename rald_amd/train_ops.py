@@ -16,39 +16,34 @@ the loop over blocks, embeddings and loss live in train_dit.py, the radar encode
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Tuple
 
 import torch
 
-from ._handles import _ptr, _stream, op_attention, op_attention_vrow, op_gemm_nt, op_gemm_tn, op_layernorm
+from ._handles import _opt, _stream, op_attention, op_attention_vrow, op_gemm_nt, op_gemm_tn, op_layernorm
 from ._lib import check, lib
 
 HEAD = 64
 
 
-def _p(t):
-    return C.c_void_p(_ptr(t) if t is not None else 0)
-
-
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    check(lib().rald_op_cast_bf16(_p(x), _p(out), x.numel(), C.c_void_p(_stream())))
+    check(lib().rald_op_cast_bf16(x.data_ptr(), out.data_ptr(), x.numel(), _stream()))
     return out
 
 
 def gemm2(A, lda, sA, sA2, B, ldb, sB, sB2, out, ldc, sC, sC2, M, N, K, batch, batch2, epilogue=0, alpha=1.0, bias=None):
     """C = alpha * A.B^T (+bias) with an outer and an inner batch; operands are (tensor-with-offset, ld, strides)."""
-    check(lib().rald_op_gemm_nt2(_p(A), lda, sA, sA2, _p(B), ldb, sB, sB2, _p(out), ldc, sC, sC2, _p(bias), M, N, K, batch, batch2, alpha,
-                                 epilogue, C.c_void_p(_stream())))
+    check(lib().rald_op_gemm_nt2(A.data_ptr(), lda, sA, sA2, B.data_ptr(), ldb, sB, sB2, out.data_ptr(), ldc, sC, sC2, _opt(bias), M, N, K, batch,
+                                 batch2, alpha, epilogue, _stream()))
     return out
 
 
 def transpose(x: torch.Tensor, rows: int, cols: int, ld_in: int, batch: int = 1, stride_in: int = 0, batch2: int = 1, stride_in2: int = 0):
     """[batch][batch2] matrices of `rows` x `cols` inside x (f32 or bf16) -> bf16 [batch, batch2, cols, rows]."""
     out = torch.empty(batch, batch2, cols, rows, device=x.device, dtype=torch.bfloat16)
-    check(lib().rald_op_transpose(_p(x), int(x.dtype == torch.bfloat16), ld_in, stride_in, stride_in2, _p(out), rows, batch2 * cols * rows,
-                                  cols * rows, rows, cols, batch, batch2, C.c_void_p(_stream())))
+    check(lib().rald_op_transpose(x.data_ptr(), int(x.dtype == torch.bfloat16), ld_in, stride_in, stride_in2, out.data_ptr(), rows,
+                                  batch2 * cols * rows, cols * rows, rows, cols, batch, batch2, _stream()))
     return out
 
 
@@ -60,23 +55,23 @@ def T2(x: torch.Tensor) -> torch.Tensor:
 def ln_mod_bwd(x, dh, scale, gstride, rows_per_group, add_one, dx, dscale, dshift, eps=1e-5, dx_bf16=None):
     """dx += LayerNorm-mod backward of dh (fp32, in place); dx_bf16 (optional, bf16 [rows, 512]) receives the updated dx rounded to bf16."""
     if dx_bf16 is not None:
-        check(lib().rald_op_ln_mod_bwd_cast(_p(x), _p(dh), _p(scale), gstride, rows_per_group, add_one, eps, x.shape[0], x.shape[1], _p(dx),
-                                            _p(dx_bf16), _p(dscale), _p(dshift), C.c_void_p(_stream())))
+        check(lib().rald_op_ln_mod_bwd_cast(x.data_ptr(), dh.data_ptr(), scale.data_ptr(), gstride, rows_per_group, add_one, eps, x.shape[0],
+                                            x.shape[1], dx.data_ptr(), dx_bf16.data_ptr(), dscale.data_ptr(), dshift.data_ptr(), _stream()))
         return
-    check(lib().rald_op_ln_mod_bwd(_p(x), _p(dh), _p(scale), gstride, rows_per_group, add_one, eps, x.shape[0], x.shape[1], _p(dx), _p(dscale),
-                                   _p(dshift), C.c_void_p(_stream())))
+    check(lib().rald_op_ln_mod_bwd(x.data_ptr(), dh.data_ptr(), scale.data_ptr(), gstride, rows_per_group, add_one, eps, x.shape[0], x.shape[1],
+                                   dx.data_ptr(), dscale.data_ptr(), dshift.data_ptr(), _stream()))
 
 
 def geglu_fwd(u: torch.Tensor) -> torch.Tensor:
     M, two_i = u.shape
     hid = torch.empty(M, two_i // 2, device=u.device, dtype=torch.bfloat16)
-    check(lib().rald_op_geglu_fwd(_p(u), _p(hid), M, two_i // 2, C.c_void_p(_stream())))
+    check(lib().rald_op_geglu_fwd(u.data_ptr(), hid.data_ptr(), M, two_i // 2, _stream()))
     return hid
 
 
 def geglu_bwd(u: torch.Tensor, dhid: torch.Tensor) -> torch.Tensor:
     du = torch.empty_like(u)
-    check(lib().rald_op_geglu_bwd(_p(u), _p(dhid), _p(du), u.shape[0], u.shape[1] // 2, C.c_void_p(_stream())))
+    check(lib().rald_op_geglu_bwd(u.data_ptr(), dhid.data_ptr(), du.data_ptr(), u.shape[0], u.shape[1] // 2, _stream()))
     return du
 
 
@@ -93,7 +88,7 @@ def lin_wgrad(dy: torch.Tensor, x_in: torch.Tensor, dW: torch.Tensor, dbias: tor
 
 def colsum(x: torch.Tensor, out: torch.Tensor) -> None:
     """out[n] += sum_m x[m, n]"""
-    check(lib().rald_op_colsum(_p(x), int(x.dtype == torch.bfloat16), x.stride(0), x.shape[0], x.shape[1], _p(out), C.c_void_p(_stream())))
+    check(lib().rald_op_colsum(x.data_ptr(), int(x.dtype == torch.bfloat16), x.stride(0), x.shape[0], x.shape[1], out.data_ptr(), _stream()))
 
 
 def attention_backward(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, nq: int, nk: int, dq, ld_dq, dk, ld_dk, dv, ld_dv):
@@ -104,9 +99,10 @@ def attention_backward(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, nq: int, 
     if nq % 128 or nk % 64:
         return attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn, H, nq, nk, dq, ld_dq, dk, ld_dk, dv, ld_dv)
     scratch = torch.empty(2, Bn * H * nq, device=O.device, dtype=torch.float32)
-    check(lib().rald_op_attention_bwd(_p(q), ldq, nq * ldq, _p(k), ldk, nk * ldk, _p(v), ldv, nk * ldv, _p(O), O.stride(0), nq * O.stride(0),
-                                      _p(dO), dO.stride(0), nq * dO.stride(0), _p(dq), ld_dq, nq * ld_dq, _p(dk), ld_dk, nk * ld_dk,
-                                      _p(dv), ld_dv, nk * ld_dv, _p(scratch[0]), _p(scratch[1]), nq, nk, H, Bn, HEAD ** -0.5, C.c_void_p(_stream())))
+    check(lib().rald_op_attention_bwd(q.data_ptr(), ldq, nq * ldq, k.data_ptr(), ldk, nk * ldk, v.data_ptr(), ldv, nk * ldv, O.data_ptr(),
+                                      O.stride(0), nq * O.stride(0), dO.data_ptr(), dO.stride(0), nq * dO.stride(0), dq.data_ptr(), ld_dq,
+                                      nq * ld_dq, dk.data_ptr(), ld_dk, nk * ld_dk, dv.data_ptr(), ld_dv, nk * ld_dv, scratch[0].data_ptr(),
+                                      scratch[1].data_ptr(), nq, nk, H, Bn, HEAD ** -0.5, _stream()))
 
 
 def attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, nq: int, nk: int, dq, ld_dq, dk, ld_dk, dv, ld_dv):
@@ -119,11 +115,11 @@ def attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, n
     gemm2(q, ldq, nq * ldq, HEAD, k, ldk, nk * ldk, HEAD, S, nk, H * nq * nk, nq * nk, nq, nk, HEAD, Bn, H, epilogue=1)
     gemm2(dO, H * HEAD, nq * H * HEAD, HEAD, v, ldv, nk * ldv, HEAD, dP, nk, H * nq * nk, nq * nk, nq, nk, HEAD, Bn, H, epilogue=1)
     lse, delta = f32(Bn, H, nq), f32(Bn, H, nq)
-    check(lib().rald_op_row_lse(_p(S), Bn * H * nq, nk, scale, _p(lse), C.c_void_p(_stream())))
-    check(lib().rald_op_rowdot_heads(_p(dO), _p(O), Bn * nq, H, nq, _p(delta), C.c_void_p(_stream())))
+    check(lib().rald_op_row_lse(S.data_ptr(), Bn * H * nq, nk, scale, lse.data_ptr(), _stream()))
+    check(lib().rald_op_rowdot_heads(dO.data_ptr(), O.data_ptr(), Bn * nq, H, nq, delta.data_ptr(), _stream()))
     dS = b16(Bn, H, nq, nk)
-    check(lib().rald_op_attn_bwd_elem(_p(S), _p(dP), _p(lse), _p(delta), Bn * H, nq, nk, nq, 1, scale, 0, _p(None), _p(dS),
-                                      C.c_void_p(_stream())))
+    check(lib().rald_op_attn_bwd_elem(S.data_ptr(), dP.data_ptr(), lse.data_ptr(), delta.data_ptr(), Bn * H, nq, nk, nq, 1, scale, 0, None,
+                                      dS.data_ptr(), _stream()))
     kT = transpose(k, nk, HEAD, ldk, Bn, nk * ldk, H, HEAD)                     # [Bn, H, 64, nk]
     gemm2(dS, nk, H * nq * nk, nq * nk, kT, nk, H * HEAD * nk, HEAD * nk, dq, ld_dq, nq * ld_dq, HEAD, nq, HEAD, nk, Bn, H)
     # key side: transposed orientation
@@ -131,8 +127,8 @@ def attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, n
     gemm2(k, ldk, nk * ldk, HEAD, q, ldq, nq * ldq, HEAD, ST, nq, H * nk * nq, nk * nq, nk, nq, HEAD, Bn, H, epilogue=1)
     gemm2(v, ldv, nk * ldv, HEAD, dO, H * HEAD, nq * H * HEAD, HEAD, dPT, nq, H * nk * nq, nk * nq, nk, nq, HEAD, Bn, H, epilogue=1)
     PT, dST = b16(Bn, H, nk, nq), b16(Bn, H, nk, nq)
-    check(lib().rald_op_attn_bwd_elem(_p(ST), _p(dPT), _p(lse), _p(delta), Bn * H, nk, nq, nq, 1, scale, 1, _p(PT), _p(dST),
-                                      C.c_void_p(_stream())))
+    check(lib().rald_op_attn_bwd_elem(ST.data_ptr(), dPT.data_ptr(), lse.data_ptr(), delta.data_ptr(), Bn * H, nk, nq, nq, 1, scale, 1,
+                                      PT.data_ptr(), dST.data_ptr(), _stream()))
     qT = transpose(q, nq, HEAD, ldq, Bn, nq * ldq, H, HEAD)                     # [Bn, H, 64, nq]
     dOT = transpose(dO, nq, HEAD, H * HEAD, Bn, nq * H * HEAD, H, HEAD)
     gemm2(dST, nq, H * nk * nq, nk * nq, qT, nq, H * HEAD * nq, HEAD * nq, dk, ld_dk, nk * ld_dk, HEAD, nk, HEAD, nq, Bn, H)

@@ -16,13 +16,12 @@ Names follow what they replace: ``FlatAdamW`` has ``param_groups`` / ``step`` / 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
-from ._handles import _ptr, _stream
+from ._handles import _stream
 from ._lib import check, lib
 
 ALIGN = 4            # elements: every tensor starts on a 16-byte boundary of the flat buffer
@@ -88,9 +87,9 @@ class FlatAdamW:
         next ``step`` (no extra pass, no host sync).  ``pre_scale`` multiplies the gradient first - 1/world
         after a SUM all-reduce."""
         L = lib()
-        check(L.rald_optim_grad_sumsq(C.c_void_p(_ptr(self.flat_g)), self.numel, C.c_void_p(_ptr(self._sumsq)), C.c_void_p(_stream())))
-        check(L.rald_optim_clip_coef(C.c_void_p(_ptr(self._sumsq)), float(pre_scale), float(max_norm if max_norm else 0.0),
-                                     C.c_void_p(_ptr(self._norm_coef)), C.c_void_p(_stream())))
+        check(L.rald_optim_grad_sumsq(self.flat_g.data_ptr(), self.numel, self._sumsq.data_ptr(), _stream()))
+        check(L.rald_optim_clip_coef(self._sumsq.data_ptr(), float(pre_scale), float(max_norm if max_norm else 0.0),
+                                     self._norm_coef.data_ptr(), _stream()))
         self._have_coef = True
         return self._norm_coef[0]
 
@@ -103,10 +102,10 @@ class FlatAdamW:
         if use_ema and self.flat_ema is None:
             raise RuntimeError("FlatAdamW was built with ema=False")
         check(lib().rald_optim_adamw_ema(
-            C.c_void_p(_ptr(self.flat_p)), C.c_void_p(_ptr(self.flat_g)), C.c_void_p(_ptr(self.exp_avg)), C.c_void_p(_ptr(self.exp_avg_sq)),
-            C.c_void_p(_ptr(self.flat_ema) if use_ema else 0), self.numel, C.c_void_p(_ptr(self._norm_coef) + 4 if self._have_coef else 0),
+            self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+            self.flat_ema.data_ptr() if use_ema else None, self.numel, self._norm_coef.data_ptr() + 4 if self._have_coef else None,
             float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count,
-            float(ema_rate if use_ema else 0.0), int(write_back_grads), C.c_void_p(_stream())))
+            float(ema_rate if use_ema else 0.0), int(write_back_grads), _stream()))
         self._have_coef = False
         self.mark_params_changed()
 
@@ -121,7 +120,7 @@ class FlatAdamW:
         """engine_generation.update_ema (:29-40) on the flat buffers (for iterations without a step)."""
         if self.flat_ema is None:
             raise RuntimeError("FlatAdamW was built with ema=False")
-        check(lib().rald_optim_ema(C.c_void_p(_ptr(self.flat_ema)), C.c_void_p(_ptr(self.flat_p)), self.numel, float(rate), C.c_void_p(_stream())))
+        check(lib().rald_optim_ema(self.flat_ema.data_ptr(), self.flat_p.data_ptr(), self.numel, float(rate), _stream()))
 
     # torch.optim.AdamW.state_dict() layout, so the reference's checkpoints ('optimizer' entry,
     # utils/misc.py:309-316) round-trip

@@ -130,7 +130,59 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(L, name), f"{name} declared in rald_hip.h but not exported"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is res and tuple(fn.argtypes) == tuple(args), name
     assert L.rald_version() >= 1
+
+
+def test_c_abi_signatures_are_derived_from_the_header():
+    """_lib reads restype / argtypes off the header's prototypes: scalars keep their width, every pointer is a c_void_p."""
+    import ctypes as C
+    from rald_amd import _lib
+    P, I32, I64, F, D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
+    S = _lib.SIGNATURES
+    assert S["rald_optim_adamw_ema"] == (I32, [P, P, P, P, P, I64, P, D, D, D, D, D, I64, D, I32, P])
+    assert S["rald_dit_profile_set_kinds"] == (I32, [P, C.c_uint32])
+    assert S["rald_last_error"] == (C.c_char_p, [])
+    assert S["rald_dit_destroy"] == (None, [P])
+    assert S["rald_lidar_create"] == (I32, [P, P])                                 # const rald_lidar_config*, rald_lidar**
+    assert S["rald_debug_f16_saturation_count"] == (I64, [I32])
+    assert S["rald_dit_sample"] == (I32, [P, P, I32, P, I32, F, F, F, P, P])
+    assert S["rald_op_ae_encode_tables"] == (I32, [I32, I32, I32, I32, P, P])       # const float* const*, float* const*
+    assert len(S["rald_op_attention_bwd"][1]) == 32
+
+
+def test_c_abi_unknown_type_is_refused_at_load(tmp_path):
+    from rald_amd import _lib
+    h = tmp_path / "h.h"
+    h.write_text("/* size_t is not part of the ABI */\nint rald_ok(int32_t a, const float* b);\nint rald_bad(int32_t a, size_t n);\n")
+    with pytest.raises(RuntimeError, match=r"size_t.*rald_bad"):
+        _lib._parse(str(h))
+
+
+def test_c_abi_config_structs_match_the_header_layout():
+    """sizeof and field offsets of the five config structs, worked out by hand from include/rald_hip.h."""
+    import ctypes as C
+    from rald_amd import _lib
+    off = lambda S: {name: getattr(S, name).offset for name, _ in S._fields_}
+    dit = ["n_latents", "channels", "depth", "n_heads", "d_head", "t_channels", "context_dim", "n_cond_tokens", "with_radar_enc",
+           "enc_hidden_ch", "enc_radar_ch", "radar_r", "radar_a", "radar_e", "sigma_data", "qkv_dtype"]
+    assert C.sizeof(_lib.DitConfig) == 64 and off(_lib.DitConfig) == {n: 4 * i for i, n in enumerate(dit)}
+    assert _lib.DitConfig.sigma_data.size == 4 and _lib.DitConfig._fields_[14][1] is C.c_float
+    ae = ["dim", "num_latents", "latent_dim", "depth", "heads", "dim_head", "num_inputs", "query_type"]
+    assert C.sizeof(_lib.AeConfig) == 32 and off(_lib.AeConfig) == {n: 4 * i for i, n in enumerate(ae)}
+    dsp = ["ntx", "nrx", "n_chirps", "n_samples", "range_fft", "doppler_fft", "angle_fft", "elevation_fft"]
+    assert C.sizeof(_lib.RadarDspConfig) == 48
+    assert off(_lib.RadarDspConfig) == {**{n: 4 * i for i, n in enumerate(dsp)}, "crop_low": 32, "crop_high": 40}
+    pts = ["in_r", "in_a", "in_e", "in_channels", "tgt_r", "tgt_a", "tgt_e"]
+    assert C.sizeof(_lib.RadarPointsConfig) == 40
+    assert off(_lib.RadarPointsConfig) == {**{n: 4 * i for i, n in enumerate(pts)}, "num_points": 32}      # int64_t after 4 bytes of padding
+    assert _lib.RadarPointsConfig.num_points.size == 8
+    lid = ["max_points_per_voxel", "max_voxels", "num_point_features", "view_cone_mode", "norm_anisotropy", "norm_isotropy"]
+    assert C.sizeof(_lib.LidarConfig) == 272
+    assert off(_lib.LidarConfig) == {"pc_range": 0, "voxel_size": 48, **{n: 72 + 4 * i for i, n in enumerate(lid)}, "extrinsic": 96, "fov": 224}
+    assert (_lib.LidarConfig.pc_range.size, _lib.LidarConfig.extrinsic.size, _lib.LidarConfig.fov.size) == (48, 128, 48)
 
 
 def test_errors_are_reported_not_crashed():
