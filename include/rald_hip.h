@@ -471,17 +471,12 @@ int rald_op_groupnorm_bwd_cast(const float* x, const double* stats, const float*
  * GroupNorm backward (da_is_bf16 = 1 above) */
 int rald_op_conv3d_bf16(const void* in_bf16, const void* w_packed_bf16, const float* bias, void* out_bf16, int32_t B, int32_t ID, int32_t IH, int32_t IW,
                         int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream);
-/* conv_in (Cin = 1 read in place from channel 0 of the cube) and its weight gradient dW [Cout][27] (accumulated) */
+/* conv_in (Cin = 1 read in place from channel 0 of the cube) */
 int rald_op_conv_in(const float* cube, int32_t cube_ch, int32_t Cin, const float* W, const float* bias, float* out, int32_t B, int32_t D, int32_t H,
                     int32_t Wd, int32_t Cout, void* stream);
-int rald_op_conv_in_wgrad(const float* cube, int32_t cube_ch, const float* dy, int32_t B, int32_t D, int32_t H, int32_t Wd, int32_t Cout, float* dW,
-                          void* stream);
 /* x [M][C] f32 -> bf16 [M][Cpad] zero-filled;  dY [B][OD][OH][OW][C] f32 -> bf16 on the even positions of a 2x grid (Downsample dgrad) */
 int rald_op_pad_channels(const float* x, void* out_bf16, int64_t M, int32_t C, int32_t Cpad, void* stream);
 int rald_op_zero_insert2(const float* dy, void* out_bf16, int32_t B, int32_t OD, int32_t OH, int32_t OW, int32_t C, void* stream);
-/* transposed im2col of output voxels [m0, m0+nchunk): out bf16 [C*27][nchunk], row ci*27 + tap (the weight tensor's own order) */
-int rald_op_im2col_t(const void* x_bf16, void* out_bf16, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t C, int32_t stride, int32_t pad,
-                     int64_t m0, int32_t nchunk, void* stream);
 int rald_op_rowdot(const void* a_bf16, const void* b_bf16, int64_t M, int32_t C, float* out, void* stream);
 int rald_op_softmax_rows(const float* S, int64_t ld_s, void* P_bf16, int64_t ld_p, int32_t rows, int32_t n, void* stream);
 /* Small-batch fused attention sub-blocks (rald_amd/csrc/attn_small.hip; CrossAttention :55-76 + the to_out Linear).
@@ -508,12 +503,9 @@ int rald_op_reduce_resid_ln(const float* part, int32_t slabs, int64_t slab_strid
 /* Streaming query decoder (KLAutoEncoder.decode :417-424; rald_amd/csrc/ae_decode.hip).  _tables: the weight-only tables
  * it is built on, computed on the HOST in double from host tensors of decoder_cross_attn (to_q [d,d], k half of to_kv [d,d],
  * norm weight / bias [d]), point_embed.mlp (weight [d,51], bias [d]) and the folded value vector [d]:
- * t2aug_out [d][64] fp32, l_img_out [64][64] fp16 bits (no GPU needed: what the CPU tests check the folding with).
- * _queries_nw: rald_ae_decode_queries with the waves per workgroup given (8, 12, 16; 0 = default) for tuning runs. */
+ * t2aug_out [d][64] fp32, l_img_out [64][64] fp16 bits (no GPU needed: what the CPU tests check the folding with). */
 int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, const float* norm_w, const float* norm_b, const float* wpe,
                              const float* bpe, const float* wfold, float* t2aug_out, uint16_t* l_img_out);
-int rald_op_ae_decode_queries_nw(rald_ae* h, const void* ctx, const float* queries, int32_t batch, int64_t n_queries, float* out_logits,
-                                 int32_t waves_per_workgroup, void* stream);
 /* Folded encoder (KLAutoEncoder.encode :351-399; rald_amd/csrc/ae_encode.hip): both attentions of the latent queries over the
  * input points run with ONE fp16 row of 52 Fourier features per point as key and value (head dim 64).
  * _tables: the weight-only tables, computed on the HOST in double (no GPU needed).  in[18] = host fp32 tensors in the reference's

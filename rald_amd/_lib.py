@@ -17,7 +17,7 @@ import subprocess
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RALD_LIB_OVERRIDE") or os.path.join(_HERE, "librald_hip.so")
+LIB_PATH = os.path.join(_HERE, "librald_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "rald_hip.h")
 _lock = threading.Lock()
 _lib = None

@@ -67,7 +67,7 @@ struct Ae {
     BlobHeader ctx_header(int B) const;
     int64_t ctx_bytes(int B) const;
     int decode_latents(const float* z, int B, void* ctx, hipStream_t st);
-    int decode_queries(const void* ctx, const float* q, int B, int64_t Q, float* out, hipStream_t st, int nw = 0);
+    int decode_queries(const void* ctx, const float* q, int B, int64_t Q, float* out, hipStream_t st);
 };
 
 }  // namespace rald

@@ -436,13 +436,13 @@ int Ae::decode_latents(const float* z, int B, void* ctx, hipStream_t st) {
     return 0;
 }
 
-int Ae::decode_queries(const void* ctx, const float* q, int B, int64_t Q, float* out, hipStream_t st, int nw) {
+int Ae::decode_queries(const void* ctx, const float* q, int B, int64_t Q, float* out, hipStream_t st) {
     RALD_CHECK(finalized, "ae: weights not finalized");
     RALD_CHECK(ctx && q && out && B >= 1 && Q >= 1, "ae: bad arguments");
     RALD_CHECK((uintptr_t)ctx % 16 == 0, "ae: decoder context must be 16-byte aligned");
     RALD_TRY(ctx_registry.check(ctx, ctx_header(B), st, "decoder context"));
     ctx = (const char*)ctx + BLOB_HEADER_BYTES;
-    return ae_decode_stream(ctx, l_img, q, out, basis, basis_diag, B, Q, cfg.num_latents, c0, st, nw);
+    return ae_decode_stream(ctx, l_img, q, out, basis, basis_diag, B, Q, cfg.num_latents, c0, st);
 }
 
 }  // namespace rald

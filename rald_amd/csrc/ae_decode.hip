@@ -373,8 +373,9 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a)
     }
 }
 
-template <bool DIAG, int NW>
+template <bool DIAG>
 static int launch_decode(const DecodeArgs& a, int B, size_t smem, hipStream_t st) {
+    constexpr int NW = 12;                                         // waves per workgroup (the measured best of 8, 12 and 16)
     auto kern = ae_decode_stream_kernel<DIAG, NW>;
     static bool attr_set = false;
     if (!attr_set) {
@@ -390,20 +391,16 @@ static int launch_decode(const DecodeArgs& a, int B, size_t smem, hipStream_t st
     return 0;
 }
 
-// nw: waves per workgroup (8, 12 or 16; 0 = the measured default) - one workgroup per CU holds the sample's image in LDS
+// one workgroup per CU holds the sample's image in LDS
 int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* queries, float* out, const float* basis, int basis_diag,
-                     int B, int64_t Q, int M, float c0, hipStream_t st, int nw) {
+                     int B, int64_t Q, int M, float c0, hipStream_t st) {
     RALD_CHECK(M % 32 == 0 && M >= 32 && M <= 1024, "ae_decode_stream: num_latents must be a multiple of 32 in [32,1024]");
     RALD_CHECK(B >= 1 && Q >= 1 && B <= 65535, "ae_decode_stream: bad batch / query count");
     DecodeArgs a;
     a.ctx = (const unsigned char*)ctx; a.ctx_stride = ae_ctx_stride(M); a.l_img = l_img; a.queries = queries; a.out = out; a.basis = basis;
     a.Q = Q; a.M = M; a.c0 = c0; a.eps = 1e-5f;
     const size_t smem = (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76) * 4;
-    if (nw == 0) nw = 12;
-    if (nw == 8) return basis_diag ? launch_decode<true, 8>(a, B, smem, st) : launch_decode<false, 8>(a, B, smem, st);
-    if (nw == 12) return basis_diag ? launch_decode<true, 12>(a, B, smem, st) : launch_decode<false, 12>(a, B, smem, st);
-    if (nw == 16) return basis_diag ? launch_decode<true, 16>(a, B, smem, st) : launch_decode<false, 16>(a, B, smem, st);
-    RALD_CHECK(false, "ae_decode_stream: nw must be 0, 8, 12 or 16");
+    return basis_diag ? launch_decode<true>(a, B, smem, st) : launch_decode<false>(a, B, smem, st);
 }
 
 }  // namespace rald

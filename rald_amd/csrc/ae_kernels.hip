@@ -118,35 +118,6 @@ int softmax_dot(const float* S, const float* u, float* out, int64_t rows, int nk
     return 0;
 }
 
-// generic-width variant (any nkeys): one wave per row, strided loop (used when num_latents is not 256/512/1024)
-__global__ __launch_bounds__(256) void softmax_dot_generic_kernel(const float* __restrict__ S, const float* __restrict__ u,
-                                                                  float* __restrict__ out, int64_t rows, int nk,
-                                                                  int rows_per_batch, float c0) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* s = S + row * nk;
-    const float* uu = u + (row / rows_per_batch) * nk;
-    float mx = -1e30f;
-    for (int i = lane; i < nk; i += 64) mx = fmaxf(mx, s[i]);
-    mx = wave_max(mx);
-    float den = 0.f, num = 0.f;
-    for (int i = lane; i < nk; i += 64) {
-        const float e = __expf(s[i] - mx);
-        den += e;
-        num += e * uu[i];
-    }
-    den = wave_sum(den);
-    num = wave_sum(num);
-    if (lane == 0) out[row] = num / den + c0;
-}
-int softmax_dot_generic(const float* S, const float* u, float* out, int64_t rows, int nkeys, int rows_per_batch, float c0, hipStream_t st) {
-    RALD_CHECK(rows > 0 && nkeys > 0 && rows_per_batch > 0, "softmax_dot: empty");
-    hipLaunchKernelGGL(softmax_dot_generic_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, S, u, out, rows, nkeys, rows_per_batch, c0);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-
 // ---- u[row] = LN_affine(x[row]) . w   (the folded value vector; one wave per latent row)
 template <int VPL>
 __global__ __launch_bounds__(256) void ln_dot_kernel(const float* __restrict__ x, const float* __restrict__ gamma,

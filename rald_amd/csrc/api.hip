@@ -151,12 +151,7 @@ int rald_ae_decode_queries(rald_ae* h, const void* ctx, const float* queries, in
     return h->impl.decode_queries(ctx, queries, batch, n_queries, out_logits, (hipStream_t)stream);
 }
 
-// tuning / test entry points of the streaming query decoder (ae_decode.hip)
-int rald_op_ae_decode_queries_nw(rald_ae* h, const void* ctx, const float* queries, int32_t batch, int64_t n_queries, float* out_logits,
-                                 int32_t waves_per_workgroup, void* stream) {
-    RALD_CHECK(h, "null handle");
-    return h->impl.decode_queries(ctx, queries, batch, n_queries, out_logits, (hipStream_t)stream, waves_per_workgroup);
-}
+// test entry point of the streaming query decoder (ae_decode.hip)
 int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, const float* norm_w, const float* norm_b, const float* wpe,
                              const float* bpe, const float* wfold, float* t2aug_out, uint16_t* l_img_out) {
     RALD_CHECK(wq && wk && norm_w && norm_b && wpe && bpe && wfold && t2aug_out && l_img_out && dim >= 64, "rald_op_ae_decode_tables: bad argument");
@@ -516,10 +511,6 @@ int rald_op_conv_in(const float* cube, int32_t cube_ch, int32_t Cin, const float
                     int32_t Wd, int32_t Cout, void* stream) {
     return conv_in_fwd(cube, cube_ch, Cin, W, bias, out, B, D, H, Wd, Cout, (hipStream_t)stream);
 }
-int rald_op_conv_in_wgrad(const float* cube, int32_t cube_ch, const float* dy, int32_t B, int32_t D, int32_t H, int32_t Wd, int32_t Cout, float* dW,
-                          void* stream) {
-    return conv_in_wgrad(cube, cube_ch, dy, B, D, H, Wd, Cout, dW, (hipStream_t)stream);
-}
 int rald_op_conv_pack_weights(const float* W, void* out_bf16, int32_t Cout, int32_t Cin, int32_t pad_to, int32_t dgrad, void* stream) {
     return conv_pack_weights(W, (bf16*)out_bf16, Cout, Cin, pad_to, dgrad, (hipStream_t)stream);
 }
@@ -528,10 +519,6 @@ int rald_op_pad_channels(const float* x, void* out_bf16, int64_t M, int32_t C, i
 }
 int rald_op_zero_insert2(const float* dy, void* out_bf16, int32_t B, int32_t OD, int32_t OH, int32_t OW, int32_t C, void* stream) {
     return zero_insert2(dy, (bf16*)out_bf16, B, OD, OH, OW, C, (hipStream_t)stream);
-}
-int rald_op_im2col_t(const void* x_bf16, void* out_bf16, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t C, int32_t stride, int32_t pad,
-                     int64_t m0, int32_t nchunk, void* stream) {
-    return im2col_t((const bf16*)x_bf16, (bf16*)out_bf16, B, ID, IH, IW, C, stride, pad, m0, nchunk, (hipStream_t)stream);
 }
 int rald_op_rowdot(const void* a_bf16, const void* b_bf16, int64_t M, int32_t C, float* out, void* stream) {
     return rowdot((const bf16*)a_bf16, (const bf16*)b_bf16, M, C, out, (hipStream_t)stream);

@@ -17,7 +17,7 @@
 // EVERY operand reaches the MFMAs through LDS in whole 128-byte lines (LDS-DMA, XOR-swizzled via the source address).  The
 // first version loaded the fragments straight from global memory: 16- and 8-byte pieces of 32 different rows per instruction,
 // ~100 such instructions per wave, and the address unit needed 60-120 cycles for each - 5 700 / 11 800 shader clocks just to
-// ISSUE the loads of the two kernels (tools/probe/small_stamps.hip), 12 / 14 us per launch.
+// ISSUE the loads of the two kernels (tools/probe/small_stamps.hip at 090822f), 12 / 14 us per launch.
 //
 // MFMA operand plumbing (v_mfma_f32_32x32x16_bf16; guide section 3, "an accumulator tile as the next MFMA's operand"):
 // every product is oriented so that the next one sums over the previous accumulator's ROW index - S^T = K.Q^T puts keys on
@@ -30,14 +30,6 @@ namespace rald {
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
-
-// tools/probe/small_stamps.hip only (never defined in the library): shader-clock stamps of one wave at the phase boundaries
-#ifdef RALD_SMALL_STAMPS
-__device__ long long g_small_stamps[2][16];
-#define RALD_STAMP(K, I) do { if (blockIdx.x == 3 && blockIdx.y == 2 && threadIdx.x == 0) g_small_stamps[K][I] = clock64(); } while (0)
-#else
-#define RALD_STAMP(K, I) do { } while (0)
-#endif
 
 // ---- LDS images -------------------------------------------------------------------------------------------------------
 // "line image": rows of 128 bytes (64 bf16), 16-byte chunk c of row n stored at chunk c ^ ((n >> 1) & 7): conflict-free for
@@ -136,12 +128,6 @@ __global__ __launch_bounds__(512) void attn_self_proj_kernel(SelfProjArgs a) {
     const int r = lane & 31, hf = lane >> 5;
     const int q0 = blockIdx.x * 32, h = blockIdx.y, b = blockIdx.z;
     const bf16* base = a.qkv + (int64_t)b * a.NL * a.ld;
-#ifdef RALD_SMALL_STAMPS
-    for (int rep = 0; rep < 3; ++rep) {                            // probe only: does a second pass over the same code run faster?
-    __syncthreads();
-    RALD_STAMP(0, 8 + rep);
-#endif
-    RALD_STAMP(0, 0);
     // ---- this wave's key tile: K (line image) and V (row-major [key][d], chunk ^ 4 on rows with bit 1 set: read transposed below)
     {
         const bf16* Kt = base + a.D + h * 64 + (int64_t)(64 * wave) * a.ld;
@@ -156,10 +142,8 @@ __global__ __launch_bounds__(512) void attn_self_proj_kernel(SelfProjArgs a) {
         }
         if (wave < 4) dma_line_piece(base + (int64_t)q0 * a.ld + h * 64, a.ld, 8 * wave, s_q, lane);
     }
-    RALD_STAMP(0, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                               // the Q tile is shared
-    RALD_STAMP(0, 2);
     // ---- S^T = K.Q^T for the two 32-key halves of the tile
     f32x16 st[2];
     {
@@ -223,7 +207,6 @@ __global__ __launch_bounds__(512) void attn_self_proj_kernel(SelfProjArgs a) {
                 else o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o1, 0, 0, 0);
             }
         }
-    RALD_STAMP(0, 3);
 
     // ---- merge the 8 key tiles: M = max m_w; O = sum_w 2^(m_w - M) O_w / sum_w 2^(m_w - M) l_w
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // my V reads have returned: the tile's space is mine to overwrite
@@ -263,7 +246,6 @@ __global__ __launch_bounds__(512) void attn_self_proj_kernel(SelfProjArgs a) {
         const bf16x4 lo = obuf[(2 * ks) * 64 + lane], hi = obuf[(2 * ks + 1) * 64 + lane];
         af[ks] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     }
-    RALD_STAMP(0, 4);
     // ---- this head's slice of the out-projection: part[q][n] = sum_d O[q][d] Wo[n][64h + d]; wave w takes n in [64w, 64w + 64)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // my share of the to_out slice has landed (wave-private space)
     const int64_t prow_el = ((int64_t)h * a.batch * a.NL + (int64_t)b * a.NL + q0) * 512;
@@ -277,11 +259,6 @@ __global__ __launch_bounds__(512) void attn_self_proj_kernel(SelfProjArgs a) {
         for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], line_perm_frag(s_k, 32 * nt + r, 16 * ks, hf), acc, 0, 0, 0);
         store_part_tile(prow, 64 * wave + 32 * nt, acc, reinterpret_cast<float*>(s_v) + nt * 1024, lane, a.part_f16 != 0);     // (every read of the exchange is behind the barrier above)
     }
-    RALD_STAMP(0, 5);
-#ifdef RALD_SMALL_STAMPS
-    RALD_STAMP(0, 12 + rep);
-    }
-#endif
 }
 
 int attn_self_proj(const bf16* qkv, int64_t ld, const bf16* Wo, float* part, int NL, int heads, int batch, hipStream_t st, bool part_f16) {
@@ -334,7 +311,6 @@ __global__ __launch_bounds__(512) void xattn_q2_proj_kernel(CrossProjArgs a) {
     const int r = lane & 31, hf = lane >> 5;
     const int m0 = blockIdx.x * 32, h = blockIdx.y;
     const int b = m0 / a.NL;
-    RALD_STAMP(1, 0);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int n = wave + 8 * i;
@@ -347,10 +323,8 @@ __global__ __launch_bounds__(512) void xattn_q2_proj_kernel(CrossProjArgs a) {
     }
     dma_line_piece(a.Kc + (int64_t)b * a.strideK + h * 64, a.ldk, 8 * wave, s_kc, lane);
     dma_line_piece(a.Vt + (int64_t)b * a.strideVt + (int64_t)(h * 64) * a.ldvt, a.ldvt, 8 * wave, s_vt, lane);
-    RALD_STAMP(1, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    RALD_STAMP(1, 2);
     // ---- Q^T[d][row] = sum_c Wq[64h + d][c] h[row][c] over this wave's 128 input columns (8 k-steps), waves 0-3
     f32x16 qt[2];
     if (wave < 4) {
@@ -379,7 +353,6 @@ __global__ __launch_bounds__(512) void xattn_q2_proj_kernel(CrossProjArgs a) {
                 ex[(wave * 8 + 4 * t + g) * 64 + lane] = make_float4(qt[t][4 * g], qt[t][4 * g + 1], qt[t][4 * g + 2], qt[t][4 * g + 3]);
     }
     __syncthreads();
-    RALD_STAMP(1, 3);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -392,7 +365,6 @@ __global__ __launch_bounds__(512) void xattn_q2_proj_kernel(CrossProjArgs a) {
             }
             qt[t][4 * g] = s0.x; qt[t][4 * g + 1] = s0.y; qt[t][4 * g + 2] = s0.z; qt[t][4 * g + 3] = s0.w;
         }
-    RALD_STAMP(1, 4);
     // (every wave now holds the whole Q^T [64 d][32 rows]: the rest is small enough to be done redundantly per wave)
     bf16x8 qf[4];
     qf[0] = acc_frag(qt[0], 0, a.qscale); qf[1] = acc_frag(qt[0], 1, a.qscale);
@@ -434,7 +406,6 @@ __global__ __launch_bounds__(512) void xattn_q2_proj_kernel(CrossProjArgs a) {
             for (int s = 0; s < 2; ++s)
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(line_perm_frag(s_vt, 32 * dt + r, 32 * u + 16 * s, hf), acc_frag(st[u], s, 1.0f), o[dt], 0, 0, 0);
     }
-    RALD_STAMP(1, 5);
     // ---- this head's slice of to_out as a partial; wave w takes output columns [64w, 64w + 64)
     bf16x8 af[4];
     af[0] = acc_frag(o[0], 0, inv); af[1] = acc_frag(o[0], 1, inv); af[2] = acc_frag(o[1], 0, inv); af[3] = acc_frag(o[1], 1, inv);
@@ -452,7 +423,6 @@ __global__ __launch_bounds__(512) void xattn_q2_proj_kernel(CrossProjArgs a) {
         for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], line_perm_frag(s_a, n0 + r, 16 * ks, hf), acc, 0, 0, 0);
         store_part_tile(prow, n0, acc, reinterpret_cast<float*>(s_c) + wave * 1024, lane, a.part_f16 != 0);
     }
-    RALD_STAMP(1, 6);
 }
 
 int xattn_q2_proj(const bf16* hin, const bf16* Wq, const bf16* Kc, int64_t ldk, int64_t strideK, const bf16* Vt, int64_t ldvt, int64_t strideVt,

@@ -194,20 +194,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
-#ifdef RALD_GEMM_CLOCK   // tools/probe/gemm_clock.hip: shader clocks vs the 100 MHz wall clock over one workgroup's life
-__device__ long long g_gemm_clk[2];
-#endif
-#ifdef RALD_GEMM_STAMPS  // tools/probe/gemm_timeline.hip: per-workgroup wall-clock stamps (100 MHz) + hardware ids, one record per launch-order block
-__device__ long long g_gemm_stamps[8192][8];
-#define RALD_GSTAMP(i) do { if (threadIdx.x == 0) g_gemm_stamps[lin & 8191][i] = wall_clock64(); } while (0)
-#else
-#define RALD_GSTAMP(i) do { } while (0)
-#endif
 template <int BM, int BN, int WM, int WN, int NSTAGE, int EPI>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) {
-#ifdef RALD_GEMM_CLOCK
-    const long long clk0 = clock64(), wall0 = wall_clock64();
-#endif
     constexpr int BK = 64;
     constexpr int WAVES = WM * WN;
     constexpr int MT = BM / (16 * WM);       // m-tiles per wave
@@ -232,15 +220,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
     const int lin = blockIdx.y * gridDim.x + blockIdx.x;
     const int xcd = lin & 7, q = nt >> 3, rr = nt & 7;
     const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (lin >> 3);
-    RALD_GSTAMP(0);
-#ifdef RALD_GEMM_STAMPS
-    if (threadIdx.x == 0) { g_gemm_stamps[lin & 8191][6] = __builtin_amdgcn_s_getreg(63492); g_gemm_stamps[lin & 8191][7] = __builtin_amdgcn_s_getreg(63508); }
-#endif
-#ifdef RALD_GN16               // A/B builds (tools/build_variant.sh): strips of 16 n-tiles (A panels fetched once at N = 4096)
-    const int GN = 16;
-#else
-    const int GN = 8;
-#endif
+    constexpr int GN = 8;
     int tm, tn;
     if (ntn % GN == 0) {
         const int strip = tile / (ntm * GN), within = tile % (ntm * GN);
@@ -263,16 +243,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         tn = tl % ntn;
     }
     const int m0 = tm * BM, n0 = tn * BN;
-    // k-steps are walked from a per-tile offset, wrapping around (2-stage engine): workgroups launched together otherwise ask the L2 for
-    // the same k-slice of a shared operand panel at the same moment, at every k-step (gemm_ln.hip has the measurement).  Offset =
-    // (m-tile + n-tile + batch entry) mod nk: the tiles that share an A panel (same m) or a B panel (same n) start on different slices,
-    // and a tile's offset does not depend on how many other tiles the launch has (sub-batches reproduce the whole batch bit for bit).
+    // k-steps run in ascending order from 0 in every tile, so a sample's sums do not depend on its tile or batch size (a per-tile
+    // rotated start was measured and not shipped: DESIGN §5).  The no-op koff / wrap stays: removing it changes the compiled code.
     const int nk_ = a.K / BK;
-#ifndef RALD_KOFF            // off in the shipped build: see below (A/B builds: tools/build_variant.sh koff -DRALD_KOFF)
     const int koff = 0;
-#else
-    const int koff = NSTAGE == 2 ? (int)((unsigned)(tm + tn + bz) % (unsigned)nk_) : 0;
-#endif
     int64_t oa, ob, coff;
     gemm_batch_offsets(a, bz, oa, ob, coff);
     const bf16* A = a.A + oa;
@@ -301,24 +275,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         unsigned char* base = smem + buf * STAGE_BYTES;
         int ks = kt + koff;
         ks = ks >= nk_ ? ks - nk_ : ks;
-        // A/B builds (timing only, wrong results): -DRALD_SKIP_A / -DRALD_SKIP_B drop the A / B pieces of every stage after the first two -
-        // is a k-step paced by the BYTES of its stage or by the latency of a stage, whatever its size?  (tools/build_variant.sh ska, skb, skab)
-#if defined(RALD_SKIP_A)
-        const bool skip_a = kt >= 2;
-#else
-        const bool skip_a = false;
-#endif
-#if defined(RALD_SKIP_B)
-        const bool skip_b = kt >= 2;
-#else
-        const bool skip_b = false;
-#endif
 #pragma unroll
         for (int p = 0; p < CA; ++p)
-            if (!skip_a) __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + ks * BK), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + ks * BK), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
 #pragma unroll
         for (int p = 0; p < CB; ++p)
-            if (!skip_b) __builtin_amdgcn_global_load_lds((glb_void*)(gB[p] + ks * BK), (lds_void*)(base + BM * 128 + (wave + WAVES * p) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_void*)(gB[p] + ks * BK), (lds_void*)(base + BM * 128 + (wave + WAVES * p) * 1024), 16, 0, 0);
     };
 
     f32x4 acc[MT][NT];
@@ -352,13 +314,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
             for (int j = 0; j < NT; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
     };
-    // Measured and removed (round 3, tools/ab_libs_gemm.py on compile-time variants of this loop): (a) dropping the A pieces, the B pieces or all
-    // DMA after the prologue (-DRALD_SKIP_A / -DRALD_SKIP_B, wrong results, timing only) takes FF1 at B = 64 on random operands 167 -> 161 / 161
-    // / 151 us and its K = 2048 form 442 -> 406 / 400 / 367 us: with NO global traffic a k-step still takes 1.25 us against 1.54 with it and
-    // 1.09 of pure MFMA time at the ~1.9 GHz the chip holds in this loop - the loop is matrix-pipe-bound at the power-limited clock, the whole DMA
-    // path costs 10-17 % (about what issuing 8-10 LDS-DMA instructions per wave and k-step costs), which is why no prefetch / ring / persistent
-    // variant ever gained; (b) the same loop on v_mfma_f32_32x32x16_bf16 (half the MFMA instructions and operand-register reads per FLOP, same
-    // LDS traffic): 5-8 % SLOWER (173 -> 184 us, 446 -> 480 us).
+    // Measured (round 3): the loop is matrix-pipe-bound at the power-limited clock - without any DMA after the prologue a k-step
+    // still takes 1.25 us against 1.54 - and the same loop on v_mfma_f32_32x32x16_bf16 is 5-8 % slower.
     if constexpr (NSTAGE == 2) {
         // Software-pipelined main loop, rotated so that an iteration starts right AFTER a tile hand-over (barrier): nothing is
         // pending on the LDS counter at the loop head, so the compiler's waits inside the iteration are exact counts (round 2: the
@@ -375,7 +332,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         if (nk > 1) { stage(1, 1); __builtin_amdgcn_s_waitcnt(W_ST1); }
         else __builtin_amdgcn_s_waitcnt(W_ALL);
         __builtin_amdgcn_s_barrier();
-        RALD_GSTAMP(1);
         read_frags(0, 0, fa0, fb0);
         read_frags(0, 1, fa1, fb1);
         mfma_all(fa0, fb0);
@@ -450,16 +406,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         __builtin_amdgcn_s_barrier();         // every wave is done reading the staging buffers: reuse them as patches
         asm volatile("" ::: "memory");
     }
-    RALD_GSTAMP(2);
     gemm_epilogue_lds<MT, NT, EPI>(acc, a, m0 + wm * (BM / WM), n0 + wn * (BN / WN), coff, lane, smem + wave * 8704);
-    RALD_GSTAMP(3);
-#ifdef RALD_GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RALD_GSTAMP(4);
-#endif
-#ifdef RALD_GEMM_CLOCK
-    if (tid == 0 && lin == nt / 2) { g_gemm_clk[0] = clock64() - clk0; g_gemm_clk[1] = wall_clock64() - wall0; }
-#endif
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -140,11 +140,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(f32x4 (&acc)[MT][NT], const Ge
                         // lines displace the weight / activation panels: FETCH_SIZE of the FF1 GEMM in situ 193 MB per launch
                         // against 80 MB with this policy (= with no stores at all; profiles/traffic.json)
                         const u32x4 vv = u32x4{v.x, v.y, v.z, v.w};
-#ifdef RALD_STORE_SC01        // A/B builds (tools/build_variant.sh): write-through without the nt hint
-                        if (a.flags & GEMM_NT_STORE) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(C), "v"(vv) : "memory");
-#else
                         if (a.flags & GEMM_NT_STORE) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(C), "v"(vv) : "memory");
-#endif
                         else *reinterpret_cast<uint4*>(C) = v;
                     } else *reinterpret_cast<uint2*>(C) = make_uint2(v.x, v.y);   // N % 8 == 4 tail
                 }

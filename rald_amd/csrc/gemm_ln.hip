@@ -25,9 +25,6 @@ namespace rald {
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
-#ifdef RALD_LN_STAMPS   // tools/probe/ln_timeline.hip: shader clocks a workgroup spends waiting at the tile hand-overs vs in the whole k-loop
-__device__ long long g_ln_stamps[1024][4];
-#endif
 
 // ---- epilogue shared by the main-loop forms: acc (+ x_old already inside unless XEPI) -> x_new, h ---------------------------------
 template <int BM, int WM, int WN, bool XEPI>
@@ -388,21 +385,9 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         }
         const unsigned voB = (unsigned)(RPP * wave + lr) * (unsigned)(a.ldw * ESZ) + (unsigned)lc * 16u;
         const unsigned stepB = (unsigned)(RPP * WAVES) * (unsigned)(a.ldw * ESZ);     // uniform: bytes between this wave's W pieces
-        // MEASURED, NOT SHIPPED (-DRALD_KOFF builds only): +0.8 % per NFE at B = 64 and B = 128, but an element's fp32 accumulation order then
-        // depends on its tile and on the engine that ran it, so the same sample comes out bit-different in batches of different size (the
-        // bf16 roundings downstream flip) - every kernel here otherwise sums k in ascending 32-chunks whatever the tile shape.
-        // k-steps are walked from a per-tile OFFSET, wrapping around (the sum over k does not care where it starts): launched together,
-        // all 256 workgroups would otherwise ask their XCD's L2 for the SAME 64-KiB k-slice of W at the same moment, 32 requesters per
-        // cache line, at every one of the k-steps - a single-round launch (B = 64: one tile per CU) ran its k-loop 37 % waiting at the
-        // hand-overs, while the same kernel with two rounds of tiles (B = 128, naturally out of step) delivered 1.6 x the FLOP/s.
-        // The offset is a function of the tile's row index alone ((index mod 256) / 8 + index mod 8, mod nk): the 32 tiles that share an XCD
-        // (launch index mod 8 equal) start on different slices, the 4 tiles of a sample with per-sample weights too, and a sub-batch that
-        // starts at a multiple of 64 samples (= 256 tiles) reproduces the whole batch bit for bit.
-#ifndef RALD_KOFF            // off in the shipped build: see below (A/B builds: tools/build_variant.sh koff -DRALD_KOFF)
+        // k-steps run in ascending order from 0 in every tile, so a sample's sums do not depend on its tile or batch size (a per-tile
+        // rotated start measured +0.8 % and was not shipped: DESIGN §5).  The no-op koff / wrap stays: removing it changes the compiled code.
         const int koff = 0;
-#else
-        const int koff = (int)((unsigned)(((mtile & 255) >> 3) + (mtile & 7)) % (unsigned)nk);
-#endif
         auto ksrc = [&](int kt) { const int k = kt + koff; return k >= nk ? k - nk : k; };
         auto stage2 = [&](int kt, int buf) {
             unsigned char* base = smem + buf * STAGE_BYTES;
@@ -481,18 +466,9 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
             __builtin_amdgcn_sched_barrier(0);
         };
         static_assert(2 * MT - CA + (NT - 4) >= CB, "all DMA pieces of a stage find a slot in the first sub-step");
-#ifdef RALD_LN_STAMPS
-        long long st_wait = 0, st_t0 = clock64();
-#endif
         auto hand_over = [&]() {
-#ifdef RALD_LN_STAMPS
-            const long long w0 = clock64();
-#endif
             __builtin_amdgcn_s_waitcnt(W_ALL);                         // the next tile has landed; my reads of this one are done
             __builtin_amdgcn_s_barrier();
-#ifdef RALD_LN_STAMPS
-            st_wait += clock64() - w0;
-#endif
         };
         stage2(0, 0);
         if (nk > 1) { stage2(1, 1); __builtin_amdgcn_s_waitcnt(W_ST1); } else __builtin_amdgcn_s_waitcnt(W_ALL);
@@ -515,9 +491,6 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         for (int kt = 1; kt + 1 < nk; ++kt) iter(kt, std::true_type{});
         if (nk > 1) iter(nk - 1, std::false_type{});
         substep(-1, 0, std::false_type{}, 0);                          // MFMAs (last tile, kk 1)
-#ifdef RALD_LN_STAMPS
-        if (threadIdx.x == 0) { g_ln_stamps[blockIdx.x & 1023][0] = st_wait; g_ln_stamps[blockIdx.x & 1023][1] = clock64() - st_t0; g_ln_stamps[blockIdx.x & 1023][2] = wall_clock64(); }
-#endif
     } else {
     stage(0, 0);
     if (nk >= 9) {                                             // K >= 576: pieces over the first eight k-steps
@@ -549,9 +522,6 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     }
     constexpr bool PIPE = !MX && MT == 4 && NT == 8 && CA + CB == 10;     // the pipelined loop adds x_old in the epilogue
     resid_ln_epilogue<BM, WM, WN, (MX || PIPE)>(a, acc, smem, m0);
-#ifdef RALD_LN_STAMPS
-    if (threadIdx.x == 0) g_ln_stamps[blockIdx.x & 1023][3] = wall_clock64();
-#endif
 }
 
 template <int BM, int WM, int WN, bool MX>

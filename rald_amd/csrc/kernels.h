@@ -217,7 +217,6 @@ int heun_correct(const float* x_hat, const float* x_euler, const float* denoised
 int point_features(const float* pts, const float* basis, bf16* feat, int64_t n, hipStream_t st);
 int softmax_rows(const float* S, int64_t ld_s, bf16* P, int64_t ld_p, int rows, int n, hipStream_t st);
 int softmax_dot(const float* S, const float* u, float* out, int64_t rows, int nkeys, int rows_per_batch, float c0, hipStream_t st);
-int softmax_dot_generic(const float* S, const float* u, float* out, int64_t rows, int nkeys, int rows_per_batch, float c0, hipStream_t st);
 int ln_dot(const float* x, const float* gamma, const float* beta, const float* w, float* out, int M, int D, hipStream_t st);
 int add_bcast_cast(const float* a, const float* d, bf16* out, int64_t per_batch, int batch, hipStream_t st);
 int posterior(const float* ml, const float* eps, float* mean_o, float* logvar_o, float* z, float* kl, int B, int rows, int L, hipStream_t st);
@@ -267,7 +266,7 @@ int ae_decode_tables(int d, const float* Wq, const float* Wk, const float* ng, c
 int ae_ctx_build(const float* x, const float* gamma, const float* beta, const float* t2aug, float* Yscratch, void* ctx, int B, int M, int d,
                  hipStream_t st);
 int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* queries, float* out, const float* basis, int basis_diag,
-                     int B, int64_t Q, int M, float c0, hipStream_t st, int nw = 0);
+                     int B, int64_t Q, int M, float c0, hipStream_t st);
 
 // ---------------------------------------------------------------- post.hip
 int post_scratch_ints(int64_t Q);
@@ -339,8 +338,6 @@ int conv_in_fwd(const float* cube, int cube_ch, int Cin, const float* W, const f
 int conv_pack_weights(const float* W, bf16* out, int Cout, int Cin, int pad_to, int dgrad, hipStream_t st);
 int pad_channels(const float* x, bf16* out, int64_t M, int C, int Cpad, hipStream_t st);
 int zero_insert2(const float* dy, bf16* out, int B, int OD, int OH, int OW, int C, hipStream_t st);
-int im2col_t(const bf16* x, bf16* out, int B, int ID, int IH, int IW, int C, int stride, int pad, int64_t m0, int nchunk, hipStream_t st);
-int conv_in_wgrad(const float* cube, int cube_ch, const float* dy, int B, int D, int H, int Wd, int Cout, float* dW, hipStream_t st);
 int groupnorm_bwd(const float* x, const double* stats, const float* gamma, const float* beta, const float* da, float* dx, float* dgamma, float* dbeta,
                   double* gsum_scratch, int B, int S, int C, int swish, int accumulate, hipStream_t st, bf16* dx_bf16 = nullptr, int da_is_bf16 = 0);
 int64_t groupnorm_bwd_scratch_bytes(int B, int S, int C);   // what gsum_scratch of groupnorm_bwd must hold

@@ -4,9 +4,8 @@
 //   * Conv3d data gradient = the forward implicit-GEMM kernel on dY with flipped, transposed weights
 //     (conv_pack_weights with dgrad = 1); the stride-2 Downsample's gradient first spreads dY onto the even
 //     positions of a zero grid (zero_insert2) and then runs the same stride-1 kernel with pad 2.
-//   * Conv3d weight gradient = one MFMA GEMM per voxel chunk: dW[co][ci*27+t] += dY^T[co][m] . patches^T[ci*27+t][m],
-//     with the transposed im2col matrix written by im2col_t (rows in the weight tensor's own order, so the result
-//     accumulates straight into the fp32 gradient of the [Cout, Cin, 3, 3, 3] parameter).
+//   * Conv3d weight gradient = conv3d_wgrad_tn (gemm_tn.hip): dY^T . patches on the row-contracting GEMM engine, the patches
+//     read from the activations as they lie; the result accumulates straight into the fp32 gradient of the [Cout, Cin, 3, 3, 3] parameter.
 //   * GroupNorm(32 groups, eps 1e-6) + swish backward in two streaming passes (group sums, then dx).
 #include "common.h"
 #include "kernels.h"
@@ -72,56 +71,9 @@ int zero_insert2(const float* dy, bf16* out, int B, int OD, int OH, int OW, int 
     return 0;
 }
 
-// Transposed im2col of a chunk of output voxels: out[(ci*27 + t)][j] = x[b][od*s - p + kd][..][ci] for output voxel
-// m0 + j (zero outside the volume).  One 64-voxel x 64-channel tile per (blockIdx.x, tap, channel block), through LDS.
-__global__ __launch_bounds__(256) void im2col_t_kernel(const bf16* __restrict__ x, bf16* __restrict__ out, int ID, int IH, int IW, int C, int OD, int OH,
-                                                       int OW, int stride, int pad, int64_t m0, int nchunk, int64_t Mtot) {
-    __shared__ bf16 tile[64][72];
-    const int j0 = blockIdx.x * 64, tap = blockIdx.y, c0 = blockIdx.z * 64;
-    const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
-    for (int p = 0; p < 2; ++p) {
-        const int jr = (threadIdx.x >> 3) + 32 * p, cc = (threadIdx.x & 7) * 8;
-        bf16x8 v;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (bf16)0.f;
-        const int64_t m = m0 + j0 + jr;
-        if (j0 + jr < nchunk && m < Mtot) {
-            const int ow = (int)(m % OW);
-            int64_t r = m / OW;
-            const int oh = (int)(r % OH); r /= OH;
-            const int od = (int)(r % OD);
-            const int64_t b = r / OD;
-            const int id = od * stride - pad + kd, ih = oh * stride - pad + kh, iw = ow * stride - pad + kw;
-            if ((unsigned)id < (unsigned)ID && (unsigned)ih < (unsigned)IH && (unsigned)iw < (unsigned)IW)
-                v = *reinterpret_cast<const bf16x8*>(x + ((((b * ID + id) * IH + ih) * IW + iw)) * C + c0 + cc);
-        }
-        *reinterpret_cast<bf16x8*>(&tile[jr][cc]) = v;
-    }
-    __syncthreads();
-    for (int p = 0; p < 2; ++p) {
-        const int c = (threadIdx.x >> 3) + 32 * p, jr = (threadIdx.x & 7) * 8;
-        if (j0 + jr < nchunk) {
-            bf16x8 v;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = tile[jr + i][c];
-            *reinterpret_cast<bf16x8*>(out + ((int64_t)(c0 + c) * 27 + tap) * nchunk + j0 + jr) = v;
-        }
-    }
-}
-int im2col_t(const bf16* x, bf16* out, int B, int ID, int IH, int IW, int C, int stride, int pad, int64_t m0, int nchunk, hipStream_t st) {
-    RALD_CHECK(x && out && C % 64 == 0 && nchunk > 0 && nchunk % 8 == 0, "im2col_t: C must be a multiple of 64 and the chunk of 8");
-    const int OD = ID / stride, OH = IH / stride, OW = IW / stride;
-    const int64_t Mtot = (int64_t)B * OD * OH * OW;
-    RALD_CHECK(m0 >= 0 && m0 < Mtot, "im2col_t: chunk start out of range");
-    hipLaunchKernelGGL(im2col_t_kernel, dim3(cdiv(nchunk, 64), 27, C / 64), dim3(256), 0, st, x, out, ID, IH, IW, C, OD, OH, OW, stride, pad, m0, nchunk,
-                       Mtot);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-
 // conv_in (Cin = 1) weight gradient as a row-contracting GEMM (gemm_tn.hip): the 27-neighbourhood of every voxel of the single input channel
-// as one bf16 row of 32 (27 taps + 5 zeros) - 134 MB for 2.1 M voxels - then dW [Cout][27] = dy^T . patches.  conv_in_wgrad_kernel below
-// (one serial pass per workgroup over its voxels, LDS-staged) takes 1.74 ms for 3.6 GFLOP; this pair ~0.15 ms.
+// as one bf16 row of 32 (27 taps + 5 zeros) - 134 MB for 2.1 M voxels - then dW [Cout][27] = dy^T . patches: ~0.15 ms for 3.6 GFLOP (a
+// direct kernel, one serial LDS-staged pass per workgroup over its voxels, took 1.74 ms).
 __global__ __launch_bounds__(256) void patches27_kernel(const float* __restrict__ cube, int cube_ch, bf16* __restrict__ out, int D, int H, int Wd, int64_t nvox) {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t v = gid >> 2;                                   // 4 threads per voxel, 8 slots each
@@ -150,58 +102,6 @@ int patches27(const float* cube, int cube_ch, bf16* out, int B, int D, int H, in
     RALD_CHECK(cube && out && B >= 1 && cube_ch >= 1, "patches27: bad arguments");
     const int64_t nvox = (int64_t)B * D * H * Wd;
     hipLaunchKernelGGL(patches27_kernel, dim3((unsigned)cdiv(nvox * 4, (int64_t)256)), dim3(256), 0, st, cube, cube_ch, out, D, H, Wd, nvox);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-
-// conv_in (Cin = 1): dW[co][t] += sum_v dY[v][co] * cube[v + off(t)][0].  A workgroup walks `chunks` tiles of 256
-// voxels (neighbourhoods staged in LDS), thread (co, tap group) keeps 7 partial sums, one atomicAdd per output per
-// workgroup.  Cout <= 64.
-__global__ __launch_bounds__(256) void conv_in_wgrad_kernel(const float* __restrict__ cube, int cube_ch, const float* __restrict__ dy, int B, int D, int H,
-                                                            int Wd, int Cout, int chunks, float* __restrict__ dW) {
-    __shared__ float sx[256][28];
-    const int64_t nvox = (int64_t)B * D * H * Wd;
-    const int co = threadIdx.x & 63, g = threadIdx.x >> 6;
-    float acc[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int ch = 0; ch < chunks; ++ch) {
-        const int64_t v0 = ((int64_t)blockIdx.x * chunks + ch) * 256;
-        if (v0 >= nvox) break;
-        __syncthreads();
-        {
-            const int64_t v = v0 + threadIdx.x;
-            int w = 0, h = 0, d = 0;
-            int64_t b = 0;
-            if (v < nvox) { w = (int)(v % Wd); int64_t r = v / Wd; h = (int)(r % H); r /= H; d = (int)(r % D); b = r / D; }
-            for (int t = 0; t < 27; ++t) {
-                const int id = d + t / 9 - 1, ih = h + (t / 3) % 3 - 1, iw = w + t % 3 - 1;
-                float x = 0.f;
-                if (v < nvox && (unsigned)id < (unsigned)D && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)Wd)
-                    x = cube[((((b * D + id) * H + ih) * Wd + iw)) * cube_ch];
-                sx[threadIdx.x][t] = x;
-            }
-        }
-        __syncthreads();
-        if (co < Cout) {
-            const int vend = (int)(nvox - v0 < 256 ? nvox - v0 : 256);
-            for (int j = 0; j < vend; ++j) {
-                const float g_ = dy[(v0 + j) * Cout + co];
-#pragma unroll
-                for (int q = 0; q < 7; ++q) { const int t = g + 4 * q; if (t < 27) acc[q] += g_ * sx[j][t]; }
-            }
-        }
-    }
-    if (co < Cout) {
-#pragma unroll
-        for (int q = 0; q < 7; ++q) { const int t = g + 4 * q; if (t < 27) atomicAdd(dW + co * 27 + t, acc[q]); }
-    }
-}
-int conv_in_wgrad(const float* cube, int cube_ch, const float* dy, int B, int D, int H, int Wd, int Cout, float* dW, hipStream_t st) {
-    RALD_CHECK(cube && dy && dW && Cout <= 64, "conv_in_wgrad: Cout must be <= 64");
-    const int64_t nvox = (int64_t)B * D * H * Wd;
-    const int64_t tiles = (nvox + 255) / 256;
-    const int chunks = (int)((tiles + 2047) / 2048);          // <= 2048 workgroups
-    hipLaunchKernelGGL(conv_in_wgrad_kernel, dim3((unsigned)((tiles + chunks - 1) / chunks)), dim3(256), 0, st, cube, cube_ch, dy, B, D, H, Wd, Cout,
-                       chunks, dW);
     RALD_HIP(hipGetLastError());
     return 0;
 }

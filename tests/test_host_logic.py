@@ -278,6 +278,28 @@ def test_shipped_library_reads_no_environment_variable():
             text = f.read()
         for word in ("getenv", "RALD_PROBE", "RALD_ABLATED"):
             assert word not in text, (path, word)
+    # one form per kernel: no compile-time variants in the shipped sources (only the host / device split of kernels.h)
+    kernel_srcs = glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip"))
+    for path in kernel_srcs:
+        with open(path) as f:
+            for n, line in enumerate(f, 1):
+                m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*)", line)
+                if m:
+                    cond = m.group(2).split("//")[0]
+                    assert "RALD_" not in cond, (path, n, line)
+                    names = set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+                    assert names == {"__HIPCC__"}, (path, n, line)
+    # and no tool compiles a variant of them: nothing under tools/ includes a product source
+    product = {os.path.basename(p) for p in kernel_srcs}
+    tools = [p for p in glob.glob(os.path.join(root, "tools", "**", "*"), recursive=True) if os.path.isfile(p)]
+    assert tools
+    for path in tools:
+        with open(path, errors="replace") as f:
+            for n, line in enumerate(f, 1):
+                m = re.match(r'\s*#\s*include\s*[<"]([^>"]+)[>"]', line)
+                if m:
+                    inc = m.group(1)
+                    assert "csrc" not in inc and os.path.basename(inc) not in product, (path, n, line)
 
 
 def test_module_forward_checks_batch_sizes_before_touching_the_gpu():
