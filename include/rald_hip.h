@@ -385,25 +385,21 @@ int rald_op_gemm_nt2(const void* A, int64_t lda, int64_t strideA, int64_t stride
 /* Backward building blocks of the transformer block (what autograd derives for
  * models_radar_generation.py:35-169).  dX = dY.W and dW = dY^T.X run on rald_op_gemm_nt with transposed operands. */
 /* Weight gradient of a Linear without transposed copies (rald_amd/csrc/gemm_tn.hip): C[n1][n2] += sum_m A[m][n1] B[m][n2] for row-major bf16
- * A [M, N1] (= dY) and B [M, N2] (= X), fp32 C accumulated into with atomics; colsum (nullable) [N1] += column sums of A (the bias gradient).
+ * A [M, N1] (= dY) and B [M, N2] (= X), fp32 C accumulated into; colsum (nullable) [N1] += column sums of A (the bias gradient).
  * N1, N2, lda, ldb multiples of 8. */
 int rald_op_gemm_tn(const void* A_bf16, int64_t lda, const void* B_bf16, int64_t ldb, float* C, int64_t ldc, float* colsum, int32_t M, int32_t N1,
-                    int32_t N2, void* stream);
+                    int32_t N2, void* workspace, int64_t workspace_bytes, void* stream);
 /* Weight gradient of a 3x3x3 Conv3d (Encoder :216-241 under autograd) with the patch matrix never formed: dW [Cout][Cin][27] +=
  * sum over output voxels of dy[v][co] x[v*stride - pad + offset(tap)][ci] (zero outside the volume); dbias (nullable) += column sums
  * of dy.  dy [B*OD*OH*OW][Cout] bf16, x [B][ID][IH][IW][Cin] bf16 channels-last, OD = ID / stride ... */
 int rald_op_conv3d_wgrad(const void* dy_bf16, const void* x_bf16, float* dW, float* dbias, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin,
-                         int32_t Cout, int32_t stride, int32_t pad, void* stream);
-/* The two weight-gradient products above without atomics: with a caller-owned workspace of _workspace_bytes(...) bytes (16-byte aligned; 0 =
- * this shape keeps the atomic form and the workspace may be null) every row / voxel range stores its partial result there and a second launch
- * adds the ranges IN ORDER into C / dW (and colsum / dbias): bit-reproducible run to run, and several times faster for the convolution below
+                         int32_t Cout, int32_t stride, int32_t pad, void* workspace, int64_t workspace_bytes, void* stream);
+/* workspace of the two weight-gradient products above: null = fp32 atomics into C / dW (and colsum / dbias).  Otherwise a caller-owned
+ * workspace of _workspace_bytes(...) bytes (16-byte aligned; 0 = this shape keeps the atomic form): every row / voxel range stores its partial
+ * result there and a second launch adds the ranges IN ORDER: bit-reproducible run to run, and several times faster for the convolution below
  * full resolution, whose atomics scatter over the parameter's tap-innermost layout. */
 int64_t rald_op_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2);
-int rald_op_gemm_tn_ws(const void* A_bf16, int64_t lda, const void* B_bf16, int64_t ldb, float* C, int64_t ldc, float* colsum, int32_t M, int32_t N1,
-                       int32_t N2, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t rald_op_conv3d_wgrad_workspace_bytes(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad);
-int rald_op_conv3d_wgrad_ws(const void* dy_bf16, const void* x_bf16, float* dW, float* dbias, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin,
-                            int32_t Cout, int32_t stride, int32_t pad, void* workspace, int64_t workspace_bytes, void* stream);
 /* conv_in (one input channel) weight gradient, first half: the 27-neighbourhood of channel 0 of cube [B][D][H][W][cube_ch] fp32 per voxel as one
  * bf16 row of 32 (taps kd*9 + kh*3 + kw, zero outside the volume, 5 zero pads); dW = rald_op_gemm_tn(dy, patches). */
 int rald_op_patches27(const float* cube, int32_t cube_ch, void* out_bf16, int32_t B, int32_t D, int32_t H, int32_t W, void* stream);
@@ -411,12 +407,10 @@ int rald_op_patches27(const float* cube, int32_t cube_ch, void* out_bf16, int32_
 int rald_op_transpose(const void* in, int32_t in_is_bf16, int64_t ld_in, int64_t stride_in, int64_t stride_in2, void* out_bf16, int64_t ld_out,
                       int64_t stride_out, int64_t stride_out2, int32_t rows, int32_t cols, int32_t batch, int32_t batch2, void* stream);
 /* AdaLayerNorm :119-131 (add_one = 1) / LayerNorm (add_one = 0, scale = weight) backward, D = 512:
- * dx += ..., dscale[g] += sum_rows dh * xhat, dshift[g] += sum_rows dh  (g = row / rows_per_group, stride gstride) */
+ * dx += ..., dscale[g] += sum_rows dh * xhat, dshift[g] += sum_rows dh  (g = row / rows_per_group, stride gstride);
+ * dx_bf16_out (nullable) receives the updated dx as bf16 [rows][512] (what the next weight-/input-gradient GEMMs of the block read) */
 int rald_op_ln_mod_bwd(const float* x, const float* dh, const float* scale, int64_t gstride, int32_t rows_per_group, float add_one, float eps,
-                       int64_t rows, int32_t D, float* dx_accum, float* dscale_accum, float* dshift_accum, void* stream);
-/* the same, and the updated dx also as bf16 [rows][512] (what the next weight-/input-gradient GEMMs of the block read) */
-int rald_op_ln_mod_bwd_cast(const float* x, const float* dh, const float* scale, int64_t gstride, int32_t rows_per_group, float add_one, float eps,
-                            int64_t rows, int32_t D, float* dx_accum, void* dx_bf16_out, float* dscale_accum, float* dshift_accum, void* stream);
+                       int64_t rows, int32_t D, float* dx_accum, void* dx_bf16_out, float* dscale_accum, float* dshift_accum, void* stream);
 /* GEGLU :88-95 in the natural layout u = [a | g] (2*inner columns): hid = a * gelu_erf(g); and its backward */
 int rald_op_geglu_fwd(const void* u_bf16, void* hid_bf16, int64_t M, int32_t inner, void* stream);
 int rald_op_geglu_bwd(const void* u_bf16, const void* dhid_bf16, void* du_bf16, int64_t M, int32_t inner, void* stream);
@@ -444,9 +438,11 @@ int rald_op_edm_loss_grad(const float* F, const float* x_noised, const float* y,
  * [b][d][h][w][c]: the forward kernels of rald_radar_encode plus the backward building blocks (the shipped
  * configuration trains the encoder jointly with the denoiser). */
 /* Conv3d k3 as implicit GEMM: in bf16 [B][ID][IH][IW][Cin], w packed bf16 [Cout][27][Cin] (rald_op_conv_pack_weights),
- * out f32 [B][ID/s][IH/s][IW/s][Cout] = conv + bias (+ resid).  Cin % 64 == 0, Cout % 4 == 0, stride 1|2. */
-int rald_op_conv3d(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, int32_t B, int32_t ID,
-                   int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream);
+ * out f32 [B][ID/s][IH/s][IW/s][Cout] = conv + bias (+ resid).  Cin % 64 == 0, Cout % 4 == 0, stride 1|2.
+ * Exactly one of out and out_bf16 is non-null: out_bf16 takes the result as bf16 without a residual (the data-gradient convolutions of the
+ * training step, whose only reader is the GroupNorm backward with da_is_bf16 = 1). */
+int rald_op_conv3d(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, void* out_bf16, int32_t B,
+                   int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream);
 /* W [Cout][Cin][27] f32 (the parameter) -> packed bf16: dgrad = 0: [Cout][27][pad_to >= Cin]; dgrad = 1: the flipped,
  * transposed weights [Cin][27][pad_to >= Cout] that make rald_op_conv3d map dY to dX */
 int rald_op_conv_pack_weights(const float* W, void* out_bf16, int32_t Cout, int32_t Cin, int32_t pad_to, int32_t dgrad, void* stream);
@@ -454,23 +450,17 @@ int rald_op_conv_pack_weights(const float* W, void* out_bf16, int32_t Cout, int3
  * {sum, sumsq} are kept for the backward, the rest is scratch for the per-block partials of the deterministic (atomic-free) reduction */
 int rald_op_groupnorm(const float* x, const float* gamma, const float* beta, void* y_bf16, double* stats, int32_t B, int32_t S, int32_t C,
                       int32_t swish, void* stream);
-/* its backward: da = gradient w.r.t. the (activated) output; dx written or accumulated; dgamma/dbeta accumulated; gsum_scratch: 8-byte aligned,
- * rald_op_groupnorm_bwd_scratch_bytes(B, S, C) bytes (group sums + the per-workgroup partial sums of the atomic-free, bit-reproducible reduction) */
+/* its backward: da = gradient w.r.t. the (activated) output, fp32 or bf16 (da_is_bf16 = 1); dx written or accumulated; dx_bf16 (nullable)
+ * receives the resulting dx rounded to bf16 (what the convolution gradients of the next layer read), and dx may then be null (not with
+ * accumulate); dgamma/dbeta accumulated; gsum_scratch: 8-byte aligned, rald_op_groupnorm_bwd_scratch_bytes(B, S, C) bytes (group sums + the
+ * per-workgroup partial sums of the atomic-free, bit-reproducible reduction) */
 int64_t rald_op_groupnorm_bwd_scratch_bytes(int32_t B, int32_t S, int32_t C);
-int rald_op_groupnorm_bwd(const float* x, const double* stats, const float* gamma, const float* beta, const float* da, float* dx, float* dgamma,
-                          float* dbeta, double* gsum_scratch, int32_t B, int32_t S, int32_t C, int32_t swish, int32_t accumulate, void* stream);
+int rald_op_groupnorm_bwd(const float* x, const double* stats, const float* gamma, const float* beta, const void* da, int32_t da_is_bf16, float* dx,
+                          void* dx_bf16, float* dgamma, float* dbeta, double* gsum_scratch, int32_t B, int32_t S, int32_t C, int32_t swish,
+                          int32_t accumulate, void* stream);
 /* rald_op_groupnorm's normalisation alone, from the [B][32][2] statistics a forward call left (the training backward re-creates activations) */
 int rald_op_groupnorm_apply(const float* x, const double* stats, const float* gamma, const float* beta, void* y_bf16, int32_t B, int32_t S, int32_t C,
                             int32_t swish, void* stream);
-/* rald_op_groupnorm_bwd that also leaves the resulting dx rounded to bf16 in dx_bf16 (what the convolution gradients of the next layer read);
- * dx may be null when only the bf16 form is wanted (not with accumulate); da may hold bf16 (da_is_bf16 = 1) */
-int rald_op_groupnorm_bwd_cast(const float* x, const double* stats, const float* gamma, const float* beta, const void* da, int32_t da_is_bf16, float* dx,
-                               void* dx_bf16, float* dgamma, float* dbeta, double* gsum_scratch, int32_t B, int32_t S, int32_t C, int32_t swish,
-                               int32_t accumulate, void* stream);
-/* rald_op_conv3d with a bf16 result and no residual: the data-gradient convolutions of the training step, whose only reader is the
- * GroupNorm backward (da_is_bf16 = 1 above) */
-int rald_op_conv3d_bf16(const void* in_bf16, const void* w_packed_bf16, const float* bias, void* out_bf16, int32_t B, int32_t ID, int32_t IH, int32_t IW,
-                        int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream);
 /* conv_in (Cin = 1 read in place from channel 0 of the cube) */
 int rald_op_conv_in(const float* cube, int32_t cube_ch, int32_t Cin, const float* W, const float* bias, float* out, int32_t B, int32_t D, int32_t H,
                     int32_t Wd, int32_t Cout, void* stream);

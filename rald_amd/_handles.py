@@ -318,14 +318,12 @@ def op_gemm_tn(A: torch.Tensor, B: torch.Tensor, C_inout: torch.Tensor, colsum: 
     N2 = B.shape[1]
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and C_inout.dtype == torch.float32 and B.shape[0] == M
     assert A.stride(1) == 1 and B.stride(1) == 1 and C_inout.stride(1) == 1 and C_inout.shape == (N1, N2)
-    if atomics:
-        check(lib().rald_op_gemm_tn(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C_inout.data_ptr(), C_inout.stride(0),
-                                    _opt(colsum), M, N1, N2, _stream()))
-        return C_inout
-    nbytes = lib().rald_op_gemm_tn_workspace_bytes(M, N1, N2)
-    ws = _scratch(nbytes, A.device)
-    check(lib().rald_op_gemm_tn_ws(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C_inout.data_ptr(), C_inout.stride(0),
-                                   _opt(colsum), M, N1, N2, ws.data_ptr(), nbytes, _stream()))
+    ws, nbytes = None, 0
+    if not atomics:
+        nbytes = lib().rald_op_gemm_tn_workspace_bytes(M, N1, N2)
+        ws = _scratch(nbytes, A.device)
+    check(lib().rald_op_gemm_tn(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C_inout.data_ptr(), C_inout.stride(0),
+                                _opt(colsum), M, N1, N2, _opt(ws), nbytes, _stream()))
     return C_inout
 
 

@@ -16,7 +16,7 @@ struct rald_ae { Ae impl; };
 extern "C" {
 
 const char* rald_last_error(void) { return rald::last_error(); }
-int rald_version(void) { return 2; }
+int rald_version(void) { return 3; }
 int rald_build_flags(void) { return 0; }
 
 int64_t rald_debug_f16_saturation_count(int32_t reset) {
@@ -399,25 +399,17 @@ int rald_op_gemm_nt2(const void* A, int64_t lda, int64_t strideA, int64_t stride
     return gemm_nt(g, epilogue, (hipStream_t)stream);
 }
 int rald_op_gemm_tn(const void* A_bf16, int64_t lda, const void* B_bf16, int64_t ldb, float* C, int64_t ldc, float* colsum, int32_t M, int32_t N1,
-                    int32_t N2, void* stream) {
-    return gemm_tn((const bf16*)A_bf16, lda, (const bf16*)B_bf16, ldb, C, ldc, colsum, M, N1, N2, (hipStream_t)stream);
-}
-int rald_op_conv3d_wgrad(const void* dy_bf16, const void* x_bf16, float* dW, float* dbias, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin,
-                         int32_t Cout, int32_t stride, int32_t pad, void* stream) {
-    return conv3d_wgrad_tn((const bf16*)dy_bf16, (const bf16*)x_bf16, dW, dbias, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream);
-}
-int64_t rald_op_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2) { return 4 * gemm_tn_workspace_floats(M, N1, N2); }
-int rald_op_gemm_tn_ws(const void* A_bf16, int64_t lda, const void* B_bf16, int64_t ldb, float* C, int64_t ldc, float* colsum, int32_t M, int32_t N1,
-                       int32_t N2, void* workspace, int64_t workspace_bytes, void* stream) {
+                    int32_t N2, void* workspace, int64_t workspace_bytes, void* stream) {
     return gemm_tn((const bf16*)A_bf16, lda, (const bf16*)B_bf16, ldb, C, ldc, colsum, M, N1, N2, (hipStream_t)stream, (float*)workspace, workspace_bytes / 4);
 }
-int64_t rald_op_conv3d_wgrad_workspace_bytes(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad) {
-    return 4 * conv3d_wgrad_workspace_floats(B, ID, IH, IW, Cin, Cout, stride, pad);
-}
-int rald_op_conv3d_wgrad_ws(const void* dy_bf16, const void* x_bf16, float* dW, float* dbias, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin,
-                            int32_t Cout, int32_t stride, int32_t pad, void* workspace, int64_t workspace_bytes, void* stream) {
+int rald_op_conv3d_wgrad(const void* dy_bf16, const void* x_bf16, float* dW, float* dbias, int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin,
+                         int32_t Cout, int32_t stride, int32_t pad, void* workspace, int64_t workspace_bytes, void* stream) {
     return conv3d_wgrad_tn((const bf16*)dy_bf16, (const bf16*)x_bf16, dW, dbias, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream, (float*)workspace,
                            workspace_bytes / 4);
+}
+int64_t rald_op_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2) { return 4 * gemm_tn_workspace_floats(M, N1, N2); }
+int64_t rald_op_conv3d_wgrad_workspace_bytes(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad) {
+    return 4 * conv3d_wgrad_workspace_floats(B, ID, IH, IW, Cin, Cout, stride, pad);
 }
 int rald_op_patches27(const float* cube, int32_t cube_ch, void* out_bf16, int32_t B, int32_t D, int32_t H, int32_t W, void* stream) {
     return patches27(cube, cube_ch, (bf16*)out_bf16, B, D, H, W, (hipStream_t)stream);
@@ -430,13 +422,8 @@ int rald_op_transpose(const void* in, int32_t in_is_bf16, int64_t ld_in, int64_t
     return transpose_rows(a, in_is_bf16, (hipStream_t)stream);
 }
 int rald_op_ln_mod_bwd(const float* x, const float* dh, const float* scale, int64_t gstride, int32_t rows_per_group, float add_one, float eps,
-                       int64_t rows, int32_t D, float* dx_accum, float* dscale_accum, float* dshift_accum, void* stream) {
+                       int64_t rows, int32_t D, float* dx_accum, void* dx_bf16_out, float* dscale_accum, float* dshift_accum, void* stream) {
     RALD_CHECK(x && dh && scale && dx_accum && dscale_accum && dshift_accum, "rald_op_ln_mod_bwd: null pointer");
-    return ln_mod_bwd(x, dh, scale, gstride, rows_per_group, add_one, eps, rows, D, dx_accum, dscale_accum, dshift_accum, (hipStream_t)stream);
-}
-int rald_op_ln_mod_bwd_cast(const float* x, const float* dh, const float* scale, int64_t gstride, int32_t rows_per_group, float add_one, float eps,
-                            int64_t rows, int32_t D, float* dx_accum, void* dx_bf16_out, float* dscale_accum, float* dshift_accum, void* stream) {
-    RALD_CHECK(x && dh && scale && dx_accum && dx_bf16_out && dscale_accum && dshift_accum, "rald_op_ln_mod_bwd_cast: null pointer");
     return ln_mod_bwd(x, dh, scale, gstride, rows_per_group, add_one, eps, rows, D, dx_accum, dscale_accum, dshift_accum, (hipStream_t)stream, (bf16*)dx_bf16_out);
 }
 int rald_op_geglu_fwd(const void* u_bf16, void* hid_bf16, int64_t M, int32_t inner, void* stream) {
@@ -479,33 +466,25 @@ int rald_op_edm_loss_grad(const float* F, const float* x_noised, const float* y,
     return edm_loss_grad(F, x_noised, y, coef3, per_sample, total, dF, D_out, loss, (hipStream_t)stream);
 }
 // ---- radar encoder, op level (forward pieces + backward building blocks) --------------------------------------
-int rald_op_conv3d(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, int32_t B, int32_t ID,
-                   int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream) {
-    return conv3d_igemm((const bf16*)in_bf16, (const bf16*)w_packed_bf16, bias, resid, out, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream);
-}
-int rald_op_conv3d_bf16(const void* in_bf16, const void* w_packed_bf16, const float* bias, void* out_bf16, int32_t B, int32_t ID, int32_t IH, int32_t IW,
-                        int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream) {
-    return conv3d_igemm((const bf16*)in_bf16, (const bf16*)w_packed_bf16, bias, nullptr, nullptr, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream,
+int rald_op_conv3d(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, void* out_bf16, int32_t B,
+                   int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream) {
+    return conv3d_igemm((const bf16*)in_bf16, (const bf16*)w_packed_bf16, bias, resid, out, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream,
                         (bf16*)out_bf16);
 }
 int rald_op_groupnorm(const float* x, const float* gamma, const float* beta, void* y_bf16, double* stats, int32_t B, int32_t S, int32_t C,
                       int32_t swish, void* stream) {
     return groupnorm_fwd(x, gamma, beta, (bf16*)y_bf16, stats, B, S, C, swish, (hipStream_t)stream);
 }
-int rald_op_groupnorm_bwd(const float* x, const double* stats, const float* gamma, const float* beta, const float* da, float* dx, float* dgamma,
-                          float* dbeta, double* gsum_scratch, int32_t B, int32_t S, int32_t C, int32_t swish, int32_t accumulate, void* stream) {
-    return groupnorm_bwd(x, stats, gamma, beta, da, dx, dgamma, dbeta, gsum_scratch, B, S, C, swish, accumulate, (hipStream_t)stream);
+int rald_op_groupnorm_bwd(const float* x, const double* stats, const float* gamma, const float* beta, const void* da, int32_t da_is_bf16, float* dx,
+                          void* dx_bf16, float* dgamma, float* dbeta, double* gsum_scratch, int32_t B, int32_t S, int32_t C, int32_t swish,
+                          int32_t accumulate, void* stream) {
+    return groupnorm_bwd(x, stats, gamma, beta, (const float*)da, dx, dgamma, dbeta, gsum_scratch, B, S, C, swish, accumulate, (hipStream_t)stream,
+                         (bf16*)dx_bf16, da_is_bf16);
 }
 int64_t rald_op_groupnorm_bwd_scratch_bytes(int32_t B, int32_t S, int32_t C) { return groupnorm_bwd_scratch_bytes(B, S, C); }
 int rald_op_groupnorm_apply(const float* x, const double* stats, const float* gamma, const float* beta, void* y_bf16, int32_t B, int32_t S, int32_t C,
                             int32_t swish, void* stream) {
     return groupnorm_apply(x, stats, gamma, beta, (bf16*)y_bf16, B, S, C, swish, (hipStream_t)stream);
-}
-int rald_op_groupnorm_bwd_cast(const float* x, const double* stats, const float* gamma, const float* beta, const void* da, int32_t da_is_bf16, float* dx,
-                               void* dx_bf16, float* dgamma, float* dbeta, double* gsum_scratch, int32_t B, int32_t S, int32_t C, int32_t swish,
-                               int32_t accumulate, void* stream) {
-    return groupnorm_bwd(x, stats, gamma, beta, (const float*)da, dx, dgamma, dbeta, gsum_scratch, B, S, C, swish, accumulate, (hipStream_t)stream,
-                         (bf16*)dx_bf16, da_is_bf16);
 }
 int rald_op_conv_in(const float* cube, int32_t cube_ch, int32_t Cin, const float* W, const float* bias, float* out, int32_t B, int32_t D, int32_t H,
                     int32_t Wd, int32_t Cout, void* stream) {

@@ -27,8 +27,8 @@ import torch
 from . import train_ops as TO
 from ._handles import _opt, _scratch, _stream, op_attention, op_attention_vrow, op_gemm_nt, op_gemm_tn, op_layernorm
 from ._lib import check, lib
+from .train_ops import HEAD, param_grad, sgemm_acc
 
-HEAD = 64
 DROP_PATH_RATE = 0.1
 LN_EPS = 1e-5
 
@@ -87,29 +87,13 @@ def scale_rows_bf16(dx: torch.Tensor, s: torch.Tensor, rows_per_sample: int) -> 
     return out
 
 
-def wgrad(dy: torch.Tensor, x: torch.Tensor, dW: torch.Tensor, db: Optional[torch.Tensor] = None) -> None:
-    """dW += dy^T . x (and db += column sums of dy) without atomics (bit-reproducible)."""
-    if dy.dtype != torch.bfloat16:
-        dy = TO.cast_bf16(dy)
-    if x.dtype != torch.bfloat16:
-        x = TO.cast_bf16(x)
-    op_gemm_tn(dy, x, dW, db, atomics=False)
-
-
 def wgrad_narrow(dy: torch.Tensor, x: torch.Tensor, n: int):
     """(dy[:, :n]^T . x, column sums of dy[:, :n]) for a narrow fp32 dy [R, n] (n <= 64: mean_fc | logvar_fc, to_outputs).  gemm_tn keeps
     fp32 atomics for outputs of at most 64 rows, so dy is zero-padded to 128 columns and the workspace form runs: reproducible."""
     C_ = torch.zeros(128, x.shape[1], device=dy.device, dtype=torch.float32)
     cs = torch.zeros(128, device=dy.device, dtype=torch.float32)
-    op_gemm_tn(pad_bf16(dy, 128), x, C_, cs, atomics=False)
+    TO.lin_wgrad(TO.pad_channels(dy, 128), x, C_, cs, atomics=False)
     return C_[:n], cs[:n]
-
-
-def pad_bf16(x: torch.Tensor, cols: int) -> torch.Tensor:
-    """fp32 [M, C] -> bf16 [M, cols] with zero columns C .. cols-1."""
-    out = torch.empty(x.shape[0], cols, device=x.device, dtype=torch.bfloat16)
-    check(lib().rald_op_pad_channels(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], cols, _stream()))
-    return out
 
 
 class AeTrainer:
@@ -165,23 +149,17 @@ class AeTrainer:
         attn("cross_attend_blocks.0.", False)
         ff("cross_attend_blocks.1.")
         attn("decoder_cross_attn.", False)
-        W["pe"] = pad_bf16(d("point_embed.mlp.weight"), 64)                                   # [512, 64], features 51.. zero
+        W["pe"] = TO.pad_channels(d("point_embed.mlp.weight"), 64)                            # [512, 64], features 51.. zero
         mv = torch.cat([d("mean_fc.weight"), d("logvar_fc.weight")], 0)                      # [2L, 512]
         mat("mv", mv)
         W["b_mv"] = torch.cat([d("mean_fc.bias"), d("logvar_fc.bias")], 0).contiguous()
         Lp = _round_up(self.L, 64)
-        W["proj"] = pad_bf16(d("proj.weight"), Lp)                                           # [512, Lp]
+        W["proj"] = TO.pad_channels(d("proj.weight"), Lp)                                    # [512, Lp]
         W["projT"] = TO.T2(d("proj.weight").contiguous())                                   # [L, 512]
         to = torch.zeros(4, 512, device=self.dev, dtype=torch.float32)
         to[0] = d("to_outputs.weight")[0]
         W["to"] = TO.cast_bf16(to)                                                           # [4, 512], rows 1..3 zero
         self.W = W
-
-    def _grad(self, name: str) -> torch.Tensor:
-        p = self.P[name]
-        if p.grad is None:
-            p.grad = torch.zeros_like(p.data)
-        return p.grad
 
     # -- building blocks --------------------------------------------------------------------------------------------------------
     def _point_embed(self, pts: torch.Tensor) -> torch.Tensor:
@@ -195,10 +173,10 @@ class AeTrainer:
         return op_layernorm(x, self.P[p + ".weight"].data, self.P[p + ".bias"].data, gstride=0, rows_per_group=1 << 30, add_one=0.0, eps=LN_EPS)
 
     def _ln_bwd(self, x, dh, p, dx, dx_bf16=None):
-        ln_affine_bwd(x, dh, self.P[p + ".weight"].data, dx, self._grad(p + ".weight"), self._grad(p + ".bias"), dx_bf16)
+        ln_affine_bwd(x, dh, self.P[p + ".weight"].data, dx, param_grad(self.P[p + ".weight"]), param_grad(self.P[p + ".bias"]), dx_bf16)
 
     def _lin_bwd(self, dy, x_in, wname, bname=None):
-        wgrad(dy, x_in, self._grad(wname), self._grad(bname) if bname is not None else None)
+        TO.lin_wgrad(dy, x_in, param_grad(self.P[wname]), param_grad(self.P[bname]) if bname is not None else None, atomics=False)
 
     def _attn512_fwd(self, q: torch.Tensor, kv: torch.Tensor, Bn: int, nq: int, kp: int, nk: int):
         """1-head dim-512 attention: q [Bn*nq, 512] bf16, kv [Bn*kp, 1024] bf16 (k | v, rows nk.. of each sample padding) ->
@@ -206,8 +184,7 @@ class AeTrainer:
         D = 512
         kv3 = kv.view(Bn, kp, 2 * D)
         S = op_gemm_nt(q.view(Bn, nq, D), kv3[:, :, :D], epilogue=1, alpha=D ** -0.5)
-        P = torch.empty(Bn, nq, kp, device=self.dev, dtype=torch.bfloat16)
-        check(lib().rald_op_softmax_rows(S.data_ptr(), kp, P.data_ptr(), kp, Bn * nq, nk, _stream()))
+        P = TO.softmax_rows(S, nk)
         vT = TO.transpose(kv[:, D:], kp, D, 2 * D, Bn, kp * 2 * D).view(Bn, D, kp)
         O = op_gemm_nt(P, vT, epilogue=0)
         return O.view(Bn * nq, D), S
@@ -217,8 +194,7 @@ class AeTrainer:
         D = 512
         kv3 = kv.view(Bn, kp, 2 * D)
         dP = op_gemm_nt(dO.view(Bn, nq, D), kv3[:, :, D:], epilogue=1)
-        delta = _f32(Bn * nq, device=self.dev)
-        check(lib().rald_op_rowdot(dO.data_ptr(), O.data_ptr(), Bn * nq, D, delta.data_ptr(), _stream()))
+        delta = TO.rowdot(dO, O)
         P = torch.empty(Bn, nq, kp, device=self.dev, dtype=torch.bfloat16)
         dS = torch.empty(Bn, nq, kp, device=self.dev, dtype=torch.bfloat16)
         check(lib().rald_op_softmax_bwd_rows(S.data_ptr(), dP.data_ptr(), delta.data_ptr(), Bn * nq, kp, nk, D ** -0.5, P.data_ptr(), dS.data_ptr(),
@@ -357,7 +333,7 @@ class AeTrainer:
         check(lib().rald_op_posterior(ml.data_ptr(), eps_d.data_ptr(), z.data_ptr(), kl.data_ptr(), Bn, M, L, _stream()))
         st.update(x3b=x3b, ml=ml, eps=eps_d)
         # ---- decoder: proj, latent stack ---------------------------------------------------------------------------------------------
-        zb = pad_bf16(z, _round_up(L, 64))
+        zb = TO.pad_channels(z, _round_up(L, 64))
         x = op_gemm_nt(zb, W["proj"], bias=P["proj.bias"].data, epilogue=1)                  # [B*M, 512]
         st["zb"] = zb
         layers = []
@@ -389,16 +365,16 @@ class AeTrainer:
         dkl_d = (dkl.to(device=dev, dtype=torch.float32).reshape(Bn).contiguous() if dkl is not None else torch.zeros(Bn, device=dev))
         # ---- to_outputs: logits = lat . w^T + b ------------------------------------------------------------------------------------
         gto, gtb = wgrad_narrow(dlog, st["latb"], 1)
-        self._grad("to_outputs.weight").add_(gto)
-        self._grad("to_outputs.bias").add_(gtb)
+        param_grad(P["to_outputs.weight"]).add_(gto)
+        param_grad(P["to_outputs.bias"]).add_(gtb)
         dlat = _zeros(Bn * Q, D, device=dev)
-        TO_sgemm(dlog, P["to_outputs.weight"].data, dlat)                                    # dlat = dlogits x w (K = 1)
+        sgemm_acc(dlog, P["to_outputs.weight"].data, dlat, trans_b=True)                     # dlat = dlogits x w (K = 1)
         # ---- decoder cross-attention ------------------------------------------------------------------------------------------------
         dqe = _zeros(Bn * Q, D, device=dev)
         dxl = _zeros(Bn * M, D, device=dev)                                                  # gradient w.r.t. the latent stack's output
         self._cross_bwd(st["dc"], "decoder_cross_attn.", TO.cast_bf16(dlat), dqe, None, dxl, Bn, Q, M, M)
         del dlat
-        pe_wgrad(dqe, st["qp"], self.basis, self._grad("point_embed.mlp.weight"), self._grad("point_embed.mlp.bias"))
+        pe_wgrad(dqe, st["qp"], self.basis, param_grad(P["point_embed.mlp.weight"]), param_grad(P["point_embed.mlp.bias"]))
         del dqe
         # ---- latent stack ---------------------------------------------------------------------------------------------------------
         dxb = TO.cast_bf16(dxl)
@@ -410,18 +386,18 @@ class AeTrainer:
         # ---- proj, posterior ----------------------------------------------------------------------------------------------------------
         zb = st["zb"]
         gp = _zeros(D, zb.shape[1], device=dev)
-        op_gemm_tn(dxb, zb, gp, self._grad("proj.bias"), atomics=False)
-        self._grad("proj.weight").add_(gp[:, :L])
+        op_gemm_tn(dxb, zb, gp, param_grad(P["proj.bias"]), atomics=False)
+        param_grad(P["proj.weight"]).add_(gp[:, :L])
         dz = op_gemm_nt(dxb, W["projT"], epilogue=1)                                        # [B*M, L]
         dml = _f32(Bn * M, 2 * L, device=dev)
         check(lib().rald_op_posterior_bwd(dz.data_ptr(), dkl_d.data_ptr(), st["ml"].data_ptr(), st["eps"].data_ptr(), dml.data_ptr(), Bn, M, L,
                                           _stream()))
         dmlb = TO.cast_bf16(dml)
         gmv, gmb = wgrad_narrow(dml, st["x3b"], 2 * L)
-        self._grad("mean_fc.weight").add_(gmv[:L])
-        self._grad("mean_fc.bias").add_(gmb[:L])
-        self._grad("logvar_fc.weight").add_(gmv[L:])
-        self._grad("logvar_fc.bias").add_(gmb[L:])
+        param_grad(P["mean_fc.weight"]).add_(gmv[:L])
+        param_grad(P["mean_fc.bias"]).add_(gmb[:L])
+        param_grad(P["logvar_fc.weight"]).add_(gmv[L:])
+        param_grad(P["logvar_fc.bias"]).add_(gmb[L:])
         dx = op_gemm_nt(dmlb, W["mvT"], epilogue=1)                                          # [B*M, 512]
         dxb = TO.cast_bf16(dx)
         # ---- cross_attend_blocks ------------------------------------------------------------------------------------------------------
@@ -433,42 +409,26 @@ class AeTrainer:
             mx, p = st["mix"], "mix_attn_layer."
             self._lin_bwd(dxb, mx["x0b"], "query_proj.weight", "query_proj.bias")
             dx0 = op_gemm_nt(dxb, W["query_projT"], epilogue=1)                              # d(static + dynamic)
-            self._grad("s_latents.weight").add_(dx0.view(Bn, M, D).sum(0))
+            param_grad(P["s_latents.weight"]).add_(dx0.view(Bn, M, D).sum(0))
             dbranch = scale_rows_bf16(dx0, masks[0], M)
             self._lin_bwd(dbranch, mx["o"], p + "fn.to_out.weight", p + "fn.to_out.bias")
             dO = op_gemm_nt(dbranch, W[p + "oT"])
             dq = torch.empty_like(mx["q"])
             dkv = torch.zeros_like(mx["kv"])                                                 # key rows N .. Np-1 stay zero
-            attention_bwd_rows(mx["q"], mx["kv"], mx["o"], dO, dq, dkv, Bn, self.H, M, Np, N)
+            TO.attention_backward(mx["q"], D, mx["kv"], 2 * D, mx["kv"][:, D:], 2 * D, mx["o"], dO, Bn, self.H, M, N, dq, D, dkv, 2 * D, dkv[:, D:],
+                                  2 * D, k_rows=Np)
             self._lin_bwd(dq, mx["h"], p + "fn.to_q.weight")
             self._lin_bwd(dkv, mx["embb"], p + "fn.to_kv.weight")
             op_gemm_nt(dkv, W[p + "kvT"], epilogue=2, C_inout=demb)
             dd = _zeros(Bn * M, D, device=dev)
             self._ln_bwd(mx["x"], op_gemm_nt(dq, W[p + "qT"], epilogue=1), p + "norm", dd)
-            self._grad("d_latents.weight").add_(dd.view(Bn, M, D).sum(0))
+            param_grad(P["d_latents.weight"]).add_(dd.view(Bn, M, D).sum(0))
         else:
-            self._grad("latents.weight").add_(dx.view(Bn, M, D).sum(0))
-        pe_wgrad(demb, st["pcp"], self.basis, self._grad("point_embed.mlp.weight"), self._grad("point_embed.mlp.bias"))
+            param_grad(P["latents.weight"]).add_(dx.view(Bn, M, D).sum(0))
+        pe_wgrad(demb, st["pcp"], self.basis, param_grad(P["point_embed.mlp.weight"]), param_grad(P["point_embed.mlp.bias"]))
         st.clear()
 
 
 def st_off(mix: bool) -> int:
     """Index of layers.0's attention mask in the drop-path list (the mix layer draws first)."""
     return 1 if mix else 0
-
-
-def TO_sgemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> None:
-    """out[m, n] += a[m, 0] * w[0, n] (a K = 1 product: the fp32 FMA kernel runs it without a split over K)."""
-    check(lib().rald_op_sgemm_acc(a.data_ptr(), a.stride(0), 0, w.data_ptr(), w.stride(0), 1, out.data_ptr(), out.stride(0), out.shape[0],
-                                  out.shape[1], 1, 1.0, _stream()))
-
-
-def attention_bwd_rows(q, kv, O, dO, dq, dkv, Bn: int, H: int, nq: int, k_rows: int, nk: int) -> None:
-    """Fused head-64 attention backward (csrc/attn_bwd.hip) for q [Bn*nq, H*64] and a fused k | v buffer kv [Bn*k_rows, 2*H*64] whose
-    first nk rows per sample are keys (nk need not be a multiple of 64: the last tile is masked)."""
-    D = H * HEAD
-    scratch = torch.empty(2, Bn * H * nq, device=O.device, dtype=torch.float32)
-    check(lib().rald_op_attention_bwd(q.data_ptr(), D, nq * D, kv.data_ptr(), 2 * D, k_rows * 2 * D, kv[:, D:].data_ptr(), 2 * D, k_rows * 2 * D,
-                                      O.data_ptr(), D, nq * D, dO.data_ptr(), D, nq * D, dq.data_ptr(), D, nq * D, dkv.data_ptr(), 2 * D,
-                                      k_rows * 2 * D, dkv[:, D:].data_ptr(), 2 * D, k_rows * 2 * D, scratch[0].data_ptr(), scratch[1].data_ptr(), nq,
-                                      nk, H, Bn, HEAD ** -0.5, _stream()))

@@ -25,15 +25,7 @@ import torch
 from . import train_ops as TO
 from ._handles import _stream, op_gemm_nt, op_layernorm
 from ._lib import check, lib
-
-def sgemm_acc(A, B, out, trans_a=False, trans_b=False, alpha=1.0, M=None, N=None, K=None):
-    """out[m, n] += alpha * sum_k A(m, k) B(n, k) in fp32 (see rald_op_sgemm_acc)."""
-    M = M if M is not None else (A.shape[1] if trans_a else A.shape[0])
-    K = K if K is not None else (A.shape[0] if trans_a else A.shape[1])
-    N = N if N is not None else (B.shape[1] if trans_b else B.shape[0])
-    check(lib().rald_op_sgemm_acc(A.data_ptr(), A.stride(0), int(trans_a), B.data_ptr(), B.stride(0), int(trans_b), out.data_ptr(), out.stride(0), M,
-                                  N, K, alpha, _stream()))
-    return out
+from .train_ops import param_grad, sgemm_acc
 
 
 def linear_f32(x, W, b=None):
@@ -117,18 +109,12 @@ class DitTrainer:
         self.w_mod = torch.cat([sd[f"transformer_blocks.{i}.norm{j}.linear.weight"] for i in range(L) for j in (1, 2, 3)], 0)
         self.b_mod = torch.cat([sd[f"transformer_blocks.{i}.norm{j}.linear.bias"] for i in range(L) for j in (1, 2, 3)], 0)
 
-    def _grad(self, name: str) -> torch.Tensor:
-        p = self.P[name]
-        if p.grad is None:
-            p.grad = torch.zeros_like(p.data)
-        return p.grad
-
     def _block_grad_views(self, i: int):
         """fp32 destinations for block i's gradients, keyed like ``train_ops.prepare_block_weights``: the parameters'
         own ``.grad`` tensors (views of the optimizer's flat buffer), so the dW GEMMs accumulate in place.  The fused
         q/k/v gradient needs the three ``.grad`` views to be adjacent (they are in ``FlatAdamW``'s layout)."""
         pre, D = f"transformer_blocks.{i}.", self.D
-        g = lambda n: self._grad(pre + n)
+        g = lambda n: param_grad(self.P[pre + n])
         views = {"o": g("attn1.to_out.0.weight"), "bo": g("attn1.to_out.0.bias"), "q2": g("attn2.to_q.weight"), "k2": g("attn2.to_k.weight"),
                  "v2": g("attn2.to_v.weight"), "o2": g("attn2.to_out.0.weight"), "bo2": g("attn2.to_out.0.bias"),
                  "w1": g("ff.net.0.proj.weight"), "b1": g("ff.net.0.proj.bias"), "w2": g("ff.net.2.weight"), "b2": g("ff.net.2.bias")}
@@ -236,12 +222,12 @@ class DitTrainer:
         M = x_final.shape[0]
         f32 = dict(device=dev, dtype=torch.float32)
         ng = P["norm.weight"].data
-        sgemm_acc(dF, yn, self._grad("proj_out.weight"), trans_a=True, trans_b=True)             # dW_out = dF^T . yn
+        sgemm_acc(dF, yn, param_grad(P["proj_out.weight"]), trans_a=True, trans_b=True)          # dW_out = dF^T . yn
         dyn = torch.zeros(M, D, **f32)
         sgemm_acc(dF, P["proj_out.weight"].data, dyn, trans_b=True)                              # dyn = dF . W_out
         dx = torch.zeros(M, D, **f32)
         dxb = torch.empty(M, D, device=dev, dtype=torch.bfloat16)               # bf16(dx), kept current by every LayerNorm backward
-        TO.ln_mod_bwd(x_final, dyn, ng, 0, 1 << 30, 0.0, dx, self._grad("norm.weight"), self._grad("norm.bias"), dx_bf16=dxb)
+        TO.ln_mod_bwd(x_final, dyn, ng, 0, 1 << 30, 0.0, dx, param_grad(P["norm.weight"]), param_grad(P["norm.bias"]), dx_bf16=dxb)
         dmod = torch.zeros(Bn, L * 3, 2 * D, **f32)
         dcond = torch.zeros(Bn * T, cond16.shape[1], **f32)
         for i in reversed(range(L)):
@@ -250,8 +236,8 @@ class DitTrainer:
             saved[i] = None
             dcond += dc
             for name, key, rows in pending:                 # q/k/v gradients not adjacent in memory: split the fused one
-                self._grad(name).add_(grads[key][rows])
-        sgemm_acc(dx, xin, self._grad("proj_in.weight"), trans_a=True, trans_b=True)             # dW_in = dx^T . xin
+                param_grad(P[name]).add_(grads[key][rows])
+        sgemm_acc(dx, xin, param_grad(P["proj_in.weight"]), trans_a=True, trans_b=True)          # dW_in = dx^T . xin
         # AdaLN linears: mod = temb . w_mod^T + b_mod
         dmod2 = dmod.view(Bn, L * 3 * 2 * D)
         gw = torch.zeros_like(self.w_mod)
@@ -259,18 +245,18 @@ class DitTrainer:
         gb = torch.zeros(1, dmod2.shape[1], **f32)
         TO.colsum(dmod2, gb[0])
         for idx, (i, j) in enumerate((i, j) for i in range(L) for j in (1, 2, 3)):
-            self._grad(f"transformer_blocks.{i}.norm{j}.linear.weight").add_(gw[idx * 2 * D:(idx + 1) * 2 * D])
-            self._grad(f"transformer_blocks.{i}.norm{j}.linear.bias").add_(gb[0, idx * 2 * D:(idx + 1) * 2 * D])
+            param_grad(P[f"transformer_blocks.{i}.norm{j}.linear.weight"]).add_(gw[idx * 2 * D:(idx + 1) * 2 * D])
+            param_grad(P[f"transformer_blocks.{i}.norm{j}.linear.bias"]).add_(gb[0, idx * 2 * D:(idx + 1) * 2 * D])
         dtemb = torch.zeros(Bn, D, **f32)
         sgemm_acc(dmod2, self.w_mod, dtemb, trans_b=True)                                        # dmod . w_mod
         da1 = silu_bwd(a1, dtemb)
-        sgemm_acc(da1, e0, self._grad("map_layer1.weight"), trans_a=True, trans_b=True)
-        TO.colsum(da1, self._grad("map_layer1.bias"))
+        sgemm_acc(da1, e0, param_grad(P["map_layer1.weight"]), trans_a=True, trans_b=True)
+        TO.colsum(da1, param_grad(P["map_layer1.bias"]))
         de0 = torch.zeros(Bn, D, **f32)
         sgemm_acc(da1, P["map_layer1.weight"].data, de0, trans_b=True)
         da0 = silu_bwd(a0, de0)
-        sgemm_acc(da0, pe, self._grad("map_layer0.weight"), trans_a=True, trans_b=True)
-        TO.colsum(da0, self._grad("map_layer0.bias"))
+        sgemm_acc(da0, pe, param_grad(P["map_layer0.weight"]), trans_a=True, trans_b=True)
+        TO.colsum(da0, param_grad(P["map_layer0.bias"]))
         return dcond.view(Bn, T, -1)
 
 

@@ -23,6 +23,7 @@ import torch
 from . import train_ops as TO
 from ._handles import _opt, _scratch, _stream, op_gemm_nt
 from ._lib import check, lib
+from .train_ops import param_grad, sgemm_acc
 
 CH_MULT = (1, 1, 2, 2, 4)            # models_radar_encoder.py factories (ch_mult of ae_ch64_mult5_*)
 
@@ -42,14 +43,10 @@ def conv3d(x16: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, resid: Optio
     """x16 bf16 [B, D, H, W, Cin], wp packed [Cout][27][Cin] -> f32 [B, D/s, H/s, W/s, Cout] (+ resid), or the same as bf16 (no resid)."""
     B, D, H, W, Cin = x16.shape
     Cout = wp.shape[0]
-    if out_bf16:
-        assert resid is None
-        out = torch.empty(B, D // stride, H // stride, W // stride, Cout, device=x16.device, dtype=torch.bfloat16)
-        check(lib().rald_op_conv3d_bf16(x16.data_ptr(), wp.data_ptr(), _opt(bias), out.data_ptr(), B, D, H, W, Cin, Cout, stride, pad, _stream()))
-        return out
-    out = torch.empty(B, D // stride, H // stride, W // stride, Cout, device=x16.device, dtype=torch.float32)
-    check(lib().rald_op_conv3d(x16.data_ptr(), wp.data_ptr(), _opt(bias), _opt(resid), out.data_ptr(), B, D, H, W, Cin, Cout, stride, pad,
-                               _stream()))
+    out = torch.empty(B, D // stride, H // stride, W // stride, Cout, device=x16.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
+    ptr = out.data_ptr()
+    check(lib().rald_op_conv3d(x16.data_ptr(), wp.data_ptr(), _opt(bias), _opt(resid), None if out_bf16 else ptr, ptr if out_bf16 else None, B, D,
+                               H, W, Cin, Cout, stride, pad, _stream()))
     return out
 
 
@@ -78,14 +75,9 @@ def groupnorm_bwd(x, stats, gamma, beta, da, dx, dgamma, dbeta, swish: bool, acc
     B, Cc = x.shape[0], x.shape[-1]
     S = x.numel() // (B * Cc)
     scratch = torch.empty((lib().rald_op_groupnorm_bwd_scratch_bytes(B, S, Cc) + 7) // 8, device=x.device, dtype=torch.float64)
-    if dx_bf16 is None:
-        assert da.dtype == torch.float32
-        check(lib().rald_op_groupnorm_bwd(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), da.data_ptr(), _opt(dx),
-                                          dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), B, S, Cc, int(swish), int(accumulate), _stream()))
-    else:
-        check(lib().rald_op_groupnorm_bwd_cast(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), da.data_ptr(),
-                                               int(da.dtype == torch.bfloat16), _opt(dx), dx_bf16.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                               scratch.data_ptr(), B, S, Cc, int(swish), int(accumulate), _stream()))
+    check(lib().rald_op_groupnorm_bwd(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), da.data_ptr(),
+                                      int(da.dtype == torch.bfloat16), _opt(dx), _opt(dx_bf16), dgamma.data_ptr(), dbeta.data_ptr(),
+                                      scratch.data_ptr(), B, S, Cc, int(swish), int(accumulate), _stream()))
 
 
 def _zero_bias(n, dev):
@@ -96,13 +88,10 @@ def conv_dgrad(dy: torch.Tensor, W: torch.Tensor, out_bf16: bool = False) -> tor
     """Gradient w.r.t. the input of a k3 s1 p1 conv: dy f32 or bf16 [B, D, H, W, Cout], W the f32 parameter -> f32 (or bf16) [B, D, H, W, Cin]."""
     Cout, Cin = W.shape[0], W.shape[1]
     cpad = -(-Cout // 64) * 64
-    B = dy.shape[0]
-    M = dy.numel() // Cout
     if dy.dtype == torch.bfloat16 and cpad == Cout:
         dy16 = dy.contiguous()                               # already what the convolution reads (the caller's one bf16 copy of dy)
     else:
-        dy16 = torch.empty(*dy.shape[:-1], cpad, device=dy.device, dtype=torch.bfloat16)
-        check(lib().rald_op_pad_channels((dy.float() if dy.dtype != torch.float32 else dy).data_ptr(), dy16.data_ptr(), M, Cout, cpad, _stream()))
+        dy16 = TO.pad_channels(dy.float(), cpad)
     return conv3d(dy16, pack_conv(W, dgrad=True, pad_to=cpad), _zero_bias(Cin, dy.device), None, 1, 1, out_bf16=out_bf16)
 
 
@@ -130,23 +119,8 @@ def conv_wgrad(dy: torch.Tensor, x16: torch.Tensor, dW: torch.Tensor, dbias: Opt
     # full resolution - csrc/gemm_tn.hip)
     nbytes = lib().rald_op_conv3d_wgrad_workspace_bytes(B, ID, IH, IW, Cin, Cout, stride, pad)
     ws = _scratch(nbytes, dy16.device)
-    check(lib().rald_op_conv3d_wgrad_ws(dy16.data_ptr(), x16.data_ptr(), dW.data_ptr(), _opt(dbias), B, ID, IH, IW, Cin, Cout, stride, pad,
-                                        ws.data_ptr(), nbytes, _stream()))
-
-
-def _g(p: torch.nn.Parameter) -> torch.Tensor:
-    if p.grad is None:
-        p.grad = torch.zeros_like(p.data)
-    return p.grad
-
-
-def _sgemm(A, B, out, trans_a=False, trans_b=False):
-    M = A.shape[1] if trans_a else A.shape[0]
-    K = A.shape[0] if trans_a else A.shape[1]
-    N = B.shape[1] if trans_b else B.shape[0]
-    check(lib().rald_op_sgemm_acc(A.data_ptr(), A.stride(0), int(trans_a), B.data_ptr(), B.stride(0), int(trans_b), out.data_ptr(), out.stride(0), M,
-                                  N, K, 1.0, _stream()))
-    return out
+    check(lib().rald_op_conv3d_wgrad(dy16.data_ptr(), x16.data_ptr(), dW.data_ptr(), _opt(dbias), B, ID, IH, IW, Cin, Cout, stride, pad,
+                                     ws.data_ptr(), nbytes, _stream()))
 
 
 class EncoderTrainer:
@@ -192,14 +166,14 @@ class EncoderTrainer:
         P = lambda n: self.p(name + n)
         if dout16 is None:
             dout16 = TO.cast_bf16(dout)
-        conv_wgrad(dout16, h2, _g(P(".conv2.weight")), _g(P(".conv2.bias")))
+        conv_wgrad(dout16, h2, param_grad(P(".conv2.weight")), param_grad(P(".conv2.bias")))
         del h2
         dh2 = conv_dgrad(dout16, P(".conv2.weight").data, out_bf16=True)     # read only by the GroupNorm backward
         dt1 = torch.empty(t1.shape, device=t1.device, dtype=torch.bfloat16)                 # consumed by the two convolution gradients only
-        groupnorm_bwd(t1, st2, P(".norm2.weight").data, P(".norm2.bias").data, dh2, None, _g(P(".norm2.weight")), _g(P(".norm2.bias")), True, False,
-                      dx_bf16=dt1)
+        groupnorm_bwd(t1, st2, P(".norm2.weight").data, P(".norm2.bias").data, dh2, None, param_grad(P(".norm2.weight")),
+                      param_grad(P(".norm2.bias")), True, False, dx_bf16=dt1)
         del dh2
-        conv_wgrad(dt1, h1, _g(P(".conv1.weight")), _g(P(".conv1.bias")))
+        conv_wgrad(dt1, h1, param_grad(P(".conv1.weight")), param_grad(P(".conv1.bias")))
         del h1
         dh1 = conv_dgrad(dt1, P(".conv1.weight").data, out_bf16=True)
         if cin == cout:
@@ -208,10 +182,11 @@ class EncoderTrainer:
             d16 = dout16.view(-1, cout)
             W16 = P(".nin_shortcut.weight").data.view(cout, cin).to(torch.bfloat16)
             dx = op_gemm_nt(d16, TO.T2(W16), epilogue=1).view(*x.shape)
-            TO.lin_wgrad(d16, TO.cast_bf16(x).view(-1, cin), _g(P(".nin_shortcut.weight")).view(cout, cin), _g(P(".nin_shortcut.bias")))
+            TO.lin_wgrad(d16, TO.cast_bf16(x).view(-1, cin), param_grad(P(".nin_shortcut.weight")).view(cout, cin),
+                         param_grad(P(".nin_shortcut.bias")))
         dx16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-        groupnorm_bwd(x, st1, P(".norm1.weight").data, P(".norm1.bias").data, dh1, dx, _g(P(".norm1.weight")), _g(P(".norm1.bias")), True, True,
-                      dx_bf16=dx16)
+        groupnorm_bwd(x, st1, P(".norm1.weight").data, P(".norm1.bias").data, dh1, dx, param_grad(P(".norm1.weight")),
+                      param_grad(P(".norm1.bias")), True, True, dx_bf16=dx16)
         return dx, dx16
 
     # ---- AttnBlock :102-135 (single head, S tokens, scale C^-1/2) -----------------------------------------------------
@@ -227,11 +202,8 @@ class EncoderTrainer:
         scale = float(Cc) ** -0.5
         Sm = torch.empty(B, S, S, device=x.device, dtype=torch.float32)
         TO.gemm2(q, Cc, S * Cc, 0, k, Cc, S * Cc, 0, Sm, S, S * S, 0, S, S, Cc, B, 1, epilogue=1)
-        lse = torch.empty(B, S, device=x.device, dtype=torch.float32)
-        check(lib().rald_op_row_lse(Sm.data_ptr(), B * S, S, scale, lse.data_ptr(), _stream()))
-        Pm = torch.empty(B, S, S, device=x.device, dtype=torch.bfloat16)
-        Ssc = Sm * scale                                                # [B,64,64]: tiny
-        check(lib().rald_op_softmax_rows(Ssc.data_ptr(), S, Pm.data_ptr(), S, B * S, S, _stream()))
+        lse = TO.row_lse(Sm, scale)
+        Pm = TO.softmax_rows(Sm * scale, S)                             # [B,64,64]: tiny
         vT = TO.transpose(v, S, Cc, Cc, B, S * Cc).view(B, Cc, S)
         o = torch.empty(B * S, Cc, device=x.device, dtype=torch.bfloat16)
         TO.gemm2(Pm, S, S * S, 0, vT, S, Cc * S, 0, o, Cc, S * Cc, 0, S, Cc, S, B, 1)
@@ -251,14 +223,12 @@ class EncoderTrainer:
         n16 = groupnorm_apply(x, st, P(".norm.weight").data, P(".norm.bias").data, False)
         n2 = n16.view(B * S, Cc)
         do = op_gemm_nt(TO.cast_bf16(d2), TO.T2(W16(".proj_out.weight")))                       # [B*S, C] bf16
-        TO.lin_wgrad(d2, o, _g(P(".proj_out.weight")).view(Cc, Cc), _g(P(".proj_out.bias")))
+        TO.lin_wgrad(d2, o, param_grad(P(".proj_out.weight")).view(Cc, Cc), param_grad(P(".proj_out.bias")))
         dP = torch.empty(B, S, S, device=x.device, dtype=torch.float32)
         TO.gemm2(do, Cc, S * Cc, 0, v, Cc, S * Cc, 0, dP, S, S * S, 0, S, S, Cc, B, 1, epilogue=1)
-        delta = torch.empty(B, S, device=x.device, dtype=torch.float32)
-        check(lib().rald_op_rowdot(do.data_ptr(), o.data_ptr(), B * S, Cc, delta.data_ptr(), _stream()))
+        delta = TO.rowdot(do, o)
         dS = torch.empty(B, S, S, device=x.device, dtype=torch.bfloat16)
-        check(lib().rald_op_attn_bwd_elem(Sm.data_ptr(), dP.data_ptr(), lse.data_ptr(), delta.data_ptr(), B, S, S, S, 1, scale, 0, None,
-                                          dS.data_ptr(), _stream()))
+        TO.attn_bwd_elem(Sm, dP, lse, delta, B, S, S, S, 1, scale, 0, None, dS)
         tb = lambda t, r, c: TO.transpose(t, r, c, c, B, r * c).view(B, c, r)                  # per-sample transpose
         dq = torch.empty(B * S, Cc, device=x.device, dtype=torch.bfloat16)
         dk, dv = torch.empty_like(dq), torch.empty_like(dq)
@@ -269,10 +239,10 @@ class EncoderTrainer:
         op_gemm_nt(dk, TO.T2(W16(".k.weight")), epilogue=2, C_inout=dn)
         op_gemm_nt(dv, TO.T2(W16(".v.weight")), epilogue=2, C_inout=dn)
         for g, nm in ((dq, ".q"), (dk, ".k"), (dv, ".v")):
-            TO.lin_wgrad(g, n2, _g(P(nm + ".weight")).view(Cc, Cc), _g(P(nm + ".bias")))
+            TO.lin_wgrad(g, n2, param_grad(P(nm + ".weight")).view(Cc, Cc), param_grad(P(nm + ".bias")))
         dx = dxo                                                                         # residual path
-        groupnorm_bwd(x, st, P(".norm.weight").data, P(".norm.bias").data, dn.view(*x.shape), dx, _g(P(".norm.weight")), _g(P(".norm.bias")),
-                      False, True)
+        groupnorm_bwd(x, st, P(".norm.weight").data, P(".norm.bias").data, dn.view(*x.shape), dx, param_grad(P(".norm.weight")),
+                      param_grad(P(".norm.bias")), False, True)
         return dx
 
     # ---- Encoder.forward :216-241 + tokeniser (models_radar_generation.py:363-407) -------------------------------------
@@ -310,7 +280,7 @@ class EncoderTrainer:
         emb = (r_e[:, None, None, :] + a_e[None, :, None, :] + e_e[None, None, :, :]).reshape(-1, r_e.shape[1])     # [64, 512]
         tok = (emb + self.P["radar_token_project.bias"].data)[None].repeat(B, 1, 1).contiguous()
         z2 = z.view(-1, z.shape[-1])
-        _sgemm(z2, self.P["radar_token_project.weight"].data, tok.view(-1, tok.shape[-1]))
+        sgemm_acc(z2, self.P["radar_token_project.weight"].data, tok.view(-1, tok.shape[-1]))
         self.saved.append(("tok", z2, (r_e.shape[0], a_e.shape[0], e_e.shape[0])))
         return tok
 
@@ -320,23 +290,23 @@ class EncoderTrainer:
         _, z2, (nr, na, ne) = self.saved.pop()
         B = dtok.shape[0]
         d2 = dtok.reshape(-1, dtok.shape[-1]).contiguous()
-        _sgemm(d2, z2, _g(P["radar_token_project.weight"]), trans_a=True, trans_b=True)          # [512, 16] = dtok^T . z
-        TO.colsum(d2, _g(P["radar_token_project.bias"]))
+        sgemm_acc(d2, z2, param_grad(P["radar_token_project.weight"]), trans_a=True, trans_b=True)   # [512, 16] = dtok^T . z
+        TO.colsum(d2, param_grad(P["radar_token_project.bias"]))
         # embedding rows: one-hot selection matrices [B*T, n] (token t = (r*na + a)*ne + e)
         t = torch.arange(nr * na * ne, device=self.dev)
         for idx, n, key in ((t // (na * ne), nr, "radar_r_emb.weight"), ((t // ne) % na, na, "radar_a_emb.weight"), (t % ne, ne, "radar_e_emb.weight")):
             sel = torch.nn.functional.one_hot(idx, n).to(torch.float32).repeat(B, 1).contiguous()
-            _sgemm(sel, d2, _g(P[key]), trans_a=True, trans_b=True)
+            sgemm_acc(sel, d2, param_grad(P[key]), trans_a=True, trans_b=True)
         dz = torch.zeros(z2.shape, device=self.dev, dtype=torch.float32)
-        _sgemm(d2, P["radar_token_project.weight"].data, dz, trans_b=True)                       # dtok . Wp
+        sgemm_acc(d2, P["radar_token_project.weight"].data, dz, trans_b=True)                    # dtok . Wp
         _, x, st = self.saved.pop()
         dz5 = dz.view(*x.shape[:-1], dz.shape[-1])
         h = groupnorm_apply(x, st, self.w("norm_out.weight"), self.w("norm_out.bias"), True)
-        conv_wgrad(dz5, h, _g(self.p("conv_out.weight")), _g(self.p("conv_out.bias")))
+        conv_wgrad(dz5, h, param_grad(self.p("conv_out.weight")), param_grad(self.p("conv_out.bias")))
         dh = conv_dgrad(dz5, self.w("conv_out.weight"), out_bf16=True)
         dx, dx16 = torch.empty_like(x), torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-        groupnorm_bwd(x, st, self.w("norm_out.weight"), self.w("norm_out.bias"), dh, dx, _g(self.p("norm_out.weight")), _g(self.p("norm_out.bias")),
-                      True, False, dx_bf16=dx16)
+        groupnorm_bwd(x, st, self.w("norm_out.weight"), self.w("norm_out.bias"), dh, dx, param_grad(self.p("norm_out.weight")),
+                      param_grad(self.p("norm_out.bias")), True, False, dx_bf16=dx16)
         while self.saved:
             rec = self.saved.pop()
             kind = rec[0]
@@ -346,7 +316,8 @@ class EncoderTrainer:
                 dx, dx16 = self._attn_bwd(rec, dx), None
             elif kind == "down":
                 _, name, x16 = rec
-                conv_wgrad(dx16 if dx16 is not None else dx, x16, _g(self.p(name + ".weight")), _g(self.p(name + ".bias")), stride=2, pad=0)
+                conv_wgrad(dx16 if dx16 is not None else dx, x16, param_grad(self.p(name + ".weight")), param_grad(self.p(name + ".bias")), stride=2,
+                           pad=0)
                 dx, dx16 = down_dgrad(dx, self.w(name + ".weight")), None
             elif kind == "conv_in":
                 cube = rec[1]
@@ -355,5 +326,5 @@ class EncoderTrainer:
                 pat = torch.empty(Bc * R * A * E, 32, device=cube.device, dtype=torch.bfloat16)
                 check(lib().rald_op_patches27(cube.data_ptr(), cch, pat.data_ptr(), Bc, R, A, E, _stream()))
                 dw32 = torch.zeros(self.ch, 32, device=cube.device, dtype=torch.float32)
-                TO.lin_wgrad(dx.view(-1, self.ch), pat, dw32, _g(self.p("conv_in.bias")))
-                _g(self.p("conv_in.weight")).view(self.ch, 27).add_(dw32[:, :27])
+                TO.lin_wgrad(dx.view(-1, self.ch), pat, dw32, param_grad(self.p("conv_in.bias")))
+                param_grad(self.p("conv_in.weight")).view(self.ch, 27).add_(dw32[:, :27])

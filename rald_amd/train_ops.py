@@ -1,4 +1,7 @@
-"""Backward pass of the denoiser's transformer block on the HIP kernels ("backward
+"""The training-side kernel wrappers of all three trainers: the denoiser (train_dit.py), the radar encoder (train_encoder.py) and
+the autoencoder (train_ae.py).  A training entry point of the library that more than one trainer uses is called from here only.
+
+Backward pass of the denoiser's transformer block on the HIP kernels ("backward
 kernels for K2-K5").  ``block_forward`` / ``block_backward`` restate what autograd derives for
 ``BasicTransformerBlock`` (models_radar_generation.py:133-169: AdaLayerNorm -> self-attention -> AdaLayerNorm ->
 radar cross-attention -> AdaLayerNorm -> GEGLU feed-forward, residual after each) as explicit launches:
@@ -12,11 +15,11 @@ and dP = dO.V^T per head as batched K = 64 GEMMs, the softmax backward element-w
 transposed orientation.
 
 Gradient parity against autograd of the CPU oracle: tests/test_train_block.py (one block, whole denoiser);
-the loop over blocks, embeddings and loss live in train_dit.py, the radar encoder in train_encoder.py.
+the loop over blocks, embeddings and loss live in train_dit.py, the radar encoder in train_encoder.py, the autoencoder in train_ae.py.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional
 
 import torch
 
@@ -24,6 +27,13 @@ from ._handles import _opt, _stream, op_attention, op_attention_vrow, op_gemm_nt
 from ._lib import check, lib
 
 HEAD = 64
+
+
+def param_grad(p: torch.nn.Parameter) -> torch.Tensor:
+    """p.grad, created as zeros on first use: the trainers accumulate every gradient into it."""
+    if p.grad is None:
+        p.grad = torch.zeros_like(p.data)
+    return p.grad
 
 
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
@@ -54,12 +64,8 @@ def T2(x: torch.Tensor) -> torch.Tensor:
 
 def ln_mod_bwd(x, dh, scale, gstride, rows_per_group, add_one, dx, dscale, dshift, eps=1e-5, dx_bf16=None):
     """dx += LayerNorm-mod backward of dh (fp32, in place); dx_bf16 (optional, bf16 [rows, 512]) receives the updated dx rounded to bf16."""
-    if dx_bf16 is not None:
-        check(lib().rald_op_ln_mod_bwd_cast(x.data_ptr(), dh.data_ptr(), scale.data_ptr(), gstride, rows_per_group, add_one, eps, x.shape[0],
-                                            x.shape[1], dx.data_ptr(), dx_bf16.data_ptr(), dscale.data_ptr(), dshift.data_ptr(), _stream()))
-        return
     check(lib().rald_op_ln_mod_bwd(x.data_ptr(), dh.data_ptr(), scale.data_ptr(), gstride, rows_per_group, add_one, eps, x.shape[0], x.shape[1],
-                                   dx.data_ptr(), dscale.data_ptr(), dshift.data_ptr(), _stream()))
+                                   dx.data_ptr(), _opt(dx_bf16), dscale.data_ptr(), dshift.data_ptr(), _stream()))
 
 
 def geglu_fwd(u: torch.Tensor) -> torch.Tensor:
@@ -75,15 +81,29 @@ def geglu_bwd(u: torch.Tensor, dhid: torch.Tensor) -> torch.Tensor:
     return du
 
 
-def lin_wgrad(dy: torch.Tensor, x_in: torch.Tensor, dW: torch.Tensor, dbias: torch.Tensor = None) -> None:
-    """dW [N1, N2] f32 += dy^T . x_in for dy [M, N1], x_in [M, N2] (bf16, or f32: cast first); dbias [N1] += column sums of dy."""
+def lin_wgrad(dy: torch.Tensor, x_in: torch.Tensor, dW: torch.Tensor, dbias: Optional[torch.Tensor] = None, atomics: Optional[bool] = None) -> None:
+    """dW [N1, N2] f32 += dy^T . x_in for dy [M, N1], x_in [M, N2] (bf16, or f32: cast first); dbias [N1] += column sums of dy.
+    atomics: the form of ``op_gemm_tn``; None picks it by the size of dW (the denoiser and the encoder), False always takes the workspace
+    form (the autoencoder: its backward pass is bit-reproducible)."""
     if dy.dtype != torch.bfloat16:
         dy = cast_bf16(dy)
     if x_in.dtype != torch.bfloat16:
         x_in = cast_bf16(x_in)
-    # large gradients: the row ranges meet in a workspace and are summed in order (no atomics: reproducible, and 59 -> 38 us for ff.net.2 at
-    # 4 096 rows); a 512 x 512 gradient has too few ranges for the extra launch to pay (20.9 vs 24.0 us)
-    op_gemm_tn(dy, x_in, dW, dbias, atomics=dy.shape[1] * x_in.shape[1] < 512 * 1024)
+    if atomics is None:
+        # large gradients: the row ranges meet in a workspace and are summed in order (no atomics: reproducible, and 59 -> 38 us for ff.net.2
+        # at 4 096 rows); a 512 x 512 gradient has too few ranges for the extra launch to pay (20.9 vs 24.0 us)
+        atomics = dy.shape[1] * x_in.shape[1] < 512 * 1024
+    op_gemm_tn(dy, x_in, dW, dbias, atomics=atomics)
+
+
+def sgemm_acc(A, B, out, trans_a=False, trans_b=False, alpha=1.0, M=None, N=None, K=None):
+    """out[m, n] += alpha * sum_k A(m, k) B(n, k) in fp32 (see rald_op_sgemm_acc)."""
+    M = M if M is not None else (A.shape[1] if trans_a else A.shape[0])
+    K = K if K is not None else (A.shape[0] if trans_a else A.shape[1])
+    N = N if N is not None else (B.shape[1] if trans_b else B.shape[0])
+    check(lib().rald_op_sgemm_acc(A.data_ptr(), A.stride(0), int(trans_a), B.data_ptr(), B.stride(0), int(trans_b), out.data_ptr(), out.stride(0), M,
+                                  N, K, alpha, _stream()))
+    return out
 
 
 def colsum(x: torch.Tensor, out: torch.Tensor) -> None:
@@ -91,17 +111,22 @@ def colsum(x: torch.Tensor, out: torch.Tensor) -> None:
     check(lib().rald_op_colsum(x.data_ptr(), int(x.dtype == torch.bfloat16), x.stride(0), x.shape[0], x.shape[1], out.data_ptr(), _stream()))
 
 
-def attention_backward(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, nq: int, nk: int, dq, ld_dq, dk, ld_dk, dv, ld_dv):
+def attention_backward(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, nq: int, nk: int, dq, ld_dq, dk, ld_dk, dv, ld_dv, k_rows: int = 0):
     """Gradients of O = softmax(q k^T / 8) v per head (models_radar_generation.py:56-74).  q/k/v/dq/dk/dv are bf16
     tensors (possibly column slices of a fused buffer: pass the slice and its row stride); O, dO [Bn*nq, H*64] bf16.
-    Two launches of csrc/attn_bwd.hip (nothing score-shaped in memory) when nq % 128 == 0 and nk % 64 == 0 - the denoiser's
-    512 latents x 512 / 64 keys; other shapes take the unfused GEMM form below."""
-    if nq % 128 or nk % 64:
+    The key-side buffers (k, v, dk, dv) hold nk rows per sample, or k_rows >= nk when given: the autoencoder's mix attention keeps its nk
+    point embeddings in a buffer padded to a multiple of 64 rows.
+    Two launches of csrc/attn_bwd.hip (nothing score-shaped in memory; the last key tile is masked when nk % 64 != 0) when nq % 128 == 0
+    and the key rows per sample are a multiple of 64 - the denoiser's 512 latents x 512 / 64 keys, the autoencoder's 512 latents; other
+    shapes take the unfused GEMM form below (nk rows per sample)."""
+    k_rows = k_rows or nk
+    if nq % 128 or k_rows % 64:
+        assert k_rows == nk, "attention_backward: the unfused form reads nk key rows per sample"
         return attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn, H, nq, nk, dq, ld_dq, dk, ld_dk, dv, ld_dv)
     scratch = torch.empty(2, Bn * H * nq, device=O.device, dtype=torch.float32)
-    check(lib().rald_op_attention_bwd(q.data_ptr(), ldq, nq * ldq, k.data_ptr(), ldk, nk * ldk, v.data_ptr(), ldv, nk * ldv, O.data_ptr(),
+    check(lib().rald_op_attention_bwd(q.data_ptr(), ldq, nq * ldq, k.data_ptr(), ldk, k_rows * ldk, v.data_ptr(), ldv, k_rows * ldv, O.data_ptr(),
                                       O.stride(0), nq * O.stride(0), dO.data_ptr(), dO.stride(0), nq * dO.stride(0), dq.data_ptr(), ld_dq,
-                                      nq * ld_dq, dk.data_ptr(), ld_dk, nk * ld_dk, dv.data_ptr(), ld_dv, nk * ld_dv, scratch[0].data_ptr(),
+                                      nq * ld_dq, dk.data_ptr(), ld_dk, k_rows * ld_dk, dv.data_ptr(), ld_dv, k_rows * ld_dv, scratch[0].data_ptr(),
                                       scratch[1].data_ptr(), nq, nk, H, Bn, HEAD ** -0.5, _stream()))
 
 
@@ -114,12 +139,10 @@ def attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, n
     S, dP = f32(Bn, H, nq, nk), f32(Bn, H, nq, nk)
     gemm2(q, ldq, nq * ldq, HEAD, k, ldk, nk * ldk, HEAD, S, nk, H * nq * nk, nq * nk, nq, nk, HEAD, Bn, H, epilogue=1)
     gemm2(dO, H * HEAD, nq * H * HEAD, HEAD, v, ldv, nk * ldv, HEAD, dP, nk, H * nq * nk, nq * nk, nq, nk, HEAD, Bn, H, epilogue=1)
-    lse, delta = f32(Bn, H, nq), f32(Bn, H, nq)
-    check(lib().rald_op_row_lse(S.data_ptr(), Bn * H * nq, nk, scale, lse.data_ptr(), _stream()))
+    lse, delta = row_lse(S, scale), f32(Bn, H, nq)
     check(lib().rald_op_rowdot_heads(dO.data_ptr(), O.data_ptr(), Bn * nq, H, nq, delta.data_ptr(), _stream()))
     dS = b16(Bn, H, nq, nk)
-    check(lib().rald_op_attn_bwd_elem(S.data_ptr(), dP.data_ptr(), lse.data_ptr(), delta.data_ptr(), Bn * H, nq, nk, nq, 1, scale, 0, None,
-                                      dS.data_ptr(), _stream()))
+    attn_bwd_elem(S, dP, lse, delta, Bn * H, nq, nk, nq, 1, scale, 0, None, dS)
     kT = transpose(k, nk, HEAD, ldk, Bn, nk * ldk, H, HEAD)                     # [Bn, H, 64, nk]
     gemm2(dS, nk, H * nq * nk, nq * nk, kT, nk, H * HEAD * nk, HEAD * nk, dq, ld_dq, nq * ld_dq, HEAD, nq, HEAD, nk, Bn, H)
     # key side: transposed orientation
@@ -127,12 +150,48 @@ def attention_backward_unfused(q, ldq, k, ldk, v, ldv, O, dO, Bn: int, H: int, n
     gemm2(k, ldk, nk * ldk, HEAD, q, ldq, nq * ldq, HEAD, ST, nq, H * nk * nq, nk * nq, nk, nq, HEAD, Bn, H, epilogue=1)
     gemm2(v, ldv, nk * ldv, HEAD, dO, H * HEAD, nq * H * HEAD, HEAD, dPT, nq, H * nk * nq, nk * nq, nk, nq, HEAD, Bn, H, epilogue=1)
     PT, dST = b16(Bn, H, nk, nq), b16(Bn, H, nk, nq)
-    check(lib().rald_op_attn_bwd_elem(ST.data_ptr(), dPT.data_ptr(), lse.data_ptr(), delta.data_ptr(), Bn * H, nk, nq, nq, 1, scale, 1,
-                                      PT.data_ptr(), dST.data_ptr(), _stream()))
+    attn_bwd_elem(ST, dPT, lse, delta, Bn * H, nk, nq, nq, 1, scale, 1, PT, dST)
     qT = transpose(q, nq, HEAD, ldq, Bn, nq * ldq, H, HEAD)                     # [Bn, H, 64, nq]
     dOT = transpose(dO, nq, HEAD, H * HEAD, Bn, nq * H * HEAD, H, HEAD)
     gemm2(dST, nq, H * nk * nq, nk * nq, qT, nq, H * HEAD * nq, HEAD * nq, dk, ld_dk, nk * ld_dk, HEAD, nk, HEAD, nq, Bn, H)
     gemm2(PT, nq, H * nk * nq, nk * nq, dOT, nq, H * HEAD * nq, HEAD * nq, dv, ld_dv, nk * ld_dv, HEAD, nk, HEAD, nq, Bn, H)
+
+
+def row_lse(S: torch.Tensor, scale: float) -> torch.Tensor:
+    """fp32 S [..., cols] -> lse [...] fp32 = log sum_c exp(scale * S[..., c])."""
+    lse = torch.empty(S.shape[:-1], device=S.device, dtype=torch.float32)
+    check(lib().rald_op_row_lse(S.data_ptr(), lse.numel(), S.shape[-1], scale, lse.data_ptr(), _stream()))
+    return lse
+
+
+def attn_bwd_elem(S, dP, lse, delta, batch: int, R: int, cols: int, vbatch_stride: int, vstride: int, scale: float, by_col: int,
+                  P: Optional[torch.Tensor], dS: torch.Tensor) -> None:
+    """Softmax backward of S [batch][R][cols] (fp32 scores, dP their gradient), element-wise: P = exp(scale*S - lse[i]) (bf16, optional),
+    dS = P*(dP - delta[i])*scale (bf16), i = the row (by_col 0) or the column (by_col 1); see rald_op_attn_bwd_elem."""
+    check(lib().rald_op_attn_bwd_elem(S.data_ptr(), dP.data_ptr(), lse.data_ptr(), delta.data_ptr(), batch, R, cols, vbatch_stride, vstride, scale,
+                                      by_col, _opt(P), dS.data_ptr(), _stream()))
+
+
+def rowdot(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """bf16 a, b [M, C] -> fp32 [M] of the row dot products (the delta = <dO, O> of a 1-head attention backward)."""
+    out = torch.empty(a.shape[0], device=a.device, dtype=torch.float32)
+    check(lib().rald_op_rowdot(a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], out.data_ptr(), _stream()))
+    return out
+
+
+def softmax_rows(S: torch.Tensor, n: int) -> torch.Tensor:
+    """fp32 S [..., ld] -> bf16 P of the same shape: the softmax of each row's first n entries, zero past them."""
+    P = torch.empty(S.shape, device=S.device, dtype=torch.bfloat16)
+    ld = S.shape[-1]
+    check(lib().rald_op_softmax_rows(S.data_ptr(), ld, P.data_ptr(), ld, S.numel() // ld, n, _stream()))
+    return P
+
+
+def pad_channels(x: torch.Tensor, cols: int) -> torch.Tensor:
+    """fp32 [..., C] -> bf16 [..., cols] with zero columns C .. cols-1."""
+    out = torch.empty(*x.shape[:-1], cols, device=x.device, dtype=torch.bfloat16)
+    check(lib().rald_op_pad_channels(x.data_ptr(), out.data_ptr(), x.numel() // x.shape[-1], x.shape[-1], cols, _stream()))
+    return out
 
 
 def prepare_block_weights(sd: Dict[str, torch.Tensor], prefix: str, device) -> Dict[str, torch.Tensor]:

@@ -198,7 +198,7 @@ def test_backward_is_bit_reproducible_and_single_use():
 def test_attention_bwd_key_tail_matches_fp32_autograd(nk):
     """The fused head-64 backward with a masked last key tile (nk % 64 != 0) against autograd of the fp32 definition on the same bf16
     inputs (the unfused train_ops form needs nk % 64 == 0 too: its dQ product contracts over the keys)."""
-    from rald_amd.train_ae import attention_bwd_rows
+    from rald_amd import train_ops as TO
     B, H, nq, D = 2, 8, 512, 512
     kp = (nk + 63) // 64 * 64
     g = torch.Generator().manual_seed(nk)
@@ -216,7 +216,7 @@ def test_attention_bwd_key_tail_matches_fp32_autograd(nk):
     (Of * dO.float().view(B, nq, H, 64).transpose(1, 2)).sum().backward()
     O = Of.detach().transpose(1, 2).reshape(B * nq, D).to(torch.bfloat16).contiguous()
     dq, dkv = torch.empty_like(q), torch.zeros_like(kv)
-    attention_bwd_rows(q, kv, O, dO, dq, dkv, B, H, nq, kp, nk)
+    TO.attention_backward(q, D, kv, 2 * D, kv[:, D:], 2 * D, O, dO, B, H, nq, nk, dq, D, dkv, 2 * D, dkv[:, D:], 2 * D, k_rows=kp)
     dkv3 = dkv.view(B, kp, 2 * D).float()
     e = (rel_l2(dq.float(), qf.grad.transpose(1, 2).reshape(B * nq, D)),
          rel_l2(dkv3[:, :nk, :D], kf.grad.transpose(1, 2).reshape(B, nk, D)),

@@ -302,6 +302,24 @@ def test_shipped_library_reads_no_environment_variable():
                     assert "csrc" not in inc and os.path.basename(inc) not in product, (path, n, line)
 
 
+def test_each_op_entry_point_is_called_from_one_module():
+    """A rald_op_* entry point has one Python wrapper: it is called from one module of the package only (the three trainers share the
+    wrappers of train_ops.py), and an optional argument is a nullable parameter of the entry, not a second entry beside it."""
+    callers = {}
+    for path in sorted(glob.glob(os.path.join(ROOT, "rald_amd", "*.py"))):
+        with open(path) as f:
+            for name in set(re.findall(r"\.(rald_op_\w+)\s*\(", f.read())):
+                callers.setdefault(name, []).append(os.path.basename(path))
+    shared = {name: mods for name, mods in callers.items() if len(mods) > 1}
+    assert not shared, shared
+    with open(os.path.join(ROOT, "include", "rald_hip.h")) as f:
+        hdr = f.read()
+    # (kept entry, suffix of the twin it absorbed)
+    for kept, suffix in (("rald_op_gemm_tn", "_ws"), ("rald_op_conv3d_wgrad", "_ws"), ("rald_op_ln_mod_bwd", "_cast"), ("rald_op_groupnorm_bwd", "_cast"),
+                         ("rald_op_conv3d", "_bf16")):
+        assert re.search(rf"\b{kept}\s*\(", hdr) and not re.search(rf"\b{kept}{suffix}\b", hdr), kept + suffix
+
+
 def test_module_forward_checks_batch_sizes_before_touching_the_gpu():
     """VERDICT r02 weak #5: a condition batch that does not match x used to reach the kernels (out-of-bounds reads)."""
     from rald_amd import models_radar_generation as G

@@ -92,7 +92,7 @@ def test_weight_gradients_through_the_workspace_are_bit_reproducible_and_match_t
             outs.append((dW, db))
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
         aW, ab = torch.full((Cout, Cin, 3, 3, 3), 0.5, device="cuda"), torch.full((Cout,), 0.25, device="cuda")
-        check(lib().rald_op_conv3d_wgrad(p(dy), p(x16), p(aW), p(ab), B, D, H, W, Cin, Cout, 1, 1, None))
+        check(lib().rald_op_conv3d_wgrad(p(dy), p(x16), p(aW), p(ab), B, D, H, W, Cin, Cout, 1, 1, None, 0, None))
         torch.cuda.synchronize()
         assert rel_l2(outs[0][0].cpu(), aW.cpu()) < 1e-6 and rel_l2(outs[0][1].cpu(), ab.cpu()) < 1e-6
     A, Bm = synth.normal([1024, 256], 622).bfloat16().cuda(), synth.normal([1024, 384], 623).bfloat16().cuda()
