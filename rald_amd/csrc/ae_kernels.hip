@@ -67,7 +67,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     for (int i = threadIdx.x; i < (int)ld_p; i += 256) p[i] = (bf16)(i < n ? __expf(s[i] - mx) * inv : 0.f);
 }
 int softmax_rows(const float* S, int64_t ld_s, bf16* P, int64_t ld_p, int rows, int n, hipStream_t st) {
-    RALD_CHECK(rows > 0 && n > 0 && ld_s >= n && ld_p >= n, "softmax_rows: bad shape");
+    RALD_CHECK(rows > 0 && n > 0, "softmax_rows: bad shape");
+    RALD_CHECK(ld_s >= n && ld_p >= n, "softmax_rows: ld_s and ld_p must be >= n");
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, st, S, ld_s, P, ld_p, n);
     RALD_HIP(hipGetLastError());
     return 0;

@@ -102,7 +102,8 @@ int ln_affine_bwd(const float* x, const float* dh, const float* g, float eps, in
     RALD_CHECK(rows > 0, "ln_affine_bwd: empty");
     const int64_t nwg = (rows + LN_ROWS - 1) / LN_ROWS;
     RALD_CHECK(nwg < (1ll << 31), "ln_affine_bwd: too many rows");
-    RALD_CHECK(scratch && scratch_bytes >= ln_affine_bwd_scratch_bytes(rows) && (uintptr_t)scratch % 16 == 0, "ln_affine_bwd: scratch too small");
+    RALD_CHECK(scratch && scratch_bytes >= ln_affine_bwd_scratch_bytes(rows), "ln_affine_bwd: scratch too small");
+    RALD_CHECK((uintptr_t)scratch % 16 == 0, "ln_affine_bwd: scratch must be 16-byte aligned");
     RALD_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)dh % 16 == 0 && (uintptr_t)dx % 16 == 0 && (uintptr_t)dx_bf16 % 16 == 0,
                "ln_affine_bwd: 16-byte alignment");
     hipLaunchKernelGGL(ln_affine_bwd_kernel, dim3((unsigned)nwg), dim3(256), 0, st, x, dh, g, eps, rows, dx, dx_bf16, scratch);
@@ -183,6 +184,7 @@ int pe_wgrad(const float* dY, const float* pts, const float* basis, int64_t rows
     const int64_t nwg = (rows + PE_ROWS - 1) / PE_ROWS;
     RALD_CHECK(nwg < (1ll << 31), "pe_wgrad: too many rows");
     RALD_CHECK(scratch && scratch_bytes >= pe_wgrad_scratch_bytes(rows), "pe_wgrad: scratch too small");
+    RALD_CHECK((uintptr_t)scratch % 16 == 0, "pe_wgrad: scratch must be 16-byte aligned");
     hipLaunchKernelGGL(pe_wgrad_kernel, dim3((unsigned)nwg), dim3(256), 0, st, dY, pts, basis, rows, scratch);
     hipLaunchKernelGGL(pe_wgrad_reduce_kernel, dim3(cdiv(512 * PE_F, 256)), dim3(256), 0, st, scratch, (int)nwg, dW, db);
     RALD_HIP(hipGetLastError());
@@ -236,7 +238,8 @@ __global__ __launch_bounds__(256) void scale_rows_bf16_kernel(const float* __res
 }
 
 int scale_rows(const float* in, const float* s, float* x_accum, bf16* out_bf16, int64_t rows, int cols, int64_t rows_per_sample, hipStream_t st) {
-    RALD_CHECK(in && s && (x_accum || out_bf16) && rows > 0 && cols > 0 && cols % 4 == 0 && rows_per_sample > 0, "scale_rows: bad arguments");
+    RALD_CHECK(in && s && (x_accum || out_bf16) && rows > 0 && cols > 0 && rows_per_sample > 0, "scale_rows: bad arguments");
+    RALD_CHECK(cols % 4 == 0, "scale_rows: cols must be a multiple of 4");
     const int64_t total4 = rows * cols / 4;
     const dim3 grid((unsigned)((total4 + 255) / 256));
     if (x_accum) hipLaunchKernelGGL(scale_rows_add_kernel, grid, dim3(256), 0, st, in, s, x_accum, rows_per_sample, cols, total4);
@@ -276,7 +279,8 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float* __re
 
 int softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_t rows, int64_t ld, int n, float scale, bf16* P, bf16* dS,
                      hipStream_t st) {
-    RALD_CHECK(S && dP && delta && dS && rows > 0 && n > 0 && ld >= n, "softmax_bwd_rows: bad arguments");
+    RALD_CHECK(S && dP && delta && dS && rows > 0 && n > 0, "softmax_bwd_rows: bad arguments");
+    RALD_CHECK(ld >= n, "softmax_bwd_rows: ld must be >= n");
     RALD_CHECK(rows < (1ll << 31), "softmax_bwd_rows: too many rows");
     hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, S, dP, delta, ld, n, scale, P, dS);
     RALD_HIP(hipGetLastError());

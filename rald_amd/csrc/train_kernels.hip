@@ -407,15 +407,21 @@ int sgemm_acc(const float* A, int64_t lda, int trans_a, const float* B, int64_t 
     return 0;
 }
 
-// silu(x) = x * sigmoid(x)  (models_radar_generation.py:217-219)
+// silu(x) = x * sigmoid(x)  (models_radar_generation.py:217-219).  sigmoid from exp(-|x|), which cannot overflow: 1 / (1 + exp(-x))
+// flushed sigmoid to zero below x = -88.7 (exp(-x) = inf), so silu and its gradient came out 0 where they are ~1e-37, and __expf's
+// argument scaling cost ~|x| ulps near that edge.
+__device__ __forceinline__ float sigmoid_f32(float v) {
+    const float e = expf(-fabsf(v)), s = 1.0f / (1.0f + e);
+    return v >= 0.f ? s : e * s;
+}
 __global__ void silu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { const float v = x[i]; y[i] = v / (1.0f + __expf(-v)); }
+    if (i < n) { const float v = x[i]; y[i] = v * sigmoid_f32(v); }
 }
 __global__ void silu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        const float v = x[i], s = 1.0f / (1.0f + __expf(-v));
+        const float v = x[i], s = sigmoid_f32(v);
         dx[i] = dy[i] * s * (1.0f + v * (1.0f - s));
     }
 }

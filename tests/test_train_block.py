@@ -57,6 +57,79 @@ def test_backward_kernels_vs_torch_autograd():
     out.zero_()
     TO.colsum(y.bfloat16().cuda(), out)
     assert rel_l2(out.cpu(), y.bfloat16().float().sum(0)) < 1e-5
+    _colsum_widths_against_float64(TO)
+    _transpose_elementwise_path_with_both_batch_levels(TO)
+    _ln_mod_bwd_row_tails_against_float64(TO)
+
+
+def _ratio(got, ref, terms):
+    """max |got - ref| / (2^-24 * terms) per element (terms: the sum of the absolute terms that make the result)"""
+    err = (got.detach().cpu().double() - ref).abs()
+    r = err / (2.0 ** -24 * terms.clamp_min(2.0 ** -126))
+    return float(torch.where(torch.isnan(err), torch.full_like(r, float("inf")), r).max())
+
+
+def _colsum_widths_against_float64(TO):
+    """colsum at every column-width rule (cw = N when N divides 256, else 256 with a ragged last block) over 5 000 rows (several row blocks
+    meeting in atomics): per column against float64, accumulated into a non-zero prefill; the input is a column window of a wider buffer
+    whose gap holds NaN (a read of it poisons the sum) and the 8 floats past the output keep their sentinel.  Measured k <= 11.9 (the
+    fp32 atomics' order); bound 29."""
+    worst = 0.0
+    for N in (1, 3, 64, 256, 300, 1000):
+        for bf in (False, True):
+            Xb = torch.full((5000, N + 8), float("nan"))
+            Xb[:, :N] = synth.normal([5000, N], 508 + N) + 0.5
+            X = Xb.bfloat16() if bf else Xb
+            o0 = synth.normal([N], 509 + N)
+            o = torch.full((N + 8,), -7.5, device="cuda")
+            o[:N] = o0.cuda()
+            TO.colsum(X.cuda()[:, :N], o[:N])
+            Xd = X[:, :N].double()
+            worst = max(worst, _ratio(o[:N], o0.double() + Xd.sum(0), o0.double().abs() + Xd.abs().sum(0)))
+            assert bool((o[N:] == -7.5).all()), (N, bf)
+    print(f"colsum ratio {worst:.3g}")
+    assert worst <= 29
+
+
+def _transpose_elementwise_path_with_both_batch_levels(TO):
+    """transpose's element-wise path (rows 37, cols 20: not multiples of 8) on 3 x 3 column slices of rows 64 wide, f32 and bf16 in: bit for bit"""
+    x = synth.normal([3, 37, 64], 514).cuda()
+    want = x[:, :, :60].reshape(3, 37, 3, 20).permute(0, 2, 3, 1).bfloat16()
+    assert torch.equal(TO.transpose(x, 37, 20, 64, batch=3, stride_in=37 * 64, batch2=3, stride_in2=20), want)
+    assert torch.equal(TO.transpose(x.bfloat16(), 37, 20, 64, batch=3, stride_in=37 * 64, batch2=3, stride_in2=20), want)
+
+
+def _ln_mod_bwd_row_tails_against_float64(TO):
+    """ln_mod_bwd (16 rows per workgroup) at 150 rows in groups of 48 (the last group and the last workgroup partial) and at one group of 37
+    rows (rows_per_group >= rows), per element against float64 autograd of LayerNorm * (1 + scale) + shift; modulation rows 2*512 + 64 apart
+    (the 64-float gaps of dscale / dshift keep their prefill), dx and dscale / dshift accumulated into non-zero values, the bf16 copy equal
+    to the updated dx rounded.  Measured k (dx, dscale, dshift): 150 rows (2.08, 1.91, 1.47), 37 rows (1.67, 1.2, 1.01); bounds as below."""
+    D = 512
+    for rows, rpg, bounds in ((150, 48, (5, 4.7, 3.6)), (37, 37, (4.1, 3, 2.5))):
+        ng, gs = -(-rows // rpg), 2 * D + 64
+        x64 = (synth.normal([rows, D], 515) * 2 + 0.3).double().requires_grad_()
+        modb = synth.normal([ng, gs], 516) * 0.2
+        s64, t64 = modb[:, :D].double().requires_grad_(), modb[:, D:2 * D].double().requires_grad_()
+        dh = synth.normal([rows, D], 517)
+        grp = torch.arange(rows) // rpg
+        (torch.nn.functional.layer_norm(x64, (D,)) * (1 + s64[grp]) + t64[grp]).backward(dh.double())
+        mod = modb.cuda()
+        dmod = torch.full_like(mod, 0.5)
+        dx = torch.ones(rows, D, device="cuda")
+        dxb = torch.zeros(rows, D, device="cuda", dtype=torch.bfloat16)
+        TO.ln_mod_bwd(x64.detach().float().cuda(), dh.cuda(), mod[:, :D], gs, rpg, 1.0, dx, dmod[:, :D], dmod[:, D:2 * D], dx_bf16=dxb)
+        assert torch.equal(dxb, dx.bfloat16()) and bool((dmod[:, 2 * D:] == 0.5).all())
+        xx = x64.detach()
+        mu = xx.mean(-1, keepdim=True)
+        rstd = 1 / torch.sqrt(((xx - mu) ** 2).mean(-1, keepdim=True) + 1e-5)
+        xh = (xx - mu) * rstd
+        gh = (dh.double() * (1 + s64.detach()[grp])).abs()
+        tdx = 1 + rstd * (gh + gh.mean(-1, keepdim=True) + xh.abs() * (gh * xh.abs()).mean(-1, keepdim=True))
+        e = (_ratio(dx, 1 + x64.grad, tdx),
+             _ratio(dmod[:, :D], 0.5 + s64.grad, 0.5 + torch.zeros(ng, D, dtype=torch.float64).index_add_(0, grp, (dh.double() * xh).abs())),
+             _ratio(dmod[:, D:2 * D], 0.5 + t64.grad, 0.5 + torch.zeros(ng, D, dtype=torch.float64).index_add_(0, grp, dh.double().abs())))
+        print(f"ln_mod_bwd rows={rows} rpg={rpg} ratios dx {e[0]:.3g} dscale {e[1]:.3g} dshift {e[2]:.3g}")
+        assert all(v <= b for v, b in zip(e, bounds)), (e, bounds)
 
 
 def test_attention_backward_vs_autograd():
