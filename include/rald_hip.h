@@ -496,6 +496,15 @@ int rald_op_reduce_resid_ln(const float* part, int32_t slabs, int64_t slab_strid
  * t2aug_out [d][64] fp32, l_img_out [64][64] fp16 bits (no GPU needed: what the CPU tests check the folding with). */
 int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, const float* norm_w, const float* norm_b, const float* wpe,
                              const float* bpe, const float* wfold, float* t2aug_out, uint16_t* l_img_out);
+/* rald_op_ae_decode: the decoder on such tables, as rald_ae_decode_latents ends and rald_ae_decode_queries runs it.  All device memory:
+ * x fp32 [batch*num_latents][dim] (output of the latent stack), gamma / beta [dim] (norm_context), t2aug [dim][64], l_img [64][64] fp16
+ * (16-byte aligned), basis [3][24] (block-diagonal -> one multiply per projection, anything else -> three; decided here as at weight load),
+ * queries fp32 [batch][n_queries][3] -> out_logits fp32 [batch][n_queries].  dim 256 or 512, num_latents a multiple of 32 in [32,1024],
+ * batch in [1,65535]; scratch (16-byte aligned) of rald_op_ae_decode_scratch_bytes(batch, num_latents) bytes (-1: refused). */
+int64_t rald_op_ae_decode_scratch_bytes(int32_t batch, int32_t num_latents);
+int rald_op_ae_decode(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
+                      float c0, const float* queries, float* out_logits, int32_t batch, int64_t n_queries, int32_t num_latents, int32_t dim,
+                      void* scratch, int64_t scratch_bytes, void* stream);
 /* Folded encoder (KLAutoEncoder.encode :351-399; rald_amd/csrc/ae_encode.hip): both attentions of the latent queries over the
  * input points run with ONE fp16 row of 52 Fourier features per point as key and value (head dim 64).
  * _tables: the weight-only tables, computed on the HOST in double (no GPU needed).  in[18] = host fp32 tensors in the reference's

@@ -403,6 +403,28 @@ def op_ae_enc_features(pc: torch.Tensor, basis: torch.Tensor, var_factor: torch.
     return F, G
 
 
+def op_ae_decode(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2aug: torch.Tensor, l_img: torch.Tensor, basis: torch.Tensor,
+                 c0: float, queries: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The streaming query decoder on caller-made tables (rald_amd/csrc/ae_decode.hip): x fp32 [B,M,dim] (output of the latent stack),
+    gamma / beta [dim] (norm_context), t2aug fp32 [dim,64] and l_img [64*64] fp16 (or its bits as int16) as rald_op_ae_decode_tables writes
+    them, basis [3,24], queries fp32 [B,Q,3] -> logits fp32 [B,Q], written to `out` (B*Q contiguous floats) when it is given."""
+    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis"), (queries, "queries")):
+        _need_cuda(t, what)
+    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
+    x, gamma, beta, t2aug, basis, queries = (_f32c(t) for t in (x, gamma, beta, t2aug, basis, queries))
+    (B, M, dim), Q = x.shape, queries.shape[1]
+    assert queries.shape[0] == B and queries.shape[2] == 3 and t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim
+    assert basis.shape == (3, 24)
+    if out is None:
+        out = torch.empty(B, Q, device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() == B * Q
+    nbytes = _nbytes(lib().rald_op_ae_decode_scratch_bytes(B, M))
+    scratch = _scratch(nbytes, x.device)
+    check(lib().rald_op_ae_decode(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), t2aug.data_ptr(), l_img.data_ptr(), basis.data_ptr(), c0,
+                                  queries.data_ptr(), out.data_ptr(), B, Q, M, dim, scratch.data_ptr(), nbytes, _stream()))
+    return out.view(B, Q)
+
+
 class AeHandle(_Handle):
     """rald_ae*: encode / decode_latents / decode_queries of the set-latent autoencoder."""
 

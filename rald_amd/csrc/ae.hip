@@ -275,10 +275,7 @@ int Ae::finalize() {
     RALD_TRY(ae_decode_tables(d, h_dec_wq.data(), h_dec_wkv.data(), h_dec_ng.data(), h_dec_nb.data(), h_wpe.data(), h_bpe.data(), wf.data(), t2, limg));
     RALD_HIP(hipMemcpy(t2aug, t2.data(), t2.size() * 4, hipMemcpyHostToDevice));
     RALD_HIP(hipMemcpy(l_img, limg.data(), limg.size() * 2, hipMemcpyHostToDevice));
-    basis_diag = 1;                    // block-diagonal basis (x -> columns 0-7, y -> 8-15, z -> 16-23): one multiply per projection
-    for (int a = 0; a < 3; ++a)
-        for (int e = 0; e < 24; ++e)
-            if (e / 8 != a && h_basis[(size_t)a * 24 + e] != 0.f) basis_diag = 0;
+    basis_diag = ae_basis_is_block_diagonal(h_basis.data());
     finalized = true;
     return 0;
 }

@@ -28,6 +28,15 @@
 // S^T = H~.f~^T puts the latent index on the accumulator registers and the query on the lane: the softmax over the M
 // latents is lane-local (online, lazily rescaled), u is read from LDS as a broadcast.  Bound: v_exp_f32 + the 3 VALU per
 // score next to 4 MFMA per 32x32 score tile - not HBM (16 B/query) and not the 2.15 MFLOP/query the reference executes.
+//
+// A query's logit is reproducible for the same 64-query chunk (any batch size, any grid), but not bit for bit in other company: the
+// running maximum moves when ANY lane of the wave asks for it (__any), so the steps at which a query's sums are rescaled depend on
+// its wave-mates; the last bits follow (measured: 1e-6 on logits of a few units).
+//
+// Domain: scores (log2 units) below 2^29 in size.  vm = tm * rq is a rounded product while the exponents fmaf(acc, rq, -m) use the exact
+// one, so a score can sit half an ulp of itself above the maximum it was compared with: harmless up to 2^29 (8 + 64 < 127), but from
+// 2^31 on that half ulp alone is 2^7 and exp2 returns inf (logit NaN).  No fp32 softmax means anything there (the reference's own scores
+// carry the same ulp of 2^9); real contexts have scores of 10 .. 100.
 #include <cmath>
 #include <vector>
 
@@ -177,9 +186,11 @@ __global__ __launch_bounds__(256) void ae_ctx_pack_kernel(const float* __restric
     const float* y = Y + (int64_t)b * M * 64;
     unsigned char* out = ctx + (int64_t)b * ctx_stride;
     const float mx = __uint_as_float(absmax[b]);
-    // power-of-two scale that puts the largest entry into [2^13, 2^14): fp16 keeps 11 bits for everything within 2^-27 of it
+    // power-of-two scale that puts the largest entry into [2^13, 2^14): fp16 keeps 11 bits for everything within 2^-27 of it.
+    // The exponent stops at 126: a largest entry below 2^-113 would ask for a scale (and 0 * scale = NaN) beyond fp32, and 1 / scale
+    // stays a normal number; such a context sits lower in the fp16 range instead (2^-120 -> 2^6, still 11 bits down to 2^-20 of it)
     float scale = 1.0f;
-    if (mx > 0.f && mx < 3.0e38f) scale = exp2f((float)(13 - ilogbf(mx)));
+    if (mx > 0.f && mx < 3.0e38f) scale = exp2f((float)min(13 - ilogbf(mx), 126));
     float v = 0.f;
     if (k < SLOT_ONE) v = y[l * 64 + k] * scale;
     else if (k == SLOT_ONE || k == SLOT_ONE + 1) {

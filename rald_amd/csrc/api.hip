@@ -162,6 +162,31 @@ int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, cons
     memcpy(l_img_out, li.data(), li.size() * 2);
     return 0;
 }
+// the decoder itself on caller-made tables: the context build and the streaming kernel of Ae::decode_latents / Ae::decode_queries, the
+// kernel's form picked from the basis by the same rule.  Every argument check comes before the first HIP call.
+int64_t rald_op_ae_decode_scratch_bytes(int32_t batch, int32_t num_latents) {
+    if (batch < 1 || batch > 65535 || num_latents < 32 || num_latents > 1024 || num_latents % 32) return -1;
+    return ae_decode_op_scratch_bytes(batch, num_latents);
+}
+int rald_op_ae_decode(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
+                      float c0, const float* queries, float* out_logits, int32_t batch, int64_t n_queries, int32_t num_latents, int32_t dim,
+                      void* scratch, int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(x && gamma && beta && t2aug && l_img && basis && queries && out_logits && scratch, "rald_op_ae_decode: null pointer");
+    RALD_CHECK(dim == 256 || dim == 512, "rald_op_ae_decode: dim must be 256 or 512");
+    RALD_CHECK(num_latents >= 32 && num_latents <= 1024 && num_latents % 32 == 0,
+               "rald_op_ae_decode: num_latents must be a multiple of 32 in [32,1024]");
+    RALD_CHECK(batch >= 1 && batch <= 65535, "rald_op_ae_decode: batch must be in [1,65535]");
+    RALD_CHECK(n_queries >= 1, "rald_op_ae_decode: n_queries must be at least 1");
+    RALD_CHECK((uintptr_t)scratch % 16 == 0 && (uintptr_t)l_img % 16 == 0, "rald_op_ae_decode: scratch and l_img must be 16-byte aligned");
+    RALD_CHECK(scratch_bytes >= ae_decode_op_scratch_bytes(batch, num_latents), "rald_op_ae_decode: scratch too small");
+    hipStream_t st = (hipStream_t)stream;
+    float h_basis[72];
+    RALD_HIP(hipMemcpyAsync(h_basis, basis, sizeof(h_basis), hipMemcpyDeviceToHost, st));
+    RALD_HIP(hipStreamSynchronize(st));
+    void* ctx = (char*)scratch + ae_decode_op_ctx_offset(batch, num_latents);
+    RALD_TRY(ae_ctx_build(x, gamma, beta, t2aug, (float*)scratch, ctx, batch, num_latents, dim, st));
+    return ae_decode_stream(ctx, l_img, queries, out_logits, basis, ae_basis_is_block_diagonal(h_basis), batch, n_queries, num_latents, c0, st);
+}
 
 // ---- standalone radar-spectrum encoder (RadarAutoencoder.encoder) -------------------------------
 struct rald_radar { DeviceArena arena; Stager stager; RadarEncoder enc, dec; int R, A, E, cin, zc; bool dec_touched = false; };

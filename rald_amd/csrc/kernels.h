@@ -267,6 +267,17 @@ int ae_ctx_build(const float* x, const float* gamma, const float* beta, const fl
                  hipStream_t st);
 int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* queries, float* out, const float* basis, int basis_diag,
                      int B, int64_t Q, int M, float c0, hipStream_t st);
+// basis_diag of a host copy of point_embed.basis [3][24]: 1 when it is block-diagonal (x -> columns 0-7, y -> 8-15, z -> 16-23), which
+// makes a projection one multiply instead of three; the one rule by which every caller picks the streaming kernel's form
+inline int ae_basis_is_block_diagonal(const float* basis_host) {
+    for (int a = 0; a < 3; ++a)
+        for (int e = 0; e < 24; ++e)
+            if (e / 8 != a && basis_host[a * 24 + e] != 0.f) return 0;
+    return 1;
+}
+// scratch of one rald_op_ae_decode call: projection [B*M][64] fp32 + one |max| word per sample, then the B contexts (16-byte aligned)
+inline int64_t ae_decode_op_ctx_offset(int B, int M) { return ((int64_t)B * M * 64 * 4 + (int64_t)B * 4 + 15) / 16 * 16; }
+inline int64_t ae_decode_op_scratch_bytes(int B, int M) { return ae_decode_op_ctx_offset(B, M) + (int64_t)B * ae_ctx_stride(M); }
 
 // ---------------------------------------------------------------- post.hip
 int post_scratch_ints(int64_t Q);
