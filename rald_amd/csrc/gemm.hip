@@ -406,7 +406,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         __builtin_amdgcn_s_barrier();         // every wave is done reading the staging buffers: reuse them as patches
         asm volatile("" ::: "memory");
     }
-    gemm_epilogue_lds<MT, NT, EPI>(acc, a, m0 + wm * (BM / WM), n0 + wn * (BN / WN), coff, lane, smem + wave * 8704);
+    gemm_epilogue_lds<MT, NT, EPI>(acc, a, m0 + wm * (BM / WM), n0 + wn * (BN / WN), coff, lane, smem + wave * EPI_PATCH_BYTES,
+                                   reinterpret_cast<float*>(smem + WAVES * EPI_PATCH_BYTES) + wave * NT * 16);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -428,7 +429,7 @@ template <int BM, int BN, int WM, int WN, int NSTAGE, int EPI>
 static int launch_glds_epi(const GemmArgs& a, hipStream_t st) {
     constexpr int WAVES = WM * WN;
     constexpr int smem = NSTAGE * (BM + BN) * 64 * 2;
-    static_assert(smem >= WAVES * 8704, "epilogue patches must fit in the staging buffers");
+    static_assert(smem >= epi_lds_bytes<BN / (16 * WN)>(WAVES), "epilogue patches and bias slots must fit in the staging buffers");
     static bool attr_set = false;
     auto kern = gemm_nt_glds_kernel<BM, BN, WM, WN, NSTAGE, EPI>;
     if (!attr_set && smem > 64 * 1024) {

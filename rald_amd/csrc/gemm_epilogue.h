@@ -15,11 +15,22 @@ static __device__ unsigned g_f16_sat_gemm;
 // the FF1 kernel).  Instead each wave transposes one 16-row m-tile at a time through a private LDS
 // patch (row stride padded by 16 B) and writes it back as whole rows, 16 B per lane: full 128-B
 // lines.  Wave-private, so no workgroup barrier; LDS ops of one wave execute in order.
-// lds_bias (GEGLU only): the wave's NT*16 bias values already in LDS (persistent engine: an ordinary global load next to
-// in-flight LDS-DMA makes hipcc wait vmcnt(0), draining the next tile's prefetch - guide section 5, trap (b))
+//
+// RULE for every epilogue in this project: all VMEM loads go BEFORE the first store; per-column vectors (bias, modulation rows)
+// are read from LDS inside the m-tile loop; no reads through generic pointers.  On gfx950 vmcnt is ONE in-order counter for
+// loads and stores, so the s_waitcnt of a load issued behind a store also waits for that store's acknowledgement: a bias load
+// per m-tile (which an `asm volatile(... "memory")` store forces the compiler to repeat) serialises the m-tiles on a store round
+// trip each, and a generic (FLAT) read brings a vmcnt(0) lgkmcnt(0) of its own.  tools/isa_audit.py checks the hot kernels.
+//
+// Here: the wave's NT*16 bias values (zeros without a bias or past column N) are fetched once, written to the wave's own
+// `wbias` slot in LDS and read back per m-tile with ds_read - wave-private like the patch, so no barrier.  `patch` and `wbias`
+// must both be derived from the kernel's __shared__ array in the caller, so that the compiler addresses them as LDS.
+constexpr int EPI_PATCH_BYTES = 8704;                                    // one wave's transpose patch (16 rows x (512 + 16) B is the largest)
+template <int NT> constexpr int epi_lds_bytes(int waves) { return waves * (EPI_PATCH_BYTES + NT * 16 * 4); }   // patches, then the bias slots
+
 template <int MT, int NT, int EPI>
 __device__ __forceinline__ void gemm_epilogue_lds(f32x4 (&acc)[MT][NT], const GemmArgs& a, int mb, int nb, int64_t coff, int lane,
-                                                  unsigned char* patch, const float* lds_bias = nullptr) {
+                                                  unsigned char* patch, float* wbias) {
     const int fr = lane & 15, fq = lane >> 4;
     constexpr bool F32OUT = (EPI == EPI_F32 || EPI == EPI_RESID);
     constexpr int OC = (EPI == EPI_GEGLU) ? NT * 8 : NT * 16;            // output columns of this wave
@@ -27,18 +38,27 @@ __device__ __forceinline__ void gemm_epilogue_lds(f32x4 (&acc)[MT][NT], const Ge
     constexpr int STRIDE = ROWB + 16;
     constexpr int LPR = ROWB / 16;                                       // lanes per row (16 B each)
     constexpr int RPI = (64 / LPR) > 16 ? 16 : (64 / LPR);               // rows per store instruction (narrow tiles: lanes >= 16*LPR idle)
-    static_assert(ROWB % 16 == 0 && 64 % LPR == 0 && 16 % RPI == 0 && 16 * STRIDE <= 8704, "epilogue tiling");
+    static_assert(ROWB % 16 == 0 && 64 % LPR == 0 && 16 % RPI == 0 && 16 * STRIDE <= EPI_PATCH_BYTES, "epilogue tiling");
     const int oc0 = (EPI == EPI_GEGLU) ? nb / 2 : nb;                     // first output column
     const int ncols = (EPI == EPI_GEGLU) ? a.N / 2 : a.N;
+    if constexpr (EPI != EPI_SOFTMAX64) {
+        // the only VMEM load of the epilogue (EPI_RESID's read-modify-write of C aside): lane l < 4*NT fetches columns nb + 4l .. + 3
+        static_assert(NT * 4 <= 64, "one float4 per lane covers the wave's bias slice");
+        if (lane < NT * 4) {
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (a.bias && nb + 4 * lane < a.N) b = *reinterpret_cast<const float4*>(a.bias + nb + 4 * lane);
+            *reinterpret_cast<float4*>(wbias + 4 * lane) = b;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         // ---- lane-owned values -> LDS patch [16 rows][OC]
         if constexpr (EPI == EPI_GEGLU) {
 #pragma unroll
             for (int p = 0; p < NT / 2; ++p) {
-                const int nx = nb + 32 * p + 4 * fq;
-                const float4 bx = lds_bias ? *reinterpret_cast<const float4*>(lds_bias + 32 * p + 4 * fq) : *reinterpret_cast<const float4*>(a.bias + nx);
-                const float4 bg = lds_bias ? *reinterpret_cast<const float4*>(lds_bias + 32 * p + 4 * fq + 16) : *reinterpret_cast<const float4*>(a.bias + nx + 16);
+                // packed rows nb + 32p + 4fq .. + 3 are the 'x' half, + 16 the gate half
+                const float4 bx = *reinterpret_cast<const float4*>(wbias + 32 * p + 4 * fq);
+                const float4 bg = *reinterpret_cast<const float4*>(wbias + 32 * p + 4 * fq + 16);
                 const f32x4 x = acc[i][2 * p], g = acc[i][2 * p + 1];
                 const f32x2 g01 = gelu_poly2(f32x2{g[0] + bg.x, g[1] + bg.y});
                 const f32x2 g23 = gelu_poly2(f32x2{g[2] + bg.z, g[3] + bg.w});
@@ -76,8 +96,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(f32x4 (&acc)[MT][NT], const Ge
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int n = nb + j * 16 + 4 * fq;
-                float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a.bias && n < a.N) b = *reinterpret_cast<const float4*>(a.bias + n);
+                const float4 b = *reinterpret_cast<const float4*>(wbias + 16 * j + 4 * fq);
                 const f32x4 v = acc[i][j];
                 const float al = n < a.alpha_ncols ? a.alpha : 1.0f;
                 const float o0 = al * v[0] + b.x, o1 = al * v[1] + b.y, o2 = al * v[2] + b.z, o3 = al * v[3] + b.w;

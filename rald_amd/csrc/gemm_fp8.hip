@@ -162,14 +162,15 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx8_kernel(Mx8Args a) {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();             // staging buffers become the epilogue patches
     asm volatile("" ::: "memory");
-    gemm_epilogue_lds<MT, NT, EPI>(acc, g, m0 + wm * (BM / WM), n0 + wn * (BN / WN), coff, lane, smem + wave * 8704);
+    gemm_epilogue_lds<MT, NT, EPI>(acc, g, m0 + wm * (BM / WM), n0 + wn * (BN / WN), coff, lane, smem + wave * EPI_PATCH_BYTES,
+                                   reinterpret_cast<float*>(smem + WAVES * EPI_PATCH_BYTES) + wave * NT * 16);
 }
 
 template <int BM, int BN, int WM, int WN, int EPI>
 static int launch_mx8_epi(const Mx8Args& a, hipStream_t st) {
     constexpr int WAVES = WM * WN;
     constexpr int smem = 2 * (BM + BN) * 128;
-    static_assert(smem >= WAVES * 8704, "epilogue patches must fit in the staging buffers");
+    static_assert(smem >= epi_lds_bytes<BN / (16 * WN)>(WAVES), "epilogue patches and bias slots must fit in the staging buffers");
     static bool attr_set = false;
     auto kern = gemm_mx8_kernel<BM, BN, WM, WN, EPI>;
     if (!attr_set && smem > 64 * 1024) {

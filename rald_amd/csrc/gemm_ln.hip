@@ -10,6 +10,7 @@
 //
 // Tile BM x 512 x 64, 8 waves as WM x WN, LDS-DMA staged double buffer (same engine as
 // gemm_nt_glds_kernel; at BM = 128 the two stages take exactly the CU's 160 KiB).  Epilogue:
+//   0. (group-uniform form) bias, g, b of the 512 columns -> LDS, once per workgroup, before any store;
 //   1. v = acc + bias + x_old in the accumulator layout (lane: 4 columns of 16 rows per m-tile);
 //   2. per-row sum / sum-of-squares: 32 in-lane values, 2 cross-lane steps, then across the WN waves
 //      through a 4 KiB LDS table and ONE workgroup barrier (single-pass variance in fp32: 512 terms);
@@ -27,7 +28,13 @@ typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
 // ---- epilogue shared by the main-loop forms: acc (+ x_old already inside unless XEPI) -> x_new, h ---------------------------------
-template <int BM, int WM, int WN, bool XEPI>
+// GU (group-uniform, chosen on the host): all BM rows of a tile share one modulation row (gstride == 0 or rows_per_group % BM == 0).
+// bias, g and b of the tile's 512 columns are then fetched ONCE per workgroup, before any store, into 6 KiB of LDS behind `red`
+// and read from there in both phases.  The per-row form (GU = false) is for tiles that straddle modulation groups: every
+// m-tile of phase 2 loads its 16 g / b vectors behind the x_new stores it has just issued, and - vmcnt being one in-order counter for loads and stores on gfx950 - waits for
+// those stores and the previous m-tile's h stores to be acknowledged before it can compute (gemm_epilogue.h states the rule).
+// DEAD: every wave's last read of the staging buffers already lies behind a barrier (the pipelined main loop).
+template <int BM, int WM, int WN, bool XEPI, bool GU, bool DEAD>
 __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&acc)[BM / (16 * WM)][512 / (16 * WN)], unsigned char* smem, int m0) {
     constexpr int BN = 512;
     constexpr int WAVES = WM * WN;
@@ -37,6 +44,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
     constexpr int PATCH = 16 * STRIDE_F;
     constexpr int RED_OFF = WAVES * PATCH;                            // float2 red[BM][WN]
+    constexpr int VEC_OFF = RED_OFF + BM * WN * 8;                    // GU: float vec[3][512] = bias | g | b
     (void)ROWB_H;
     typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x;
@@ -45,6 +53,24 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     const int wm = wave / WN, wn = wave % WN;
     const int fr = lane & 15, fq = lane >> 4;
     const bool nt_io = (a.nt_io & 1) != 0;
+    const float* vec = reinterpret_cast<const float*>(smem + VEC_OFF);
+    if constexpr (GU) {
+        static_assert(WAVES * 64 >= 3 * BN / 4, "one float4 per thread covers bias, g and b");
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int which = tid / (BN / 4), col = (tid % (BN / 4)) * 4;          // uniform per wave: 0 bias, 1 g, 2 b
+        if (which < 3) {
+            const int64_t goff = (int64_t)(m0 / a.rows_per_group) * a.gstride;
+            const float* src = which == 0 ? a.bias : (which == 1 ? a.g : a.b) + goff;
+            t = *reinterpret_cast<const float4*>(src + col);
+        }
+        if constexpr (!DEAD) {
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_barrier();         // staging buffers are dead: reuse them (vec, then patches + red)
+            asm volatile("" ::: "memory");
+        }
+        if (which < 3) *reinterpret_cast<float4*>(smem + VEC_OFF + (which * BN + col) * 4) = t;
+        __syncthreads();
+    }
     // ---- 1. v = acc + bias + x_old (accumulator layout), row partial sums -------------------------
     const int mb = m0 + wm * (BM / WM);
     const int nb = wn * (BN / WN);
@@ -57,7 +83,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int n = nb + j * 16 + 4 * fq;
-            const float4 b = *reinterpret_cast<const float4*>(a.bias + n);
+            const float4 b = GU ? *reinterpret_cast<const float4*>(vec + n) : *reinterpret_cast<const float4*>(a.bias + n);
             // (bf16 operands: x_old is already in the accumulators, see the main loop)
             float4 xo = make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (XEPI) {
@@ -75,9 +101,11 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
         s1[i] += __shfl_xor(s1[i], 32, 64); s2[i] += __shfl_xor(s2[i], 32, 64);
         asm volatile("" ::: "memory");            // keep only one m-tile's x_old loads in flight (register pressure)
     }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();                 // staging buffers are dead: reuse them (patches + red)
-    asm volatile("" ::: "memory");
+    if constexpr (!GU) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();             // staging buffers are dead: reuse them (patches + red)
+        asm volatile("" ::: "memory");
+    }
     float2* red = reinterpret_cast<float2*>(smem + RED_OFF);
     if (fq == 0) {
 #pragma unroll
@@ -127,8 +155,8 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int n = nb + j * 16 + 4 * fq;
-            const float4 gg = *reinterpret_cast<const float4*>(a.g + goff + n);
-            const float4 bb = *reinterpret_cast<const float4*>(a.b + goff + n);
+            const float4 gg = GU ? *reinterpret_cast<const float4*>(vec + BN + n) : *reinterpret_cast<const float4*>(a.g + goff + n);
+            const float4 bb = GU ? *reinterpret_cast<const float4*>(vec + 2 * BN + n) : *reinterpret_cast<const float4*>(a.b + goff + n);
             const f32x4 v = acc[i][j];
             *reinterpret_cast<bf16x4*>(patch + fr * STRIDE_H + (16 * j + 4 * fq) * 2) =
                 pack4((v[0] - mean[i]) * rstd[i] * (a.add_one + gg.x) + bb.x, (v[1] - mean[i]) * rstd[i] * (a.add_one + gg.y) + bb.y,
@@ -168,7 +196,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
 }
 
 // LDS rows of 128 bytes (64 bf16 or 128 e4m3 of one k-step), 8 chunks of 16 bytes, chunk ^ (row & 7).
-template <int BM, int WM, int WN, bool MX>
+template <int BM, int WM, int WN, bool MX, bool GU>
 __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     constexpr int BN = 512, NSTAGE = 2, BK = 64;
     constexpr int WAVES = WM * WN;
@@ -186,7 +214,7 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
     constexpr int PATCH = 16 * STRIDE_F;
     constexpr int RED_OFF = WAVES * PATCH;                            // float2 red[BM][WN]
-    static_assert(RED_OFF + BM * WN * 8 <= NSTAGE * STAGE_BYTES, "epilogue scratch must fit in the staging buffers");
+    static_assert(RED_OFF + BM * WN * 8 + 3 * BN * 4 <= NSTAGE * STAGE_BYTES, "epilogue scratch (patches, red, bias | g | b) must fit in the staging buffers");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -521,17 +549,17 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
 
     }
     constexpr bool PIPE = !MX && MT == 4 && NT == 8 && CA + CB == 10;     // the pipelined loop adds x_old in the epilogue
-    resid_ln_epilogue<BM, WM, WN, (MX || PIPE)>(a, acc, smem, m0);
+    resid_ln_epilogue<BM, WM, WN, (MX || PIPE), GU, PIPE>(a, acc, smem, m0);
 }
 
-template <int BM, int WM, int WN, bool MX>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_resid_ln_kernel(GemmLnArgs a) { gemm_resid_ln_body<BM, WM, WN, MX>(a); }
+template <int BM, int WM, int WN, bool MX, bool GU>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_resid_ln_kernel(GemmLnArgs a) { gemm_resid_ln_body<BM, WM, WN, MX, GU>(a); }
 
-template <int BM, int WM, int WN, bool MX>
-static int launch_ln(const GemmLnArgs& a, hipStream_t st) {
+template <int BM, int WM, int WN, bool MX, bool GU>
+static int launch_ln_gu(const GemmLnArgs& a, hipStream_t st) {
     constexpr int smem = 2 * (BM + 512) * 64 * 2;
     static bool attr_set = false;
-    auto kern = gemm_resid_ln_kernel<BM, WM, WN, MX>;
+    auto kern = gemm_resid_ln_kernel<BM, WM, WN, MX, GU>;
     if (!attr_set) {
         RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_set = true;
@@ -539,6 +567,13 @@ static int launch_ln(const GemmLnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(cdiv(a.M, BM)), dim3(WM * WN * 64), smem, st, a);
     RALD_HIP(hipGetLastError());
     return 0;
+}
+
+// group-uniform form when a tile's BM rows all share one modulation row (the denoiser: 512 rows per sample; the AE stack: gstride 0)
+template <int BM, int WM, int WN, bool MX>
+static int launch_ln(const GemmLnArgs& a, hipStream_t st) {
+    if (a.gstride == 0 || a.rows_per_group % BM == 0) return launch_ln_gu<BM, WM, WN, MX, true>(a, st);
+    return launch_ln_gu<BM, WM, WN, MX, false>(a, st);
 }
 
 int gemm_resid_ln(const GemmLnArgs& a, hipStream_t st) {
