@@ -27,9 +27,6 @@
 
 namespace rald {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 constexpr float ATTN_LAZY = 8.f;   // how far (exp2 units) scores may pass the reference max before it moves: p <= 2^8

@@ -24,9 +24,6 @@
 
 namespace rald {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 namespace {
 constexpr int TB = 64 * 128;                                   // one staged tile
 

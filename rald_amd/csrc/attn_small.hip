@@ -28,9 +28,6 @@
 
 namespace rald {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 // ---- LDS images -------------------------------------------------------------------------------------------------------
 // "line image": rows of 128 bytes (64 bf16), 16-byte chunk c of row n stored at chunk c ^ ((n >> 1) & 7): conflict-free for
 // ds_read_b128 fragment reads of 16 consecutive rows at one column (two rows share a 256-byte bank row) - attention.hip.

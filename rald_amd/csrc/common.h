@@ -13,6 +13,9 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;     // 16x16 MFMA accumulator
 typedef __attribute__((ext_vector_type(16))) float f32x16;   // 32x32 MFMA accumulator
 
+typedef __attribute__((address_space(3))) void lds_void;          // the operand types of __builtin_amdgcn_global_load_lds (LDS-DMA)
+typedef const __attribute__((address_space(1))) void glb_void;
+
 constexpr int WAVE = 64;
 
 // ---- error plumbing: C-ABI functions return int status + rald_last_error() ------------
@@ -37,6 +40,21 @@ void set_error(const std::string& msg);
         int _rc = (expr);                                                           \
         if (_rc) return _rc;                                                        \
     } while (0)
+
+#ifdef __HIPCC__
+// Launch of a kernel that takes `smem` bytes of dynamic LDS: above the 64-KiB default the kernel's limit is raised first, once per kernel
+// (`raised` is the caller's static flag for this kernel).
+template <typename Args>
+static int launch_dyn_lds(void (*kern)(Args), bool& raised, dim3 grid, int threads, int smem, hipStream_t st, const Args& a) {
+    if (!raised && smem > 64 * 1024) {
+        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        raised = true;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(threads), smem, st, a);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+#endif
 
 // ---- device helpers --------------------------------------------------------------------
 // Wave-wide reductions on DPP (data-parallel primitives: a VALU operand read through a fixed lane permutation) instead of __shfl_xor, which

@@ -6,7 +6,8 @@
 //
 // Two staging engines share one tile/epilogue design (BM x BN x 64, waves in a 2 x (WAVES/2) grid,
 // 16x16 MFMA tiles, LDS rows of 128 B whose 16-byte chunks are XOR-swizzled by (row & 7) so every
-// ds_read_b128 lane group is bank-conflict free):
+// ds_read_b128 lane group is bank-conflict free; the swizzled read, the LDS-DMA staging and the tile
+// walk are gemm_tile.h's, shared with the MXFP8 and residual+LayerNorm GEMMs):
 //   * gemm_nt_kernel      register staging: global_load_dwordx4 -> VGPR -> ds_write_b128.  At 2
 //                         workgroups/CU the ds_write path (~79 B/clk/CU) makes this LDS-bound.
 //   * gemm_nt_glds_kernel LDS-DMA staging: global_load_lds_dwordx4 writes the tile straight into
@@ -30,6 +31,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace rald {
 
@@ -139,12 +141,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
             int r = srow + 32 * p;
-            sA[(buf * BM + r) * 8 + (schunk ^ (r & 7))] = rA[p];
+            sA[(buf * BM + r) * 8 + RALD_SWZ(r, schunk)] = rA[p];
         }
 #pragma unroll
         for (int p = 0; p < PB; ++p) {
             int r = srow + 32 * p;
-            sB[(buf * BN + r) * 8 + (schunk ^ (r & 7))] = rB[p];
+            sB[(buf * BN + r) * 8 + RALD_SWZ(r, schunk)] = rB[p];
         }
     };
 
@@ -169,12 +171,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 int r = wm * (BM / 2) + i * 16 + fr;
-                fa[i] = sA[(buf * BM + r) * 8 + (chunk ^ (r & 7))];
+                fa[i] = sA[(buf * BM + r) * 8 + RALD_SWZ(r, chunk)];
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 int r = wn * (BN / 2) + j * 16 + fr;
-                fb[j] = sB[(buf * BN + r) * 8 + (chunk ^ (r & 7))];
+                fb[j] = sB[(buf * BN + r) * 8 + RALD_SWZ(r, chunk)];
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -191,9 +193,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 // =================================================================================================
 // LDS-DMA engine: WM x WN waves; NSTAGE LDS buffers
 // =================================================================================================
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 template <int BM, int BN, int WM, int WN, int NSTAGE, int EPI>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) {
     constexpr int BK = 64;
@@ -209,27 +208,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    // XCD-aware tile order (speed only): workgroups are dealt round-robin over the 8 XCDs, so the
-    // blocks with equal id%8 share an L2.  Give each of those 8 groups a CONTIGUOUS span of the tile
-    // walk (bijective for any grid size, guide 5 q/r form), and walk the tiles in column STRIPS of
-    // GN n-tiles (n fastest inside a strip, then m, then the next strip): the 32 tiles an XCD runs at
-    // once then share <= GN weight panels (2 MB at GN = 8, 256-row tiles, K = 512) that stay in its
-    // 4 MB L2 while the A panels stream through.  Row-major order re-fetched the whole 4 MB FF1
-    // weight matrix for every round of tiles (measured: 296 MB fetched vs 37.5 MB algorithmic).
-    const int ntn = gridDim.x, ntm = gridDim.y, nt = ntn * ntm;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xcd = lin & 7, q = nt >> 3, rr = nt & 7;
-    const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (lin >> 3);
-    constexpr int GN = 8;
     int tm, tn;
-    if (ntn % GN == 0) {
-        const int strip = tile / (ntm * GN), within = tile % (ntm * GN);
-        tm = within / GN;
-        tn = strip * GN + within % GN;
-    } else {
-        tm = tile / ntn;
-        tn = tile % ntn;
-    }
+    xcd_strip_tile(tm, tn);
+    const int ntn = gridDim.x, nt = ntn * gridDim.y;
     int bz = blockIdx.z;
     if (nt < 8 && (gridDim.z & 7) == 0) {
         // batched problems of a few tiles each (the folded cross-attention: 2 x 2 tiles per sample, per-sample B operand): in launch order
@@ -243,45 +224,17 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
         tn = tl % ntn;
     }
     const int m0 = tm * BM, n0 = tn * BN;
-    // k-steps run in ascending order from 0 in every tile, so a sample's sums do not depend on its tile or batch size (a per-tile
-    // rotated start was measured and not shipped: DESIGN §5).  The no-op koff / wrap stays: removing it changes the compiled code.
-    const int nk_ = a.K / BK;
-    const int koff = 0;
     int64_t oa, ob, coff;
     gemm_batch_offsets(a, bz, oa, ob, coff);
     const bf16* A = a.A + oa;
     const bf16* B = a.B + ob;
 
-    // DMA source addresses.  Piece p of this wave covers tile rows 8*(wave + WAVES*p) .. +7; lane l
-    // lands in LDS at piece_base + 16*l = (row r = l>>3, physical chunk l&7), which must hold the
-    // LOGICAL chunk (l&7) ^ (r&7): the XOR goes on the source address, the destination stays linear.
-    const int lr = lane >> 3;
-    const int lc = (lane & 7) ^ lr;
+    const int nk = a.K / BK;
     const bf16* gA[CA];
     const bf16* gB[CB];
-#pragma unroll
-    for (int p = 0; p < CA; ++p) {
-        int r = m0 + 8 * (wave + WAVES * p) + lr;
-        r = r < a.M ? r : a.M - 1;
-        gA[p] = A + (int64_t)r * a.lda + lc * 8;
-    }
-#pragma unroll
-    for (int p = 0; p < CB; ++p) {
-        int r = n0 + 8 * (wave + WAVES * p) + lr;
-        r = r < a.N ? r : a.N - 1;
-        gB[p] = B + (int64_t)r * a.ldb + lc * 8;
-    }
-    auto stage = [&](int kt, int buf) {
-        unsigned char* base = smem + buf * STAGE_BYTES;
-        int ks = kt + koff;
-        ks = ks >= nk_ ? ks - nk_ : ks;
-#pragma unroll
-        for (int p = 0; p < CA; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + ks * BK), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int p = 0; p < CB; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(gB[p] + ks * BK), (lds_void*)(base + BM * 128 + (wave + WAVES * p) * 1024), 16, 0, 0);
-    };
+    dma_sources<WAVES>(gA, A, a.lda, m0, a.M, wave, lane);
+    dma_sources<WAVES>(gB, B, a.ldb, n0, a.N, wave, lane);
+    auto stage = [&](int kt, int buf) { dma_stage<BM, WAVES>(gA, gB, kt, nk, smem + buf * STAGE_BYTES, wave); };
 
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -289,7 +242,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = a.K / BK;
     const int fr = lane & 15, fq = lane >> 4;
     // fragment reads of one 32-deep k sub-step (kk) of the tile in LDS buffer `buf`
     auto read_frags = [&](int buf, int kk, bf16x8 (&fa)[MT], bf16x8 (&fb)[NT]) {
@@ -299,12 +251,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int r = wm * (BM / WM) + i * 16 + fr;
-            fa[i] = sA[r * 8 + (chunk ^ (r & 7))];
+            fa[i] = sA[r * 8 + RALD_SWZ(r, chunk)];
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int r = wn * (BN / WN) + j * 16 + fr;
-            fb[j] = sB[r * 8 + (chunk ^ (r & 7))];
+            fb[j] = sB[r * 8 + RALD_SWZ(r, chunk)];
         }
     };
     auto mfma_all = [&](const bf16x8 (&fa)[MT], const bf16x8 (&fb)[NT]) {
@@ -430,16 +382,8 @@ static int launch_glds_epi(const GemmArgs& a, hipStream_t st) {
     constexpr int WAVES = WM * WN;
     constexpr int smem = NSTAGE * (BM + BN) * 64 * 2;
     static_assert(smem >= epi_lds_bytes<BN / (16 * WN)>(WAVES), "epilogue patches and bias slots must fit in the staging buffers");
-    static bool attr_set = false;
-    auto kern = gemm_nt_glds_kernel<BM, BN, WM, WN, NSTAGE, EPI>;
-    if (!attr_set && smem > 64 * 1024) {
-        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
-    dim3 grid(cdiv(a.N, BN), cdiv(a.M, BM), a.batch * a.batch2);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), smem, st, a);
-    RALD_HIP(hipGetLastError());
-    return 0;
+    static bool raised = false;
+    return launch_dyn_lds(gemm_nt_glds_kernel<BM, BN, WM, WN, NSTAGE, EPI>, raised, dim3(cdiv(a.N, BN), cdiv(a.M, BM), a.batch * a.batch2), WAVES * 64, smem, st, a);
 }
 template <int BM, int BN, int WM, int WN, int NSTAGE>
 static int launch_glds(const GemmArgs& a, int epi, hipStream_t st) {

@@ -9,155 +9,40 @@
 //   byte[opsel] of lane l's scale operand is the e8m0 scale of row r, K-block g (K = 32g .. 32g+31);
 //   C/D as every 16x16 MFMA: col = l & 15, row = 4*(l >> 4) + reg.
 //
-// Same engine as gemm_nt_glds_kernel (gemm.hip): a k-step is 128 BYTES per row in both, so the LDS-DMA
-// staging, the XOR swizzle, the XCD-aware strip walk and the LDS-staged epilogue are byte-for-byte the
-// same; only the fragment reads (chunks g and g+4) and the MFMA differ.  Scales are one byte per lane
-// per tile row per k-step, fetched a k-step ahead with plain byte loads (they stay in L2).
+// The engine is gemm_tile.h's, shared with gemm_nt_glds_kernel (gemm.hip): a k-step is 128 BYTES per row in both, so the LDS-DMA
+// staging, the XOR swizzle and the XCD-aware strip walk are the same code and the LDS-staged epilogue is gemm_epilogue.h's; only the
+// fragment reads (chunks g and g+4) and the MFMA differ (Mx8Loop).
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 #include "mx8.h"
 
 namespace rald {
-
-typedef __attribute__((address_space(3))) void lds_void8;
-typedef const __attribute__((address_space(1))) void glb_void8;
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 template <int BM, int BN, int WM, int WN, int EPI>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_mx8_kernel(Mx8Args a) {
     constexpr int WAVES = WM * WN;
     constexpr int MT = BM / (16 * WM);
     constexpr int NT = BN / (16 * WN);
-    constexpr int CA = BM / 8 / WAVES;       // 1-KiB DMA pieces (8 rows x 128 B) per wave
-    constexpr int CB = BN / 8 / WAVES;
-    constexpr int STAGE_BYTES = (BM + BN) * 128;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][A tile | B tile]
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    // XCD-aware strip walk: see gemm_nt_glds_kernel
-    const int ntn = gridDim.x, ntm = gridDim.y, nt = ntn * ntm;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xcd = lin & 7, q = nt >> 3, rr = nt & 7;
-    const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (lin >> 3);
-    constexpr int GN = 8;
     int tm, tn;
-    if (ntn % GN == 0) {
-        const int strip = tile / (ntm * GN), within = tile % (ntm * GN);
-        tm = within / GN;
-        tn = strip * GN + within % GN;
-    } else {
-        tm = tile / ntn;
-        tn = tile % ntn;
-    }
+    xcd_strip_tile(tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int bz = blockIdx.z;                // (the MXFP8 engine has no inner batch: batch2 = 1)
     const GemmArgs& g = a.g;
     const int64_t coff = (int64_t)bz * g.strideC;
-    const unsigned char* A = a.A8 + (int64_t)bz * g.strideA;
-    const unsigned char* B = a.B8 + (int64_t)bz * g.strideB;
-    const unsigned char* SA = a.SA + (int64_t)bz * a.strideSA;
-    const unsigned char* SB = a.SB + (int64_t)bz * a.strideSB;
-    const int kb = g.K / 32;                 // scale bytes per row
-
-    const int lr = lane >> 3;
-    const int lc = (lane & 7) ^ lr;
-    const unsigned char* gA[CA];
-    const unsigned char* gB[CB];
-#pragma unroll
-    for (int p = 0; p < CA; ++p) {
-        int r = m0 + 8 * (wave + WAVES * p) + lr;
-        r = r < g.M ? r : g.M - 1;
-        gA[p] = A + (int64_t)r * g.lda + lc * 16;
-    }
-#pragma unroll
-    for (int p = 0; p < CB; ++p) {
-        int r = n0 + 8 * (wave + WAVES * p) + lr;
-        r = r < g.N ? r : g.N - 1;
-        gB[p] = B + (int64_t)r * g.ldb + lc * 16;
-    }
-    auto stage = [&](int kt, int buf) {
-        unsigned char* base = smem + buf * STAGE_BYTES;
-#pragma unroll
-        for (int p = 0; p < CA; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void8*)(gA[p] + kt * 128), (lds_void8*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int p = 0; p < CB; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void8*)(gB[p] + kt * 128), (lds_void8*)(base + BM * 128 + (wave + WAVES * p) * 1024), 16, 0, 0);
-    };
-
-    const int fr = lane & 15, fq = lane >> 4;
-    // scale byte of this lane's (tile row, K-block fq) for k-step kt: S[row * kb + kt * 4 + fq]
-    int offA[MT], offB[NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        int r = m0 + wm * (BM / WM) + i * 16 + fr;
-        r = r < g.M ? r : g.M - 1;
-        offA[i] = r * kb + fq;
-    }
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        int r = n0 + wn * (BN / WN) + j * 16 + fr;
-        r = r < g.N ? r : g.N - 1;
-        offB[j] = r * kb + fq;
-    }
-    int sa_next[MT], sb_next[NT];
-    auto load_scales = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) sa_next[i] = SA[offA[i] + kt * 4];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) sb_next[j] = SB[offB[j] + kt * 4];
-    };
-
     f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = g.K / 128;
-    auto read_frag = [&](const unsigned char* tile_base, int row) -> i32x8 {
-        const i32x4* s = reinterpret_cast<const i32x4*>(tile_base) + row * 8;
-        const i32x4 lo = s[fq ^ (row & 7)], hi = s[(fq + 4) ^ (row & 7)];
-        return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
-
-    stage(0, 0);
-    load_scales(0);
-    for (int kt = 0; kt < nk; ++kt) {
+    Mx8Loop<BM, BN, WM, WN> L;
+    L.begin(acc, a.A8 + (int64_t)bz * g.strideA, g.lda, a.SA + (int64_t)bz * a.strideSA, m0, g.M,
+            a.B8 + (int64_t)bz * g.strideB, g.ldb, a.SB + (int64_t)bz * a.strideSB, n0, g.N, g.K, smem, wave, lane);
+    for (int kt = 0; kt < L.nk; ++kt) {
         const int cur = kt & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile kt and its scales have landed
-        __builtin_amdgcn_s_barrier();                          // ... for every wave; buffer cur^1 is free
-        asm volatile("" ::: "memory");
-        int sa[MT], sb[NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) sa[i] = sa_next[i];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) sb[j] = sb_next[j];
-        if (kt + 1 < nk) {
-            stage(kt + 1, cur ^ 1);
-            load_scales(kt + 1);
-        }
-        const unsigned char* tA = smem + cur * STAGE_BYTES;
-        const unsigned char* tB = tA + BM * 128;
-        i32x8 fa[MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fa[i] = read_frag(tA, wm * (BM / WM) + i * 16 + fr);
-        // weight fragments one n-tile ahead of the MFMAs that consume them (an LDS round trip per n-tile otherwise)
-        i32x8 fb = read_frag(tB, wn * (BN / WN) + fr);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            i32x8 fb_next = fb;
-            if (j + 1 < NT) fb_next = read_frag(tB, wn * (BN / WN) + (j + 1) * 16 + fr);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa[i], acc[i][j], 0, 0, 0, sb[j], 0, sa[i]);
-            fb = fb_next;
-        }
+        L.step(acc, kt, cur, cur ^ 1, smem, wave, lane);
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();             // staging buffers become the epilogue patches
@@ -171,16 +56,8 @@ static int launch_mx8_epi(const Mx8Args& a, hipStream_t st) {
     constexpr int WAVES = WM * WN;
     constexpr int smem = 2 * (BM + BN) * 128;
     static_assert(smem >= epi_lds_bytes<BN / (16 * WN)>(WAVES), "epilogue patches and bias slots must fit in the staging buffers");
-    static bool attr_set = false;
-    auto kern = gemm_mx8_kernel<BM, BN, WM, WN, EPI>;
-    if (!attr_set && smem > 64 * 1024) {
-        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
-    dim3 grid(cdiv(a.g.N, BN), cdiv(a.g.M, BM), a.g.batch);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), smem, st, a);
-    RALD_HIP(hipGetLastError());
-    return 0;
+    static bool raised = false;
+    return launch_dyn_lds(gemm_mx8_kernel<BM, BN, WM, WN, EPI>, raised, dim3(cdiv(a.g.N, BN), cdiv(a.g.M, BM), a.g.batch), WAVES * 64, smem, st, a);
 }
 template <int BM, int BN, int WM, int WN>
 static int launch_mx8(const Mx8Args& a, int epi, hipStream_t st) {

@@ -8,8 +8,8 @@
 // LayerNorm is a separate HBM-bound pass that re-reads the 4-byte stream; fused, x is read once
 // and written once per sub-block and three launches per transformer block disappear.
 //
-// Tile BM x 512 x 64, 8 waves as WM x WN, LDS-DMA staged double buffer (same engine as
-// gemm_nt_glds_kernel; at BM = 128 the two stages take exactly the CU's 160 KiB).  Epilogue:
+// Tile BM x 512 x 64, 8 waves as WM x WN, LDS-DMA staged double buffer (the engine of gemm_tile.h, as in
+// gemm_nt_glds_kernel and gemm_mx8_kernel; at BM = 128 the two stages take exactly the CU's 160 KiB).  Epilogue:
 //   0. (group-uniform form) bias, g, b of the 512 columns -> LDS, once per workgroup, before any store;
 //   1. v = acc + bias + x_old in the accumulator layout (lane: 4 columns of 16 rows per m-tile);
 //   2. per-row sum / sum-of-squares: 32 in-lane values, 2 cross-lane steps, then across the WN waves
@@ -17,15 +17,32 @@
 //   3. x_new and h leave through the wave-private LDS transpose as whole rows (16 B per lane).
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "kernels.h"
+#include "gemm_tile.h"
 #include "mx8.h"
 
 namespace rald {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
+// LDS layout of the epilogue (it reuses the staging buffers): per-wave transpose patches of 16 rows, the row-sum table, then bias | g | b
+template <int BM, int WM, int WN>
+struct LnEpiLds {
+    static constexpr int NT = 512 / (16 * WN);
+    static constexpr int ROWB_F = NT * 16 * 4, STRIDE_F = ROWB_F + 16;      // fp32 patch row (x_new)
+    static constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
+    static constexpr int PATCH = 16 * STRIDE_F;
+    static constexpr int RED_OFF = WM * WN * PATCH;                         // float2 red[BM][WN]
+    static constexpr int VEC_OFF = RED_OFF + BM * WN * 8;                   // GU: float vec[3][512] = bias | g | b
+    static constexpr int BYTES = VEC_OFF + 3 * 512 * 4;
+};
+
+// the calls f(0), ..., f(N - 1) with the index as a compile-time constant
+template <int... Q, typename F>
+__device__ __forceinline__ void unrolled(std::integer_sequence<int, Q...>, F&& f) { (f(std::integral_constant<int, Q>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void unrolled(F&& f) { unrolled(std::make_integer_sequence<int, N>{}, f); }
 
 // ---- epilogue shared by the main-loop forms: acc (+ x_old already inside unless XEPI) -> x_new, h ---------------------------------
 // GU (group-uniform, chosen on the host): all BM rows of a tile share one modulation row (gstride == 0 or rows_per_group % BM == 0).
@@ -40,12 +57,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     constexpr int WAVES = WM * WN;
     constexpr int MT = BM / (16 * WM);
     constexpr int NT = BN / (16 * WN);
-    constexpr int ROWB_F = NT * 16 * 4, STRIDE_F = ROWB_F + 16;      // fp32 patch row (x_new)
-    constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
-    constexpr int PATCH = 16 * STRIDE_F;
-    constexpr int RED_OFF = WAVES * PATCH;                            // float2 red[BM][WN]
-    constexpr int VEC_OFF = RED_OFF + BM * WN * 8;                    // GU: float vec[3][512] = bias | g | b
-    (void)ROWB_H;
+    using L = LnEpiLds<BM, WM, WN>;
     typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -53,7 +65,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     const int wm = wave / WN, wn = wave % WN;
     const int fr = lane & 15, fq = lane >> 4;
     const bool nt_io = (a.nt_io & 1) != 0;
-    const float* vec = reinterpret_cast<const float*>(smem + VEC_OFF);
+    const float* vec = reinterpret_cast<const float*>(smem + L::VEC_OFF);
     if constexpr (GU) {
         static_assert(WAVES * 64 >= 3 * BN / 4, "one float4 per thread covers bias, g and b");
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -68,7 +80,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
             __builtin_amdgcn_s_barrier();         // staging buffers are dead: reuse them (vec, then patches + red)
             asm volatile("" ::: "memory");
         }
-        if (which < 3) *reinterpret_cast<float4*>(smem + VEC_OFF + (which * BN + col) * 4) = t;
+        if (which < 3) *reinterpret_cast<float4*>(smem + L::VEC_OFF + (which * BN + col) * 4) = t;
         __syncthreads();
     }
     // ---- 1. v = acc + bias + x_old (accumulator layout), row partial sums -------------------------
@@ -106,7 +118,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
         __builtin_amdgcn_s_barrier();             // staging buffers are dead: reuse them (patches + red)
         asm volatile("" ::: "memory");
     }
-    float2* red = reinterpret_cast<float2*>(smem + RED_OFF);
+    float2* red = reinterpret_cast<float2*>(smem + L::RED_OFF);
     if (fq == 0) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) red[(wm * (BM / WM) + i * 16 + fr) * WN + wn] = make_float2(s1[i], s2[i]);
@@ -127,20 +139,20 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     }
 
     // ---- 2. x_new (fp32) and h (bf16) out as whole rows through the wave-private patch -------------
-    unsigned char* patch = smem + wave * PATCH;
+    unsigned char* patch = smem + wave * L::PATCH;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         // x_new
 #pragma unroll
         for (int j = 0; j < NT; ++j)
-            *reinterpret_cast<float4*>(patch + fr * STRIDE_F + (16 * j + 4 * fq) * 4) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+            *reinterpret_cast<float4*>(patch + fr * L::STRIDE_F + (16 * j + 4 * fq) * 4) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
         {
-            constexpr int LPR = ROWB_F / 16, RPI = 64 / LPR;
+            constexpr int LPR = L::ROWB_F / 16, RPI = 64 / LPR;
 #pragma unroll
             for (int r0 = 0; r0 < 16; r0 += RPI) {
                 const int r = r0 + lane / LPR, pc = lane % LPR;
                 const int m = mb + i * 16 + r;
-                const uint4 v = *reinterpret_cast<const uint4*>(patch + r * STRIDE_F + pc * 16);
+                const uint4 v = *reinterpret_cast<const uint4*>(patch + r * L::STRIDE_F + pc * 16);
                 if (m < a.M) {
                     typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
                     if (nt_io) __builtin_nontemporal_store(nt_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_u32x4*>(a.x + (int64_t)m * BN + nb + pc * 4));
@@ -158,17 +170,17 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
             const float4 gg = GU ? *reinterpret_cast<const float4*>(vec + BN + n) : *reinterpret_cast<const float4*>(a.g + goff + n);
             const float4 bb = GU ? *reinterpret_cast<const float4*>(vec + 2 * BN + n) : *reinterpret_cast<const float4*>(a.b + goff + n);
             const f32x4 v = acc[i][j];
-            *reinterpret_cast<bf16x4*>(patch + fr * STRIDE_H + (16 * j + 4 * fq) * 2) =
+            *reinterpret_cast<bf16x4*>(patch + fr * L::STRIDE_H + (16 * j + 4 * fq) * 2) =
                 pack4((v[0] - mean[i]) * rstd[i] * (a.add_one + gg.x) + bb.x, (v[1] - mean[i]) * rstd[i] * (a.add_one + gg.y) + bb.y,
                       (v[2] - mean[i]) * rstd[i] * (a.add_one + gg.z) + bb.z, (v[3] - mean[i]) * rstd[i] * (a.add_one + gg.w) + bb.w);
         }
         {
-            constexpr int LPR = ROWB_H / 16, RPI = 64 / LPR;
+            constexpr int LPR = L::ROWB_H / 16, RPI = 64 / LPR;
 #pragma unroll
             for (int r0 = 0; r0 < 16; r0 += RPI) {
                 const int r = r0 + lane / LPR, pc = lane % LPR;
                 const int mm = mb + i * 16 + r;
-                const uint4 v = *reinterpret_cast<const uint4*>(patch + r * STRIDE_H + pc * 16);
+                const uint4 v = *reinterpret_cast<const uint4*>(patch + r * L::STRIDE_H + pc * 16);
                 if (a.h8) {
                     // MXFP8 output: this lane's 16-byte piece is 8 consecutive columns, 4 consecutive lanes = one 32-column
                     // block (nb and the pieces are 32-column aligned); every lane of the wave takes part in the shuffles
@@ -195,7 +207,7 @@ __device__ __forceinline__ void resid_ln_epilogue(const GemmLnArgs& a, f32x4 (&a
     }
 }
 
-// LDS rows of 128 bytes (64 bf16 or 128 e4m3 of one k-step), 8 chunks of 16 bytes, chunk ^ (row & 7).
+// Staging, swizzle and the MXFP8 loop body are gemm_tile.h's; the pipelined 128-row bf16 loop keeps its own scalar-base DMA addressing.
 template <int BM, int WM, int WN, bool MX, bool GU>
 __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     constexpr int BN = 512, NSTAGE = 2, BK = 64;
@@ -203,18 +215,12 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
     constexpr int MT = BM / (16 * WM);
     constexpr int NT = BN / (16 * WN);
     constexpr int ROWB = 128;                                    // bytes per LDS row
-    constexpr int CPR = ROWB / 16;                               // 16-byte chunks per row
     constexpr int RPP = 1024 / ROWB;                             // rows per DMA piece (one wave instruction = 1 KiB)
-    constexpr int PA = BM / RPP, PB = BN / RPP;                  // pieces per stage
-    constexpr int CA = PA / WAVES;
-    constexpr int CB = PB / WAVES;
-    static_assert(CA >= 1 && CB >= 1 && PA % WAVES == 0 && PB % WAVES == 0 && MT >= 1 && NT >= 1, "tile/wave split");
+    constexpr int CA = BM / RPP / WAVES;                         // pieces per stage and wave
+    constexpr int CB = BN / RPP / WAVES;
+    static_assert(CA >= 1 && CB >= 1 && BM % (RPP * WAVES) == 0 && BN % (RPP * WAVES) == 0 && MT >= 1 && NT >= 1, "tile/wave split");
     constexpr int STAGE_BYTES = (BM + BN) * ROWB;
-    constexpr int ROWB_F = NT * 16 * 4, STRIDE_F = ROWB_F + 16;      // fp32 patch row (x_new)
-    constexpr int ROWB_H = NT * 16 * 2, STRIDE_H = ROWB_H + 16;      // bf16 patch row (h)
-    constexpr int PATCH = 16 * STRIDE_F;
-    constexpr int RED_OFF = WAVES * PATCH;                            // float2 red[BM][WN]
-    static_assert(RED_OFF + BM * WN * 8 + 3 * BN * 4 <= NSTAGE * STAGE_BYTES, "epilogue scratch (patches, red, bias | g | b) must fit in the staging buffers");
+    static_assert(LnEpiLds<BM, WM, WN>::BYTES <= NSTAGE * STAGE_BYTES, "epilogue scratch (patches, red, bias | g | b) must fit in the staging buffers");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -231,95 +237,25 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         }
     }
     const int m0 = mtile * BM;
-    const int lr = lane / CPR;                                    // row inside a DMA piece
-    const int lc = (lane & 7) ^ lr;                               // source chunk that lands in physical chunk lane % CPR
     // operand rows per k-step: 128 bytes = 64 bf16 or 128 e4m3 (MX: e4m3 + e8m0 per 32, see gemm_fp8.hip)
     constexpr int ESZ = MX ? 1 : 2;
     const unsigned char* A0 = MX ? a.A8 : reinterpret_cast<const unsigned char*>(a.A);
     const unsigned char* W0 = MX ? a.W8 : reinterpret_cast<const unsigned char*>(a.W + (int64_t)(m0 / a.w_rows) * a.strideW);
-    const unsigned char* gA[CA];
-    const unsigned char* gB[CB];
-#pragma unroll
-    for (int p = 0; p < CA; ++p) {
-        int r = m0 + RPP * (wave + WAVES * p) + lr;
-        r = r < a.M ? r : a.M - 1;
-        gA[p] = A0 + ((int64_t)r * a.lda) * ESZ + lc * 16;
-    }
-#pragma unroll
-    for (int p = 0; p < CB; ++p) gB[p] = W0 + ((int64_t)(RPP * (wave + WAVES * p) + lr) * a.ldw) * ESZ + lc * 16;
-    auto stage = [&](int kt, int buf) {
-        unsigned char* base = smem + buf * STAGE_BYTES;
-#pragma unroll
-        for (int p = 0; p < CA; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + kt * ROWB), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int p = 0; p < CB; ++p)
-            __builtin_amdgcn_global_load_lds((glb_void*)(gB[p] + kt * ROWB), (lds_void*)(base + BM * ROWB + (wave + WAVES * p) * 1024), 16, 0, 0);
-    };
 
     typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
     const bool nt_io_ = (a.nt_io & 1) != 0;
     f32x4 acc[MT][NT];
+    const int nk = MX ? a.K / 128 : a.K / BK;
+    const int fr = lane & 15, fq = lane >> 4;
+    if constexpr (MX) {
+        Mx8Loop<BM, BN, WM, WN> L;
+        L.begin(acc, A0, a.lda, a.SA, m0, a.M, W0, a.ldw, a.SW, 0, BN, a.K, smem, wave, lane);
+        for (int kt = 0; kt < nk; ++kt) L.step(acc, kt, kt & 1, (kt + 1) & 1, smem, wave, lane);
+    } else {
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int nk = MX ? a.K / 128 : a.K / BK;
-    (void)lr;
-    const int fr = lane & 15, fq = lane >> 4;
-    if constexpr (MX) {
-        typedef int i32x8 __attribute__((ext_vector_type(8)));
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
-        const int kb = a.K / 32;
-        int offA[MT], offB[NT], sa_n[MT], sb_n[NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            int r = m0 + wm * (BM / WM) + i * 16 + fr;
-            r = r < a.M ? r : a.M - 1;
-            offA[i] = r * kb + fq;
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) offB[j] = (wn * (BN / WN) + j * 16 + fr) * kb + fq;
-        auto load_scales = [&](int kt) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i) sa_n[i] = a.SA[offA[i] + kt * 4];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) sb_n[j] = a.SW[offB[j] + kt * 4];
-        };
-        auto read_frag = [&](const unsigned char* tile_base, int row) -> i32x8 {
-            const i32x4* sp = reinterpret_cast<const i32x4*>(tile_base) + row * 8;
-            const i32x4 lo = sp[fq ^ (row & 7)], hi = sp[(fq + 4) ^ (row & 7)];
-            return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        };
-        stage(0, 0);
-        load_scales(0);
-        for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            int sa[MT], sb[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) sa[i] = sa_n[i];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) sb[j] = sb_n[j];
-            if (kt + 1 < nk) { stage(kt + 1, (kt + 1) & 1); load_scales(kt + 1); }
-            const unsigned char* tA = smem + (kt & 1) * STAGE_BYTES;
-            const unsigned char* tB = tA + BM * 128;
-            i32x8 fa[MT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) fa[i] = read_frag(tA, wm * (BM / WM) + i * 16 + fr);
-            i32x8 fb = read_frag(tB, wn * (BN / WN) + fr);          // one n-tile ahead of its MFMAs
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                i32x8 fb_next = fb;
-                if (j + 1 < NT) fb_next = read_frag(tB, wn * (BN / WN) + (j + 1) * 16 + fr);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa[i], acc[i][j], 0, 0, 0, sb[j], 0, sa[i]);
-                fb = fb_next;
-            }
-        }
-    } else {
     // The residual x_old rides into the accumulators DURING the main loop: k-step q < 8 loads one eighth of this wave's x
     // tile (MT*NT/8 float4 per lane) right after the next stage's DMA is issued, and k-step q+1 adds it to the accumulators.
     // With one 160-KiB workgroup per CU every CU is in the same phase at the same time, so an epilogue that first READS
@@ -359,6 +295,22 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
             acc[i][j][0] += xt[e][0]; acc[i][j][1] += xt[e][1]; acc[i][j][2] += xt[e][2]; acc[i][j][3] += xt[e][3];
         }
     };
+    const unsigned char* gA[CA];
+    const unsigned char* gB[CB];
+    dma_sources<WAVES>(gA, A0, a.lda * ESZ, m0, a.M, wave, lane);
+    dma_sources<WAVES>(gB, W0, a.ldw * ESZ, 0, BN, wave, lane);
+    // (dma_stage's issue order, written out: in the unrolled k-steps below `buf` and `kt` are constants, and through the shared helper the
+    //  LDS destinations of the ten pieces fold differently - two more scalar adds in each 800-instruction block of the 64-row form)
+    auto stage = [&](int kt, int buf) {
+        unsigned char* base = smem + buf * STAGE_BYTES;
+#pragma unroll
+        for (int p = 0; p < CA; ++p)
+            __builtin_amdgcn_global_load_lds((glb_void*)(gA[p] + kt * ROWB), (lds_void*)(base + (wave + WAVES * p) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int p = 0; p < CB; ++p)
+            __builtin_amdgcn_global_load_lds((glb_void*)(gB[p] + kt * ROWB), (lds_void*)(base + BM * ROWB + (wave + WAVES * p) * 1024), 16, 0, 0);
+    };
+    // piece q of x_old loads in k-step q and is added in k-step q + 1
     auto kstep = [&](int kt, auto QC) {
         constexpr int q = decltype(QC)::value;                        // 0..7: x piece of this k-step; 8: add the last piece; 9: none
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -368,7 +320,7 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         if constexpr (q >= 1 && q <= 8) x_add(std::integral_constant<int, q - 1>{});
         if constexpr (q <= 7) x_load(QC);
         const bf16x8* sA = reinterpret_cast<const bf16x8*>(smem + (kt & 1) * STAGE_BYTES);
-        const bf16x8* sB = sA + BM * CPR;
+        const bf16x8* sB = sA + BM * 8;
 #pragma unroll
         for (int kk = 0; kk < BK / 32; ++kk) {
             bf16x8 fa[MT], fb[NT];
@@ -376,12 +328,12 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int r = wm * (BM / WM) + i * 16 + fr;
-                fa[i] = sA[r * CPR + (chunk ^ (r & 7))];
+                fa[i] = sA[r * 8 + RALD_SWZ(r, chunk)];
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int r = wn * (BN / WN) + j * 16 + fr;
-                fb[j] = sB[r * CPR + (chunk ^ (r & 7))];
+                fb[j] = sB[r * 8 + RALD_SWZ(r, chunk)];
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -404,6 +356,8 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         // DMA sources as scalar base + 32-bit lane offset (the saddr form of global_load_lds): 3 VGPRs instead of the 20 that ten
         // 64-bit lane pointers take - the register file has 128 accumulators, 48 fragment registers and 16 of x_old to hold
         const unsigned char* sbA = A0 + (int64_t)m0 * a.lda * ESZ;                    // uniform
+        const int lr = lane >> 3;                                                     // row inside a DMA piece
+        const int lc = RALD_SWZ(lr, lane & 7);                                        // source chunk that lands in physical chunk lane & 7
         unsigned voA[CA];
 #pragma unroll
         for (int p = 0; p < CA; ++p) {
@@ -431,12 +385,12 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         auto rdA = [&](int buf, int kk, int i) -> bf16x8 {
             const bf16x8* sA = reinterpret_cast<const bf16x8*>(smem + buf * STAGE_BYTES);
             const int r = wm * (BM / WM) + i * 16 + fr;
-            return sA[r * 8 + ((kk * 4 + fq) ^ (r & 7))];
+            return sA[r * 8 + RALD_SWZ(r, kk * 4 + fq)];
         };
         auto rdB = [&](int buf, int kk, int j) -> bf16x8 {
             const bf16x8* sB = reinterpret_cast<const bf16x8*>(smem + buf * STAGE_BYTES) + BM * 8;
             const int r = wn * (BN / WN) + j * 16 + fr;
-            return sB[r * 8 + ((kk * 4 + fq) ^ (r & 7))];
+            return sB[r * 8 + RALD_SWZ(r, kk * 4 + fq)];
         };
         // One 32-deep sub-step = 32 MFMAs on the fragments in registers, with the 12 fragment reads of the NEXT sub-step (buffer nbuf,
         // half nkk) going out in place as soon as a fragment's last MFMA has been issued:
@@ -521,29 +475,15 @@ __device__ __forceinline__ void gemm_resid_ln_body(const GemmLnArgs& a) {
         substep(-1, 0, std::false_type{}, 0);                          // MFMAs (last tile, kk 1)
     } else {
     stage(0, 0);
-    if (nk >= 9) {                                             // K >= 576: pieces over the first eight k-steps
-        kstep(0, std::integral_constant<int, 0>{}); kstep(1, std::integral_constant<int, 1>{});
-        kstep(2, std::integral_constant<int, 2>{}); kstep(3, std::integral_constant<int, 3>{});
-        kstep(4, std::integral_constant<int, 4>{}); kstep(5, std::integral_constant<int, 5>{});
-        kstep(6, std::integral_constant<int, 6>{}); kstep(7, std::integral_constant<int, 7>{});
-        kstep(8, std::integral_constant<int, 8>{});
+    if (nk >= 9) {                                                    // K >= 576: pieces over the first eight k-steps
+        unrolled<9>([&](auto q) { kstep(q, q); });
         for (int kt = 9; kt < nk; ++kt) kstep(kt, std::integral_constant<int, 9>{});
     } else if (nk == 8) {                                             // K = 512: the last piece is added after the loop
-        kstep(0, std::integral_constant<int, 0>{}); kstep(1, std::integral_constant<int, 1>{});
-        kstep(2, std::integral_constant<int, 2>{}); kstep(3, std::integral_constant<int, 3>{});
-        kstep(4, std::integral_constant<int, 4>{}); kstep(5, std::integral_constant<int, 5>{});
-        kstep(6, std::integral_constant<int, 6>{}); kstep(7, std::integral_constant<int, 7>{});
+        unrolled<8>([&](auto q) { kstep(q, q); });
         x_add(std::integral_constant<int, 7>{});
     } else {                                                          // short K: all of x after the loop
         for (int kt = 0; kt < nk; ++kt) kstep(kt, std::integral_constant<int, 9>{});
-        x_load(std::integral_constant<int, 0>{}); x_add(std::integral_constant<int, 0>{});
-        x_load(std::integral_constant<int, 1>{}); x_add(std::integral_constant<int, 1>{});
-        x_load(std::integral_constant<int, 2>{}); x_add(std::integral_constant<int, 2>{});
-        x_load(std::integral_constant<int, 3>{}); x_add(std::integral_constant<int, 3>{});
-        x_load(std::integral_constant<int, 4>{}); x_add(std::integral_constant<int, 4>{});
-        x_load(std::integral_constant<int, 5>{}); x_add(std::integral_constant<int, 5>{});
-        x_load(std::integral_constant<int, 6>{}); x_add(std::integral_constant<int, 6>{});
-        x_load(std::integral_constant<int, 7>{}); x_add(std::integral_constant<int, 7>{});
+        unrolled<8>([&](auto q) { x_load(q); x_add(q); });
     }
     }
 
@@ -557,16 +497,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_resid_ln_kernel(GemmLnArgs 
 
 template <int BM, int WM, int WN, bool MX, bool GU>
 static int launch_ln_gu(const GemmLnArgs& a, hipStream_t st) {
-    constexpr int smem = 2 * (BM + 512) * 64 * 2;
-    static bool attr_set = false;
-    auto kern = gemm_resid_ln_kernel<BM, WM, WN, MX, GU>;
-    if (!attr_set) {
-        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(cdiv(a.M, BM)), dim3(WM * WN * 64), smem, st, a);
-    RALD_HIP(hipGetLastError());
-    return 0;
+    constexpr int smem = 2 * (BM + 512) * 64 * 2;                 // (always above 64 KiB)
+    static bool raised = false;
+    return launch_dyn_lds(gemm_resid_ln_kernel<BM, WM, WN, MX, GU>, raised, dim3(cdiv(a.M, BM)), WM * WN * 64, smem, st, a);
 }
 
 // group-uniform form when a tile's BM rows all share one modulation row (the denoiser: 512 rows per sample; the AE stack: gstride 0)

@@ -123,6 +123,49 @@ def test_key_loop_patterns():
     assert any("occupancy" in x for x in A.audit_kernel(_kernel(_LOOP_TWO_STAGE), 4, A.RESOURCES))
 
 
+_MFMA_KERNEL = """
+s_load_dwordx2 s[0:1], s[4:5], 0x0
+v_lshlrev_b32_e32 v1, 4, v0
+.LBB0_1:
+ds_read_b128 v[4:7], v1 offset:1024
+s_waitcnt lgkmcnt(0)
+v_mfma_f32_16x16x32_bf16 v[8:11], v[4:7], v[4:7], v[8:11]
+s_cmp_eq_u32 s2, s3
+s_cbranch_scc1 .LBB0_2
+s_branch .LBB0_1
+.LBB0_2:
+global_store_dwordx4 v[2:3], v[8:11], off
+s_endpgm
+"""
+
+
+def test_comparison_against_another_tree():
+    old = _kernel(_MFMA_KERNEL).replace("; Occupancy", "; LDSByteSize: 4096 bytes/workgroup (compile time only)\n; Occupancy")
+    assert A.resources(old) == {"NumVgprs": "100", "ScratchSize": "0", "Occupancy": "3", "LDSByteSize": "4096"}
+    assert [len(b) for b in A.mfma_blocks(old)] == [5]              # the loop body: label to branch
+    # other registers and block numbers, one more set-up instruction: the MFMA block is the same, the delta is counted outside it
+    renamed = old.replace("v[4:7]", "v[12:15]").replace("v1", "v20").replace("s2, s3", "s6, s7").replace(".LBB0_", ".LBB7_")
+    renamed = renamed.replace("v_lshlrev_b32_e32 v20, 4, v0", "v_lshlrev_b32_e32 v20, 4, v0\n\ts_mov_b32 s9, 0")
+    findings, notes = A.compare_kernel(old, renamed, True)
+    assert findings == [] and notes == ["1 MFMA block(s) identical, +1 instruction(s) outside them"]
+    # an instruction changed inside the block: a finding for a hot kernel, a note for any other
+    flipped = old.replace("s_cmp_eq_u32", "s_cmp_lg_u32").replace("s_cbranch_scc1 .LBB0_2", "s_cbranch_scc0 .LBB0_2")
+    findings, notes = A.compare_kernel(old, flipped, True)
+    assert len(findings) == 1 and "first at instruction 3: `s_cmp_eq_u32 s#, s#` -> `s_cmp_lg_u32 s#, s#`" in findings[0] and "DIFFER" in notes[0]
+    findings, notes = A.compare_kernel(old, flipped, False)
+    assert findings == [] and len(notes) == 2
+    # an offset is not a register name; a changed register count is a finding for every kernel
+    assert A.compare_kernel(old, old.replace("offset:1024", "offset:2048"), True)[0]
+    assert A.compare_kernel(old, old.replace("NumVgprs: 100", "NumVgprs: 104"), False)[0] == ["NumVgprs 100 -> 104"]
+    # a barrier lost outside the MFMA blocks (the hand-over of the staging buffers to the epilogue) is a finding for every kernel
+    with_barrier = old.replace("global_store_dwordx4", "s_barrier\n\tglobal_store_dwordx4")
+    assert A.compare_kernel(with_barrier, old, False)[0] == ["s_barrier count 1 -> 0"] and A.compare_kernel(with_barrier, with_barrier, True)[0] == []
+    # the hot set: the GEMM entries of HOT and every epilogue of the other shipped tile shapes
+    assert A.is_compare_hot(("gemm_mx8_kernel", (128, 128, 2, 2, 3))) and A.is_compare_hot(("gemm_resid_ln_kernel", (64, 1, 8, 1, 1)))
+    assert A.is_compare_hot(("gemm_nt_glds_kernel", (256, 256, 4, 2, 2, 3))) and not A.is_compare_hot(("gemm_nt_glds_kernel", (256, 256, 4, 2, 2, 1)))
+    assert not A.is_compare_hot(("gemm_resid_ln_kernel", (64, 1, 8, 1, 0))) and not A.is_compare_hot(None)
+
+
 def test_makefile_flags_are_the_library_s():
     hipcc, flags = A.makefile_flags(A.CSRC)
     assert "--offload-arch=gfx950" in flags and "-O3" in flags and "-amdgpu-mfma-vgpr-form=1" in flags

@@ -25,10 +25,12 @@ epilogue and the key loop's blocks out in program order.  A key loop whose shape
 no LDS-DMA issue behind the barrier) is reported, not passed.
 
     python tools/isa_audit.py [--csrc DIR] [--keep DIR] [--keyloop-all]      exit status 0 = clean, 1 = findings
+    python tools/isa_audit.py --against DIR      compare gemm.hip, gemm_fp8.hip and gemm_ln.hip with another tree's (see compare)
 """
 from __future__ import annotations
 
 import argparse
+import difflib
 import os
 import re
 import shutil
@@ -86,16 +88,26 @@ def compile_to_asm(csrc: str, name: str, out_dir: str) -> str:
     return open(out, encoding="utf-8").read()
 
 
-def split_kernels(asm: str) -> dict:
-    """(kernel name, template argument tuple) -> the kernel's text, from its label to its resource comment block."""
+def kernel_texts(asm: str) -> dict:
+    """mangled symbol -> the kernel's text, from its label to its resource comment block."""
     out = {}
-    for m in re.finditer(r"^(_ZN4rald\d+(\w+?)I((?:L[ib]\d+E)+)E\w*):", asm, flags=re.M):
+    for m in re.finditer(r"^(_ZN4rald\w+):\s*; @", asm, flags=re.M):        # (a function label; device variables carry no `; @`)
         end = asm.find("\n\t.section", m.end())
         tail = asm.find("; Occupancy:", m.end())
         stop = asm.find("\n", tail) if tail != -1 else end
-        args = tuple(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(3)))
-        out[(m.group(2), args)] = asm[m.start():stop if stop != -1 else len(asm)]
+        out[m.group(1)] = asm[m.start():stop if stop != -1 else len(asm)]
     return out
+
+
+def template_id(symbol: str):
+    """(kernel name, template argument tuple) of a kernel whose template arguments are all integers or bools, else None."""
+    m = re.match(r"_ZN4rald\d+(\w+?)I((?:L[ib]\d+E)+)E\w*$", symbol)
+    return (m.group(1), tuple(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2)))) if m else None
+
+
+def split_kernels(asm: str) -> dict:
+    """(kernel name, template argument tuple) -> the kernel's text."""
+    return {template_id(sym): text for sym, text in kernel_texts(asm).items() if template_id(sym)}
 
 
 def _instructions(text: str) -> list:
@@ -181,12 +193,108 @@ def audit(csrc: str = CSRC, keep: str | None = None, keyloop_all: bool = False) 
     return report
 
 
+# ---- comparison against another source tree (a refactor must leave the hot loops as they were) -----------------------------------
+ENGINE_FILES = ("gemm.hip", "gemm_fp8.hip", "gemm_ln.hip")
+# kernels whose MFMA blocks must not change (None = every value of that template argument): the GEMM entries of HOT and the other
+# shipped tile shapes of the two LDS-DMA GEMMs
+COMPARE_HOT = tuple((k, a) for f, k, a, *_ in HOT if f in ENGINE_FILES) + (
+    ("gemm_mx8_kernel", (256, 256, 4, 2, None)), ("gemm_mx8_kernel", (128, 128, 2, 2, None)),
+    ("gemm_nt_glds_kernel", (128, 128, 2, 2, 2, None)), ("gemm_nt_glds_kernel", (64, 128, 2, 2, 3, None)),
+    ("gemm_nt_glds_kernel", (64, 64, 2, 2, 8, None)),
+)
+_RESOURCES = ("NumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")
+_REG = re.compile(r"\b[vsa](\d+|\[\d+:\d+\])|\bttmp\d+")
+_BLOCK_END = re.compile(r"s_c?branch|s_endpgm|s_setpc")
+
+
+def is_compare_hot(tid) -> bool:
+    return tid is not None and any(tid[0] == k and len(tid[1]) == len(a) and all(y is None or x == y for x, y in zip(tid[1], a))
+                                   for k, a in COMPARE_HOT)
+
+
+def resources(text: str) -> dict:
+    return {k: (m.group(1) if (m := re.search(rf"; {k}: (\d+)", text)) else "?") for k in _RESOURCES}
+
+
+def mfma_blocks(text: str) -> list:
+    """The basic blocks (label or branch to branch) that hold an MFMA, registers and block labels replaced by placeholders."""
+    blocks, cur = [], []
+    for s in _instructions(text):
+        label = re.match(r"\.LBB\d+_\d+:$", s)
+        if label and cur:
+            blocks.append(cur)
+            cur = []
+        if not label:
+            cur.append(re.sub(r"\.LBB\d+_\d+", ".LBB", _REG.sub(lambda m: m.group(0)[0] + "#", s)))
+            if _BLOCK_END.match(s):
+                blocks.append(cur)
+                cur = []
+    blocks.append(cur)
+    return [b for b in blocks if any(i.startswith("v_mfma") for i in b)]
+
+
+def compare_kernel(old: str, new: str, hot: bool):
+    """(findings, notes) for one kernel present in both trees.  Findings: a resource or the number of barriers that changed and, for a hot kernel, every MFMA
+    block that is not instruction for instruction the same; the same differences of a kernel that is not hot are notes."""
+    findings = [f"{k} {a} -> {b}" for k, a, b in ((k, resources(old)[k], resources(new)[k]) for k in _RESOURCES) if a != b or a == "?"]
+    barriers = [sum(i == "s_barrier" for i in _instructions(t)) for t in (old, new)]
+    if barriers[0] != barriers[1]:
+        findings.append(f"s_barrier count {barriers[0]} -> {barriers[1]}")
+    bo, bn = mfma_blocks(old), mfma_blocks(new)
+    diffs = [f"{len(bo)} -> {len(bn)} MFMA blocks"] if len(bo) != len(bn) else []
+    for i, (x, y) in enumerate(zip(bo, bn)):
+        if x != y:
+            d = next((j for j, (p, q) in enumerate(zip(x, y)) if p != q), min(len(x), len(y)))
+            changed = sum(1 for t in difflib.SequenceMatcher(None, x, y, autojunk=False).get_opcodes() if t[0] != "equal")
+            diffs.append(f"MFMA block {i} ({len(x)} -> {len(y)} instructions) differs in {changed} place(s), first at instruction {d}: "
+                         f"`{x[d] if d < len(x) else '<end>'}` -> `{y[d] if d < len(y) else '<end>'}`")
+    count = lambda text, blocks: len([s for s in _instructions(text) if not s.endswith(":")]) - sum(map(len, blocks))
+    delta = count(new, bn) - count(old, bo)
+    notes = [f"{len(bn)} MFMA block(s) {'identical' if not diffs else 'DIFFER'}, {delta:+d} instruction(s) outside them"]
+    return findings + (diffs if hot else []), notes + ([] if hot else diffs)
+
+
+def compare(csrc: str, against: str, keep: str | None = None) -> int:
+    """Prints the comparison of the LDS-DMA GEMM files of `csrc` with those of `against`; returns the number of kernels with findings."""
+    tmp = keep or tempfile.mkdtemp(prefix="isa_audit_")
+    bad = 0
+    try:
+        for name in ENGINE_FILES:
+            sides = []
+            for tag, d in (("against", against), ("tree", csrc)):
+                os.makedirs(os.path.join(tmp, tag), exist_ok=True)
+                sides.append(kernel_texts(compile_to_asm(d, name, os.path.join(tmp, tag))))
+            old, new = sides
+            print(f"{name}: {len(new)} kernel symbols" + ("" if set(old) == set(new) else
+                  f"; ONLY against: {sorted(set(old) - set(new))}; ONLY tree: {sorted(set(new) - set(old))}"))
+            bad += set(old) != set(new)
+            for sym in sorted(set(old) & set(new)):
+                tid = template_id(sym)
+                hot = is_compare_hot(tid)
+                findings, notes = compare_kernel(old[sym], new[sym], hot)
+                title = f"{tid[0]}<{','.join(map(str, tid[1]))}>" if tid else sym
+                r = resources(new[sym])
+                print(f"{'FAIL' if findings else 'ok  '}  {'hot ' if hot else '    '}{title}  vgpr {r['NumVgprs']} occ {r['Occupancy']} lds {r['LDSByteSize']}: {notes[0]}")
+                for f in findings + notes[1:]:
+                    print("        " + f)
+                bad += bool(findings)
+    finally:
+        if keep is None:
+            shutil.rmtree(tmp, ignore_errors=True)
+    print("identical resources and hot MFMA blocks" if not bad else f"{bad} kernel(s) or file(s) with findings")
+    return bad
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--csrc", default=CSRC, help="directory with the .hip sources and the Makefile")
     ap.add_argument("--keep", default=None, help="keep the assembly files in this directory")
     ap.add_argument("--keyloop-all", action="store_true", help="hold every attention form to the key-loop rule (reports the row-major-V forms' mid-tile drain)")
+    ap.add_argument("--against", default=None, metavar="DIR", help="compare the LDS-DMA GEMM files' kernels with those of another csrc directory "
+                    "(symbols, registers, scratch, occupancy, LDS; the hot kernels' MFMA blocks instruction for instruction) instead of auditing")
     o = ap.parse_args()
+    if o.against:
+        return 1 if compare(o.csrc, o.against, o.keep) else 0
     report = audit(o.csrc, o.keep, o.keyloop_all)
     bad = 0
     for title, findings in report.items():
