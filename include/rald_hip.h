@@ -596,6 +596,19 @@ int rald_op_scale_rows(const float* in, const float* s, float* x_accum, void* ou
                        void* stream);
 int rald_op_softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_t rows, int64_t ld, int32_t n, float scale, void* P_bf16,
                              void* dS_bf16, void* stream);
+/* The stage-1 loss, its metrics and its gradient (engine_ae.py:70-101) for logits / labels [batch][n_queries] fp32 (labels exactly 0 or 1)
+ * and kl [batch].  n = *in_voxel_num_dev (device int32, clamped to [0, n_queries]) is read by the kernels, so a captured graph serves any
+ * split point.  out_losses4 (device double[4]) = [vol_weight vol + near_weight near + kl_weight kl, vol, near, kl]: vol / near = the mean of
+ * max(x, 0) - x y + log1p(exp(-|x|)) over [:, :n] / [:, n:] (NaN for an empty span, as torch's mean), kl = sum(kl) / batch; the total is not
+ * multiplied by grad_scale.  out_counts3 (device int32 [batch][3]) = (#(pred == label), #(pred and label), #(pred or label)) with
+ * pred = (x >= 0).  dlogits [batch][n_queries] (nullable) = grad_scale * w_span / (batch * n_span) * (sigmoid(x) - y); dkl [batch]
+ * (nullable) = grad_scale * kl_weight / batch.  Sums are accumulated in double through per-workgroup partials in the caller-owned scratch
+ * (16-byte aligned, _scratch_bytes(batch, n_queries) bytes - host arithmetic) and added in a fixed order: no float atomics, the same bits
+ * run to run, and one sample's counts and dlogits row do not depend on the rest of the batch.  Two launches. */
+int64_t rald_op_ae_loss_scratch_bytes(int32_t batch, int64_t n_queries);
+int rald_op_ae_loss(const float* logits, const float* labels, const float* kl, const int32_t* in_voxel_num_dev, int32_t batch, int64_t n_queries,
+                    float vol_weight, float near_weight, float kl_weight, float grad_scale, double* out_losses4, int32_t* out_counts3,
+                    float* dlogits, float* dkl, void* scratch, int64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

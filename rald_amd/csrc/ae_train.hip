@@ -14,6 +14,8 @@
 //   scale_rows_bf16   its backward: out_bf16[r] = s[r / rows_per_sample] * dx[r]               (the branch's gradient)
 //   softmax_bwd_rows  the single-head dim-512 attentions' softmax backward on stored fp32 scores: P = softmax(S[r][:n]),
 //                     dS = P (dP - delta[r]) * scale as bf16, columns n .. ld zero (keys padded to a multiple of 64 for the GEMMs)
+//   ae_loss           the stage-1 loss (engine_ae.py:70-101): BCE-with-logits means over [:, :n] and [:, n:] with n read on the device,
+//                     sum(kl) / B, the accuracy / IoU counts per sample, dlogits and dkl; sums in double through ordered partials
 #include "common.h"
 #include "kernels.h"
 
@@ -283,6 +285,144 @@ int softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_
     RALD_CHECK(ld >= n, "softmax_bwd_rows: ld must be >= n");
     RALD_CHECK(rows < (1ll << 31), "softmax_bwd_rows: too many rows");
     hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, S, dP, delta, ld, n, scale, P, dS);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the stage-1 loss
+// engine_ae.py:70-101 in two launches.  ae_loss_kernel: one workgroup per AL_CHUNK queries of one sample; every thread loads its AL_ITEMS
+// logits and labels before the first dependent operation, writes dlogits, and the workgroup leaves one partial (two double sums, three
+// counts) in scratch[b][chunk].  ae_loss_finish_kernel (one workgroup) adds the partials in (b, chunk) order.  The split point n is read
+// from device memory, so a captured graph serves any in_voxel_num.  A sample's counts, partials and dlogits row depend on its own row
+// only: the same bits in any batch.
+constexpr int AL_ITEMS = 4;
+constexpr int AL_CHUNK = 256 * AL_ITEMS;
+
+struct AeLossPart { double vol, near; int32_t eq, inter, uni, pad; };
+static_assert(sizeof(AeLossPart) == 32, "AeLossPart layout");
+
+__device__ __forceinline__ float sigmoidf_acc(float x) {                       // no cancellation on either side
+    const float e = expf(-fabsf(x));
+    return (x >= 0.f ? 1.0f : e) / (1.0f + e);
+}
+
+__global__ __launch_bounds__(256) void ae_loss_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
+                                                      const int32_t* __restrict__ n_dev, int batch, int64_t Q, float vol_w, float near_w,
+                                                      float grad_scale, float* __restrict__ dlogits, AeLossPart* __restrict__ part) {
+    __shared__ double shv[4], shn[4];
+    __shared__ int shc[4][3];
+    const int b = blockIdx.y;
+    const int64_t j0 = (int64_t)blockIdx.x * AL_CHUNK + threadIdx.x;
+    const float* xr = logits + (int64_t)b * Q;
+    const float* yr = labels + (int64_t)b * Q;
+    float x[AL_ITEMS], y[AL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < AL_ITEMS; ++i) {
+        const int64_t j = j0 + i * 256;
+        const bool in = j < Q;
+        x[i] = in ? xr[j] : 0.f;
+        y[i] = in ? yr[j] : 0.f;
+    }
+    int64_t n = *n_dev;
+    n = n < 0 ? 0 : (n > Q ? Q : n);
+    // grad_scale * w / (B * n_span) in double, rounded once: (3 w) / (3 n) and w / n are the same real number, hence the same float
+    const float cv = (float)((double)grad_scale * (double)vol_w / ((double)batch * (double)n));
+    const float cn = (float)((double)grad_scale * (double)near_w / ((double)batch * (double)(Q - n)));
+    double sv = 0.0, sn = 0.0;
+    int eq = 0, inter = 0, uni = 0;
+#pragma unroll
+    for (int i = 0; i < AL_ITEMS; ++i) {
+        const int64_t j = j0 + i * 256;
+        if (j >= Q) continue;
+        const float xv = x[i], yv = y[i];
+        const float term = fmaxf(xv, 0.f) - xv * yv + log1pf(expf(-fabsf(xv)));
+        const bool vol = j < n;
+        if (vol) sv += (double)term;
+        else sn += (double)term;
+        const bool pred = xv >= 0.f, lab = yv != 0.f;
+        eq += pred == lab;
+        inter += pred && lab;
+        uni += pred || lab;
+        if (dlogits) {
+            const float d = yv == 1.0f ? -sigmoidf_acc(-xv) : sigmoidf_acc(xv) - yv;
+            dlogits[(int64_t)b * Q + j] = (vol ? cv : cn) * d;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        sv += __shfl_xor(sv, o, 64);
+        sn += __shfl_xor(sn, o, 64);
+        eq += __shfl_xor(eq, o, 64);
+        inter += __shfl_xor(inter, o, 64);
+        uni += __shfl_xor(uni, o, 64);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { shv[wave] = sv; shn[wave] = sn; shc[wave][0] = eq; shc[wave][1] = inter; shc[wave][2] = uni; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        AeLossPart p;
+        p.vol = ((shv[0] + shv[1]) + shv[2]) + shv[3];
+        p.near = ((shn[0] + shn[1]) + shn[2]) + shn[3];
+        p.eq = shc[0][0] + shc[1][0] + shc[2][0] + shc[3][0];
+        p.inter = shc[0][1] + shc[1][1] + shc[2][1] + shc[3][1];
+        p.uni = shc[0][2] + shc[1][2] + shc[2][2] + shc[3][2];
+        p.pad = 0;
+        part[(int64_t)b * gridDim.x + blockIdx.x] = p;
+    }
+}
+
+__global__ __launch_bounds__(256) void ae_loss_finish_kernel(const AeLossPart* __restrict__ part, int nchunk, const float* __restrict__ kl,
+                                                             const int32_t* __restrict__ n_dev, int batch, int64_t Q, float vol_w, float near_w,
+                                                             float kl_w, float grad_scale, double* __restrict__ losses, int32_t* __restrict__ counts,
+                                                             float* __restrict__ dkl) {
+    __shared__ double shv[256], shn[256], shk[256];
+    const int t = threadIdx.x;
+    const int64_t total = (int64_t)batch * nchunk;
+    double sv = 0.0, sn = 0.0, sk = 0.0;
+    for (int64_t i = t; i < total; i += 256) { sv += part[i].vol; sn += part[i].near; }
+    for (int b = t; b < batch; b += 256) {
+        sk += (double)kl[b];
+        int eq = 0, inter = 0, uni = 0;
+        for (int c = 0; c < nchunk; ++c) {
+            const AeLossPart p = part[(int64_t)b * nchunk + c];
+            eq += p.eq; inter += p.inter; uni += p.uni;
+        }
+        counts[b * 3 + 0] = eq; counts[b * 3 + 1] = inter; counts[b * 3 + 2] = uni;
+        if (dkl) dkl[b] = (float)((double)grad_scale * (double)kl_w / (double)batch);
+    }
+    shv[t] = sv; shn[t] = sn; shk[t] = sk;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {                                       // a fixed tree: thread t adds slot t + o
+        if (t < o) { shv[t] += shv[t + o]; shn[t] += shn[t + o]; shk[t] += shk[t + o]; }
+        __syncthreads();
+    }
+    if (t == 0) {
+        int64_t n = *n_dev;
+        n = n < 0 ? 0 : (n > Q ? Q : n);
+        const double vol = shv[0] / ((double)batch * (double)n);              // 0 / 0 = NaN for an empty span, as torch's mean gives
+        const double near = shn[0] / ((double)batch * (double)(Q - n));
+        const double klm = shk[0] / (double)batch;
+        losses[0] = (double)vol_w * vol + (double)near_w * near + (double)kl_w * klm;
+        losses[1] = vol; losses[2] = near; losses[3] = klm;
+    }
+}
+
+int64_t ae_loss_scratch_bytes(int batch, int64_t n_queries) {
+    return batch > 0 && n_queries > 0 ? (int64_t)batch * ((n_queries + AL_CHUNK - 1) / AL_CHUNK) * (int64_t)sizeof(AeLossPart) : 0;
+}
+
+int ae_loss(const float* logits, const float* labels, const float* kl, const int32_t* n_dev, int batch, int64_t Q, float vol_w, float near_w,
+            float kl_w, float grad_scale, double* losses4, int32_t* counts3, float* dlogits, float* dkl, void* scratch, int64_t scratch_bytes,
+            hipStream_t st) {
+    RALD_CHECK(batch > 0 && Q > 0, "ae_loss: empty");
+    RALD_CHECK(batch <= 65535, "ae_loss: at most 65535 samples");
+    const int64_t nchunk = (Q + AL_CHUNK - 1) / AL_CHUNK;
+    RALD_CHECK(nchunk < (1ll << 31) && (int64_t)batch * nchunk < (1ll << 31), "ae_loss: too many queries");
+    RALD_CHECK(scratch && scratch_bytes >= ae_loss_scratch_bytes(batch, Q), "ae_loss: scratch too small");
+    RALD_CHECK((uintptr_t)scratch % 16 == 0 && (uintptr_t)losses4 % 8 == 0, "ae_loss: scratch must be 16-byte, out_losses4 8-byte aligned");
+    hipLaunchKernelGGL(ae_loss_kernel, dim3((unsigned)nchunk, (unsigned)batch), dim3(256), 0, st, logits, labels, n_dev, batch, Q, vol_w, near_w,
+                       grad_scale, dlogits, (AeLossPart*)scratch);
+    hipLaunchKernelGGL(ae_loss_finish_kernel, dim3(1), dim3(256), 0, st, (const AeLossPart*)scratch, (int)nchunk, kl, n_dev, batch, Q, vol_w,
+                       near_w, kl_w, grad_scale, losses4, counts3, dkl);
     RALD_HIP(hipGetLastError());
     return 0;
 }

@@ -703,6 +703,14 @@ int rald_op_softmax_bwd_rows(const float* S, const float* dP, const float* delta
                              void* dS_bf16, void* stream) {
     return softmax_bwd_rows(S, dP, delta, rows, ld, n, scale, (bf16*)P_bf16, (bf16*)dS_bf16, (hipStream_t)stream);
 }
+int64_t rald_op_ae_loss_scratch_bytes(int32_t batch, int64_t n_queries) { return ae_loss_scratch_bytes(batch, n_queries); }
+int rald_op_ae_loss(const float* logits, const float* labels, const float* kl, const int32_t* in_voxel_num_dev, int32_t batch, int64_t n_queries,
+                    float vol_weight, float near_weight, float kl_weight, float grad_scale, double* out_losses4, int32_t* out_counts3,
+                    float* dlogits, float* dkl, void* scratch, int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(logits && labels && kl && in_voxel_num_dev && out_losses4 && out_counts3, "rald_op_ae_loss: null pointer");
+    return ae_loss(logits, labels, kl, in_voxel_num_dev, batch, n_queries, vol_weight, near_weight, kl_weight, grad_scale, out_losses4, out_counts3,
+                   dlogits, dkl, scratch, scratch_bytes, (hipStream_t)stream);
+}
 int rald_op_cast_bf16(const float* in, void* out_bf16, int64_t n, void* stream) {
     RALD_CHECK(in && out_bf16, "rald_op_cast_bf16: null pointer");
     return cast_f32_bf16(in, (bf16*)out_bf16, n, (hipStream_t)stream);

@@ -177,6 +177,10 @@ int pe_wgrad(const float* dY, const float* pts, const float* basis, int64_t rows
              hipStream_t st);
 int posterior_bwd(const float* dz, const float* dkl, const float* ml, const float* eps, float* dml, int B, int rows, int L, hipStream_t st);
 int scale_rows(const float* in, const float* s, float* x_accum, bf16* out_bf16, int64_t rows, int cols, int64_t rows_per_sample, hipStream_t st);
+int64_t ae_loss_scratch_bytes(int batch, int64_t n_queries);
+int ae_loss(const float* logits, const float* labels, const float* kl, const int32_t* n_dev, int batch, int64_t Q, float vol_w, float near_w,
+            float kl_w, float grad_scale, double* losses4, int32_t* counts3, float* dlogits, float* dkl, void* scratch, int64_t scratch_bytes,
+            hipStream_t st);
 int softmax_bwd_rows(const float* S, const float* dP, const float* delta, int64_t rows, int64_t ld, int n, float scale, bf16* P, bf16* dS,
                      hipStream_t st);
 

@@ -17,6 +17,10 @@ The two 1-head dim-512 attentions run unfused: S = q.k^T / sqrt(512) as one batc
 64), the row softmax, P.V; backward dP = dO.V^T, csrc/ae_train.hip's softmax backward, dQ = dS.K and the key side through gemm_tn.
 The kernels specific to the AE (affine LayerNorm backward, PointEmbed weight gradient, posterior backward, drop-path rows, the masked
 softmax backward) are in csrc/ae_train.hip.
+
+``AeStepTrainer`` / ``GraphedAeStep`` are the stage-1 counterparts of ``train_dit.EdmTrainer`` / ``GraphedTrainStep``: the whole iteration
+(forward, ``train_ops.ae_loss``, backward, clip, fused AdamW / EMA) on ``train_utils.FlatAdamW`` storage with no host sync, eagerly or
+with the forward + loss + backward captured in one hipGraph.  ``engine_ae.train_one_epoch`` drives either.
 """
 from __future__ import annotations
 
@@ -432,3 +436,147 @@ class AeTrainer:
 def st_off(mix: bool) -> int:
     """Index of layers.0's attention mask in the drop-path list (the mix layer draws first)."""
     return 1 if mix else 0
+
+
+class AeStepTrainer:
+    """The reference's stage-1 iteration (engine_ae.py:55-116) on flat storage, as ``train_dit.EdmTrainer`` is for stage 2:
+
+        opt = FlatAdamW(model.parameters(), lr=..., ema=True)
+        step = AeStepTrainer(model, opt)
+        losses, counts, grad_norm = step.step(surface, points, labels, in_voxel_num)
+
+    One ``AeTrainer`` sits directly on the model's parameters: their ``.grad`` are views of ``opt.flat_g``, so ``backward`` fills the flat
+    gradient with no shadow copies.  The loss, its metrics and its gradient are ``train_ops.ae_loss`` (two launches, no host sync);
+    ``losses`` is the float64 device tensor [total, vol, near, kl], ``counts`` the int32 device tensor [B, 3] of ``ae_loss``.  ``logits``
+    and ``kl`` of the last forward stay on the object."""
+
+    def __init__(self, model, opt, reducer=None):
+        named = dict(model.named_parameters())
+        self.tr = AeTrainer(named, model.point_embed.basis, model.depth, model.latent_dim, model.query_type, heads=model.heads)
+        base, end = opt.flat_g.data_ptr(), opt.flat_g.data_ptr() + opt.flat_g.numel() * 4
+        for n, p in named.items():
+            if p.grad is None or not base <= p.grad.data_ptr() < end:
+                raise RuntimeError(f"AeStepTrainer: the gradient of {n} is not a view of opt.flat_g (build FlatAdamW over model.parameters())")
+        self.model, self.opt, self.reducer = model, opt, reducer
+        self.logits = self.kl = self.masks = None                   # of the last forward_backward
+        self._window_open = False
+
+    def refresh_weights(self) -> None:
+        self.tr.refresh_weights()
+
+    def draw(self, batch: int, eps=None, masks=None):
+        """The reference's draws for what is not given, in the autograd route's order (models_ae.KLAutoEncoder._train_forward): timm's
+        DropPath on the device RNG, then torch.randn on the CPU global RNG - one torch seed gives both routes the same masks and noise."""
+        if masks is None:
+            masks = drop_path_masks(batch, self.tr.n_masks, self.tr.dev)
+        if eps is None:
+            eps = torch.randn(batch, self.model.num_latents, self.model.latent_dim)
+        return eps, masks
+
+    def forward_backward(self, pc, queries, labels, in_voxel_num, eps=None, masks=None, grad_scale: float = 1.0, vol_weight: float = 1.0,
+                         near_weight: float = 0.1, kl_weight: float = 1e-3):
+        """AeTrainer.forward -> ae_loss -> AeTrainer.backward(st, dlogits, dkl): accumulates the gradient of grad_scale * loss into the flat
+        gradient.  Returns (losses, counts) as device tensors."""
+        eps, masks = self.draw(pc.shape[0], eps, masks)
+        self.masks = masks
+        logits, kl, st = self.tr.forward(pc, queries, eps, masks)
+        losses, counts, dlogits, dkl = TO.ae_loss(logits, labels.to(self.tr.dev), kl, in_voxel_num, vol_weight, near_weight, kl_weight, grad_scale)
+        self.tr.backward(st, dlogits, dkl)
+        self.logits, self.kl = logits, kl
+        return losses, counts
+
+    def _begin(self) -> None:
+        if not self._window_open:                                   # optimizer.zero_grad() at :46 and after every update (:111-112)
+            self.opt.zero_grad()
+            self._window_open = True
+
+    def _finish(self, update: bool, max_norm, ema_rate: float, refresh):
+        """engine_ae.py:107-116 after the backward pass: on an update iteration clip, AdamW with the EMA in the same pass, and the bf16
+        copies; otherwise the EMA alone (the reference updates it every iteration)."""
+        if not update:
+            self.opt.update_ema(ema_rate)
+            return None
+        pre = 1.0
+        if self.reducer is not None:
+            self.reducer.start()
+            pre = self.reducer.finish()
+        norm = self.opt.clip_grad_norm_(max_norm, pre_scale=pre)
+        self.opt.step(ema_rate=ema_rate)
+        refresh()
+        self._window_open = False
+        return norm
+
+    def step(self, pc, queries, labels, in_voxel_num, eps=None, masks=None, update: bool = True, accum_iter: int = 1, max_norm=None,
+             ema_rate: float = 0.999, vol_weight: float = 1.0, near_weight: float = 0.1, kl_weight: float = 1e-3):
+        """One iteration: ``update`` is the reference's ``(data_iter_step + 1) % accum_iter == 0``.  Returns (losses, counts, total gradient
+        norm or None) - device tensors, no host sync."""
+        self._begin()
+        losses, counts = self.forward_backward(pc, queries, labels, in_voxel_num, eps, masks, 1.0 / accum_iter, vol_weight, near_weight, kl_weight)
+        return losses, counts, self._finish(update, max_norm, ema_rate, self.tr.refresh_weights)
+
+
+class GraphedAeStep:
+    """``AeStepTrainer.step`` with its launches captured in two hipGraphs (torch.cuda.CUDAGraph on the current stream), after the pattern of
+    ``train_dit.GraphedTrainStep``:
+      graph A = forward + loss + backward on static input buffers (pc, queries, labels, eps, the drop-path scales as one [n_masks, B]
+                tensor, the int32 in_voxel_num the loss kernels read),
+      eager   = zero_grad when an accumulation window starts, the mask / noise draws, the input copies, clip + fused AdamW / EMA (or the EMA
+                alone between updates), the optional reducer,
+      graph B = refresh of the bf16 weight copies.
+    Shapes, the loss weights and accum_iter (it is the gradient scale inside graph A) are fixed at construction.  The trainer's bf16 copies
+    live in graph B's pool afterwards: drive the trainer through this object only.  The returned tensors are the graphs' static outputs,
+    rewritten by the next call."""
+
+    def __init__(self, step_trainer: AeStepTrainer, B: int, N: int, Q: int, accum_iter: int = 1, vol_weight: float = 1.0, near_weight: float = 0.1,
+                 kl_weight: float = 1e-3):
+        self.st, self.B, self.N, self.Q = step_trainer, B, N, Q
+        tr, opt, m = step_trainer.tr, step_trainer.opt, step_trainer.model
+        dev = tr.dev
+        self.fixed = dict(accum_iter=int(accum_iter), vol_weight=float(vol_weight), near_weight=float(near_weight), kl_weight=float(kl_weight))
+        z = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+        self.pc, self.queries, self.labels, self.eps = z(B, N, 3), z(B, Q, 3), z(B, Q), z(B, m.num_latents, m.latent_dim)
+        self.masks = torch.full((tr.n_masks, B), 1.0 / (1.0 - DROP_PATH_RATE), device=dev, dtype=torch.float32)
+        self.n_in = torch.full((1,), Q // 2, device=dev, dtype=torch.int32)
+        fb = lambda: step_trainer.forward_backward(self.pc, self.queries, self.labels, self.n_in, eps=self.eps, masks=list(self.masks.unbind(0)),
+                                                   grad_scale=1.0 / accum_iter, vol_weight=vol_weight, near_weight=near_weight,
+                                                   kl_weight=kl_weight)
+        grad = opt.flat_g.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                          # warm-up outside capture (lazy allocations, function attributes)
+            fb()
+            tr.refresh_weights()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.g_refresh = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.g_refresh):
+            tr.refresh_weights()                               # tr.W now lives in the graph's pool, rewritten by every replay
+        self.g_fb = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.g_fb):
+            self.losses, self.counts = fb()
+        self.logits, self.kl = step_trainer.logits, step_trainer.kl
+        opt.flat_g.copy_(grad)                                 # the warm-up pass and the capture leave the gradient as they found it
+        self.g_refresh.replay()
+
+    def __call__(self, pc, queries, labels, in_voxel_num, eps=None, masks=None, update: bool = True, accum_iter: int = None, max_norm=None,
+                 ema_rate: float = 0.999, vol_weight: float = None, near_weight: float = None, kl_weight: float = None):
+        """``AeStepTrainer.step`` with the same arguments; accum_iter and the weights, when given, must be those of the capture."""
+        for k, v in dict(accum_iter=accum_iter, vol_weight=vol_weight, near_weight=near_weight, kl_weight=kl_weight).items():
+            if v is not None and float(v) != float(self.fixed[k]):
+                raise ValueError(f"GraphedAeStep: {k}={v} differs from the captured {self.fixed[k]}")
+        if tuple(pc.shape) != (self.B, self.N, 3) or tuple(queries.shape) != (self.B, self.Q, 3) or tuple(labels.shape) != (self.B, self.Q):
+            raise ValueError(f"GraphedAeStep: captured for pc [{self.B},{self.N},3], queries [{self.B},{self.Q},3], labels [{self.B},{self.Q}]")
+        st = self.st
+        st._begin()
+        eps, masks = st.draw(self.B, eps, masks)
+        self.pc.copy_(pc, non_blocking=True)
+        self.queries.copy_(queries, non_blocking=True)
+        self.labels.copy_(labels, non_blocking=True)
+        self.eps.copy_(eps, non_blocking=True)
+        self.masks.copy_(torch.stack([m.reshape(self.B) for m in masks]), non_blocking=True)
+        if isinstance(in_voxel_num, torch.Tensor):
+            self.n_in.copy_(in_voxel_num.reshape(1), non_blocking=True)
+        else:
+            self.n_in.fill_(int(in_voxel_num))
+        self.g_fb.replay()
+        return self.losses, self.counts, st._finish(update, max_norm, ema_rate, self.g_refresh.replay)

@@ -194,6 +194,39 @@ def pad_channels(x: torch.Tensor, cols: int) -> torch.Tensor:
     return out
 
 
+def ae_loss(logits: torch.Tensor, labels: torch.Tensor, kl: torch.Tensor, in_voxel_num, vol_weight: float = 1.0, near_weight: float = 0.1,
+            kl_weight: float = 1e-3, grad_scale: float = 1.0, want_grad: bool = True):
+    """The autoencoder's stage-1 loss on the device (engine_ae.py:70-101; csrc/ae_train.hip): fp32 logits / labels [B, Q] (labels 0 or 1),
+    kl [B] -> (losses float64 [4] = [vol_weight vol + near_weight near + kl_weight kl, vol, near, kl], counts int32 [B, 3] =
+    (#(pred == label), #(pred and label), #(pred or label)) with pred = logits >= 0, dlogits [B, Q], dkl [B]); the gradients are those of
+    grad_scale * total, None when want_grad is False (evaluation).  ``in_voxel_num`` reaches the kernels as one int32 in device memory (the same captured
+    graph serves any split point): a device int32 tensor of one element passes as it is, a Python int or another tensor is copied there
+    first.  No host sync."""
+    B, Q = logits.shape
+    dev = logits.device
+    if not (logits.is_cuda and labels.is_cuda and kl.is_cuda):
+        raise RuntimeError("ae_loss runs on the HIP device only (no CPU fallback)")
+    if labels.shape != logits.shape or kl.numel() != B:
+        raise ValueError(f"ae_loss: logits {tuple(logits.shape)}, labels {tuple(labels.shape)} and kl {tuple(kl.shape)} do not belong together")
+    if not isinstance(in_voxel_num, torch.Tensor):
+        in_voxel_num = torch.tensor([int(in_voxel_num)], dtype=torch.int32)
+    if in_voxel_num.numel() != 1:
+        raise ValueError("ae_loss: in_voxel_num must be a Python int or a tensor of one element")
+    in_voxel_num = in_voxel_num.reshape(1).to(device=dev, dtype=torch.int32)          # the graphed step's int32 device buffer passes as it is
+    f32c = lambda t: t.detach().to(torch.float32).contiguous()
+    logits, labels, kl = f32c(logits), f32c(labels), f32c(kl)
+    losses = torch.empty(4, device=dev, dtype=torch.float64)
+    counts = torch.empty(B, 3, device=dev, dtype=torch.int32)
+    dlogits = torch.empty(B, Q, device=dev, dtype=torch.float32) if want_grad else None
+    dkl = torch.empty(B, device=dev, dtype=torch.float32) if want_grad else None
+    nbytes = lib().rald_op_ae_loss_scratch_bytes(B, Q)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    check(lib().rald_op_ae_loss(logits.data_ptr(), labels.data_ptr(), kl.data_ptr(), in_voxel_num.data_ptr(), B, Q, float(vol_weight),
+                                float(near_weight), float(kl_weight), float(grad_scale), losses.data_ptr(), counts.data_ptr(), _opt(dlogits),
+                                _opt(dkl), scratch.data_ptr(), nbytes, _stream()))
+    return losses, counts, dlogits, dkl
+
+
 def prepare_block_weights(sd: Dict[str, torch.Tensor], prefix: str, device) -> Dict[str, torch.Tensor]:
     """bf16 compute copies (and their transposes for the dX products) of one block's fp32 master weights."""
     g = lambda n: sd[prefix + n].to(device=device, dtype=torch.float32)
