@@ -169,6 +169,14 @@ int rald_ae_decode_latents(rald_ae* h, const float* z, int32_t batch, void* ctx,
 /* queries [B,Q,3] -> occupancy logits [B,Q] (the reference returns [B,Q,1]; occupied iff > 0) */
 int rald_ae_decode_queries(rald_ae* h, const void* ctx, const float* queries, int32_t batch, int64_t n_queries,
                            float* out_logits, void* stream);
+/* The same decoder on RAGGED query sets (the batched inference tail): queries [n_total,3] and out_logits [n_total] are the samples'
+ * rows concatenated, offsets = DEVICE int64 [batch+1] with offsets[0] = 0 and sample b owning rows offsets[b] .. offsets[b+1]-1 (an
+ * empty segment is legal, a segment may start anywhere); max_per_sample = a HOST upper bound of the longest segment (it sizes the
+ * grid; nothing is read back, so the bound cannot be checked: with a bound BELOW the longest segment the rows behind it stay
+ * unwritten and no error is returned).  A segment is cut into 64-query chunks from its own first row, so its logits are bit-identical
+ * to rald_ae_decode_queries with the same ctx on that segment alone.  Rows from offsets[batch] on are not written. */
+int rald_ae_decode_queries_ragged(rald_ae* h, const void* ctx, const float* queries, const int64_t* offsets, int32_t batch,
+                                  int64_t max_per_sample, float* out_logits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Radar-spectrum encoder alone: RadarAutoencoder.encoder / _encode (model/models_radar_encoder.py
@@ -202,12 +210,25 @@ int64_t rald_post_scratch_bytes(int64_t n_queries);
 int rald_post_occupied_points(const float* logits, const float* queries, int64_t n_queries, const double* pc_range6_host,
                               int32_t norm_anisotropy, int32_t norm_isotropy, int32_t view_cone_mode, float threshold,
                               float* out_points, int64_t* out_index, int64_t* out_count, void* scratch, void* stream);
+/* rald_post_occupied_points for a ragged batch (layout as rald_ae_decode_queries_ragged; in_offsets / out_offsets DEVICE int64
+ * [batch+1]): the positives of every sample in ascending query order, the samples packed one behind the other in out_points
+ * [<=n_total,3]; out_offsets[b] .. out_offsets[b+1]-1 are sample b's rows; out_index (optional) counts from the sample's first query.
+ * Rows from in_offsets[batch] on (n_total may be a worst-case size) belong to no sample and are not counted.
+ * scratch: rald_post_scratch_bytes(n_total), 8-byte aligned.  No host read. */
+int rald_post_occupied_points_ragged(const float* logits, const float* queries, const int64_t* in_offsets, int32_t batch, int64_t n_total,
+                                     const double* pc_range6_host, int32_t norm_anisotropy, int32_t norm_isotropy, int32_t view_cone_mode,
+                                     float threshold, float* out_points, int64_t* out_index, int64_t* out_offsets, void* scratch, void* stream);
 /* inverse_norm_points (+ polar2cartesian) of a whole array (the ground-truth surface, :290, :317) */
 int rald_post_transform_points(const float* points, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy,
                                int32_t norm_isotropy, int32_t view_cone_mode, float* out_points, void* stream);
 /* cal_metrics' two sums (exact nearest neighbour, fp64): out_sums2[0] = sum_pred min_gt ||.||,
  * out_sums2[1] = sum_gt min_pred ||.||;  chamfer = 0.5*out[0]/n_pred + 0.5*out[1]/n_gt */
 int rald_post_chamfer_sums(const float* pred, int64_t n_pred, const float* gt, int64_t n_gt, double* out_sums2, void* stream);
+/* rald_post_chamfer_sums per sample of a ragged batch: out_sums [batch,2] (device doubles, zeroed here); max_pred / max_gt = HOST upper
+ * bounds of the longest segment of either side (they size the grids; the device offsets are not read back, so a bound BELOW a segment's
+ * length silently leaves that segment's rows behind the bound out of its sum).  A sample with an empty side keeps 0 for that sum. */
+int rald_post_chamfer_sums_ragged(const float* pred, const int64_t* pred_offsets, const float* gt, const int64_t* gt_offsets, int32_t batch,
+                                  int64_t max_pred, int64_t max_gt, double* out_sums, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 
@@ -240,6 +261,15 @@ int rald_query_norm_points(const float* points, int64_t n, const double* pc_rang
 int rald_query_refine(const float* helper_points, int64_t n_helper, int64_t aug_num, const int64_t* sel_index, const int64_t* aug_scales,
                       const double* u_bias, const double* pc_range6_host, const double* voxel_size3_host, int32_t norm_anisotropy,
                       int32_t norm_isotropy, int32_t normalise, float* out_points, void* stream);
+/* rald_query_refine for a ragged batch of helper points (points [n_total,3], offsets DEVICE int64 [batch+1]): a sample with N_b > 0
+ * points gets aug_num rows - its first min(N_b, aug_num) points, then row j >= N_b from draw g = j - N_b of ITS rows of the draws
+ * (sel_index / aug_scales int64 [batch,aug_num], u_bias float64 [batch,aug_num,3]; sel_index NULL: the point min(floor(u_sel[b,g] *
+ * N_b), N_b - 1) in float64, u_sel float64 [batch,aug_num] in [0,1)) - and a sample without points gets none.  out_queries
+ * [batch*aug_num,3] holds the samples packed, out_offsets (DEVICE int64 [batch+1]) their rows.  No host read. */
+int rald_query_refine_ragged(const float* points, const int64_t* offsets, int32_t batch, int64_t aug_num, const int64_t* sel_index,
+                             const double* u_sel, const int64_t* aug_scales, const double* u_bias, const double* pc_range6_host,
+                             const double* voxel_size3_host, int32_t norm_anisotropy, int32_t norm_isotropy, int32_t normalise,
+                             float* out_queries, int64_t* out_offsets, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer step of train_one_epoch (engine_generation.py:96-110) on FLAT fp32 storage: the model's

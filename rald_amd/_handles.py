@@ -60,6 +60,14 @@ def _doubles(vals: Sequence[float], n: int, what: str, layout: str = "") -> C.Ar
     return (C.c_double * n)(*[float(v) for v in vals])
 
 
+def _ragged_batch(offsets: torch.Tensor, what: str) -> int:
+    """B of a ragged layout's offsets: a contiguous int64 [B+1] DEVICE tensor (checked by shape and dtype only: its values stay on the device)."""
+    if not (isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1
+            and offsets.numel() >= 2 and offsets.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous int64 [B+1] tensor on the GPU")
+    return offsets.numel() - 1
+
+
 class _Handle:
     """Owner of one rald_<kind>* handle: created from `args` by rald_<kind>_create, destroyed by rald_<kind>_destroy when the owner
     drops it.  `_h` is the handle itself (a c_void_p) for the calls."""
@@ -480,6 +488,20 @@ class AeHandle(_Handle):
                                "must have the same batch size")
         out = torch.empty(B, Q, device=queries.device, dtype=torch.float32)
         check(lib().rald_ae_decode_queries(self._h, ctx.data_ptr(), queries.data_ptr(), B, Q, out.data_ptr(), _stream()))
+        return out
+
+    def decode_queries_ragged(self, ctx: torch.Tensor, queries: torch.Tensor, offsets: torch.Tensor, max_per_sample: int) -> torch.Tensor:
+        """queries [T,3] = the samples' query sets concatenated, offsets int64 [B+1] on the device (sample b owns rows
+        offsets[b] .. offsets[b+1]-1), max_per_sample a host upper bound of the longest set -> logits [T].  Nothing is read back."""
+        _need_cuda(queries, "queries")
+        queries = _f32c(queries).reshape(-1, 3)
+        B = _ragged_batch(offsets, "offsets")
+        if ctx.dtype != torch.uint8 or not ctx.is_cuda or ctx.numel() != lib().rald_ae_ctx_bytes(self._h, B):
+            raise RuntimeError(f"decoder context of {ctx.numel()} bytes does not belong to a batch of {B}: decode_latents(z) and the offsets "
+                               "must have the same batch size")
+        out = torch.empty(queries.shape[0], device=queries.device, dtype=torch.float32)
+        check(lib().rald_ae_decode_queries_ragged(self._h, ctx.data_ptr(), queries.data_ptr(), offsets.data_ptr(), B, int(max_per_sample),
+                                                  out.data_ptr(), _stream()))
         return out
 
 

@@ -68,6 +68,8 @@ struct Ae {
     int64_t ctx_bytes(int B) const;
     int decode_latents(const float* z, int B, void* ctx, hipStream_t st);
     int decode_queries(const void* ctx, const float* q, int B, int64_t Q, float* out, hipStream_t st);
+    int decode_queries_ragged(const void* ctx, const float* q, const int64_t* offsets, int B, int64_t max_per_sample, float* out,
+                              hipStream_t st);
 };
 
 }  // namespace rald

@@ -442,4 +442,14 @@ int Ae::decode_queries(const void* ctx, const float* q, int B, int64_t Q, float*
     return ae_decode_stream(ctx, l_img, q, out, basis, basis_diag, B, Q, cfg.num_latents, c0, st);
 }
 
+int Ae::decode_queries_ragged(const void* ctx, const float* q, const int64_t* offsets, int B, int64_t max_per_sample, float* out,
+                              hipStream_t st) {
+    RALD_CHECK(finalized, "ae: weights not finalized");
+    RALD_CHECK(ctx && offsets && B >= 1 && max_per_sample >= 0 && (max_per_sample == 0 || (q && out)), "ae: bad arguments");
+    RALD_CHECK((uintptr_t)ctx % 16 == 0, "ae: decoder context must be 16-byte aligned");
+    RALD_TRY(ctx_registry.check(ctx, ctx_header(B), st, "decoder context"));
+    ctx = (const char*)ctx + BLOB_HEADER_BYTES;
+    return ae_decode_stream_ragged(ctx, l_img, q, offsets, out, basis, basis_diag, B, max_per_sample, cfg.num_latents, c0, st);
+}
+
 }  // namespace rald

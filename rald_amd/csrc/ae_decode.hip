@@ -237,8 +237,10 @@ struct DecodeArgs {
     float c0, eps;
 };
 
-template <bool DIAG, int NW>
-__global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a) {
+// RAGGED = false: sample b owns queries [b*Q, (b+1)*Q).  RAGGED = true: rows offsets[b] .. offsets[b+1] - 1 of one concatenated array
+// (a.Q unused), chunked from the segment's own first row, so a query has the wave-mates it has in a dense launch on that segment alone.
+template <bool DIAG, int NW, bool RAGGED>
+__global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a, const int64_t* __restrict__ offsets) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int M = a.M;
     unsigned char* s_h = smem;                                   // M * 128
@@ -249,6 +251,14 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.y;
+    int64_t first = 0, seg = 0;
+    if constexpr (RAGGED) {
+        first = offsets[b];
+        seg = offsets[b + 1] - first;
+        // an empty or short segment leaves this workgroup without a chunk (the grid is sized by the longest one): it is done before it
+        // loads the context; a descending or negative pair of offsets decodes nothing
+        if (first < 0 || seg <= 0 || (int64_t)blockIdx.x * NW * 64 >= seg) return;
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(a.ctx + (int64_t)b * a.ctx_stride);
         uint4* dst = reinterpret_cast<uint4*>(s_h);
@@ -265,9 +275,10 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a)
     __syncthreads();
     const float inv_scale = s_u[M];
     const int r = lane & 31, h = lane >> 5;
-    const float* qin = a.queries + (int64_t)b * a.Q * 3;
-    float* qout = a.out + (int64_t)b * a.Q;
-    const int64_t nchunks = (a.Q + 63) / 64;
+    const int64_t Q = RAGGED ? seg : a.Q;
+    const float* qin = a.queries + (RAGGED ? first : (int64_t)b * a.Q) * 3;
+    float* qout = a.out + (RAGGED ? first : (int64_t)b * a.Q);
+    const int64_t nchunks = (Q + 63) / 64;
     const float quarter = h ? 0.25f : 0.0f;                       // cos(t) = sin(t + 1/4 revolution)
 
     for (int64_t chunk = (int64_t)blockIdx.x * NW + wave; chunk < nchunks; chunk += (int64_t)gridDim.x * NW) {
@@ -276,7 +287,7 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a)
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             int64_t q = chunk * 64 + qb * 32 + r;
-            q = q < a.Q ? q : a.Q - 1;
+            q = q < Q ? q : Q - 1;
             const float x = qin[q * 3 + 0], y = qin[q * 3 + 1], z = qin[q * 3 + 2];
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
@@ -379,25 +390,26 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a)
             const float wa = __builtin_amdgcn_exp2f(m[qb] - mm), wb = __builtin_amdgcn_exp2f(mo - mm);
             const float dsum = den[qb] * wa + dn * wb, nsum = num[qb] * wa + nn * wb;
             const int64_t q = chunk * 64 + qb * 32 + r;
-            if (h == 0 && q < a.Q) qout[q] = nsum / dsum + a.c0;
+            if (h == 0 && q < Q) qout[q] = nsum / dsum + a.c0;
         }
     }
 }
 
-template <bool DIAG>
-static int launch_decode(const DecodeArgs& a, int B, size_t smem, hipStream_t st) {
+// longest = the queries of one sample (dense) or a host upper bound of the longest segment (ragged): it sizes the grid
+template <bool DIAG, bool RAGGED>
+static int launch_decode(const DecodeArgs& a, const int64_t* offsets, int B, int64_t longest, size_t smem, hipStream_t st) {
     constexpr int NW = 12;                                         // waves per workgroup (the measured best of 8, 12 and 16)
-    auto kern = ae_decode_stream_kernel<DIAG, NW>;
+    auto kern = ae_decode_stream_kernel<DIAG, NW, RAGGED>;
     static bool attr_set = false;
     if (!attr_set) {
         RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 * 128 + 8192 + (1024 + 4 + 76) * 4));
         attr_set = true;
     }
-    const int64_t nchunks = (a.Q + 63) / 64;
+    const int64_t nchunks = (longest + 63) / 64;
     int64_t per_sample = (nchunks + NW - 1) / NW;                  // workgroups that have at least one chunk per wave
     const int64_t cap = B >= 256 ? 1 : 256 / B;                    // about one workgroup per CU over the whole batch
     if (per_sample > cap) per_sample = cap;
-    hipLaunchKernelGGL(kern, dim3((unsigned)per_sample, (unsigned)B), dim3(NW * 64), smem, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)per_sample, (unsigned)B), dim3(NW * 64), smem, st, a, offsets);
     RALD_HIP(hipGetLastError());
     return 0;
 }
@@ -411,7 +423,25 @@ int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* 
     a.ctx = (const unsigned char*)ctx; a.ctx_stride = ae_ctx_stride(M); a.l_img = l_img; a.queries = queries; a.out = out; a.basis = basis;
     a.Q = Q; a.M = M; a.c0 = c0; a.eps = 1e-5f;
     const size_t smem = (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76) * 4;
-    return basis_diag ? launch_decode<true>(a, B, smem, st) : launch_decode<false>(a, B, smem, st);
+    return basis_diag ? launch_decode<true, false>(a, nullptr, B, Q, smem, st) : launch_decode<false, false>(a, nullptr, B, Q, smem, st);
+}
+
+// the same decoder on ragged query sets: queries [T][3] / out [T] concatenated over the samples, offsets [B + 1] on the device (sample b owns
+// rows offsets[b] .. offsets[b+1] - 1; empty segments are fine), max_per_sample a host upper bound of the longest segment (trusted: the
+// offsets are on the device, so a bound that is too small leaves the rows behind it undecoded and returns no error).  Nothing is read
+// back: a workgroup without a chunk in its sample's segment returns at once.
+int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const float* queries, const int64_t* offsets, float* out,
+                            const float* basis, int basis_diag, int B, int64_t max_per_sample, int M, float c0, hipStream_t st) {
+    RALD_CHECK(M % 32 == 0 && M >= 32 && M <= 1024, "ae_decode_stream_ragged: num_latents must be a multiple of 32 in [32,1024]");
+    RALD_CHECK(B >= 1 && B <= 65535 && max_per_sample >= 0, "ae_decode_stream_ragged: bad batch / query count");
+    RALD_CHECK(offsets, "ae_decode_stream_ragged: null offsets");
+    if (max_per_sample == 0) return 0;
+    RALD_CHECK(queries && out, "ae_decode_stream_ragged: null pointer");
+    DecodeArgs a;
+    a.ctx = (const unsigned char*)ctx; a.ctx_stride = ae_ctx_stride(M); a.l_img = l_img; a.queries = queries; a.out = out; a.basis = basis;
+    a.Q = 0; a.M = M; a.c0 = c0; a.eps = 1e-5f;
+    const size_t smem = (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76) * 4;
+    return basis_diag ? launch_decode<true, true>(a, offsets, B, max_per_sample, smem, st) : launch_decode<false, true>(a, offsets, B, max_per_sample, smem, st);
 }
 
 }  // namespace rald

@@ -150,6 +150,11 @@ int rald_ae_decode_queries(rald_ae* h, const void* ctx, const float* queries, in
     RALD_CHECK(h, "null handle");
     return h->impl.decode_queries(ctx, queries, batch, n_queries, out_logits, (hipStream_t)stream);
 }
+int rald_ae_decode_queries_ragged(rald_ae* h, const void* ctx, const float* queries, const int64_t* offsets, int32_t batch,
+                                  int64_t max_per_sample, float* out_logits, void* stream) {
+    RALD_CHECK(h, "null handle");
+    return h->impl.decode_queries_ragged(ctx, queries, offsets, batch, max_per_sample, out_logits, (hipStream_t)stream);
+}
 
 // test entry point of the streaming query decoder (ae_decode.hip)
 int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, const float* norm_w, const float* norm_b, const float* wpe,
@@ -245,12 +250,22 @@ int rald_post_occupied_points(const float* logits, const float* queries, int64_t
     return post_occupied_points(logits, queries, n_queries, pc_range6_host, norm_anisotropy, norm_isotropy, view_cone_mode, threshold,
                                 out_points, out_index, out_count, (int*)scratch, (hipStream_t)stream);
 }
+int rald_post_occupied_points_ragged(const float* logits, const float* queries, const int64_t* in_offsets, int32_t batch, int64_t n_total,
+                                     const double* pc_range6_host, int32_t norm_anisotropy, int32_t norm_isotropy, int32_t view_cone_mode,
+                                     float threshold, float* out_points, int64_t* out_index, int64_t* out_offsets, void* scratch, void* stream) {
+    return post_occupied_points_ragged(logits, queries, in_offsets, batch, n_total, pc_range6_host, norm_anisotropy, norm_isotropy,
+                                       view_cone_mode, threshold, out_points, out_index, out_offsets, (int*)scratch, (hipStream_t)stream);
+}
 int rald_post_transform_points(const float* points, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy,
                                int32_t norm_isotropy, int32_t view_cone_mode, float* out_points, void* stream) {
     return post_transform_points(points, n, pc_range6_host, norm_anisotropy, norm_isotropy, view_cone_mode, out_points, (hipStream_t)stream);
 }
 int rald_post_chamfer_sums(const float* pred, int64_t n_pred, const float* gt, int64_t n_gt, double* out_sums2, void* stream) {
     return post_chamfer_sums(pred, n_pred, gt, n_gt, out_sums2, (hipStream_t)stream);
+}
+int rald_post_chamfer_sums_ragged(const float* pred, const int64_t* pred_offsets, const float* gt, const int64_t* gt_offsets, int32_t batch,
+                                  int64_t max_pred, int64_t max_gt, double* out_sums, void* stream) {
+    return post_chamfer_sums_ragged(pred, pred_offsets, gt, gt_offsets, batch, max_pred, max_gt, out_sums, (hipStream_t)stream);
 }
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream) {
     return post_iou(logits, labels, batch, n_queries, out_accuracy, out_iou, (hipStream_t)stream);
@@ -381,6 +396,13 @@ int rald_query_refine(const float* helper_points, int64_t n_helper, int64_t aug_
     RALD_CHECK(pc_range6_host && voxel_size3_host && (aug_num == 0 || (helper_points && out_points)), "rald_query_refine: null argument");
     return query_refine(helper_points, n_helper, aug_num, sel_index, aug_scales, u_bias, pc_range6_host, voxel_size3_host, norm_anisotropy,
                         norm_isotropy, normalise, out_points, (hipStream_t)stream);
+}
+int rald_query_refine_ragged(const float* points, const int64_t* offsets, int32_t batch, int64_t aug_num, const int64_t* sel_index,
+                             const double* u_sel, const int64_t* aug_scales, const double* u_bias, const double* pc_range6_host,
+                             const double* voxel_size3_host, int32_t norm_anisotropy, int32_t norm_isotropy, int32_t normalise,
+                             float* out_queries, int64_t* out_offsets, void* stream) {
+    return query_refine_ragged(points, offsets, batch, aug_num, sel_index, u_sel, aug_scales, u_bias, pc_range6_host, voxel_size3_host,
+                               norm_anisotropy, norm_isotropy, normalise, out_queries, out_offsets, (hipStream_t)stream);
 }
 
 // ---- optimizer step on flat parameter storage --------------------------------------

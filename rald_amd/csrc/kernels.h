@@ -271,6 +271,9 @@ int ae_ctx_build(const float* x, const float* gamma, const float* beta, const fl
                  hipStream_t st);
 int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* queries, float* out, const float* basis, int basis_diag,
                      int B, int64_t Q, int M, float c0, hipStream_t st);
+// ragged query sets: queries [T][3] / out [T], device offsets [B + 1], max_per_sample = host upper bound of the longest segment
+int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const float* queries, const int64_t* offsets, float* out,
+                            const float* basis, int basis_diag, int B, int64_t max_per_sample, int M, float c0, hipStream_t st);
 // basis_diag of a host copy of point_embed.basis [3][24]: 1 when it is block-diagonal (x -> columns 0-7, y -> 8-15, z -> 16-23), which
 // makes a projection one multiply instead of three; the one rule by which every caller picks the streaming kernel's form
 inline int ae_basis_is_block_diagonal(const float* basis_host) {
@@ -290,6 +293,12 @@ int post_occupied_points(const float* logits, const float* queries, int64_t Q, c
                          int view_cone, float thr, float* out_pts, int64_t* out_idx, int64_t* out_count, int* scratch, hipStream_t st);
 int post_transform_points(const float* in, int64_t n, const double* pc_range_host, int aniso, int iso, int view_cone, float* out, hipStream_t st);
 int post_chamfer_sums(const float* a, int64_t na, const float* b, int64_t nb, double* sums, hipStream_t st);
+// ragged batches: concatenated rows + device int64 offsets [B + 1]; no host read
+int post_occupied_points_ragged(const float* logits, const float* queries, const int64_t* in_offsets, int B, int64_t T,
+                                const double* pc_range_host, int aniso, int iso, int view_cone, float thr, float* out_pts, int64_t* out_idx,
+                                int64_t* out_offsets, int* scratch, hipStream_t st);
+int post_chamfer_sums_ragged(const float* a, const int64_t* a_off, const float* b, const int64_t* b_off, int B, int64_t max_a, int64_t max_b,
+                             double* sums, hipStream_t st);
 int post_iou(const float* logits, const float* labels, int B, int64_t Q, float* acc, float* iou, hipStream_t st);
 int radar_cube_prepare(const float* raw, int B, int R, int A, int E, int Craw, int tA, int tE, int norm_i, float max_i, int norm_d,
                        float max_d, float* out, hipStream_t st);
@@ -301,6 +310,9 @@ int query_uniform_cart(const double* u, int64_t n, const double* range_cart, con
 int query_norm_points(const float* in, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_refine(const float* pred, int64_t n_pred, int64_t aug_num, const int64_t* sel, const int64_t* scales, const double* u,
                  const double* pc_range, const double* voxel, int aniso, int iso, int normalise, float* out, hipStream_t st);
+int query_refine_ragged(const float* points, const int64_t* offsets, int B, int64_t aug_num, const int64_t* sel, const double* u_sel,
+                        const int64_t* scales, const double* u, const double* pc_range, const double* voxel, int aniso, int iso, int normalise,
+                        float* out, int64_t* out_offsets, hipStream_t st);
 
 // ---------------------------------------------------------------- gemm_fp8.hip (MXFP8: e4m3 + e8m0 per 32 K-elements)
 struct Mx8Args {

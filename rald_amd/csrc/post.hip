@@ -86,10 +86,22 @@ __device__ __forceinline__ void xform_point(const PostXform& t, float px, float 
     out[0] = x; out[1] = y; out[2] = z;
 }
 
-// pass 3: scatter the positives in index order, transformed
+// first row of the segment that owns row i: seg[b] <= i < seg[b + 1] (seg ascending, seg[B] > i; empty segments repeat a value)
+__device__ __forceinline__ int64_t segment_start(const int64_t* __restrict__ seg, int B, int64_t i) {
+    int lo = 0, hi = B;                                          // the last b in [0, B) with seg[b] <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seg[mid] <= i) lo = mid; else hi = mid;
+    }
+    return seg[lo];
+}
+
+// pass 3: scatter the positives in index order, transformed.  RAGGED: out_idx counts from the first row of the query's own segment.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void scatter_pos_kernel(const float* __restrict__ logits, const float* __restrict__ queries, int64_t Q,
                                                           float thr, const int* __restrict__ offsets, PostXform t,
-                                                          float* __restrict__ out_pts, int64_t* __restrict__ out_idx) {
+                                                          float* __restrict__ out_pts, int64_t* __restrict__ out_idx,
+                                                          const int64_t* __restrict__ seg, int B) {
     __shared__ int wave_base[4];
     const int64_t base = (int64_t)blockIdx.x * CB;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -107,11 +119,30 @@ __global__ __launch_bounds__(256) void scatter_pos_kernel(const float* __restric
         if (pos) {
             const int64_t o = (int64_t)running + wb + before;
             xform_point(t, queries[i * 3], queries[i * 3 + 1], queries[i * 3 + 2], out_pts + o * 3);
-            if (out_idx) out_idx[o] = i;
+            if (out_idx) out_idx[o] = RAGGED ? i - segment_start(seg, B, i) : i;
         }
         running += sub_total;
         __syncthreads();
     }
+}
+
+// A flat order-preserving compaction keeps every segment contiguous, so the segment boundaries of the output are the numbers of
+// positives in front of the input boundaries: the scanned count of the boundary's 1024-query block plus the positives of the block's
+// part in front of it.  One wave per boundary b <= B: rows from seg[B] on belong to no segment (a buffer sized for the worst case) and
+// are not counted, though the scatter still writes their positives behind out_offsets[B].
+__global__ __launch_bounds__(256) void ragged_out_offsets_kernel(const float* __restrict__ logits, int64_t Q, float thr,
+                                                                 const int* __restrict__ scanned, const int64_t* __restrict__ total,
+                                                                 const int64_t* __restrict__ seg, int B, int64_t* __restrict__ out_offsets) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b > B) return;
+    int64_t e = seg[b];
+    e = e < 0 ? 0 : e;
+    if (e >= Q) { if (lane == 0) out_offsets[b] = *total; return; }              // nothing behind the boundary: the scan's total
+    const int64_t blk = e / CB;
+    int c = 0;
+    for (int64_t i = blk * CB + lane; i < e; i += 64) c += logits[i] > thr ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) out_offsets[b] = (int64_t)scanned[blk] + c;
 }
 
 __global__ void xform_points_kernel(const float* __restrict__ in, int64_t n, PostXform t, float* __restrict__ out) {
@@ -120,10 +151,21 @@ __global__ void xform_points_kernel(const float* __restrict__ in, int64_t n, Pos
 }
 
 // ---- Chamfer: sum_i min_j ||a_i - b_j||  (fp64), b staged through LDS in tiles of 1024 points
+// RAGGED (grid.y = sample): a / b are the samples' rows concatenated, a_off / b_off their [B + 1] row offsets, and the sample's sum goes to
+// sum[sample * 2]; an empty side leaves it at its zero
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void nn_dist_sum_kernel(const float* __restrict__ a, int64_t na, const float* __restrict__ b, int64_t nb,
-                                                          double* __restrict__ sum) {
+                                                          double* __restrict__ sum, const int64_t* __restrict__ a_off,
+                                                          const int64_t* __restrict__ b_off) {
     __shared__ double sb[3][1024];
     __shared__ double red[4];
+    if constexpr (RAGGED) {
+        const int s = blockIdx.y;
+        const int64_t a0 = a_off[s], b0 = b_off[s];
+        na = a_off[s + 1] - a0; nb = b_off[s + 1] - b0;
+        if (nb <= 0 || (int64_t)blockIdx.x * 256 >= na) return;
+        a += a0 * 3; b += b0 * 3; sum += (int64_t)s * 2;
+    }
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double ax = 0, ay = 0, az = 0;
     if (i < na) { ax = a[i * 3]; ay = a[i * 3 + 1]; az = a[i * 3 + 2]; }
@@ -200,7 +242,28 @@ int post_occupied_points(const float* logits, const float* queries, int64_t Q, c
     const PostXform t = make_xform(pc_range_host, aniso, iso, view_cone);
     hipLaunchKernelGGL(count_pos_kernel, dim3(nblocks), dim3(256), 0, st, logits, Q, thr, scratch);
     hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, st, scratch, nblocks, out_count);
-    hipLaunchKernelGGL(scatter_pos_kernel, dim3(nblocks), dim3(256), 0, st, logits, queries, Q, thr, scratch, t, out_pts, out_idx);
+    hipLaunchKernelGGL(scatter_pos_kernel<false>, dim3(nblocks), dim3(256), 0, st, logits, queries, Q, thr, scratch, t, out_pts, out_idx,
+                       (const int64_t*)nullptr, 0);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+int post_occupied_points_ragged(const float* logits, const float* queries, const int64_t* in_offsets, int B, int64_t T,
+                                const double* pc_range_host, int aniso, int iso, int view_cone, float thr, float* out_pts, int64_t* out_idx,
+                                int64_t* out_offsets, int* scratch, hipStream_t st) {
+    RALD_CHECK(in_offsets && out_offsets && pc_range_host && B >= 1 && B <= 65535 && T >= 0, "post_occupied_points_ragged: bad argument");
+    RALD_CHECK(T <= (int64_t)1 << 30, "post_occupied_points_ragged: too many queries");
+    if (T == 0) { RALD_HIP(hipMemsetAsync(out_offsets, 0, (size_t)(B + 1) * sizeof(int64_t), st)); return 0; }
+    RALD_CHECK(logits && queries && out_pts && scratch && (uintptr_t)scratch % 8 == 0, "post_occupied_points_ragged: null or unaligned pointer");
+    const int nblocks = (int)((T + CB - 1) / CB);
+    const PostXform t = make_xform(pc_range_host, aniso, iso, view_cone);
+    hipLaunchKernelGGL(count_pos_kernel, dim3(nblocks), dim3(256), 0, st, logits, T, thr, scratch);
+    int64_t* total = reinterpret_cast<int64_t*>(scratch + ((nblocks + 1) & ~1));          // inside the 8 spare ints of post_scratch_ints
+    hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, st, scratch, nblocks, total);
+    hipLaunchKernelGGL(ragged_out_offsets_kernel, dim3((B + 4) / 4), dim3(256), 0, st, logits, T, thr, scratch, total, in_offsets, B,
+                       out_offsets);
+    hipLaunchKernelGGL(scatter_pos_kernel<true>, dim3(nblocks), dim3(256), 0, st, logits, queries, T, thr, scratch, t, out_pts, out_idx,
+                       in_offsets, B);
     RALD_HIP(hipGetLastError());
     return 0;
 }
@@ -217,8 +280,26 @@ int post_transform_points(const float* in, int64_t n, const double* pc_range_hos
 int post_chamfer_sums(const float* a, int64_t na, const float* b, int64_t nb, double* sums, hipStream_t st) {
     RALD_CHECK(a && b && sums && na >= 1 && nb >= 1, "post_chamfer_sums: empty point set");
     RALD_HIP(hipMemsetAsync(sums, 0, 16, st));
-    hipLaunchKernelGGL(nn_dist_sum_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, a, na, b, nb, sums);
-    hipLaunchKernelGGL(nn_dist_sum_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, b, nb, a, na, sums + 1);
+    const int64_t* none = nullptr;
+    hipLaunchKernelGGL(nn_dist_sum_kernel<false>, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, a, na, b, nb, sums, none, none);
+    hipLaunchKernelGGL(nn_dist_sum_kernel<false>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, b, nb, a, na, sums + 1, none, none);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+// sums [B][2] as post_chamfer_sums per sample; max_a / max_b: host upper bounds of the longest segment of either side (they size the grids).
+// The offsets live on the device and are not read back, so the bounds are trusted: one that is too small gives PARTIAL sums (the rows
+// behind it have no workgroup) and no error.  The inference tail passes bounds that hold by construction (a frame's query count, the refine pass's aug_num, the surface's point count).
+int post_chamfer_sums_ragged(const float* a, const int64_t* a_off, const float* b, const int64_t* b_off, int B, int64_t max_a, int64_t max_b,
+                             double* sums, hipStream_t st) {
+    RALD_CHECK(a_off && b_off && sums && B >= 1 && B <= 65535 && max_a >= 0 && max_b >= 0, "post_chamfer_sums_ragged: bad argument");
+    RALD_CHECK(max_a < (int64_t)1 << 38 && max_b < (int64_t)1 << 38, "post_chamfer_sums_ragged: point sets too large");
+    RALD_HIP(hipMemsetAsync(sums, 0, (size_t)B * 16, st));
+    if (max_a == 0 || max_b == 0) return 0;
+    RALD_CHECK(a && b, "post_chamfer_sums_ragged: null pointer");
+    const int64_t zero = 0;
+    hipLaunchKernelGGL(nn_dist_sum_kernel<true>, dim3((unsigned)((max_a + 255) / 256), B), dim3(256), 0, st, a, zero, b, zero, sums, a_off, b_off);
+    hipLaunchKernelGGL(nn_dist_sum_kernel<true>, dim3((unsigned)((max_b + 255) / 256), B), dim3(256), 0, st, b, zero, a, zero, sums + 1, b_off, a_off);
     RALD_HIP(hipGetLastError());
     return 0;
 }

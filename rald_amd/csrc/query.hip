@@ -165,6 +165,67 @@ __global__ void refine_kernel(RefineArgs a) {
     else for (int c = 0; c < 3; ++c) a.out[j * 3 + c] = p[c];
 }
 
+// ---- the refine pass of a ragged batch: sample b owns rows offsets[b] .. offsets[b+1] - 1 of pred and its own rows of the draws
+struct RefineRaggedArgs {
+    const float* pred; const int64_t* offsets; int64_t aug_num;
+    const int64_t* sel; const double* u_sel; const int64_t* scales; const double* u;     // [B][aug_num] (u: [B][aug_num][3])
+    double lo[3], hi[3], voxel[3];
+    QRange q; int aniso, iso, normalise;
+    float* out; const int64_t* out_offsets;
+};
+
+// out_offsets[b] = aug_num * (samples before b that have a point): a sample without points gets no refined query.  One workgroup.
+__global__ __launch_bounds__(1024) void refine_offsets_kernel(const int64_t* __restrict__ offsets, int B, int64_t aug_num,
+                                                              int64_t* __restrict__ out_offsets) {
+    __shared__ int sh[1024];
+    int carry = 0;
+    if (threadIdx.x == 0) out_offsets[0] = 0;
+    for (int base = 0; base < B; base += 1024) {
+        const int b = base + threadIdx.x;
+        sh[threadIdx.x] = (b < B && offsets[b + 1] > offsets[b]) ? 1 : 0;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {                      // Hillis-Steele inclusive scan
+            const int t = threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += t;
+            __syncthreads();
+        }
+        if (b < B) out_offsets[b + 1] = (int64_t)(carry + sh[threadIdx.x]) * aug_num;
+        const int blk_total = sh[1023];
+        __syncthreads();
+        carry += blk_total;
+    }
+}
+
+// refine_kernel's row j for sample blockIdx.y; the selected point is sel[b][g], or floor(u_sel[b][g] * N) (float64, at most N - 1)
+__global__ void refine_ragged_kernel(RefineRaggedArgs a) {
+#pragma clang fp contract(off)
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    const int64_t first = a.offsets[b], N = a.offsets[b + 1] - first;
+    if (j >= a.aug_num || N <= 0) return;
+    const float* pred = a.pred + first * 3;
+    float* out = a.out + (a.out_offsets[b] + j) * 3;
+    const int64_t n_pred = N < a.aug_num ? N : a.aug_num;
+    float p[3];
+    if (j < n_pred) {                                             // the helper points themselves come first
+        for (int c = 0; c < 3; ++c) p[c] = pred[j * 3 + c];
+    } else {
+        const int64_t g = j - n_pred, d = (int64_t)b * a.aug_num + g;
+        int64_t s = a.sel ? a.sel[d] : (int64_t)floor(a.u_sel[d] * (double)N);
+        s = s < 0 ? 0 : (s > N - 1 ? N - 1 : s);                  // u * N can round up to N; an index outside the sample reads nothing foreign
+        const double sc = (double)a.scales[d];
+        for (int c = 0; c < 3; ++c) {
+            const double bias = (a.u[d * 3 + c] * 2 - 1) * (a.voxel[c] * sc);
+            double v = (double)pred[s * 3 + c] + bias;
+            v = fmin(fmax(v, a.lo[c]), a.hi[c]);                  // np.clip
+            p[c] = (float)v;                                      // assignment into the float32 result
+        }
+    }
+    if (a.normalise) norm_point_f32(a.q, a.aniso, a.iso, p, out);
+    else for (int c = 0; c < 3; ++c) out[c] = p[c];
+}
+
 // ---- launchers ---------------------------------------------------------------------------------
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st) {
     RALD_CHECK(n >= 0 && (aniso || iso), "query_uniform: n >= 0 and one of norm_anisotropy / norm_isotropy expected");
@@ -209,6 +270,23 @@ int query_refine(const float* pred, int64_t n_pred, int64_t aug_num, const int64
     for (int c = 0; c < 3; ++c) { a.lo[c] = pc_range[c]; a.hi[c] = pc_range[3 + c]; a.voxel[c] = voxel[c]; }
     a.q = make_qrange(pc_range); a.aniso = aniso; a.iso = iso; a.normalise = normalise; a.out = out;
     hipLaunchKernelGGL(refine_kernel, dim3((unsigned)((aug_num + 255) / 256)), dim3(256), 0, st, a);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+int query_refine_ragged(const float* points, const int64_t* offsets, int B, int64_t aug_num, const int64_t* sel, const double* u_sel,
+                        const int64_t* scales, const double* u, const double* pc_range, const double* voxel, int aniso, int iso, int normalise,
+                        float* out, int64_t* out_offsets, hipStream_t st) {
+    RALD_CHECK(offsets && out_offsets && pc_range && voxel && B >= 1 && B <= 65535 && aug_num >= 0, "query_refine_ragged: bad argument");
+    RALD_CHECK(aug_num == 0 || (out && (sel || u_sel) && scales && u), "query_refine_ragged: null pointer (points may be null only for an empty batch)");
+    hipLaunchKernelGGL(refine_offsets_kernel, dim3(1), dim3(1024), 0, st, offsets, B, aug_num, out_offsets);
+    RALD_HIP(hipGetLastError());
+    if (aug_num == 0) return 0;
+    RefineRaggedArgs a;
+    a.pred = points; a.offsets = offsets; a.aug_num = aug_num; a.sel = sel; a.u_sel = u_sel; a.scales = scales; a.u = u;
+    for (int c = 0; c < 3; ++c) { a.lo[c] = pc_range[c]; a.hi[c] = pc_range[3 + c]; a.voxel[c] = voxel[c]; }
+    a.q = make_qrange(pc_range); a.aniso = aniso; a.iso = iso; a.normalise = normalise; a.out = out; a.out_offsets = out_offsets;
+    hipLaunchKernelGGL(refine_ragged_kernel, dim3((unsigned)((aug_num + 255) / 256), B), dim3(256), 0, st, a);
     RALD_HIP(hipGetLastError());
     return 0;
 }

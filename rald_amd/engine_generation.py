@@ -5,8 +5,9 @@ inference tail (:250-322: query generation, helper points, refine pass, Chamfer)
 Data loading and PLY writing are out of scope."""
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import distributed as D
@@ -79,6 +80,177 @@ def infer_point_cloud(vae, sampled_tokens: torch.Tensor, args, helper_points: Op
         gt = PP.inverse_norm_points(surface.to(dev), lidar.pc_range, aniso, iso)                 # :290
         cd = PP.cal_metrics(pred, PP.polar2cartesian(gt) if view_cone else gt)                   # :320
     return {"pred": pred, "cd": cd, "n_queries": n_queries}
+
+
+def offsets_from_lengths(lengths: Sequence[int]) -> List[int]:
+    """Host offsets [B+1] of a ragged layout from its B segment lengths (offsets[0] = 0; a length of 0 is an empty segment)."""
+    out = [0]
+    for n in lengths:
+        n = int(n)
+        if n < 0:
+            raise ValueError("segment lengths must be non-negative")
+        out.append(out[-1] + n)
+    return out
+
+
+def _check_batch_inputs(sampled_tokens, helper_points, surfaces) -> List[Optional[torch.Tensor]]:
+    """The shape and length rules of infer_point_clouds, all on the host: raises ValueError before any GPU work."""
+    if not isinstance(sampled_tokens, torch.Tensor) or sampled_tokens.dim() != 3:
+        raise ValueError("sampled_tokens must be [B, M, C]")
+    B = sampled_tokens.shape[0]
+    if B < 1:
+        raise ValueError("sampled_tokens must hold at least one frame")
+    helpers: List[Optional[torch.Tensor]] = [None] * B
+    if helper_points is not None:
+        if isinstance(helper_points, torch.Tensor) or len(helper_points) != B:
+            raise ValueError(f"helper_points must be a list of {B} tensors [H_b, 3], one per frame")
+        for b, h in enumerate(helper_points):
+            if not isinstance(h, torch.Tensor) or h.dim() != 2 or h.shape[1] != 3:
+                raise ValueError(f"helper_points[{b}] must be a tensor [H_b, 3]")
+        helpers = list(helper_points)
+    if surfaces is not None:
+        if not isinstance(surfaces, torch.Tensor) or surfaces.dim() != 3 or surfaces.shape[2] != 3:
+            raise ValueError("surfaces must be [B, P, 3]")
+        if surfaces.shape[0] != B:
+            raise ValueError(f"surfaces holds {surfaces.shape[0]} frames, sampled_tokens {B}")
+        if surfaces.shape[1] < 1:
+            raise ValueError("surfaces must hold at least one point per frame")
+    return helpers
+
+
+def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tensor]], B: int):
+    """The ragged query sets of the first decode: every frame = the shared grid + its own helper points.
+    grid [n_cap,3]; n_grid = n_cap as an int, or (use_cart_query) a device int64 [1] count of the valid grid rows.
+    -> (queries [T_cap,3], offsets int64 [B+1] on the device, max_per_sample)."""
+    dev = grid.device
+    n_cap = grid.shape[0]
+    h_len = [0 if h is None else h.shape[0] for h in helpers]
+    parts = [h.to(dev, torch.float32) for h in helpers if h is not None and h.shape[0]]
+    if isinstance(n_grid, int):
+        rows = []
+        for h in helpers:
+            rows.append(grid)
+            if h is not None and h.shape[0]:
+                rows.append(h.to(dev, torch.float32))
+        offsets = torch.tensor(offsets_from_lengths([n_cap + n for n in h_len]), dtype=torch.int64, device=dev)
+        return torch.cat(rows, dim=0), offsets, n_cap + max(h_len)
+    # the FoV filter leaves a number of grid rows only the device knows: gather every frame's rows out of [grid | all helper points]
+    # by index arithmetic on the device (row r of frame b is grid row r below the count, else the frame's helper row r - count)
+    h_off = torch.tensor(offsets_from_lengths(h_len), dtype=torch.int64, device=dev)
+    offsets = torch.arange(B + 1, dtype=torch.int64, device=dev) * n_grid + h_off
+    source = torch.cat([grid] + parts, dim=0) if parts else grid
+    t_cap = B * n_cap + sum(h_len)
+    pos = torch.arange(t_cap, dtype=torch.int64, device=dev)
+    frame = (torch.searchsorted(offsets, pos, right=True) - 1).clamp_(0, B - 1)
+    local = pos - offsets[frame]
+    src = torch.where(local < n_grid, local, n_cap + h_off[frame] + (local - n_grid)).clamp_(0, source.shape[0] - 1)
+    return source[src], offsets, n_cap + max(h_len)
+
+
+@torch.no_grad()
+def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
+                              rng: Optional[torch.Generator] = None, draws: Optional[dict] = None):
+    """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
+    device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
+    read to the host and the device is not synchronised."""
+    return _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws)[:3]
+
+
+def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws):
+    """The batched tail -> (points, offsets, cd or None, n_queries int64 [B]) on the device: what infer_point_clouds_device returns plus
+    the frames' query counts, which infer_point_clouds copies to the host with the rest."""
+    helpers = _check_batch_inputs(sampled_tokens, helper_points, surfaces)
+    B = sampled_tokens.shape[0]
+    lidar, inf = args.dataset.lidar, args.eval.inference
+    aniso, iso = lidar.norm_anisotropy, lidar.norm_isotropy
+    if not (aniso or iso):
+        raise ValueError("one of norm_anisotropy / norm_isotropy is required")
+    dev = sampled_tokens.device
+    n = int(inf.num_query_points)
+    refine = bool(_get(inf, "refine_query", False))
+    aug_num = int(inf.refine_query_aug_num) if refine else 0
+    host_draws = draws is None and rng is None
+    if draws is None and rng is not None:
+        draws = QP.draw_tail_randoms(B, n, aug_num, int(inf.refine_query_scale) if refine else 1, rng)
+    u3n = torch.from_numpy(np.random.random_sample((3, n))).to(dev) if host_draws else draws["u3n"]
+    if u3n.dtype != torch.float64 or tuple(u3n.shape) != (3, n) or not u3n.is_cuda:
+        raise ValueError(f"draws['u3n'] must be a float64 tensor [3, {n}] on the GPU")
+    if _get(args.eval, "use_cart_query", False):                                                   # :251-256
+        grid, n_grid = QP.cart_queries_from_uniform_device(u3n, args)
+    else:
+        grid, n_grid = QP.uniform_queries_from(u3n, lidar.pc_range, aniso, iso), n                 # :258
+    if not _get(inf, "query_helper", False):
+        helpers = [None] * B
+    queries, offsets, longest = _batch_queries(grid, n_grid, helpers, B)                           # :264-271
+    logits = vae.decode_ragged(sampled_tokens, queries, offsets, longest)                          # :275
+    pts, p_off, _ = PP.occupied_points_ragged(logits, queries, offsets, lidar.pc_range, aniso, iso, view_cone_mode=False)   # :283-289
+    n_queries = offsets[1:] - offsets[:-1]
+    if refine:
+        if host_draws:
+            draws = _numpy_refine_draws(p_off, aug_num, int(inf.refine_query_scale), dev)
+        refined, r_off = QP.refine_queries_ragged(pts, p_off, args, draws)                         # :292-297
+        logits_r = vae.decode_ragged(sampled_tokens, refined, r_off, aug_num)                      # :300
+        pts, p_off, _ = PP.occupied_points_ragged(logits_r, refined, r_off, lidar.pc_range, aniso, iso, view_cone_mode=False)   # :304-310
+        n_queries = n_queries + (r_off[1:] - r_off[:-1])
+        longest = aug_num
+    view_cone = bool(_get(lidar, "view_cone_mode", False))
+    if view_cone:
+        pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
+    cd = None
+    if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
+        P = surfaces.shape[1]
+        gt = PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso)   # :290
+        if view_cone:
+            gt = PP.polar2cartesian(gt)
+        gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
+        cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, longest, P)                             # :320
+    return pts, p_off, cd, n_queries
+
+
+def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
+    """The refine draws of every frame from numpy's global RNG, frame by frame in the reference's order (query_helper.py:3-42): the
+    one host read of the numpy mode - the frames' positive counts - happens here."""
+    counts = (p_off[1:] - p_off[:-1]).cpu().numpy()
+    B = len(counts)
+    sel = np.zeros((B, aug_num), np.int64)
+    scales = np.ones((B, aug_num), np.int64)
+    u = np.zeros((B, aug_num, 3), np.float64)
+    for b, N in enumerate(int(c) for c in counts):
+        gen = aug_num - N
+        if N > 0 and gen > 0:
+            sel[b, :gen] = np.random.choice(N, size=gen, replace=True)
+            scales[b, :gen] = np.random.choice(np.arange(scale, step=1) + 1, size=gen)
+            u[b, :gen] = np.random.rand(gen, 3)
+    return {"sel": torch.from_numpy(sel).to(dev), "scales": torch.from_numpy(scales).to(dev), "u_bias": torch.from_numpy(u).to(dev)}
+
+
+@torch.no_grad()
+def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
+                       rng: Optional[torch.Generator] = None, draws: Optional[dict] = None) -> Dict[str, object]:
+    """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
+    one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
+    positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
+    positives] -> cartesian if view_cone_mode -> Chamfer distance per frame against `surfaces` [B,P,3] unless skip_eval_metric.
+    The frames' sizes differ from the first step on (helper points, positives); every step takes them from device offsets.
+
+    sampled_tokens [B,M,C]; helper_points: None or a list of B tensors [H_b,3] (normalised; H_b may be 0); random numbers from
+    `draws` (QP.draw_tail_randoms) or a device generator `rng` - then the ONLY host read is the one at the end, which copies the
+    offsets, the query counts and the Chamfer values together.  `rng=None` with `draws=None` replays numpy's global RNG in the
+    reference's order - the grid once, then frame by frame the refine pass's three draws - and passes explicit selected indices;
+    that mode reads the B positive counts to the host once more, before it draws (numpy's draw sizes depend on them).
+
+    A frame whose first decode has no positive gets no refine queries and ends with an empty prediction and cd = inf; the
+    single-frame infer_point_cloud raises there.  Shape and length errors raise ValueError before any GPU work.
+    Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
+    'n_queries': list of B ints}."""
+    pts, off, cd, nq = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws)
+    B = sampled_tokens.shape[0]
+    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []))
+    host = packed.cpu().tolist()                                                                    # the one host read
+    o = [int(v) for v in host[:B + 1]]
+    return {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
+            "cd": host[2 * B + 1:] if cd is not None else None,
+            "n_queries": [int(v) for v in host[B + 1:2 * B + 1]]}
 
 
 @torch.no_grad()

@@ -86,6 +86,14 @@ class KLAutoEncoder(_HipBacked):
         h = self._handle()
         return h.decode_queries(self._context(x), queries).unsqueeze(-1)
 
+    def decode_ragged(self, x, queries, offsets, max_per_sample):
+        """decode for query sets of different sizes: x [B,M,latent_dim], queries [T,3] = the B sets concatenated, offsets int64 [B+1]
+        on the device, max_per_sample = a host upper bound of the longest set (too small a bound leaves the rows behind it undecoded,
+        with no error) -> logits [T].  Same memoised context as decode; set b's logits are row b of decode on the same batch x with
+        its queries (not bitwise those of decode(x[b:b+1], ...): the latent stack picks its engines by batch rows)."""
+        h = self._handle()
+        return h.decode_queries_ragged(self._context(x), queries, offsets, max_per_sample)
+
     def forward(self, pc, queries):
         # Route like EDMPrecond.forward: model.train() + grad mode + trainable parameters = the stage-1 training step
         # (engine_ae.py:51, :73-104); eval() / no_grad = the inference path below, unchanged.

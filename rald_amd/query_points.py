@@ -16,7 +16,7 @@ from typing import Optional, Sequence, Union
 import numpy as np
 import torch
 
-from ._handles import _doubles, _f32c, _need_cuda, _opt, _stream
+from ._handles import _doubles, _f32c, _need_cuda, _opt, _ragged_batch, _stream
 from ._lib import check, lib
 
 Rng = Optional[torch.Generator]
@@ -61,6 +61,33 @@ def uniform_queries(n: int, pc_range, norm_anisotropy: bool, norm_isotropy: bool
     check(lib().rald_query_uniform(u.data_ptr(), n, _doubles(pc_range, 6, "pc_range"), int(norm_anisotropy), int(norm_isotropy),
                                    out.data_ptr(), _stream()))
     return out
+
+
+def uniform_queries_from(u3n: torch.Tensor, pc_range, norm_anisotropy: bool, norm_isotropy: bool) -> torch.Tensor:
+    """uniform_queries on given uniforms: u3n float64 [3,n] on the device (numpy's draw order) -> float32 [n,3]."""
+    _need_cuda(u3n, "u3n")
+    u3n = u3n.contiguous()
+    n = u3n.shape[1]
+    out = torch.empty(n, 3, device=u3n.device, dtype=torch.float32)
+    check(lib().rald_query_uniform(u3n.data_ptr(), n, _doubles(pc_range, 6, "pc_range"), int(norm_anisotropy), int(norm_isotropy),
+                                   out.data_ptr(), _stream()))
+    return out
+
+
+def cart_queries_from_uniform_device(u3n: torch.Tensor, args):
+    """generate_cart_query_points on given uniforms, without its readback: -> (queries float32 [n,3], count int64 [1]), both on the
+    device; the first `count` rows are the queries inside the field of view, in draw order."""
+    _need_cuda(u3n, "u3n")
+    u3n = u3n.contiguous()
+    n, dev = u3n.shape[1], u3n.device
+    lidar = args.dataset.lidar
+    out = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    cnt = torch.zeros(1, device=dev, dtype=torch.int64)
+    scratch = torch.empty(lib().rald_post_scratch_bytes(n), device=dev, dtype=torch.uint8)
+    check(lib().rald_query_uniform_cart(u3n.data_ptr(), n, _doubles(lidar.pc_range_cart, 6, "pc_range_cart"), _doubles(lidar.pc_range, 6, "pc_range"),
+                                        int(lidar.norm_anisotropy), int(lidar.norm_isotropy), out.data_ptr(), cnt.data_ptr(),
+                                        scratch.data_ptr(), _stream()))
+    return out, cnt
 
 
 def generate_cart_query_points(args, device=None, rng: Rng = None) -> torch.Tensor:
@@ -132,3 +159,59 @@ def refine_queries(pred_points: torch.Tensor, args, rng: Rng = None) -> torch.Te
     inf, lidar = args.eval.inference, args.dataset.lidar
     return aug_query_helper(pred_points, int(inf.refine_query_aug_num), lidar.pc_range, lidar.voxel_size, inf.refine_query_scale, rng,
                             norm=(lidar.norm_anisotropy, lidar.norm_isotropy))
+
+
+def draw_tail_randoms(B: int, n_grid: int, aug_num: int, aug_bias_scale: int, generator: torch.Generator) -> dict:
+    """Every random number the inference tail of a batch of B frames consumes, drawn from a DEVICE generator before anything is
+    decoded: 'u3n' float64 [3,n_grid] (the query grid the frames share), and per frame the refine draws 'u_sel' float64 [B,aug_num]
+    in [0,1) (row g selects point min(floor(u_sel * N_b), N_b - 1) once N_b is known - on the device), 'scales' int64 [B,aug_num]
+    in 1 .. aug_bias_scale and 'u_bias' float64 [B,aug_num,3]."""
+    if generator is None or torch.device(generator.device).type != "cuda":
+        raise ValueError("draw_tail_randoms needs a torch.Generator of the GPU")
+    dev = generator.device
+    B, n_grid, aug_num = int(B), int(n_grid), int(aug_num)
+    return {"u3n": torch.rand((3, n_grid), dtype=torch.float64, device=dev, generator=generator),
+            "u_sel": torch.rand((B, aug_num), dtype=torch.float64, device=dev, generator=generator),
+            "scales": torch.randint(1, int(aug_bias_scale) + 1, (B, aug_num), device=dev, generator=generator, dtype=torch.int64),
+            "u_bias": torch.rand((B, aug_num, 3), dtype=torch.float64, device=dev, generator=generator)}
+
+
+def aug_query_helper_ragged(points: torch.Tensor, offsets: torch.Tensor, aug_num: int, pc_range, voxel_size, draws: dict,
+                            norm: Optional[Sequence[bool]] = None):
+    """aug_query_helper for a ragged batch: points [T,3], offsets int64 [B+1] on the device, draws = 'scales' [B,aug_num],
+    'u_bias' [B,aug_num,3] and either 'sel' int64 [B,aug_num] or 'u_sel' float64 [B,aug_num] (draw_tail_randoms) ->
+    (queries [B*aug_num,3], out_offsets int64 [B+1]): a frame with points gets aug_num rows, a frame without points gets none (the
+    single-frame call raises there), the frames packed one behind the other.  No host read."""
+    _need_cuda(points, "points")
+    points = _f32c(points).reshape(-1, 3)
+    dev = points.device
+    B, aug_num = _ragged_batch(offsets, "offsets"), int(aug_num)
+    sel, u_sel = draws.get("sel"), draws.get("u_sel")
+    if sel is None and u_sel is None:
+        raise ValueError("draws needs 'sel' or 'u_sel'")
+
+    def field(t, dtype, shape, name):
+        if t is None:
+            return None
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_cuda:
+            raise ValueError(f"draws[{name!r}] must be a {dtype} tensor of shape {shape} on the GPU")
+        return t.contiguous()
+    sel = field(sel, torch.int64, (B, aug_num), "sel")
+    u_sel = field(u_sel, torch.float64, (B, aug_num), "u_sel") if sel is None else None
+    scales = field(draws["scales"], torch.int64, (B, aug_num), "scales")
+    u_bias = field(draws["u_bias"], torch.float64, (B, aug_num, 3), "u_bias")
+    out = torch.empty(B * aug_num, 3, device=dev, dtype=torch.float32)
+    out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    aniso, iso = (bool(norm[0]), bool(norm[1])) if norm is not None else (False, False)
+    check(lib().rald_query_refine_ragged(points.data_ptr(), offsets.data_ptr(), B, aug_num, _opt(sel), _opt(u_sel), scales.data_ptr(),
+                                         u_bias.data_ptr(), _doubles(pc_range, 6, "pc_range"), _doubles(voxel_size, 3, "voxel_size"),
+                                         int(aniso), int(iso), int(norm is not None), out.data_ptr(), out_offsets.data_ptr(), _stream()))
+    return out, out_offsets
+
+
+def refine_queries_ragged(points: torch.Tensor, offsets: torch.Tensor, args, draws: dict):
+    """refine_queries for a ragged batch of positive (un-normalised polar) points -> (queries [B*refine_query_aug_num,3] normalised,
+    out_offsets int64 [B+1]) ready for ``vae.decode_ragged``."""
+    inf, lidar = args.eval.inference, args.dataset.lidar
+    return aug_query_helper_ragged(points, offsets, int(inf.refine_query_aug_num), lidar.pc_range, lidar.voxel_size, draws,
+                                   norm=(lidar.norm_anisotropy, lidar.norm_isotropy))
