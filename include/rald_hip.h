@@ -598,6 +598,21 @@ int rald_op_attention_bwd(const void* Q, int64_t ldq, int64_t strideQ, const voi
 int rald_op_gemm_resid_ln(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* x, void* h_bf16,
                           const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps,
                           int32_t M, int32_t K, void* stream);
+/* The residual projection as the latent stacks run it, with every field of its argument block reachable (tests): bf16 operands
+ * (A_bf16, W_bf16) or MXFP8 ones (A8 / SA, W8 / SW: e4m3 + e8m0 scales [..][K/32]; the other form's pointers null); h_bf16 or the
+ * MXFP8 form h8 [M][512] / hs [M][16]; g / b null = no LayerNorm (route 0 only); strideW != 0: rows [i*w_rows, (i+1)*w_rows)
+ * multiply W + i*strideW; nt_io: non-temporal residual / output traffic of the fused kernel.
+ * route 0 = the dispatcher the models call (split-K slabs through `scratch` + reduction, the fused kernel, or GEMM + LayerNorm, by M and K);
+ * route 1 = the fused kernel directly.  scratch: at least 4 * M * 512 * 4 bytes when route 0 splits K (K >= 2048 and M <= 4096). */
+int rald_op_resid_gemm_ln(const void* A_bf16, const void* A8, const void* SA, int64_t lda, const void* W_bf16, const void* W8, const void* SW,
+                          int64_t ldw, int64_t strideW, int32_t w_rows, const float* bias, float* x, void* h_bf16, void* h8, void* hs,
+                          const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps, int32_t M,
+                          int32_t K, int32_t nt_io, int32_t route, void* scratch, int64_t scratch_bytes, void* stream);
+/* The GEGLU projection (packed W rows and bias, as epilogue 3 of rald_op_gemm_nt) on bf16 or MXFP8 operands, into out_bf16 [M][ldc] or
+ * into the MXFP8 form out8 [M][ldc] / outs [M][N/64] that the MXFP8 residual GEMM reads (full 256x256 tiles only). */
+int rald_op_gemm_geglu_mx8out(const void* A_bf16, const void* A8, const void* SA, int64_t lda, const void* W_bf16, const void* W8, const void* SW,
+                              int64_t ldw, const float* bias_packed, void* out_bf16, void* out8, void* outs, int64_t ldc, int32_t M, int32_t N,
+                              int32_t K, void* stream);
 int rald_op_cast_bf16(const float* in, void* out_bf16, int64_t n, void* stream);
 /* Set-latent autoencoder training (KLAutoEncoder under autograd, engine_ae.py:33-104; rald_amd/csrc/ae_train.hip).  No float atomics:
  * reductions over rows go through a caller-owned scratch (16-byte aligned, _scratch_bytes(rows) bytes - pure host arithmetic) and are

@@ -346,6 +346,36 @@ def op_gemm_resid_ln(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, x: to
     return h
 
 
+def op_resid_gemm_ln(x: torch.Tensor, bias: torch.Tensor, M: int, K: int, A: Optional[torch.Tensor] = None, W: Optional[torch.Tensor] = None,
+                     A8: Optional[torch.Tensor] = None, SA: Optional[torch.Tensor] = None, W8: Optional[torch.Tensor] = None,
+                     SW: Optional[torch.Tensor] = None, h: Optional[torch.Tensor] = None, h8: Optional[torch.Tensor] = None,
+                     hs: Optional[torch.Tensor] = None, g: Optional[torch.Tensor] = None, b: Optional[torch.Tensor] = None, gstride: int = 0,
+                     rows_per_group: int = 1 << 30, add_one: float = 0.0, eps: float = 1e-5, strideW: int = 0, w_rows: int = 0, nt_io: int = 1,
+                     route: int = 0, scratch: Optional[torch.Tensor] = None, lda: Optional[int] = None, ldw: Optional[int] = None) -> None:
+    """x [M,512] f32 += A.W^T + bias in place, then h (bf16) or h8 / hs (MXFP8) = LN(x)*(add_one+g)+b, all into the caller's buffers.
+    Operands bf16 (A [M,K], W [groups?,512,K]) or MXFP8 (A8 / SA, W8 / SW); strideW / w_rows: one W per w_rows rows; g = None: no
+    LayerNorm (route 0).  route 0 = resid_gemm_ln, the dispatcher of the latent stacks (needs `scratch` where it splits K); route 1 = the
+    fused kernel gemm_resid_ln."""
+    a, w = (A, W) if A is not None else (A8, W8)
+    lda = a.stride(-2) if lda is None else lda
+    ldw = w.stride(-2) if ldw is None else ldw
+    check(lib().rald_op_resid_gemm_ln(_opt(A), _opt(A8), _opt(SA), lda, _opt(W), _opt(W8), _opt(SW), ldw, strideW, w_rows, bias.data_ptr(),
+                                      x.data_ptr(), _opt(h), _opt(h8), _opt(hs), _opt(g), _opt(b), gstride, rows_per_group, add_one, eps, M, K,
+                                      nt_io, route, _opt(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size(), _stream()))
+
+
+def op_gemm_geglu_mx8out(bias_packed: torch.Tensor, M: int, N: int, K: int, A: Optional[torch.Tensor] = None, W: Optional[torch.Tensor] = None,
+                         A8: Optional[torch.Tensor] = None, SA: Optional[torch.Tensor] = None, W8: Optional[torch.Tensor] = None,
+                         SW: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None,
+                         outs: Optional[torch.Tensor] = None, ldc: Optional[int] = None) -> None:
+    """The GEGLU projection (W rows and bias packed as for op_gemm_nt's epilogue 3) on bf16 or MXFP8 operands, into `out` (bf16 [M, N/2]) or
+    into the MXFP8 form out8 [M, N/2] / outs [M, N/64] (the caller's buffers)."""
+    a, w = (A, W) if A is not None else (A8, W8)
+    ldc = (out if out is not None else out8).stride(-2) if ldc is None else ldc
+    check(lib().rald_op_gemm_geglu_mx8out(_opt(A), _opt(A8), _opt(SA), a.stride(-2), _opt(W), _opt(W8), _opt(SW), w.stride(-2),
+                                          bias_packed.data_ptr(), _opt(out), _opt(out8), _opt(outs), ldc, M, N, K, _stream()))
+
+
 def op_layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, gstride: int = 0, rows_per_group: int = 1,
                  add_one: float = 0.0, eps: float = 1e-5) -> torch.Tensor:
     M, D = x.shape

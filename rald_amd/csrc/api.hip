@@ -691,6 +691,56 @@ int rald_op_gemm_resid_ln(const void* A, int64_t lda, const void* W, int64_t ldw
     a.g = g; a.b = b; a.gstride = gstride; a.rows_per_group = rows_per_group; a.add_one = add_one; a.eps = eps; a.M = M; a.K = K;
     return gemm_resid_ln(a, (hipStream_t)stream);
 }
+int rald_op_resid_gemm_ln(const void* A_bf16, const void* A8, const void* SA, int64_t lda, const void* W_bf16, const void* W8, const void* SW,
+                          int64_t ldw, int64_t strideW, int32_t w_rows, const float* bias, float* x, void* h_bf16, void* h8, void* hs,
+                          const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps, int32_t M,
+                          int32_t K, int32_t nt_io, int32_t route, void* scratch, int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(route == 0 || route == 1, "rald_op_resid_gemm_ln: route is 0 (resid_gemm_ln, the product's choice) or 1 (gemm_resid_ln)");
+    RALD_CHECK(M > 0 && K > 0 && rows_per_group > 0, "rald_op_resid_gemm_ln: bad shape");
+    RALD_CHECK((A_bf16 != nullptr) != (A8 != nullptr), "rald_op_resid_gemm_ln: bf16 operands (A, W) or MXFP8 operands (A8, SA, W8, SW), not both");
+    RALD_CHECK(A8 ? (SA && W8 && SW && !W_bf16) : (W_bf16 && !SA && !W8 && !SW), "rald_op_resid_gemm_ln: operand pointers do not match the operand type");
+    RALD_CHECK(bias && x && (g != nullptr) == (b != nullptr), "rald_op_resid_gemm_ln: null argument");
+    RALD_CHECK(!(h_bf16 && h8) && (h8 != nullptr) == (hs != nullptr), "rald_op_resid_gemm_ln: h or h8 and hs, not both");
+    RALD_CHECK(!g || h_bf16 || h8, "rald_op_resid_gemm_ln: a LayerNorm needs h or h8 and hs");
+    RALD_CHECK(g || route == 0, "rald_op_resid_gemm_ln: only the dispatcher route runs without a LayerNorm");
+    RALD_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)h_bf16 % 16 == 0 && (uintptr_t)h8 % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)b % 16 == 0 &&
+               (uintptr_t)bias % 16 == 0 && gstride % 4 == 0, "rald_op_resid_gemm_ln: 16-byte alignment");
+    RALD_CHECK(strideW == 0 || w_rows > 0, "rald_op_resid_gemm_ln: per-group weights need w_rows > 0");
+    GemmLnArgs a;
+    a.A = (const bf16*)A_bf16; a.lda = lda; a.W = (const bf16*)W_bf16; a.ldw = ldw; a.bias = bias; a.x = x; a.h = (bf16*)h_bf16;
+    a.h8 = (unsigned char*)h8; a.hs = (unsigned char*)hs; a.nt_io = nt_io;
+    a.A8 = (const unsigned char*)A8; a.SA = (const unsigned char*)SA; a.W8 = (const unsigned char*)W8; a.SW = (const unsigned char*)SW;
+    a.g = g; a.b = b; a.gstride = gstride; a.rows_per_group = rows_per_group; a.add_one = add_one; a.eps = eps; a.M = M; a.K = K;
+    if (strideW != 0) { a.strideW = strideW; a.w_rows = w_rows; }
+    if (route == 1) return gemm_resid_ln(a, (hipStream_t)stream);
+    const int splits = splitk_for(M, K);
+    if (splits) {
+        RALD_CHECK(scratch && (uintptr_t)scratch % 16 == 0, "rald_op_resid_gemm_ln: split-K needs a 16-byte aligned scratch");
+        RALD_CHECK(scratch_bytes >= (int64_t)splits * M * 512 * 4, "rald_op_resid_gemm_ln: scratch too small for the split-K slabs");
+    }
+    // (the unfused route checks its operands in gemm_nt, which knows rows of 8 elements only)
+    RALD_CHECK(K % (A8 ? 128 : 64) == 0 && lda % 16 == 0 && ldw % 16 == 0 && lda >= K && ldw >= K, "rald_op_resid_gemm_ln: K and the leading dimensions");
+    return resid_gemm_ln(a, 512, (float*)scratch, (hipStream_t)stream);
+}
+int rald_op_gemm_geglu_mx8out(const void* A_bf16, const void* A8, const void* SA, int64_t lda, const void* W_bf16, const void* W8, const void* SW,
+                              int64_t ldw, const float* bias_packed, void* out_bf16, void* out8, void* outs, int64_t ldc, int32_t M, int32_t N,
+                              int32_t K, void* stream) {
+    RALD_CHECK((A_bf16 != nullptr) != (A8 != nullptr), "rald_op_gemm_geglu_mx8out: bf16 operands (A, W) or MXFP8 operands (A8, SA, W8, SW), not both");
+    RALD_CHECK(A8 ? (SA && W8 && SW && !W_bf16) : (W_bf16 && !SA && !W8 && !SW), "rald_op_gemm_geglu_mx8out: operand pointers do not match the operand type");
+    RALD_CHECK((out_bf16 != nullptr) != (out8 != nullptr) && (out8 != nullptr) == (outs != nullptr),
+               "rald_op_gemm_geglu_mx8out: a bf16 output or out8 and outs, not both");
+    RALD_CHECK(bias_packed && M > 0 && N > 0 && K > 0, "rald_op_gemm_geglu_mx8out: null bias or empty problem");
+    RALD_CHECK(!out8 || ((uintptr_t)out8 % 16 == 0 && ldc % 32 == 0), "rald_op_gemm_geglu_mx8out: out8 16-byte aligned, ldc a multiple of 32");
+    // (with out8 set C is never written; the product passes its bf16 buffer there, the test has none)
+    GemmArgs g = gemm_args((const bf16*)A_bf16, lda, (const bf16*)W_bf16, ldw, out_bf16 ? out_bf16 : out8, ldc, bias_packed, M, N, K);
+    g.out8 = (unsigned char*)out8; g.outs = (unsigned char*)outs;
+    if (!A8) return gemm_nt(g, EPI_GEGLU, (hipStream_t)stream);
+    Mx8Args a;
+    a.g = g;
+    a.A8 = (const unsigned char*)A8; a.SA = (const unsigned char*)SA; a.B8 = (const unsigned char*)W8; a.SB = (const unsigned char*)SW;
+    a.strideSA = 0; a.strideSB = 0;
+    return gemm_mx8(a, EPI_GEGLU, (hipStream_t)stream);
+}
 int64_t rald_op_ln_affine_bwd_scratch_bytes(int64_t rows) { return ln_affine_bwd_scratch_bytes(rows); }
 int rald_op_ln_affine_bwd(const float* x, const float* dh, const float* gamma, float eps, int64_t rows, float* dx_accum, void* dx_bf16_out,
                           float* dgamma_accum, float* dbeta_accum, void* scratch, int64_t scratch_bytes, void* stream) {

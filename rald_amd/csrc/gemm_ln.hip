@@ -526,6 +526,8 @@ int gemm_resid_ln(const GemmLnArgs& a, hipStream_t st) {
 }
 
 int resid_gemm_ln(const GemmLnArgs& a, int n, float* scratch, hipStream_t st) {
+    // (the batched fallback below runs M / w_rows whole groups; the product has M = B * n_latents)
+    RALD_CHECK(a.strideW == 0 || (a.w_rows > 0 && a.M % a.w_rows == 0), "resid_gemm_ln: per-group weights need M to be a multiple of w_rows");
     const int splits = splitk_for(a.M, a.K);
     if (n == 512 && splits && !a.A8 && !a.h8 && a.strideW == 0)
         return resid_splitk_ln(a.A, a.lda, a.W, a.ldw, a.bias, a.x, a.g ? a.h : nullptr, a.g, a.b, a.gstride, a.rows_per_group, a.add_one, a.eps,

@@ -22,8 +22,16 @@ def _ints(shape, lo, hi, seed):
     return torch.randint(lo, hi + 1, shape, generator=g).float()
 
 
+# one shape per engine of gemm_nt's ladder (wg128 = cdiv(M,128) cdiv(N,128), wg64 likewise, wg256 = (M/256)(N/256)):
+#   (1000, 1100, 192)   wg128 = 8 * 9 = 72 < 192, wg64 = 16 * 18 = 288 > 256: register-staged 64x64; ragged M and N
+#   (3000, 1028, 128)   wg128 = 24 * 9 = 216, M % 64 != 0: 128x128; the N % 8 == 4 tail
+#   (4096, 4096, 64), (2048, 8192, 192)   wg256 = 256: 256x256
+#   (1600, 2048, K)     wg128 = 13 * 16 = 208 <= 320, M % 64 == 0: 64x128 with 3 stages, nk = 1, 2, 4 (below, at, above stages - 1)
+#   (128, 128, 576), (64, 64, 1024)   wg64 <= 256: the 8-stage 64x64 ring with nk = 9 and 16
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (64, 64, 128), (256, 384, 512), (512, 512, 512),
-                                   (200, 132, 64), (8192, 512, 512), (1024, 4096, 512), (300, 1000, 1024)])
+                                   (200, 132, 64), (8192, 512, 512), (1024, 4096, 512), (300, 1000, 1024),
+                                   (1000, 1100, 192), (3000, 1028, 128), (4096, 4096, 64), (2048, 8192, 192),
+                                   (1600, 2048, 64), (1600, 2048, 128), (1600, 2048, 256), (128, 128, 576), (64, 64, 1024)])
 def test_gemm_exact_integers(H, M, N, K):
     A = _ints((M, K), -3, 3, 1).cuda()
     B = (_ints((N, K), -2, 2, 2) + (torch.arange(N) % 3 == 0).float()[:, None]).cuda()   # asymmetric

@@ -151,6 +151,8 @@ def test_c_abi_signatures_are_derived_from_the_header():
     assert S["rald_dit_sample"] == (I32, [P, P, I32, P, I32, F, F, F, P, P])
     assert S["rald_op_ae_encode_tables"] == (I32, [I32, I32, I32, I32, P, P])       # const float* const*, float* const*
     assert len(S["rald_op_attention_bwd"][1]) == 32
+    assert S["rald_op_resid_gemm_ln"] == (I32, [P, P, P, I64, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, I64, I32, F, F, I32, I32, I32, I32, P, I64, P])
+    assert S["rald_op_gemm_geglu_mx8out"] == (I32, [P, P, P, I64, P, P, P, I64, P, P, P, P, I64, I32, I32, I32, P])
 
 
 def test_c_abi_unknown_type_is_refused_at_load(tmp_path):
