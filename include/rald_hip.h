@@ -229,6 +229,33 @@ int rald_post_chamfer_sums(const float* pred, int64_t n_pred, const float* gt, i
  * length silently leaves that segment's rows behind the bound out of its sum).  A sample with an empty side keeps 0 for that sum. */
 int rald_post_chamfer_sums_ragged(const float* pred, const int64_t* pred_offsets, const float* gt, const int64_t* gt_offsets, int32_t batch,
                                   int64_t max_pred, int64_t max_gt, double* out_sums, void* stream);
+/* ---- point-cloud metrics: exact nearest neighbours in float64 (coordinates fp32 in; d^2 = dx*dx + dy*dy + dz*dz,
+ * every operation rounded, left to right), ragged batches as above (DEVICE int64 offsets [batch+1], HOST upper bounds of the longest
+ * segment of either side that size the grids and the scratch).  Nothing is read back, so the bounds cannot be checked: a bound BELOW a
+ * segment's length silently gives PARTIAL results (the rows behind it get no output and enter no sum, the candidates behind it are not
+ * searched) and no error.  No atomics: every result is the same bits in every call, for every chunk length and in every batch.
+ * Scratch of the rald_post_* calls: rald_post_cloud_metrics_scratch_bytes of the same batch and bounds (for rald_post_nn_ragged with
+ * max_pred = max_a, max_gt = max_b), 8-byte aligned; -1 for arguments the calls refuse. */
+int64_t rald_post_cloud_metrics_scratch_bytes(int32_t batch, int64_t max_pred, int64_t max_gt);
+/* per row of a: out_dist (double) = distance to the nearest row of b in the same sample, out_idx (int64) = that row's index from the
+ * sample's first b row; equal distances: the lowest index.  Either output may be NULL.  Outputs are laid out like a (row a_offsets[s] + i);
+ * rows from a_offsets[batch] on are not written.  A sample without b rows gets dist = inf, idx = -1. */
+int rald_post_nn_ragged(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int32_t batch, int64_t max_a,
+                        int64_t max_b, double* out_dist, int64_t* out_idx, void* scratch, void* stream);
+/* both directions (0: pred -> gt, 1: gt -> pred) and their reductions: out_raw [batch,2,3+K] doubles = sum of d, sum of d^2, max of d,
+ * number of rows with d < thresholds_host[k] (strict, in float64, on d) for the K = n_thresholds <= 8 HOST doubles (finite, >= 0).
+ * The sums run in a fixed order counted from the sample's own first row: a sample's out_raw is the same bits alone and in any batch.
+ * A sample with an empty side gets zeros.  The four per-row outputs (as rald_post_nn_ragged) may each be NULL. */
+int rald_post_cloud_metrics_ragged(const float* pred, const int64_t* pred_offsets, const float* gt, const int64_t* gt_offsets, int32_t batch,
+                                   int64_t max_pred, int64_t max_gt, const double* thresholds_host, int32_t n_thresholds, double* out_raw,
+                                   double* out_dist_pred, int64_t* out_idx_pred, double* out_dist_gt, int64_t* out_idx_gt, void* scratch,
+                                   void* stream);
+/* rald_post_nn_ragged with an explicit chunk length (test-facing: several chunks at small sizes): the b rows one workgroup searches,
+ * 0 = the automatic choice (a function of batch, max_a and max_b only), otherwise a multiple of 1024.  scratch_bytes >=
+ * rald_op_nn_scratch_bytes of the same arguments. */
+int64_t rald_op_nn_scratch_bytes(int32_t batch, int64_t max_a, int64_t max_b, int64_t b_chunk);
+int rald_op_nn_ragged(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int32_t batch, int64_t max_a,
+                      int64_t max_b, int64_t b_chunk, double* out_dist, int64_t* out_idx, void* scratch, int64_t scratch_bytes, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

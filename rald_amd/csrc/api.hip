@@ -271,6 +271,30 @@ int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64
     return post_iou(logits, labels, batch, n_queries, out_accuracy, out_iou, (hipStream_t)stream);
 }
 
+// ---- point-cloud metrics ---------------------------------------------------------
+int64_t rald_post_cloud_metrics_scratch_bytes(int32_t batch, int64_t max_pred, int64_t max_gt) {
+    return cloud_metrics_scratch_bytes(batch, max_pred, max_gt);
+}
+int rald_post_nn_ragged(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int32_t batch, int64_t max_a,
+                        int64_t max_b, double* out_dist, int64_t* out_idx, void* scratch, void* stream) {
+    return cloud_nn_ragged(a, a_offsets, b, b_offsets, batch, max_a, max_b, 0, out_dist, out_idx, scratch,
+                           cloud_nn_scratch_bytes(batch, max_a, max_b, 0), (hipStream_t)stream);
+}
+int rald_post_cloud_metrics_ragged(const float* pred, const int64_t* pred_offsets, const float* gt, const int64_t* gt_offsets, int32_t batch,
+                                   int64_t max_pred, int64_t max_gt, const double* thresholds_host, int32_t n_thresholds, double* out_raw,
+                                   double* out_dist_pred, int64_t* out_idx_pred, double* out_dist_gt, int64_t* out_idx_gt, void* scratch,
+                                   void* stream) {
+    return cloud_metrics_ragged(pred, pred_offsets, gt, gt_offsets, batch, max_pred, max_gt, thresholds_host, n_thresholds, out_raw,
+                                out_dist_pred, out_idx_pred, out_dist_gt, out_idx_gt, scratch, (hipStream_t)stream);
+}
+int64_t rald_op_nn_scratch_bytes(int32_t batch, int64_t max_a, int64_t max_b, int64_t b_chunk) {
+    return cloud_nn_scratch_bytes(batch, max_a, max_b, b_chunk);
+}
+int rald_op_nn_ragged(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int32_t batch, int64_t max_a,
+                      int64_t max_b, int64_t b_chunk, double* out_dist, int64_t* out_idx, void* scratch, int64_t scratch_bytes, void* stream) {
+    return cloud_nn_ragged(a, a_offsets, b, b_offsets, batch, max_a, max_b, b_chunk, out_dist, out_idx, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

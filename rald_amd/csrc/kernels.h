@@ -303,6 +303,16 @@ int post_iou(const float* logits, const float* labels, int B, int64_t Q, float* 
 int radar_cube_prepare(const float* raw, int B, int R, int A, int E, int Craw, int tA, int tE, int norm_i, float max_i, int norm_d,
                        float max_d, float* out, hipStream_t st);
 
+// ---------------------------------------------------------------- cloud_metrics.hip
+// exact nearest neighbours (fp64) of ragged batches, per row and reduced per frame; scratch: the *_scratch_bytes of the same arguments
+int64_t cloud_metrics_scratch_bytes(int B, int64_t max_pred, int64_t max_gt);
+int64_t cloud_nn_scratch_bytes(int B, int64_t max_a, int64_t max_b, int64_t b_chunk);     // b_chunk 0: the automatic chunk length
+int cloud_nn_ragged(const float* a, const int64_t* a_off, const float* b, const int64_t* b_off, int B, int64_t max_a, int64_t max_b, int64_t b_chunk,
+                    double* out_dist, int64_t* out_idx, void* scratch, int64_t scratch_bytes, hipStream_t st);
+int cloud_metrics_ragged(const float* pred, const int64_t* pred_off, const float* gt, const int64_t* gt_off, int B, int64_t max_pred, int64_t max_gt,
+                         const double* thresholds_host, int n_thr, double* out_raw, double* out_dist_pred, int64_t* out_idx_pred,
+                         double* out_dist_gt, int64_t* out_idx_gt, void* scratch, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

@@ -149,16 +149,20 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 
 @torch.no_grad()
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
-                              rng: Optional[torch.Generator] = None, draws: Optional[dict] = None):
+                              rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
-    read to the host and the device is not synchronised."""
-    return _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws)[:3]
+    read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
+    element follows: the device dict of postprocess.cloud_metrics_ragged (None where no metric is computed), whose 'cd' is the third."""
+    pts, off, cd, _, metrics = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds)
+    return (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
 
 
-def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws):
-    """The batched tail -> (points, offsets, cd or None, n_queries int64 [B]) on the device: what infer_point_clouds_device returns plus
-    the frames' query counts, which infer_point_clouds copies to the host with the rest."""
+def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None):
+    """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None) on the device: what
+    infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest."""
+    if metric_thresholds is not None:
+        metric_thresholds = PP._thresholds(metric_thresholds)
     helpers = _check_batch_inputs(sampled_tokens, helper_points, surfaces)
     B = sampled_tokens.shape[0]
     lidar, inf = args.dataset.lidar, args.eval.inference
@@ -196,15 +200,19 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
     view_cone = bool(_get(lidar, "view_cone_mode", False))
     if view_cone:
         pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
-    cd = None
+    cd, metrics = None, None
     if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
         P = surfaces.shape[1]
         gt = PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso)   # :290
         if view_cone:
             gt = PP.polar2cartesian(gt)
         gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
-        cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, longest, P)                             # :320
-    return pts, p_off, cd, n_queries
+        if metric_thresholds is None:
+            cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, longest, P)                         # :320
+        else:
+            metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
+            cd = metrics["cd"]
+    return pts, p_off, cd, n_queries, metrics
 
 
 def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
@@ -226,7 +234,7 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 
 @torch.no_grad()
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
-                       rng: Optional[torch.Generator] = None, draws: Optional[dict] = None) -> Dict[str, object]:
+                       rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -241,16 +249,24 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
 
     A frame whose first decode has no positive gets no refine queries and ends with an empty prediction and cd = inf; the
     single-frame infer_point_cloud raises there.  Shape and length errors raise ValueError before any GPU work.
+    `metric_thresholds` (None, or a sequence of up to 8 distances, () included): when given, the metric comes from
+    postprocess.cloud_metrics_ragged instead of cal_metrics_ragged - 'cd' keeps its meaning, and 'metrics' holds one dict per frame
+    (postprocess.cloud_metrics' keys: accuracy, completeness, cd, cd_l2, hausdorff, mhd as floats; precision, recall, f_score as lists
+    per threshold), copied in the same single host read; None where no metric is computed.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
-    'n_queries': list of B ints}."""
-    pts, off, cd, nq = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws)
+    'n_queries': list of B ints} (+ 'metrics' with metric_thresholds)."""
+    pts, off, cd, nq, metrics = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds)
     B = sampled_tokens.shape[0]
-    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []))
+    extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
+    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra)
     host = packed.cpu().tolist()                                                                    # the one host read
     o = [int(v) for v in host[:B + 1]]
-    return {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
-            "cd": host[2 * B + 1:] if cd is not None else None,
-            "n_queries": [int(v) for v in host[B + 1:2 * B + 1]]}
+    out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
+           "cd": host[2 * B + 1:3 * B + 1] if cd is not None else None,
+           "n_queries": [int(v) for v in host[B + 1:2 * B + 1]]}
+    if metric_thresholds is not None:
+        out["metrics"] = PP._metrics_to_host(host[3 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
+    return out
 
 
 @torch.no_grad()

@@ -4,14 +4,18 @@
 ``dataset_preprocessor/lidar.py`` (``polar2cartesian``), operating on CUDA tensors through
 ``rald_post_*`` (include/rald_hip.h).  ``occupied_points`` is the fused form of
 ``np.where(output > 0)`` -> ``grid[ind]`` -> ``inverse_norm_points`` -> ``polar2cartesian``.
+
+Beyond the reference's one metric: ``nearest_neighbors*`` and ``cloud_metrics*`` (exact nearest neighbours per point, and accuracy,
+completeness, both Chamfer variants, (modified) Hausdorff distance and precision / recall / F-score per frame).
 """
 from __future__ import annotations
 
-from typing import Tuple
+import math
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from ._handles import _doubles, _f32c, _need_cuda, _opt, _ragged_batch, _stream
+from ._handles import _doubles, _f32c, _nbytes, _need_cuda, _opt, _ragged_batch, _scratch, _stream
 from ._lib import check, lib
 
 
@@ -114,6 +118,160 @@ def cal_metrics_ragged(y_pred: torch.Tensor, pred_offsets: torch.Tensor, y_gt: t
     n_gt = (gt_offsets[1:] - gt_offsets[:-1]).double()
     cd = 0.5 * sums[:, 1] / n_gt + 0.5 * sums[:, 0] / n_pred
     return torch.where(n_pred == 0, torch.full_like(cd, float("inf")), cd)
+
+
+MAX_THRESHOLDS = 8                                       # K of rald_post_cloud_metrics_ragged
+METRIC_KEYS = ("accuracy", "completeness", "cd", "cd_l2", "hausdorff", "mhd", "precision", "recall", "f_score")
+
+
+def _xyz(t, what: str) -> None:
+    if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == 3):
+        raise ValueError(f"{what} must be a tensor [n, 3]")
+
+
+def _offsets_shape(t, what: str) -> int:
+    """B of int64 offsets [B+1], by shape and dtype alone (before anything asks where the tensor lives)."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 1 and t.numel() >= 2):
+        raise ValueError(f"{what} must be an int64 tensor [B+1]")
+    return t.numel() - 1
+
+
+def _bound(v, what: str) -> int:
+    if int(v) != v or v < 0:
+        raise ValueError(f"{what} must be a non-negative integer")
+    return int(v)
+
+
+def _thresholds(thresholds) -> list:
+    taus = [float(t) for t in thresholds]
+    if len(taus) > MAX_THRESHOLDS:
+        raise ValueError(f"at most {MAX_THRESHOLDS} thresholds")
+    if any(not math.isfinite(t) or t < 0 for t in taus):
+        raise ValueError("thresholds must be finite and >= 0")
+    return taus
+
+
+def _ragged_pair(a, a_offsets, b, b_offsets, names) -> int:
+    """The shape rules of a ragged pair of clouds (ValueError), then the device rules; -> B."""
+    _xyz(a, names[0])
+    _xyz(b, names[2])
+    B = _offsets_shape(a_offsets, names[1])
+    if _offsets_shape(b_offsets, names[3]) != B:
+        raise ValueError(f"{names[1]} and {names[3]} must describe the same batch")
+    _need_cuda(a, names[0])
+    _ragged_batch(a_offsets, names[1])
+    _ragged_batch(b_offsets, names[3])
+    return B
+
+
+def nearest_neighbors_ragged(a: torch.Tensor, a_offsets: torch.Tensor, b: torch.Tensor, b_offsets: torch.Tensor, max_a: int, max_b: int,
+                             b_chunk: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per row of a [Ta,3] the exact nearest row of b [Tb,3] in the same frame (offsets int64 [B+1] on the device; max_a / max_b host
+    upper bounds of the longest segment, trusted as in cal_metrics_ragged): (dist float64 [Ta], idx int64 [Ta]), idx counting from the
+    frame's first b row, the lowest index on equal distances; a frame without b rows gets (inf, -1).  Rows from a_offsets[B] on are
+    unspecified.  float64 arithmetic on the fp32 coordinates, no atomics, no host read.  b_chunk (tests): the b rows per workgroup,
+    a multiple of 1024, 0 or None = automatic; the result does not depend on it."""
+    max_a, max_b = _bound(max_a, "max_a"), _bound(max_b, "max_b")
+    B = _ragged_pair(a, a_offsets, b, b_offsets, ("a", "a_offsets", "b", "b_offsets"))
+    a, b = _f32c(a), _f32c(b).to(a.device)
+    dist = torch.empty(a.shape[0], device=a.device, dtype=torch.float64)
+    idx = torch.empty(a.shape[0], device=a.device, dtype=torch.int64)
+    if b_chunk is None:
+        scratch = _scratch(_nbytes(lib().rald_post_cloud_metrics_scratch_bytes(B, max_a, max_b)), a.device)
+        check(lib().rald_post_nn_ragged(a.data_ptr(), a_offsets.data_ptr(), b.data_ptr(), b_offsets.data_ptr(), B, max_a, max_b,
+                                        dist.data_ptr(), idx.data_ptr(), scratch.data_ptr(), _stream()))
+    else:
+        nbytes = _nbytes(lib().rald_op_nn_scratch_bytes(B, max_a, max_b, int(b_chunk)))
+        scratch = _scratch(nbytes, a.device)
+        check(lib().rald_op_nn_ragged(a.data_ptr(), a_offsets.data_ptr(), b.data_ptr(), b_offsets.data_ptr(), B, max_a, max_b, int(b_chunk),
+                                      dist.data_ptr(), idx.data_ptr(), scratch.data_ptr(), nbytes, _stream()))
+    return dist, idx
+
+
+def nearest_neighbors(a: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dist float64 [n_a], idx int64 [n_a]): the exact nearest row of b for every row of a (nearest_neighbors_ragged for one frame)."""
+    _xyz(a, "a")
+    _xyz(b, "b")
+    _need_cuda(a, "a")
+    off = torch.tensor([[0, a.shape[0]], [0, b.shape[0]]], dtype=torch.int64, device=a.device)
+    return nearest_neighbors_ragged(a, off[0], b, off[1], a.shape[0], b.shape[0])
+
+
+def _derive_cloud_metrics(raw: torch.Tensor, n_pred: torch.Tensor, n_gt: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """raw [B,2,3+K] (direction 0 pred -> gt, 1 gt -> pred: sum d, sum d^2, max d, counts below the K thresholds) and the frames'
+    sizes (float64 [B]) -> the metrics.  A frame with an empty side: the six distances inf, the three ratios 0."""
+    empty = (n_pred == 0) | (n_gt == 0)
+    n = torch.stack((n_pred, n_gt), dim=1)                                       # [B,2]
+    safe = torch.where(n == 0, torch.ones_like(n), n)
+    mean_d, mean_d2, max_d = raw[:, :, 0] / safe, raw[:, :, 1] / safe, raw[:, :, 2]
+    inf = torch.full_like(n_pred, float("inf"))
+    dist = {"accuracy": mean_d[:, 0], "completeness": mean_d[:, 1], "cd": 0.5 * mean_d[:, 0] + 0.5 * mean_d[:, 1],
+            "cd_l2": mean_d2[:, 0] + mean_d2[:, 1], "hausdorff": torch.maximum(max_d[:, 0], max_d[:, 1]),
+            "mhd": torch.maximum(mean_d[:, 0], mean_d[:, 1])}
+    out = {k: torch.where(empty, inf, v) for k, v in dist.items()}
+    ratio = torch.where(empty[:, None, None], torch.zeros_like(raw[:, :, 3:]), raw[:, :, 3:] / safe[:, :, None])     # [B,2,K]
+    p, r = ratio[:, 0], ratio[:, 1]
+    s = p + r
+    out["precision"], out["recall"] = p, r
+    out["f_score"] = torch.where(s > 0, 2.0 * p * r / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(s))
+    return out
+
+
+def cloud_metrics_ragged(y_pred: torch.Tensor, pred_offsets: torch.Tensor, y_gt: torch.Tensor, gt_offsets: torch.Tensor, max_pred: int,
+                         max_gt: int, thresholds: Sequence[float] = (), per_point: bool = False) -> Dict[str, torch.Tensor]:
+    """Per frame of a ragged batch, float64 [B] on the device, from the exact nearest-neighbour distances d of both directions:
+    accuracy (mean d over pred), completeness (mean d over gt), cd = 0.5 accuracy + 0.5 completeness (cal_metrics' definition),
+    cd_l2 (mean d^2 over pred + mean d^2 over gt), hausdorff (the larger maximum), mhd (the larger mean), and [B,K] per threshold tau:
+    precision (share of pred with d < tau), recall (share of gt with d < tau), f_score = 2PR / (P + R), 0 where P + R = 0.
+    A frame with an empty prediction or ground truth: the six distances inf, the three ratios 0.  max_pred / max_gt as in
+    cal_metrics_ragged.  per_point adds dist_pred / idx_pred [Tp] and dist_gt / idx_gt [Tg] (nearest_neighbors_ragged's outputs of both
+    directions).  Bit-reproducible (no atomics; a frame's values do not depend on the batch around it).  No host read."""
+    taus = _thresholds(thresholds)
+    max_pred, max_gt = _bound(max_pred, "max_pred"), _bound(max_gt, "max_gt")
+    B = _ragged_pair(y_pred, pred_offsets, y_gt, gt_offsets, ("y_pred", "pred_offsets", "y_gt", "gt_offsets"))
+    y_pred, y_gt = _f32c(y_pred), _f32c(y_gt).to(y_pred.device)
+    dev, K = y_pred.device, len(taus)
+    raw = torch.empty(B, 2, 3 + K, device=dev, dtype=torch.float64)
+    pp = {}
+    if per_point:
+        for side, t in (("pred", y_pred), ("gt", y_gt)):
+            pp["dist_" + side] = torch.empty(t.shape[0], device=dev, dtype=torch.float64)
+            pp["idx_" + side] = torch.empty(t.shape[0], device=dev, dtype=torch.int64)
+    scratch = _scratch(_nbytes(lib().rald_post_cloud_metrics_scratch_bytes(B, max_pred, max_gt)), dev)
+    check(lib().rald_post_cloud_metrics_ragged(y_pred.data_ptr(), pred_offsets.data_ptr(), y_gt.data_ptr(), gt_offsets.data_ptr(), B, max_pred,
+                                               max_gt, _doubles(taus, K, "thresholds") if K else None, K, raw.data_ptr(),
+                                               _opt(pp.get("dist_pred")), _opt(pp.get("idx_pred")), _opt(pp.get("dist_gt")),
+                                               _opt(pp.get("idx_gt")), scratch.data_ptr(), _stream()))
+    out = _derive_cloud_metrics(raw, (pred_offsets[1:] - pred_offsets[:-1]).double(), (gt_offsets[1:] - gt_offsets[:-1]).double())
+    out.update(pp)
+    return out
+
+
+def _metrics_to_host(values: Sequence[float], B: int, K: int) -> list:
+    """The METRIC_KEYS tensors of a batch, flattened and concatenated in that order, as host floats -> one dict per frame."""
+    frames = [{} for _ in range(B)]
+    at = 0
+    for key in METRIC_KEYS:
+        width = K if key in ("precision", "recall", "f_score") else None
+        for b in range(B):
+            if width is None:
+                frames[b][key] = values[at + b]
+            else:
+                frames[b][key] = list(values[at + b * K:at + (b + 1) * K])
+        at += B * (width if width is not None else 1)
+    return frames
+
+
+def cloud_metrics(y_pred: torch.Tensor, y_gt: torch.Tensor, thresholds: Sequence[float] = ()) -> dict:
+    """cloud_metrics_ragged for one frame, read to the host: Python floats, and lists of K floats for precision / recall / f_score."""
+    taus = _thresholds(thresholds)
+    _xyz(y_pred, "y_pred")
+    _xyz(y_gt, "y_gt")
+    _need_cuda(y_pred, "y_pred")
+    off = torch.tensor([[0, y_pred.shape[0]], [0, y_gt.shape[0]]], dtype=torch.int64, device=y_pred.device)
+    m = cloud_metrics_ragged(y_pred, off[0], y_gt, off[1], y_pred.shape[0], y_gt.shape[0], taus)
+    host = torch.cat([m[k].reshape(-1) for k in METRIC_KEYS]).cpu().tolist()
+    return _metrics_to_host(host, 1, len(taus))[0]
 
 
 def accuracy_iou(outputs: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
