@@ -500,6 +500,34 @@ int rald_op_edm_loss_grad(const float* F, const float* x_noised, const float* y,
  * training step, whose only reader is the GroupNorm backward with da_is_bf16 = 1). */
 int rald_op_conv3d(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, void* out_bf16, int32_t B,
                    int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream);
+/* Which engine a Conv3d shape runs on: the library's one engine-choice function (pure host arithmetic, no HIP call, works where no GPU is
+ * visible).  Returns 0 igemm (gathers per tap; any stride / width), 1 line (stride 1, pad 1, W in {8,16,32}, M % 128 == 0), 2 plane and
+ * 3 persistent plane (the 64-input-channel full-resolution levels), 4 igemm with split K + reduce pass (allow_split = 1 only: few tiles x
+ * long K, as the encoder runs its 512- and 64-voxel levels); *splits_out (nullable) = the number of k-ranges, 1 when not split.
+ * -1 (and rald_last_error) for a shape rald_op_conv3d_full refuses. */
+int rald_op_conv3d_route(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, int32_t allow_split,
+                         int32_t* splits_out);
+/* rald_op_conv3d with every field of the kernels' argument block reachable (tests): allow_split = 0 is rald_op_conv3d exactly; 1 takes the
+ * route the encoder takes, i.e. where rald_op_conv3d_route reports 4 the k-ranges meet as fp32 partial sums in split_workspace (caller-owned,
+ * 16-byte aligned, at least splits * M * Cout * 4 bytes, M = B * output voxels) and a second launch adds them in order with bias and residual.
+ * gn_part (nullable): [B * So / 128][32][2] doubles = {sum, sum of squares} per 128-voxel tile and GroupNorm group of the OUTPUT, written by
+ * the convolution epilogue (So = output voxels per sample, So % 128 == 0, Cout in {64, 128, 256}; not where the route splits).
+ * resid == out is allowed (the in-place residual of a ResnetBlock: every element is read and then written by the same thread).
+ * out_bf16 excludes out, resid and a split route. */
+int rald_op_conv3d_full(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, void* out_bf16,
+                        double* gn_part, void* split_workspace, int64_t split_workspace_bytes, int32_t allow_split, int32_t B, int32_t ID,
+                        int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream);
+/* stats [B][32][2] = per sample the sum, in a fixed order, of its nblk partial slots part[b * nblk + k][32][2] (what rald_op_conv3d_full's
+ * gn_part holds with nblk = So / 128): the statistics rald_op_groupnorm_apply normalises with */
+int rald_op_gn_finish(const double* part, double* stats, int32_t B, int32_t nblk, void* stream);
+/* The radar decoder's data movement: nearest-neighbour x2 of x f32 [B][D][H][W][C] -> bf16 [B][2D][2H][2W][C] (C % 4 == 0);
+ * z f32 [rows][zc] -> bf16 [rows][64], zero beyond zc (1 <= zc <= 64). */
+int rald_op_upsample2_cast(const float* x, void* y_bf16, int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, void* stream);
+int rald_op_pad_cast64(const float* z, void* y_bf16, int64_t rows, int32_t zc, void* stream);
+/* The tokeniser half of rald_radar_tokens without the encoder (EDMPrecond.process_radar_cond :387-407): z f32 [B][R][A][E][zc] on the token
+ * grid -> tokens f32 [B][R*A*E][C] = z . Wp[C][zc]^T + bp + r_emb[r] + a_emb[a] + e_emb[e] (embeddings [R|A|E][C]); zc <= 64, B <= 65535. */
+int rald_op_radar_tokens(const float* z, const float* Wp, const float* bp, const float* r_emb, const float* a_emb, const float* e_emb, float* tokens,
+                         int32_t B, int32_t R, int32_t A, int32_t E, int32_t zc, int32_t C, void* stream);
 /* W [Cout][Cin][27] f32 (the parameter) -> packed bf16: dgrad = 0: [Cout][27][pad_to >= Cin]; dgrad = 1: the flipped,
  * transposed weights [Cin][27][pad_to >= Cout] that make rald_op_conv3d map dY to dX */
 int rald_op_conv_pack_weights(const float* W, void* out_bf16, int32_t Cout, int32_t Cin, int32_t pad_to, int32_t dgrad, void* stream);

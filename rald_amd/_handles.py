@@ -364,6 +364,52 @@ def op_resid_gemm_ln(x: torch.Tensor, bias: torch.Tensor, M: int, K: int, A: Opt
                                       nt_io, route, _opt(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size(), _stream()))
 
 
+CONV_ENGINES = ("igemm", "line", "plane", "pplane", "igemm-split")     # what rald_op_conv3d_route returns, by index
+
+
+def op_conv3d_route(B: int, ID: int, IH: int, IW: int, Cin: int, Cout: int, stride: int = 1, pad: int = 1, allow_split: int = 0):
+    """(engine name, split count) of a Conv3d k3 shape: the library's one engine-choice function (host arithmetic, needs no GPU)."""
+    splits = C.c_int32(0)
+    e = lib().rald_op_conv3d_route(B, ID, IH, IW, Cin, Cout, stride, pad, int(allow_split), C.addressof(splits))
+    if e < 0:
+        check(1)
+    return CONV_ENGINES[e], splits.value
+
+
+def op_conv3d_full(x16: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, B: int, ID: int, IH: int, IW: int, Cin: int, Cout: int,
+                   out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                   gn_part: Optional[torch.Tensor] = None, split_ws: Optional[torch.Tensor] = None, allow_split: int = 0, stride: int = 1,
+                   pad: int = 1) -> None:
+    """Conv3d k3 of x16 (bf16 [B,ID,IH,IW,Cin]) with packed weights wp [Cout,27,Cin] into the caller's buffers: out (f32, + resid; resid may
+    be `out` itself) or out_bf16; gn_part (f64 [B*So/128,32,2]) takes the GroupNorm partials of the output from the epilogue.
+    allow_split = 1: the route the encoder takes (split K through split_ws where op_conv3d_route says "igemm-split"); 0: one pass."""
+    check(lib().rald_op_conv3d_full(x16.data_ptr(), wp.data_ptr(), bias.data_ptr(), _opt(resid), _opt(out), _opt(out_bf16), _opt(gn_part),
+                                    _opt(split_ws), 0 if split_ws is None else split_ws.numel() * split_ws.element_size(), int(allow_split),
+                                    B, ID, IH, IW, Cin, Cout, stride, pad, _stream()))
+
+
+def op_gn_finish(part: torch.Tensor, stats: torch.Tensor, B: int, nblk: int) -> None:
+    """stats f64 [B,32,2] = per sample the in-order sum of its nblk slots part [B*nblk,32,2] (partials of op_conv3d_full's gn_part)."""
+    check(lib().rald_op_gn_finish(part.data_ptr(), stats.data_ptr(), B, nblk, _stream()))
+
+
+def op_upsample2_cast(x: torch.Tensor, y16: torch.Tensor, B: int, D: int, H: int, W: int, Cc: int) -> None:
+    """x f32 [B,D,H,W,C] -> y16 bf16 [B,2D,2H,2W,C], nearest neighbour (the radar decoder's Upsample before its convolution)."""
+    check(lib().rald_op_upsample2_cast(x.data_ptr(), y16.data_ptr(), B, D, H, W, Cc, _stream()))
+
+
+def op_pad_cast64(z: torch.Tensor, y16: torch.Tensor, rows: int, zc: int) -> None:
+    """z f32 [rows,zc] -> y16 bf16 [rows,64], zero beyond zc."""
+    check(lib().rald_op_pad_cast64(z.data_ptr(), y16.data_ptr(), rows, zc, _stream()))
+
+
+def op_radar_tokens(z: torch.Tensor, Wp: torch.Tensor, bp: torch.Tensor, r_emb: torch.Tensor, a_emb: torch.Tensor, e_emb: torch.Tensor,
+                    tokens: torch.Tensor, B: int, R: int, A: int, E: int, zc: int, Cc: int) -> None:
+    """tokens f32 [B,R*A*E,C] = z [B,R,A,E,zc] . Wp [C,zc]^T + bp + r_emb[r] + a_emb[a] + e_emb[e] (the tokeniser without the encoder)."""
+    check(lib().rald_op_radar_tokens(z.data_ptr(), Wp.data_ptr(), bp.data_ptr(), r_emb.data_ptr(), a_emb.data_ptr(), e_emb.data_ptr(),
+                                     tokens.data_ptr(), B, R, A, E, zc, Cc, _stream()))
+
+
 def op_gemm_geglu_mx8out(bias_packed: torch.Tensor, M: int, N: int, K: int, A: Optional[torch.Tensor] = None, W: Optional[torch.Tensor] = None,
                          A8: Optional[torch.Tensor] = None, SA: Optional[torch.Tensor] = None, W8: Optional[torch.Tensor] = None,
                          SW: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None,

@@ -542,6 +542,37 @@ int rald_op_conv3d(const void* in_bf16, const void* w_packed_bf16, const float* 
     return conv3d_igemm((const bf16*)in_bf16, (const bf16*)w_packed_bf16, bias, resid, out, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream,
                         (bf16*)out_bf16);
 }
+int rald_op_conv3d_route(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, int32_t allow_split,
+                         int32_t* splits_out) {
+    if (splits_out) *splits_out = 0;
+    if (!(B > 0 && ID > 0 && IH > 0 && IW > 0 && (stride == 1 || stride == 2) && ID >= stride && IH >= stride && IW >= stride && Cin > 0 &&
+          Cin % 64 == 0 && Cout > 0 && Cout % 4 == 0 && pad >= 0 && pad <= 2 && (allow_split == 0 || allow_split == 1))) {
+        set_error("rald_op_conv3d_route: not a shape rald_op_conv3d_full takes (Cin % 64, Cout % 4, stride 1|2, pad 0..2, allow_split 0|1)");
+        return -1;
+    }
+    const ConvRoute r = conv3d_route(B, ID, IH, IW, Cin, Cout, stride, pad, allow_split);
+    if (splits_out) *splits_out = r.splits;
+    return r.engine;
+}
+int rald_op_conv3d_full(const void* in_bf16, const void* w_packed_bf16, const float* bias, const float* resid, float* out, void* out_bf16,
+                        double* gn_part, void* split_workspace, int64_t split_workspace_bytes, int32_t allow_split, int32_t B, int32_t ID,
+                        int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, void* stream) {
+    return conv3d_full((const bf16*)in_bf16, (const bf16*)w_packed_bf16, bias, resid, out, (bf16*)out_bf16, gn_part, (float*)split_workspace,
+                       split_workspace_bytes, allow_split, B, ID, IH, IW, Cin, Cout, stride, pad, (hipStream_t)stream);
+}
+int rald_op_gn_finish(const double* part, double* stats, int32_t B, int32_t nblk, void* stream) {
+    return gn_finish(part, stats, B, nblk, (hipStream_t)stream);
+}
+int rald_op_upsample2_cast(const float* x, void* y_bf16, int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, void* stream) {
+    return upsample2_cast(x, (bf16*)y_bf16, B, D, H, W, C, (hipStream_t)stream);
+}
+int rald_op_pad_cast64(const float* z, void* y_bf16, int64_t rows, int32_t zc, void* stream) {
+    return pad_cast64(z, (bf16*)y_bf16, rows, zc, (hipStream_t)stream);
+}
+int rald_op_radar_tokens(const float* z, const float* Wp, const float* bp, const float* r_emb, const float* a_emb, const float* e_emb, float* tokens,
+                         int32_t B, int32_t R, int32_t A, int32_t E, int32_t zc, int32_t C, void* stream) {
+    return radar_tokens(z, Wp, bp, r_emb, a_emb, e_emb, tokens, B, R, A, E, zc, C, (hipStream_t)stream);
+}
 int rald_op_groupnorm(const float* x, const float* gamma, const float* beta, void* y_bf16, double* stats, int32_t B, int32_t S, int32_t C,
                       int32_t swish, void* stream) {
     return groupnorm_fwd(x, gamma, beta, (bf16*)y_bf16, stats, B, S, C, swish, (hipStream_t)stream);

@@ -374,7 +374,10 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(ConvArgs a) {
     }
     conv_epilogue(acc, a, M, m0, n0, wm, wn, fr, fq, tid, smem);
 }
-// out = bias + sum_z part[z] (+ resid), z in order; one float4 per thread
+// out = bias + sum_z part[z] (+ resid), z in order; one float4 per thread.  Aliasing contract: resid == out is allowed (resblock's in-place
+// residual) although both are __restrict__ - the one thread that writes out[i .. i+3] is the only one that reads resid[i .. i+3], and its
+// store depends on that load, so no reordering the qualifier permits can change the result; `part` must not overlap either
+// (tests/test_gpu_radar_encoder_ops.py runs every split shape in place and compares bit for bit).
 __global__ __launch_bounds__(256) void conv_split_reduce_kernel(const float* __restrict__ part, int splits, int64_t MC, int Cout,
                                                                 const float* __restrict__ bias, const float* __restrict__ resid,
                                                                 float* __restrict__ out) {
@@ -882,31 +885,79 @@ __global__ __launch_bounds__(512) void conv3d_pplane_kernel(ConvArgs a, int lw, 
     }
 }
 
-// engine choice for one convolution
-static void launch_conv(const ConvArgs& a, hipStream_t st) {
-    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
-    const dim3 grid(cdiv(a.Cout, 64), (unsigned)((M + 127) / 128));
-    const bool pow2 = a.OW == 8 || a.OW == 16 || a.OW == 32;
-    if (a.stride == 1 && a.pad == 1 && pow2 && M % 128 == 0 && a.Cin % 64 == 0 && a.OD == a.ID && a.OH == a.IH && a.OW == a.IW) {
-        const int lw = a.OW == 8 ? 3 : a.OW == 16 ? 4 : 5;
+// Engine choice for one convolution: THE one place that decides it (pure host arithmetic, no HIP call; exported as
+// rald_op_conv3d_route so that a test can ask which engine a shape runs on).  In order:
+//   CONV_IGEMM_SPLIT  allow_split, not a line shape, few tiles x long K (<= 64 tiles, >= 12 k-steps: the 512- and 64-voxel levels, every
+//                     downsample below full resolution): conv3d_igemm_kernel with gridDim.z = splits k-ranges + conv_split_reduce_kernel
+//   line shapes (stride 1, pad 1, W in {8, 16, 32}, M % 128 == 0):
+//     CONV_PPLANE     Cin = 64, Cout % 64 == 0, W >= 16, H a multiple of the 256 / W lines of a tile, D % 8 == 0 and >= 256 workgroups
+//     CONV_PLANE      the same without the D condition, M / 256 >= 256 tiles
+//     CONV_LINE       every other line shape
+//   CONV_IGEMM        everything else (stride 2, W not a power of two in range, M % 128 != 0, pad != 1)
+ConvRoute conv3d_route(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad, int allow_split) {
+    ConvRoute r{CONV_IGEMM, 1};
+    if (B <= 0 || ID <= 0 || IH <= 0 || IW <= 0 || Cin <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return r;
+    const int OD = ID / stride, OH = IH / stride, OW = IW / stride;
+    const int64_t M = (int64_t)B * OD * OH * OW;
+    const bool line_shape = stride == 1 && pad == 1 && (OW == 8 || OW == 16 || OW == 32) && M % 128 == 0 && Cin % 64 == 0;
+    if (line_shape) {
+        const int lw = OW == 8 ? 3 : OW == 16 ? 4 : 5;
         constexpr int pds = 8;                                                // planes per persistent workgroup
         const int Lp = 256 >> lw;
-        if (a.Cin == 64 && a.Cout % 64 == 0 && lw >= 4 && a.OH % Lp == 0 && a.OD % pds == 0 && 3 * (Lp + 2) * (a.OW + 2) <= 1024 &&
-            (int64_t)a.B * (a.OH / Lp) * (a.OD / pds) >= 256) {
-            constexpr int LDSP = 1024 * 128 + 3 * 64 * 128;
+        const bool plane_shape = Cin == 64 && Cout % 64 == 0 && lw >= 4 && OH % Lp == 0 && 3 * (Lp + 2) * (OW + 2) <= 1024;
+        if (plane_shape && OD % pds == 0 && (int64_t)B * (OH / Lp) * (OD / pds) >= 256) r.engine = CONV_PPLANE;
+        else if (plane_shape && M % 256 == 0 && M / 256 >= 256) r.engine = CONV_PLANE;
+        else r.engine = CONV_LINE;
+        return r;
+    }
+    // few tiles x long K (the 512- and 64-voxel levels: 8-64 workgroups looping over 54-108 k-steps): split K over gridDim.z
+    const int64_t tiles = (int64_t)cdiv(Cout, 64) * ((M + 127) / 128);
+    const int nk = 27 * (Cin / 64);
+    if (allow_split && tiles >= 1 && tiles <= 64 && nk >= 12 && Cout % 4 == 0) {
+        int splits = (int)(256 / tiles);
+        if (splits > 16) splits = 16;
+        if (splits > nk / 3) splits = nk / 3;
+        if (splits >= 2) { r.engine = CONV_IGEMM_SPLIT; r.splits = splits; }   // (splits * tiles <= 256: at most 8 MiB of partial sums)
+    }
+    return r;
+}
+
+// One convolution on the engine `r` names.  split_ws: r.splits * M * Cout floats when r splits (bias / residual are added by the reduce pass;
+// a.resid == a.out, the in-place residual of resblock, is fine on every route: each output element is read and then written by one thread).
+static void launch_conv(ConvArgs a, const ConvRoute& r, float* split_ws, hipStream_t st) {
+    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
+    const dim3 grid(cdiv(a.Cout, 64), (unsigned)((M + 127) / 128));
+    const int lw = a.OW == 8 ? 3 : a.OW == 16 ? 4 : 5;
+    const int Lp = 256 >> lw;
+    constexpr int pds = 8;                                                    // planes per persistent workgroup (as conv3d_route)
+    constexpr int LDSP = 1024 * 128 + 3 * 64 * 128;                          // the tile's input image staged once + one (kd, kh) pair of weights
+    switch (r.engine) {
+        case CONV_PPLANE: {
             static bool attr_set = false;
             if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3d_pplane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSP); attr_set = true; }
             hipLaunchKernelGGL(conv3d_pplane_kernel, dim3(cdiv(a.Cout, 64), (unsigned)(a.B * (a.OH / Lp) * (a.OD / pds))), dim3(512), LDSP, st, a, lw, pds);
-        } else
-        if (a.Cin == 64 && a.Cout % 64 == 0 && lw >= 4 && a.OH % Lp == 0 && M % 256 == 0 && M / 256 >= 256 && 3 * (Lp + 2) * (a.OW + 2) <= 1024) {
-            constexpr int LDSP = 1024 * 128 + 3 * 64 * 128;                  // the tile's input image staged once + one (kd, kh) pair of weights
+            break;
+        }
+        case CONV_PLANE: {
             static bool attr_set = false;
             if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3d_plane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSP); attr_set = true; }
             hipLaunchKernelGGL(conv3d_plane_kernel, dim3(cdiv(a.Cout, 64), (unsigned)(M / 256)), dim3(512), LDSP, st, a, lw);
-        } else
-        hipLaunchKernelGGL(conv3d_line_kernel, grid, dim3(256), 0, st, a, lw);
-    } else {
-        hipLaunchKernelGGL(conv3d_igemm_kernel, grid, dim3(256), 0, st, a);
+            break;
+        }
+        case CONV_LINE:
+            hipLaunchKernelGGL(conv3d_line_kernel, grid, dim3(256), 0, st, a, lw);
+            break;
+        case CONV_IGEMM_SPLIT: {
+            float* out = a.out;
+            a.split_part = split_ws;
+            hipLaunchKernelGGL(conv3d_igemm_kernel, dim3(grid.x, grid.y, r.splits), dim3(256), 0, st, a);
+            const int64_t MC = M * a.Cout;
+            hipLaunchKernelGGL(conv_split_reduce_kernel, dim3((unsigned)((MC / 4 + 255) / 256)), dim3(256), 0, st, split_ws, r.splits, MC, a.Cout,
+                               a.bias, a.resid, out);
+            break;
+        }
+        default:
+            hipLaunchKernelGGL(conv3d_igemm_kernel, grid, dim3(256), 0, st, a);
     }
 }
 
@@ -1206,33 +1257,17 @@ int RadarEncoder::Impl::run_conv(const bf16* in, const std::string& name, const 
     RALD_CHECK(cin % 64 == 0 && cout % 4 == 0, "conv3d: Cin must be a multiple of 64 and Cout of 4");
     const int64_t M = (int64_t)B * a.OD * a.OH * a.OW;
     const int So = a.OD * a.OH * a.OW;
-    // few tiles x long K (the 512- and 64-voxel levels: 8-64 workgroups looping over 54-108 k-steps): split K over gridDim.z
-    const int64_t tiles = (int64_t)cdiv(cout, 64) * ((M + 127) / 128);
-    const int nk = 27 * (cin / 64);
-    const bool line_engine = stride == 1 && pad == 1 && (a.OW == 8 || a.OW == 16 || a.OW == 32) && M % 128 == 0;
-    if (!line_engine && tiles <= 64 && nk >= 12 && cout % 4 == 0) {
-        int splits = (int)(256 / tiles);
-        if (splits > 16) splits = 16;
-        if (splits > nk / 3) splits = nk / 3;
-        if (splits >= 2 && (size_t)splits * M * cout * 4 <= spart_bytes) {
-            if (out == fused_src) fused_src = nullptr;         // no GroupNorm partials from this path
-            a.split_part = spart;
-            hipLaunchKernelGGL(conv3d_igemm_kernel, dim3(cdiv(cout, 64), (unsigned)((M + 127) / 128), splits), dim3(256), 0, st, a);
-            const int64_t MC = M * cout;
-            hipLaunchKernelGGL(conv_split_reduce_kernel, dim3((unsigned)((MC / 4 + 255) / 256)), dim3(256), 0, st, spart, splits, MC, cout,
-                               a.bias, resid, out);
-            RALD_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    if (out == f0 || out == f1 || out == f2) {
+    const ConvRoute r = conv3d_route(B, ID, IH, IW, cin, cout, stride, pad, 1);
+    if (r.engine == CONV_IGEMM_SPLIT) {
+        RALD_CHECK((size_t)r.splits * M * cout * 4 <= spart_bytes, "radar encoder: split-K workspace too small");
+        if (out == fused_src) fused_src = nullptr;             // no GroupNorm partials from this path
+    } else if (out == f0 || out == f1 || out == f2) {
         if (So % 128 == 0 && cout % 64 == 0 && (cout == 64 || cout == 128 || cout == 256) && (size_t)B * (So / 128) * 64 * 8 <= cpart_bytes) {
             a.gn_part = cpart;
             fused_src = out; fused_B = B; fused_S = So; fused_C = cout;
         } else if (out == fused_src) fused_src = nullptr;      // this buffer is being overwritten without new partials
     }
-    (void)M;
-    launch_conv(a, st);
+    launch_conv(a, r, spart, st);
     RALD_HIP(hipGetLastError());
     return 0;
 }
@@ -1412,19 +1447,45 @@ int RadarEncoder::tokens(const float* cube, int B, float** tokens_out, hipStream
 RadarEncoder::~RadarEncoder() { delete impl; }
 
 // ---- op-level launchers of the kernels above (used by the training path, radar_train.hip / train_encoder.py) ------
-int conv3d_igemm(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, int B, int ID, int IH, int IW,
-                 int Cin, int Cout, int stride, int pad, hipStream_t st, bf16* out_bf16) {
+// The complete ConvArgs at op level.  allow_split = 1: the route Impl::run_conv takes (split-K through the caller's workspace where
+// conv3d_route says so); 0: never split.  gn_part (nullable): [B*So/128][32][2] doubles, the GroupNorm partials of the output.
+// resid == out (in place) is allowed.  Every check comes before the first HIP call.
+int conv3d_full(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, bf16* out_bf16, double* gn_part,
+                float* split_ws, int64_t split_ws_bytes, int allow_split, int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad,
+                hipStream_t st) {
     RALD_CHECK(in && w_packed && bias && (out || out_bf16), "conv3d: null pointer");
     RALD_CHECK(!out_bf16 || (!out && !resid && (uintptr_t)out_bf16 % 8 == 0), "conv3d: the bf16 result replaces the fp32 one and takes no residual");
     RALD_CHECK(B > 0 && ID > 0 && IH > 0 && IW > 0 && (stride == 1 || stride == 2), "conv3d: bad geometry");
     RALD_CHECK(Cin % 64 == 0 && Cout % 4 == 0, "conv3d: Cin must be a multiple of 64 and Cout of 4");
+    RALD_CHECK(Cin > 0 && Cout > 0 && ID >= stride && IH >= stride && IW >= stride && pad >= 0 && pad <= 2, "conv3d: bad geometry");
+    RALD_CHECK(allow_split == 0 || allow_split == 1, "conv3d: allow_split is 0 (never split K) or 1 (the encoder's route)");
     ConvArgs a;
     a.in = in; a.w = w_packed; a.bias = bias; a.resid = resid; a.out = out; a.out16 = out_bf16;
     a.B = B; a.ID = ID; a.IH = IH; a.IW = IW; a.Cin = Cin; a.Cout = Cout; a.stride = stride; a.pad = pad;
     a.OD = ID / stride; a.OH = IH / stride; a.OW = IW / stride;
-    launch_conv(a, st);
+    const int64_t M = (int64_t)B * a.OD * a.OH * a.OW;
+    const int64_t So = (int64_t)a.OD * a.OH * a.OW;
+    const ConvRoute r = conv3d_route(B, ID, IH, IW, Cin, Cout, stride, pad, allow_split);
+    if (r.engine == CONV_IGEMM_SPLIT) {
+        RALD_CHECK(!out_bf16, "conv3d: the bf16 result is not available where the route splits K (allow_split = 0 keeps one pass)");
+        RALD_CHECK(!gn_part, "conv3d: no GroupNorm partials (gn_part) where the route splits K");
+        RALD_CHECK(split_ws && (uintptr_t)split_ws % 16 == 0, "conv3d: split-K needs a 16-byte aligned workspace");
+        RALD_CHECK(split_ws_bytes >= (int64_t)r.splits * M * Cout * 4, "conv3d: split-K workspace too small (splits * M * Cout * 4 bytes)");
+    }
+    if (gn_part) {
+        RALD_CHECK(So % 128 == 0, "conv3d: gn_part needs output voxels per sample (So) % 128 == 0, so that no tile straddles two samples");
+        RALD_CHECK(Cout == 64 || Cout == 128 || Cout == 256, "conv3d: gn_part needs Cout of 64, 128 or 256");
+        RALD_CHECK((uintptr_t)gn_part % 8 == 0, "conv3d: gn_part must be 8-byte aligned");
+        a.gn_part = gn_part;
+    }
+    launch_conv(a, r, split_ws, st);
     RALD_HIP(hipGetLastError());
     return 0;
+}
+
+int conv3d_igemm(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, int B, int ID, int IH, int IW,
+                 int Cin, int Cout, int stride, int pad, hipStream_t st, bf16* out_bf16) {
+    return conv3d_full(in, w_packed, bias, resid, out, out_bf16, nullptr, nullptr, 0, 0, B, ID, IH, IW, Cin, Cout, stride, pad, st);
 }
 
 int groupnorm_fwd(const float* x, const float* gamma, const float* beta, bf16* y, double* stats, int B, int S, int C, int swish,
@@ -1448,6 +1509,49 @@ int groupnorm_apply(const float* x, const double* stats, const float* gamma, con
     const int64_t quads = (int64_t)S * C / 4;
     const int blocks = (int)((quads + 255) / 256 < 1024 ? (quads + 255) / 256 : 1024);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks, B), dim3(256), 0, st, x, stats, gamma, beta, y, S, C, 1e-6f, swish ? 1 : 0);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+// gn_finish_kernel on caller partials: stats [B][32][2] = the sums over each sample's nblk slots part[b*nblk + k][32][2] (the route Impl::gn
+// takes when the convolution epilogue left per-tile partials, nblk = S / 128)
+int gn_finish(const double* part, double* stats, int B, int nblk, hipStream_t st) {
+    RALD_CHECK(part && stats, "gn_finish: null pointer");
+    RALD_CHECK(B > 0 && nblk > 0, "gn_finish: B and nblk must be positive");
+    hipLaunchKernelGGL(gn_finish_kernel, dim3(B), dim3(1024), 0, st, part, stats, nblk);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+int upsample2_cast(const float* x, bf16* y, int B, int D, int H, int W, int C, hipStream_t st) {
+    RALD_CHECK(x && y, "upsample2_cast: null pointer");
+    RALD_CHECK(B > 0 && D > 0 && H > 0 && W > 0 && C > 0, "upsample2_cast: bad shape");
+    RALD_CHECK(C % 4 == 0, "upsample2_cast: C must be a multiple of 4 (float4 reads, 4 x bf16 stores)");
+    RALD_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)y % 8 == 0, "upsample2_cast: x must be 16-byte and y 8-byte aligned");
+    const int64_t quads = (int64_t)B * 8 * D * H * W * (C / 4);
+    const unsigned blocks = (unsigned)((quads + 255) / 256 < 8192 ? (quads + 255) / 256 : 8192);
+    hipLaunchKernelGGL(upsample2_cast_kernel, dim3(blocks), dim3(256), 0, st, x, y, B, D, H, W, C);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+int pad_cast64(const float* z, bf16* y, int64_t rows, int zc, hipStream_t st) {
+    RALD_CHECK(z && y, "pad_cast64: null pointer");
+    RALD_CHECK(rows > 0 && rows <= ((int64_t)1 << 31), "pad_cast64: bad row count");
+    RALD_CHECK(zc >= 1 && zc <= 64, "pad_cast64: zc must be in 1 .. 64 (rows of 64 channels)");
+    hipLaunchKernelGGL(pad_cast64_kernel, dim3((unsigned)((rows * 64 + 255) / 256)), dim3(256), 0, st, z, y, rows, zc);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+// the tokeniser half of RadarEncoder::tokens without the encoder: z [B][R*A*E][zc] (R, A, E = the token grid) -> tok [B][R*A*E][C]
+int radar_tokens(const float* z, const float* Wp, const float* bp, const float* re, const float* ae, const float* ee, float* tok, int B, int R, int A,
+                 int E, int zc, int C, hipStream_t st) {
+    RALD_CHECK(z && Wp && bp && re && ae && ee && tok, "radar_tokens: null pointer");
+    RALD_CHECK(B > 0 && B <= 65535 && R > 0 && A > 0 && E > 0 && C > 0, "radar_tokens: bad shape (B <= 65535)");
+    RALD_CHECK(zc >= 1 && zc <= 64, "radar_tokens: zc must be in 1 .. 64");
+    RALD_CHECK((int64_t)R * A * E <= 0x7fffffff, "radar_tokens: too many tokens per sample");
+    hipLaunchKernelGGL(radar_token_kernel, dim3(R * A * E, B), dim3(256), 0, st, z, Wp, bp, re, ae, ee, tok, R, A, E, zc, C);
     RALD_HIP(hipGetLastError());
     return 0;
 }

@@ -25,7 +25,7 @@ epilogue and the key loop's blocks out in program order.  A key loop whose shape
 no LDS-DMA issue behind the barrier) is reported, not passed.
 
     python tools/isa_audit.py [--csrc DIR] [--keep DIR] [--keyloop-all]      exit status 0 = clean, 1 = findings
-    python tools/isa_audit.py --against DIR      compare gemm.hip, gemm_fp8.hip and gemm_ln.hip with another tree's (see compare)
+    python tools/isa_audit.py --against DIR      compare gemm.hip, gemm_fp8.hip, gemm_ln.hip and radar.hip with another tree's (see compare)
 """
 from __future__ import annotations
 
@@ -194,7 +194,7 @@ def audit(csrc: str = CSRC, keep: str | None = None, keyloop_all: bool = False) 
 
 
 # ---- comparison against another source tree (a refactor must leave the hot loops as they were) -----------------------------------
-ENGINE_FILES = ("gemm.hip", "gemm_fp8.hip", "gemm_ln.hip")
+ENGINE_FILES = ("gemm.hip", "gemm_fp8.hip", "gemm_ln.hip", "radar.hip")
 # kernels whose MFMA blocks must not change (None = every value of that template argument): the GEMM entries of HOT and the other
 # shipped tile shapes of the two LDS-DMA GEMMs
 COMPARE_HOT = tuple((k, a) for f, k, a, *_ in HOT if f in ENGINE_FILES) + (
@@ -202,6 +202,9 @@ COMPARE_HOT = tuple((k, a) for f, k, a, *_ in HOT if f in ENGINE_FILES) + (
     ("gemm_nt_glds_kernel", (128, 128, 2, 2, 2, None)), ("gemm_nt_glds_kernel", (64, 128, 2, 2, 3, None)),
     ("gemm_nt_glds_kernel", (64, 64, 2, 2, 8, None)),
 )
+# plain (non-template) kernels held to the same rule, by name: the radar encoder's convolution engines, split-K reduce and GroupNorm
+COMPARE_HOT_PLAIN = ("conv3d_igemm_kernel", "conv3d_line_kernel", "conv3d_plane_kernel", "conv3d_pplane_kernel", "conv_split_reduce_kernel",
+                     "gn_stats_kernel", "gn_finish_kernel", "gn_apply_kernel")
 _RESOURCES = ("NumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")
 _REG = re.compile(r"\b[vsa](\d+|\[\d+:\d+\])|\bttmp\d+")
 _BLOCK_END = re.compile(r"s_c?branch|s_endpgm|s_setpc")
@@ -210,6 +213,12 @@ _BLOCK_END = re.compile(r"s_c?branch|s_endpgm|s_setpc")
 def is_compare_hot(tid) -> bool:
     return tid is not None and any(tid[0] == k and len(tid[1]) == len(a) and all(y is None or x == y for x, y in zip(tid[1], a))
                                    for k, a in COMPARE_HOT)
+
+
+def is_compare_hot_symbol(symbol: str) -> bool:
+    """a plain kernel of COMPARE_HOT_PLAIN, by its mangled symbol (_ZN4rald<len><name>E...)"""
+    m = re.match(r"_ZN4rald(\d+)", symbol)
+    return bool(m) and symbol[m.end():m.end() + int(m.group(1))] in COMPARE_HOT_PLAIN
 
 
 def resources(text: str) -> dict:
@@ -255,7 +264,7 @@ def compare_kernel(old: str, new: str, hot: bool):
 
 
 def compare(csrc: str, against: str, keep: str | None = None) -> int:
-    """Prints the comparison of the LDS-DMA GEMM files of `csrc` with those of `against`; returns the number of kernels with findings."""
+    """Prints the comparison of the LDS-DMA GEMM files and radar.hip of `csrc` with those of `against`; returns the number of kernels with findings."""
     tmp = keep or tempfile.mkdtemp(prefix="isa_audit_")
     bad = 0
     try:
@@ -270,7 +279,7 @@ def compare(csrc: str, against: str, keep: str | None = None) -> int:
             bad += set(old) != set(new)
             for sym in sorted(set(old) & set(new)):
                 tid = template_id(sym)
-                hot = is_compare_hot(tid)
+                hot = is_compare_hot(tid) or is_compare_hot_symbol(sym)
                 findings, notes = compare_kernel(old[sym], new[sym], hot)
                 title = f"{tid[0]}<{','.join(map(str, tid[1]))}>" if tid else sym
                 r = resources(new[sym])
