@@ -117,6 +117,29 @@ int rald_dit_denoise(rald_dit* h, const float* x, int32_t batch, int32_t sigma_r
 int rald_dit_sample(rald_dit* h, const float* latents, int32_t batch, const void* cond_cache, int32_t num_steps,
                     float sigma_min, float sigma_max, float rho, float* out, void* stream);
 
+/* The noise levels of edm_sampler (:246-249, :258-259) on the HOST, fp32 in the reference's operation order: the Karras levels
+ * t [num_steps + 1] (t_N = 0) and t_hat [num_steps], t_hat_i = t_i + gamma * t_i with gamma = min(S_churn / num_steps, sqrt(2) - 1)
+ * where S_min <= t_i <= S_max, else 0.  Step i is CHURNED iff t_hat[i] != t[i].  rald_dit_sample_stochastic uses this function; a
+ * caller asks it which steps need noise.  Needs no GPU.  The scalars are doubles because the reference evaluates sigma^(1/rho) and
+ * S_churn / num_steps as Python floats before they meet fp32 tensors; t agrees with the reference's t_steps bit for bit on the shipped
+ * schedule (rald_dit_sample's own all-fp32 table differs from it by a few ulp and is left as it is). */
+int rald_edm_schedule(int32_t num_steps, double sigma_min, double sigma_max, double rho, double S_churn, double S_min, double S_max, float* t,
+                      float* t_hat);
+/* edm_sampler (:235-275) with S_churn >= 0.  Before the Euler NFE of every churned step i the state is raised to t_hat_i,
+ *   x_hat = x + sqrt(t_hat_i^2 - t_i^2) * S_noise * n_i,
+ * with n_i read from `noise` - [n_churned, B, n_latents, channels], the churned steps only, in step order - or generated in the
+ * same kernel from `seeds` (int64 [B], device; rald_op_philox_normal's stream with tag 1 and step = i).  Exactly one of the two is
+ * non-NULL when a step is churned.  With no churned step this IS rald_dit_sample (same kernels, same bits; noise / seeds ignored).
+ * Enqueues only (no allocation or synchronisation once the batch and the schedule have been seen): the call captures into a hipGraph. */
+int rald_dit_sample_stochastic(rald_dit* h, const float* latents, int32_t batch, const void* cond_cache, int32_t num_steps, double sigma_min,
+                               double sigma_max, double rho, double S_churn, double S_min, double S_max, double S_noise, const float* noise,
+                               const int64_t* seeds, float* out, void* stream);
+/* Counter-based N(0,1) on the device: out [B, n_per_sample] (16-byte aligned; n_per_sample a multiple of 4), a pure function of
+ * (seed, tag, step, element).  Philox4x32-10 with key (seeds[b] mod 2^32, tag) and counter (e / 4, step, 0, 0) gives elements
+ * 4*(e/4) .. +3 by Box-Muller: u1 = ((x >> 8) + 1) * 2^-24, u2 = (y >> 8) * 2^-24, r = sqrtf(-2 logf(u1)), (r cosf(2 pi u2),
+ * r sinf(2 pi u2)) from the word pairs (x0, x1) and (x2, x3).  tag 0 = initial latents, 1 = churn noise.  seeds: int64 [B], device. */
+int rald_op_philox_normal(const int64_t* seeds, int32_t B, int64_t n_per_sample, int32_t tag, int32_t step, float* out, void* stream);
+
 /* Live timing of the dominant kernel (the FF1 GEGLU GEMM, FeedForward :88-117): between begin
  * and end every launch of it inside rald_dit_denoise is bracketed by HIP events recorded on the
  * launch stream (up to 4096 launches); end synchronises those events and returns their sum. */

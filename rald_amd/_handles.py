@@ -156,6 +156,7 @@ class DitHandle(_Handle):
         self._graphs = _GraphCache(lambda: lib().rald_dit_workspace_generation(self._h))
         self._reserved = 0
         self._sched = None
+        self._sched_churn = None
         # Two-stream schedule of an NFE between 128 and 255 samples: which of the two bit-identical schedules is faster depends on the box
         # (clocks under MFMA load differ by ~6 % across the pool; two interleaved half-batches measured +2.5 % on slower boxes and -1.5 % on the
         # fastest).  Opt-in: with autotune_two_stream = True the first NFE of such a batch times both (eight NFEs each way, once per handle
@@ -273,12 +274,16 @@ class DitHandle(_Handle):
                                     sigma_min, sigma_max, rho, out.data_ptr(), _stream()))
 
     def sample(self, latents: torch.Tensor, cache: torch.Tensor, num_steps: int = 18, sigma_min: float = 0.002,
-               sigma_max: float = 80.0, rho: float = 7.0, use_graph: Optional[bool] = None) -> torch.Tensor:
+               sigma_max: float = 80.0, rho: float = 7.0, use_graph: Optional[bool] = None, S_churn: float = 0, S_min: float = 0,
+               S_max: float = float("inf"), S_noise: float = 1, noise: Optional[torch.Tensor] = None,
+               seeds: Optional[torch.Tensor] = None) -> torch.Tensor:
         _need_cuda(latents, "latents")
         latents = _f32c(latents)
         B = latents.shape[0]
         if cache.dtype != torch.uint8 or not cache.is_cuda or cache.numel() != lib().rald_dit_cond_cache_bytes(self._h, B):
             raise RuntimeError(f"condition cache of {cache.numel()} bytes does not belong to a batch of {B}: encode the condition for the same batch")
+        if S_churn != 0:
+            return self._sample_churn(latents, cache, num_steps, sigma_min, sigma_max, rho, use_graph, S_churn, S_min, S_max, S_noise, noise, seeds)
         self.reserve(B)
         sched = (num_steps, float(sigma_min), float(sigma_max), float(rho))
         if sched != self._sched:                       # the sampler's sigma table is rebuilt for a new schedule
@@ -294,8 +299,80 @@ class DitHandle(_Handle):
                                   lambda ins, outs: self._sample_eager(ins[0], ins[1], outs[0], *sched))
         return out
 
+    def _sample_churn_eager(self, latents, cache, out, sched, noise, seeds):
+        check(lib().rald_dit_sample_stochastic(self._h, latents.data_ptr(), latents.shape[0], cache.data_ptr(), *sched, _opt(noise), _opt(seeds),
+                                               out.data_ptr(), _stream()))
+
+    def _sample_churn(self, latents, cache, num_steps, sigma_min, sigma_max, rho, use_graph, S_churn, S_min, S_max, S_noise, noise, seeds):
+        """edm_sampler with S_churn > 0 (rald_dit_sample_stochastic): `noise` [n_churned, B, n_latents, channels] - the churned steps'
+        draws in step order - or `seeds` int64 [B] for noise generated inside the kernel (op_philox_normal's tag 1, step = i)."""
+        if S_churn < 0 or S_noise < 0:
+            raise ValueError("S_churn and S_noise must be >= 0")
+        B = latents.shape[0]
+        sched = (int(num_steps), float(sigma_min), float(sigma_max), float(rho), float(S_churn), float(S_min), float(S_max), float(S_noise))
+        t, t_hat = edm_schedule(*sched[:7])
+        n_churned = int((t_hat != t[:-1]).sum())
+        if n_churned == 0:                             # nothing to add (the levels lie outside [S_min, S_max]): the deterministic loop
+            return self.sample(latents, cache, *sched[:4], use_graph=use_graph)
+        if (noise is None) == (seeds is None):
+            raise ValueError(f"{n_churned} of the {num_steps} steps are churned: pass exactly one of `noise` (host-drawn) and `seeds` (device Philox)")
+        if noise is not None:
+            _need_cuda(noise, "noise")
+            noise = _f32c(noise)
+            if tuple(noise.shape) != (n_churned,) + tuple(latents.shape):
+                raise ValueError(f"noise must be [{n_churned}, {B}, {self.cfg.n_latents}, {self.cfg.channels}] (the churned steps only, in order), "
+                                 f"got {tuple(noise.shape)}")
+            extra, mode = noise, "noise"
+        else:
+            if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int64 and tuple(seeds.shape) == (B,)):
+                raise ValueError(f"seeds must be an int64 [{B}] tensor on the GPU")
+            extra, mode = seeds.contiguous(), "seeds"
+        self.reserve(B)
+        if sched != self._sched_churn:                 # the stochastic sampler's sigma table is rebuilt for a new schedule
+            self._graphs.clear()
+            self._sched_churn = sched
+        if use_graph is None:
+            use_graph = _graphs_enabled() and B <= GRAPH_MAX_BATCH
+
+        def run(lat, cc, ex, out):
+            self._sample_churn_eager(lat, cc, out, sched, ex if mode == "noise" else None, ex if mode == "seeds" else None)
+        if not use_graph:
+            out = torch.empty_like(latents)
+            run(latents, cache, extra, out)
+            return out
+        (out,) = self._graphs.run(("sample_churn", B, mode) + sched, [latents, cache, extra], lambda: [torch.empty_like(latents)],
+                                  lambda ins, outs: run(ins[0], ins[1], ins[2], outs[0]))
+        return out
+
+
+def edm_schedule(num_steps: int, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0, S_churn: float = 0, S_min: float = 0,
+                 S_max: float = float("inf")):
+    """(t [num_steps + 1], t_hat [num_steps]) float32 numpy arrays: the sampler's noise levels as the library computes them
+    (rald_edm_schedule, host arithmetic, needs no GPU).  Step i is churned iff t_hat[i] != t[i]."""
+    import numpy as np
+    if int(num_steps) < 1:
+        raise ValueError("num_steps must be positive")
+    t, t_hat = np.zeros(int(num_steps) + 1, np.float32), np.zeros(int(num_steps), np.float32)
+    check(lib().rald_edm_schedule(int(num_steps), sigma_min, sigma_max, rho, S_churn, S_min, S_max, t.ctypes.data, t_hat.ctypes.data))
+    return t, t_hat
+
 
 # ---- kernel-level wrappers used by the parity tests and microbenchmarks -----------------------
+def op_philox_normal(seeds: torch.Tensor, n_per_sample: int, tag: int = 0, step: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """N(0,1) [B, n_per_sample] from the device generator (rald_amd/csrc/rng.hip): a pure function of (seeds[b] mod 2^32, tag, step, element).
+    seeds int64 [B] on the GPU; tag 0 = initial latents, 1 = churn noise of sampler step `step`."""
+    _need_cuda(seeds, "seeds")
+    if seeds.dtype != torch.int64 or seeds.dim() != 1:
+        raise ValueError("seeds must be an int64 [B] tensor")
+    seeds = seeds.contiguous()
+    B = seeds.shape[0]
+    if out is None:
+        out = torch.empty(B, int(n_per_sample), device=seeds.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() == B * int(n_per_sample)
+    check(lib().rald_op_philox_normal(seeds.data_ptr(), B, int(n_per_sample), int(tag), int(step), out.data_ptr(), _stream()))
+    return out
+
+
 def op_gemm_nt(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
                C_inout: Optional[torch.Tensor] = None, alpha: float = 1.0) -> torch.Tensor:
     """A [batch?,M,K] bf16, B [batch?,N,K] bf16 -> C.  epilogue 0 bf16, 1 f32, 2 f32 accumulate into

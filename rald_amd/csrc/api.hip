@@ -91,6 +91,20 @@ int rald_dit_sample(rald_dit* h, const float* latents, int32_t batch, const void
     RALD_CHECK(h && latents && cond_cache && out && batch >= 1, "rald_dit_sample: bad argument");
     return h->impl.sample(latents, batch, cond_cache, num_steps, sigma_min, sigma_max, rho, out, (hipStream_t)stream);
 }
+int rald_edm_schedule(int32_t num_steps, double sigma_min, double sigma_max, double rho, double S_churn, double S_min, double S_max, float* t,
+                      float* t_hat) {
+    return edm_schedule(num_steps, sigma_min, sigma_max, rho, S_churn, S_min, S_max, t, t_hat);
+}
+int rald_dit_sample_stochastic(rald_dit* h, const float* latents, int32_t batch, const void* cond_cache, int32_t num_steps, double sigma_min,
+                               double sigma_max, double rho, double S_churn, double S_min, double S_max, double S_noise, const float* noise,
+                               const int64_t* seeds, float* out, void* stream) {
+    RALD_CHECK(h && latents && cond_cache && out && batch >= 1, "rald_dit_sample_stochastic: bad argument");
+    return h->impl.sample_stochastic(latents, batch, cond_cache, num_steps, sigma_min, sigma_max, rho, S_churn, S_min, S_max, S_noise, noise,
+                                     seeds, out, (hipStream_t)stream);
+}
+int rald_op_philox_normal(const int64_t* seeds, int32_t B, int64_t n_per_sample, int32_t tag, int32_t step, float* out, void* stream) {
+    return philox_normal(seeds, B, n_per_sample, tag, step, out, (hipStream_t)stream);
+}
 
 int rald_dit_profile_begin(rald_dit* h) { RALD_CHECK(h, "null handle"); h->impl.prof_mask = 0xf; return h->impl.profile_begin(); }
 int rald_dit_profile_set_kinds(rald_dit* h, uint32_t kind_mask) {

@@ -91,7 +91,8 @@ struct Dit {
     RadarEncoder radar;
     std::set<std::string> expected, loaded;
     bool finalized = false;
-    // noise-level tables: slot 0 = ad-hoc (rald_dit_set_sigmas / forward), slot 1 = the sampler's schedule.
+    // noise-level tables: slot 0 = ad-hoc (rald_dit_set_sigmas / forward), slot 1 = the sampler's schedule, slot 2 = the stochastic
+    // sampler's (t_hat_i and t_{i+1} interleaved).
     // Separate slots so that a captured hipGraph of the sampler keeps pointing at valid modulations
     // even if forward() is called with other sigmas in between.
     struct SigmaTable {
@@ -100,7 +101,7 @@ struct Dit {
         int n = 0, cap = 0;
         float *sigma = nullptr, *coef = nullptr, *cnoise = nullptr, *pe = nullptr, *temb0 = nullptr, *temb = nullptr, *mod = nullptr;
     };
-    SigmaTable tables[2];
+    SigmaTable tables[3];
     int build_table(SigmaTable& t, const float* sig, int n, hipStream_t st);
     int64_t mod_row() const { return (int64_t)cfg.depth * 3 * 2 * D; }
     // activation workspace.  ws_generation counts every reallocation of a buffer that a captured hipGraph may point
@@ -175,6 +176,9 @@ struct Dit {
                       hipStream_t st, int slot, Work& w, bool timed_ok);
     int sample(const float* latents, int B, const void* cache, int num_steps, float smin, float smax, float rho, float* out,
                hipStream_t st);
+    // edm_sampler with churn: `noise` [n_churned, B, n_latents, channels] (host-drawn) or `seeds` [B] int64 (drawn in the kernel), device pointers
+    int sample_stochastic(const float* latents, int B, const void* cache, int num_steps, double smin, double smax, double rho, double S_churn,
+                          double S_min, double S_max, double S_noise, const float* noise, const int64_t* seeds, float* out, hipStream_t st);
 };
 
 }  // namespace rald

@@ -244,6 +244,7 @@ int Dit::load_weight(const std::string& name, const float* data, int64_t nelem) 
     loaded.insert(name);
     tables[0].key.clear();   // any cached table depends on the weights
     tables[1].key.clear();
+    tables[2].key.clear();
     return 0;
 }
 
@@ -718,6 +719,53 @@ int Dit::sample(const float* latents, int B, const void* cache, int num_steps, f
         if (!last) {                                                                 // 2nd-order correction (:269-273)
             RALD_TRY(denoise(ws_xeul, B, i + 1, 0, cache, ws_den, 0, st, 1));
             RALD_TRY(heun_correct(ws_xcur, ws_xeul, ws_den, ws_dcur, tc, tn, ws_xcur, n, st));   // in place, elementwise
+        }
+    }
+    return 0;
+}
+
+// edm_sampler with S_churn > 0 (:254-273).  Step i raises the noise level from t_i to t_hat_i by adding fresh noise (:258-260), runs its
+// Euler NFE at t_hat_i and its correction NFE at t_{i+1}: sigma-table row 2i = t_hat_i, row 2i+1 = t_{i+1} (2*num_steps - 1 rows, table slot 2,
+// so the deterministic sampler's table and the graphs captured over it stay valid).  `noise` holds the churned steps only, in step order.
+int Dit::sample_stochastic(const float* latents, int B, const void* cache, int num_steps, double smin, double smax, double rho, double S_churn,
+                           double S_min, double S_max, double S_noise, const float* noise, const int64_t* seeds, float* out, hipStream_t st) {
+#pragma clang fp contract(off)
+    RALD_CHECK(num_steps >= 2 && num_steps <= 2048, "dit: num_steps must be in [2,2048]");
+    RALD_CHECK(S_churn >= 0.0 && S_noise >= 0.0, "dit: S_churn and S_noise must be >= 0");
+    std::vector<float> t(num_steps + 1), th(num_steps);
+    RALD_TRY(edm_schedule(num_steps, smin, smax, rho, S_churn, S_min, S_max, t.data(), th.data()));
+    int n_churned = 0;
+    for (int i = 0; i < num_steps; ++i) n_churned += th[i] != t[i];
+    if (n_churned == 0) return sample(latents, B, cache, num_steps, (float)smin, (float)smax, (float)rho, out, st);
+    RALD_CHECK((noise != nullptr) != (seeds != nullptr),
+               "dit: a churned step needs its noise: pass exactly one of `noise` (host-drawn, compact) and `seeds` (drawn on the device)");
+    const int64_t per = (int64_t)cfg.n_latents * cfg.channels;
+    RALD_CHECK(per % 4 == 0, "dit: n_latents*channels must be a multiple of 4 for the churn step");
+    RALD_TRY(cond_registry.check(cache, cond_header(B), st, "condition cache"));
+    std::vector<float> rows(2 * num_steps - 1);
+    for (int i = 0; i < num_steps; ++i) {
+        rows[2 * i] = th[i];
+        if (i + 1 < num_steps) rows[2 * i + 1] = t[i + 1];
+    }
+    RALD_TRY(reserve(B));
+    RALD_TRY(build_table(tables[2], rows.data(), (int)rows.size(), st));
+    const int64_t n = (int64_t)B * per;
+    RALD_TRY(scale_f32(latents, ws_xcur, t[0], n, st));                              // x_next = latents * t_0
+    int k = 0;                                                                       // index of the next churned step inside `noise`
+    for (int i = 0; i < num_steps; ++i) {
+        const float tc = t[i], thi = th[i], tn = t[i + 1];
+        if (thi != tc) {                                                             // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) * S_noise * n   (:260)
+            const float a = thi * thi, b = tc * tc;
+            const float scale = sqrtf(a - b) * (float)S_noise;
+            RALD_TRY(churn_noise(ws_xcur, noise ? noise + (int64_t)k * n : nullptr, seeds, B, per, i, scale, st));
+            ++k;
+        }
+        RALD_TRY(denoise(ws_xcur, B, 2 * i, 0, cache, ws_den, 0, st, 2));            // Euler step (:263-266)
+        const bool last = i == num_steps - 1;
+        RALD_TRY(heun_euler(ws_xcur, ws_den, thi, tn, ws_dcur, last ? out : ws_xeul, n, st));
+        if (!last) {                                                                 // 2nd-order correction (:269-273)
+            RALD_TRY(denoise(ws_xeul, B, 2 * i + 1, 0, cache, ws_den, 0, st, 2));
+            RALD_TRY(heun_correct(ws_xcur, ws_xeul, ws_den, ws_dcur, thi, tn, ws_xcur, n, st));
         }
     }
     return 0;

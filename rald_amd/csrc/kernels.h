@@ -217,6 +217,14 @@ int heun_euler(const float* x_hat, const float* denoised, float t_hat, float t_n
 int heun_correct(const float* x_hat, const float* x_euler, const float* denoised, const float* d_cur,
                  float t_hat, float t_next, float* x_next, int64_t n, hipStream_t st);
 
+// ---------------------------------------------------------------- rng.hip
+// out[b][0:n_per_sample] = N(0,1) from Philox4x32-10, key (seeds[b] mod 2^32, tag), counter (element / 4, step, 0, 0); seeds on the device
+int philox_normal(const int64_t* seeds, int B, int64_t n_per_sample, int tag, int step, float* out, hipStream_t st);
+// the churn step of edm_sampler (:260) in place: x[b] += scale * n[b], n = noise [B][n_per_sample] or generated from seeds (tag 1, `step`)
+int churn_noise(float* x, const float* noise, const int64_t* seeds, int B, int64_t n_per_sample, int step, float scale, hipStream_t st);
+// host: Karras levels t [num_steps + 1] (t_N = 0) and churned levels t_hat [num_steps] (:246-249, :258-259)
+int edm_schedule(int num_steps, double smin, double smax, double rho, double S_churn, double S_min, double S_max, float* t, float* t_hat);
+
 // ---------------------------------------------------------------- ae_kernels.hip
 int point_features(const float* pts, const float* basis, bf16* feat, int64_t n, hipStream_t st);
 int softmax_rows(const float* S, int64_t ld_s, bf16* P, int64_t ld_p, int rows, int n, hipStream_t st);

@@ -17,12 +17,13 @@ from . import query_points as QP
 
 @torch.no_grad()
 def sample_and_decode(model, vae, radar_cube: torch.Tensor, query_sets: Sequence[torch.Tensor],
-                      batch_seeds: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                      batch_seeds: Optional[torch.Tensor] = None, sampler_kwargs: Optional[dict] = None) -> Dict[str, object]:
     """One evaluation batch on ONE rank: `model.sample` (18 Heun steps, condition encoded once),
     then every query set decoded against the same latents (the 24-layer latent stack runs once:
-    rald_amd.models_ae memoises the decoder context per latent tensor).
+    rald_amd.models_ae memoises the decoder context per latent tensor).  `sampler_kwargs` goes to `model.sample`
+    (num_steps, S_churn, S_min, S_max, S_noise, rng).
     Returns {'latents': [B,512,C], 'logits': [ [B,Q_i] ... ], 'occupied': [bool masks]}."""
-    sampled = model.sample(cond=radar_cube, batch_seeds=batch_seeds, cond_type='radar')        # :195
+    sampled = model.sample(cond=radar_cube, batch_seeds=batch_seeds, cond_type='radar', **(sampler_kwargs or {}))        # :195
     logits = [vae.decode(sampled, q).squeeze(-1) for q in query_sets]                          # :204, :275, :300
     return {"latents": sampled, "logits": logits, "occupied": [l > 0 for l in logits]}        # :229-232
 
@@ -271,11 +272,12 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
 
 @torch.no_grad()
 def evaluate_sharded(model, vae, cubes: torch.Tensor, queries: torch.Tensor, eval_batch_size: int = 1,
-                     metric_fn: Optional[Callable[[torch.Tensor, int], float]] = None) -> Dict[str, float]:
+                     metric_fn: Optional[Callable[[torch.Tensor, int], float]] = None,
+                     sampler_kwargs: Optional[dict] = None) -> Dict[str, float]:
     """Batch-sharded evaluation: every rank owns the samples DistributedSampler would give it,
     runs them in eval batches with seeds = global sample index, and the only collective is the
     final metric reduction (utils/misc.py:45-47).  `cubes` [N,R,A,E,2] and `queries` [N,Q,3] are the
-    full (host) arrays; each rank moves only its shard to the device."""
+    full (host) arrays; each rank moves only its shard to the device.  `sampler_kwargs`: see sample_and_decode."""
     rank = torch.distributed.get_rank() if D.is_dist() else 0
     world = D.world_size()
     mine = D.shard_sample_indices(cubes.shape[0], rank, world)
@@ -285,7 +287,7 @@ def evaluate_sharded(model, vae, cubes: torch.Tensor, queries: torch.Tensor, eva
     for i in range(0, len(mine), eval_batch_size):
         idx = mine[i:i + eval_batch_size]
         out = sample_and_decode(model, vae, cubes[idx].to(dev), [queries[idx].to(dev)],
-                                batch_seeds=torch.tensor(idx))
+                                batch_seeds=torch.tensor(idx), sampler_kwargs=sampler_kwargs)
         occ = out["occupied"][0].float().mean(dim=1)
         for j, gi in enumerate(idx):
             val = metric_fn(out["logits"][0][j], gi) if metric_fn else float(occ[j])

@@ -172,18 +172,42 @@ class LatentArrayTransformer(_HipBacked):
 # ----------------------------------------------------------------------------------------------
 # sampler / loss / RNG helpers
 # ----------------------------------------------------------------------------------------------
+def _churn_inputs(randn_like, latents, num_steps, sigma_min, sigma_max, rho, S_churn, S_min, S_max, S_noise) -> dict:
+    """The noise arguments of a churned sampler call, `{'noise': ...}` or `{'seeds': ...}` (+ the four churn values).
+    `randn_like(latents)` is called once per step, in step order, churned or not - the reference consumes its generators that way
+    (:260, where an unchurned step multiplies its draw by 0) and parity with its CPU streams depends on it - and the churned steps'
+    draws are kept, stacked in order.  The bound `randn_like` of a PhiloxGenerator draws nothing here: its seeds go to the library."""
+    from ._handles import edm_schedule
+    kw = dict(S_churn=S_churn, S_min=S_min, S_max=S_max, S_noise=S_noise)
+    gen = getattr(randn_like, "__self__", None)
+    if isinstance(gen, PhiloxGenerator) and getattr(randn_like, "__func__", None) is PhiloxGenerator.randn_like:
+        return dict(kw, seeds=gen.seeds)
+    t, t_hat = edm_schedule(num_steps, sigma_min, sigma_max, rho, S_churn, S_min, S_max)
+    kept = []
+    for i in range(num_steps):
+        n = randn_like(latents)
+        if t_hat[i] != t[i]:
+            kept.append(n)
+    return dict(kw, noise=torch.stack(kept) if kept else None)
+
+
 def edm_sampler(net, latents, class_labels=None, cond_type=None, randn_like=torch.randn_like,
                 num_steps=18, sigma_min=0.002, sigma_max=80, rho=7,
                 S_churn=0, S_min=0, S_max=float('inf'), S_noise=1):
-    """Same signature as the reference (:235-240).  With the shipped S_churn=0 the whole loop
-    (2*num_steps-1 NFEs + Heun updates) runs inside librald_hip.so with the radar condition
-    encoded once; `randn_like` is never consumed because the reference multiplies it by exactly
-    0 (:258-260).  S_churn > 0 is not on the reference's path and is rejected."""
-    if S_churn != 0:
-        raise NotImplementedError("S_churn > 0: the reference ships S_churn=0 (:239)")
+    """Same signature as the reference (:235-240).  The whole loop (2*num_steps-1 NFEs + Heun updates, and with S_churn > 0 the
+    noise injection of :258-260) runs inside librald_hip.so with the radar condition encoded once.  With the shipped S_churn=0
+    `randn_like` is never consumed because the reference multiplies it by exactly 0 (:258-260); with S_churn > 0 it is called once
+    per step like the reference does (see _churn_inputs), or - for a PhiloxGenerator's - replaced by noise generated on the device."""
+    if class_labels is None:
+        raise NotImplementedError("unconditional sampling is not a reference path (class_labels is always the radar cube)")
+    if S_churn < 0 or S_noise < 0:
+        raise ValueError("S_churn and S_noise must be >= 0")
     sigma_min = max(sigma_min, net.sigma_min)
     sigma_max = min(sigma_max, net.sigma_max)
-    return net._sample_from(latents, class_labels, cond_type, num_steps, sigma_min, sigma_max, rho)
+    if S_churn == 0:
+        return net._sample_from(latents, class_labels, cond_type, num_steps, sigma_min, sigma_max, rho)
+    churn = _churn_inputs(randn_like, latents, num_steps, sigma_min, sigma_max, rho, S_churn, S_min, S_max, S_noise)
+    return net._sample_from(latents, class_labels, cond_type, num_steps, sigma_min, sigma_max, rho, **churn)
 
 
 class _EdmDenoiseFn(torch.autograd.Function):
@@ -256,6 +280,26 @@ class StackedRandomGenerator:
         assert size[0] == len(self.generators)
         kwargs.pop("device", None)
         return torch.stack([torch.randint(*args, size=size[1:], generator=gen, **kwargs) for gen in self.generators]).to(self.device)
+
+
+class PhiloxGenerator:
+    """The device counterpart of StackedRandomGenerator: per-sample seeds, but the numbers come from the library's counter-based
+    generator (rald_amd/csrc/rng.hip) - a pure function of (seed mod 2^32, purpose, step, element), no state, no host draw, no copy.
+    `randn` draws with tag 0 (initial latents), `randn_like` with tag 1 (churn noise of sampler step `step`).  Handed to `edm_sampler`
+    as `randn_like=gen.randn_like` it is not called at all: the seeds go to the library, which generates the same numbers inside the
+    churn kernel.  Not the reference's stream: results differ from a StackedRandomGenerator's for the same seeds."""
+
+    def __init__(self, device, seeds):
+        self.device = device
+        self.seeds = torch.as_tensor(seeds).to(torch.int64).reshape(-1).to(device)
+
+    def randn(self, size, step=0, tag=0, **kwargs):
+        from ._handles import op_philox_normal
+        assert size[0] == self.seeds.shape[0]
+        return op_philox_normal(self.seeds, int(np.prod(size[1:])), tag, step).view(*size)
+
+    def randn_like(self, input, step=0):
+        return self.randn(tuple(input.shape), step=step, tag=1)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -379,12 +423,20 @@ class EDMPrecond(_HipBacked):
     def round_sigma(self, sigma):
         return torch.as_tensor(sigma)
 
-    def _sample_from(self, latents, cond, cond_type, num_steps, sigma_min, sigma_max, rho):
+    def _sample_from(self, latents, cond, cond_type, num_steps, sigma_min, sigma_max, rho, **churn):
+        """`churn`: S_churn / S_min / S_max / S_noise + `noise` or `seeds` of a stochastic call (edm_sampler), empty otherwise."""
         if cond_type != 'radar':
             raise NotImplementedError("cond_type must be 'radar'")
         h = self._handle()
         _, cache = self._cond(cond, h)
-        return h.sample(latents, cache, num_steps, float(sigma_min), float(sigma_max), float(rho))
+        return h.sample(latents, cache, num_steps, float(sigma_min), float(sigma_max), float(rho), **churn)
+
+    def _generator(self, rng: str, device, seeds):
+        if rng == 'host':
+            return StackedRandomGenerator(device, seeds)
+        if rng == 'device':
+            return PhiloxGenerator(device, seeds)
+        raise ValueError("rng must be 'host' (the reference's per-sample CPU streams) or 'device' (Philox noise generated on the GPU)")
 
     def _replica(self, i: int) -> DitHandle:
         """i-th independent C handle over the same parameters (0 = the module's own): a handle runs one stream at a time."""
@@ -399,7 +451,8 @@ class EDMPrecond(_HipBacked):
         return reps[i][0]
 
     @torch.no_grad()
-    def sample_concurrent(self, conds, batch_seeds=None, cond_type=None, num_steps=18):
+    def sample_concurrent(self, conds, batch_seeds=None, cond_type=None, num_steps=18, *, S_churn=0, S_min=0, S_max=float('inf'), S_noise=1,
+                          rng='host'):
         """`[self.sample(c, s, cond_type) for c, s in zip(conds, batch_seeds)]` - same values, bit for bit - with every
         condition batch on its own HIP stream and handle replica.  Not a reference API: the reference's evaluate loop
         (engine_generation.py:186-232) samples its batches one after the other.  All kernels of one launch run the same
@@ -411,6 +464,9 @@ class EDMPrecond(_HipBacked):
         seeds = list(batch_seeds) if batch_seeds is not None else [None] * len(conds)
         if len(seeds) != len(conds):
             raise ValueError("one seed tensor (or None) per condition batch")
+        if S_churn < 0 or S_noise < 0:
+            raise ValueError("S_churn and S_noise must be >= 0")
+        smin, smax = float(max(0.002, self.sigma_min)), float(min(80, self.sigma_max))
         cur = torch.cuda.current_stream()
         streams = self.__dict__.setdefault("_streams", [])
         while len(streams) < len(conds):
@@ -419,17 +475,20 @@ class EDMPrecond(_HipBacked):
         for i, (cond, sd) in enumerate(zip(conds, seeds)):
             if sd is None:
                 sd = torch.arange(cond.shape[0])
-            rnd = StackedRandomGenerator(cond.device, sd)
+            rnd = self._generator(rng, cond.device, sd)
             latents = rnd.randn([cond.shape[0], self.n_latents, self.channels])
+            churn = _churn_inputs(rnd.randn_like, latents, num_steps, smin, smax, 7.0, S_churn, S_min, S_max, S_noise) if S_churn != 0 else {}
             h = self._replica(i)
             streams[i].wait_stream(cur)
             with torch.cuda.stream(streams[i]):
                 _, cache = h.encode_cond(cond, want_tokens=False)
                 # graph replays of different streams overlap less than eager launches do (measured: two batches of 8 take
                 # 248 ms replayed, 223 ms eager, 241 ms one after the other), so only latency-bound batches replay a graph
-                out = h.sample(latents, cache, num_steps, float(max(0.002, self.sigma_min)), float(min(80, self.sigma_max)), 7.0,
-                               use_graph=None if cond.shape[0] <= 4 else False)
+                out = h.sample(latents, cache, num_steps, smin, smax, 7.0, use_graph=None if cond.shape[0] <= 4 else False, **churn)
             latents.record_stream(streams[i])          # allocated on the caller's stream, consumed on the side stream
+            for extra in (churn.get("noise"), churn.get("seeds")):
+                if extra is not None:
+                    extra.record_stream(streams[i])
             out.record_stream(cur)                     # ... and the other way round
             outs.append(out)
         for st in streams[:len(conds)]:
@@ -437,16 +496,20 @@ class EDMPrecond(_HipBacked):
         return outs
 
     @torch.no_grad()
-    def sample(self, cond, batch_seeds=None, cond_type=None):
+    def sample(self, cond, batch_seeds=None, cond_type=None, *, num_steps=18, S_churn=0, S_min=0, S_max=float('inf'), S_noise=1, rng='host'):
+        """The reference's `sample` (:435-449); the keyword arguments are additions.  rng='host': initial latents and churn noise from the
+        reference's per-sample CPU streams (the reference's numbers; with S_churn=0 exactly the call the reference makes); rng='device':
+        both from the library's Philox generator on the GPU (tag 0 / tag 1), no host draw and no copy."""
         if cond is not None:
             batch_size, device = cond.shape[0], cond.device
             if batch_seeds is None:
                 batch_seeds = torch.arange(batch_size)
         else:
             raise NotImplementedError("unconditional sampling is not a reference path (cond is always the radar cube)")
-        rnd = StackedRandomGenerator(device, batch_seeds)
+        rnd = self._generator(rng, device, batch_seeds)
         latents = rnd.randn([batch_size, self.n_latents, self.channels])
-        return edm_sampler(self, latents, cond, cond_type, randn_like=rnd.randn_like)
+        return edm_sampler(self, latents, cond, cond_type, randn_like=rnd.randn_like, num_steps=num_steps,
+                           S_churn=S_churn, S_min=S_min, S_max=S_max, S_noise=S_noise)
 
 
 # ---- factories (:452-482) --------------------------------------------------------------------
