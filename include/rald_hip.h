@@ -588,6 +588,19 @@ int rald_op_attn_self_proj(const void* qkv_bf16, int64_t ld, const void* Wo_bf16
 int rald_op_xattn_q2_proj(const void* h_bf16, const void* Wq_bf16, const void* Kc_bf16, int64_t ldk, int64_t strideK, const void* Vt_bf16,
                           int64_t ldvt, int64_t strideVt, const void* Wo_bf16, float* part, int32_t M, int32_t n_latents, int32_t heads,
                           int32_t n_keys, float qscale, void* stream);
+/* The same two sub-blocks and the slab reduction with the slab type as an argument (tests): part_f16 != 0 = the slabs are fp16 holding
+ * 2^-6 x the value, saturated at +-65504 (+-4.19e6 in value), as the models run these kernels; `part` then points at halves and
+ * slab_stride counts halves.  fp16 slabs are reduced in eights (one per head) or fours.  rald_debug_f16_saturation_attn: the number of
+ * 4-element groups the two sub-blocks clamped since the last reset (reset != 0 clears it); synchronises the device; -1 on error. */
+int rald_op_attn_self_proj_slabs(const void* qkv_bf16, int64_t ld, const void* Wo_bf16, void* part, int32_t n_latents, int32_t heads, int32_t batch,
+                                 int32_t part_f16, void* stream);
+int rald_op_xattn_q2_proj_slabs(const void* h_bf16, const void* Wq_bf16, const void* Kc_bf16, int64_t ldk, int64_t strideK, const void* Vt_bf16,
+                                int64_t ldvt, int64_t strideVt, const void* Wo_bf16, void* part, int32_t M, int32_t n_latents, int32_t heads,
+                                int32_t n_keys, float qscale, int32_t part_f16, void* stream);
+int rald_op_reduce_resid_ln_slabs(const void* part, int32_t slabs, int64_t slab_stride, const float* bias, float* x, void* h_bf16, int32_t M,
+                                  const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps, int32_t part_f16,
+                                  void* stream);
+int64_t rald_debug_f16_saturation_attn(int32_t reset);
 /* The denoiser's first and last layers (LatentArrayTransformer.forward :221, :230-232, fused with the EDM coefficients :424-429; norm.hip),
  * fp32 throughout.  coef[s][coef_stride] = {c_in, c_skip, c_out, ...} of the sample s = row / rows_per_group.
  *   proj_in:         x[m][n] = c_in * sum_k xin[m][k] W[n][k]                                   W [D][C]
@@ -622,7 +635,8 @@ int rald_op_ae_decode(const float* x, const float* gamma, const float* beta, con
  *   2-8, 10, 11 may be null when mix == 0).  out[7] (any may be null) = variance factor [52,52], mix queries [M,I], T4 [d,I], X0 [M,d],
  *   T1 [d,64], T3 [d,64], c3 [d] - see ae_encode.hip for what each multiplies.
  * _features: F, G fp16 [batch][rows_per_sample][64] from pc [batch][n_points][3] (rows_per_sample = n_points rounded up to 64).
- * rald_op_attention_f16kv: the attention kernel's fp16 form on such rows (fp32 queries already times scale*log2(e); ksplit < 0 = pick;
+ * rald_op_attention_f16kv: the attention kernel's fp16 form on such rows (rows nk .. k_rows-1 must be ZERO, as _features writes them; fp32
+ *   queries already times scale*log2(e); ksplit < 0 = pick;
  *   scratch = rald_op_attention_split_scratch_bytes(16, ...) when the keys may be split). */
 int rald_op_ae_encode_tables(int32_t dim, int32_t num_latents, int32_t heads, int32_t mix, const float* const* in, float* const* out);
 int rald_op_ae_enc_features(const float* pc, const float* basis, const float* var_factor, void* F_f16, void* G_f16, int32_t batch, int32_t n_points,
@@ -658,10 +672,27 @@ int rald_op_attention_split(const void* Q, int64_t ldq, int64_t strideQ, const v
                             int64_t strideVt, void* O, int64_t ldo, int64_t strideO, int32_t nq, int32_t nk, int32_t k_rows, int32_t heads,
                             int32_t batch, float scale, int32_t ksplit, void* scratch, void* stream);
 /* rald_op_attention with V row-major like K (V[b][j][h*64+d], e.g. a column slice of a fused q|k|v projection): the kernel
- * transposes it on the LDS read (ds_read_b64_tr_b16).  nk % 64 == 0. */
+ * transposes it on the LDS read (ds_read_b64_tr_b16).  nk % 64 == 0 (rald_op_attention_args takes a ragged nk with a zero pad). */
 int rald_op_attention_vrow(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK, const void* V, int64_t ldv,
                            int64_t strideV, void* O, int64_t ldo, int64_t strideO, int32_t nq, int32_t nk, int32_t heads, int32_t batch, float scale,
                            void* stream);
+/* The attention kernel with every field of its argument block from the caller (tests; the entries above fix some of them).
+ *   queries   Q_bf16 [b][i][h*64+d], or Qf fp32 with f16 != 0 (the fp16 form: K and V hold fp16, q_prescaled and a row-major V required);
+ *             strideQ = 0 shares one set of queries between the batch entries
+ *   keys      K [b][j][h*hsk+d], hsk = 64, or 0 = every head reads the same 64 columns (of K and of V / Vt); k_rows >= nk rounded up to
+ *             64 rows are allocated per batch entry and read; rows nk.. may hold any finite values (they are masked)
+ *   values    Vt [b][h*hsk+d][j] with ldvt >= nk rounded up to 64, columns nk.. any finite values; or V [b][j][h*hsk+d] row-major with
+ *             nk % 64 == 0, or with v_padded != 0 and rows nk .. k_rows-1 ZERO (the pad contract of the row-major and fp16 forms)
+ *   output    O_bf16 [b][i][h*64+d]; only columns h*64 .. h*64+63 of rows 0 .. nq-1 are written (ldo may be wider)
+ *   q_prescaled != 0: the queries already carry scale*log2(e) and `scale` is ignored
+ *   ksplit    0 / 1 = one pass; 2..64 = that many key ranges per query block + the combine pass; < 0 = pick from the shape;
+ *             scratch (8-byte aligned) of rald_op_attention_split_scratch_bytes(ksplit, nq, heads, batch) bytes when the keys are split
+ * nq % 32 == 0; leading dimensions multiples of 8 elements; 16-byte aligned pointers. */
+int rald_op_attention_args(const void* Q_bf16, const float* Qf, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
+                           int32_t k_rows, const void* Vt, int64_t ldvt, int64_t strideVt, const void* V, int64_t ldv, int64_t strideV, void* O_bf16,
+                           int64_t ldo, int64_t strideO, int32_t nq, int32_t nk, int32_t heads, int32_t batch, float scale, int32_t q_prescaled,
+                           int32_t f16, int32_t hsk, int32_t v_padded, int32_t ksplit, void* scratch, int64_t scratch_bytes, void* stream);
+int32_t rald_op_attention_pick_ksplit(int32_t nq, int32_t nk, int32_t heads, int32_t batch);
 /* gradients of rald_op_attention_vrow's O = softmax(Q K^T scale) V per head (torch autograd of CrossAttention,
  * model/models_radar_generation.py:66-75, in the training step engine_generation.py:74-98): dQ, dK, dV bf16 in the layouts of Q, K, V
  * (own leading dimensions and batch strides: column slices of fused buffers are fine).  Two launches, nothing score-shaped in memory.

@@ -553,6 +553,58 @@ def op_attention_f16kv(Q: torch.Tensor, KV: torch.Tensor, nk: int, heads: int, k
     return O
 
 
+def op_attention_args(O: torch.Tensor, K: torch.Tensor, nq: int, nk: int, heads: int, k_rows: int, Q: Optional[torch.Tensor] = None,
+                      Qf: Optional[torch.Tensor] = None, Vt: Optional[torch.Tensor] = None, V: Optional[torch.Tensor] = None, scale: float = 1.0,
+                      q_prescaled: bool = False, f16: bool = False, hsk: int = 64, v_padded: bool = False, ksplit: int = 0,
+                      scratch: Optional[torch.Tensor] = None, strideQ: Optional[int] = None) -> None:
+    """attention_d64 with every field of its argument block: O / K / Q or Qf / Vt or V are 3-D views [batch, rows, columns] (column and
+    row slices of wider buffers are fine: leading dimensions and batch strides are the views' strides; strideQ = 0 shares the queries),
+    written into the caller's O.  ksplit < 0 = pick; `scratch` is needed when the keys are split."""
+    q = Q if Q is not None else Qf
+    v = Vt if Vt is not None else V
+    sv = (v.stride(1), v.stride(0))
+    check(lib().rald_op_attention_args(_opt(Q), _opt(Qf), q.stride(1), q.stride(0) if strideQ is None else strideQ, K.data_ptr(), K.stride(1),
+                                       K.stride(0), k_rows, _opt(Vt), *(sv if Vt is not None else (0, 0)), _opt(V), *(sv if V is not None else (0, 0)),
+                                       O.data_ptr(), O.stride(1), O.stride(0), nq, nk, heads, O.shape[0], scale, int(q_prescaled), int(f16), hsk,
+                                       int(v_padded), ksplit, _opt(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size(),
+                                       _stream()))
+
+
+def op_attn_self_proj(qkv: torch.Tensor, Wo: torch.Tensor, part: torch.Tensor, n_latents: int, heads: int, batch: int, ld: Optional[int] = None,
+                      part_f16: Optional[bool] = None) -> None:
+    """part [heads, batch*n_latents, 512] (fp32, or fp16 holding 2^-6 x the value) = per head softmax(q k^T) v . Wo[:, 64h:64h+64]^T of the
+    fused q|k|v rows qkv [batch*n_latents, ld] (q pre-multiplied by scale*log2 e)."""
+    f16 = part.dtype == torch.float16 if part_f16 is None else part_f16
+    check(lib().rald_op_attn_self_proj_slabs(qkv.data_ptr(), qkv.stride(0) if ld is None else ld, Wo.data_ptr(), part.data_ptr(), n_latents, heads,
+                                             batch, int(f16), _stream()))
+
+
+def op_xattn_q2_proj(hin: torch.Tensor, Wq: torch.Tensor, Kc: torch.Tensor, Vt: torch.Tensor, Wo: torch.Tensor, part: torch.Tensor, n_latents: int,
+                     qscale: float, heads: int = 8, n_keys: int = 64, part_f16: Optional[bool] = None) -> None:
+    """part [heads, M, 512] = per head softmax(qscale to_q(hin) Kc^T) Vc . Wo[:, 64h:64h+64]^T; Kc [batch, 64, >= 512] and Vt [batch, >= 512, 64]
+    are views of the condition cache (this block's 512 columns / rows)."""
+    f16 = part.dtype == torch.float16 if part_f16 is None else part_f16
+    check(lib().rald_op_xattn_q2_proj_slabs(hin.data_ptr(), Wq.data_ptr(), Kc.data_ptr(), Kc.stride(1), Kc.stride(0), Vt.data_ptr(), Vt.stride(1),
+                                            Vt.stride(0), Wo.data_ptr(), part.data_ptr(), hin.shape[0], n_latents, heads, n_keys, qscale, int(f16),
+                                            _stream()))
+
+
+def op_reduce_resid_ln(part: torch.Tensor, bias: torch.Tensor, x: torch.Tensor, h: Optional[torch.Tensor] = None, g: Optional[torch.Tensor] = None,
+                       b: Optional[torch.Tensor] = None, gstride: int = 0, rows_per_group: int = 1 << 30, add_one: float = 0.0,
+                       eps: float = 1e-5) -> None:
+    """x [M,512] f32 += bias + sum_s part[s] in place (part [S, M, 512] fp32, or fp16 holding 2^-6 x the value); h = LN(x)*(add_one+g)+b."""
+    check(lib().rald_op_reduce_resid_ln_slabs(part.data_ptr(), part.shape[0], part.stride(0), bias.data_ptr(), x.data_ptr(), _opt(h), x.shape[0],
+                                              _opt(g), _opt(b), gstride, rows_per_group, add_one, eps, int(part.dtype == torch.float16), _stream()))
+
+
+def f16_saturation_attn(reset: bool = True) -> int:
+    """4-element groups of fp16 slab values that attn_self_proj / xattn_q2_proj clamped since the last reset (synchronises)."""
+    n = lib().rald_debug_f16_saturation_attn(int(reset))
+    if n < 0:
+        check(1)
+    return n
+
+
 def op_ae_enc_features(pc: torch.Tensor, basis: torch.Tensor, var_factor: torch.Tensor):
     """pc [B,P,3] fp32, basis [3,24], var_factor [52,52] -> (F, G) fp16 [B, round_up(P,64), 64] (rald_amd/csrc/ae_encode.hip)."""
     Bn, P = pc.shape[0], pc.shape[1]

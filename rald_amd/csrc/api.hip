@@ -26,6 +26,14 @@ int64_t rald_debug_f16_saturation_count(int32_t reset) {
     return (int64_t)a + (int64_t)b;
 }
 
+// the per-head slabs of attn_self_proj / xattn_q2_proj alone
+int64_t rald_debug_f16_saturation_attn(int32_t reset) {
+    unsigned a = 0;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (f16_saturation_attn(&a, reset != 0)) return -1;
+    return (int64_t)a;
+}
+
 int rald_debug_poison_lds(void* stream) { return poison_lds((hipStream_t)stream); }
 
 void rald_dit_default_config(rald_dit_config* c) {
@@ -712,6 +720,28 @@ int rald_op_attention_f16kv(const float* Q, int64_t ldq, int64_t strideQ, const 
     a.part = (float*)scratch;
     return attention_d64(a, (hipStream_t)stream);
 }
+// every field of AttnArgs from the caller (tests): bf16 Q or fp32 Qf, Vt or row-major V, the head stride, the pad contract, the key split
+int rald_op_attention_args(const void* Q_bf16, const float* Qf, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
+                           int32_t k_rows, const void* Vt, int64_t ldvt, int64_t strideVt, const void* V, int64_t ldv, int64_t strideV, void* O_bf16,
+                           int64_t ldo, int64_t strideO, int32_t nq, int32_t nk, int32_t heads, int32_t batch, float scale, int32_t q_prescaled,
+                           int32_t f16, int32_t hsk, int32_t v_padded, int32_t ksplit, void* scratch, int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(K && O_bf16 && (Q_bf16 != nullptr) != (Qf != nullptr), "rald_op_attention_args: K, O and one of Q (bf16) and Qf (fp32)");
+    RALD_CHECK((Vt != nullptr) != (V != nullptr), "rald_op_attention_args: Vt or a row-major V, not both");
+    RALD_CHECK((f16 != 0) == (Qf != nullptr), "rald_op_attention_args: fp32 queries belong to the fp16 form");
+    AttnArgs a;
+    a.Q = (const bf16*)Q_bf16; a.Qf = Qf; a.ldq = ldq; a.strideQ = strideQ; a.K = (const bf16*)K; a.ldk = ldk; a.strideK = strideK;
+    a.Vt = (const bf16*)Vt; a.ldvt = ldvt; a.strideVt = strideVt; a.V = (const bf16*)V; a.ldv = ldv; a.strideV = strideV;
+    a.O = (bf16*)O_bf16; a.ldo = ldo; a.strideO = strideO;
+    a.nq = nq; a.nk = nk; a.k_rows = k_rows; a.heads = heads; a.batch = batch; a.scale = scale; a.q_prescaled = q_prescaled != 0;
+    a.f16 = f16 != 0; a.hsk = hsk; a.v_padded = v_padded != 0;
+    RALD_CHECK(nq > 0 && nk > 0 && heads > 0 && batch > 0, "rald_op_attention_args: empty problem");
+    a.ksplit = ksplit >= 0 ? ksplit : attention_pick_ksplit(nq, nk, heads, batch);
+    a.part = (float*)scratch;
+    if (a.ksplit > 1 && a.ksplit <= 64)
+        RALD_CHECK(scratch_bytes >= attention_split_scratch_bytes(a.ksplit, nq, heads, batch), "rald_op_attention_args: scratch too small for the key split");
+    return attention_d64(a, (hipStream_t)stream);
+}
+int32_t rald_op_attention_pick_ksplit(int32_t nq, int32_t nk, int32_t heads, int32_t batch) { return attention_pick_ksplit(nq, nk, heads, batch); }
 int rald_op_ae_enc_features(const float* pc, const float* basis, const float* var_factor, void* F_f16, void* G_f16, int32_t batch, int32_t n_points,
                             int32_t rows_per_sample, void* stream) {
     return ae_enc_features(pc, basis, var_factor, F_f16, G_f16, batch, n_points, rows_per_sample, (hipStream_t)stream);
@@ -751,6 +781,24 @@ int rald_op_xattn_q2_proj(const void* h_bf16, const void* Wq_bf16, const void* K
 int rald_op_reduce_resid_ln(const float* part, int32_t slabs, int64_t slab_stride, const float* bias, float* x, void* h_bf16, int32_t M,
                             const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps, void* stream) {
     return reduce_resid_ln(part, slabs, slab_stride, bias, x, (bf16*)h_bf16, M, g, b, gstride, rows_per_group, add_one, eps, (hipStream_t)stream);
+}
+// the three entries above with the slab type as an argument (part_f16 != 0: fp16 slabs of 2^-6 x the value, as dit.hip and ae.hip run them)
+int rald_op_attn_self_proj_slabs(const void* qkv_bf16, int64_t ld, const void* Wo_bf16, void* part, int32_t n_latents, int32_t heads, int32_t batch,
+                                 int32_t part_f16, void* stream) {
+    return attn_self_proj((const bf16*)qkv_bf16, ld, (const bf16*)Wo_bf16, (float*)part, n_latents, heads, batch, (hipStream_t)stream, part_f16 != 0);
+}
+int rald_op_xattn_q2_proj_slabs(const void* h_bf16, const void* Wq_bf16, const void* Kc_bf16, int64_t ldk, int64_t strideK, const void* Vt_bf16,
+                                int64_t ldvt, int64_t strideVt, const void* Wo_bf16, void* part, int32_t M, int32_t n_latents, int32_t heads,
+                                int32_t n_keys, float qscale, int32_t part_f16, void* stream) {
+    return xattn_q2_proj((const bf16*)h_bf16, (const bf16*)Wq_bf16, (const bf16*)Kc_bf16, ldk, strideK, (const bf16*)Vt_bf16, ldvt, strideVt,
+                         (const bf16*)Wo_bf16, (float*)part, M, n_latents, heads, n_keys, qscale, (hipStream_t)stream, part_f16 != 0);
+}
+int rald_op_reduce_resid_ln_slabs(const void* part, int32_t slabs, int64_t slab_stride, const float* bias, float* x, void* h_bf16, int32_t M,
+                                  const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps, int32_t part_f16,
+                                  void* stream) {
+    RALD_CHECK(part && bias && x && M >= 1 && (!h_bf16 || (g && b && rows_per_group > 0)), "rald_op_reduce_resid_ln_slabs: bad arguments");
+    return reduce_resid_ln((const float*)part, slabs, slab_stride, bias, x, (bf16*)h_bf16, M, g, b, gstride, rows_per_group, add_one, eps,
+                           (hipStream_t)stream, part_f16 != 0);
 }
 int rald_op_gemm_resid_ln(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* x, void* h_bf16,
                           const float* g, const float* b, int64_t gstride, int32_t rows_per_group, float add_one, float eps,

@@ -119,7 +119,7 @@ int split_hi_lo(const float* w, bf16* out, int n, hipStream_t st);
 struct AttnArgs {
     const bf16* Q;  int64_t ldq,  strideQ;     // Q [b][i][h*64+d]
     const bf16* K;  int64_t ldk,  strideK;     // K [b][j][h*64+d]
-    const bf16* Vt; int64_t ldvt, strideVt;    // Vt[b][h*64+d][j]  (keys contiguous, zero padded to 32)
+    const bf16* Vt; int64_t ldvt, strideVt;    // Vt[b][h*hsk+d][j]  (keys contiguous; columns nk .. round_up(nk,64)-1 finite)
     // alternative V operand, row-major like K (V[b][j][h*64+d]): set V and leave Vt null; needs nk % 64 == 0.  Read through
     // ds_read_b64_tr_b16, so a fused q|k|v projection can feed the kernel without a transposed copy of V.
     const bf16* V = nullptr; int64_t ldv = 0, strideV = 0;
@@ -136,7 +136,7 @@ struct AttnArgs {
     // ldq / strideQ, in elements), converted on load.  Needs q_prescaled and the row-major V.
     int f16 = 0; const float* Qf = nullptr;
     int hsk = 64;                              // column offset between the heads' K / V slices; 0 = every head reads the same 64 columns
-    int v_padded = 0;                          // row-major V: rows nk .. k_rows-1 are finite (zero), so nk need not be a multiple of 64
+    int v_padded = 0;                          // row-major V: rows nk .. k_rows-1 are ZERO (the caller's contract), so nk need not be a multiple of 64
 };
 int attention_d64(const AttnArgs& a, hipStream_t st);
 // self-attention of n tokens per sample over a fused projection qkv [batch][n][q | k | v of `inner` columns each] (q prescaled,

@@ -152,6 +152,12 @@ def test_c_abi_signatures_are_derived_from_the_header():
     assert S["rald_op_ae_encode_tables"] == (I32, [I32, I32, I32, I32, P, P])       # const float* const*, float* const*
     assert len(S["rald_op_attention_bwd"][1]) == 32
     assert S["rald_op_resid_gemm_ln"] == (I32, [P, P, P, I64, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, I64, I32, F, F, I32, I32, I32, I32, P, I64, P])
+    assert S["rald_op_attention_args"] == (I32, [P, P, I64, I64, P, I64, I64, I32, P, I64, I64, P, I64, I64, P, I64, I64, I32, I32, I32, I32, F, I32, I32,
+                                                 I32, I32, I32, P, I64, P])
+    assert S["rald_op_attn_self_proj_slabs"] == (I32, [P, I64, P, P, I32, I32, I32, I32, P])
+    assert S["rald_op_xattn_q2_proj_slabs"] == (I32, [P, P, P, I64, I64, P, I64, I64, P, P, I32, I32, I32, I32, F, I32, P])
+    assert S["rald_op_reduce_resid_ln_slabs"] == (I32, [P, I32, I64, P, P, P, I32, P, P, I64, I32, F, F, I32, P])
+    assert S["rald_debug_f16_saturation_attn"] == (I64, [I32]) and S["rald_op_attention_pick_ksplit"] == (I32, [I32, I32, I32, I32])
     assert S["rald_op_gemm_geglu_mx8out"] == (I32, [P, P, P, I64, P, P, P, I64, P, P, P, P, I64, I32, I32, I32, P])
 
 
