@@ -200,6 +200,18 @@ int rald_ae_decode_queries(rald_ae* h, const void* ctx, const float* queries, in
  * to rald_ae_decode_queries with the same ctx on that segment alone.  Rows from offsets[batch] on are not written. */
 int rald_ae_decode_queries_ragged(rald_ae* h, const void* ctx, const float* queries, const int64_t* offsets, int32_t batch,
                                   int64_t max_per_sample, float* out_logits, void* stream);
+/* Logit AND its gradient with respect to the query point, in the decoder's normalised coordinates (forward mode, closed form: DESIGN
+ * section 18): out_logits [B,Q] are rald_ae_decode_queries' bit for bit, out_grad [B,Q,3].  out_projected (NULL to skip) [B,Q,3] is the
+ * query after one clamped Newton step towards logit = 0: s = -logit g / |g|^2, scaled by min(1, max_step / |s|), s = 0 when |g|^2 is
+ * not > 1e-20 or the step is not finite, then clamped to [-1,1] per axis; max_step must be finite and > 0 when out_projected is given.
+ * num_latents <= 512 (a second, transposed image of the context shares LDS with the first); otherwise what the plain entries accept.
+ * _ragged: layout, offsets and max_per_sample as rald_ae_decode_queries_ragged; all three outputs are bit-identical to the dense call
+ * on the segment alone. */
+int rald_ae_decode_queries_grad(rald_ae* h, const void* ctx, const float* queries, int32_t batch, int64_t n_queries, float* out_logits,
+                                float* out_grad, float* out_projected, float max_step, void* stream);
+int rald_ae_decode_queries_grad_ragged(rald_ae* h, const void* ctx, const float* queries, const int64_t* offsets, int32_t batch,
+                                       int64_t max_per_sample, float* out_logits, float* out_grad, float* out_projected, float max_step,
+                                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Radar-spectrum encoder alone: RadarAutoencoder.encoder / _encode (model/models_radar_encoder.py
@@ -244,6 +256,16 @@ int rald_post_occupied_points_ragged(const float* logits, const float* queries, 
 /* inverse_norm_points (+ polar2cartesian) of a whole array (the ground-truth surface, :290, :317) */
 int rald_post_transform_points(const float* points, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy,
                                int32_t norm_isotropy, int32_t view_cone_mode, float* out_points, void* stream);
+/* rald_post_transform_points (out_points: the same bits) + one unit normal per point: grad [n,3] is the logit's gradient in the
+ * NORMALISED coordinates (rald_ae_decode_queries_grad); out_normals [n,3] = -J^-T grad / |J^-T grad| with J = d(metric point) /
+ * d(normalised point), computed in double and rounded once: it points from occupied to empty.  (0,0,0) where the transform is singular
+ * (range 0, the poles of the view cone), the gradient vanishes or anything is not finite.  _ragged: offsets DEVICE int64 [batch+1],
+ * n_total may be a worst-case size; rows from offsets[batch] on are not written.  No host read. */
+int rald_post_oriented_points(const float* points, const float* grad, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy,
+                              int32_t norm_isotropy, int32_t view_cone_mode, float* out_points, float* out_normals, void* stream);
+int rald_post_oriented_points_ragged(const float* points, const float* grad, const int64_t* offsets, int32_t batch, int64_t n_total,
+                                     const double* pc_range6_host, int32_t norm_anisotropy, int32_t norm_isotropy, int32_t view_cone_mode,
+                                     float* out_points, float* out_normals, void* stream);
 /* cal_metrics' two sums (exact nearest neighbour, fp64): out_sums2[0] = sum_pred min_gt ||.||,
  * out_sums2[1] = sum_gt min_pred ||.||;  chamfer = 0.5*out[0]/n_pred + 0.5*out[1]/n_gt */
 int rald_post_chamfer_sums(const float* pred, int64_t n_pred, const float* gt, int64_t n_gt, double* out_sums2, void* stream);
@@ -626,6 +648,13 @@ int64_t rald_op_ae_decode_scratch_bytes(int32_t batch, int32_t num_latents);
 int rald_op_ae_decode(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
                       float c0, const float* queries, float* out_logits, int32_t batch, int64_t n_queries, int32_t num_latents, int32_t dim,
                       void* scratch, int64_t scratch_bytes, void* stream);
+/* rald_op_ae_decode_grad: rald_op_ae_decode's arguments and checks (num_latents <= 512 here) + offsets (NULL: dense; else DEVICE int64
+ * [batch+1], queries / outputs concatenated and n_queries = the host bound of the longest segment), out_grad, out_projected (NULL to
+ * skip) and max_step as rald_ae_decode_queries_grad.  Same scratch as rald_op_ae_decode. */
+int rald_op_ae_decode_grad(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
+                           float c0, const float* queries, const int64_t* offsets, float* out_logits, float* out_grad, float* out_projected,
+                           float max_step, int32_t batch, int64_t n_queries, int32_t num_latents, int32_t dim, void* scratch,
+                           int64_t scratch_bytes, void* stream);
 /* Folded encoder (KLAutoEncoder.encode :351-399; rald_amd/csrc/ae_encode.hip): both attentions of the latent queries over the
  * input points run with ONE fp16 row of 52 Fourier features per point as key and value (head dim 64).
  * _tables: the weight-only tables, computed on the HOST in double (no GPU needed).  in[18] = host fp32 tensors in the reference's

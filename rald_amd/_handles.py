@@ -638,6 +638,33 @@ def op_ae_decode(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2aug
     return out.view(B, Q)
 
 
+def op_ae_decode_grad(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2aug: torch.Tensor, l_img: torch.Tensor, basis: torch.Tensor,
+                      c0: float, queries: torch.Tensor, out: torch.Tensor, grad: torch.Tensor, projected: Optional[torch.Tensor] = None,
+                      max_step: float = 0.05, offsets: Optional[torch.Tensor] = None, max_per_sample: Optional[int] = None) -> None:
+    """The gradient decoder on caller-made tables (rald_op_ae_decode_grad; arguments as op_ae_decode): queries [B,Q,3], or with
+    `offsets` (int64 [B+1] on the device) [T,3] concatenated and max_per_sample the host bound of the longest segment.  Writes the
+    caller's buffers: out (one float per query), grad and, when given, projected (three per query)."""
+    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis"), (queries, "queries")):
+        _need_cuda(t, what)
+    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
+    x, gamma, beta, t2aug, basis, queries = (_f32c(t) for t in (x, gamma, beta, t2aug, basis, queries))
+    B, M, dim = x.shape
+    assert queries.shape[-1] == 3 and t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim and basis.shape == (3, 24)
+    if offsets is None:
+        assert queries.dim() == 3 and queries.shape[0] == B
+        n, total = queries.shape[1], B * queries.shape[1]
+    else:
+        assert _ragged_batch(offsets, "offsets") == B and queries.dim() == 2
+        n, total = int(max_per_sample), queries.shape[0]
+    for t, k in ((out, 1), (grad, 3), (projected, 3)):
+        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == k * total)
+    nbytes = _nbytes(lib().rald_op_ae_decode_scratch_bytes(B, M))
+    scratch = _scratch(nbytes, x.device)
+    check(lib().rald_op_ae_decode_grad(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), t2aug.data_ptr(), l_img.data_ptr(), basis.data_ptr(), c0,
+                                       queries.data_ptr(), _opt(offsets), out.data_ptr(), grad.data_ptr(), _opt(projected), float(max_step),
+                                       B, n, M, dim, scratch.data_ptr(), nbytes, _stream()))
+
+
 class AeHandle(_Handle):
     """rald_ae*: encode / decode_latents / decode_queries of the set-latent autoencoder."""
 
@@ -708,6 +735,41 @@ class AeHandle(_Handle):
         check(lib().rald_ae_decode_queries_ragged(self._h, ctx.data_ptr(), queries.data_ptr(), offsets.data_ptr(), B, int(max_per_sample),
                                                   out.data_ptr(), _stream()))
         return out
+
+    def _check_ctx(self, ctx: torch.Tensor, B: int, what: str) -> None:
+        if ctx.dtype != torch.uint8 or not ctx.is_cuda or ctx.numel() != lib().rald_ae_ctx_bytes(self._h, B):
+            raise RuntimeError(f"decoder context of {ctx.numel()} bytes does not belong to a batch of {B}: decode_latents(z) and the {what} "
+                               "must have the same batch size")
+
+    def decode_queries_grad(self, ctx: torch.Tensor, queries: torch.Tensor, project: bool = False, max_step: float = 0.05):
+        """queries [B,Q,3] -> (logits [B,Q] - decode_queries' bit for bit -, d logit / d query [B,Q,3] in the normalised coordinates
+        [, the queries after one clamped Newton step towards logit = 0, [B,Q,3]]): one launch, closed form."""
+        _need_cuda(queries, "queries")
+        queries = _f32c(queries)
+        B, Q, _ = queries.shape
+        self._check_ctx(ctx, B, "queries")
+        out = torch.empty(B, Q, device=queries.device, dtype=torch.float32)
+        grad = torch.empty(B, Q, 3, device=queries.device, dtype=torch.float32)
+        proj = torch.empty_like(grad) if project else None
+        check(lib().rald_ae_decode_queries_grad(self._h, ctx.data_ptr(), queries.data_ptr(), B, Q, out.data_ptr(), grad.data_ptr(), _opt(proj),
+                                                float(max_step), _stream()))
+        return (out, grad, proj) if project else (out, grad)
+
+    def decode_queries_grad_ragged(self, ctx: torch.Tensor, queries: torch.Tensor, offsets: torch.Tensor, max_per_sample: int,
+                                   project: bool = False, max_step: float = 0.05):
+        """decode_queries_grad on the ragged layout of decode_queries_ragged: queries [T,3] -> (logits [T], grad [T,3][, projected [T,3]]).
+        Nothing is read back."""
+        _need_cuda(queries, "queries")
+        queries = _f32c(queries).reshape(-1, 3)
+        B = _ragged_batch(offsets, "offsets")
+        self._check_ctx(ctx, B, "offsets")
+        out = torch.empty(queries.shape[0], device=queries.device, dtype=torch.float32)
+        grad = torch.empty(queries.shape[0], 3, device=queries.device, dtype=torch.float32)
+        proj = torch.empty_like(grad) if project else None
+        check(lib().rald_ae_decode_queries_grad_ragged(self._h, ctx.data_ptr(), queries.data_ptr(), offsets.data_ptr(), B, int(max_per_sample),
+                                                       out.data_ptr(), grad.data_ptr(), _opt(proj), float(max_step), _stream()))
+        return (out, grad, proj) if project else (out, grad)
+
 
 
 # ---- MXFP8 (OCP microscaling: e4m3 elements + one e8m0 scale per 32 K-elements) -----------------------

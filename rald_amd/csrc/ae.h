@@ -70,6 +70,9 @@ struct Ae {
     int decode_queries(const void* ctx, const float* q, int B, int64_t Q, float* out, hipStream_t st);
     int decode_queries_ragged(const void* ctx, const float* q, const int64_t* offsets, int B, int64_t max_per_sample, float* out,
                               hipStream_t st);
+    // logits + d logit / d query (+ one clamped Newton step): offsets == nullptr -> dense [B][n][3], else ragged with n = max_per_sample
+    int decode_queries_grad(const void* ctx, const float* q, const int64_t* offsets, int B, int64_t n, float* out, float* grad, float* proj,
+                            float max_step, hipStream_t st);
 };
 
 }  // namespace rald

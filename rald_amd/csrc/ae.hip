@@ -452,4 +452,16 @@ int Ae::decode_queries_ragged(const void* ctx, const float* q, const int64_t* of
     return ae_decode_stream_ragged(ctx, l_img, q, offsets, out, basis, basis_diag, B, max_per_sample, cfg.num_latents, c0, st);
 }
 
+int Ae::decode_queries_grad(const void* ctx, const float* q, const int64_t* offsets, int B, int64_t n, float* out, float* grad, float* proj,
+                            float max_step, hipStream_t st) {
+    RALD_CHECK(finalized, "ae: weights not finalized");
+    RALD_CHECK(ctx && B >= 1 && (offsets ? n >= 0 : n >= 1) && ((offsets && n == 0) || (q && out && grad)), "ae: bad arguments");
+    RALD_CHECK(!proj || (std::isfinite(max_step) && max_step > 0.f), "ae: max_step must be finite and > 0");
+    RALD_CHECK(cfg.num_latents <= AE_DECODE_GRAD_MAX_LATENTS, "ae: the gradient decoder takes num_latents <= 512");
+    RALD_CHECK((uintptr_t)ctx % 16 == 0, "ae: decoder context must be 16-byte aligned");
+    RALD_TRY(ctx_registry.check(ctx, ctx_header(B), st, "decoder context"));
+    ctx = (const char*)ctx + BLOB_HEADER_BYTES;
+    return ae_decode_grad_stream(ctx, l_img, q, offsets, out, grad, proj, max_step, basis, basis_diag, B, n, cfg.num_latents, c0, st);
+}
+
 }  // namespace rald

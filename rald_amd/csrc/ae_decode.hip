@@ -444,4 +444,413 @@ int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const 
     return basis_diag ? launch_decode<true, true>(a, offsets, B, max_per_sample, smem, st) : launch_decode<false, true>(a, offsets, B, max_per_sample, smem, st);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// logit + gradient with respect to the query point
+// ---------------------------------------------------------------------------------------------------------------
+// The logit is a closed form of the query's 51 features, so its gradient is one too.  With D = d f / d q (51 x 3: cos(p_e) basis[:,e],
+// -sin(p_e) basis[:,e], identity), ubar = p.u, a_l = p_l (u_l - ubar), A_l = f.H_l + h0_l:
+//
+//     grad = ln2 [ rstd D^T G  -  rstd^3 (sum_l a_l A_l) D~^T L^T L f~ ],      G = sum_l a_l H_l
+//
+// Two passes over the score tiles per 64-query chunk.  Pass 1 is ae_decode_stream_kernel's own statement sequence (same features, same
+// variance, same lazily rescaled softmax, same merge of the lane halves): the logit is that kernel's, bit for bit, for the same segment.
+// Pass 2 recomputes each score tile, forms a_l from the final maximum, denominator and ubar, and feeds it - the latents sit on the
+// accumulator registers, the queries on the lanes, which is the MFMA B-operand layout up to a fixed order of the contraction index -
+// into a second product G^T[k,q] += H~^T[k,l] a[l,q].  Its A operand is a transposed copy of the image, built once per workgroup in
+// LDS in exactly that order: row k holds, for tile t, k-step s, lane half h, the 8 latents 32t + 8(2s + (j>>2)) + 4h + (j&3), j = 0..7,
+// i.e. the rows that accumulator registers 8s .. 8s+7 of a lane of half h carry.  Rows are 2M + 16 bytes apart (an odd number of
+// 16-byte chunks: the 32 rows of an operand read fall into different banks).  a_l is rounded to fp16 after a per-sample power-of-two
+// scale (2^12 / 2^ilogb(max |u|), so |a_l| < 2^14); what falls below fp16's range is below 2^-37 max|u| per term, under the 2^-24
+// max|u| that ubar's own fp32 rounding leaves in every a_l.  sum_l a_l A_l is f~.G over the slots <= 52; d var / d q is three more
+// B operands (the columns of D~ in fp16) against the resident variance factor, dotted lane-locally with the L f~ accumulators.
+//
+// LDS: the plain layout + 72 floats of the basis in radians + the transposed image 64 (2M + 16) bytes: 139.6 KiB at M = 512, the
+// largest M taken (M = 1024 would need 269 KiB).  8 waves per workgroup (two per SIMD, up to 256 registers each: the kernel takes 190
+// with the block-diagonal basis, 219 with a general one, and spills with the 168 that 12 waves would leave).
+struct DecodeGradArgs {
+    DecodeArgs d;
+    float* grad;                                      // [B][Q][3]
+    float* proj;                                      // nullptr or [B][Q][3]
+    float max_step;
+};
+
+// One clamped Newton step towards logit = 0.  Contraction is off: the float64 replay of the tests states this operation sequence
+// (products, sums, one division per quotient), and an fma here would be a different sequence.
+__device__ __forceinline__ void newton_step(float x, float y, float z, float logit, float gx, float gy, float gz, float max_step, float* o) {
+#pragma clang fp contract(off)
+    const float g2 = gx * gx + gy * gy + gz * gz;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    if (g2 > 1e-20f) {
+        const float t = -logit / g2;
+        sx = t * gx; sy = t * gy; sz = t * gz;
+        const float n = sqrtf(sx * sx + sy * sy + sz * sz);
+        if (n > max_step) {
+            const float c = max_step / n;
+            sx *= c; sy *= c; sz *= c;
+        }
+        if (!(isfinite(sx) && isfinite(sy) && isfinite(sz))) { sx = 0.f; sy = 0.f; sz = 0.f; }
+    }
+    o[0] = fminf(fmaxf(x + sx, -1.f), 1.f);
+    o[1] = fminf(fmaxf(y + sy, -1.f), 1.f);
+    o[2] = fminf(fmaxf(z + sz, -1.f), 1.f);
+}
+
+constexpr int GRAD_NW = 8;
+__host__ __device__ static inline int ht_row_bytes(int M) { return 2 * M + 16; }
+static inline size_t grad_smem_bytes(int M) { return (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76 + 76) * 4 + (size_t)64 * ht_row_bytes(M); }
+
+template <bool DIAG, int NW, bool RAGGED>
+__global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGradArgs ga, const int64_t* __restrict__ offsets) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const DecodeArgs& a = ga.d;
+    const int M = a.M;
+    unsigned char* s_h = smem;                                   // M * 128
+    unsigned char* s_l = smem + (size_t)M * 128;                 // 8192
+    float* s_u = reinterpret_cast<float*>(s_l + 8192);           // M + 4
+    float* s_basis = s_u + M + 4;                                // 72 (+ pad): revolutions
+    float* s_brad = s_basis + 76;                                // 72 (+ pad): radians, the factor of D
+    unsigned char* s_ht = reinterpret_cast<unsigned char*>(s_brad + 76);     // 64 rows of 2M + 16 bytes
+    const int RS = ht_row_bytes(M);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.y;
+    int64_t first = 0, seg = 0;
+    if constexpr (RAGGED) {
+        first = offsets[b];
+        seg = offsets[b + 1] - first;
+        if (first < 0 || seg <= 0 || (int64_t)blockIdx.x * NW * 64 >= seg) return;
+    }
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(a.ctx + (int64_t)b * a.ctx_stride);
+        uint4* dst = reinterpret_cast<uint4*>(s_h);
+        const int n16 = M * 8;                                   // image
+        for (int i = tid; i < n16; i += NW * 64) dst[i] = src[i];
+        const uint4* su = src + n16;                             // u | inv_scale
+        uint4* du = reinterpret_cast<uint4*>(s_u);
+        for (int i = tid; i < M / 4 + 1; i += NW * 64) du[i] = su[i];
+        const uint4* sl = reinterpret_cast<const uint4*>(a.l_img);
+        uint4* dl = reinterpret_cast<uint4*>(s_l);
+        for (int i = tid; i < 512; i += NW * 64) dl[i] = sl[i];
+        if (tid < 72) {
+            const float bv = a.basis[tid];
+            s_basis[tid] = bv * 0.15915494309189535f;            // radians -> revolutions (v_sin_f32 takes revolutions)
+            s_brad[tid] = bv;
+        }
+    }
+    __syncthreads();
+    {
+        // transposed image in the second product's contraction order (see above)
+        const int cpr = M >> 3;                                  // 16-byte chunks per row
+        for (int idx = tid; idx < 64 * cpr; idx += NW * 64) {
+            const int k = idx / cpr, c = idx - k * cpr;
+            const int base = 32 * (c >> 2) + 16 * ((c >> 1) & 1) + 4 * (c & 1);
+            f16x8 v;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const f16*>(s_h + img_off(base + 8 * (j >> 2) + (j & 3), k));
+            *reinterpret_cast<f16x8*>(s_ht + k * RS + c * 16) = v;
+        }
+    }
+    // power-of-two scale of a_l = p_l (u_l - ubar) for its fp16 rounding: |u_l - ubar| <= 2 max|u| < 2^(ilogb + 2)
+    float a_scale = 1.0f, inv_a_scale = 1.0f;
+    {
+        float um = 0.f;
+        for (int i = lane; i < M; i += 64) um = fmaxf(um, fabsf(s_u[i]));
+        um = wave_max(um);
+        if (um > 0.f && um < 3.0e38f) {
+            const int e = max(min(12 - ilogbf(um), 100), -100);
+            a_scale = exp2f((float)e);
+            inv_a_scale = exp2f((float)-e);
+        }
+    }
+    __syncthreads();
+    const float inv_scale = s_u[M];
+    const int r = lane & 31, h = lane >> 5;
+    const int64_t Q = RAGGED ? seg : a.Q;
+    const int64_t row0 = RAGGED ? first : (int64_t)b * a.Q;
+    const float* qin = a.queries + row0 * 3;
+    float* qout = a.out + row0;
+    float* gout = ga.grad + row0 * 3;
+    float* pout = ga.proj ? ga.proj + row0 * 3 : nullptr;
+    const int64_t nchunks = (Q + 63) / 64;
+    const float quarter = h ? 0.25f : 0.0f;                       // cos(t) = sin(t + 1/4 revolution)
+    const float gk = inv_scale * inv_a_scale;                     // G and f~.G carry the image's scale and a_scale
+
+    // One 32-query half of a 64-query chunk at a time (the halves of ae_decode_stream_kernel share only their operand loads: each has
+    // its own running maximum), so the state of one half - 16 registers of features, 32 of G - is what a wave holds.
+    for (int64_t chunk = (int64_t)blockIdx.x * NW + wave; chunk < nchunks; chunk += (int64_t)gridDim.x * NW) {
+#pragma unroll 1
+        for (int qb = 0; qb < 2; ++qb) {
+            if (chunk * 64 + qb * 32 >= Q) break;                 // wave-uniform: a half without a query
+            f16x8 bq[4];
+            int64_t q = chunk * 64 + qb * 32 + r;
+            const bool live = h == 0 && q < Q;
+            q = q < Q ? q : Q - 1;
+            const float x = qin[q * 3 + 0], y = qin[q * 3 + 1], z = qin[q * 3 + 2];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                f16x8 f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int e = 8 * s + j;
+                    float p;
+                    if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
+                    else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
+                    p += quarter;
+                    p = __builtin_amdgcn_fractf(p);
+                    f[j] = (f16)__builtin_amdgcn_sinf(p);
+                }
+                bq[s] = f;
+            }
+            {
+                f16x8 f;
+                f[0] = (f16)(h ? 0.f : x); f[1] = (f16)(h ? 0.f : y); f[2] = (f16)(h ? 0.f : z);
+                f[3] = (f16)(h ? 0.f : 1.f); f[4] = f[3];
+                f[5] = (f16)0.f; f[6] = (f16)0.f; f[7] = (f16)0.f;
+                bq[3] = f;
+            }
+            // ---- LayerNorm statistics of the query embedding: var_q = |L.f~|^2 (two 32-row tiles x 4 k-steps) ...
+            f32x16 lf[2];
+            float ss = 0.f;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                f32x16 acc;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                const int row = 32 * t + r;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const f16x8 la = *reinterpret_cast<const f16x8*>(s_l + row * 128 + (((2 * s + h) ^ (row & 7)) << 4));
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(la, bq[s], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) ss = fmaf(acc[i], acc[i], ss);
+                lf[t] = acc;
+            }
+            ss += __shfl_xor(ss, 32, 64);
+            // ... and its derivative, one axis at a time: the column of D~ in the B-operand layout (the h = 0 lanes hold d sin(p_e) =
+            // cos(p_e) b, the h = 1 lanes d cos(p_e) = -sin(p_e) b, both sin(p + quarter + 1/4 revolution) b; the last k-step is the
+            // identity on the axis' own slot) against the resident factor, dotted with the L.f~ accumulators
+            float vd[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                f16x8 dq[4];
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    if (DIAG && s != ax) continue;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int e = 8 * s + j;
+                        float p;
+                        if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
+                        else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
+                        p += quarter + 0.25f;
+                        dq[s][j] = (f16)(__builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p)) * s_brad[24 * ax + e]);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dq[3][j] = (f16)((j == ax && h == 0) ? 1.f : 0.f);
+                float dd = 0.f;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    f32x16 ad;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) ad[i] = 0.f;
+                    const int row = 32 * t + r;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        if (DIAG && s != 3 && s != ax) continue;
+                        const f16x8 la = *reinterpret_cast<const f16x8*>(s_l + row * 128 + (((2 * s + h) ^ (row & 7)) << 4));
+                        ad = __builtin_amdgcn_mfma_f32_32x32x16_f16(la, dq[s], ad, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) dd = fmaf(lf[t][i], ad[i], dd);
+                }
+                vd[ax] = dd + __shfl_xor(dd, 32, 64);
+            }
+            const float var = ss + a.eps;
+            const float rstd = rsqrtf(var);
+            const float sd = var * rstd;                           // sqrt(var + eps)
+            const f16 sd_hi = (f16)sd;
+            const f16 sd_lo = (f16)(sd - (float)sd_hi);
+            {
+                f16x8 f = bq[3];
+                f[5] = h ? (f16)0.f : sd_hi; f[6] = h ? (f16)0.f : sd_lo; f[7] = h ? (f16)0.f : sd_hi;
+                bq[3] = f;
+            }
+            const float rq = rstd * inv_scale;                     // rstd_q / scale
+            // ---- pass 1: scores + online softmax over the latents (the statements of ae_decode_stream_kernel)
+            float m = -INFINITY, den = 0.f, num = 0.f;
+            const int ntile = M >> 5;
+            for (int t = 0; t < ntile; ++t) {
+                const int row = 32 * t + r;
+                f16x8 fa[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(s_h + row * 128 + (((2 * s + h) ^ (row & 7)) << 4));
+                float4 uv[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) uv[g] = *reinterpret_cast<const float4*>(s_u + 32 * t + 8 * g + 4 * h);
+                f32x16 acc;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bq[s], acc, 0, 0, 0);
+                float tm = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
+#pragma unroll
+                for (int i = 4; i < 16; i += 4) tm = fmaxf(tm, fmaxf(fmaxf(acc[i], acc[i + 1]), fmaxf(acc[i + 2], acc[i + 3])));
+                const float vm = tm * rq;
+                if (__any(vm > m + 8.0f)) {                        // lazy running maximum: p stays <= 2^8
+                    const float mn = fmaxf(m, vm);
+                    const float alpha = __builtin_amdgcn_exp2f(m - mn);
+                    den *= alpha; num *= alpha;
+                    m = mn;
+                }
+                const float nm = -m;
+                float d0 = 0.f, d1 = 0.f, n0 = 0.f, n1 = 0.f;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float p0 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 0], rq, nm));
+                    const float p1 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 1], rq, nm));
+                    const float p2 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 2], rq, nm));
+                    const float p3 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 3], rq, nm));
+                    d0 += p0; d1 += p1; d0 += p2; d1 += p3;
+                    n0 = fmaf(p0, uv[g].x, n0); n1 = fmaf(p1, uv[g].y, n1); n0 = fmaf(p2, uv[g].z, n0); n1 = fmaf(p3, uv[g].w, n1);
+                }
+                den += d0 + d1;
+                num += n0 + n1;
+            }
+            // ---- merge the two lane halves of the query; both halves go on with the h = 0 lane's numbers (the ones that are stored)
+            const float mo = __shfl_xor(m, 32, 64), dn = __shfl_xor(den, 32, 64), nn = __shfl_xor(num, 32, 64);
+            const float mm = fmaxf(m, mo);
+            const float wa = __builtin_amdgcn_exp2f(m - mm), wb = __builtin_amdgcn_exp2f(mo - mm);
+            const float dsum = den * wa + dn * wb, nsum = num * wa + nn * wb;
+            const float logit = nsum / dsum + a.c0;
+            const float ub = __shfl(nsum / dsum, r, 64);
+            const float cs = a_scale / __shfl(dsum, r, 64);
+            const float nm2 = -mm;
+            // ---- pass 2: a_l = p_l (u_l - ubar) and G^T += H~^T . a (two 32-slot tiles)
+            f32x16 G[2];
+#pragma unroll
+            for (int T = 0; T < 2; ++T)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) G[T][i] = 0.f;
+            for (int t = 0; t < ntile; ++t) {
+                const int row = 32 * t + r;
+                f16x8 fa[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(s_h + row * 128 + (((2 * s + h) ^ (row & 7)) << 4));
+                float4 uv[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) uv[g] = *reinterpret_cast<const float4*>(s_u + 32 * t + 8 * g + 4 * h);
+                f16x8 ht[2][2];
+#pragma unroll
+                for (int T = 0; T < 2; ++T)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) ht[T][s] = *reinterpret_cast<const f16x8*>(s_ht + (32 * T + r) * RS + t * 64 + s * 32 + h * 16);
+                f32x16 acc;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bq[s], acc, 0, 0, 0);
+                f16x8 ab[2];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float p0 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 0], rq, nm2));
+                    const float p1 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 1], rq, nm2));
+                    const float p2 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 2], rq, nm2));
+                    const float p3 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 3], rq, nm2));
+                    ab[g >> 1][4 * (g & 1) + 0] = (f16)(p0 * ((uv[g].x - ub) * cs));
+                    ab[g >> 1][4 * (g & 1) + 1] = (f16)(p1 * ((uv[g].y - ub) * cs));
+                    ab[g >> 1][4 * (g & 1) + 2] = (f16)(p2 * ((uv[g].z - ub) * cs));
+                    ab[g >> 1][4 * (g & 1) + 3] = (f16)(p3 * ((uv[g].w - ub) * cs));
+                }
+#pragma unroll
+                for (int T = 0; T < 2; ++T)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) G[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ht[T][s], ab[s], G[T], 0, 0, 0);
+            }
+            // ---- epilogue: register i of tile T of a lane of half h holds slot 32T + 8(i>>2) + 4h + (i&3) of its query's G, i.e. k-step
+            // 2T + (i>>3), sin (i&4 == 0) or cos, frequency 4h + (i&3); the last k-step holds x, y, z, 1 (h = 0) and the second 1 (h = 1)
+            float sa = 0.f, gt[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const int e = 8 * s + 4 * h + jj;
+                    float p;
+                    if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
+                    else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
+                    const float sn = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p));
+                    const float cn = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p + 0.25f));
+                    const float Gs = G[s >> 1][8 * (s & 1) + jj], Gc = G[s >> 1][8 * (s & 1) + 4 + jj];
+                    sa = fmaf(Gs, (float)(f16)sn, sa);             // the fp16 features that the scores were made of
+                    sa = fmaf(Gc, (float)(f16)cn, sa);
+                    const float w = Gs * cn - Gc * sn;
+                    if (DIAG) gt[s] = fmaf(w, s_brad[24 * s + e], gt[s]);
+                    else {
+#pragma unroll
+                        for (int ax = 0; ax < 3; ++ax) gt[ax] = fmaf(w, s_brad[24 * ax + e], gt[ax]);
+                    }
+                }
+            }
+            if (h == 0) {
+                sa = fmaf(G[1][8], (float)(f16)x, sa);
+                sa = fmaf(G[1][9], (float)(f16)y, sa);
+                sa = fmaf(G[1][10], (float)(f16)z, sa);
+                sa += G[1][11];
+                gt[0] += G[1][8]; gt[1] += G[1][9]; gt[2] += G[1][10];
+            } else {
+                sa += G[1][8];
+            }
+            sa += __shfl_xor(sa, 32, 64);
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) gt[ax] += __shfl_xor(gt[ax], 32, 64);
+            const float c1 = 0.6931471805599453f * rstd * gk;
+            const float c2 = c1 * rstd * rstd * sa;
+            const float gx = c1 * gt[0] - c2 * vd[0], gy = c1 * gt[1] - c2 * vd[1], gz = c1 * gt[2] - c2 * vd[2];
+            if (live) {
+                qout[q] = logit;
+                gout[q * 3 + 0] = gx; gout[q * 3 + 1] = gy; gout[q * 3 + 2] = gz;
+                if (pout) newton_step(x, y, z, logit, gx, gy, gz, ga.max_step, pout + q * 3);
+            }
+        }
+    }
+}
+
+template <bool DIAG, bool RAGGED>
+static int launch_decode_grad(const DecodeGradArgs& a, const int64_t* offsets, int B, int64_t longest, hipStream_t st) {
+    constexpr int NW = GRAD_NW;
+    auto kern = ae_decode_grad_stream_kernel<DIAG, NW, RAGGED>;
+    static bool attr_set = false;
+    if (!attr_set) {
+        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_smem_bytes(AE_DECODE_GRAD_MAX_LATENTS)));
+        attr_set = true;
+    }
+    const int64_t nchunks = (longest + 63) / 64;
+    int64_t per_sample = (nchunks + NW - 1) / NW;                  // workgroups that have at least one chunk per wave
+    const int64_t cap = B >= 256 ? 1 : 256 / B;                    // about one workgroup per CU over the whole batch
+    if (per_sample > cap) per_sample = cap;
+    hipLaunchKernelGGL(kern, dim3((unsigned)per_sample, (unsigned)B), dim3(NW * 64), grad_smem_bytes(a.d.M), st, a, offsets);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+// offsets == nullptr: dense, n = the queries of one sample; else ragged, n = the host upper bound of the longest segment.
+// out_proj may be null (then max_step is not read)
+int ae_decode_grad_stream(const void* ctx, const unsigned short* l_img, const float* queries, const int64_t* offsets, float* out, float* grad,
+                          float* proj, float max_step, const float* basis, int basis_diag, int B, int64_t n, int M, float c0, hipStream_t st) {
+    RALD_CHECK(M % 32 == 0 && M >= 32 && M <= AE_DECODE_GRAD_MAX_LATENTS,
+               "ae_decode_grad_stream: num_latents must be a multiple of 32 in [32,512] (the transposed image has to fit in LDS)");
+    RALD_CHECK(B >= 1 && B <= 65535 && (offsets ? n >= 0 : n >= 1), "ae_decode_grad_stream: bad batch / query count");
+    RALD_CHECK(!proj || (std::isfinite(max_step) && max_step > 0.f), "ae_decode_grad_stream: max_step must be finite and > 0");
+    if (offsets && n == 0) return 0;
+    RALD_CHECK(queries && out && grad, "ae_decode_grad_stream: null pointer");
+    DecodeGradArgs a;
+    a.d.ctx = (const unsigned char*)ctx; a.d.ctx_stride = ae_ctx_stride(M); a.d.l_img = l_img; a.d.queries = queries; a.d.out = out;
+    a.d.basis = basis; a.d.Q = offsets ? 0 : n; a.d.M = M; a.d.c0 = c0; a.d.eps = 1e-5f;
+    a.grad = grad; a.proj = proj; a.max_step = proj ? max_step : 0.f;
+    if (offsets) return basis_diag ? launch_decode_grad<true, true>(a, offsets, B, n, st) : launch_decode_grad<false, true>(a, offsets, B, n, st);
+    return basis_diag ? launch_decode_grad<true, false>(a, nullptr, B, n, st) : launch_decode_grad<false, false>(a, nullptr, B, n, st);
+}
+
 }  // namespace rald

@@ -177,6 +177,19 @@ int rald_ae_decode_queries_ragged(rald_ae* h, const void* ctx, const float* quer
     RALD_CHECK(h, "null handle");
     return h->impl.decode_queries_ragged(ctx, queries, offsets, batch, max_per_sample, out_logits, (hipStream_t)stream);
 }
+int rald_ae_decode_queries_grad(rald_ae* h, const void* ctx, const float* queries, int32_t batch, int64_t n_queries, float* out_logits,
+                                float* out_grad, float* out_projected, float max_step, void* stream) {
+    RALD_CHECK(h, "null handle");
+    return h->impl.decode_queries_grad(ctx, queries, nullptr, batch, n_queries, out_logits, out_grad, out_projected, max_step, (hipStream_t)stream);
+}
+int rald_ae_decode_queries_grad_ragged(rald_ae* h, const void* ctx, const float* queries, const int64_t* offsets, int32_t batch,
+                                       int64_t max_per_sample, float* out_logits, float* out_grad, float* out_projected, float max_step,
+                                       void* stream) {
+    RALD_CHECK(h, "null handle");
+    RALD_CHECK(offsets, "rald_ae_decode_queries_grad_ragged: null offsets");
+    return h->impl.decode_queries_grad(ctx, queries, offsets, batch, max_per_sample, out_logits, out_grad, out_projected, max_step,
+                                       (hipStream_t)stream);
+}
 
 // test entry point of the streaming query decoder (ae_decode.hip)
 int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, const float* norm_w, const float* norm_b, const float* wpe,
@@ -213,6 +226,30 @@ int rald_op_ae_decode(const float* x, const float* gamma, const float* beta, con
     void* ctx = (char*)scratch + ae_decode_op_ctx_offset(batch, num_latents);
     RALD_TRY(ae_ctx_build(x, gamma, beta, t2aug, (float*)scratch, ctx, batch, num_latents, dim, st));
     return ae_decode_stream(ctx, l_img, queries, out_logits, basis, ae_basis_is_block_diagonal(h_basis), batch, n_queries, num_latents, c0, st);
+}
+// the gradient decoder on caller-made tables: rald_op_ae_decode's checks, then the same context build and ae_decode_grad_stream.  offsets
+// NULL: dense, n_queries per sample; else the ragged layout of rald_ae_decode_queries_ragged with n_queries = max_per_sample.
+int rald_op_ae_decode_grad(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
+                           float c0, const float* queries, const int64_t* offsets, float* out_logits, float* out_grad, float* out_projected,
+                           float max_step, int32_t batch, int64_t n_queries, int32_t num_latents, int32_t dim, void* scratch,
+                           int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(x && gamma && beta && t2aug && l_img && basis && queries && out_logits && out_grad && scratch, "rald_op_ae_decode_grad: null pointer");
+    RALD_CHECK(dim == 256 || dim == 512, "rald_op_ae_decode_grad: dim must be 256 or 512");
+    RALD_CHECK(num_latents >= 32 && num_latents <= AE_DECODE_GRAD_MAX_LATENTS && num_latents % 32 == 0,
+               "rald_op_ae_decode_grad: num_latents must be a multiple of 32 in [32,512]");
+    RALD_CHECK(batch >= 1 && batch <= 65535, "rald_op_ae_decode_grad: batch must be in [1,65535]");
+    RALD_CHECK(n_queries >= 1, "rald_op_ae_decode_grad: n_queries must be at least 1");
+    RALD_CHECK(!out_projected || (std::isfinite(max_step) && max_step > 0.f), "rald_op_ae_decode_grad: max_step must be finite and > 0");
+    RALD_CHECK((uintptr_t)scratch % 16 == 0 && (uintptr_t)l_img % 16 == 0, "rald_op_ae_decode_grad: scratch and l_img must be 16-byte aligned");
+    RALD_CHECK(scratch_bytes >= ae_decode_op_scratch_bytes(batch, num_latents), "rald_op_ae_decode_grad: scratch too small");
+    hipStream_t st = (hipStream_t)stream;
+    float h_basis[72];
+    RALD_HIP(hipMemcpyAsync(h_basis, basis, sizeof(h_basis), hipMemcpyDeviceToHost, st));
+    RALD_HIP(hipStreamSynchronize(st));
+    void* ctx = (char*)scratch + ae_decode_op_ctx_offset(batch, num_latents);
+    RALD_TRY(ae_ctx_build(x, gamma, beta, t2aug, (float*)scratch, ctx, batch, num_latents, dim, st));
+    return ae_decode_grad_stream(ctx, l_img, queries, offsets, out_logits, out_grad, out_projected, max_step, basis,
+                                 ae_basis_is_block_diagonal(h_basis), batch, n_queries, num_latents, c0, st);
 }
 
 // ---- standalone radar-spectrum encoder (RadarAutoencoder.encoder) -------------------------------
@@ -281,6 +318,18 @@ int rald_post_occupied_points_ragged(const float* logits, const float* queries, 
 int rald_post_transform_points(const float* points, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy,
                                int32_t norm_isotropy, int32_t view_cone_mode, float* out_points, void* stream) {
     return post_transform_points(points, n, pc_range6_host, norm_anisotropy, norm_isotropy, view_cone_mode, out_points, (hipStream_t)stream);
+}
+int rald_post_oriented_points(const float* points, const float* grad, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy,
+                              int32_t norm_isotropy, int32_t view_cone_mode, float* out_points, float* out_normals, void* stream) {
+    return post_oriented_points(points, grad, n, nullptr, 0, pc_range6_host, norm_anisotropy, norm_isotropy, view_cone_mode, out_points,
+                                out_normals, (hipStream_t)stream);
+}
+int rald_post_oriented_points_ragged(const float* points, const float* grad, const int64_t* offsets, int32_t batch, int64_t n_total,
+                                     const double* pc_range6_host, int32_t norm_anisotropy, int32_t norm_isotropy, int32_t view_cone_mode,
+                                     float* out_points, float* out_normals, void* stream) {
+    RALD_CHECK(offsets, "rald_post_oriented_points_ragged: null offsets");
+    return post_oriented_points(points, grad, n_total, offsets, batch, pc_range6_host, norm_anisotropy, norm_isotropy, view_cone_mode,
+                                out_points, out_normals, (hipStream_t)stream);
 }
 int rald_post_chamfer_sums(const float* pred, int64_t n_pred, const float* gt, int64_t n_gt, double* out_sums2, void* stream) {
     return post_chamfer_sums(pred, n_pred, gt, n_gt, out_sums2, (hipStream_t)stream);

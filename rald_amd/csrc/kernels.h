@@ -282,6 +282,11 @@ int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* 
 // ragged query sets: queries [T][3] / out [T], device offsets [B + 1], max_per_sample = host upper bound of the longest segment
 int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const float* queries, const int64_t* offsets, float* out,
                             const float* basis, int basis_diag, int B, int64_t max_per_sample, int M, float c0, hipStream_t st);
+// logit + gradient with respect to the query point (+ one clamped Newton step when proj is given): offsets == nullptr -> dense, n queries per
+// sample; else ragged with n = the host upper bound of the longest segment.  The logits are ae_decode_stream[_ragged]'s bit for bit.
+constexpr int AE_DECODE_GRAD_MAX_LATENTS = 512;     // the second product's transposed image must fit in LDS next to the plain layout
+int ae_decode_grad_stream(const void* ctx, const unsigned short* l_img, const float* queries, const int64_t* offsets, float* out, float* grad,
+                          float* proj, float max_step, const float* basis, int basis_diag, int B, int64_t n, int M, float c0, hipStream_t st);
 // basis_diag of a host copy of point_embed.basis [3][24]: 1 when it is block-diagonal (x -> columns 0-7, y -> 8-15, z -> 16-23), which
 // makes a projection one multiply instead of three; the one rule by which every caller picks the streaming kernel's form
 inline int ae_basis_is_block_diagonal(const float* basis_host) {
@@ -300,6 +305,10 @@ void post_scan_counts(int* counts, int nblocks, int64_t* total, hipStream_t st);
 int post_occupied_points(const float* logits, const float* queries, int64_t Q, const double* pc_range_host, int aniso, int iso,
                          int view_cone, float thr, float* out_pts, int64_t* out_idx, int64_t* out_count, int* scratch, hipStream_t st);
 int post_transform_points(const float* in, int64_t n, const double* pc_range_host, int aniso, int iso, int view_cone, float* out, hipStream_t st);
+// post_transform_points + unit normals -J^-T g / |.| of the gradients g taken in normalised coordinates (J = d metric / d normalised)
+// (offsets: nullptr, or the device [B + 1] row offsets of a ragged batch of worst-case size n: rows from offsets[B] on are not written)
+int post_oriented_points(const float* in, const float* grad, int64_t n, const int64_t* offsets, int B, const double* pc_range_host, int aniso,
+                         int iso, int view_cone, float* out_pts, float* out_normals, hipStream_t st);
 int post_chamfer_sums(const float* a, int64_t na, const float* b, int64_t nb, double* sums, hipStream_t st);
 // ragged batches: concatenated rows + device int64 offsets [B + 1]; no host read
 int post_occupied_points_ragged(const float* logits, const float* queries, const int64_t* in_offsets, int B, int64_t T,

@@ -150,6 +150,51 @@ __global__ void xform_points_kernel(const float* __restrict__ in, int64_t n, Pos
     if (i < n) xform_point(t, in[i * 3], in[i * 3 + 1], in[i * 3 + 2], out + i * 3);
 }
 
+// Unit normal of the decoder's level set at a point, in metric coordinates: -J^-T g / |J^-T g| with g the gradient of the logit in the
+// normalised coordinates and J = d xform_point / d (normalised point); it points from occupied to empty (the falling logit).  J's
+// columns are orthogonal: the per-axis scale s (smax on every axis when isotropic), and in view-cone mode times the polar ->
+// cartesian columns e_r, -d2r r cos(el) e_az, d2r r e_el (az = -y d2r, el = z d2r as in xform_point), so the inverse transpose is a
+// division per column.  In double, rounded once.  (0,0,0) when r = 0, at the poles (|cos el| < 2^-20: nearer than an fp32 elevation
+// resolves), when the result has no length or anything is not finite.
+__device__ __forceinline__ void normal_of(const PostXform& t, float px, float py, float pz, float g0, float g1, float g2, float* out) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, X = 0.0, Y = 0.0, Z = 0.0;
+    if (t.aniso) {
+        s0 = t.sx; s1 = t.sy; s2 = t.sz;
+        X = (double)px * s0 + t.ox; Y = (double)py * s1 + t.oy; Z = (double)pz * s2 + t.oz;
+    }
+    if (t.iso) {
+        s0 = s1 = s2 = t.smax;
+        X = (double)px * s0 + t.dox; Y = (double)py * s1 + t.doy; Z = (double)pz * s2 + t.doz;
+    }
+    double n0 = (double)g0 / s0, n1 = (double)g1 / s1, n2 = (double)g2 / s2;
+    if (t.view_cone) {
+        const double d2r = 0.017453292519943295;
+        const double r = X, az = -(Y * d2r), el = Z * d2r;
+        const double ce = cos(el), se = sin(el), ca = cos(az), sa = sin(az);
+        const double a = n0, b = n1 / (-d2r * r * ce), c = n2 / (d2r * r);
+        n0 = a * ce * ca - b * sa - c * se * ca;
+        n1 = a * ce * sa + b * ca - c * se * sa;
+        n2 = a * se + c * ce;
+        if (r == 0.0 || fabs(ce) < 9.5367431640625e-07) n0 = n1 = n2 = 0.0;
+    }
+    const double len = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    const bool ok = len > 0.0 && isfinite(len);
+    out[0] = ok ? (float)(-n0 / len) : 0.f;
+    out[1] = ok ? (float)(-n1 / len) : 0.f;
+    out[2] = ok ? (float)(-n2 / len) : 0.f;
+}
+
+// offsets (optional, device [B + 1]): only the rows before offsets[B] belong to a sample and are written
+__global__ void oriented_points_kernel(const float* __restrict__ in, const float* __restrict__ grad, int64_t n, const int64_t* __restrict__ offsets,
+                                       int B, PostXform t, float* __restrict__ out, float* __restrict__ normals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (offsets) { const int64_t used = offsets[B]; n = used < n ? used : n; }
+    if (i >= n) return;
+    const float px = in[i * 3], py = in[i * 3 + 1], pz = in[i * 3 + 2];
+    xform_point(t, px, py, pz, out + i * 3);
+    normal_of(t, px, py, pz, grad[i * 3], grad[i * 3 + 1], grad[i * 3 + 2], normals + i * 3);
+}
+
 // ---- Chamfer: sum_i min_j ||a_i - b_j||  (fp64), b staged through LDS in tiles of 1024 points
 // RAGGED (grid.y = sample): a / b are the samples' rows concatenated, a_off / b_off their [B + 1] row offsets, and the sample's sum goes to
 // sum[sample * 2]; an empty side leaves it at its zero
@@ -272,6 +317,17 @@ int post_transform_points(const float* in, int64_t n, const double* pc_range_hos
     RALD_CHECK(in && out && pc_range_host && n >= 1, "post_transform_points: bad argument");
     const PostXform t = make_xform(pc_range_host, aniso, iso, view_cone);
     hipLaunchKernelGGL(xform_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, n, t, out);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
+int post_oriented_points(const float* in, const float* grad, int64_t n, const int64_t* offsets, int B, const double* pc_range_host, int aniso,
+                         int iso, int view_cone, float* out_pts, float* out_normals, hipStream_t st) {
+    RALD_CHECK(pc_range_host && n >= (offsets ? 0 : 1) && (!offsets || (B >= 1 && B <= 65535)), "post_oriented_points: bad argument");
+    if (n == 0) return 0;
+    RALD_CHECK(in && grad && out_pts && out_normals, "post_oriented_points: null pointer");
+    const PostXform t = make_xform(pc_range_host, aniso, iso, view_cone);
+    hipLaunchKernelGGL(oriented_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, grad, n, offsets, B, t, out_pts, out_normals);
     RALD_HIP(hipGetLastError());
     return 0;
 }

@@ -150,18 +150,24 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 
 @torch.no_grad()
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
-                              rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None):
+                              rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
+                              normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
-    element follows: the device dict of postprocess.cloud_metrics_ragged (None where no metric is computed), whose 'cd' is the third."""
-    pts, off, cd, _, metrics = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds)
-    return (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
+    element follows: the device dict of postprocess.cloud_metrics_ragged (None where no metric is computed), whose 'cd' is the third.
+    With `normals` or `surface_steps` (see infer_point_clouds) the unit normals [T_cap,3] follow as the last element."""
+    pts, off, cd, _, metrics, nrm = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
+                                                    normals, surface_steps, surface_max_step)
+    out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
+    return out + (nrm,) if nrm is not None else out
 
 
-def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None):
-    """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None) on the device: what
+def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None, normals=False, surface_steps=0,
+                    surface_max_step=0.05):
+    """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None, normals or None) on the device: what
     infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest."""
+    oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
     helpers = _check_batch_inputs(sampled_tokens, helper_points, surfaces)
@@ -188,18 +194,31 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         helpers = [None] * B
     queries, offsets, longest = _batch_queries(grid, n_grid, helpers, B)                           # :264-271
     logits = vae.decode_ragged(sampled_tokens, queries, offsets, longest)                          # :275
-    pts, p_off, _ = PP.occupied_points_ragged(logits, queries, offsets, lidar.pc_range, aniso, iso, view_cone_mode=False)   # :283-289
+    pts, p_off, p_idx = PP.occupied_points_ragged(logits, queries, offsets, lidar.pc_range, aniso, iso, view_cone_mode=False,
+                                                  return_index=oriented and not refine)                                    # :283-289
+    kept_src, kept_off = queries, offsets
     n_queries = offsets[1:] - offsets[:-1]
     if refine:
         if host_draws:
             draws = _numpy_refine_draws(p_off, aug_num, int(inf.refine_query_scale), dev)
         refined, r_off = QP.refine_queries_ragged(pts, p_off, args, draws)                         # :292-297
         logits_r = vae.decode_ragged(sampled_tokens, refined, r_off, aug_num)                      # :300
-        pts, p_off, _ = PP.occupied_points_ragged(logits_r, refined, r_off, lidar.pc_range, aniso, iso, view_cone_mode=False)   # :304-310
+        pts, p_off, p_idx = PP.occupied_points_ragged(logits_r, refined, r_off, lidar.pc_range, aniso, iso, view_cone_mode=False,
+                                                      return_index=oriented)                                               # :304-310
+        kept_src, kept_off = refined, r_off
         n_queries = n_queries + (r_off[1:] - r_off[:-1])
         longest = aug_num
     view_cone = bool(_get(lidar, "view_cone_mode", False))
-    if view_cone:
+    nrm = None
+    if oriented:
+        # the kept queries in normalised coordinates (row r of frame b is query p_idx[r] of that frame's set), moved onto the surface if
+        # asked, then the gradient there: positions and normals in one pass.  All by device offsets; rows past the last frame unspecified
+        pos = torch.arange(pts.shape[0], dtype=torch.int64, device=dev)
+        frame = (torch.searchsorted(p_off, pos, right=True) - 1).clamp_(0, B - 1)
+        kept = kept_src[(kept_off[frame] + p_idx).clamp_(0, kept_src.shape[0] - 1)]
+        kept, _, grad = QP.project_to_surface_ragged(vae, sampled_tokens, kept, p_off, longest, int(surface_steps), surface_max_step)
+        pts, nrm = PP.oriented_points_ragged(kept, grad, p_off, lidar.pc_range, aniso, iso, view_cone_mode=view_cone)
+    elif view_cone:
         pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
     cd, metrics = None, None
     if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
@@ -213,7 +232,7 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         else:
             metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
             cd = metrics["cd"]
-    return pts, p_off, cd, n_queries, metrics
+    return pts, p_off, cd, n_queries, metrics, nrm
 
 
 def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
@@ -235,7 +254,8 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 
 @torch.no_grad()
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
-                       rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None) -> Dict[str, object]:
+                       rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
+                       surface_steps: int = 0, surface_max_step: float = 0.05) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -254,9 +274,16 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     postprocess.cloud_metrics_ragged instead of cal_metrics_ragged - 'cd' keeps its meaning, and 'metrics' holds one dict per frame
     (postprocess.cloud_metrics' keys: accuracy, completeness, cd, cd_l2, hausdorff, mhd as floats; precision, recall, f_score as lists
     per threshold), copied in the same single host read; None where no metric is computed.
+    `normals` / `surface_steps` (off by default: today's path and today's dict): with either, the queries that the last thresholding
+    kept are gathered in normalised coordinates, moved onto the decoder's surface by `surface_steps` Newton steps of at most
+    `surface_max_step` (query_points.project_to_surface_ragged; 0 = left where they are), and decoded once more with the logit's
+    gradient (KLAutoEncoder.decode_ragged_with_gradient); 'pred' then holds those points and a new 'normals' list one unit vector per
+    point [n_b,3] (occupied -> empty; zero where undefined), both from postprocess.oriented_points_ragged, and the metric is computed
+    on those points.  No host read is added.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
-    'n_queries': list of B ints} (+ 'metrics' with metric_thresholds)."""
-    pts, off, cd, nq, metrics = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds)
+    'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps)."""
+    pts, off, cd, nq, metrics, nrm = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
+                                                     normals, surface_steps, surface_max_step)
     B = sampled_tokens.shape[0]
     extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
     packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra)
@@ -267,6 +294,8 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
            "n_queries": [int(v) for v in host[B + 1:2 * B + 1]]}
     if metric_thresholds is not None:
         out["metrics"] = PP._metrics_to_host(host[3 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
+    if nrm is not None:
+        out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
     return out
 
 

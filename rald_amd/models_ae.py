@@ -94,6 +94,19 @@ class KLAutoEncoder(_HipBacked):
         h = self._handle()
         return h.decode_queries_ragged(self._context(x), queries, offsets, max_per_sample)
 
+    def decode_with_gradient(self, x, queries, project=False, max_step=0.05):
+        """decode + the gradient of each logit with respect to its query point, forward mode in one launch (no autograd, no graph):
+        x [B,M,latent_dim], queries [B,Q,3] -> (logits [B,Q,1] - decode's bit for bit -, grad [B,Q,3] in the normalised coordinates
+        [, projected [B,Q,3]: the queries after one Newton step towards the surface, at most max_step long, inside [-1,1]^3])."""
+        with torch.no_grad():
+            out = self._handle().decode_queries_grad(self._context(x), queries, project, max_step)
+        return (out[0].unsqueeze(-1),) + tuple(out[1:])
+
+    def decode_ragged_with_gradient(self, x, queries, offsets, max_per_sample, project=False, max_step=0.05):
+        """decode_with_gradient on decode_ragged's layout -> (logits [T], grad [T,3][, projected [T,3]])."""
+        with torch.no_grad():
+            return self._handle().decode_queries_grad_ragged(self._context(x), queries, offsets, max_per_sample, project, max_step)
+
     def forward(self, pc, queries):
         # Route like EDMPrecond.forward: model.train() + grad mode + trainable parameters = the stage-1 training step
         # (engine_ae.py:51, :73-104); eval() / no_grad = the inference path below, unchanged.
@@ -108,8 +121,9 @@ class KLAutoEncoder(_HipBacked):
         and ``eps`` [B, M, latent_dim] default to the reference's draws: timm's DropPath on the device RNG in forward order, then
         torch.randn on the CPU global RNG (:153)."""
         if pc.requires_grad or queries.requires_grad:
-            raise NotImplementedError("gradients with respect to the points / the query points are not built (the reference trains the "
-                                      "parameters only)")
+            raise NotImplementedError("gradients with respect to the points / the query points are not built into autograd (the reference "
+                                      "trains the parameters only); the logit's forward-mode gradient with respect to the query points is "
+                                      "KLAutoEncoder.decode_with_gradient")
         if self.dim != 512 or self.heads * self.dim_head != 512 or self.dim_head != 64 or self.num_latents != 512 \
                 or self.latent_dim < 32 or self.latent_dim % 32:
             raise NotImplementedError("the differentiable autoencoder covers dim 512, 8 x 64 heads, 512 latents and latent_dim a multiple "

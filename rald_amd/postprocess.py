@@ -77,6 +77,37 @@ def _transform(points: torch.Tensor, lidar_pc_range, aniso: bool, iso: bool, vie
     return out
 
 
+def oriented_points(points_norm: torch.Tensor, grad: torch.Tensor, lidar_pc_range, norm_anisotropy: bool, norm_isotropy: bool,
+                    view_cone_mode: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Normalised points [n,3] and the logit's gradients there [n,3] (KLAutoEncoder.decode_with_gradient) -> (points, normals): the
+    points in metric coordinates, bit for bit what inverse_norm_points (+ polar2cartesian) gives, and one unit normal each, pointing
+    from occupied to empty: -J^-T grad normalised, J the Jacobian of that transform.  (0,0,0) where the transform is singular (range 0,
+    the view cone's poles) or the gradient vanishes."""
+    return oriented_points_ragged(points_norm, grad, None, lidar_pc_range, norm_anisotropy, norm_isotropy, view_cone_mode)
+
+
+def oriented_points_ragged(points_norm: torch.Tensor, grad: torch.Tensor, offsets: Optional[torch.Tensor], lidar_pc_range,
+                           norm_anisotropy: bool, norm_isotropy: bool, view_cone_mode: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """oriented_points for a ragged batch held in worst-case sized arrays: offsets int64 [B+1] on the device, rows from offsets[B] on
+    are not read and stay unspecified.  No host read."""
+    _need_cuda(points_norm, "points")
+    points, grad = _f32c(points_norm).reshape(-1, 3), _f32c(grad).reshape(-1, 3)
+    if grad.shape != points.shape or grad.device != points.device:
+        raise ValueError("one gradient per point expected, on the points' device")
+    out, normals = torch.empty_like(points), torch.empty_like(points)
+    n = points.shape[0]
+    rng = _doubles(lidar_pc_range, 6, "pc_range", _PC_RANGE)
+    if offsets is None:
+        if n:
+            check(lib().rald_post_oriented_points(points.data_ptr(), grad.data_ptr(), n, rng, int(norm_anisotropy), int(norm_isotropy),
+                                                  int(view_cone_mode), out.data_ptr(), normals.data_ptr(), _stream()))
+    else:
+        B = _ragged_batch(offsets, "offsets")
+        check(lib().rald_post_oriented_points_ragged(points.data_ptr(), grad.data_ptr(), offsets.data_ptr(), B, n, rng, int(norm_anisotropy),
+                                                     int(norm_isotropy), int(view_cone_mode), out.data_ptr(), normals.data_ptr(), _stream()))
+    return out, normals
+
+
 def inverse_norm_points(points, lidar_pc_range, norm_anisotropy, norm_isotropy):
     """utils/utils.py:50-75."""
     return _transform(points, lidar_pc_range, norm_anisotropy, norm_isotropy, False)

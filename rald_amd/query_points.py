@@ -215,3 +215,30 @@ def refine_queries_ragged(points: torch.Tensor, offsets: torch.Tensor, args, dra
     inf, lidar = args.eval.inference, args.dataset.lidar
     return aug_query_helper_ragged(points, offsets, int(inf.refine_query_aug_num), lidar.pc_range, lidar.voxel_size, draws,
                                    norm=(lidar.norm_anisotropy, lidar.norm_isotropy))
+
+
+def project_to_surface_ragged(vae, z_or_ctx: torch.Tensor, points_norm: torch.Tensor, offsets: torch.Tensor, max_per_sample: int,
+                              steps: int = 3, max_step: float = 0.05):
+    """Moves normalised points onto the decoder's surface (logit = 0) by `steps` clamped Newton steps along the logit's gradient, one
+    gradient-decode launch per step (KLAutoEncoder.decode_ragged_with_gradient with project=True, each launch fed the previous one's
+    projected points), then one more gradient launch at the final positions: -> (points_norm [T,3], logits [T], grad [T,3]), the
+    logits and gradients OF the returned points.  z_or_ctx: the latents [B,M,C] (the autoencoder's memoised context is used) or a
+    decoder context from AeHandle.decode_latents (uint8).  Ragged layout as decode_ragged; nothing is read back.  The refine pass of
+    the reference only keeps jittered copies that stay positive; this uses where the decoder says the surface is."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must be >= 0")
+    is_ctx = z_or_ctx.dtype == torch.uint8
+
+    def decode(pts, project):
+        if is_ctx:
+            with torch.no_grad():
+                return vae._handle().decode_queries_grad_ragged(z_or_ctx, pts, offsets, max_per_sample, project, max_step)
+        return vae.decode_ragged_with_gradient(z_or_ctx, pts, offsets, max_per_sample, project, max_step)
+
+    pts = _f32c(points_norm).reshape(-1, 3)
+    for _ in range(steps):
+        pts = decode(pts, True)[2]
+    logits, grad = decode(pts, False)
+    return pts, logits, grad
+
