@@ -484,6 +484,12 @@ int rald_op_gemm_nt(const void* A, int64_t lda, int64_t strideA, const void* B, 
 int rald_op_gemm_nt2(const void* A, int64_t lda, int64_t strideA, int64_t strideA2, const void* B, int64_t ldb, int64_t strideB, int64_t strideB2,
                      void* C, int64_t ldc, int64_t strideC, int64_t strideC2, const float* bias, int32_t M, int32_t N, int32_t K, int32_t batch,
                      int32_t batch2, float alpha, int32_t epilogue, void* stream);
+/* Test entry of the 256 x 256 LDS-DMA tiles: one problem (no batch) with M, N multiples of 256, K a multiple of 64, epilogue 0 (bf16;
+ * alpha applies to columns n < alpha_ncols only) or 3 (GEGLU, packed bias required), launched whatever the tile count:
+ * persistent = 1 the persistent tile loop on at most max_workgroups workgroups (and at most one per CU), persistent = 0 the one-tile
+ * kernel.  The two are bit-identical; rald_op_gemm_nt picks between them by tile count. */
+int rald_op_gemm_nt_256(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias, int32_t M, int32_t N,
+                        int32_t K, float alpha, int32_t alpha_ncols, int32_t epilogue, int32_t persistent, int32_t max_workgroups, void* stream);
 /* Backward building blocks of the transformer block (what autograd derives for
  * models_radar_generation.py:35-169).  dX = dY.W and dW = dY^T.X run on rald_op_gemm_nt with transposed operands. */
 /* Weight gradient of a Linear without transposed copies (rald_amd/csrc/gemm_tn.hip): C[n1][n2] += sum_m A[m][n1] B[m][n2] for row-major bf16

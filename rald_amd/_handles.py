@@ -396,6 +396,19 @@ def op_gemm_nt(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = 
     return out
 
 
+def op_gemm_nt_256(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0, alpha: float = 1.0,
+                   alpha_ncols: int = 1 << 30, persistent: int = 1, max_workgroups: int = 1 << 30) -> torch.Tensor:
+    """The 256 x 256 LDS-DMA tiles on one problem, whatever its tile count: A [M,K], B [N,K] bf16 (row slices allowed) into the caller's bf16
+    `out` [M, N] (epilogue 0; alpha on columns < alpha_ncols) or [M, N/2] (epilogue 3, GEGLU).  persistent=1: the persistent tile loop on at
+    most max_workgroups workgroups; persistent=0: the one-tile kernel."""
+    (M, K), N = A.shape, B.shape[0]
+    assert A.dtype == B.dtype == out.dtype == torch.bfloat16 and A.stride(1) == B.stride(1) == out.stride(1) == 1
+    assert out.shape == (M, N // 2 if epilogue == 3 else N) and B.shape[1] == K
+    check(lib().rald_op_gemm_nt_256(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), out.data_ptr(), out.stride(0), _opt(bias), M, N, K,
+                                    alpha, int(alpha_ncols), int(epilogue), int(persistent), int(max_workgroups), _stream()))
+    return out
+
+
 def op_gemm_tn(A: torch.Tensor, B: torch.Tensor, C_inout: torch.Tensor, colsum: Optional[torch.Tensor] = None, atomics: bool = True) -> torch.Tensor:
     """C_inout [N1,N2] f32 += A^T.B for row-major bf16 A [M,N1], B [M,N2] (column slices allowed); colsum [N1] f32 += column sums of A.
     atomics=False: the row ranges meet in a workspace and are added in order by a second launch (bit-reproducible)."""

@@ -25,6 +25,7 @@
 //   EPI_GEGLU  C_bf16[m][c] = (acc_x + b_x) * gelu_erf(acc_g + b_g)   weights pre-packed so that
 //              packed rows [32t,32t+16) are the 'x' half and [32t+16,32t+32) the 'gate' half of
 //              output columns [16t,16t+16)  (models_radar_generation.py:93-95, models_ae.py:52-54)
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -362,6 +363,256 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
                                    reinterpret_cast<float*>(smem + WAVES * EPI_PATCH_BYTES) + wave * NT * 16);
 }
 
+// =================================================================================================
+// persistent LDS-DMA engine: 256 x 256 x 64 tiles, 8 waves (4 x 2), 2 stages; one workgroup per CU walks its tiles
+// =================================================================================================
+// The one-tile kernel above spends a third of a K = 512 tile outside its k-loop (first stage, epilogue, dispatch), with every CU in the
+// same phase at the same time.  Here workgroup w runs tiles w, w + grid, ... (through the same XCD strip walk, so each round of tiles is
+// the set a plain launch runs together) and the next tile's stages 0 and 1 are issued BEFORE the epilogue's stores.  vmcnt is one
+// in-order counter per wave for loads and stores, so the two duties go to different waves, fixed for the whole kernel:
+//   waves 0-3  DMA waves:   every LDS-DMA piece of every stage (8 A + 8 B pieces per k-step) and the tile's bias row; no global store
+//   waves 4-7  store waves: every global store of the epilogue; no VMEM load, and no vmcnt wait inside the tile loop
+// (wave i and wave i + 4 share SIMD i & 3 if waves are placed round-robin: one of each kind per SIMD; speed only).  All eight waves run
+// the MFMAs of the one-tile kernel on the same fragments, k-steps ascending from 0: every element's arithmetic is that kernel's.
+// The stage buffers belong to the next tile during the epilogue, so the transpose patches live in the 32 KiB behind them: per 16-row
+// m-tile (EPI_BF16: per 8-row half, a 16-row patch of 128 columns x 8 waves does not fit) every wave writes its patch, barrier, each
+// store wave writes out its own patch and that of DMA wave (wave - 4) as whole rows, barrier.
+// Host contract (gemm_nt / gemm_nt_256_test): M % 256 == 0, N % 256 == 0, batch * batch2 == 1, no out8.
+constexpr int PERSIST_LDS_BYTES = 160 * 1024;
+template <int EPI>
+__global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
+    static_assert(EPI == EPI_BF16 || EPI == EPI_GEGLU, "the persistent engine is built for the two bf16-output epilogues");
+    constexpr int BM = 256, BN = 256, BK = 64, WN = 2, MT = 4, NT = 8;
+    constexpr int DW = 4;                             // DMA waves
+    constexpr int CP = BM / 8 / DW;                   // 1-KiB DMA pieces per operand per DMA wave and k-step
+    constexpr int STAGE_BYTES = (BM + BN) * BK * 2;
+    constexpr int OC = (EPI == EPI_GEGLU) ? NT * 8 : NT * 16;            // output columns of a wave
+    constexpr int ROWB = OC * 2, STRIDE = ROWB + 16, LPR = ROWB / 16;    // as gemm_epilogue_lds
+    constexpr int PR = (EPI == EPI_GEGLU) ? 16 : 8;                      // rows of a patch
+    constexpr int PATCH = PR * STRIDE;
+    constexpr int RPI = 64 / LPR;                                        // rows per store instruction
+    constexpr int BIAS_OFF = 2 * STAGE_BYTES + 31 * 1024;                // the tile's 256 bias values
+    static_assert(2 * STAGE_BYTES + 8 * PATCH <= BIAS_OFF && BIAS_OFF + BN * 4 <= PERSIST_LDS_BYTES && PR % RPI == 0, "LDS plan");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][A tile | B tile] [8 patches] ... [bias]
+    float* tbias = reinterpret_cast<float*>(smem + BIAS_OFF);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const bool dma = wave < DW;
+    const int ntm = a.M / BM, ntn = a.N / BN, nt = ntm * ntn;
+    const int nk = a.K / BK;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    // lane part of every DMA source address (bytes): row lane >> 3 of the piece, swizzled chunk; the piece and k-step parts are uniform
+    const unsigned voA = (unsigned)((lane >> 3) * (int)a.lda + RALD_SWZ(lane >> 3, lane & 7) * 8) * 2u;
+    const unsigned voB = (unsigned)((lane >> 3) * (int)a.ldb + RALD_SWZ(lane >> 3, lane & 7) * 8) * 2u;
+    // One 1-KiB LDS-DMA piece: lane l's 16 bytes at base + voff go to LDS byte lds + 16 l.  Written as assembly so that the compiler's
+    // wait-count pass does not see it: the roles are a run-time branch, and the pass - which merges both sides of a branch - would put a
+    // vmcnt(0) in front of the LDS reads of ALL waves, the store waves' wait for their own stores included.  Every wait for a DMA in this
+    // kernel is written out (W_ST1, hand_over).
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_void*)smem;
+    auto dma_piece = [&](const char* base, unsigned voff, unsigned lds) {
+        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "{m0}"(lds) : "memory");
+    };
+    // DMA wave d issues pieces d, d + 4, ... (tile rows 8 * piece .. + 7) of both operands
+    auto stage = [&](int m0, int n0, int kt, int buf) {
+        const char* pa = reinterpret_cast<const char*>(a.A) + ((int64_t)(m0 + 8 * wave) * a.lda + kt * BK) * 2;
+        const char* pb = reinterpret_cast<const char*>(a.B) + ((int64_t)(n0 + 8 * wave) * a.ldb + kt * BK) * 2;
+        const unsigned s = lds0 + buf * STAGE_BYTES + wave * 1024;
+#pragma unroll
+        for (int p = 0; p < CP; ++p) dma_piece(pa + (int64_t)p * (8 * DW * 2) * a.lda, voA, s + p * DW * 1024);
+#pragma unroll
+        for (int p = 0; p < CP; ++p) dma_piece(pb + (int64_t)p * (8 * DW * 2) * a.ldb, voB, s + BM * 128 + p * DW * 1024);
+    };
+    auto read_frags = [&](int buf, int kk, bf16x8 (&fa)[MT], bf16x8 (&fb)[NT]) {
+        const bf16x8* sA = reinterpret_cast<const bf16x8*>(smem + buf * STAGE_BYTES);
+        const bf16x8* sB = sA + BM * 8;
+        const int chunk = kk * 4 + fq;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int r = wm * (MT * 16) + i * 16 + fr;
+            fa[i] = sA[r * 8 + RALD_SWZ(r, chunk)];
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int r = wn * (NT * 16) + j * 16 + fr;
+            fb[j] = sB[r * 8 + RALD_SWZ(r, chunk)];
+        }
+    };
+    f32x4 acc[MT][NT];
+    auto mfma_all = [&](const bf16x8 (&fa)[MT], const bf16x8 (&fb)[NT]) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+    };
+    constexpr int W_ALL = 0x0070;                                        // vmcnt(0) lgkmcnt(0), expcnt untouched
+    constexpr int W_LGKM = 0xc07f;                                       // lgkmcnt(0) only
+    constexpr int W_ST1 = ((2 * CP) & 15) | (((2 * CP) >> 4) << 14) | 0x0070;   // vmcnt(2 CP) lgkmcnt(0): the older of two stages has landed
+    // tile hand-over: the DMA waves' pieces have landed, everybody's fragment reads are done.  The store waves have nothing but their own
+    // output stores on vmcnt and never wait for them.
+    auto hand_over = [&]() {
+        if (dma) __builtin_amdgcn_s_waitcnt(W_ALL);
+        else __builtin_amdgcn_s_waitcnt(W_LGKM);
+        __builtin_amdgcn_s_barrier();
+    };
+    // one k-step of the one-tile kernel's rotated loop (see there); the DMA waves issue the next stage first
+    bf16x8 fa0[MT], fb0[NT], fa1[MT], fb1[NT];
+    auto body = [&](int m0, int n0, int kt, bool with_dma) {
+        const int cur = kt & 1;
+        if (with_dma && dma) stage(m0, n0, kt + 1, cur ^ 1);
+        __builtin_amdgcn_sched_barrier(0);
+        read_frags(cur, 0, fa0, fb0);
+        mfma_all(fa1, fb1);                                  // sub-step 1 of k-step kt-1
+#pragma unroll
+        for (int g = 0; g < 12; ++g) {                       // 2 MFMAs, then one fragment read (12 x)
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        read_frags(cur, 1, fa1, fb1);
+        mfma_all(fa0, fb0);                                  // sub-step 0 of k-step kt
+#pragma unroll
+        for (int g = 0; g < 12; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        hand_over();
+    };
+
+    if (!a.bias && tid < BN / 4) *reinterpret_cast<float4*>(tbias + 4 * tid) = make_float4(0.f, 0.f, 0.f, 0.f);
+    int t = blockIdx.x;                                      // launch-order index of the tile in the virtual ntn x ntm grid
+    int tm, tn;
+    xcd_strip_tile_at(t, ntn, ntm, tm, tn);
+    int m0 = tm * BM, n0 = tn * BN;
+    if (dma) {
+        stage(m0, n0, 0, 0);
+        if (nk > 1) stage(m0, n0, 1, 1);
+    }
+    for (;;) {
+        // stages 0 and 1 of this tile are in flight (DMA waves), issued under the previous tile's epilogue
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (dma) {
+            if (nk > 1) __builtin_amdgcn_s_waitcnt(W_ST1);
+            else __builtin_amdgcn_s_waitcnt(W_ALL);
+        } else __builtin_amdgcn_s_waitcnt(W_LGKM);
+        __builtin_amdgcn_s_barrier();
+        // the tile's bias row, one 1-KiB piece: behind the barrier nobody reads the previous tile's any more, and the DMA waves' next
+        // hand-over wait covers it
+        if (wave == 0 && a.bias) dma_piece(reinterpret_cast<const char*>(a.bias + n0), 16u * lane, lds0 + BIAS_OFF);
+        read_frags(0, 0, fa0, fb0);
+        read_frags(0, 1, fa1, fb1);
+        mfma_all(fa0, fb0);
+        hand_over();
+        for (int kt = 1; kt + 1 < nk; ++kt) body(m0, n0, kt, true);
+        if (nk > 1) body(m0, n0, nk - 1, false);
+        // both stage buffers are free (the loop ends on a barrier behind its last fragment reads): the next tile's first two stages go
+        // out before any store of this one
+        const int tnext = t + gridDim.x;
+        int m0n = 0, n0n = 0;
+        if (tnext < nt) {
+            xcd_strip_tile_at(tnext, ntn, ntm, tm, tn);
+            m0n = tm * BM;
+            n0n = tn * BN;
+            if (dma) {
+                stage(m0n, n0n, 0, 0);
+                if (nk > 1) stage(m0n, n0n, 1, 1);
+            }
+        }
+        mfma_all(fa1, fb1);                                  // sub-step 1 of the last k-step
+
+        // ---- epilogue: the arithmetic and rounding of gemm_epilogue_lds
+        {
+            int lane_e = lane;                                // opaque: the epilogue's lane addresses are made here, not kept across the k-loops
+            asm volatile("" : "+v"(lane_e));
+            const int fr = lane_e & 15, fq = lane_e >> 4;
+            unsigned char* patch = smem + 2 * STAGE_BYTES + wave * PATCH;
+            const int mb = m0 + wm * (MT * 16), nb = n0 + wn * (NT * 16);
+            const int oc0 = (EPI == EPI_GEGLU) ? nb / 2 : nb;
+            const float* wbias = tbias + wn * (NT * 16);
+            bf16* C = reinterpret_cast<bf16*>(a.C);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+#pragma unroll
+                for (int h = 0; h < 16 / PR; ++h) {
+                    asm volatile("" ::: "memory");
+                    if (PR == 16 || (fr >> 3) == h) {
+                        const int pr = fr & (PR - 1);
+                        if constexpr (EPI == EPI_GEGLU) {
+#pragma unroll
+                            for (int p = 0; p < NT / 2; ++p) {
+                                const float4 bx = *reinterpret_cast<const float4*>(wbias + 32 * p + 4 * fq);
+                                const float4 bg = *reinterpret_cast<const float4*>(wbias + 32 * p + 4 * fq + 16);
+                                const f32x4 x = acc[i][2 * p], g = acc[i][2 * p + 1];
+                                const f32x2 g01 = gelu_poly2(f32x2{g[0] + bg.x, g[1] + bg.y});
+                                const f32x2 g23 = gelu_poly2(f32x2{g[2] + bg.z, g[3] + bg.w});
+                                const f32x2 o01 = f32x2{x[0] + bx.x, x[1] + bx.y} * g01;
+                                const f32x2 o23 = f32x2{x[2] + bx.z, x[3] + bx.w} * g23;
+                                *reinterpret_cast<bf16x4*>(patch + pr * STRIDE + (16 * p + 4 * fq) * 2) = pack4(o01[0], o01[1], o23[0], o23[1]);
+                            }
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < NT; ++j) {
+                                const int n = nb + j * 16 + 4 * fq;
+                                const float4 b = *reinterpret_cast<const float4*>(wbias + 16 * j + 4 * fq);
+                                const f32x4 v = acc[i][j];
+                                const float al = n < a.alpha_ncols ? a.alpha : 1.0f;
+                                const float o0 = al * v[0] + b.x, o1 = al * v[1] + b.y, o2 = al * v[2] + b.z, o3 = al * v[3] + b.w;
+                                *reinterpret_cast<bf16x4*>(patch + pr * STRIDE + (16 * j + 4 * fq) * 2) = pack4(o0, o1, o2, o3);
+                            }
+                        }
+                    }
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_s_waitcnt(W_LGKM);
+                    __builtin_amdgcn_s_barrier();          // every patch of this step is written
+                    asm volatile("" ::: "memory");
+                    if (!dma) {
+                        // own patch (w2 = 0), then DMA wave (wave - 4)'s: 128 rows up, same columns.  All reads first, then the stores.
+                        const int r = lane_e / LPR, pc = lane_e % LPR;
+                        uint4 v[2][PR / RPI];
+#pragma unroll
+                        for (int w2 = 0; w2 < 2; ++w2)
+#pragma unroll
+                            for (int q = 0; q < PR / RPI; ++q)
+                                v[w2][q] = *reinterpret_cast<const uint4*>(patch - w2 * DW * PATCH + (q * RPI + r) * STRIDE + pc * 16);
+#pragma unroll
+                        for (int w2 = 0; w2 < 2; ++w2)
+#pragma unroll
+                            for (int q = 0; q < PR / RPI; ++q) {
+                                const int m = mb - w2 * (BM / 2) + i * 16 + h * PR + q * RPI + r;
+                                bf16* Cp = C + (int64_t)m * a.ldc + oc0 + pc * 8;
+                                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+                                const u32x4 vv = u32x4{v[w2][q].x, v[w2][q].y, v[w2][q].z, v[w2][q].w};
+                                // streamed output, the policy of gemm_epilogue_lds under GEMM_NT_STORE (which gemm_nt always sets).  The s_nop
+                                // is the hazard the compiler cannot see through the asm: a VALU write to the data registers of a store of
+                                // more than 8 bytes needs two wait states behind it (without it the next row's address arithmetic, placed in
+                                // v[data] directly behind the store, reached memory in 16 lanes of the row: found by the bit-equality test)
+                                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt\n\ts_nop 1" ::"v"(Cp), "v"(vv) : "memory");
+                            }
+                    }
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_s_waitcnt(W_LGKM);
+                    __builtin_amdgcn_s_barrier();          // the patches are read: the next step may overwrite them
+                    asm volatile("" ::: "memory");
+                }
+            }
+        }
+        if (tnext >= nt) break;
+        t = tnext;
+        m0 = m0n;
+        n0 = n0n;
+    }
+}
+
 // -------------------------------------------------------------------------------------------------
 template <int BM, int BN>
 static int launch_tile(const GemmArgs& a, int epi, hipStream_t st) {
@@ -399,6 +650,31 @@ static int launch_glds(const GemmArgs& a, int epi, hipStream_t st) {
             if constexpr ((BN / WN) % 64 == 0 && BM >= 128) return launch_glds_epi<BM, BN, WM, WN, NSTAGE, EPI_SOFTMAX64>(a, st);
             else { set_error("gemm: the softmax epilogue needs waves of 64-column groups"); return 1; }
         default: set_error("gemm: bad epilogue"); return 1;
+    }
+}
+
+// CUs of the current device, asked once per device and cached: launches inside a stream capture find the value there
+static int cu_count(int& cus) {
+    static int cached[64] = {};
+    int dev = 0;
+    RALD_HIP(hipGetDevice(&dev));
+    RALD_CHECK(dev >= 0 && dev < 64, "gemm: device index out of range");
+    if (cached[dev] == 0) RALD_HIP(hipDeviceGetAttribute(&cached[dev], hipDeviceAttributeMultiprocessorCount, dev));
+    cus = cached[dev];
+    return 0;
+}
+// one workgroup per CU (at most max_workgroups), each walking its tiles
+static int launch_persist(const GemmArgs& a, int epi, int max_workgroups, hipStream_t st) {
+    int cus = 0;
+    if (int rc = cu_count(cus)) return rc;
+    const int64_t tiles = (int64_t)(a.M / 256) * (a.N / 256);
+    const int grid = (int)std::min<int64_t>(tiles, std::min(cus, max_workgroups));
+    RALD_CHECK(grid >= 1, "gemm: the persistent engine needs at least one workgroup");
+    static bool raised_bf16 = false, raised_geglu = false;
+    switch (epi) {
+        case EPI_BF16:  return launch_dyn_lds(gemm_nt_persist_kernel<EPI_BF16>, raised_bf16, dim3(grid), 512, PERSIST_LDS_BYTES, st, a);
+        case EPI_GEGLU: return launch_dyn_lds(gemm_nt_persist_kernel<EPI_GEGLU>, raised_geglu, dim3(grid), 512, PERSIST_LDS_BYTES, st, a);
+        default: set_error("gemm: the persistent engine has the bf16 and GEGLU epilogues"); return 1;
     }
 }
 
@@ -460,12 +736,38 @@ int gemm_nt(const GemmArgs& a0, int epi, hipStream_t st) {
         return launch_glds<64, 64, 2, 2, 8>(a, epi, st);
     }
     const int64_t wg256 = (int64_t)(a.M / 256) * (a.N / 256) * nbatch;
-    if (a.M % 256 == 0 && a.N % 256 == 0 && wg256 >= 256) return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
+    if (a.M % 256 == 0 && a.N % 256 == 0 && wg256 >= 256) {
+        // two or more tiles per CU: the persistent tile loop
+        if (nbatch == 1 && (epi == EPI_BF16 || epi == EPI_GEGLU)) {
+            int cus = 0;
+            if (int rc = cu_count(cus)) return rc;
+            if (wg256 >= 2 * (int64_t)cus) return launch_persist(a, epi, 1 << 30, st);
+        }
+        return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
+    }
     // 192-320 tiles of 128 x 128 = about one 4-wave workgroup per CU, walking its k-steps as a latency chain (N = 512 projections at
     // M = 8192: 19-21 us for 4.3 GFLOP).  64 x 128 tiles with 3 stages give two workgroups per CU and a deeper prefetch: NFE at
     // B = 16 4.63 -> 4.36 ms, B = 8 2.94 -> 2.90 ms against 128 x 128 tiles.
     if (epi != EPI_GEGLU && wg128 <= 320 && a.M % 64 == 0) return launch_glds<64, 128, 2, 2, 3>(a, epi, st);
     return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
+}
+
+// Test entry: one full-tile bf16 problem on the 256 x 256 LDS-DMA tiles whatever the tile count - the persistent engine with a grid cap,
+// or the one-tile kernel (persistent == 0) - so that tests reach both at small shapes.
+int gemm_nt_256_test(const GemmArgs& a0, int epi, int persistent, int max_workgroups, hipStream_t st) {
+    GemmArgs a = a0;
+    a.flags |= GEMM_NT_STORE;
+    RALD_CHECK(epi == EPI_BF16 || epi == EPI_GEGLU, "gemm_nt_256_test: EPI_BF16 or EPI_GEGLU");
+    RALD_CHECK(a.M > 0 && a.N > 0 && a.K > 0 && a.M % 256 == 0 && a.N % 256 == 0 && a.K % 64 == 0, "gemm_nt_256_test: M, N % 256 == 0 and K % 64 == 0");
+    RALD_CHECK(a.batch == 1 && a.batch2 == 1 && !a.out8, "gemm_nt_256_test: one problem, bf16 output");
+    RALD_CHECK(a.lda % 8 == 0 && a.ldb % 8 == 0 && a.lda >= a.K && a.ldb >= a.K, "gemm_nt_256_test: lda/ldb must be multiples of 8 and at least K");
+    RALD_CHECK(((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.B % 16 == 0) && ((uintptr_t)a.C % 16 == 0) && ((uintptr_t)a.bias % 16 == 0),
+               "gemm_nt_256_test: pointers must be 16-byte aligned");
+    RALD_CHECK(a.ldc % 8 == 0 && a.ldc >= (epi == EPI_GEGLU ? a.N / 2 : a.N), "gemm_nt_256_test: ldc");
+    RALD_CHECK(epi != EPI_GEGLU || a.bias, "gemm_nt_256_test: GEGLU needs a packed bias");
+    RALD_CHECK(max_workgroups >= 1, "gemm_nt_256_test: max_workgroups must be at least 1");
+    if (persistent) return launch_persist(a, epi, max_workgroups, st);
+    return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
 }
 
 }  // namespace rald

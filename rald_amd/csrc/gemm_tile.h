@@ -24,9 +24,10 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // STRIPS of GN n-tiles (n fastest inside a strip, then m, then the next strip): the 32 tiles an XCD runs at once then share <= GN weight
 // panels (2 MB at GN = 8, 256-row tiles, K = 512) that stay in its 4 MB L2 while the A panels stream through.  Row-major order re-fetched
 // the whole 4 MB FF1 weight matrix for every round of tiles (measured: 296 MB fetched vs 37.5 MB algorithmic).
-__device__ __forceinline__ void xcd_strip_tile(int& tm, int& tn) {
-    const int ntn = gridDim.x, ntm = gridDim.y, nt = ntn * ntm;
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
+// `lin` is the workgroup's launch-order index in a grid of ntn x ntm tiles (the persistent GEMM passes virtual ones: its workgroup w takes
+// lin = w, w + grid, ... and so runs, round by round, the tile sets a one-tile-per-workgroup launch runs).
+__device__ __forceinline__ void xcd_strip_tile_at(int lin, int ntn, int ntm, int& tm, int& tn) {
+    const int nt = ntn * ntm;
     const int xcd = lin & 7, q = nt >> 3, rr = nt & 7;
     const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (lin >> 3);
     constexpr int GN = 8;
@@ -38,6 +39,9 @@ __device__ __forceinline__ void xcd_strip_tile(int& tm, int& tn) {
         tm = tile / ntn;
         tn = tile % ntn;
     }
+}
+__device__ __forceinline__ void xcd_strip_tile(int& tm, int& tn) {
+    xcd_strip_tile_at(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, tm, tn);
 }
 
 // ---- staging -----------------------------------------------------------------------------------------------------------------------

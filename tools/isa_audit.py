@@ -16,6 +16,10 @@ Checked per hot instantiation:
     ds_read_b64_tr_b16 - so the wait the compiler adds in front of the transposing reads covers only DMAs issued behind
     the PREVIOUS tile's last transposing read (what a three-stage ring of the row-major-V forms gives; the Vt forms have
     no such wait at all).  The shipped row-major-V forms do NOT meet this and are held to scratch and occupancy only;
+  * persistent GEMM (wave roles: DMA waves load, store waves store, chosen by a wave-uniform branch): no VMEM load other than the LDS-DMA
+    pieces; no basic block that holds both an LDS-DMA issue and a store; every `s_waitcnt vmcnt` alone in a block of its own behind a
+    conditional branch (the DMA waves' side of the hand-over) - so the path the store waves take through the tile loop has no vmcnt wait;
+    static LDS within 160 KiB (the dynamic part is PERSIST_LDS_BYTES in gemm.hip, held to the LDS plan by the kernel's static_assert);
   * ScratchSize 0 and the compiler's occupancy not below the recorded floor (2 for the GEMMs, 3 for attention, 4 for the
     unprescaled row-major-V attention form).
 
@@ -41,7 +45,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rald_amd", "csrc")
 FILES = ("gemm.hip", "gemm_ln.hip", "attention.hip")
-GEMM, KEYLOOP, RESOURCES = "gemm", "keyloop", "resources"
+GEMM, KEYLOOP, RESOURCES, PERSIST = "gemm", "keyloop", "resources", "persist"
 EPI = {"EPI_BF16": 0, "EPI_GEGLU": 3, "EPI_SOFTMAX64": 4}          # kernels.h
 
 # (file, kernel, template arguments, label, minimum occupancy, kind).  kind: GEMM = loads and waits behind the first store; KEYLOOP = loads
@@ -52,6 +56,8 @@ HOT = (
     ("gemm.hip", "gemm_nt_glds_kernel", (256, 256, 4, 2, 2, EPI["EPI_GEGLU"]), "FF1 (EPI_GEGLU)", 2, GEMM),
     ("gemm.hip", "gemm_nt_glds_kernel", (256, 256, 4, 2, 2, EPI["EPI_BF16"]), "q|k|v (EPI_BF16)", 2, GEMM),
     ("gemm.hip", "gemm_nt_glds_kernel", (256, 256, 4, 2, 2, EPI["EPI_SOFTMAX64"]), "folded cross-attention (EPI_SOFTMAX64)", 2, GEMM),
+    ("gemm.hip", "gemm_nt_persist_kernel", (EPI["EPI_GEGLU"],), "FF1, persistent tile loop (EPI_GEGLU)", 2, PERSIST),
+    ("gemm.hip", "gemm_nt_persist_kernel", (EPI["EPI_BF16"],), "q|k|v, persistent tile loop (EPI_BF16)", 2, PERSIST),
     ("gemm_ln.hip", "gemm_resid_ln_kernel", (128, 2, 4, 0, 1), "residual + LN, 128 rows, bf16, group-uniform", 2, GEMM),
     ("gemm_ln.hip", "gemm_resid_ln_kernel", (128, 2, 4, 1, 1), "residual + LN, 128 rows, MXFP8, group-uniform", 2, GEMM),
     ("gemm_ln.hip", "gemm_resid_ln_kernel", (64, 1, 8, 0, 1), "residual + LN, 64 rows, bf16, group-uniform", 2, GEMM),
@@ -141,6 +147,50 @@ def audit_kernel(text: str, min_occupancy: int, kind: str) -> list:
         findings.append(f"occupancy {m.group(1) if m else '?'} below {min_occupancy}")
     if kind == KEYLOOP:
         findings += audit_key_loop(ins)
+    if kind == PERSIST:
+        findings += audit_persistent(ins, text)
+    return findings
+
+
+def audit_persistent(ins: list, text: str) -> list:
+    """Wave roles of the persistent GEMM, as far as the text shows them (see the module docstring)."""
+    findings = []
+    plain = [s for s in ins if _VMEM_LOAD.match(s) and not s.startswith("global_load_lds")]
+    if plain:
+        findings.append(f"{len(plain)} VMEM load(s) that are not LDS-DMA pieces (first: `{plain[0]}`)")
+    blocks, cur = [], []
+    for s in ins:
+        if re.match(r"\.LBB\d+_\d+:$", s):
+            blocks.append(cur)
+            cur = []
+            continue
+        cur.append(s)
+        if _BLOCK_END.match(s):
+            blocks.append(cur)
+            cur = []
+    blocks.append(cur)
+    blocks = [b for b in blocks if b]
+    for i, b in enumerate(blocks):
+        if any(s.startswith("global_load_lds") for s in b) and any(_VMEM_STORE.match(s) for s in b):
+            findings.append("a basic block issues LDS-DMA pieces and stores: the roles are not separated")
+        if any(_VMWAIT.match(s) for s in b):
+            alone = all(s.startswith(("s_waitcnt", "s_branch", "s_nop", "s_mov_b")) for s in b)      # (s_mov: the structurizer's flags)
+            guarded = i > 0 and blocks[i - 1][-1].startswith("s_cbranch")
+            if not (alone and guarded):
+                findings.append(f"`{next(s for s in b if _VMWAIT.match(s))}` is not alone behind a conditional branch: the store waves would run it")
+    # the output stores are inline assembly, so the compiler's hazard recogniser does not see them: a VALU write to the data registers of
+    # a store of more than 8 bytes needs two wait states behind the store
+    for i, s in enumerate(ins):
+        m = re.match(r"global_store_dwordx[34] \S+ v\[(\d+):(\d+)\]", s)
+        for t in ins[i + 1:i + 3] if m else ():
+            if t.startswith("s_nop"):
+                break
+            w = re.match(r"v_\S+ v(?:\[(\d+):(\d+)\]|(\d+))", t)
+            if w and not (int(w.group(2) or w.group(3)) < int(m.group(1)) or int(w.group(1) or w.group(3)) > int(m.group(2))):
+                findings.append(f"`{t}` writes the data registers of `{s}` within two wait states")
+    m = re.search(r"; LDSByteSize: (\d+)", text)
+    if m is None or int(m.group(1)) > 160 * 1024:
+        findings.append(f"LDSByteSize {m.group(1) if m else '?'} above 160 KiB")
     return findings
 
 
