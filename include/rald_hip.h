@@ -672,10 +672,14 @@ int rald_op_ae_decode_grad(const float* x, const float* gamma, const float* beta
  * _features: F, G fp16 [batch][rows_per_sample][64] from pc [batch][n_points][3] (rows_per_sample = n_points rounded up to 64).
  * rald_op_attention_f16kv: the attention kernel's fp16 form on such rows (rows nk .. k_rows-1 must be ZERO, as _features writes them; fp32
  *   queries already times scale*log2(e); ksplit < 0 = pick;
- *   scratch = rald_op_attention_split_scratch_bytes(16, ...) when the keys may be split). */
+ *   scratch = rald_op_attention_split_scratch_bytes(16, ...) when the keys may be split).
+ * _qproj: the step between the two attentions.  x [rows][dim] = (xin ? xin : 0) + X0[row % num_latents] (fp32, kept; xin may be x itself)
+ *   and Q [rows][64] fp32 = LayerNorm(x; gamma, beta) . T1 [dim][64]; dim 256 or 512, xin may be NULL ('learnable': x = the latents). */
 int rald_op_ae_encode_tables(int32_t dim, int32_t num_latents, int32_t heads, int32_t mix, const float* const* in, float* const* out);
 int rald_op_ae_enc_features(const float* pc, const float* basis, const float* var_factor, void* F_f16, void* G_f16, int32_t batch, int32_t n_points,
                             int32_t rows_per_sample, void* stream);
+int rald_op_ae_enc_qproj(const float* xin, const float* X0, float* x, const float* gamma, const float* beta, const float* T1, float* Q,
+                         int32_t rows, int32_t num_latents, int32_t dim, void* stream);
 int rald_op_attention_f16kv(const float* Q, int64_t ldq, int64_t strideQ, const void* KV_f16, void* O_bf16, int64_t ldo, int64_t strideO, int32_t nq,
                             int32_t nk, int32_t k_rows, int32_t heads, int32_t batch, int32_t ksplit, void* scratch, void* stream);
 /* MXFP8 (OCP microscaling: e4m3 elements + one e8m0 scale per 32 consecutive K elements of a row), the

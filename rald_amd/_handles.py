@@ -629,6 +629,24 @@ def op_ae_enc_features(pc: torch.Tensor, basis: torch.Tensor, var_factor: torch.
     return F, G
 
 
+def op_ae_enc_qproj(xin: Optional[torch.Tensor], X0: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, T1: torch.Tensor,
+                    Q: torch.Tensor, rows: int) -> None:
+    """The step between the folded encoder's two attentions (rald_amd/csrc/ae_encode.hip), into the caller's buffers: x [rows, dim] fp32 =
+    (xin [rows, dim], or nothing when it is None) + X0 [M, dim][row % M]; Q [rows, 64] fp32 = LayerNorm(x; gamma, beta) . T1 [dim, 64].
+    xin may be x itself (the product runs it in place).  dim 256 or 512."""
+    for t, what in ((xin, "xin"), (X0, "X0"), (x, "x"), (gamma, "gamma"), (beta, "beta"), (T1, "T1"), (Q, "Q")):
+        if t is not None:
+            _need_cuda(t, what)
+            assert t.dtype == torch.float32 and t.is_contiguous(), f"{what} must be contiguous fp32"
+    assert X0.dim() == 2, "X0 must be [num_latents, dim]"
+    M, dim = X0.shape
+    assert rows >= 1 and x.numel() == rows * dim and Q.numel() == rows * 64, "x must hold rows * dim and Q rows * 64 floats"
+    assert xin is None or xin.numel() == rows * dim, "xin must hold rows * dim floats"
+    assert gamma.numel() == dim and beta.numel() == dim and T1.shape == (dim, 64), "gamma / beta [dim], T1 [dim, 64]"
+    check(lib().rald_op_ae_enc_qproj(_opt(xin), X0.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), T1.data_ptr(), Q.data_ptr(),
+                                     rows, M, dim, _stream()))
+
+
 def op_ae_decode(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2aug: torch.Tensor, l_img: torch.Tensor, basis: torch.Tensor,
                  c0: float, queries: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The streaming query decoder on caller-made tables (rald_amd/csrc/ae_decode.hip): x fp32 [B,M,dim] (output of the latent stack),

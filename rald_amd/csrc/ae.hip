@@ -37,7 +37,7 @@ int Ae::create() {
     RALD_CHECK(c.num_latents > 0 && c.num_latents % 64 == 0, "ae: num_latents must be a multiple of 64");
     RALD_CHECK(c.latent_dim >= 1 && c.latent_dim <= 64 && (2 * c.latent_dim) % 4 == 0, "ae: latent_dim must be in [2,64] and even");
     RALD_CHECK(c.depth >= 1 && c.depth <= 256, "ae: bad depth");
-    RALD_CHECK(c.num_inputs >= 32, "ae: num_inputs too small");
+    RALD_CHECK(c.num_inputs >= 1, "ae: num_inputs must be at least 1");
     RALD_CHECK(c.query_type == 0 || c.query_type == 1, "ae: query_type must be 0 ('mix') or 1 ('learnable'); 'point' needs torch_cluster.fps");
     const bool mixq = c.query_type == 0;
     const int M = c.num_latents, L = c.latent_dim;

@@ -22,6 +22,18 @@
 //
 // Exact in real arithmetic (tests/test_encode_fold.py checks the tables against the oracle in float64); numerically the
 // features are bounded by construction (sin, cos, normalised coordinates), fp16 keeps 11 bits of them.
+//
+// Domain of G = rstd.f in fp16 (s_p = the standard deviation of point p's embedding over its d channels, rstd = (s_p^2 + 1e-5)^-1/2):
+//   above  rstd <= 1e-5^-1/2 = 316.2 whatever the weights (an all-zero PointEmbed gives exactly that), so G never overflows for
+//          |coordinate| < 65504 / 316 = 207; the sin / cos slots and the constant slot (rstd itself) are at most 316.2.
+//   below  an entry keeps its 11 bits while |f|.rstd >= 2^-14 (fp16's normal range), i.e. for s_p <= 2^14 |f|: every feature of size
+//          >= 2^-8 up to s_p = 64, every feature >= 2^-11 (one fp16 step of a value near 1) up to s_p = 8.  Smaller entries are
+//          kept to an absolute 2^-25, which is 2^-25 / rstd of the row's constant slot.  The seeded and the reference weights have
+//          s_p of 0.5 .. 1; tests/test_gpu_ae_encode.py runs PointEmbed times 2^-4 and times 2^6 (s_p about 0.04 and 45).
+//   F holds the unscaled features: 11 bits of everything above 2^-14, |coordinate| up to 65504.
+// The arguments of sin / cos are reduced in fp32 revolutions: an argument a = p.basis carries an absolute error of about 2^-24 |a|
+// radians into the feature (2.4e-5 at the finest frequency 128 pi on the unit cube, a tenth of the fp16 step); at |coordinate| = 4 that
+// frequency makes 256 revolutions, which leaves the fraction handed to v_sin 16 bits (tested up to there).
 #include <cmath>
 #include <vector>
 

@@ -800,7 +800,20 @@ int rald_op_attention_args(const void* Q_bf16, const float* Qf, int64_t ldq, int
 int32_t rald_op_attention_pick_ksplit(int32_t nq, int32_t nk, int32_t heads, int32_t batch) { return attention_pick_ksplit(nq, nk, heads, batch); }
 int rald_op_ae_enc_features(const float* pc, const float* basis, const float* var_factor, void* F_f16, void* G_f16, int32_t batch, int32_t n_points,
                             int32_t rows_per_sample, void* stream) {
+    RALD_CHECK(pc && basis && var_factor && F_f16 && G_f16, "rald_op_ae_enc_features: null pointer");
+    RALD_CHECK(batch >= 1 && n_points >= 1, "rald_op_ae_enc_features: batch and n_points must be at least 1");
+    RALD_CHECK(rows_per_sample >= n_points && rows_per_sample % 64 == 0,
+               "rald_op_ae_enc_features: rows_per_sample must be a multiple of 64 and at least n_points");
+    RALD_CHECK((uintptr_t)F_f16 % 16 == 0 && (uintptr_t)G_f16 % 16 == 0, "rald_op_ae_enc_features: F and G must be 16-byte aligned");
     return ae_enc_features(pc, basis, var_factor, F_f16, G_f16, batch, n_points, rows_per_sample, (hipStream_t)stream);
+}
+int rald_op_ae_enc_qproj(const float* xin, const float* X0, float* x, const float* gamma, const float* beta, const float* T1, float* Q,
+                         int32_t rows, int32_t num_latents, int32_t dim, void* stream) {
+    RALD_CHECK(X0 && x && gamma && beta && T1 && Q, "rald_op_ae_enc_qproj: null pointer (only xin may be null)");
+    RALD_CHECK(rows >= 1, "rald_op_ae_enc_qproj: rows must be at least 1");
+    RALD_CHECK(num_latents >= 1, "rald_op_ae_enc_qproj: num_latents must be at least 1");
+    RALD_CHECK(dim == 256 || dim == 512, "rald_op_ae_enc_qproj: dim must be 256 or 512");
+    return ae_enc_qproj(xin, X0, x, gamma, beta, T1, Q, rows, num_latents, dim, (hipStream_t)stream);
 }
 int rald_op_ae_encode_tables(int32_t dim, int32_t num_latents, int32_t heads, int32_t mix, const float* const* in, float* const* out) {
     RALD_CHECK(in && out && dim >= 64 && num_latents >= 1 && heads >= 1, "rald_op_ae_encode_tables: bad argument");
