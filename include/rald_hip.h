@@ -490,6 +490,14 @@ int rald_op_gemm_nt2(const void* A, int64_t lda, int64_t strideA, int64_t stride
  * kernel.  The two are bit-identical; rald_op_gemm_nt picks between them by tile count. */
 int rald_op_gemm_nt_256(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias, int32_t M, int32_t N,
                         int32_t K, float alpha, int32_t alpha_ncols, int32_t epilogue, int32_t persistent, int32_t max_workgroups, void* stream);
+/* rald_op_gemm_nt_256 with a batch: entry b reads A + b strideA and B + b strideB (elements; 0 = shared by every entry) and writes
+ * C + b strideC (at least one whole output apart).  epilogue 4 (softmax over every aligned group of 64 output columns of alpha * acc, in
+ * exp2 units; no bias, alpha_ncols >= N) is accepted beside 0 and 3.  batch2 must be 1: the tiles have no inner batch.  The persistent
+ * tile loop takes a batch for epilogue 4 only (tile index over batch entry, m-tile, n-tile); batches of 0 and 3 run with persistent = 0.
+ * Every argument is checked on the host before the first HIP call. */
+int rald_op_gemm_nt_256_batched(const void* A, int64_t lda, int64_t strideA, const void* B, int64_t ldb, int64_t strideB, void* C, int64_t ldc,
+                                int64_t strideC, const float* bias, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t batch2, float alpha,
+                                int32_t alpha_ncols, int32_t epilogue, int32_t persistent, int32_t max_workgroups, void* stream);
 /* Backward building blocks of the transformer block (what autograd derives for
  * models_radar_generation.py:35-169).  dX = dY.W and dW = dY^T.X run on rald_op_gemm_nt with transposed operands. */
 /* Weight gradient of a Linear without transposed copies (rald_amd/csrc/gemm_tn.hip): C[n1][n2] += sum_m A[m][n1] B[m][n2] for row-major bf16

@@ -409,6 +409,22 @@ def op_gemm_nt_256(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, bias: Op
     return out
 
 
+def op_gemm_nt_256_batched(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
+                           alpha: float = 1.0, alpha_ncols: int = 1 << 30, persistent: int = 1, max_workgroups: int = 1 << 30) -> torch.Tensor:
+    """op_gemm_nt_256 with a batch: A [batch,M,K] or [M,K] (shared), B [batch,N,K] or [N,K] (shared), into the caller's bf16 `out`
+    [batch,M,N] (epilogue 0, or 4: softmax over every 64 columns of alpha * A.B^T in exp2 units) or [batch,M,N/2] (epilogue 3).  The
+    persistent tile loop takes a batch for epilogue 4 only."""
+    batch, M, nc = out.shape
+    K, N = A.shape[-1], B.shape[-2]
+    assert A.dtype == B.dtype == out.dtype == torch.bfloat16 and A.stride(-1) == B.stride(-1) == out.stride(-1) == 1
+    assert A.shape[-2] == M and B.shape[-1] == K and nc == (N // 2 if epilogue == 3 else N)
+    assert all(t.dim() == 2 or t.shape[0] == batch for t in (A, B))
+    check(lib().rald_op_gemm_nt_256_batched(A.data_ptr(), A.stride(-2), A.stride(0) if A.dim() == 3 else 0, B.data_ptr(), B.stride(-2),
+                                            B.stride(0) if B.dim() == 3 else 0, out.data_ptr(), out.stride(-2), out.stride(0), _opt(bias), M, N, K,
+                                            batch, 1, alpha, int(alpha_ncols), int(epilogue), int(persistent), int(max_workgroups), _stream()))
+    return out
+
+
 def op_gemm_tn(A: torch.Tensor, B: torch.Tensor, C_inout: torch.Tensor, colsum: Optional[torch.Tensor] = None, atomics: bool = True) -> torch.Tensor:
     """C_inout [N1,N2] f32 += A^T.B for row-major bf16 A [M,N1], B [M,N2] (column slices allowed); colsum [N1] f32 += column sums of A.
     atomics=False: the row ranges meet in a workspace and are added in order by a second launch (bit-reproducible)."""

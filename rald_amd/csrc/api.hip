@@ -547,6 +547,15 @@ int rald_op_gemm_nt_256(const void* A, int64_t lda, const void* B, int64_t ldb, 
     g.alpha = alpha; g.alpha_ncols = alpha_ncols;
     return gemm_nt_256_test(g, epilogue, persistent, max_workgroups, (hipStream_t)stream);
 }
+int rald_op_gemm_nt_256_batched(const void* A, int64_t lda, int64_t strideA, const void* B, int64_t ldb, int64_t strideB, void* C, int64_t ldc,
+                                int64_t strideC, const float* bias, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t batch2, float alpha,
+                                int32_t alpha_ncols, int32_t epilogue, int32_t persistent, int32_t max_workgroups, void* stream) {
+    RALD_CHECK(A && B && C, "rald_op_gemm_nt_256_batched: null pointer");
+    GemmArgs g = gemm_args((const bf16*)A, lda, (const bf16*)B, ldb, C, ldc, bias, M, N, K);
+    g.strideA = strideA; g.strideB = strideB; g.strideC = strideC; g.batch = batch; g.batch2 = batch2;
+    g.alpha = alpha; g.alpha_ncols = alpha_ncols;
+    return gemm_nt_256_batched_test(g, epilogue, persistent, max_workgroups, (hipStream_t)stream);
+}
 int rald_op_gemm_tn(const void* A_bf16, int64_t lda, const void* B_bf16, int64_t ldb, float* C, int64_t ldc, float* colsum, int32_t M, int32_t N1,
                     int32_t N2, void* workspace, int64_t workspace_bytes, void* stream) {
     return gemm_tn((const bf16*)A_bf16, lda, (const bf16*)B_bf16, ldb, C, ldc, colsum, M, N1, N2, (hipStream_t)stream, (float*)workspace, workspace_bytes / 4);

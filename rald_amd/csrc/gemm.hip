@@ -374,14 +374,39 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_glds_kernel(GemmArgs a) 
 //   waves 4-7  store waves: every global store of the epilogue; no VMEM load, and no vmcnt wait inside the tile loop
 // (wave i and wave i + 4 share SIMD i & 3 if waves are placed round-robin: one of each kind per SIMD; speed only).  All eight waves run
 // the MFMAs of the one-tile kernel on the same fragments, k-steps ascending from 0: every element's arithmetic is that kernel's.
-// The stage buffers belong to the next tile during the epilogue, so the transpose patches live in the 32 KiB behind them: per 16-row
-// m-tile (EPI_BF16: per 8-row half, a 16-row patch of 128 columns x 8 waves does not fit) every wave writes its patch, barrier, each
-// store wave writes out its own patch and that of DMA wave (wave - 4) as whole rows, barrier.
-// Host contract (gemm_nt / gemm_nt_256_test): M % 256 == 0, N % 256 == 0, batch * batch2 == 1, no out8.
+// The stage buffers belong to the next tile during the epilogue, so the transpose patches live in the 31 KiB behind them.  One epilogue
+// step = one 16-row m-tile (bf16 outputs: one 8-row half, a 16-row patch of 128 columns x 12 slots does not fit): every wave writes its
+// patch, ONE workgroup barrier, each store wave writes out its own patch and that of DMA wave (wave - 4) as whole rows.  Twelve slots:
+//   slots 4-7          a store wave's own patch: written and read by that wave alone (LDS operations of one wave execute in order), so no
+//                      barrier orders it
+//   slots 0-3, 8-11    DMA wave d's patch of step s in slot d + 8 (s & 1): the slot of step s + 1 was last read at step s - 1, i.e. before
+//                      its readers arrived at barrier s, so behind barrier s the DMA waves go straight on to step s + 1 (arithmetic and
+//                      patch write) while the store waves read and store step s
+// Every barrier stands outside the role branch: all eight waves execute 4 (GEGLU) / 8 (bf16 outputs) per tile's epilogue.
+// EPI_SOFTMAX64 (the folded cross-attention's scores) runs BATCHED: the tile index counts (batch entry, m-tile, n-tile) through
+// batched_tile_at, each entry with its own operand bases; no bias.  The bf16 and GEGLU forms take one problem.
+// Host contract (gemm_nt / the test entries): M % 256 == 0, N % 256 == 0, batch2 == 1, no out8; batch == 1 unless EPI_SOFTMAX64.
 constexpr int PERSIST_LDS_BYTES = 160 * 1024;
+// Launch-order index g of a one-tile launch's workgroup (grid ntn x ntm x nbatch) -> batch entry and tile: the mapping of
+// gemm_nt_glds_kernel, restated on an index instead of blockIdx so that persistent workgroup w, taking g = w, w + grid, ..., runs round by
+// round the tile sets that launch runs together (a batch entry's few tiles on one XCD, its operands crossing the fabric once).
+__device__ __forceinline__ void batched_tile_at(int g, int ntn, int ntm, int nbatch, int& bz, int& tm, int& tn) {
+    const int nt = ntn * ntm;
+    if (nt < 8 && (nbatch & 7) == 0) {
+        const int slot = g >> 3;
+        bz = (slot / nt) * 8 + (g & 7);
+        const int tl = slot % nt;
+        tm = tl / ntn;
+        tn = tl % ntn;
+    } else {
+        bz = g / nt;
+        xcd_strip_tile_at(g - bz * nt, ntn, ntm, tm, tn);
+    }
+}
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
-    static_assert(EPI == EPI_BF16 || EPI == EPI_GEGLU, "the persistent engine is built for the two bf16-output epilogues");
+    static_assert(EPI == EPI_BF16 || EPI == EPI_GEGLU || EPI == EPI_SOFTMAX64, "the persistent engine is built for the three bf16-output epilogues");
+    constexpr bool BATCHED = EPI == EPI_SOFTMAX64, BIAS = EPI != EPI_SOFTMAX64;
     constexpr int BM = 256, BN = 256, BK = 64, WN = 2, MT = 4, NT = 8;
     constexpr int DW = 4;                             // DMA waves
     constexpr int CP = BM / 8 / DW;                   // 1-KiB DMA pieces per operand per DMA wave and k-step
@@ -390,10 +415,12 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
     constexpr int ROWB = OC * 2, STRIDE = ROWB + 16, LPR = ROWB / 16;    // as gemm_epilogue_lds
     constexpr int PR = (EPI == EPI_GEGLU) ? 16 : 8;                      // rows of a patch
     constexpr int PATCH = PR * STRIDE;
+    constexpr int NSLOT = 12;                                            // 4 own + 2 x 4 partner patches
     constexpr int RPI = 64 / LPR;                                        // rows per store instruction
     constexpr int BIAS_OFF = 2 * STAGE_BYTES + 31 * 1024;                // the tile's 256 bias values
-    static_assert(2 * STAGE_BYTES + 8 * PATCH <= BIAS_OFF && BIAS_OFF + BN * 4 <= PERSIST_LDS_BYTES && PR % RPI == 0, "LDS plan");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][A tile | B tile] [8 patches] ... [bias]
+    static_assert(2 * STAGE_BYTES + NSLOT * PATCH <= BIAS_OFF && BIAS_OFF + BN * 4 <= PERSIST_LDS_BYTES && PR % RPI == 0 && (MT * 16 / PR) % 2 == 0,
+                  "LDS plan; an even number of steps per tile keeps the slot parity across tiles");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][A tile | B tile] [12 patch slots] ... [bias]
     float* tbias = reinterpret_cast<float*>(smem + BIAS_OFF);
 
     const int tid = threadIdx.x;
@@ -401,7 +428,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const bool dma = wave < DW;
-    const int ntm = a.M / BM, ntn = a.N / BN, nt = ntm * ntn;
+    const int ntm = a.M / BM, ntn = a.N / BN, nt = ntm * ntn * (BATCHED ? a.batch : 1);
     const int nk = a.K / BK;
     const int fr = lane & 15, fq = lane >> 4;
 
@@ -416,10 +443,18 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
     auto dma_piece = [&](const char* base, unsigned voff, unsigned lds) {
         asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "{m0}"(lds) : "memory");
     };
+    // One tile: its batch entry's operand offsets (elements; 0 for the one-problem forms) and its first row and column
+    struct Tile { int64_t oa, ob, oc; int m0, n0; };
+    auto tile_at = [&](int t) {
+        int bz = 0, tm, tn;
+        if constexpr (BATCHED) batched_tile_at(t, ntn, ntm, a.batch, bz, tm, tn);
+        else xcd_strip_tile_at(t, ntn, ntm, tm, tn);
+        return Tile{bz * a.strideA, bz * a.strideB, bz * a.strideC, tm * BM, tn * BN};
+    };
     // DMA wave d issues pieces d, d + 4, ... (tile rows 8 * piece .. + 7) of both operands
-    auto stage = [&](int m0, int n0, int kt, int buf) {
-        const char* pa = reinterpret_cast<const char*>(a.A) + ((int64_t)(m0 + 8 * wave) * a.lda + kt * BK) * 2;
-        const char* pb = reinterpret_cast<const char*>(a.B) + ((int64_t)(n0 + 8 * wave) * a.ldb + kt * BK) * 2;
+    auto stage = [&](const Tile& T, int kt, int buf) {
+        const char* pa = reinterpret_cast<const char*>(a.A) + (T.oa + (int64_t)(T.m0 + 8 * wave) * a.lda + kt * BK) * 2;
+        const char* pb = reinterpret_cast<const char*>(a.B) + (T.ob + (int64_t)(T.n0 + 8 * wave) * a.ldb + kt * BK) * 2;
         const unsigned s = lds0 + buf * STAGE_BYTES + wave * 1024;
 #pragma unroll
         for (int p = 0; p < CP; ++p) dma_piece(pa + (int64_t)p * (8 * DW * 2) * a.lda, voA, s + p * DW * 1024);
@@ -461,9 +496,9 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
     };
     // one k-step of the one-tile kernel's rotated loop (see there); the DMA waves issue the next stage first
     bf16x8 fa0[MT], fb0[NT], fa1[MT], fb1[NT];
-    auto body = [&](int m0, int n0, int kt, bool with_dma) {
+    auto body = [&](const Tile& T, int kt, bool with_dma) {
         const int cur = kt & 1;
-        if (with_dma && dma) stage(m0, n0, kt + 1, cur ^ 1);
+        if (with_dma && dma) stage(T, kt + 1, cur ^ 1);
         __builtin_amdgcn_sched_barrier(0);
         read_frags(cur, 0, fa0, fb0);
         mfma_all(fa1, fb1);                                  // sub-step 1 of k-step kt-1
@@ -486,14 +521,13 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
         hand_over();
     };
 
-    if (!a.bias && tid < BN / 4) *reinterpret_cast<float4*>(tbias + 4 * tid) = make_float4(0.f, 0.f, 0.f, 0.f);
-    int t = blockIdx.x;                                      // launch-order index of the tile in the virtual ntn x ntm grid
-    int tm, tn;
-    xcd_strip_tile_at(t, ntn, ntm, tm, tn);
-    int m0 = tm * BM, n0 = tn * BN;
+    if constexpr (BIAS)
+        if (!a.bias && tid < BN / 4) *reinterpret_cast<float4*>(tbias + 4 * tid) = make_float4(0.f, 0.f, 0.f, 0.f);
+    int t = blockIdx.x;                                      // launch-order index of the tile in the virtual ntn x ntm (x batch) grid
+    Tile T = tile_at(t);
     if (dma) {
-        stage(m0, n0, 0, 0);
-        if (nk > 1) stage(m0, n0, 1, 1);
+        stage(T, 0, 0);
+        if (nk > 1) stage(T, 1, 1);
     }
     for (;;) {
         // stages 0 and 1 of this tile are in flight (DMA waves), issued under the previous tile's epilogue
@@ -508,42 +542,70 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
         __builtin_amdgcn_s_barrier();
         // the tile's bias row, one 1-KiB piece: behind the barrier nobody reads the previous tile's any more, and the DMA waves' next
         // hand-over wait covers it
-        if (wave == 0 && a.bias) dma_piece(reinterpret_cast<const char*>(a.bias + n0), 16u * lane, lds0 + BIAS_OFF);
+        if constexpr (BIAS)
+            if (wave == 0 && a.bias) dma_piece(reinterpret_cast<const char*>(a.bias + T.n0), 16u * lane, lds0 + BIAS_OFF);
         read_frags(0, 0, fa0, fb0);
         read_frags(0, 1, fa1, fb1);
         mfma_all(fa0, fb0);
         hand_over();
-        for (int kt = 1; kt + 1 < nk; ++kt) body(m0, n0, kt, true);
-        if (nk > 1) body(m0, n0, nk - 1, false);
+        for (int kt = 1; kt + 1 < nk; ++kt) body(T, kt, true);
+        if (nk > 1) body(T, nk - 1, false);
         // both stage buffers are free (the loop ends on a barrier behind its last fragment reads): the next tile's first two stages go
         // out before any store of this one
         const int tnext = t + gridDim.x;
-        int m0n = 0, n0n = 0;
+        Tile Tn = T;
         if (tnext < nt) {
-            xcd_strip_tile_at(tnext, ntn, ntm, tm, tn);
-            m0n = tm * BM;
-            n0n = tn * BN;
+            Tn = tile_at(tnext);
             if (dma) {
-                stage(m0n, n0n, 0, 0);
-                if (nk > 1) stage(m0n, n0n, 1, 1);
+                stage(Tn, 0, 0);
+                if (nk > 1) stage(Tn, 1, 1);
             }
         }
         mfma_all(fa1, fb1);                                  // sub-step 1 of the last k-step
 
-        // ---- epilogue: the arithmetic and rounding of gemm_epilogue_lds
+        // ---- epilogue: the arithmetic and rounding of gemm_epilogue_lds.  Its first patch write lies behind this tile's k-loop barriers and
+        // so behind the store waves' last patch reads of the previous tile (which they finished before they came to that tile loop's first
+        // barrier): no barrier of its own orders it.
         {
             int lane_e = lane;                                // opaque: the epilogue's lane addresses are made here, not kept across the k-loops
             asm volatile("" : "+v"(lane_e));
             const int fr = lane_e & 15, fq = lane_e >> 4;
-            unsigned char* patch = smem + 2 * STAGE_BYTES + wave * PATCH;
-            const int mb = m0 + wm * (MT * 16), nb = n0 + wn * (NT * 16);
+            unsigned char* slot0 = smem + 2 * STAGE_BYTES + wave * PATCH;      // even steps (and every step of a store wave): slot `wave`
+            unsigned char* slot1 = slot0 + (dma ? 8 * PATCH : 0);              // odd steps of a DMA wave: slot wave + 8
+            const int mb = T.m0 + wm * (MT * 16), nb = T.n0 + wn * (NT * 16);
             const int oc0 = (EPI == EPI_GEGLU) ? nb / 2 : nb;
             const float* wbias = tbias + wn * (NT * 16);
-            bf16* C = reinterpret_cast<bf16*>(a.C);
+            bf16* C = reinterpret_cast<bf16*>(a.C) + T.oc;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
+                bf16x4 sm[EPI == EPI_SOFTMAX64 ? NT : 1];
+                if constexpr (EPI == EPI_SOFTMAX64) {
+                    // all 16 rows of the m-tile at once (the cross-lane steps want every lane): row fr's 64 columns of a group = 4 n-tiles x
+                    // the 4 lanes fr, fr + 16, fr + 32, fr + 48; the two 8-row steps below only write their half
+#pragma unroll
+                    for (int g = 0; g < NT / 4; ++g) {
+                        float e[16];
+                        float mx = -3.0e38f;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) { e[4 * q + c] = a.alpha * acc[i][4 * g + q][c]; mx = fmaxf(mx, e[4 * q + c]); }
+                        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                        float su = 0.f;
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) { e[q] = __builtin_amdgcn_exp2f(e[q] - mx); su += e[q]; }
+                        su += __shfl_xor(su, 16, 64);
+                        su += __shfl_xor(su, 32, 64);
+                        const float inv = 1.0f / su;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) sm[4 * g + q] = pack4(e[4 * q] * inv, e[4 * q + 1] * inv, e[4 * q + 2] * inv, e[4 * q + 3] * inv);
+                    }
+                }
 #pragma unroll
                 for (int h = 0; h < 16 / PR; ++h) {
+                    const int odd = (i * (16 / PR) + h) & 1;    // parity of the step within the tile
+                    unsigned char* patch = odd ? slot1 : slot0;
                     asm volatile("" ::: "memory");
                     if (PR == 16 || (fr >> 3) == h) {
                         const int pr = fr & (PR - 1);
@@ -559,6 +621,9 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
                                 const f32x2 o23 = f32x2{x[2] + bx.z, x[3] + bx.w} * g23;
                                 *reinterpret_cast<bf16x4*>(patch + pr * STRIDE + (16 * p + 4 * fq) * 2) = pack4(o01[0], o01[1], o23[0], o23[1]);
                             }
+                        } else if constexpr (EPI == EPI_SOFTMAX64) {
+#pragma unroll
+                            for (int j = 0; j < NT; ++j) *reinterpret_cast<bf16x4*>(patch + pr * STRIDE + (16 * j + 4 * fq) * 2) = sm[j];
                         } else {
 #pragma unroll
                             for (int j = 0; j < NT; ++j) {
@@ -572,18 +637,24 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
                         }
                     }
                     asm volatile("" ::: "memory");
-                    __builtin_amdgcn_s_waitcnt(W_LGKM);
-                    __builtin_amdgcn_s_barrier();          // every patch of this step is written
+                    __builtin_amdgcn_s_waitcnt(W_LGKM);        // my patch is in LDS
+                    asm volatile("" ::: "memory");
+                    // lane -> (row lane / LPR, 16-byte piece lane % LPR) of the rows going out
+                    const int r = lane_e / LPR, pc = lane_e % LPR;
+                    uint4 v[2][PR / RPI];
+                    if (!dma) {
+                        // a store wave's own patch: private to the wave, read back with no workgroup barrier in between
+#pragma unroll
+                        for (int q = 0; q < PR / RPI; ++q) v[0][q] = *reinterpret_cast<const uint4*>(slot0 + (q * RPI + r) * STRIDE + pc * 16);
+                    }
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_s_barrier();              // the step's one barrier: the DMA waves' patches of this step are written
                     asm volatile("" ::: "memory");
                     if (!dma) {
-                        // own patch (w2 = 0), then DMA wave (wave - 4)'s: 128 rows up, same columns.  All reads first, then the stores.
-                        const int r = lane_e / LPR, pc = lane_e % LPR;
-                        uint4 v[2][PR / RPI];
+                        // DMA wave (wave - 4)'s patch of this step: 128 rows up, same columns.  All reads first, then the stores.
+                        const unsigned char* partner = slot0 - DW * PATCH + (odd ? 8 * PATCH : 0);
 #pragma unroll
-                        for (int w2 = 0; w2 < 2; ++w2)
-#pragma unroll
-                            for (int q = 0; q < PR / RPI; ++q)
-                                v[w2][q] = *reinterpret_cast<const uint4*>(patch - w2 * DW * PATCH + (q * RPI + r) * STRIDE + pc * 16);
+                        for (int q = 0; q < PR / RPI; ++q) v[1][q] = *reinterpret_cast<const uint4*>(partner + (q * RPI + r) * STRIDE + pc * 16);
 #pragma unroll
                         for (int w2 = 0; w2 < 2; ++w2)
 #pragma unroll
@@ -599,17 +670,14 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmArgs a) {
                                 asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt\n\ts_nop 1" ::"v"(Cp), "v"(vv) : "memory");
                             }
                     }
-                    asm volatile("" ::: "memory");
-                    __builtin_amdgcn_s_waitcnt(W_LGKM);
-                    __builtin_amdgcn_s_barrier();          // the patches are read: the next step may overwrite them
+                    // no second barrier: the next step's patches go to the other partner slots, and a store wave's own slot is its own
                     asm volatile("" ::: "memory");
                 }
             }
         }
         if (tnext >= nt) break;
         t = tnext;
-        m0 = m0n;
-        n0 = n0n;
+        T = Tn;
     }
 }
 
@@ -667,14 +735,16 @@ static int cu_count(int& cus) {
 static int launch_persist(const GemmArgs& a, int epi, int max_workgroups, hipStream_t st) {
     int cus = 0;
     if (int rc = cu_count(cus)) return rc;
-    const int64_t tiles = (int64_t)(a.M / 256) * (a.N / 256);
+    const int64_t tiles = (int64_t)(a.M / 256) * (a.N / 256) * a.batch;
+    RALD_CHECK(tiles < (1ll << 30), "gemm: too many tiles for the persistent engine's tile index");
     const int grid = (int)std::min<int64_t>(tiles, std::min(cus, max_workgroups));
     RALD_CHECK(grid >= 1, "gemm: the persistent engine needs at least one workgroup");
-    static bool raised_bf16 = false, raised_geglu = false;
+    static bool raised_bf16 = false, raised_geglu = false, raised_softmax = false;
     switch (epi) {
+        case EPI_SOFTMAX64: return launch_dyn_lds(gemm_nt_persist_kernel<EPI_SOFTMAX64>, raised_softmax, dim3(grid), 512, PERSIST_LDS_BYTES, st, a);
         case EPI_BF16:  return launch_dyn_lds(gemm_nt_persist_kernel<EPI_BF16>, raised_bf16, dim3(grid), 512, PERSIST_LDS_BYTES, st, a);
         case EPI_GEGLU: return launch_dyn_lds(gemm_nt_persist_kernel<EPI_GEGLU>, raised_geglu, dim3(grid), 512, PERSIST_LDS_BYTES, st, a);
-        default: set_error("gemm: the persistent engine has the bf16 and GEGLU epilogues"); return 1;
+        default: set_error("gemm: the persistent engine has the bf16, GEGLU and softmax epilogues"); return 1;
     }
 }
 
@@ -716,7 +786,16 @@ int gemm_nt(const GemmArgs& a0, int epi, hipStream_t st) {
     if (epi == EPI_SOFTMAX64) {
         // whole tiles only: every wave normalises complete 64-column groups of complete rows
         RALD_CHECK(a.M % 128 == 0 && a.N % 128 == 0 && !a.bias && !a.out8 && a.alpha_ncols >= a.N, "gemm: the softmax epilogue needs M, N % 128 == 0 and no bias");
-        if (a.M % 256 == 0 && a.N % 256 == 0 && (int64_t)(a.M / 256) * (a.N / 256) * nbatch >= 256) return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
+        if (a.M % 256 == 0 && a.N % 256 == 0) {
+            const int64_t wg256 = (int64_t)(a.M / 256) * (a.N / 256) * nbatch;
+            if (a.batch2 == 1) {
+                // two or more tiles per CU, batch entries included: the persistent tile loop, batched
+                int cus = 0;
+                if (int rc = cu_count(cus)) return rc;
+                if (wg256 >= 2 * (int64_t)cus) return launch_persist(a, epi, 1 << 30, st);
+            }
+            if (wg256 >= 256) return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
+        }
         return launch_glds<128, 128, 2, 2, 2>(a, epi, st);
     }
     if (a.out8) {
@@ -766,6 +845,33 @@ int gemm_nt_256_test(const GemmArgs& a0, int epi, int persistent, int max_workgr
     RALD_CHECK(a.ldc % 8 == 0 && a.ldc >= (epi == EPI_GEGLU ? a.N / 2 : a.N), "gemm_nt_256_test: ldc");
     RALD_CHECK(epi != EPI_GEGLU || a.bias, "gemm_nt_256_test: GEGLU needs a packed bias");
     RALD_CHECK(max_workgroups >= 1, "gemm_nt_256_test: max_workgroups must be at least 1");
+    if (persistent) return launch_persist(a, epi, max_workgroups, st);
+    return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
+}
+
+// Test entry with a batch: gemm_nt_256_test's problem `batch` times over (entry b at A + b strideA, B + b strideB, C + b strideC; strideA or
+// strideB 0 = shared), and EPI_SOFTMAX64 beside the two others.  The persistent engine is batched for EPI_SOFTMAX64 only: a batch of the
+// other two runs on the one-tile kernel (persistent == 0).  Every argument is checked here, before the first HIP call.
+int gemm_nt_256_batched_test(const GemmArgs& a0, int epi, int persistent, int max_workgroups, hipStream_t st) {
+    GemmArgs a = a0;
+    a.flags |= GEMM_NT_STORE;
+    RALD_CHECK(epi == EPI_BF16 || epi == EPI_GEGLU || epi == EPI_SOFTMAX64, "gemm_nt_256_batched_test: EPI_BF16, EPI_GEGLU or EPI_SOFTMAX64");
+    RALD_CHECK(a.M > 0 && a.N > 0 && a.K > 0 && a.M % 256 == 0 && a.N % 256 == 0 && a.K % 64 == 0,
+               "gemm_nt_256_batched_test: M, N % 256 == 0 and K % 64 == 0 (full tiles only)");
+    RALD_CHECK(a.batch >= 1 && a.batch <= 65535 && !a.out8, "gemm_nt_256_batched_test: 1 <= batch <= 65535, bf16 output");
+    RALD_CHECK(a.batch2 == 1, "gemm_nt_256_batched_test: batch2 must be 1 (the engine has no inner batch)");
+    RALD_CHECK(a.lda % 8 == 0 && a.ldb % 8 == 0 && a.lda >= a.K && a.ldb >= a.K, "gemm_nt_256_batched_test: lda/ldb must be multiples of 8 and at least K");
+    RALD_CHECK(((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.B % 16 == 0) && ((uintptr_t)a.C % 16 == 0) && ((uintptr_t)a.bias % 16 == 0),
+               "gemm_nt_256_batched_test: pointers must be 16-byte aligned");
+    const int ncols = epi == EPI_GEGLU ? a.N / 2 : a.N;
+    RALD_CHECK(a.ldc % 8 == 0 && a.ldc >= ncols, "gemm_nt_256_batched_test: ldc");
+    RALD_CHECK(a.strideA >= 0 && a.strideB >= 0 && a.strideA % 8 == 0 && a.strideB % 8 == 0 && a.strideC % 8 == 0,
+               "gemm_nt_256_batched_test: strides must be non-negative multiples of 8 elements");
+    RALD_CHECK(a.batch == 1 || a.strideC >= (int64_t)(a.M - 1) * a.ldc + ncols, "gemm_nt_256_batched_test: strideC lets the outputs of two entries overlap");
+    RALD_CHECK(epi != EPI_GEGLU || a.bias, "gemm_nt_256_batched_test: GEGLU needs a packed bias");
+    RALD_CHECK(epi != EPI_SOFTMAX64 || (!a.bias && a.alpha_ncols >= a.N), "gemm_nt_256_batched_test: the softmax epilogue takes no bias and one alpha");
+    RALD_CHECK(max_workgroups >= 1, "gemm_nt_256_batched_test: max_workgroups must be at least 1");
+    RALD_CHECK(!persistent || a.batch == 1 || epi == EPI_SOFTMAX64, "gemm_nt_256_batched_test: the persistent engine is batched for EPI_SOFTMAX64 only");
     if (persistent) return launch_persist(a, epi, max_workgroups, st);
     return launch_glds<256, 256, 4, 2, 2>(a, epi, st);
 }

@@ -40,6 +40,9 @@ int gemm_nt(const GemmArgs& a, int epi, hipStream_t st);
 // test entry: a full-tile bf16 problem (EPI_BF16 / EPI_GEGLU, batch 1) on 256 x 256 tiles at any tile count: the persistent engine on at most
 // max_workgroups workgroups, or with persistent == 0 the one-tile LDS-DMA kernel
 int gemm_nt_256_test(const GemmArgs& a, int epi, int persistent, int max_workgroups, hipStream_t st);
+// the same with a.batch entries (strideA / strideB / strideC; batch2 must be 1) and EPI_SOFTMAX64 as a third epilogue; the persistent engine
+// takes a batch for EPI_SOFTMAX64 only
+int gemm_nt_256_batched_test(const GemmArgs& a, int epi, int persistent, int max_workgroups, hipStream_t st);
 // diagnostic: lanes that clamped an fp16 slab value since the last reset (EPI_F16S here, the per-head slabs in attn_small.hip); blocking
 int f16_saturation_gemm(unsigned* count, bool reset);
 int f16_saturation_attn(unsigned* count, bool reset);

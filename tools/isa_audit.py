@@ -58,6 +58,7 @@ HOT = (
     ("gemm.hip", "gemm_nt_glds_kernel", (256, 256, 4, 2, 2, EPI["EPI_SOFTMAX64"]), "folded cross-attention (EPI_SOFTMAX64)", 2, GEMM),
     ("gemm.hip", "gemm_nt_persist_kernel", (EPI["EPI_GEGLU"],), "FF1, persistent tile loop (EPI_GEGLU)", 2, PERSIST),
     ("gemm.hip", "gemm_nt_persist_kernel", (EPI["EPI_BF16"],), "q|k|v, persistent tile loop (EPI_BF16)", 2, PERSIST),
+    ("gemm.hip", "gemm_nt_persist_kernel", (EPI["EPI_SOFTMAX64"],), "folded cross-attention, persistent tile loop, batched (EPI_SOFTMAX64)", 2, PERSIST),
     ("gemm_ln.hip", "gemm_resid_ln_kernel", (128, 2, 4, 0, 1), "residual + LN, 128 rows, bf16, group-uniform", 2, GEMM),
     ("gemm_ln.hip", "gemm_resid_ln_kernel", (128, 2, 4, 1, 1), "residual + LN, 128 rows, MXFP8, group-uniform", 2, GEMM),
     ("gemm_ln.hip", "gemm_resid_ln_kernel", (64, 1, 8, 0, 1), "residual + LN, 64 rows, bf16, group-uniform", 2, GEMM),
