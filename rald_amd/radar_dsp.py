@@ -7,7 +7,8 @@ The reference makes each ``radarcube_raw/*.bin`` with a complex128 numpy chain o
 transform, argmax / validity / power over Doppler and the 30 % noise quantile, batched over frames.
 
 * ``antenna_array`` / ``load_radar_config`` / ``velocity_bins``: the reference's host-side set-up;
-* ``RadarDSP``: the device handle, ``cubes(adc)`` on a CUDA int16 tensor ``[B, ntx, nrx, nc, ns, 2]``;
+* ``RadarDSP``: the device handle, ``cubes(adc)`` on a CUDA int16 tensor ``[B, ntx, nrx, nc, ns, 2]``
+  (``range_doppler()`` reads the range-Doppler stage of the latest run);
 * ``load_adc_frames``, ``RAEIVVmap`` (drop-in, numpy in / numpy out), ``process_adc_files``
   (``{i:04d}.bin`` files byte-compatible with ``save_radarcube``, radar.py:56-62).
 """
@@ -105,6 +106,7 @@ class RadarDSP(_Handle):
         self.vbins = np.ascontiguousarray(velocity_bins(radar_config), dtype=np.float64)
         super().__init__("radar_dsp", C.byref(c), tx.ctypes.data, rx.ctypes.data, self.vbins.ctypes.data, len(self.vbins))
         self._ws: Dict[torch.device, torch.Tensor] = {}
+        self._last = None                                    # (batch, device) of the latest run
 
     def _run(self, frames: torch.Tensor, kind: int) -> torch.Tensor:
         _need_cuda(frames, "the ADC frames")
@@ -117,7 +119,21 @@ class RadarDSP(_Handle):
         out = torch.empty((B, *self.shape_out), dtype=torch.float32, device=x.device)
         ws = _cached_workspace(self._ws, _nbytes(lib().rald_radar_dsp_workspace_bytes(C.byref(self.cfg), B)), x.device)
         check(lib().rald_radar_dsp_run(self._h, x.data_ptr(), kind, B, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        self._last = (B, x.device)
         return out[0] if squeeze else out
+
+    def range_doppler(self) -> torch.Tensor:
+        """The range-Doppler stage of the latest cubes() / cubes_iq() call: complex64 [B, ntx * nrx, range_fft, doppler_fft], after
+        the Doppler fftshift and the velocity compensation; channel = tx data index * nrx + rx data index.  A view of the cached
+        workspace (radar_dsp_run's layout: the integer channel sums, 16 bytes per frame and channel rounded up to 256 bytes, then this
+        array), valid until the next run on that device."""
+        if self._last is None:
+            raise RuntimeError("range_doppler(): no run yet")
+        B, device = self._last
+        c = self.cfg
+        nch = c.ntx * c.nrx
+        off, n = (B * nch * 16 + 255) // 256 * 256, B * nch * c.range_fft * c.doppler_fft
+        return torch.view_as_complex(self._ws[device][off:off + n * 8].view(torch.float32).view(B, nch, c.range_fft, c.doppler_fft, 2))
 
     def cubes(self, adc: torch.Tensor) -> torch.Tensor:
         """int16 [B, ntx, nrx, nc, ns, 2] (or one frame without B) -> [B, R, A, E, 3] float32 (intensity dB, velocity,
