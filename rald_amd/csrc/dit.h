@@ -46,7 +46,7 @@ struct Stager {
 };
 std::vector<int> geglu_rowmap(int inner);
 
-// ---- radar-spectrum encoder (radar.hip): model/models_radar_encoder.py Encoder + the
+// ---- radar-spectrum encoder (radar.hip; its 3x3x3 convolutions: conv3d.hip): model/models_radar_encoder.py Encoder + the
 // tokeniser half of EDMPrecond.process_radar_cond
 struct RadarEncoder {
     struct Impl;

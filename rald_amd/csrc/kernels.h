@@ -389,18 +389,22 @@ int silu_bwd(const float* x, const float* dy, float* dx, int64_t n, hipStream_t 
 int edm_loss_grad(const float* F, const float* xn, const float* y, const float* coef, int64_t per_sample, int64_t total, float* dF, float* D_out,
                   double* loss, hipStream_t st);
 
-// ---------------------------------------------------------------- radar.hip / radar_train.hip (encoder, op level)
+// ---------------------------------------------------------------- conv3d.hip (Conv3d k3 of the radar encoder / decoder, op level)
 int conv3d_igemm(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, int B, int ID, int IH, int IW,
                  int Cin, int Cout, int stride, int pad, hipStream_t st, bf16* out_bf16 = nullptr);
 // the engine one Conv3d k3 runs on and its split-K count (1 = no split): conv3d_route is the ONE place that decides it, pure host arithmetic
 enum ConvEngine { CONV_IGEMM = 0, CONV_LINE = 1, CONV_PLANE = 2, CONV_PPLANE = 3, CONV_IGEMM_SPLIT = 4 };
-struct ConvRoute { int engine; int splits; };
+struct ConvRoute {
+    int engine, splits;
+    int lw = 0, pds = 0;    // internal, for the launch: log2 of the output line width (line shapes), planes per workgroup (CONV_PPLANE)
+};
 ConvRoute conv3d_route(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad, int allow_split);
 // conv3d_igemm with every field of the kernels' argument block: GroupNorm partials of the output from the epilogue (gn_part), and the
 // encoder's split-K route through a caller-owned workspace (allow_split = 1)
 int conv3d_full(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, bf16* out_bf16, double* gn_part,
                 float* split_ws, int64_t split_ws_bytes, int allow_split, int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad,
                 hipStream_t st);
+// ---------------------------------------------------------------- radar.hip / radar_train.hip (encoder, op level)
 int gn_finish(const double* part, double* stats, int B, int nblk, hipStream_t st);
 int upsample2_cast(const float* x, bf16* y, int B, int D, int H, int W, int C, hipStream_t st);
 int pad_cast64(const float* z, bf16* y, int64_t rows, int zc, hipStream_t st);

@@ -10,6 +10,9 @@
 // Conv3d zero padding applies to the normalised+activated tensor, i.e. out-of-range taps
 // contribute exact zeros (register zero-fill, no padded copy).  Downsample = F.pad(0,1) + conv
 // k3 s2 p0 (:37-41) is the same kernel with stride 2 and left pad 0.
+//
+// This file: conv_in, GroupNorm, the upsample / pad / token kernels, the model (weights, workspace, forward, decode, tokeniser) and the
+// op-level launchers of those kernels.  The 3x3x3 convolution engines, their route and conv3d_full are in conv3d.hip.
 #include "dit.h"
 
 #include <cmath>
@@ -167,797 +170,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
             o[j] = yv;
         }
         reinterpret_cast<bf16x4*>(y)[idx] = pack4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-// Implicit-GEMM Conv3d k3: same tile machinery as gemm_nt_kernel (128 voxels x 64 couts x 64 K,
-// 4 waves 2x2, XOR-swizzled double-buffered LDS); the A rows are gathered per tap.
-struct ConvArgs {
-    const bf16* in;      // [B][ID][IH][IW][Cin]
-    const bf16* w;       // [Cout][27][Cin]
-    const float* bias;   // [Cout]
-    const float* resid;  // [M][Cout] or nullptr
-    float* out;          // [M][Cout]
-    int B, ID, IH, IW, Cin, OD, OH, OW, Cout, stride, pad;
-    // optional: GroupNorm(32) partial statistics of the OUTPUT, one slot per 128-voxel tile (requires OD*OH*OW % 128 == 0 so that
-    // no tile straddles two samples): gn_part[tile][32 groups][2] doubles = {sum, sumsq}; saves the statistics pass over the fp32
-    // activation (537 MB at full resolution, B = 8) that the next GroupNorm would otherwise make
-    double* gn_part = nullptr;
-    // optional split-K (few tiles, long K: the 64- and 512-voxel levels): gridDim.z workgroups share a tile, each takes a contiguous
-    // range of k-steps and writes its raw accumulators to split_part[z][M][Cout]; conv_split_reduce_kernel adds them in order
-    float* split_part = nullptr;
-    // optional: the result as bf16 INSTEAD of fp32 (training: a data gradient whose only reader is the GroupNorm backward - half the bytes
-    // written here and read twice there); no residual, no split-K
-    bf16* out16 = nullptr;
-};
-
-// Epilogue shared by the two convolution kernels: bias (+ fp32 residual), fp32 store, optional GroupNorm partials of the output.
-// acc[i][j][e] <-> voxel m0 + wm*64 + i*16 + fr, channel n0 + wn*32 + j*16 + 4*fq + e.  Must be reached by the whole workgroup
-// after the K-loop's last barrier (it reuses the staging LDS when a.gn_part is set).
-__device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[4][2], const ConvArgs& a, int64_t M, int64_t m0, int n0, int wm, int wn, int fr,
-                                              int fq, int tid, unsigned char* smem, int64_t tile128 = -1, const float4* pre_bias = nullptr,
-                                              const float4* pre_resid = nullptr) {   // pre_*: this lane's bias [NT] / residual [MT][NT] values, loaded earlier
-    constexpr int BM = 128, BN = 64, MT = 4, NT = 2;
-    float cs[NT][4], cq[NT][4];                 // per-lane channel sums over this lane's MT voxels (GroupNorm partials)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { cs[j][e] = 0.f; cq[j][e] = 0.f; }
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int64_t m = m0 + wm * (BM / 2) + i * 16 + fr;
-        if (m >= M) continue;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int n = n0 + wn * (BN / 2) + j * 16 + 4 * fq;
-            if (n >= a.Cout) continue;
-            const float4 b = pre_bias ? pre_bias[j] : *reinterpret_cast<const float4*>(a.bias + n);
-            f32x4 v = acc[i][j];
-            float4 o = make_float4(v[0] + b.x, v[1] + b.y, v[2] + b.z, v[3] + b.w);
-            if (a.resid) {
-                const float4 r = pre_resid ? pre_resid[i * NT + j] : *reinterpret_cast<const float4*>(a.resid + m * a.Cout + n);
-                o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-            }
-            if (a.out16) *reinterpret_cast<bf16x4*>(a.out16 + m * a.Cout + n) = pack4(o.x, o.y, o.z, o.w);
-            else *reinterpret_cast<float4*>(a.out + m * a.Cout + n) = o;
-            cs[j][0] += o.x; cs[j][1] += o.y; cs[j][2] += o.z; cs[j][3] += o.w;
-            cq[j][0] += o.x * o.x; cq[j][1] += o.y * o.y; cq[j][2] += o.z * o.z; cq[j][3] += o.w * o.w;
-        }
-    }
-    if (a.gn_part) {
-        // fixed-shape reduction (bit-reproducible): 16 voxel lanes by butterfly, the two voxel halves (wm) and the channels of a
-        // group in index order.  Host contract: full tiles (M % 128 == 0, Cout % 64 == 0), the K-loop's last barrier has passed.
-        float2* sc = reinterpret_cast<float2*>(smem);                       // [wm][64 channels of this n-tile]
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // the 16 voxel lanes of one fq share a DPP row: four row-local adds (quad swaps, half-mirror, mirror) leave the row's total in every
-                // lane at VALU rate (the ds_bpermute butterfly this replaces was 2.3 us of a 24 us tile: 128 LDS-crossbar ops and their waits)
-                float s1 = cs[j][e], s2 = cq[j][e];
-                s1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1), 0xB1, 0xf, 0xf, true));
-                s2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2), 0xB1, 0xf, 0xf, true));
-                s1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1), 0x4E, 0xf, 0xf, true));
-                s2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2), 0x4E, 0xf, 0xf, true));
-                s1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1), 0x141, 0xf, 0xf, true));
-                s2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2), 0x141, 0xf, 0xf, true));
-                s1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1), 0x140, 0xf, 0xf, true));
-                s2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2), 0x140, 0xf, 0xf, true));
-                if (fr == 0) sc[wm * 64 + wn * 32 + j * 16 + 4 * fq + e] = make_float2(s1, s2);
-            }
-        __syncthreads();
-        const int cpg = a.Cout / 32, gpt = 64 / cpg;                         // channels per group, groups in this 64-channel tile
-        if (tid < gpt) {
-            double su = 0.0, sq = 0.0;
-            for (int w = 0; w < 2; ++w)
-                for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { su += (double)sc[w * 64 + c].x; sq += (double)sc[w * 64 + c].y; }
-            double* o = a.gn_part + ((tile128 >= 0 ? tile128 : (int64_t)blockIdx.y) * 32 + n0 / cpg + tid) * 2;
-            o[0] = su; o[1] = sq;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void conv3d_igemm_kernel(ConvArgs a) {
-    constexpr int BM = 128, BN = 64, BK = 64;
-    constexpr int MT = BM / 32, NT = BN / 32, PA = BM / 32, PB = BN / 32;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (BM + BN) * BK * 2];
-    bf16x8* sA = reinterpret_cast<bf16x8*>(smem);
-    bf16x8* sB = reinterpret_cast<bf16x8*>(smem + 2 * BM * BK * 2);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
-    const int64_t m0 = (int64_t)blockIdx.y * BM;
-    const int n0 = blockIdx.x * BN;
-    const int srow = tid >> 3, schunk = tid & 7;
-
-    // per staged row: base voxel coordinates of the receptive field
-    int rb[PA], rd[PA], rh[PA], rw[PA];
-#pragma unroll
-    for (int p = 0; p < PA; ++p) {
-        int64_t m = m0 + srow + 32 * p;
-        if (m >= M) m = M - 1;
-        const int ow = (int)(m % a.OW);
-        int64_t r = m / a.OW;
-        const int oh = (int)(r % a.OH); r /= a.OH;
-        const int od = (int)(r % a.OD);
-        rb[p] = (int)(r / a.OD);
-        rd[p] = od * a.stride - a.pad; rh[p] = oh * a.stride - a.pad; rw[p] = ow * a.stride - a.pad;
-    }
-    const bf16* gB[PB];
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-        int r = n0 + srow + 32 * p;
-        r = r < a.Cout ? r : a.Cout - 1;
-        gB[p] = a.w + (int64_t)r * 27 * a.Cin + schunk * 8;
-    }
-    const int cpk = a.Cin / BK;                 // K-steps per tap
-    const int nk = 27 * cpk;
-    bf16x8 rA[PA], rB[PB];
-    auto load_tile = [&](int kt) {
-        const int tap = kt / cpk, c0 = (kt - tap * cpk) * BK;
-        const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
-#pragma unroll
-        for (int p = 0; p < PA; ++p) {
-            const int id = rd[p] + kd, ih = rh[p] + kh, iw = rw[p] + kw;
-            bf16x8 v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (bf16)0.f;
-            if ((unsigned)id < (unsigned)a.ID && (unsigned)ih < (unsigned)a.IH && (unsigned)iw < (unsigned)a.IW)
-                v = *reinterpret_cast<const bf16x8*>(a.in + ((((int64_t)rb[p] * a.ID + id) * a.IH + ih) * a.IW + iw) * a.Cin + c0 + schunk * 8);
-            rA[p] = v;
-        }
-#pragma unroll
-        for (int p = 0; p < PB; ++p) rB[p] = *reinterpret_cast<const bf16x8*>(gB[p] + (int64_t)kt * BK);
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < PA; ++p) {
-            const int r = srow + 32 * p;
-            sA[(buf * BM + r) * 8 + (schunk ^ (r & 7))] = rA[p];
-        }
-#pragma unroll
-        for (int p = 0; p < PB; ++p) {
-            const int r = srow + 32 * p;
-            sB[(buf * BN + r) * 8 + (schunk ^ (r & 7))] = rB[p];
-        }
-    };
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int k_begin = (int)((int64_t)nk * blockIdx.z / gridDim.z), k_end = (int)((int64_t)nk * (blockIdx.z + 1) / gridDim.z);
-    load_tile(k_begin);
-    store_tile(k_begin & 1);
-    __syncthreads();
-    const int fr = lane & 15, fq = lane >> 4;
-    for (int kt = k_begin; kt < k_end; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < k_end) load_tile(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 fa[MT], fb[NT];
-            const int chunk = kk * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int r = wm * (BM / 2) + i * 16 + fr;
-                fa[i] = sA[(buf * BM + r) * 8 + (chunk ^ (r & 7))];
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int r = wn * (BN / 2) + j * 16 + fr;
-                fb[j] = sB[(buf * BN + r) * 8 + (chunk ^ (r & 7))];
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-        }
-        if (kt + 1 < k_end) store_tile(buf ^ 1);
-        __syncthreads();
-    }
-    if (a.split_part) {                          // raw partial sums of this k-range (bias / residual are added by the reduce pass)
-        float* part = a.split_part + (int64_t)blockIdx.z * M * a.Cout;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int64_t m = m0 + wm * (BM / 2) + i * 16 + fr;
-            if (m >= M) continue;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int n = n0 + wn * (BN / 2) + j * 16 + 4 * fq;
-                if (n >= a.Cout) continue;
-                *reinterpret_cast<float4*>(part + m * a.Cout + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-            }
-        }
-        return;
-    }
-    conv_epilogue(acc, a, M, m0, n0, wm, wn, fr, fq, tid, smem);
-}
-// out = bias + sum_z part[z] (+ resid), z in order; one float4 per thread.  Aliasing contract: resid == out is allowed (resblock's in-place
-// residual) although both are __restrict__ - the one thread that writes out[i .. i+3] is the only one that reads resid[i .. i+3], and its
-// store depends on that load, so no reordering the qualifier permits can change the result; `part` must not overlap either
-// (tests/test_gpu_radar_encoder_ops.py runs every split shape in place and compares bit for bit).
-__global__ __launch_bounds__(256) void conv_split_reduce_kernel(const float* __restrict__ part, int splits, int64_t MC, int Cout,
-                                                                const float* __restrict__ bias, const float* __restrict__ resid,
-                                                                float* __restrict__ out) {
-    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= MC) return;
-    const float4 b = *reinterpret_cast<const float4*>(bias + (int)(i % Cout));
-    float4 acc = *reinterpret_cast<const float4*>(part + i);
-    for (int z = 1; z < splits; ++z) {
-        const float4 p = *reinterpret_cast<const float4*>(part + (int64_t)z * MC + i);
-        acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
-    }
-    acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
-    if (resid) {
-        const float4 r = *reinterpret_cast<const float4*>(resid + i);
-        acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
-    }
-    *reinterpret_cast<float4*>(out + i) = acc;
-}
-
-// Stride-1, pad-1 variant that stages whole input LINES.  A tile is 128 consecutive output voxels = L = 128/OW complete w-lines
-// (OW = 2^lw in {8, 16, 32}); for a fixed (kd, kh) the three kw taps read the same L input lines shifted by one voxel, so the
-// lines are staged ONCE with a one-voxel apron (L x (OW+2) rows of 128 B) and the taps index into them: a third of the gathers of
-// conv3d_igemm_kernel, whose full-resolution launches run at the L2 -> CU rate of those gathers.  Same MFMA fragment layout
-// and epilogue.  Host contract: stride 1, pad 1, M % 128 == 0, Cin % 64 == 0.
-__global__ __launch_bounds__(256) void conv3d_line_kernel(ConvArgs a, int lw) {
-    constexpr int BM = 128, BN = 64, BK = 64, MT = 4, NT = 2, PB = 2, RE_MAX = 160, PAX = RE_MAX / 32;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * RE_MAX * 128 + 2 * BN * 128];
-    bf16x8* sA = reinterpret_cast<bf16x8*>(smem);                         // [2][RE_MAX rows][8 chunks]
-    bf16x8* sB = reinterpret_cast<bf16x8*>(smem + 2 * RE_MAX * 128);      // [2][64 couts][8 chunks]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
-    const int64_t m0 = (int64_t)blockIdx.y * BM;
-    const int n0 = blockIdx.x * BN;
-    const int srow = tid >> 3, schunk = tid & 7;
-    const int OW = 1 << lw, EW = OW + 2, RE = (BM >> lw) * EW;
-    // staged row e = srow + 32p -> (line l, apron column we): the line's (b, od, oh) and the input column iw = we - 1
-    int eb[PAX], ed[PAX], eh[PAX], ewi[PAX];
-    const int64_t ln0 = m0 >> lw;
-#pragma unroll
-    for (int p = 0; p < PAX; ++p) {
-        const int e = srow + 32 * p;
-        const int l = e / EW;
-        ewi[p] = e < RE ? e - l * EW - 1 : -2;                               // -2: no such row (never valid)
-        int64_t ln = ln0 + l;
-        const int64_t nlines = (int64_t)a.B * a.OD * a.OH;
-        if (ln >= nlines) ln = nlines - 1;
-        eh[p] = (int)(ln % a.OH);
-        const int64_t r = ln / a.OH;
-        ed[p] = (int)(r % a.OD);
-        eb[p] = (int)(r / a.OD);
-    }
-    const bf16* gB[PB];
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-        int r = n0 + srow + 32 * p;
-        r = r < a.Cout ? r : a.Cout - 1;
-        gB[p] = a.w + (int64_t)r * 27 * a.Cin + schunk * 8;
-    }
-    const int cpk = a.Cin / BK;
-    const int nsteps = 27 * cpk;                                             // step s = (pair * cpk + c) * 3 + kw, pair = kd*3 + kh
-    // Global loads run TWO k-steps ahead of their first use (a k-step is only 16 MFMAs per wave, far less than one memory
-    // latency): weights in two register sets that alternate by step parity, input lines loaded at kw = 0 of the previous
-    // (kd, kh) pair and written to LDS at its kw = 2.
-    bf16x8 rA[PAX], rB[2][PB];
-    auto load_A = [&](int pc) {                                              // pc = pair * cpk + c
-        const int pair = pc / cpk, c0 = (pc - pair * cpk) * BK;
-        const int kd = pair / 3, kh = pair - 3 * kd;
-#pragma unroll
-        for (int p = 0; p < PAX; ++p) {
-            const int id = ed[p] + kd - 1, ih = eh[p] + kh - 1, iw = ewi[p];
-            bf16x8 v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (bf16)0.f;
-            if ((unsigned)id < (unsigned)a.ID && (unsigned)ih < (unsigned)a.IH && (unsigned)iw < (unsigned)a.IW)
-                v = *reinterpret_cast<const bf16x8*>(a.in + ((((int64_t)eb[p] * a.ID + id) * a.IH + ih) * a.IW + iw) * a.Cin + c0 + schunk * 8);
-            rA[p] = v;
-        }
-    };
-    auto store_A = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < PAX; ++p) {
-            const int e = srow + 32 * p;
-            if (e < RE) sA[(buf * RE_MAX + e) * 8 + (schunk ^ (e & 7))] = rA[p];
-        }
-    };
-    auto load_B = [&](int s, auto PAR) {
-        constexpr int par = decltype(PAR)::value;
-        const int pc = s / 3, kw = s - 3 * pc;
-        const int pair = pc / cpk, c = pc - pair * cpk;
-        const int kt = (pair * 3 + kw) * cpk + c;                            // weight K index: tap-major, then the Cin chunk
-#pragma unroll
-        for (int p = 0; p < PB; ++p) rB[par][p] = *reinterpret_cast<const bf16x8*>(gB[p] + (int64_t)kt * BK);
-    };
-    auto store_B = [&](int buf, auto PAR) {
-        constexpr int par = decltype(PAR)::value;
-#pragma unroll
-        for (int p = 0; p < PB; ++p) {
-            const int r = srow + 32 * p;
-            sB[(buf * BN + r) * 8 + (schunk ^ (r & 7))] = rB[par][p];
-        }
-    };
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int fr = lane & 15, fq = lane >> 4;
-    int ebase[MT];                                                           // staged row of this lane's voxel at kw = 0
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int r = wm * (BM / 2) + i * 16 + fr;
-        ebase[i] = (r >> lw) * EW + (r & (OW - 1));
-    }
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    const int npc = 9 * cpk;
-    load_A(0); load_B(0, P0{});
-    store_A(0); store_B(0, P0{});
-    if (nsteps > 1) load_B(1, P1{});
-    if (npc > 1) load_A(1);
-    __syncthreads();
-    // one k-step; KW = s % 3, PAR = s & 1 (compile-time so that the register sets are not indexed dynamically)
-    auto step = [&](int pc, auto KWC, auto PARC) {
-        constexpr int kw = decltype(KWC)::value, par = decltype(PARC)::value;
-        const int s = 3 * pc + kw;
-        const int abuf = pc & 1;
-        if (s + 2 < nsteps) load_B(s + 2, PARC);                             // set `par` held B(s), already in LDS
-        if (kw == 0 && pc >= 1 && pc + 1 < npc) load_A(pc + 1);               // (pc = 0: issued in the prologue)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 fa[MT], fb[NT];
-            const int chunk = kk * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int e = ebase[i] + kw;
-                fa[i] = sA[(abuf * RE_MAX + e) * 8 + (chunk ^ (e & 7))];
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int r = wn * (BN / 2) + j * 16 + fr;
-                fb[j] = sB[(par * BN + r) * 8 + (chunk ^ (r & 7))];
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-        }
-        if (s + 1 < nsteps) store_B(par ^ 1, std::integral_constant<int, par ^ 1>{});   // B(s+1), loaded one step ago
-        if (kw == 2 && pc + 1 < npc) store_A(abuf ^ 1);                       // lines of the next pair, loaded at its kw = 0
-        __syncthreads();
-    };
-    using K0 = std::integral_constant<int, 0>;
-    using K1 = std::integral_constant<int, 1>;
-    using K2 = std::integral_constant<int, 2>;
-    for (int pc = 0; pc < npc; pc += 2) {                                    // s = 3 pc + kw: parity (pc + kw) & 1
-        step(pc, K0{}, P0{}); step(pc, K1{}, P1{}); step(pc, K2{}, P0{});
-        if (pc + 1 < npc) { step(pc + 1, K0{}, P1{}); step(pc + 1, K1{}, P0{}); step(pc + 1, K2{}, P1{}); }
-    }
-    conv_epilogue(acc, a, M, m0, n0, wm, wn, fr, fq, tid, smem);
-}
-
-// Plane-staged form for the 64-channel levels: a workgroup of 8 waves takes 256 output voxels = L = 256 / OW whole w-lines of ONE (b, d) plane
-// and stages everything those voxels ever read - the three d-planes x (L + 2) h-lines x (OW + 2) columns, <= 1 024 rows of 128 B = 128 KiB -
-// ONCE; the 27 taps then only index into that image, and the only traffic of the main loop is the weights of one (kd, kh) pair at a time
-// (3 taps, 24 KiB, from L2).  conv3d_line_kernel re-stages its lines for each of the nine (kd, kh) pairs (360 KB per 256 voxels instead of
-// 130 KB) and, worse, WAITS for them: with one or two k-steps of prefetch in registers a step lasts as long as a trip to memory - 3.6 us per
-// pair for 0.7 us of MFMA work, 18 GB/s per CU, whatever the inner loop looks like (a 3-taps-per-barrier form of that kernel with
-// software-pipelined fragment reads measured exactly the same 515 us per full-resolution convolution of 4 samples).  Here a tile pays the trip
-// once.  Measured (radar-condition encode at B = 8, eight full-resolution launches): 7.72 -> 7.06 ms, 515 -> ~455 us per launch; with the
-// staging loads redirected to one address (compile-time variant) 7.05 ms, without the epilogue 6.06 ms - what is left of a 28 us tile is ~7 us of
-// prologue (16 rows of address arithmetic, loads and LDS stores per thread, one exposed trip to memory), ~12 us of main loop (6.6 us of MFMA work:
-// two barriers and one exposed fragment-read latency per pair, one workgroup per CU) and 8.5 us of epilogue (residual read, GroupNorm partial
-// sums, fp32 stores) that nothing overlaps.  Host contract: stride 1, pad 1, Cin = 64, Cout % 64 == 0, OW in {16, 32}, OH % L == 0 (a tile never leaves its plane), M % 256 == 0.
-// LDS (dynamic): 128 KiB of lines + 24 KiB of weights; the epilogue's scratch reuses the weights' 24 KiB.
-__global__ __launch_bounds__(512) void conv3d_plane_kernel(ConvArgs a, int lw) {
-    constexpr int BN = 64, MT = 4, NT = 2, RE_MAX = 1024, PAX = RE_MAX / 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
-    bf16x8* sA = reinterpret_cast<bf16x8*>(smem3);                        // [RE rows][8 chunks], row e = ((kd * (L + 2)) + l) * (OW + 2) + we
-    bf16x8* sB = reinterpret_cast<bf16x8*>(smem3 + RE_MAX * 128);         // [3 taps][64 couts][8 chunks]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
-    const int64_t m0 = (int64_t)blockIdx.y * 256;
-    const int n0 = blockIdx.x * BN;
-    const int srow = tid >> 3, schunk = tid & 7;
-    const int OW = 1 << lw, EW = OW + 2, L = 256 >> lw, LH = L + 2, PL = LH * EW, RE = 3 * PL;
-    const int64_t ln0 = m0 >> lw;
-    const int oh0 = (int)(ln0 % a.OH);
-    const int64_t pl = ln0 / a.OH;
-    const int od = (int)(pl % a.OD), b = (int)(pl / a.OD);
-    int rw = n0 + srow;
-    rw = rw < a.Cout ? rw : a.Cout - 1;
-    const bf16* gW = a.w + (int64_t)rw * 27 * 64 + schunk * 8;               // (Cin = 64: tap t of output channel rw at element t * 64)
-    // the weights run THREE pairs ahead of their use in a register ring (12 VGPRs per pair): with one pair of prefetch every pair waited for its
-    // weights - all 256 CUs ask the L2 for the same 24 KiB at the same moment, ~3 us a trip - and a tile took 30 us for 6.6 us of MFMA work
-    bf16x8 rB[3][3];
-    auto loadW = [&](int pair, auto SLOT) {
-        constexpr int sl = decltype(SLOT)::value;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) rB[sl][kw] = *reinterpret_cast<const bf16x8*>(gW + (pair * 3 + kw) * 64);
-    };
-    auto storeW = [&](auto SLOT) {
-        constexpr int sl = decltype(SLOT)::value;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) sB[(kw * BN + srow) * 8 + (schunk ^ (srow & 7))] = rB[sl][kw];
-    };
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
-    using S2 = std::integral_constant<int, 2>;
-    {   // the tile's whole input image, once: unconditional loads from clamped addresses, zeros selected at the LDS store
-        bf16x8 rA[PAX];
-        unsigned rvalid = 0;
-#pragma unroll
-        for (int p = 0; p < PAX; ++p) {
-            const int e = srow + 64 * p;
-            const int kd = e / PL, rem = e - kd * PL;
-            const int l = rem / EW, we = rem - l * EW;
-            const int id = od + kd - 1, ih = oh0 - 1 + l, iw = we - 1;
-            const bool ok = e < RE && (unsigned)id < (unsigned)a.ID && (unsigned)ih < (unsigned)a.IH && (unsigned)iw < (unsigned)a.IW;
-            const int64_t off = ok ? ((((int64_t)b * a.ID + id) * a.IH + ih) * a.IW + iw) * 64 + schunk * 8 : (int64_t)schunk * 8;
-            rA[p] = *reinterpret_cast<const bf16x8*>(a.in + off);
-            rvalid |= ok ? (1u << p) : 0u;
-        }
-        loadW(0, S0{});
-        loadW(1, S1{});
-        loadW(2, S2{});
-        bf16x8 zero;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) zero[j] = (bf16)0.f;
-#pragma unroll
-        for (int p = 0; p < PAX; ++p) {
-            const int e = srow + 64 * p;
-            if (e < RE) sA[e * 8 + (schunk ^ (e & 7))] = (rvalid >> p) & 1 ? rA[p] : zero;
-        }
-        storeW(S0{});
-        loadW(3, S0{});
-    }
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int fr = lane & 15, fq = lane >> 4;
-    int ebase[MT];                                                           // staged row of this lane's voxel for tap (0, 0, 0)
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int r = wm * 64 + i * 16 + fr;
-        ebase[i] = (r >> lw) * EW + (r & (OW - 1));
-    }
-    // fragments of one tap (both 32-deep halves), double-buffered: tap kw + 1 is read under the MFMAs of tap kw
-    bf16x8 fa[2][2][MT], fb[2][2][NT];
-    auto rd = [&](int poff, int kw, auto BUF) {
-        constexpr int bb = decltype(BUF)::value;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int chunk = kk * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int e = ebase[i] + poff + kw;
-                fa[bb][kk][i] = sA[e * 8 + (chunk ^ (e & 7))];
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int r = wn * (BN / 2) + j * 16 + fr;
-                fb[bb][kk][j] = sB[(kw * BN + r) * 8 + (chunk ^ (r & 7))];
-            }
-        }
-    };
-    auto mm = [&](auto BUF) {
-        constexpr int bb = decltype(BUF)::value;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[bb][kk][j], fa[bb][kk][i], acc[i][j], 0, 0, 0);
-    };
-    using F0 = std::integral_constant<int, 0>;
-    using F1 = std::integral_constant<int, 1>;
-    __syncthreads();
-    auto step = [&](auto PAIR) {
-        constexpr int pair = decltype(PAIR)::value;
-        constexpr int kd = pair / 3, kh = pair - 3 * kd;
-        const int poff = (kd * LH + kh) * EW;
-        rd(poff, 0, F0{});
-        __builtin_amdgcn_sched_barrier(0);
-        rd(poff, 1, F1{});
-        mm(F0{});
-#pragma unroll
-        for (int g = 0; g < 12; ++g) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        rd(poff, 2, F0{});
-        mm(F1{});
-#pragma unroll
-        for (int g = 0; g < 12; ++g) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mm(F0{});
-        __syncthreads();                                                      // every wave has read this pair's weights
-        if constexpr (pair + 1 < 9) {
-            using SL = std::integral_constant<int, (pair + 1) % 3>;
-            storeW(SL{});                                                     // pair + 1, loaded three pairs ago
-            if constexpr (pair + 4 < 9) loadW(pair + 4, SL{});
-            __syncthreads();
-        }
-    };
-    step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
-    step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
-    // what the epilogue adds - bias and fp32 residual of this lane's outputs - is fetched under the last three pairs (one workgroup per CU:
-    // nothing else would hide that trip to memory; M % 256 == 0 and Cout % 64 == 0, so every index exists)
-    float4 pb[NT], pr[MT * NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) pb[j] = *reinterpret_cast<const float4*>(a.bias + n0 + wn * (BN / 2) + j * 16 + 4 * fq);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-            pr[i * NT + j] = a.resid ? *reinterpret_cast<const float4*>(a.resid + (m0 + wm * 64 + i * 16 + fr) * a.Cout + n0 + wn * (BN / 2) + j * 16 + 4 * fq)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-    step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{}); step(std::integral_constant<int, 8>{});
-    // the epilogue is the 128-voxel one, once per half of the tile (waves 0-3 / 4-7); its scratch lies in the weights' area
-    conv_epilogue(acc, a, M, m0 + (wm >> 1) * 128, n0, wm & 1, wn, fr, fq, tid & 255, smem3 + RE_MAX * 128 + (wm >> 1) * 2048,
-                  2 * (int64_t)blockIdx.y + (wm >> 1), pb, pr);
-}
-
-// The plane-staged form made persistent along d: a workgroup walks `ds` consecutive d-planes of one (b, 256-voxel h-block) column with a rolling window of
-// three input planes in LDS (plane id lives in slot id mod 3).  Per output tile it stages ONE new plane instead of three - loaded into registers at the start
-// of the tile, stored over the plane that leaves the window as soon as the kd = 0 pairs have read it - the weights' register ring runs on across tiles (pair (p + 4) mod 9 is
-// fetched under pair p, whatever tile that belongs to), and the next tile's first fragment reads follow this tile's output stores directly: the prologue
-// of conv3d_plane_kernel (address arithmetic, one exposed trip to memory, 16 LDS stores per thread) is paid once per `ds` tiles.
-// grid.y = columns x segments: column = (b, oh0 / L), segment = ds planes.  Host contract: conv3d_plane_kernel's, and OD % ds == 0.
-__global__ __launch_bounds__(512) void conv3d_pplane_kernel(ConvArgs a, int lw, int ds) {
-    constexpr int BN = 64, MT = 4, NT = 2, RE_MAX = 1024, PPX = 6;                 // a plane image is <= 340 rows: 6 staging rows per thread
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
-    bf16x8* sA = reinterpret_cast<bf16x8*>(smem3);                        // [3 slots][PL rows][8 chunks]; swizzle by the absolute row index
-    bf16x8* sB = reinterpret_cast<bf16x8*>(smem3 + RE_MAX * 128);         // [3 taps][64 couts][8 chunks]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
-    const int n0 = blockIdx.x * BN;
-    const int srow = tid >> 3, schunk = tid & 7;
-    const int OW = 1 << lw, EW = OW + 2, L = 256 >> lw, LH = L + 2, PL = LH * EW;
-    const int nseg = a.OD / ds, nhb = a.OH / L;
-    const int seg = blockIdx.y % nseg, col = blockIdx.y / nseg;
-    const int hb = col % nhb, b = col / nhb;
-    const int oh0 = hb * L, d_lo = seg * ds;
-    // this thread's staging rows of a plane image: row e = l * EW + we <-> input (ih = oh0 - 1 + l, iw = we - 1); the same for every plane
-    int rowoff[PPX];                                                         // element offset inside a plane, or -1
-#pragma unroll
-    for (int p = 0; p < PPX; ++p) {
-        const int e = srow + 64 * p;
-        const int l = e / EW, we = e - l * EW;
-        const int ih = oh0 - 1 + l, iw = we - 1;
-        rowoff[p] = (e < PL && (unsigned)ih < (unsigned)a.IH && (unsigned)iw < (unsigned)a.IW) ? (ih * a.IW + iw) * 64 + schunk * 8 : -1;
-    }
-    const int64_t plane_elems = (int64_t)a.IH * a.IW * 64;
-    const bf16* inb = a.in + (int64_t)b * a.ID * plane_elems;
-    bf16x8 zero;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) zero[j] = (bf16)0.f;
-    auto loadP = [&](int id, bf16x8 (&r)[PPX]) {                              // plane id (may lie outside the volume: zeros at the store)
-        const bool inside = (unsigned)id < (unsigned)a.ID;
-        const bf16* pb_ = inb + (int64_t)(inside ? id : 0) * plane_elems;
-#pragma unroll
-        for (int p = 0; p < PPX; ++p) r[p] = *reinterpret_cast<const bf16x8*>(pb_ + (rowoff[p] >= 0 ? rowoff[p] : schunk * 8));
-    };
-    auto storeP = [&](int id, const bf16x8 (&r)[PPX]) {
-        const bool inside = (unsigned)id < (unsigned)a.ID;
-        const int slot = (id + 3) % 3;
-#pragma unroll
-        for (int p = 0; p < PPX; ++p) {
-            const int e = srow + 64 * p;
-            if (e < PL) { const int ea = slot * PL + e; sA[ea * 8 + (schunk ^ (ea & 7))] = (inside && rowoff[p] >= 0) ? r[p] : zero; }
-        }
-    };
-    int rw = n0 + srow;
-    rw = rw < a.Cout ? rw : a.Cout - 1;
-    const bf16* gW = a.w + (int64_t)rw * 27 * 64 + schunk * 8;
-    bf16x8 rB[3][3];
-    auto loadW = [&](int pair, auto SLOT) {
-        constexpr int sl = decltype(SLOT)::value;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) rB[sl][kw] = *reinterpret_cast<const bf16x8*>(gW + (pair * 3 + kw) * 64);
-    };
-    auto storeW = [&](auto SLOT) {
-        constexpr int sl = decltype(SLOT)::value;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) sB[(kw * BN + srow) * 8 + (schunk ^ (srow & 7))] = rB[sl][kw];
-    };
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
-    using S2 = std::integral_constant<int, 2>;
-    bf16x8 rP[PPX];
-    {   // the first window: planes d_lo - 1, d_lo, d_lo + 1
-        bf16x8 r0[PPX], r1[PPX];
-        loadP(d_lo - 1, r0); loadP(d_lo, r1); loadP(d_lo + 1, rP);
-        loadW(0, S0{}); loadW(1, S1{}); loadW(2, S2{});
-        storeP(d_lo - 1, r0); storeP(d_lo, r1); storeP(d_lo + 1, rP);
-        storeW(S0{});
-        loadW(3, S0{});
-    }
-    const int fr = lane & 15, fq = lane >> 4;
-    int ebase[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int r = wm * 64 + i * 16 + fr;
-        ebase[i] = (r >> lw) * EW + (r & (OW - 1));
-    }
-    float4 pb[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) pb[j] = *reinterpret_cast<const float4*>(a.bias + n0 + wn * (BN / 2) + j * 16 + 4 * fq);
-    f32x4 acc[MT][NT];
-    bf16x8 fa[2][2][MT], fb[2][2][NT];
-    auto rd = [&](int poff, int kw, auto BUF) {
-        constexpr int bb = decltype(BUF)::value;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int chunk = kk * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int e = ebase[i] + poff + kw;
-                fa[bb][kk][i] = sA[e * 8 + (chunk ^ (e & 7))];
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int r = wn * (BN / 2) + j * 16 + fr;
-                fb[bb][kk][j] = sB[(kw * BN + r) * 8 + (chunk ^ (r & 7))];
-            }
-        }
-    };
-    auto mm = [&](auto BUF) {
-        constexpr int bb = decltype(BUF)::value;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[bb][kk][j], fa[bb][kk][i], acc[i][j], 0, 0, 0);
-    };
-    using F0 = std::integral_constant<int, 0>;
-    using F1 = std::integral_constant<int, 1>;
-    __syncthreads();
-    for (int d = d_lo; d < d_lo + ds; ++d) {
-        const bool more = d + 1 < d_lo + ds;
-        if (more) loadP(d + 2, rP);                                          // the plane the NEXT tile adds to the window: a whole tile ahead
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int64_t m0 = (((int64_t)b * a.OD + d) * a.OH + oh0) * OW;
-        const int sl0 = (d + 2) % 3;                                          // slot of plane d - 1; d -> (sl0 + 1) % 3, d + 1 -> (sl0 + 2) % 3
-        float4 pr[MT * NT];
-        auto step = [&](auto PAIR) {
-            constexpr int pair = decltype(PAIR)::value;
-            constexpr int kd = pair / 3, kh = pair - 3 * kd;
-            int slot = sl0 + kd;
-            slot = slot >= 3 ? slot - 3 : slot;
-            const int poff = slot * PL + kh * EW;
-            rd(poff, 0, F0{});
-            __builtin_amdgcn_sched_barrier(0);
-            rd(poff, 1, F1{});
-            mm(F0{});
-#pragma unroll
-            for (int g = 0; g < 12; ++g) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            rd(poff, 2, F0{});
-            mm(F1{});
-#pragma unroll
-            for (int g = 0; g < 12; ++g) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            mm(F0{});
-            __syncthreads();                                                  // every wave has read this pair's weights
-            if constexpr (pair < 8) {
-                using SL = std::integral_constant<int, (pair + 1) % 3>;
-                storeW(SL{});                                                 // pair + 1, loaded three pairs ago
-                loadW((pair + 4) % 9, SL{});                                  // (wraps into the next tile: the weights do not depend on the tile)
-                if constexpr (pair == 2) { if (more) storeP(d + 2, rP); }     // over plane d - 1, whose last readers were pairs 0-2 (frees rP's registers)
-                __syncthreads();
-            }
-        };
-        step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
-        step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                pr[i * NT + j] = a.resid ? *reinterpret_cast<const float4*>(a.resid + (m0 + wm * 64 + i * 16 + fr) * a.Cout + n0 + wn * (BN / 2) + j * 16 + 4 * fq)
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
-        step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{}); step(std::integral_constant<int, 8>{});
-        // (after pair 8's barrier nobody reads the weights' area: the epilogue's scratch lies there)
-        conv_epilogue(acc, a, M, m0 + (wm >> 1) * 128, n0, wm & 1, wn, fr, fq, tid & 255, smem3 + RE_MAX * 128 + (wm >> 1) * 2048, m0 / 128 + (wm >> 1), pb, pr);
-        if (more) {
-            __syncthreads();                                                  // the epilogue's scratch has been read
-            storeW(S0{});                                                     // pair 0 of the next tile (fetched under pair 5)
-            loadW(3, S0{});
-            __syncthreads();
-        }
-    }
-}
-
-// Engine choice for one convolution: THE one place that decides it (pure host arithmetic, no HIP call; exported as
-// rald_op_conv3d_route so that a test can ask which engine a shape runs on).  In order:
-//   CONV_IGEMM_SPLIT  allow_split, not a line shape, few tiles x long K (<= 64 tiles, >= 12 k-steps: the 512- and 64-voxel levels, every
-//                     downsample below full resolution): conv3d_igemm_kernel with gridDim.z = splits k-ranges + conv_split_reduce_kernel
-//   line shapes (stride 1, pad 1, W in {8, 16, 32}, M % 128 == 0):
-//     CONV_PPLANE     Cin = 64, Cout % 64 == 0, W >= 16, H a multiple of the 256 / W lines of a tile, D % 8 == 0 and >= 256 workgroups
-//     CONV_PLANE      the same without the D condition, M / 256 >= 256 tiles
-//     CONV_LINE       every other line shape
-//   CONV_IGEMM        everything else (stride 2, W not a power of two in range, M % 128 != 0, pad != 1)
-ConvRoute conv3d_route(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad, int allow_split) {
-    ConvRoute r{CONV_IGEMM, 1};
-    if (B <= 0 || ID <= 0 || IH <= 0 || IW <= 0 || Cin <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return r;
-    const int OD = ID / stride, OH = IH / stride, OW = IW / stride;
-    const int64_t M = (int64_t)B * OD * OH * OW;
-    const bool line_shape = stride == 1 && pad == 1 && (OW == 8 || OW == 16 || OW == 32) && M % 128 == 0 && Cin % 64 == 0;
-    if (line_shape) {
-        const int lw = OW == 8 ? 3 : OW == 16 ? 4 : 5;
-        constexpr int pds = 8;                                                // planes per persistent workgroup
-        const int Lp = 256 >> lw;
-        const bool plane_shape = Cin == 64 && Cout % 64 == 0 && lw >= 4 && OH % Lp == 0 && 3 * (Lp + 2) * (OW + 2) <= 1024;
-        if (plane_shape && OD % pds == 0 && (int64_t)B * (OH / Lp) * (OD / pds) >= 256) r.engine = CONV_PPLANE;
-        else if (plane_shape && M % 256 == 0 && M / 256 >= 256) r.engine = CONV_PLANE;
-        else r.engine = CONV_LINE;
-        return r;
-    }
-    // few tiles x long K (the 512- and 64-voxel levels: 8-64 workgroups looping over 54-108 k-steps): split K over gridDim.z
-    const int64_t tiles = (int64_t)cdiv(Cout, 64) * ((M + 127) / 128);
-    const int nk = 27 * (Cin / 64);
-    if (allow_split && tiles >= 1 && tiles <= 64 && nk >= 12 && Cout % 4 == 0) {
-        int splits = (int)(256 / tiles);
-        if (splits > 16) splits = 16;
-        if (splits > nk / 3) splits = nk / 3;
-        if (splits >= 2) { r.engine = CONV_IGEMM_SPLIT; r.splits = splits; }   // (splits * tiles <= 256: at most 8 MiB of partial sums)
-    }
-    return r;
-}
-
-// One convolution on the engine `r` names.  split_ws: r.splits * M * Cout floats when r splits (bias / residual are added by the reduce pass;
-// a.resid == a.out, the in-place residual of resblock, is fine on every route: each output element is read and then written by one thread).
-static void launch_conv(ConvArgs a, const ConvRoute& r, float* split_ws, hipStream_t st) {
-    const int64_t M = (int64_t)a.B * a.OD * a.OH * a.OW;
-    const dim3 grid(cdiv(a.Cout, 64), (unsigned)((M + 127) / 128));
-    const int lw = a.OW == 8 ? 3 : a.OW == 16 ? 4 : 5;
-    const int Lp = 256 >> lw;
-    constexpr int pds = 8;                                                    // planes per persistent workgroup (as conv3d_route)
-    constexpr int LDSP = 1024 * 128 + 3 * 64 * 128;                          // the tile's input image staged once + one (kd, kh) pair of weights
-    switch (r.engine) {
-        case CONV_PPLANE: {
-            static bool attr_set = false;
-            if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3d_pplane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSP); attr_set = true; }
-            hipLaunchKernelGGL(conv3d_pplane_kernel, dim3(cdiv(a.Cout, 64), (unsigned)(a.B * (a.OH / Lp) * (a.OD / pds))), dim3(512), LDSP, st, a, lw, pds);
-            break;
-        }
-        case CONV_PLANE: {
-            static bool attr_set = false;
-            if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3d_plane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSP); attr_set = true; }
-            hipLaunchKernelGGL(conv3d_plane_kernel, dim3(cdiv(a.Cout, 64), (unsigned)(M / 256)), dim3(512), LDSP, st, a, lw);
-            break;
-        }
-        case CONV_LINE:
-            hipLaunchKernelGGL(conv3d_line_kernel, grid, dim3(256), 0, st, a, lw);
-            break;
-        case CONV_IGEMM_SPLIT: {
-            float* out = a.out;
-            a.split_part = split_ws;
-            hipLaunchKernelGGL(conv3d_igemm_kernel, dim3(grid.x, grid.y, r.splits), dim3(256), 0, st, a);
-            const int64_t MC = M * a.Cout;
-            hipLaunchKernelGGL(conv_split_reduce_kernel, dim3((unsigned)((MC / 4 + 255) / 256)), dim3(256), 0, st, split_ws, r.splits, MC, a.Cout,
-                               a.bias, a.resid, out);
-            break;
-        }
-        default:
-            hipLaunchKernelGGL(conv3d_igemm_kernel, grid, dim3(256), 0, st, a);
     }
 }
 
@@ -1232,44 +444,32 @@ int RadarEncoder::Impl::ensure_ws(int nsub) {
 
 int RadarEncoder::Impl::gn(const float* x, const std::string& name, bf16* y, int B, int S, int C, bool swish, hipStream_t st) {
     RALD_CHECK(gn_blocks(S) <= gn_part_blocks, "radar encoder: GroupNorm partial buffer too small");
+    const float *gamma = P<float>(name + ".weight"), *beta = P<float>(name + ".bias");
     if (x == fused_src && B == fused_B && S == fused_S && C == fused_C) {
         // the convolution that produced x left per-tile partials: no statistics pass over x
-        hipLaunchKernelGGL(gn_finish_kernel, dim3(B), dim3(1024), 0, st, cpart, stats, S / 128);
-    } else {
-        double* part = stats + (size_t)B * 64;
-        hipLaunchKernelGGL(gn_stats_kernel, dim3(gn_blocks(S), B), dim3(256), 0, st, x, part, S, C, GN_VPB);
-        hipLaunchKernelGGL(gn_finish_kernel, dim3(B), dim3(1024), 0, st, part, stats, gn_blocks(S));
+        RALD_TRY(gn_finish(cpart, stats, B, S / 128, st));
+        return groupnorm_apply(x, stats, gamma, beta, y, B, S, C, swish ? 1 : 0, st);
     }
-    const int64_t quads = (int64_t)S * C / 4;
-    const int blocks = (int)((quads + 255) / 256 < 1024 ? (quads + 255) / 256 : 1024);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks, B), dim3(256), 0, st, x, stats, P<float>(name + ".weight"), P<float>(name + ".bias"), y,
-                       S, C, 1e-6f, swish ? 1 : 0);
-    RALD_HIP(hipGetLastError());
-    return 0;
+    return groupnorm_fwd(x, gamma, beta, y, stats, B, S, C, swish ? 1 : 0, st);
 }
 
+// One 3x3x3 convolution of the model through conv3d_full (its checks, the route, split-K through spart).  What stays here is the
+// bookkeeping of the GroupNorm partials: a convolution into a trunk buffer leaves them in cpart where the shape allows, and fused_src
+// names the activation they belong to until something else writes that buffer.
 int RadarEncoder::Impl::run_conv(const bf16* in, const std::string& name, const float* resid, float* out, int B, int ID, int IH,
                                  int IW, int cin, int cout, int stride, int pad, hipStream_t st) {
-    ConvArgs a;
-    a.in = in; a.w = P<bf16>(name + ".weight"); a.bias = P<float>(name + ".bias"); a.resid = resid; a.out = out;
-    a.B = B; a.ID = ID; a.IH = IH; a.IW = IW; a.Cin = cin; a.Cout = cout; a.stride = stride; a.pad = pad;
-    a.OD = ID / stride; a.OH = IH / stride; a.OW = IW / stride;
-    RALD_CHECK(cin % 64 == 0 && cout % 4 == 0, "conv3d: Cin must be a multiple of 64 and Cout of 4");
-    const int64_t M = (int64_t)B * a.OD * a.OH * a.OW;
-    const int So = a.OD * a.OH * a.OW;
-    const ConvRoute r = conv3d_route(B, ID, IH, IW, cin, cout, stride, pad, 1);
-    if (r.engine == CONV_IGEMM_SPLIT) {
-        RALD_CHECK((size_t)r.splits * M * cout * 4 <= spart_bytes, "radar encoder: split-K workspace too small");
+    const int So = (ID / stride) * (IH / stride) * (IW / stride);
+    double* part = nullptr;
+    if (conv3d_route(B, ID, IH, IW, cin, cout, stride, pad, 1).engine == CONV_IGEMM_SPLIT) {
         if (out == fused_src) fused_src = nullptr;             // no GroupNorm partials from this path
     } else if (out == f0 || out == f1 || out == f2) {
         if (So % 128 == 0 && cout % 64 == 0 && (cout == 64 || cout == 128 || cout == 256) && (size_t)B * (So / 128) * 64 * 8 <= cpart_bytes) {
-            a.gn_part = cpart;
+            part = cpart;
             fused_src = out; fused_B = B; fused_S = So; fused_C = cout;
         } else if (out == fused_src) fused_src = nullptr;      // this buffer is being overwritten without new partials
     }
-    launch_conv(a, r, spart, st);
-    RALD_HIP(hipGetLastError());
-    return 0;
+    return conv3d_full(in, P<bf16>(name + ".weight"), P<float>(name + ".bias"), resid, out, nullptr, part, spart, (int64_t)spart_bytes, 1, B, ID,
+                       IH, IW, cin, cout, stride, pad, st);
 }
 
 // ResnetBlock.forward (:82-100): x -> x + conv2(swish(GN(conv1(swish(GN(x)))))), 1x1 shortcut if channels change.
@@ -1324,14 +524,8 @@ int RadarEncoder::Impl::forward(const float* cube, int cube_ch, int B, float* zo
     float *x = f0, *t1 = f1, *t2 = f2;
     fused_src = nullptr;
     int Dd = R, Hh = A, Ww = E;
-    {
-        const int groups = ch / 8, vpb = 256 / groups;
-        const int64_t nvox = (int64_t)B * Dd * Hh * Ww;
-        RALD_CHECK(cube_ch >= cin, "radar encoder: cube has fewer channels than conv_in expects");
-        hipLaunchKernelGGL(conv_in_kernel, dim3((unsigned)((nvox + vpb - 1) / vpb)), dim3(256), cin * 27 * ch * 4, st, cube, cube_ch, cin,
-                           P<float>("conv_in.weight"), P<float>("conv_in.bias"), x, B, Dd, Hh, Ww, ch);
-        RALD_HIP(hipGetLastError());
-    }
+    RALD_CHECK(cube_ch >= cin, "radar encoder: cube has fewer channels than conv_in expects");
+    RALD_TRY(conv_in_fwd(cube, cube_ch, cin, P<float>("conv_in.weight"), P<float>("conv_in.bias"), x, B, Dd, Hh, Ww, ch, st));
     int cin = ch;
     for (int l = 0; l < 5; ++l) {
         const int cout = ch * kChMult[l];
@@ -1364,12 +558,8 @@ int RadarEncoder::Impl::decode(const float* zin, int B, float* out, hipStream_t 
     fused_src = nullptr;
     int Dd = R / 16, Hh = A / 16, Ww = E / 16;
     int cin = ch * kChMult[4];
-    {
-        const int64_t rows = (int64_t)B * Dd * Hh * Ww;
-        hipLaunchKernelGGL(pad_cast64_kernel, dim3((unsigned)((rows * 64 + 255) / 256)), dim3(256), 0, st, zin, n16, rows, zc);
-        RALD_HIP(hipGetLastError());
-        RALD_TRY(run_conv(n16, "conv_in", nullptr, x, B, Dd, Hh, Ww, 64, cin, 1, 1, st));
-    }
+    RALD_TRY(pad_cast64(zin, n16, (int64_t)B * Dd * Hh * Ww, zc, st));
+    RALD_TRY(run_conv(n16, "conv_in", nullptr, x, B, Dd, Hh, Ww, 64, cin, 1, 1, st));
     RALD_TRY(resblock(x, t1, t2, "mid.block_1", B, Dd, Hh, Ww, cin, cin, st));
     RALD_TRY(attnblock(x, "mid.attn_1", B, Dd * Hh * Ww, cin, st));
     RALD_TRY(resblock(x, t1, t2, "mid.block_2", B, Dd, Hh, Ww, cin, cin, st));
@@ -1380,10 +570,7 @@ int RadarEncoder::Impl::decode(const float* zin, int B, float* out, hipStream_t 
             cin = cout;
         }
         if (l != 0) {
-            const int64_t quads = (int64_t)B * 8 * Dd * Hh * Ww * (cin / 4);
-            const unsigned blocks = (unsigned)((quads + 255) / 256 < 8192 ? (quads + 255) / 256 : 8192);
-            hipLaunchKernelGGL(upsample2_cast_kernel, dim3(blocks), dim3(256), 0, st, x, n16, B, Dd, Hh, Ww, cin);
-            RALD_HIP(hipGetLastError());
+            RALD_TRY(upsample2_cast(x, n16, B, Dd, Hh, Ww, cin, st));
             Dd *= 2; Hh *= 2; Ww *= 2;
             RALD_TRY(run_conv(n16, "up." + std::to_string(l) + ".upsample.conv", nullptr, t1, B, Dd, Hh, Ww, cin, cin, 1, 1, st));
             std::swap(x, t1);
@@ -1437,69 +624,23 @@ int RadarEncoder::tokens(const float* cube, int B, float** tokens_out, hipStream
     float* z = nullptr;
     RALD_TRY(encode(cube, 2, B, &z, st));                      // intensity channel of the [.,2] cube (:378)
     const int nr = m.R / 16, na = m.A / 16, ne = m.E / 16;
-    hipLaunchKernelGGL(radar_token_kernel, dim3(nr * na * ne, B), dim3(256), 0, st, z, m.w_tok, m.b_tok, m.emb_r, m.emb_a, m.emb_e, m.tok, nr,
-                       na, ne, m.zc, m.token_ch);
-    RALD_HIP(hipGetLastError());
+    RALD_TRY(radar_tokens(z, m.w_tok, m.b_tok, m.emb_r, m.emb_a, m.emb_e, m.tok, B, nr, na, ne, m.zc, m.token_ch, st));
     *tokens_out = m.tok;
     return 0;
 }
 
 RadarEncoder::~RadarEncoder() { delete impl; }
 
-// ---- op-level launchers of the kernels above (used by the training path, radar_train.hip / train_encoder.py) ------
-// The complete ConvArgs at op level.  allow_split = 1: the route Impl::run_conv takes (split-K through the caller's workspace where
-// conv3d_route says so); 0: never split.  gn_part (nullable): [B*So/128][32][2] doubles, the GroupNorm partials of the output.
-// resid == out (in place) is allowed.  Every check comes before the first HIP call.
-int conv3d_full(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, bf16* out_bf16, double* gn_part,
-                float* split_ws, int64_t split_ws_bytes, int allow_split, int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad,
-                hipStream_t st) {
-    RALD_CHECK(in && w_packed && bias && (out || out_bf16), "conv3d: null pointer");
-    RALD_CHECK(!out_bf16 || (!out && !resid && (uintptr_t)out_bf16 % 8 == 0), "conv3d: the bf16 result replaces the fp32 one and takes no residual");
-    RALD_CHECK(B > 0 && ID > 0 && IH > 0 && IW > 0 && (stride == 1 || stride == 2), "conv3d: bad geometry");
-    RALD_CHECK(Cin % 64 == 0 && Cout % 4 == 0, "conv3d: Cin must be a multiple of 64 and Cout of 4");
-    RALD_CHECK(Cin > 0 && Cout > 0 && ID >= stride && IH >= stride && IW >= stride && pad >= 0 && pad <= 2, "conv3d: bad geometry");
-    RALD_CHECK(allow_split == 0 || allow_split == 1, "conv3d: allow_split is 0 (never split K) or 1 (the encoder's route)");
-    ConvArgs a;
-    a.in = in; a.w = w_packed; a.bias = bias; a.resid = resid; a.out = out; a.out16 = out_bf16;
-    a.B = B; a.ID = ID; a.IH = IH; a.IW = IW; a.Cin = Cin; a.Cout = Cout; a.stride = stride; a.pad = pad;
-    a.OD = ID / stride; a.OH = IH / stride; a.OW = IW / stride;
-    const int64_t M = (int64_t)B * a.OD * a.OH * a.OW;
-    const int64_t So = (int64_t)a.OD * a.OH * a.OW;
-    const ConvRoute r = conv3d_route(B, ID, IH, IW, Cin, Cout, stride, pad, allow_split);
-    if (r.engine == CONV_IGEMM_SPLIT) {
-        RALD_CHECK(!out_bf16, "conv3d: the bf16 result is not available where the route splits K (allow_split = 0 keeps one pass)");
-        RALD_CHECK(!gn_part, "conv3d: no GroupNorm partials (gn_part) where the route splits K");
-        RALD_CHECK(split_ws && (uintptr_t)split_ws % 16 == 0, "conv3d: split-K needs a 16-byte aligned workspace");
-        RALD_CHECK(split_ws_bytes >= (int64_t)r.splits * M * Cout * 4, "conv3d: split-K workspace too small (splits * M * Cout * 4 bytes)");
-    }
-    if (gn_part) {
-        RALD_CHECK(So % 128 == 0, "conv3d: gn_part needs output voxels per sample (So) % 128 == 0, so that no tile straddles two samples");
-        RALD_CHECK(Cout == 64 || Cout == 128 || Cout == 256, "conv3d: gn_part needs Cout of 64, 128 or 256");
-        RALD_CHECK((uintptr_t)gn_part % 8 == 0, "conv3d: gn_part must be 8-byte aligned");
-        a.gn_part = gn_part;
-    }
-    launch_conv(a, r, split_ws, st);
-    RALD_HIP(hipGetLastError());
-    return 0;
-}
-
-int conv3d_igemm(const bf16* in, const bf16* w_packed, const float* bias, const float* resid, float* out, int B, int ID, int IH, int IW,
-                 int Cin, int Cout, int stride, int pad, hipStream_t st, bf16* out_bf16) {
-    return conv3d_full(in, w_packed, bias, resid, out, out_bf16, nullptr, nullptr, 0, 0, B, ID, IH, IW, Cin, Cout, stride, pad, st);
-}
-
+// ---- op-level launchers of the kernels above: the ONE launch site of each (the model above, the training path - radar_train.hip /
+// train_encoder.py - and the tests all come through here) ------------------------------------------------------------------------
 int groupnorm_fwd(const float* x, const float* gamma, const float* beta, bf16* y, double* stats, int B, int S, int C, int swish,
                   hipStream_t st) {
     RALD_CHECK(x && gamma && beta && y && stats, "groupnorm: null pointer");
     RALD_CHECK(B > 0 && S > 0 && C % 64 == 0 && 256 % (C / 4) == 0, "groupnorm: channel count must be 64, 128 or 256");
     double* part = stats + (size_t)B * 64;                 // caller contract: B*64*(1 + ceil(S/512)) doubles
     hipLaunchKernelGGL(gn_stats_kernel, dim3(gn_blocks(S), B), dim3(256), 0, st, x, part, S, C, GN_VPB);
-    hipLaunchKernelGGL(gn_finish_kernel, dim3(B), dim3(1024), 0, st, part, stats, gn_blocks(S));
-    const int64_t quads = (int64_t)S * C / 4;
-    const int blocks = (int)((quads + 255) / 256 < 1024 ? (quads + 255) / 256 : 1024);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks, B), dim3(256), 0, st, x, stats, gamma, beta, y, S, C, 1e-6f, swish ? 1 : 0);
-    RALD_HIP(hipGetLastError());
-    return 0;
+    RALD_TRY(gn_finish(part, stats, B, gn_blocks(S), st));
+    return groupnorm_apply(x, stats, gamma, beta, y, B, S, C, swish, st);
 }
 
 // the normalisation alone from statistics already in hand (the training backward re-creates the activations it did not keep)

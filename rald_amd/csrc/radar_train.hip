@@ -1,5 +1,5 @@
 // Backward-pass building blocks of the radar-spectrum encoder (model/models_radar_encoder.py:29-241; the shipped
-// configuration trains it jointly with the denoiser, `unfreeze_radar_enc: true`).  Layout as in radar.hip:
+// configuration trains it jointly with the denoiser, `unfreeze_radar_enc: true`).  Layout as in radar.hip / conv3d.hip:
 // activations channels-last [b][d][h][w][c], fp32 trunk, bf16 conv inputs.
 //   * Conv3d data gradient = the forward implicit-GEMM kernel on dY with flipped, transposed weights
 //     (conv_pack_weights with dgrad = 1); the stride-2 Downsample's gradient first spreads dY onto the even

@@ -11,7 +11,7 @@ their gradients:
     own [Cout, Cin*27] order so it accumulates straight into ``param.grad``;
   * GroupNorm(+swish) backward in two streaming passes; AttnBlock (single head over 64 tokens) with thin GEMMs.
 
-Layout: channels-last [B, D, H, W, C]; fp32 trunk, bf16 conv inputs (as the inference path, csrc/radar.hip).
+Layout: channels-last [B, D, H, W, C]; fp32 trunk, bf16 conv inputs (as the inference path, csrc/conv3d.hip and csrc/radar.hip).
 PyTorch owns the buffers only.
 """
 from __future__ import annotations

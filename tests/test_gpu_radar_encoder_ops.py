@@ -1,4 +1,4 @@
-"""The radar encoder's kernels (rald_amd/csrc/radar.hip) per element against float64: the four implicit-GEMM Conv3d engines (igemm, line,
+"""The radar encoder's kernels (rald_amd/csrc/conv3d.hip, rald_amd/csrc/radar.hip) per element against float64: the four implicit-GEMM Conv3d engines (igemm, line,
 plane, persistent plane), the split-K route with its reduce pass, the GroupNorm partials of the convolution epilogue, gn_finish, the
 GroupNorm forward, and the three small data-movement / tokeniser kernels.  Conventions of tests/test_gpu_train_ops.py (whose helpers
 this file imports): the reference is a plain float64 statement on the CPU from exactly the values the kernel read; B >= 3 where the
@@ -152,7 +152,7 @@ GN_SHAPES = [((3, 4, 16, 16, 64, 64), "line"), ((3, 2, 2, 32, 128, 128), "line")
              ((4, 12, 48, 32, 64, 128), "plane"), ((4, 64, 64, 32, 64, 64), "pplane")]
 
 # The encoder and decoder at R, A, E = 128, 64, 32, B = 4 (samples per pass), every convolution form in the order the two networks run them:
-# (layer, D, H, W, Cin, Cout, stride, engine, splits).  Engines as radar.hip's comments and DESIGN.md section 4 state them: the full-resolution
+# (layer, D, H, W, Cin, Cout, stride, engine, splits).  Engines as conv3d.hip's comments and DESIGN.md section 4 state them: the full-resolution
 # 64-channel level is persistent-plane, the half-resolution 64-channel level plane, the other stride-1 levels with W in {8, 16, 32} line (also
 # Cin = 128 at W = 16 and the 4-output conv_out), the downsamples at and above 16 384 output voxels plain igemm, and every convolution of the
 # 512- and 64-voxel levels split-K.

@@ -139,7 +139,7 @@ s_endpgm
 """
 
 
-def test_comparison_against_another_tree():
+def test_comparison_against_another_tree(capsys):
     old = _kernel(_MFMA_KERNEL).replace("; Occupancy", "; LDSByteSize: 4096 bytes/workgroup (compile time only)\n; Occupancy")
     assert A.resources(old) == {"NumVgprs": "100", "ScratchSize": "0", "Occupancy": "3", "LDSByteSize": "4096"}
     assert [len(b) for b in A.mfma_blocks(old)] == [5]              # the loop body: label to branch
@@ -164,6 +164,27 @@ def test_comparison_against_another_tree():
     assert A.is_compare_hot(("gemm_mx8_kernel", (128, 128, 2, 2, 3))) and A.is_compare_hot(("gemm_resid_ln_kernel", (64, 1, 8, 1, 1)))
     assert A.is_compare_hot(("gemm_nt_glds_kernel", (256, 256, 4, 2, 2, 3))) and not A.is_compare_hot(("gemm_nt_glds_kernel", (256, 256, 4, 2, 2, 1)))
     assert not A.is_compare_hot(("gemm_resid_ln_kernel", (64, 1, 8, 1, 0))) and not A.is_compare_hot(None)
+    # all engine files of a tree go into one symbol table, so a kernel that moved from radar.hip to conv3d.hip is still compared with the
+    # other tree's - a changed instruction in it is found - and a file that one tree does not have is simply absent from that tree
+    conv, gn = "_ZN4rald19conv3d_igemm_kernelENS_8ConvArgsE", "_ZN4rald15gn_stats_kernelEPKfPdiii"
+    sec = "\t.section\t.rodata\n"
+    _kernel_lds = lambda body, name: _kernel(body, name).replace("; Occupancy", "; LDSByteSize: 4096 bytes/workgroup (compile time only)\n; Occupancy")
+    old = A.engine_kernels({"radar.hip": _kernel_lds(_MFMA_KERNEL, conv) + sec + _kernel_lds("s_endpgm", gn)})
+    new = A.engine_kernels({"conv3d.hip": _kernel_lds(_MFMA_KERNEL, conv), "radar.hip": _kernel_lds("s_endpgm", gn)})
+    assert set(old) == set(new) == {conv, gn} and A.is_compare_hot_symbol(conv) and A.is_compare_hot_symbol(gn)
+    assert A.compare_kernels(old, new) == 0
+    assert "2 kernel symbols" in capsys.readouterr().out
+    flipped = _MFMA_KERNEL.replace("s_cmp_eq_u32", "s_cmp_lg_u32")
+    moved_and_changed = A.engine_kernels({"conv3d.hip": _kernel_lds(flipped, conv), "radar.hip": _kernel_lds("s_endpgm", gn)})
+    assert A.compare_kernels(old, moved_and_changed) == 1
+    out = capsys.readouterr().out
+    assert "FAIL  hot " + conv in out and "ok    hot " + gn in out
+    # a kernel that one tree lacks is one finding (the symbol sets differ); the same symbol in two files of one tree is an error
+    assert A.compare_kernels(old, A.engine_kernels({"radar.hip": _kernel_lds("s_endpgm", gn)})) == 1
+    assert "ONLY against: ['" + conv + "']" in capsys.readouterr().out
+    with pytest.raises(RuntimeError, match="two engine files"):
+        A.engine_kernels({"conv3d.hip": _kernel_lds("s_endpgm", gn), "radar.hip": _kernel_lds("s_endpgm", gn)})
+    assert "conv3d.hip" in A.ENGINE_FILES and "radar.hip" in A.ENGINE_FILES
 
 
 def test_makefile_flags_are_the_library_s():

@@ -48,7 +48,7 @@ def test_conv3d_forward_dgrad_wgrad_vs_autograd():
 
 @pytest.mark.parametrize("B,D,H,W", [(2, 32, 64, 32), (4, 64, 64, 32), (4, 32, 32, 16)])
 def test_plane_staged_convolution_equals_the_line_staged_one_on_a_crop(B, D, H, W):
-    """The 64-channel convolutions of large volumes run on the plane-staged kernels (csrc/radar.hip: conv3d_plane_kernel, and its persistent
+    """The 64-channel convolutions of large volumes run on the plane-staged kernels (csrc/conv3d.hip: conv3d_plane_kernel, and its persistent
     form conv3d_pplane_kernel from 256 columns x segments up - the second shape); small volumes stay on conv3d_line_kernel.  A convolution is
     local: the result on a d-slab of the big volume must equal the result on that slab cropped out with a one-plane halo - computed by the
     other kernel.  fp32 accumulation of the same 1 728 products per output in both: 1e-6; with the residual and as bf16 output too."""

@@ -29,7 +29,7 @@ epilogue and the key loop's blocks out in program order.  A key loop whose shape
 no LDS-DMA issue behind the barrier) is reported, not passed.
 
     python tools/isa_audit.py [--csrc DIR] [--keep DIR] [--keyloop-all]      exit status 0 = clean, 1 = findings
-    python tools/isa_audit.py --against DIR      compare gemm.hip, gemm_fp8.hip, gemm_ln.hip and radar.hip with another tree's (see compare)
+    python tools/isa_audit.py --against DIR      compare gemm.hip, gemm_fp8.hip, gemm_ln.hip, conv3d.hip and radar.hip with another tree's (see compare)
 """
 from __future__ import annotations
 
@@ -245,7 +245,7 @@ def audit(csrc: str = CSRC, keep: str | None = None, keyloop_all: bool = False) 
 
 
 # ---- comparison against another source tree (a refactor must leave the hot loops as they were) -----------------------------------
-ENGINE_FILES = ("gemm.hip", "gemm_fp8.hip", "gemm_ln.hip", "radar.hip")
+ENGINE_FILES = ("gemm.hip", "gemm_fp8.hip", "gemm_ln.hip", "conv3d.hip", "radar.hip")
 # kernels whose MFMA blocks must not change (None = every value of that template argument): the GEMM entries of HOT and the other
 # shipped tile shapes of the two LDS-DMA GEMMs
 COMPARE_HOT = tuple((k, a) for f, k, a, *_ in HOT if f in ENGINE_FILES) + (
@@ -314,34 +314,53 @@ def compare_kernel(old: str, new: str, hot: bool):
     return findings + (diffs if hot else []), notes + ([] if hot else diffs)
 
 
+def engine_kernels(asm_by_file: dict) -> dict:
+    """mangled symbol -> the kernel's text over the assembly of all of one tree's engine files ({file name: assembly}).  Symbols are unique in
+    `namespace rald`, so a kernel keeps its key whichever file holds it."""
+    out = {}
+    for name, asm in asm_by_file.items():
+        for sym, text in kernel_texts(asm).items():
+            if sym in out:
+                raise RuntimeError(f"{name}: kernel symbol {sym} is defined in two engine files")
+            out[sym] = text
+    return out
+
+
+def compare_kernels(old: dict, new: dict) -> int:
+    """Prints the comparison of two trees' symbol tables (engine_kernels); returns the number of findings (kernels, and one for a symbol set that differs)."""
+    print(f"{len(new)} kernel symbols" + ("" if set(old) == set(new) else
+          f"; ONLY against: {sorted(set(old) - set(new))}; ONLY tree: {sorted(set(new) - set(old))}"))
+    bad = int(set(old) != set(new))
+    for sym in sorted(set(old) & set(new)):
+        tid = template_id(sym)
+        hot = is_compare_hot(tid) or is_compare_hot_symbol(sym)
+        findings, notes = compare_kernel(old[sym], new[sym], hot)
+        title = f"{tid[0]}<{','.join(map(str, tid[1]))}>" if tid else sym
+        r = resources(new[sym])
+        print(f"{'FAIL' if findings else 'ok  '}  {'hot ' if hot else '    '}{title}  vgpr {r['NumVgprs']} occ {r['Occupancy']} lds {r['LDSByteSize']}: {notes[0]}")
+        for f in findings + notes[1:]:
+            print("        " + f)
+        bad += bool(findings)
+    return bad
+
+
 def compare(csrc: str, against: str, keep: str | None = None) -> int:
-    """Prints the comparison of the LDS-DMA GEMM files and radar.hip of `csrc` with those of `against`; returns the number of kernels with findings."""
+    """Prints the comparison of the engine files' kernels (LDS-DMA GEMMs, conv3d.hip, radar.hip) of `csrc` with those of `against`; returns the number of
+    findings.  All of a tree's engine files go into one symbol table first (a file that a tree does not have is skipped for that tree), so a
+    kernel that moved between files is still compared."""
     tmp = keep or tempfile.mkdtemp(prefix="isa_audit_")
-    bad = 0
     try:
-        for name in ENGINE_FILES:
-            sides = []
-            for tag, d in (("against", against), ("tree", csrc)):
-                os.makedirs(os.path.join(tmp, tag), exist_ok=True)
-                sides.append(kernel_texts(compile_to_asm(d, name, os.path.join(tmp, tag))))
-            old, new = sides
-            print(f"{name}: {len(new)} kernel symbols" + ("" if set(old) == set(new) else
-                  f"; ONLY against: {sorted(set(old) - set(new))}; ONLY tree: {sorted(set(new) - set(old))}"))
-            bad += set(old) != set(new)
-            for sym in sorted(set(old) & set(new)):
-                tid = template_id(sym)
-                hot = is_compare_hot(tid) or is_compare_hot_symbol(sym)
-                findings, notes = compare_kernel(old[sym], new[sym], hot)
-                title = f"{tid[0]}<{','.join(map(str, tid[1]))}>" if tid else sym
-                r = resources(new[sym])
-                print(f"{'FAIL' if findings else 'ok  '}  {'hot ' if hot else '    '}{title}  vgpr {r['NumVgprs']} occ {r['Occupancy']} lds {r['LDSByteSize']}: {notes[0]}")
-                for f in findings + notes[1:]:
-                    print("        " + f)
-                bad += bool(findings)
+        sides = []
+        for tag, d in (("against", against), ("tree", csrc)):
+            os.makedirs(os.path.join(tmp, tag), exist_ok=True)
+            names = [n for n in ENGINE_FILES if os.path.exists(os.path.join(d, n))]
+            print(f"{tag}: {', '.join(names)}")
+            sides.append(engine_kernels({n: compile_to_asm(d, n, os.path.join(tmp, tag)) for n in names}))
+        bad = compare_kernels(*sides)
     finally:
         if keep is None:
             shutil.rmtree(tmp, ignore_errors=True)
-    print("identical resources and hot MFMA blocks" if not bad else f"{bad} kernel(s) or file(s) with findings")
+    print("identical resources and hot MFMA blocks" if not bad else f"{bad} kernel(s) or symbol set(s) with findings")
     return bad
 
 
@@ -350,7 +369,7 @@ def main() -> int:
     ap.add_argument("--csrc", default=CSRC, help="directory with the .hip sources and the Makefile")
     ap.add_argument("--keep", default=None, help="keep the assembly files in this directory")
     ap.add_argument("--keyloop-all", action="store_true", help="hold every attention form to the key-loop rule (reports the row-major-V forms' mid-tile drain)")
-    ap.add_argument("--against", default=None, metavar="DIR", help="compare the LDS-DMA GEMM files' kernels with those of another csrc directory "
+    ap.add_argument("--against", default=None, metavar="DIR", help="compare the engine files' kernels with those of another csrc directory "
                     "(symbols, registers, scratch, occupancy, LDS; the hot kernels' MFMA blocks instruction for instruction) instead of auditing")
     o = ap.parse_args()
     if o.against:
