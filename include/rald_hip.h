@@ -212,6 +212,19 @@ int rald_ae_decode_queries_grad(rald_ae* h, const void* ctx, const float* querie
 int rald_ae_decode_queries_grad_ragged(rald_ae* h, const void* ctx, const float* queries, const int64_t* offsets, int32_t batch,
                                        int64_t max_per_sample, float* out_logits, float* out_grad, float* out_projected, float max_step,
                                        void* stream);
+/* First-return beam casting through the decoder field (rald_amd/csrc/ae_rays.hip): a LiDAR-like scan of the sample
+ * whose context is `ctx`, one launch.  origins / dirs fp32 in the decoder's normalised coordinates, ray r of the table is the segment
+ * from o to o + d; ray_batch_stride (in floats) = 0 for one [n_rays,3] table shared by all samples, or 3 * n_rays for [batch,n_rays,3].
+ * March: for k = 0 .. n_steps, t_k = (float)k / (float)n_steps, point o + t_k d (every operation rounded on its own); the ray hits at
+ * the first k whose logit is > 0 (a NaN logit never hits): k_hit = k, hi = t_k, lo = t_(k-1) (k = 0: lo = hi = 0).  Refine: n_refine
+ * bisection steps mid = 0.5f (lo + hi) for the rays with k_hit >= 1 (logit > 0: hi = mid; else lo = mid).  Every logit is
+ * rald_ae_decode_queries' on the same [n_rays,3] points, bit for bit.  Outputs: out_t [batch,n_rays] = hi (-1: no return), out_logit
+ * = the logit at hi (NaN: no return), out_step int32 = k_hit (-1), out_points (NULL to skip) [batch,n_rays,3] = o + hi d (NaN): always
+ * a point at which the logit was seen > 0.  n_steps in [1,65535], n_refine in [0,30], n_rays in [1,2^28]; a refused call (bad counts,
+ * another stride, a null required pointer) returns an error and leaves every output untouched. */
+int rald_ae_cast_rays(rald_ae* h, const void* ctx, const float* origins, const float* dirs, int64_t ray_batch_stride, int32_t batch,
+                      int64_t n_rays, int32_t n_steps, int32_t n_refine, float* out_t, float* out_logit, int32_t* out_step, float* out_points,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Radar-spectrum encoder alone: RadarAutoencoder.encoder / _encode (model/models_radar_encoder.py
@@ -662,6 +675,11 @@ int64_t rald_op_ae_decode_scratch_bytes(int32_t batch, int32_t num_latents);
 int rald_op_ae_decode(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
                       float c0, const float* queries, float* out_logits, int32_t batch, int64_t n_queries, int32_t num_latents, int32_t dim,
                       void* scratch, int64_t scratch_bytes, void* stream);
+/* rald_op_ae_cast_rays: rald_ae_cast_rays on caller-made tables, with rald_op_ae_decode's arguments, checks and scratch. */
+int rald_op_ae_cast_rays(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
+                         float c0, const float* origins, const float* dirs, int64_t ray_batch_stride, int32_t n_steps, int32_t n_refine,
+                         float* out_t, float* out_logit, int32_t* out_step, float* out_points, int32_t batch, int64_t n_rays,
+                         int32_t num_latents, int32_t dim, void* scratch, int64_t scratch_bytes, void* stream);
 /* rald_op_ae_decode_grad: rald_op_ae_decode's arguments and checks (num_latents <= 512 here) + offsets (NULL: dense; else DEVICE int64
  * [batch+1], queries / outputs concatenated and n_queries = the host bound of the longest segment), out_grad, out_projected (NULL to
  * skip) and max_step as rald_ae_decode_queries_grad.  Same scratch as rald_op_ae_decode. */

@@ -712,6 +712,53 @@ def op_ae_decode_grad(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, 
                                        B, n, M, dim, scratch.data_ptr(), nbytes, _stream()))
 
 
+def _ray_tables(origins: torch.Tensor, dirs: torch.Tensor, B: int):
+    """origins / dirs [R,3] (one table for every sample) or [B,R,3] -> (origins, dirs, ray_batch_stride in floats, R), contiguous fp32"""
+    _need_cuda(origins, "origins")
+    _need_cuda(dirs, "dirs")
+    origins, dirs = _f32c(origins), _f32c(dirs)
+    if origins.shape != dirs.shape or origins.dim() not in (2, 3) or origins.shape[-1] != 3 or origins.shape[-2] < 1:
+        raise ValueError("origins and dirs must both be [R,3] or both [B,R,3], R >= 1")
+    if origins.dim() == 3 and origins.shape[0] != B:
+        raise ValueError(f"origins / dirs hold {origins.shape[0]} samples, the latents {B}")
+    R = origins.shape[-2]
+    return origins, dirs, (3 * R if origins.dim() == 3 else 0), R
+
+
+def _ray_counts(n_steps, n_refine):
+    """the march's and the bisection's step counts, checked on the host (ValueError) -> ints"""
+    if int(n_steps) != n_steps or not 1 <= int(n_steps) <= 65535:
+        raise ValueError("n_steps must be an integer in [1, 65535]")
+    if int(n_refine) != n_refine or not 0 <= int(n_refine) <= 30:
+        raise ValueError("n_refine must be an integer in [0, 30]")
+    return int(n_steps), int(n_refine)
+
+
+def op_ae_cast_rays(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2aug: torch.Tensor, l_img: torch.Tensor, basis: torch.Tensor,
+                    c0: float, origins: torch.Tensor, dirs: torch.Tensor, ray_batch_stride: int, n_steps: int, n_refine: int,
+                    out_t: torch.Tensor, out_logit: torch.Tensor, out_step: torch.Tensor, out_points: Optional[torch.Tensor] = None,
+                    n_rays: Optional[int] = None) -> int:
+    """First-return beam casting on caller-made tables (rald_op_ae_cast_rays; tables as op_ae_decode): origins / dirs contiguous fp32
+    holding [R,3] (ray_batch_stride 0) or [B,R,3] (3 * R) in the caller's buffers, out_t / out_logit fp32 and out_step int32 of B * R
+    elements, out_points None or fp32 of 3 * B * R; n_rays = R (default: out_step's elements / B).  What the entry checks is not checked
+    here (any pointer may be None): -> its status (0 = done), the message in rald_last_error."""
+    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis")):
+        _need_cuda(t, what)
+    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
+    x, gamma, beta, t2aug, basis = (_f32c(t) for t in (x, gamma, beta, t2aug, basis))
+    B, M, dim = x.shape
+    assert t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim and basis.shape == (3, 24)
+    R = int(n_rays) if n_rays is not None else out_step.numel() // B
+    for t, dt, k in ((origins, torch.float32, None), (dirs, torch.float32, None), (out_t, torch.float32, 1), (out_logit, torch.float32, 1),
+                     (out_step, torch.int32, 1), (out_points, torch.float32, 3)):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.is_contiguous())
+    nbytes = _nbytes(lib().rald_op_ae_decode_scratch_bytes(B, M))
+    scratch = _scratch(nbytes, x.device)
+    return lib().rald_op_ae_cast_rays(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), t2aug.data_ptr(), l_img.data_ptr(), basis.data_ptr(), c0,
+                                      _opt(origins), _opt(dirs), int(ray_batch_stride), int(n_steps), int(n_refine), _opt(out_t),
+                                      _opt(out_logit), _opt(out_step), _opt(out_points), B, R, M, dim, scratch.data_ptr(), nbytes, _stream())
+
+
 class AeHandle(_Handle):
     """rald_ae*: encode / decode_latents / decode_queries of the set-latent autoencoder."""
 
@@ -816,6 +863,24 @@ class AeHandle(_Handle):
         check(lib().rald_ae_decode_queries_grad_ragged(self._h, ctx.data_ptr(), queries.data_ptr(), offsets.data_ptr(), B, int(max_per_sample),
                                                        out.data_ptr(), grad.data_ptr(), _opt(proj), float(max_step), _stream()))
         return (out, grad, proj) if project else (out, grad)
+
+    def cast_rays(self, ctx: torch.Tensor, batch: int, origins: torch.Tensor, dirs: torch.Tensor, n_steps: int = 256, n_refine: int = 8,
+                  points: bool = True):
+        """First returns of the segments o -> o + d through the decoder field of `ctx`, the context of `batch` samples
+        (rald_ae_cast_rays): origins / dirs [R,3] (shared by the samples) or [B,R,3], normalised coordinates ->
+        (t [B,R] in [0,1] or -1, logit [B,R] or NaN, step int32 [B,R] or -1[, points [B,R,3] or NaN]).  One launch, nothing read back."""
+        n_steps, n_refine = _ray_counts(n_steps, n_refine)
+        B = int(batch)
+        origins, dirs, stride, R = _ray_tables(origins, dirs, B)
+        self._check_ctx(ctx, B, "ray tables")
+        dev = origins.device
+        t = torch.empty(B, R, device=dev, dtype=torch.float32)
+        logit = torch.empty(B, R, device=dev, dtype=torch.float32)
+        step = torch.empty(B, R, device=dev, dtype=torch.int32)
+        pts = torch.empty(B, R, 3, device=dev, dtype=torch.float32) if points else None
+        check(lib().rald_ae_cast_rays(self._h, ctx.data_ptr(), origins.data_ptr(), dirs.data_ptr(), stride, B, R, n_steps, n_refine,
+                                      t.data_ptr(), logit.data_ptr(), step.data_ptr(), _opt(pts), _stream()))
+        return (t, logit, step, pts) if points else (t, logit, step)
 
 
 

@@ -73,6 +73,9 @@ struct Ae {
     // logits + d logit / d query (+ one clamped Newton step): offsets == nullptr -> dense [B][n][3], else ragged with n = max_per_sample
     int decode_queries_grad(const void* ctx, const float* q, const int64_t* offsets, int B, int64_t n, float* out, float* grad, float* proj,
                             float max_step, hipStream_t st);
+    // first-return beam casting (ae_rays.hip): origins / dirs [R][3] (ray_batch_stride 0) or [B][R][3] (3 * R); points may be null
+    int cast_rays(const void* ctx, const float* origins, const float* dirs, int64_t ray_batch_stride, int B, int64_t R, int n_steps, int n_refine,
+                  float* out_t, float* out_logit, int32_t* out_step, float* out_points, hipStream_t st);
 };
 
 }  // namespace rald

@@ -464,4 +464,20 @@ int Ae::decode_queries_grad(const void* ctx, const float* q, const int64_t* offs
     return ae_decode_grad_stream(ctx, l_img, q, offsets, out, grad, proj, max_step, basis, basis_diag, B, n, cfg.num_latents, c0, st);
 }
 
+// every refusal comes before the first launch: the outputs stay as they are
+int Ae::cast_rays(const void* ctx, const float* origins, const float* dirs, int64_t ray_batch_stride, int B, int64_t R, int n_steps, int n_refine,
+                  float* out_t, float* out_logit, int32_t* out_step, float* out_points, hipStream_t st) {
+    RALD_CHECK(finalized, "ae: weights not finalized");
+    RALD_CHECK(ctx && origins && dirs && out_t && out_logit && out_step, "ae: cast_rays: null pointer");
+    RALD_CHECK(B >= 1 && B <= 65535 && R >= 1 && R <= (1 << 28), "ae: cast_rays: bad batch / ray count");
+    RALD_CHECK(ray_batch_stride == 0 || ray_batch_stride == 3 * R, "ae: cast_rays: ray_batch_stride must be 0 or 3 * n_rays");
+    RALD_CHECK(n_steps >= 1 && n_steps <= 65535, "ae: cast_rays: n_steps must be in [1,65535]");
+    RALD_CHECK(n_refine >= 0 && n_refine <= 30, "ae: cast_rays: n_refine must be in [0,30]");
+    RALD_CHECK((uintptr_t)ctx % 16 == 0, "ae: decoder context must be 16-byte aligned");
+    RALD_TRY(ctx_registry.check(ctx, ctx_header(B), st, "decoder context"));
+    ctx = (const char*)ctx + BLOB_HEADER_BYTES;
+    return ae_cast_rays(ctx, l_img, origins, dirs, ray_batch_stride, basis, basis_diag, B, (int)R, cfg.num_latents, n_steps, n_refine, c0, out_t,
+                        out_logit, out_step, out_points, st);
+}
+
 }  // namespace rald

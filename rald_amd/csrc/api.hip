@@ -190,6 +190,13 @@ int rald_ae_decode_queries_grad_ragged(rald_ae* h, const void* ctx, const float*
     return h->impl.decode_queries_grad(ctx, queries, offsets, batch, max_per_sample, out_logits, out_grad, out_projected, max_step,
                                        (hipStream_t)stream);
 }
+int rald_ae_cast_rays(rald_ae* h, const void* ctx, const float* origins, const float* dirs, int64_t ray_batch_stride, int32_t batch,
+                      int64_t n_rays, int32_t n_steps, int32_t n_refine, float* out_t, float* out_logit, int32_t* out_step, float* out_points,
+                      void* stream) {
+    RALD_CHECK(h, "null handle");
+    return h->impl.cast_rays(ctx, origins, dirs, ray_batch_stride, batch, n_rays, n_steps, n_refine, out_t, out_logit, out_step, out_points,
+                             (hipStream_t)stream);
+}
 
 // test entry point of the streaming query decoder (ae_decode.hip)
 int rald_op_ae_decode_tables(int32_t dim, const float* wq, const float* wk, const float* norm_w, const float* norm_b, const float* wpe,
@@ -250,6 +257,34 @@ int rald_op_ae_decode_grad(const float* x, const float* gamma, const float* beta
     RALD_TRY(ae_ctx_build(x, gamma, beta, t2aug, (float*)scratch, ctx, batch, num_latents, dim, st));
     return ae_decode_grad_stream(ctx, l_img, queries, offsets, out_logits, out_grad, out_projected, max_step, basis,
                                  ae_basis_is_block_diagonal(h_basis), batch, n_queries, num_latents, c0, st);
+}
+
+// first-return beam casting on caller-made tables: rald_op_ae_decode's checks + the ray checks, all before the first HIP call (a refusal
+// leaves every output untouched), then the same context build and ae_cast_rays
+int rald_op_ae_cast_rays(const float* x, const float* gamma, const float* beta, const float* t2aug, const uint16_t* l_img, const float* basis,
+                         float c0, const float* origins, const float* dirs, int64_t ray_batch_stride, int32_t n_steps, int32_t n_refine,
+                         float* out_t, float* out_logit, int32_t* out_step, float* out_points, int32_t batch, int64_t n_rays,
+                         int32_t num_latents, int32_t dim, void* scratch, int64_t scratch_bytes, void* stream) {
+    RALD_CHECK(x && gamma && beta && t2aug && l_img && basis && origins && dirs && out_t && out_logit && out_step && scratch,
+               "rald_op_ae_cast_rays: null pointer");
+    RALD_CHECK(dim == 256 || dim == 512, "rald_op_ae_cast_rays: dim must be 256 or 512");
+    RALD_CHECK(num_latents >= 32 && num_latents <= 1024 && num_latents % 32 == 0,
+               "rald_op_ae_cast_rays: num_latents must be a multiple of 32 in [32,1024]");
+    RALD_CHECK(batch >= 1 && batch <= 65535, "rald_op_ae_cast_rays: batch must be in [1,65535]");
+    RALD_CHECK(n_rays >= 1 && n_rays <= (1 << 28), "rald_op_ae_cast_rays: n_rays must be in [1,2^28]");
+    RALD_CHECK(ray_batch_stride == 0 || ray_batch_stride == 3 * n_rays, "rald_op_ae_cast_rays: ray_batch_stride must be 0 or 3 * n_rays");
+    RALD_CHECK(n_steps >= 1 && n_steps <= 65535, "rald_op_ae_cast_rays: n_steps must be in [1,65535]");
+    RALD_CHECK(n_refine >= 0 && n_refine <= 30, "rald_op_ae_cast_rays: n_refine must be in [0,30]");
+    RALD_CHECK((uintptr_t)scratch % 16 == 0 && (uintptr_t)l_img % 16 == 0, "rald_op_ae_cast_rays: scratch and l_img must be 16-byte aligned");
+    RALD_CHECK(scratch_bytes >= ae_decode_op_scratch_bytes(batch, num_latents), "rald_op_ae_cast_rays: scratch too small");
+    hipStream_t st = (hipStream_t)stream;
+    float h_basis[72];
+    RALD_HIP(hipMemcpyAsync(h_basis, basis, sizeof(h_basis), hipMemcpyDeviceToHost, st));
+    RALD_HIP(hipStreamSynchronize(st));
+    void* ctx = (char*)scratch + ae_decode_op_ctx_offset(batch, num_latents);
+    RALD_TRY(ae_ctx_build(x, gamma, beta, t2aug, (float*)scratch, ctx, batch, num_latents, dim, st));
+    return ae_cast_rays(ctx, l_img, origins, dirs, ray_batch_stride, basis, ae_basis_is_block_diagonal(h_basis), batch, (int)n_rays, num_latents,
+                        n_steps, n_refine, c0, out_t, out_logit, out_step, out_points, st);
 }
 
 // ---- standalone radar-spectrum encoder (RadarAutoencoder.encoder) -------------------------------

@@ -293,6 +293,11 @@ int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const 
 constexpr int AE_DECODE_GRAD_MAX_LATENTS = 512;     // the second product's transposed image must fit in LDS next to the plain layout
 int ae_decode_grad_stream(const void* ctx, const unsigned short* l_img, const float* queries, const int64_t* offsets, float* out, float* grad,
                           float* proj, float max_step, const float* basis, int basis_diag, int B, int64_t n, int M, float c0, hipStream_t st);
+// ae_rays.hip: first-return beam casting through the decoder field.  origins / dirs [R][3] (ray_batch_stride 0) or
+// [B][R][3] (3 * R); every logit is ae_decode_stream's on the same points, bit for bit.  out_points may be null.
+int ae_cast_rays(const void* ctx, const unsigned short* l_img, const float* origins, const float* dirs, int64_t ray_batch_stride,
+                 const float* basis, int basis_diag, int B, int R, int M, int n_steps, int n_refine, float c0, float* out_t, float* out_logit,
+                 int* out_step, float* out_points, hipStream_t st);
 // basis_diag of a host copy of point_embed.basis [3][24]: 1 when it is block-diagonal (x -> columns 0-7, y -> 8-15, z -> 16-23), which
 // makes a projection one multiply instead of three; the one rule by which every caller picks the streaming kernel's form
 inline int ae_basis_is_block_diagonal(const float* basis_host) {

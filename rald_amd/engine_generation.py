@@ -299,6 +299,85 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     return out
 
 
+def _check_scan_inputs(sampled_tokens, args, az_deg, el_deg, n_steps, n_refine, surfaces):
+    """The argument rules of scan_point_clouds, all on the host: ValueError before any library call -> (az, el, n_steps, n_refine)."""
+    from ._handles import _ray_counts
+    _check_batch_inputs(sampled_tokens, None, surfaces)
+    az, el = QP._beam_tables(args, az_deg, el_deg)
+    n_steps, n_refine = _ray_counts(n_steps, n_refine)
+    return az, el, n_steps, n_refine
+
+
+@torch.no_grad()
+def scan_point_clouds(vae, sampled_tokens: torch.Tensor, args, az_deg, el_deg, n_steps: int = 256, n_refine: int = 8,
+                      surfaces: Optional[torch.Tensor] = None, metric_thresholds=None, normals: bool = False) -> Dict[str, object]:
+    """A LiDAR-like scan of every frame's decoder field instead of the thresholded volume of infer_point_clouds: one first return per
+    sensor beam (az_deg / el_deg [R], degrees: query_points.beam_grid), view-cone mode only.
+
+    beam_segments (the beams as segments of the normalised (r, az, el) cube, from pc_range[0] to pc_range[3]) -> KLAutoEncoder.cast_rays
+    (one launch: the beam is sampled at n_steps + 1 ranges, returns at the first positive logit, and the return is bisected n_refine
+    times) -> the existing compaction and un-normalisation (postprocess.occupied_points_ragged on the returned logits
+    and points) -> [normals: the logit's gradient at the returned points, postprocess.oriented_points_ragged] -> cartesian -> the
+    Chamfer / cloud_metrics_ragged tail of infer_point_clouds against `surfaces` [B,P,3] (normalised ground truth) unless
+    skip_eval_metric.  One host read at the end, packed as infer_point_clouds packs it.  Shape and range errors raise ValueError before
+    any GPU work.
+
+    Returns {'pred': list of B tensors [n_b,3] (metric, cartesian, on the device, in beam order), 'range': [B,R] metres on the device
+    (NaN = no return; the r column of the un-normalised polar hit point), 'beam_index': list of B int64 tensors [n_b] (the beam of
+    every row of 'pred'), 'cd': list of B floats or None (inf for a frame without returns), 'n_queries': list of B ints}
+    (+ 'metrics' with metric_thresholds, + 'normals' with normals: unit vectors [n_b,3], zero where undefined).
+    'n_queries' counts evaluated points as R * (n_steps + 1 + n_refine): an UPPER bound, a wave whose 64 beams have all returned stops
+    marching and a wave without a return between two samples skips the bisection."""
+    az, el, n_steps, n_refine = _check_scan_inputs(sampled_tokens, args, az_deg, el_deg, n_steps, n_refine, surfaces)
+    if metric_thresholds is not None:
+        metric_thresholds = PP._thresholds(metric_thresholds)
+    lidar = args.dataset.lidar
+    aniso, iso = lidar.norm_anisotropy, lidar.norm_isotropy
+    B, dev = sampled_tokens.shape[0], sampled_tokens.device
+    origins, dirs = QP.beam_segments(args, az, el, device=dev)
+    R = origins.shape[0]
+    _, logit, step, hit = vae.cast_rays(sampled_tokens, origins, dirs, n_steps, n_refine, points=True)
+    offsets = torch.arange(B + 1, dtype=torch.int64, device=dev) * R
+    flat = hit.reshape(-1, 3)
+    pts, p_off, p_idx = PP.occupied_points_ragged(logit.reshape(-1), flat, offsets, lidar.pc_range, aniso, iso, view_cone_mode=False,
+                                                  return_index=True)
+    polar = PP.inverse_norm_points(flat, lidar.pc_range, aniso, iso)
+    rng_m = torch.where(step.reshape(-1) >= 0, polar[:, 0], torch.full_like(polar[:, 0], float("nan"))).view(B, R)
+    nrm = None
+    if normals:
+        pos = torch.arange(pts.shape[0], dtype=torch.int64, device=dev)
+        frame = (torch.searchsorted(p_off, pos, right=True) - 1).clamp_(0, B - 1)
+        kept = flat[(offsets[frame] + p_idx).clamp_(0, flat.shape[0] - 1)]
+        _, grad = vae.decode_ragged_with_gradient(sampled_tokens, kept, p_off, R)
+        pts, nrm = PP.oriented_points_ragged(kept, grad, p_off, lidar.pc_range, aniso, iso, view_cone_mode=True)
+    else:
+        pts = PP.polar2cartesian(pts)                                                              # rows past the last frame: unspecified
+    cd, metrics = None, None
+    if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
+        P = surfaces.shape[1]
+        gt = PP.polar2cartesian(PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso))
+        gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
+        if metric_thresholds is None:
+            cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, R, P)
+        else:
+            metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, R, P, metric_thresholds)
+            cd = metrics["cd"]
+    extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
+    packed = torch.cat([p_off.double()] + ([cd] if cd is not None else []) + extra)
+    host = packed.cpu().tolist()                                                                    # the one host read
+    o = [int(v) for v in host[:B + 1]]
+    out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
+           "range": rng_m,
+           "beam_index": [p_idx[o[b]:o[b + 1]] for b in range(B)],
+           "cd": host[B + 1:2 * B + 1] if cd is not None else None,
+           "n_queries": [R * (n_steps + 1 + n_refine)] * B}
+    if metric_thresholds is not None:
+        out["metrics"] = PP._metrics_to_host(host[2 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
+    if nrm is not None:
+        out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
+    return out
+
+
 @torch.no_grad()
 def evaluate_sharded(model, vae, cubes: torch.Tensor, queries: torch.Tensor, eval_batch_size: int = 1,
                      metric_fn: Optional[Callable[[torch.Tensor, int], float]] = None,

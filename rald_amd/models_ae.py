@@ -107,6 +107,16 @@ class KLAutoEncoder(_HipBacked):
         with torch.no_grad():
             return self._handle().decode_queries_grad_ragged(self._context(x), queries, offsets, max_per_sample, project, max_step)
 
+    def cast_rays(self, x, origins, dirs, n_steps=256, n_refine=8, points=True):
+        """First-return scan of the decoder field, one launch: x [B,M,latent_dim]; origins / dirs [R,3] (one beam table
+        for every sample) or [B,R,3], in the decoder's normalised coordinates, beam r the segment from o to o + d.  The beam is sampled at
+        t_k = k / n_steps, k = 0 .. n_steps; it returns at the first sample whose logit is > 0, refined by n_refine bisection steps between
+        that sample and the one before.  -> (t [B,R] in [0,1], -1 without a return; logit [B,R] at the returned point - decode's bit for
+        bit there -, NaN without; step int32 [B,R], the first positive sample, -1 without[; points [B,R,3] = o + t d, NaN without]).
+        Same memoised context as decode; no autograd."""
+        with torch.no_grad():
+            return self._handle().cast_rays(self._context(x), x.shape[0], origins, dirs, n_steps, n_refine, points)
+
     def forward(self, pc, queries):
         # Route like EDMPrecond.forward: model.train() + grad mode + trainable parameters = the stage-1 training step
         # (engine_ae.py:51, :73-104); eval() / no_grad = the inference path below, unchanged.

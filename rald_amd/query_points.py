@@ -11,7 +11,7 @@ different stream, no host work).
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Union
+from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -242,3 +242,47 @@ def project_to_surface_ragged(vae, z_or_ctx: torch.Tensor, points_norm: torch.Te
     logits, grad = decode(pts, False)
     return pts, logits, grad
 
+
+
+def beam_grid(az_min: float, az_max: float, n_az: int, el_min: float, el_max: float, n_el: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The beam directions of a spinning sensor: n_az azimuths from az_min to az_max and n_el elevations from el_min to el_max (degrees,
+    both ends included, evenly spaced; a count of 1 takes the minimum) -> (az_deg [n], el_deg [n]) float64 on the host, n = n_el * n_az,
+    elevation-major: beam i has elevation i // n_az and azimuth i % n_az."""
+    n_az, n_el = int(n_az), int(n_el)
+    if n_az < 1 or n_el < 1:
+        raise ValueError("n_az and n_el must be at least 1")
+    az = torch.linspace(float(az_min), float(az_max), n_az, dtype=torch.float64)
+    el = torch.linspace(float(el_min), float(el_max), n_el, dtype=torch.float64)
+    return az.repeat(n_el), el.repeat_interleave(n_az)
+
+
+def _beam_tables(args, az_deg, el_deg):
+    """beam_segments' host checks -> (az, el) float32 [n]: ValueError before any GPU work"""
+    lidar = args.dataset.lidar
+    view_cone = lidar.get("view_cone_mode", False) if hasattr(lidar, "get") else getattr(lidar, "view_cone_mode", False)
+    if not view_cone:
+        raise ValueError("beam_segments needs view_cone_mode: the field must live in (r, az, el) for a beam to be a straight segment")
+    if not (lidar.norm_anisotropy or lidar.norm_isotropy):
+        raise ValueError("one of norm_anisotropy / norm_isotropy is required")
+    az, el = torch.as_tensor(az_deg), torch.as_tensor(el_deg)
+    if az.dim() != 1 or el.dim() != 1 or az.numel() != el.numel() or az.numel() < 1:
+        raise ValueError("az_deg and el_deg must be two vectors of the same length >= 1, one entry per beam")
+    return az.to(torch.float32), el.to(torch.float32)
+
+
+def beam_segments(args, az_deg, el_deg, r_min: Optional[float] = None, r_max: Optional[float] = None, device=None):
+    """Sensor beams as segments of the decoder's normalised coordinates (view-cone mode: the field lives in (r, az deg, el deg), so the
+    beam of direction (az, el) is the axis-0 segment from (r_min, az, el) to (r_max, az, el)): az_deg / el_deg [n] (beam_grid) ->
+    (origins [n,3], dirs [n,3]) on the device, origins = norm_points(start), dirs = norm_points(end) - norm_points(start).  r_min /
+    r_max default to pc_range[0] / pc_range[3].  ValueError outside view-cone mode and on shape errors, before any GPU work."""
+    az, el = _beam_tables(args, az_deg, el_deg)
+    lidar = args.dataset.lidar
+    r0 = float(lidar.pc_range[0] if r_min is None else r_min)
+    r1 = float(lidar.pc_range[3] if r_max is None else r_max)
+    if not (r1 > r0):
+        raise ValueError("r_max must be greater than r_min")
+    dev = _device(device, None)
+    az, el = az.to(dev), el.to(dev)
+    start = norm_points(torch.stack((torch.full_like(az, r0), az, el), dim=1), lidar.pc_range, lidar.norm_anisotropy, lidar.norm_isotropy)
+    end = norm_points(torch.stack((torch.full_like(az, r1), az, el), dim=1), lidar.pc_range, lidar.norm_anisotropy, lidar.norm_isotropy)
+    return start, end - start
