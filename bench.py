@@ -7,9 +7,12 @@ metric   : denoising steps/sec (whole node) = sample*NFE per second: one forward
 workload : BASELINE.json configs[2] - models_radar_generation DiT denoiser
            (kl_d512_m512_l32_d24_edm) on random 512x32 latents + synthetic radar-spectrum
            condition tokens [B,64,512]; seeded random weights (no checkpoints exist offline).
-extras   : the AE half of the metric (configs[1]: encode / decode ms + `roofline_ae`, one object per leg), the config-#4 chain
-           (radar cube -> 18-step sample -> decode of 1.2 M + 500 k queries, frames/s) and, at N > 1, one data-parallel
-           training step with the RCCL gradient exchange are appended to the same JSON line.
+plain    : without --full a run does only what the headline needs: set-up, warm-up, the timed NFEs, --dump-outputs, the result line
+           (the roofline figures in it come from HIP events inside the timed NFEs and cost no run of their own).
+--full   : adds everything that takes runs of its own to the same JSON line: the fp32 CPU baseline (`cpu_baseline`), the AE half of
+           the metric (configs[1]: encode / decode ms + `roofline_ae`, one object per leg), the config-#4 chain (radar cube ->
+           18-step sample -> decode of 1.2 M + 500 k queries, frames/s), the sampler / MXFP8 / training-step timings and, at N > 1,
+           one data-parallel training step with the RCCL gradient exchange.  --no-extras / --no-cpu-baseline drop one half of it.
 guard    : every RALD_* environment variable is recorded in config.env; the run exits non-zero if the loaded library is a
            PROBE build (the only build with work-skipping switches) or if a probe-only / library-override variable is set.
 outputs  : --dump-outputs DIR writes what the last timed NFE returned (rank 0's shard) as DIR/denoised.npy, float32; inputs
@@ -19,7 +22,7 @@ Multi-GPU (driver launches torchrun, one rank per GPU): samples are independent,
 is sharded across ranks with NO data-path collective ("weak" scaling: B per GPU is fixed);
 the only communication is the barrier + MAX-reduce of the elapsed time (RCCL).
 
-  python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
 """
 import argparse
 import json
@@ -210,19 +213,33 @@ def cpu_baseline_nfe(sd, depth, seconds_budget=20.0):
     return res
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128, help="samples per GPU per NFE")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and the secondary legs (AE, config-#4 chain, sampler, "
+                         "MXFP8 modes, training step); off by default")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed NFE's output as DIR/denoised.npy (float32, at most 64 MB: a fixed subset of samples beyond)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def secondary_legs(args):
+    """(cpu_baseline, extras): which of the measurements beyond the headline this run makes - none without --full."""
+    return args.full and not args.no_cpu_baseline, args.full and not args.no_extras
+
+
+def main():
+    args = parse_args()
+    want_cpu_baseline, want_extras = secondary_legs(args)
 
     env = env_guard()
     world, rank, local = dist_setup(args.gpus)
@@ -312,7 +329,7 @@ def main():
         "metric": "denoising steps/sec (whole node)", "value": value, "unit": "sample*NFE/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "full": args.full,
         "config": {"workload": "configs[2]: kl_d512_m512_l32_d24_edm denoiser NFE, 512x32 latents, 64x512 radar condition tokens (cached)",
                    "batch_per_gpu": B, "global_batch": world * B, "parallelism": f"batch-sharded x{world}, no data-path collective",
                    "nfe_schedule": schedule, "samples_per_timed_launch": Bt,
@@ -327,12 +344,12 @@ def main():
         "roofline_resid_ln": roofline_ln,
     }
     log(f"GPU: {value:.1f} sample*NFE/s, FF1 kernel {achieved:.0f} TFLOP/s over {ff1_launches} launches")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and want_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_nfe(sd, depth)
     elif rank == 0:
         out["cpu_baseline"] = None
     watchdog = None
-    if not args.no_extras:
+    if want_extras:
         # every rank runs these two legs on its own shard (frames / training samples are independent; the training step
         # exchanges gradients over RCCL); rank 0 reports the whole-job rates
         from rald_amd import bench_extras
@@ -371,7 +388,7 @@ def main():
             barrier(world)
     if watchdog is not None:
         watchdog.cancel()
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and want_extras:
         log("extras: sampler / AE timings")
         try:
             out.update(bench_extras.run(h))

@@ -1,4 +1,4 @@
-"""Secondary measurements bench.py appends to its JSON line at N=1: the 18-step Heun sampler
+"""Secondary measurements `bench.py --full` appends to its JSON line at N=1: the 18-step Heun sampler
 (35 NFE, condition cached) and - once built - AE encode/decode latency (BASELINE configs[1])."""
 from __future__ import annotations
 
