@@ -9,10 +9,15 @@
    the radar cube loading switched off (set_load_radar(False)).
 
 spconv and cumm.tensorview are not installed here, so they are stubbed in memory, as easydict and tqdm are.  The stub's
-Point2VoxelCPU3d is a RESTATEMENT of spconv's CPU voxelizer rules, not spconv itself: cell c = floor((p - lo) / v) in float32,
-outside when c < 0 or c >= grid (grid = round((hi - lo) / v)); voxels numbered in order of their first point; a new voxel beyond
-max_voxels is dropped while later points of kept voxels still count; each voxel keeps its first max_points points; coordinates in
-z, y, x order; the voxel tensor zero-filled.
+Point2VoxelCPU3d is a RESTATEMENT of spconv's CPU voxelizer rules, not spconv itself (tests/lidar_ref.py:point_to_voxel, the one
+copy): cell c = floor((p - lo) / v) in float32, outside when c < 0 or c >= grid (grid = round((hi - lo) / v)); voxels numbered in
+order of their first point; a new voxel beyond max_voxels is dropped while later points of kept voxels still count; each voxel
+keeps its first max_points points; coordinates in z, y, x order; the voxel tensor zero-filled.
+
+3. g25_lidar_configs.npz: the same loader away from the shipped flags, on scans of 4096 points (seed 2501) with num_samples 512,
+   'train' and 'test', tags iso / both / none (the norm flags), cart / cart_iso (view_cone_mode False on a 64 x 64 x 32 grid).
+   Stored: crop_b{b}, polar_b{b} as below; cfg_{tag}_pc_range / _voxel_size / _flags (view cone, anisotropic, isotropic);
+   ds_{tag}_{loader}_b{b}_sha / _in as below; the full arrays of ds_{tag}_train_b0.
 
 The scans are not stored (tests regenerate them from SEED).  Stored:
   fov, pc_range_*, voxel_size_*, caps     the configs used;  extrinsic  the reference's T_RADAR_TO_LIDAR (scipy-built)
@@ -42,6 +47,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import lidar_ref  # noqa: E402
 from rald_amd import synth  # noqa: E402
 
 SEED, FRAMES, NPTS = 2301, 2, 16384
@@ -51,6 +58,13 @@ SHIPPED = dict(pc_range=[0, -90, -20, 15.8, 90, 20], num_point_features=3, voxel
                max_number_of_voxels=50000, sampling=True, num_samples=10000, query_ratio=0.0625, norm_isotropy=False,
                norm_anisotropy=True, cache_voxel=False, view_cone_mode=True)
 VARIANTS = {"ship": {}, "cap": dict(max_number_of_voxels=600, max_points_per_voxel=3)}
+# g25_lidar_configs.npz: the shipped section with num_samples 512 on scans of 4096 points, and per tag the change from it
+SEED25, NPTS25 = 2501, 4096
+BASE25 = dict(num_samples=512)
+CART = dict(view_cone_mode=False, pc_range=[0, -8, -2, 16, 8, 2], voxel_size=[0.25, 0.25, 0.125])      # 64 x 64 x 32 cells
+CONFIGS = {"iso": dict(norm_anisotropy=False, norm_isotropy=True), "both": dict(norm_anisotropy=True, norm_isotropy=True),
+           "none": dict(norm_anisotropy=False, norm_isotropy=False), "cart": dict(CART),
+           "cart_iso": dict(CART, norm_anisotropy=False, norm_isotropy=True)}
 
 
 def sha(a) -> np.ndarray:
@@ -59,43 +73,20 @@ def sha(a) -> np.ndarray:
 
 
 class Point2VoxelCPU3d:
-    """Restatement of spconv's Point2VoxelCPU3d.point_to_voxel rules (see the module docstring); not spconv's source."""
+    """spconv's constructor and call shape around the restated rules of tests/lidar_ref.py:point_to_voxel; not spconv's source."""
 
     def __init__(self, vsize_xyz, coors_range_xyz, num_point_features, max_num_points_per_voxel, max_num_voxels):
-        self.v = np.asarray(vsize_xyz, dtype=np.float32)
-        self.lo = np.asarray(coors_range_xyz[:3], dtype=np.float32)
-        r = np.asarray(coors_range_xyz, dtype=np.float64)
-        self.grid = np.round((r[3:] - r[:3]) / np.asarray(vsize_xyz, dtype=np.float64)).astype(np.int64)
+        self.v, self.r = [float(v) for v in vsize_xyz], [float(v) for v in coors_range_xyz]
         self.F, self.maxp, self.maxv = int(num_point_features), int(max_num_points_per_voxel), int(max_num_voxels)
 
     def point_to_voxel(self, points):
-        pts = np.asarray(points, dtype=np.float32)
-        c = np.floor((pts[:, :3] - self.lo) / self.v)                          # float32 throughout
-        inside = np.all((c >= 0) & (c < self.grid.astype(np.float32)), axis=1)
-        voxels = np.zeros((self.maxv, self.maxp, self.F), dtype=np.float32)
-        coords = np.zeros((self.maxv, 3), dtype=np.int32)
-        num = np.zeros((self.maxv,), dtype=np.int32)
-        ids = {}
-        for i in np.nonzero(inside)[0]:
-            key = (int(c[i, 2]), int(c[i, 1]), int(c[i, 0]))                  # z, y, x
-            v = ids.get(key)
-            if v is None:
-                if len(ids) >= self.maxv:
-                    continue
-                v = ids[key] = len(ids)
-                coords[v] = key
-            if num[v] < self.maxp:
-                voxels[v, num[v]] = pts[i]
-                num[v] += 1
-        V = len(ids)
-
         class T:
             def __init__(self, a):
                 self.a = a
 
             def numpy(self):
                 return self.a.copy()
-        return T(voxels[:V]), T(coords[:V]), T(num[:V])
+        return tuple(T(a) for a in lidar_ref.point_to_voxel(points, self.v, self.r, self.F, self.maxp, self.maxv))
 
 
 def install_stubs():
@@ -129,6 +120,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("reference")
     ap.add_argument("--out", default=os.path.join(HERE, "g23_lidar.npz"))
+    ap.add_argument("--out-configs", default=os.path.join(HERE, "g25_lidar_configs.npz"))
     args = ap.parse_args()
     ref = os.path.abspath(args.reference)
     ED = install_stubs()
@@ -211,6 +203,57 @@ def main():
                     np.random.default_rng = orig
     np.savez_compressed(args.out, **out)
     print(f"wrote {args.out}: {os.path.getsize(args.out) / 1e3:.0f} KB")
+    configs_fixture(ED, L, torch, ColoRadarDataset, limits, args.out_configs)
+
+
+def configs_fixture(ED, L, torch, ColoRadarDataset, limits, path):
+    """g25_lidar_configs.npz: the unmodified loader away from the shipped flags (CONFIGS), on two scans of NPTS25 points."""
+    out = {"seeds": np.array([NP_SEED, TORCH_SEED]), "meta": np.array([SEED25, FRAMES, NPTS25]), "tags": np.array(list(CONFIGS))}
+    crops = []
+    for b, raw in enumerate(synth.lidar_scan(FRAMES, SEED25, NPTS25)):
+        pol = L.cartesian2polar(L.transform_lidar_data(L.remove_empty_points(raw[:, :3])))
+        kept = L.polar2cartesian(L.filter_points_polar(pol, limits)).astype(np.float32)
+        out[f"crop_b{b}"] = kept
+        out[f"polar_b{b}"] = L.cartesian2polar(kept)
+        assert out[f"polar_b{b}"].dtype == np.float32
+        crops.append(kept)
+        print(f"configs frame {b}: {len(raw)} points, {len(kept)} kept")
+    with tempfile.TemporaryDirectory() as root:
+        seq = os.path.join(root, "seq0")
+        os.makedirs(os.path.join(seq, "lidar_sc"))
+        os.makedirs(os.path.join(seq, "single_chip", "radarcube_raw"))
+        for b, kept in enumerate(crops):
+            L.save_lidar_data(kept, os.path.join(seq, "lidar_sc", f"{b:04d}.bin"))
+            open(os.path.join(seq, "single_chip", "radarcube_raw", f"{b:04d}.bin"), "wb").close()
+        with open(os.path.join(root, "split.json"), "w") as f:
+            json.dump({"train": ["seq0"], "val": ["seq0"], "test": ["seq0"]}, f)
+        orig = np.random.default_rng
+        for tag, over in CONFIGS.items():
+            lc = dict(SHIPPED, **BASE25, **over)
+            out[f"cfg_{tag}_pc_range"] = np.array(lc["pc_range"], dtype=np.float64)
+            out[f"cfg_{tag}_voxel_size"] = np.array(lc["voxel_size"], dtype=np.float64)
+            out[f"cfg_{tag}_flags"] = np.array([lc["view_cone_mode"], lc["norm_anisotropy"], lc["norm_isotropy"]], dtype=np.int64)
+            cfg = ED(split_file="split.json", lidar=ED(lc), radar=ED())
+            for loader in ("train", "test"):
+                ds = ColoRadarDataset(root, cfg, "scRadar", loader)
+                ds.set_load_radar(False)
+                g = orig(NP_SEED)
+                np.random.default_rng = lambda *a, **k: g
+                torch.manual_seed(TORCH_SEED)
+                try:
+                    for b in range(FRAMES):
+                        d = ds[b]
+                        key = f"ds_{tag}_{loader}_b{b}"
+                        out[key + "_sha"] = np.stack([sha(d["lidar_points"]), sha(d["query_points"]), sha(d["query_labels"])])
+                        out[key + "_in"] = np.array(d["in_voxel_num"])
+                        if b == 0 and loader == "train":
+                            out[key + "_lidar_points"] = d["lidar_points"].numpy()
+                            out[key + "_query_points"] = d["query_points"].numpy()
+                            out[key + "_query_labels"] = d["query_labels"].numpy()
+                finally:
+                    np.random.default_rng = orig
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e3:.0f} KB")
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from lidar_ref import polar_f32 as _polar_correctly_rounded
 
 SEED, FRAMES, NPTS = 2301, 2, 16384
 SHIPPED = dict(pc_range=[0, -90, -20, 15.8, 90, 20], num_point_features=3, voxel_size=[0.05, 0.25, 0.5], max_points_per_voxel=10,
@@ -38,16 +39,6 @@ def _ulp(a, b) -> int:
     a = np.ascontiguousarray(a, dtype=np.float32).view(np.int32).astype(np.int64)
     b = np.ascontiguousarray(b, dtype=np.float32).view(np.int32).astype(np.int64)
     return int(np.abs(a - b).max()) if a.size else 0
-
-
-def _polar_correctly_rounded(p: np.ndarray) -> np.ndarray:
-    """numpy's float32 cartesian2polar with the transcendentals correctly rounded (double, rounded once)"""
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    c = np.float32(180.0) / np.float32(np.pi)
-    r = np.sqrt(x * x + y * y + z * z)
-    az = -(np.arctan2(y.astype(np.float64), x.astype(np.float64)).astype(np.float32) * c)
-    el = np.arcsin((z / r).astype(np.float64)).astype(np.float32) * c
-    return np.stack([r, az, el], axis=1)
 
 
 def _keys(polar: np.ndarray, cfg) -> np.ndarray:
