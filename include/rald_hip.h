@@ -314,6 +314,29 @@ int rald_post_cloud_metrics_ragged(const float* pred, const int64_t* pred_offset
 int64_t rald_op_nn_scratch_bytes(int32_t batch, int64_t max_a, int64_t max_b, int64_t b_chunk);
 int rald_op_nn_ragged(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int32_t batch, int64_t max_a,
                       int64_t max_b, int64_t b_chunk, double* out_dist, int64_t* out_idx, void* scratch, int64_t scratch_bytes, void* stream);
+/* ---- farthest-point sampling: k rows per cloud, each the row farthest from the rows chosen so far.  Defined
+ * to the bit, so the result is the same in every call and in every batch:
+ *   p' = fl(p * scale) per coordinate, once (scale3_host: 3 HOST floats, NULL = 1, 1, 1);
+ *   d2(i, j) = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), dx = fl(p'_i.x - p'_j.x) ...: fp32, round to nearest, no contraction;
+ *   mind[i] = +inf; the first choice is start[b] mod n (non-negative modulo; start: DEVICE int64 [batch], NULL = 0); after a choice c,
+ *   mind[i] = min(mind[i], d2(i, c)); the next choice is the i of the largest mind[i], the SMALLEST such i on equal values.
+ * Chosen rows are not excluded: once fewer than k distinct points remain, the smallest index repeats with distance 0.
+ * out_idx int64 [batch,k]: row indices from the cloud's own first row; out_dist2 fp32 [batch,k] (may be NULL): +inf in slot 0, then
+ * mind of the chosen row when it was chosen.  A cloud of n < k rows gets its n choices, then idx = -1 and dist2 = NaN; n = 0: all.
+ * Layout: points [T,3]; offsets DEVICE int64 [batch+1], or NULL for dense clouds of n_dense rows each (cloud b at row b * n_dense);
+ * counts DEVICE int32 [batch] or NULL: the valid rows from the cloud's first row (the cropped LiDAR layout), capped at the segment.
+ * max_per_sample: HOST bound of the longest cloud, 1 .. 65536.  Nothing is read back, so it cannot be checked: a cloud LONGER than
+ * the bound is sampled from its FIRST max_per_sample rows only, silently.
+ * Coordinates must be finite.  With non-finite ones the choice is unspecified, but every index written lies in [0, n) and no address
+ * depends on the data.  One workgroup per cloud; the loop runs min(k, n) - 1 times and waits on no other workgroup.
+ * form: 0 = automatic (resident up to 16384, streaming above), 1 = resident (coordinates in registers, max_per_sample <= 16384),
+ * 2 = streaming (coordinates re-read from a scaled copy in scratch); test-facing, the result does not depend on it.
+ * scratch: rald_post_fps_scratch_bytes of the same batch, bound and form (0 bytes for the resident form: scratch may then be NULL),
+ * 16-byte aligned; -1 (and rald_last_error) for arguments the call refuses. */
+int64_t rald_post_fps_scratch_bytes(int32_t batch, int64_t max_per_sample, int32_t form);
+int rald_post_fps_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                         int64_t max_per_sample, int32_t k, const int64_t* start, const float* scale3_host, int64_t* out_idx, float* out_dist2,
+                         void* scratch, int64_t scratch_bytes, int32_t form, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

@@ -401,6 +401,19 @@ int rald_op_nn_ragged(const float* a, const int64_t* a_offsets, const float* b, 
     return cloud_nn_ragged(a, a_offsets, b, b_offsets, batch, max_a, max_b, b_chunk, out_dist, out_idx, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// ---- farthest-point sampling ------------------------------------------------------
+int64_t rald_post_fps_scratch_bytes(int32_t batch, int64_t max_per_sample, int32_t form) {
+    const int64_t n = fps_scratch_bytes(batch, max_per_sample, form);
+    if (n < 0) set_error("rald_post_fps_scratch_bytes: batch >= 1, max_per_sample 1 .. 65536 (16384 for form 1), form 0 .. 2");
+    return n;
+}
+int rald_post_fps_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                         int64_t max_per_sample, int32_t k, const int64_t* start, const float* scale3_host, int64_t* out_idx, float* out_dist2,
+                         void* scratch, int64_t scratch_bytes, int32_t form, void* stream) {
+    return fps_ragged(points, offsets, counts, batch, n_dense, max_per_sample, k, start, scale3_host, out_idx, out_dist2, scratch, scratch_bytes,
+                      form, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

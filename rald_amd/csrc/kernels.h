@@ -341,6 +341,13 @@ int cloud_metrics_ragged(const float* pred, const int64_t* pred_off, const float
                          const double* thresholds_host, int n_thr, double* out_raw, double* out_dist_pred, int64_t* out_idx_pred,
                          double* out_dist_gt, int64_t* out_idx_gt, void* scratch, hipStream_t st);
 
+// ---------------------------------------------------------------- fps.hip
+// farthest-point sampling of a ragged batch, one workgroup per cloud; form 0 auto, 1 resident, 2 streaming (scratch: fps_scratch_bytes)
+int64_t fps_scratch_bytes(int B, int64_t max_per_sample, int form);
+int fps_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t max_per_sample, int k,
+               const int64_t* start, const float* scale3_host, int64_t* out_idx, float* out_dist2, void* scratch, int64_t scratch_bytes, int form,
+               hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

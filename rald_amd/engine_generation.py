@@ -151,22 +151,40 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 @torch.no_grad()
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
-                              normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05):
+                              normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
     element follows: the device dict of postprocess.cloud_metrics_ragged (None where no metric is computed), whose 'cd' is the third.
-    With `normals` or `surface_steps` (see infer_point_clouds) the unit normals [T_cap,3] follow as the last element."""
-    pts, off, cd, _, metrics, nrm = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
-                                                    normals, surface_steps, surface_max_step)
+    With `normals` or `surface_steps` (see infer_point_clouds) the unit normals [T_cap,3] follow.  With `resample=k` (see
+    infer_point_clouds) the last two elements are the resampled clouds [B,k,3] and their row indices [B,k]."""
+    resample = _check_resample(resample)
+    pts, off, cd, _, metrics, nrm, longest = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
+                                                             normals, surface_steps, surface_max_step)
     out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
-    return out + (nrm,) if nrm is not None else out
+    if nrm is not None:
+        out = out + (nrm,)
+    return out + _resample(pts, off, resample, longest) if resample is not None else out
+
+
+def _check_resample(resample) -> Optional[int]:
+    if resample is None:
+        return None
+    if isinstance(resample, bool) or int(resample) != resample or resample < 1:
+        raise ValueError("resample must be None or a positive integer")
+    return int(resample)
+
+
+def _resample(pts: torch.Tensor, off: torch.Tensor, k: int, longest: int):
+    """The final clouds as k evenly spread points each -> (resampled [B,k,3], index [B,k]); after the metric, which keeps the full cloud."""
+    return PP.resample_points_ragged(pts, off, k, max(1, min(int(longest), PP.FPS_MAX_POINTS)), return_index=True)
 
 
 def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None, normals=False, surface_steps=0,
                     surface_max_step=0.05):
     """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None, normals or None) on the device: what
-    infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest."""
+    infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest; the
+    last element is the host bound of the longest final cloud."""
     oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
@@ -232,7 +250,7 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         else:
             metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
             cd = metrics["cd"]
-    return pts, p_off, cd, n_queries, metrics, nrm
+    return pts, p_off, cd, n_queries, metrics, nrm, longest
 
 
 def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
@@ -255,7 +273,7 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 @torch.no_grad()
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
-                       surface_steps: int = 0, surface_max_step: float = 0.05) -> Dict[str, object]:
+                       surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -280,10 +298,21 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     gradient (KLAutoEncoder.decode_ragged_with_gradient); 'pred' then holds those points and a new 'normals' list one unit vector per
     point [n_b,3] (occupied -> empty; zero where undefined), both from postprocess.oriented_points_ragged, and the metric is computed
     on those points.  No host read is added.
+    `resample` (None: today's dict; or k >= 1): every final cloud additionally as exactly k evenly spread points - 'resampled' [B,k,3]
+    (metric coordinates, on the device) and 'resample_index' int64 [B,k] (rows of the frame's 'pred'; -1 in padded slots), from
+    postprocess.resample_points_ragged (farthest-point sampling from row 0) after the metric, which stays on the full
+    cloud.  A frame with fewer than k points repeats its points in order, an empty one gives NaN rows.  The sampler takes clouds of
+    up to 65536 points: a frame LONGER than that is sampled from its first 65536 rows only (the rows are in query order, so that is a
+    spatial bias) - a caller who expects such frames thins first, with fewer query points / a smaller refine_query_aug_num, or by
+    resampling slices of 'pred' and then their union.  No host read is added.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
-    'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps)."""
-    pts, off, cd, nq, metrics, nrm = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
-                                                     normals, surface_steps, surface_max_step)
+    'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps, + 'resampled' and
+    'resample_index' with resample)."""
+    resample = _check_resample(resample)
+    pts, off, cd, nq, metrics, nrm, longest = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
+                                                              metric_thresholds, normals, surface_steps, surface_max_step)
+    if resample is not None:
+        resampled, resample_index = _resample(pts, off, resample, longest)
     B = sampled_tokens.shape[0]
     extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
     packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra)
@@ -296,6 +325,8 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         out["metrics"] = PP._metrics_to_host(host[3 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
     if nrm is not None:
         out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
+    if resample is not None:
+        out["resampled"], out["resample_index"] = resampled, resample_index
     return out
 
 

@@ -120,6 +120,22 @@ def lidar_config_struct(cfg) -> LidarConfig:
     return c
 
 
+def fps_scale(cfg):
+    """Per-axis factors that make farthest-point distances those of the normalised coordinates the encoder sees: 1 / half extent per
+    axis with norm_anisotropy, 1 / the largest half extent with norm_isotropy (both: their product), None when neither is on.
+    float64 arithmetic, rounded to float32 once."""
+    pc = np.array(cfg.pc_range, dtype=np.float64)
+    half = (pc[3:6] - pc[0:3]) / 2
+    s = np.ones(3, dtype=np.float64)
+    if cfg.get("norm_anisotropy", False):
+        s = s / half
+    if cfg.get("norm_isotropy", False):
+        s = s / half.max()
+    if not (cfg.get("norm_anisotropy", False) or cfg.get("norm_isotropy", False)):
+        return None
+    return [float(v) for v in s.astype(np.float32)]
+
+
 def grid_size(cfg) -> np.ndarray:
     """round((hi - lo) / voxel_size) in float64, as the dataset computes it (Coloradar_dataset.py:57-58); create checks the sizes."""
     pc = np.array(cfg.pc_range, dtype=np.float64)
@@ -293,13 +309,21 @@ class LidarFrames(_Handle):
         return lp, qp, lab
 
     def batch(self, scans: Sequence, loader_type: str = "train", load_query: bool = True,
-              rng: Union[None, np.random.Generator, torch.Generator] = None, crop: bool = False, polar: bool = False) -> dict:
+              rng: Union[None, np.random.Generator, torch.Generator] = None, crop: bool = False, polar: bool = False,
+              point_sampling: str = "random") -> dict:
         """ColoRadarDataset.__getitem__'s LiDAR part for a batch, collated.  `scans`: cartesian float32 [N_b, 3] (the lidar_sc files),
         or raw [N_b, 4] scans with crop=True (lidar.py's crop first); polar=True: float32 polar rows that are used as they are (the
         view-cone conversion skipped).  Returns (device tensors) lidar_points [B, S, 3] and, with load_query, query_points,
         raw_query_points (the same tensor: the reference normalises its alias in place), query_labels [B, S], in_voxel_num [B]
-        int64; for loaders other than 'train' also raw_lidar_points, the cartesian scans (a list: their lengths differ)."""
+        int64; for loaders other than 'train' also raw_lidar_points, the cartesian scans (a list: their lengths differ).
+        point_sampling: 'random' (the reference's permutation draw, and the default: the same draws bit for bit) or 'fps': the S
+        encoder points of a frame are its farthest-point sample (postprocess.farthest_point_sample_ragged over the rows the queries
+        sample from, distances scaled as the point normalisation scales them: fps_scale), started at one index drawn from `rng` in
+        place of the permutation; every other draw is unchanged.  'fps' takes frames of up to 65536 points."""
         cfg = self.config
+        if point_sampling not in ("random", "fps"):
+            raise ValueError("point_sampling must be 'random' or 'fps'")
+        fps = point_sampling == "fps"
         if loader_type not in ("train", "val", "test"):
             raise AssertionError(f"Invalid loader type {loader_type}")
         if cfg.get("shuffle_pts", False) or cfg.get("DOUBLE_FLIP", False):
@@ -336,7 +360,8 @@ class LidarFrames(_Handle):
             if isinstance(rng, torch.Generator):
                 if N < S:
                     raise ValueError(f"Error sampling points from {N} points")
-                sidx.append(torch.randperm(N, generator=rng, device=dev)[:S])
+                sidx.append(torch.randint(0, N, (1,), generator=rng, device=dev)[0] if fps else
+                            torch.randperm(N, generator=rng, device=dev)[:S])
                 if load_query:
                     if V == 0:
                         raise ValueError("a cannot be empty unless no samples are taken")
@@ -348,10 +373,15 @@ class LidarFrames(_Handle):
                                  torch.zeros(0, dtype=torch.int64, device=dev))
                 continue
             g = (lambda: rng) if isinstance(rng, np.random.Generator) else np.random.default_rng
-            try:
-                sidx.append(g().choice(N, S, replace=False))
-            except ValueError:
-                raise ValueError(f"Error sampling points from {N} points")
+            if fps:
+                if N < S:
+                    raise ValueError(f"Error sampling points from {N} points")
+                sidx.append(int(g().integers(0, N)))
+            else:
+                try:
+                    sidx.append(g().choice(N, S, replace=False))
+                except ValueError:
+                    raise ValueError(f"Error sampling points from {N} points")
             if not load_query:
                 continue
             if train:
@@ -364,6 +394,13 @@ class LidarFrames(_Handle):
                 vidx.append(g().choice(V, S, replace=True))
         up = lambda xs, dt: (torch.stack([torch.as_tensor(v) for v in xs]).to(device=dev, dtype=dt).contiguous() if xs else None)
         sample_idx = up(sidx, torch.int64)
+        if fps:                                 # sidx: one start per frame; the S rows come from the sampler, on the device
+            from . import postprocess as PP
+            longest = int(n_host.max())
+            if longest > PP.FPS_MAX_POINTS:
+                raise ValueError(f"point_sampling='fps' takes frames of up to {PP.FPS_MAX_POINTS} points, got {longest}")
+            sample_idx = PP.farthest_point_sample_ragged(src, torch.from_numpy(offs).to(dev), S, longest, counts=counts, start=sample_idx,
+                                                         scale=fps_scale(cfg))
         if load_query:
             u_in, voxel_idx = up(uin, torch.float64), up(vidx, torch.int64)
             u_out, empty_rank = (up(uout, torch.float64), up(erank, torch.int64)) if out_num else (None, None)

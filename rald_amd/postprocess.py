@@ -6,7 +6,9 @@
 ``np.where(output > 0)`` -> ``grid[ind]`` -> ``inverse_norm_points`` -> ``polar2cartesian``.
 
 Beyond the reference's one metric: ``nearest_neighbors*`` and ``cloud_metrics*`` (exact nearest neighbours per point, and accuracy,
-completeness, both Chamfer variants, (modified) Hausdorff distance and precision / recall / F-score per frame).
+completeness, both Chamfer variants, (modified) Hausdorff distance and precision / recall / F-score per frame),
+and ``farthest_point_sample*`` / ``resample_points_ragged`` (k evenly spread points per cloud, the device counterpart of
+``torch_cluster.fps``).
 """
 from __future__ import annotations
 
@@ -314,3 +316,109 @@ def accuracy_iou(outputs: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Ten
     iou = torch.empty(B, device=outputs.device, dtype=torch.float32)
     check(lib().rald_post_iou(outputs.data_ptr(), labels.data_ptr(), B, Q, acc.data_ptr(), iou.data_ptr(), _stream()))
     return acc, iou
+
+
+FPS_MAX_POINTS = 65536                                   # the largest max_per_sample of rald_post_fps_ragged
+FPS_FORMS = {None: 0, "auto": 0, "resident": 1, "streaming": 2}
+
+
+def _fps_args(points, dim: int, k, max_per_sample, counts, start, scale, B: Optional[int], form):
+    """The shape, dtype and range rules of the farthest-point calls (ValueError, before anything asks where a tensor lives)
+    -> (k, max_per_sample, scale as 3 floats or None, form code)."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == dim and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor " + ("[B, N, 3]" if dim == 3 else "[T, 3]"))
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError("k must be a positive integer")
+    if isinstance(max_per_sample, bool) or int(max_per_sample) != max_per_sample or not 1 <= max_per_sample <= FPS_MAX_POINTS:
+        raise ValueError(f"max_per_sample must be an integer in 1 .. {FPS_MAX_POINTS}")
+    if B is not None:
+        if counts is not None and not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int32 and tuple(counts.shape) == (B,)):
+            raise ValueError(f"counts must be an int32 tensor [{B}] (LidarFrames.crop's)")
+        if start is not None and not (isinstance(start, torch.Tensor) and start.dtype == torch.int64 and tuple(start.shape) == (B,)):
+            raise ValueError(f"start must be an int64 tensor [{B}]")
+    if scale is not None:
+        scale = [float(v) for v in scale]
+        if len(scale) != 3 or any(not math.isfinite(v) for v in scale):
+            raise ValueError("scale must be 3 finite numbers")
+    if form not in FPS_FORMS:
+        raise ValueError("form must be None, 'auto', 'resident' or 'streaming'")
+    return int(k), int(max_per_sample), scale, FPS_FORMS[form]
+
+
+def _fps_call(points, offsets, counts, B, n_dense, max_per_sample, k, start, scale, return_dist, form):
+    import ctypes as C
+    dev = points.device
+    idx = torch.empty(B, k, device=dev, dtype=torch.int64)
+    dist = torch.empty(B, k, device=dev, dtype=torch.float32) if return_dist else None
+    nbytes = _nbytes(lib().rald_post_fps_scratch_bytes(B, max_per_sample, form))
+    scratch = _scratch(nbytes, dev)
+    scale3 = (C.c_float * 3)(*scale) if scale is not None else None
+    check(lib().rald_post_fps_ragged(points.data_ptr(), _opt(offsets), _opt(counts), B, n_dense, max_per_sample, k, _opt(start), scale3,
+                                     idx.data_ptr(), _opt(dist), scratch.data_ptr(), nbytes, form, _stream()))
+    return (idx, dist) if return_dist else idx
+
+
+def farthest_point_sample_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, max_per_sample: int, counts: Optional[torch.Tensor] = None,
+                                 start: Optional[torch.Tensor] = None, scale: Optional[Sequence[float]] = None, return_dist: bool = False,
+                                 form: Optional[str] = None):
+    """Farthest-point sampling per cloud of a ragged batch (rald_post_fps_ragged): points [T,3], offsets int64
+    [B+1] on the device -> idx int64 [B,k] (row indices from the cloud's own first row) and, with return_dist, dist2 float32 [B,k]
+    (+inf first, then the squared distance of every choice to the set chosen before it), both on the device.
+    The first choice is start[b] mod n (start: int64 [B] on the device; None = row 0), every further one the row with the largest
+    squared distance to the rows chosen so far, the SMALLEST index on equal distances; distances are fp32 on points * scale (3 numbers
+    per axis, None = 1), every operation rounded, so the result is the same bits in every call and batch.  counts (int32 [B] on the
+    device, LidarFrames.crop's): only the first counts[b] rows of a cloud are valid.  max_per_sample: host bound of the longest cloud,
+    at most 65536 - it is trusted, a cloud LONGER than it is sampled from its first max_per_sample rows.  A cloud with n < k rows gets
+    its n choices, then idx -1 and dist2 NaN; with fewer than k distinct points the smallest index repeats at distance 0.  Coordinates
+    must be finite.  form (tests): 'resident' / 'streaming' force the kernel form, the result does not depend on it.
+    No host read, no synchronisation; runs on the current stream."""
+    k, max_per_sample, scale, form = _fps_args(points, 2, k, max_per_sample, counts, start, scale, _offsets_shape(offsets, "offsets"), form)
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    for t, what in ((counts, "counts"), (start, "start")):
+        if t is not None:
+            _need_cuda(t, what)
+    points = _f32c(points)
+    return _fps_call(points, offsets, None if counts is None else counts.contiguous(), B, 0, max_per_sample, k,
+                     None if start is None else start.contiguous(), scale, return_dist, form)
+
+
+def farthest_point_sample(points: torch.Tensor, k: int, start: Optional[torch.Tensor] = None, scale: Optional[Sequence[float]] = None,
+                          return_dist: bool = False, form: Optional[str] = None):
+    """farthest_point_sample_ragged for dense clouds: points [B,N,3] (1 <= N <= 65536) -> idx int64 [B,k] (and dist2 float32 [B,k])."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 3):
+        raise ValueError("points must be a floating-point tensor [B, N, 3]")
+    B, N = points.shape[0], points.shape[1]
+    if B < 1 or N < 1:
+        raise ValueError("points must hold at least one cloud of at least one point")
+    k, N, scale, form = _fps_args(points, 3, k, N, None, start, scale, B, form)
+    _need_cuda(points, "points")
+    if start is not None:
+        _need_cuda(start, "start")
+    return _fps_call(_f32c(points), None, None, B, N, N, k, None if start is None else start.contiguous(), scale, return_dist, form)
+
+
+def resample_points_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, max_per_sample: int, counts: Optional[torch.Tensor] = None,
+                           start: Optional[torch.Tensor] = None, scale: Optional[Sequence[float]] = None, pad: str = "repeat",
+                           return_index: bool = False):
+    """Every cloud of a ragged batch as exactly k evenly spread points: -> [B,k,3] float32 = the rows farthest_point_sample_ragged
+    chooses (same arguments), in the order chosen.  pad='repeat': a cloud with 0 < n < k rows fills slot j >= n with the point of slot
+    j mod n; pad='nan': those slots are NaN.  An empty cloud gives NaN rows.  return_index adds idx [B,k] (-1 in the padded slots).
+    The gather and the padding are torch indexing on the device; no host read."""
+    if pad not in ("repeat", "nan"):
+        raise ValueError("pad must be 'repeat' or 'nan'")
+    idx = farthest_point_sample_ragged(points, offsets, k, max_per_sample, counts=counts, start=start, scale=scale)
+    B, k = idx.shape
+    pts = _f32c(points)
+    slot = torch.arange(k, dtype=torch.int64, device=idx.device).expand(B, k)
+    if pad == "repeat":
+        n_sel = (idx >= 0).sum(dim=1, keepdim=True)                              # min(n, k) per cloud
+        slot = slot % n_sel.clamp(min=1)
+    src = torch.gather(idx, 1, slot)                                             # -1 where nothing can fill the slot
+    rows = (offsets[:-1, None] + src).clamp_(0, max(pts.shape[0] - 1, 0))
+    if pts.shape[0]:
+        out = pts[rows]
+    else:
+        out = torch.zeros(B, k, 3, device=idx.device, dtype=torch.float32)
+    out = torch.where((src >= 0)[:, :, None], out, torch.full_like(out, float("nan")))
+    return (out, idx) if return_index else out
