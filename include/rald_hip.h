@@ -337,6 +337,45 @@ int64_t rald_post_fps_scratch_bytes(int32_t batch, int64_t max_per_sample, int32
 int rald_post_fps_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
                          int64_t max_per_sample, int32_t k, const int64_t* start, const float* scale3_host, int64_t* out_idx, float* out_dist2,
                          void* scratch, int64_t scratch_bytes, int32_t form, void* stream);
+/* ---- voxel-grid down-sampling: every cloud of a ragged batch becomes one point per occupied cell of a fixed
+ * grid.  Defined to the bit, so the result is the same in every call, in every batch and for every chunk length:
+ *   grid (HOST values): lo3_host 3 floats (finite), v3_host 3 floats (the cell edge per axis, finite and > 0), dims3_host 3 int32
+ *   (>= 1), cells = dims0 * dims1 * dims2 <= 2^31 - 1.
+ *   cell of a row, per axis: c = floorf(fl(fl(p - lo) / v)): fp32, round to nearest, no contraction, the division correctly rounded.
+ *   The row is inside iff 0 <= c < (float)dims on all three axes, compared in float before any conversion (NaN, +-inf: outside).
+ *   key = (c0 * dims1 + c1) * dims2 + c2.  Rows outside are dropped: counted nowhere, out_inverse -1.
+ *   voxels of a cloud: the distinct keys of its inside rows in ASCENDING KEY order (a canonical order, independent of the row order).
+ *   out_points fp32 [n_total,3]: the centroid - per coordinate the voxel's rows added in float64 in ascending row order, left to
+ *   right, divided by (double)n, rounded to fp32 once.  out_offsets DEVICE int64 [batch+1]: cloud b's voxels are rows
+ *   out_offsets[b] .. out_offsets[b+1]-1, the clouds packed one behind the other; rows from out_offsets[batch] on are not written.
+ *   Optional (NULL = not wanted), one per voxel: out_count int32 (rows in the voxel), out_first int64 (its smallest row index, from the
+ *   cloud's first row), out_cells int32 [n_total,3] (c0, c1, c2).  Optional per row, laid out like points: out_inverse int64 [n_total],
+ *   the rank of the row's voxel inside its cloud, -1 for a dropped row.
+ * Layout: points [n_total,3]; offsets DEVICE int64 [batch+1], or NULL for dense clouds of n_dense rows each; counts DEVICE int32
+ * [batch] or NULL: the valid rows from the cloud's first row, capped at the segment; rows behind counts[b] are neither read nor written.
+ * max_per_sample: HOST bound of the longest cloud, 1 .. 16777216; it is trusted and sizes grids and scratch: a cloud LONGER than the
+ * bound is reduced from its FIRST max_per_sample rows, silently (the rows behind get no out_inverse).  A cloud's span is clamped into
+ * [0, n_total] on the device: no access leaves points, the outputs or the scratch whatever offsets and bound hold.  batch 1 .. 65535,
+ * n_total 0 .. 2^31 - 1.
+ * Separate launches, none waits on another workgroup; no float atomics.  The sort is a stable LSD radix sort of (key, row), 8 bits
+ * per pass, rald_op_voxel_passes(cells) = ceil(bits(cells) / 8) passes; a cloud bound above one chunk is sorted by one workgroup per
+ * chunk, one that fits a chunk by one workgroup per cloud.  One lane adds a voxel's rows: the time of a cloud with ALL rows in one
+ * cell grows with its length.
+ * scratch: rald_post_voxel_scratch_bytes of the same batch, n_total and bound, 16-byte aligned, never NULL; -1 (and rald_last_error)
+ * for sizes the call refuses.  Every invalid argument is refused with a status before any GPU work.
+ * rald_op_*: test-facing, with the chunk length of the split sort: 0 = automatic (what rald_post_* uses), else a multiple of 1024; a
+ * chunk >= max_per_sample forces the one-workgroup sort.  The result does not depend on it. */
+int64_t rald_post_voxel_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample);
+int rald_post_voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                      int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                      const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
+                                      int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t rald_op_voxel_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int32_t rald_op_voxel_passes(int64_t cells);
+int rald_op_voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                    const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
+                                    int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

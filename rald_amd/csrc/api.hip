@@ -414,6 +414,39 @@ int rald_post_fps_ragged(const float* points, const int64_t* offsets, const int3
                       form, (hipStream_t)stream);
 }
 
+// ---- voxel-grid down-sampling ------------------------------------------------------
+static const char* const kVoxelSizes =
+    ": batch 1 .. 65535, n_total 0 .. 2^31 - 1, max_per_sample 1 .. 16777216, chunk 0 or a multiple of 1024";
+int64_t rald_post_voxel_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample) {
+    const int64_t n = voxel_scratch_bytes(batch, n_total, max_per_sample, 0);
+    if (n < 0) set_error(std::string("rald_post_voxel_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int rald_post_voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                      int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                      const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
+                                      int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, void* stream) {
+    return voxel_downsample_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, out_points,
+                                   out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, 0, (hipStream_t)stream);
+}
+int64_t rald_op_voxel_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t n = voxel_scratch_bytes(batch, n_total, max_per_sample, chunk);
+    if (n < 0) set_error(std::string("rald_op_voxel_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int32_t rald_op_voxel_passes(int64_t cells) {
+    const int p = voxel_passes(cells);
+    if (p < 0) set_error("rald_op_voxel_passes: cells must be 1 .. 2^31 - 1");
+    return p;
+}
+int rald_op_voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                    const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
+                                    int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return voxel_downsample_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, out_points,
+                                   out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

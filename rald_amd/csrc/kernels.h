@@ -348,6 +348,15 @@ int fps_ragged(const float* points, const int64_t* offsets, const int32_t* count
                const int64_t* start, const float* scale3_host, int64_t* out_idx, float* out_dist2, void* scratch, int64_t scratch_bytes, int form,
                hipStream_t st);
 
+// ---------------------------------------------------------------- voxel_reduce.hip
+// voxel-grid down-sampling of a ragged batch: one centroid per occupied cell, ascending key; chunk 0 = automatic, else a multiple of 1024
+int voxel_passes(int64_t cells);                   // radix passes of 8 bits for keys 0 .. cells; -1 outside 1 .. 2^31 - 1
+int64_t voxel_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                            int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float* out_points,
+                            int64_t* out_offsets, int32_t* out_count, int64_t* out_first, int32_t* out_cells, int64_t* out_inverse,
+                            void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

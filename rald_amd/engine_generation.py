@@ -151,19 +151,28 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 @torch.no_grad()
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
-                              normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None):
+                              normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
+                              thin=None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
     element follows: the device dict of postprocess.cloud_metrics_ragged (None where no metric is computed), whose 'cd' is the third.
     With `normals` or `surface_steps` (see infer_point_clouds) the unit normals [T_cap,3] follow.  With `resample=k` (see
-    infer_point_clouds) the last two elements are the resampled clouds [B,k,3] and their row indices [B,k]."""
+    infer_point_clouds) the last two elements are the resampled clouds [B,k,3] and their row indices [B,k].  With `thin` (see
+    infer_point_clouds) four elements come before those two: (thinned [T_cap,3], thin_offsets int64 [B+1], thin_count int32 [T_cap],
+    thin_first int64 [T_cap]) - frame b's voxels are rows thin_offsets[b] .. thin_offsets[b+1]-1 - and the resample indices count rows
+    of the frame's thinned cloud."""
     resample = _check_resample(resample)
+    grid = _thin_grid(thin, args)
     pts, off, cd, _, metrics, nrm, longest = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
                                                              normals, surface_steps, surface_max_step)
     out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
     if nrm is not None:
         out = out + (nrm,)
+    if grid is not None:
+        thinned = _thin(pts, off, grid, longest)
+        out = out + thinned
+        pts, off, longest = thinned[0], thinned[1], _thin_bound(longest, grid)
     return out + _resample(pts, off, resample, longest) if resample is not None else out
 
 
@@ -173,6 +182,30 @@ def _check_resample(resample) -> Optional[int]:
     if isinstance(resample, bool) or int(resample) != resample or resample < 1:
         raise ValueError("resample must be None or a positive integer")
     return int(resample)
+
+
+def _thin_grid(thin, args):
+    """The grid of `thin` (None, or the cell edge: a number or 3) in the final clouds' coordinates -> None or postprocess.voxel_grid's
+    triple: the cube [-r_max, r_max]^3 (r_max = pc_range[3]) in view-cone mode, where the clouds are cartesian, else pc_range itself.
+    ValueError for a bad edge or too many cells, on the host."""
+    if thin is None:
+        return None
+    lidar = args.dataset.lidar
+    rng = [float(v) for v in lidar.pc_range]
+    if bool(_get(lidar, "view_cone_mode", False)):
+        return PP.voxel_grid([-rng[3]] * 3, [rng[3]] * 3, thin)
+    return PP.voxel_grid(rng[:3], rng[3:], thin)
+
+
+def _thin(pts: torch.Tensor, off: torch.Tensor, grid, longest: int):
+    """The final clouds, one centroid per occupied cell -> (thinned [T,3], thin_offsets [B+1], thin_count [T], thin_first [T]); after
+    the metric, which keeps the full cloud."""
+    return PP.voxel_downsample_ragged(pts, off, grid, max(1, int(longest)), return_count=True, return_first=True)
+
+
+def _thin_bound(longest: int, grid) -> int:
+    """Host bound of the longest thinned cloud: no more voxels than rows, nor than cells."""
+    return min(int(longest), grid[2][0] * grid[2][1] * grid[2][2])
 
 
 def _resample(pts: torch.Tensor, off: torch.Tensor, k: int, longest: int):
@@ -273,7 +306,8 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 @torch.no_grad()
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
-                       surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None) -> Dict[str, object]:
+                       surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
+                       thin=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -303,19 +337,32 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     postprocess.resample_points_ragged (farthest-point sampling from row 0) after the metric, which stays on the full
     cloud.  A frame with fewer than k points repeats its points in order, an empty one gives NaN rows.  The sampler takes clouds of
     up to 65536 points: a frame LONGER than that is sampled from its first 65536 rows only (the rows are in query order, so that is a
-    spatial bias) - a caller who expects such frames thins first, with fewer query points / a smaller refine_query_aug_num, or by
-    resampling slices of 'pred' and then their union.  No host read is added.
+    spatial bias) - a caller who expects such frames thins first, with `thin`.  No host read is added.
+    `thin` (None: today's calls, dict and host read; or the cell edge in the final clouds' coordinates, a number or 3): every final
+    cloud additionally with one point per occupied cell of a fixed grid - the cube [-r_max, r_max]^3, r_max = pc_range[3], in
+    view_cone_mode, else pc_range - from postprocess.voxel_downsample_ragged after the metric, which stays on the
+    full cloud: 'thinned' a list of B tensors [m_b,3] (the cells' centroids in ascending cell-key order), 'thin_count' a list of int32
+    [m_b] (rows per cell), 'thin_first' a list of int64 [m_b] (the cell's first row of the frame's 'pred'), and with normals /
+    surface_steps 'thinned_normals' [m_b,3], the normals of the thin_first rows.  Too many cells (more than 2^31 - 1) raise ValueError
+    before any GPU work.  The thinned offsets join the one host read.  With `resample` as well the sampler runs on the THINNED clouds
+    and 'resample_index' counts rows of 'thinned'; a thinned cloud above 65536 voxels is still truncated to its first 65536 - now in
+    cell-key order, a slab of the grid - so a coarser cell is the remedy.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
     'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps, + 'resampled' and
-    'resample_index' with resample)."""
+    'resample_index' with resample, + 'thinned', 'thin_count', 'thin_first' (and 'thinned_normals') with thin)."""
     resample = _check_resample(resample)
+    grid = _thin_grid(thin, args)
     pts, off, cd, nq, metrics, nrm, longest = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
                                                               metric_thresholds, normals, surface_steps, surface_max_step)
-    if resample is not None:
-        resampled, resample_index = _resample(pts, off, resample, longest)
     B = sampled_tokens.shape[0]
+    s_pts, s_off, s_longest = pts, off, longest
+    if grid is not None:
+        t_pts, t_off, t_count, t_first = _thin(pts, off, grid, longest)
+        s_pts, s_off, s_longest = t_pts, t_off, _thin_bound(longest, grid)
+    if resample is not None:
+        resampled, resample_index = _resample(s_pts, s_off, resample, s_longest)
     extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
-    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra)
+    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + ([t_off.double()] if grid is not None else []))
     host = packed.cpu().tolist()                                                                    # the one host read
     o = [int(v) for v in host[:B + 1]]
     out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
@@ -325,6 +372,12 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         out["metrics"] = PP._metrics_to_host(host[3 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
     if nrm is not None:
         out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
+    if grid is not None:
+        to = [int(v) for v in host[len(host) - (B + 1):]]
+        for key, t in (("thinned", t_pts), ("thin_count", t_count), ("thin_first", t_first)):
+            out[key] = [t[to[b]:to[b + 1]] for b in range(B)]
+        if nrm is not None:
+            out["thinned_normals"] = [nrm[o[b] + out["thin_first"][b]] for b in range(B)]
     if resample is not None:
         out["resampled"], out["resample_index"] = resampled, resample_index
     return out

@@ -7,8 +7,9 @@
 
 Beyond the reference's one metric: ``nearest_neighbors*`` and ``cloud_metrics*`` (exact nearest neighbours per point, and accuracy,
 completeness, both Chamfer variants, (modified) Hausdorff distance and precision / recall / F-score per frame),
-and ``farthest_point_sample*`` / ``resample_points_ragged`` (k evenly spread points per cloud, the device counterpart of
-``torch_cluster.fps``).
+``farthest_point_sample*`` / ``resample_points_ragged`` (k evenly spread points per cloud, the device counterpart of
+``torch_cluster.fps``), and ``voxel_grid`` / ``voxel_downsample*`` (one centroid per occupied cell of a fixed
+grid, the device counterpart of Open3D's ``voxel_down_sample``).
 """
 from __future__ import annotations
 
@@ -422,3 +423,140 @@ def resample_points_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, 
         out = torch.zeros(B, k, 3, device=idx.device, dtype=torch.float32)
     out = torch.where((src >= 0)[:, :, None], out, torch.full_like(out, float("nan")))
     return (out, idx) if return_index else out
+
+
+VOXEL_MAX_POINTS = 1 << 24                               # the largest max_per_sample of rald_post_voxel_downsample_ragged
+VOXEL_MAX_CELLS = (1 << 31) - 1
+
+
+def _f32(v: float) -> float:
+    import struct
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def voxel_grid(lo: Sequence[float], hi: Sequence[float], voxel) -> Tuple[Tuple[float, ...], Tuple[float, ...], Tuple[int, ...]]:
+    """The fixed grid of the voxel calls -> (lo3, v3, dims3): `voxel` is the cell edge, one number or one per axis; per axis
+    dims = floor((hi - lo) / v) + 1 (in double, on the numbers given), so that hi itself lies in the last cell; lo3 and v3 are lo and
+    voxel rounded to float32, what the kernels compute with.  ValueError for non-finite bounds, hi < lo, a non-positive or non-finite
+    edge (also one that rounds to 0 or inf in float32), and for more than 2^31 - 1 cells."""
+    try:
+        lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+        v = [float(voxel)] * 3 if isinstance(voxel, (int, float)) and not isinstance(voxel, bool) else [float(x) for x in voxel]
+    except TypeError:
+        raise ValueError("lo, hi must be 3 numbers each, voxel a number or 3 numbers") from None
+    if len(lo) != 3 or len(hi) != 3 or len(v) != 3:
+        raise ValueError("lo, hi must be 3 numbers each, voxel a number or 3 numbers")
+    if any(not math.isfinite(x) for x in lo + hi) or any(h < l for l, h in zip(lo, hi)):
+        raise ValueError("lo and hi must be finite with lo <= hi")
+    if any(not math.isfinite(x) or x <= 0 for x in v):
+        raise ValueError("the cell edge must be finite and > 0")
+    try:
+        lo3, v3 = tuple(_f32(x) for x in lo), tuple(_f32(x) for x in v)
+    except OverflowError:
+        raise ValueError("lo and the cell edge must fit float32") from None
+    if any(x <= 0 or not math.isfinite(x) for x in v3) or any(not math.isfinite(x) for x in lo3):
+        raise ValueError("lo and the cell edge must fit float32")
+    dims = tuple(int(math.floor((h - l) / x)) + 1 for l, h, x in zip(lo, hi, v))
+    if dims[0] * dims[1] * dims[2] > VOXEL_MAX_CELLS:
+        raise ValueError(f"the grid has {dims[0] * dims[1] * dims[2]} cells, more than 2^31 - 1: use a coarser cell")
+    return lo3, v3, dims
+
+
+def _voxel_grid_arg(grid):
+    """(lo3, v3, dims3) of voxel_grid, checked again (a caller may build it by hand) -> three ctypes host arrays."""
+    import ctypes as C
+    try:
+        lo3, v3, dims3 = grid
+        lo3, v3 = [float(x) for x in lo3], [float(x) for x in v3]
+        ok = len(lo3) == 3 and len(v3) == 3 and len(dims3) == 3 and all(int(d) == d and not isinstance(d, bool) for d in dims3)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("grid must be (lo3, v3, dims3) as voxel_grid returns it")
+    dims3 = [int(d) for d in dims3]
+    if any(not math.isfinite(x) for x in lo3) or any(not math.isfinite(x) or x <= 0 for x in v3):
+        raise ValueError("grid: lo must be finite and every cell edge finite and > 0")
+    if any(d < 1 for d in dims3) or dims3[0] * dims3[1] * dims3[2] > VOXEL_MAX_CELLS:
+        raise ValueError("grid: every dim must be >= 1 and the grid at most 2^31 - 1 cells")
+    return (C.c_float * 3)(*lo3), (C.c_float * 3)(*v3), (C.c_int32 * 3)(*dims3)
+
+
+def _voxel_args(points, max_per_sample, counts, B: Optional[int], chunk):
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [T, 3]")
+    if isinstance(max_per_sample, bool) or int(max_per_sample) != max_per_sample or not 1 <= max_per_sample <= VOXEL_MAX_POINTS:
+        raise ValueError(f"max_per_sample must be an integer in 1 .. {VOXEL_MAX_POINTS}")
+    if B is not None and counts is not None and not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int32 and tuple(counts.shape) == (B,)):
+        raise ValueError(f"counts must be an int32 tensor [{B}] (LidarFrames.crop's)")
+    if isinstance(chunk, bool) or int(chunk) != chunk or chunk < 0 or chunk % 1024:
+        raise ValueError("chunk must be 0 (automatic) or a multiple of 1024")
+    return int(max_per_sample), int(chunk)
+
+
+def voxel_downsample_ragged(points: torch.Tensor, offsets: torch.Tensor, grid, max_per_sample: int, counts: Optional[torch.Tensor] = None,
+                            return_count: bool = False, return_first: bool = False, return_cells: bool = False, return_inverse: bool = False,
+                            chunk: int = 0):
+    """Voxel-grid down-sampling per cloud of a ragged batch (rald_post_voxel_downsample_ragged): points [T,3],
+    offsets int64 [B+1] on the device, grid = voxel_grid(lo, hi, voxel) -> (points [T,3], out_offsets int64 [B+1], ...), on the device
+    and sized for the worst case: cloud b's voxels are rows out_offsets[b] .. out_offsets[b+1]-1, one per occupied cell in ASCENDING
+    cell-key order ((c0 * dims1 + c1) * dims2 + c2 - a canonical order, independent of the order of the rows), each the centroid of
+    the cell's rows (added in float64 in row order, rounded to float32 once).  Rows past out_offsets[B] are unspecified.
+    A row's cell is floor((p - lo) / v) in float32; rows outside the grid (NaN and inf rows included) are dropped.
+    Then, in this order, for every flag set: count int32 [T] (rows per voxel), first int64 [T] (the voxel's smallest row index, from
+    the cloud's first row: gathers any attribute of a representative row), cells int32 [T,3], inverse int64 [T] (per ROW, laid out
+    like points: the rank of its voxel inside its cloud, -1 for a dropped row; rows past offsets[B] or behind counts / the bound are
+    unspecified).
+    counts (int32 [B] on the device): only the first counts[b] rows of a cloud are valid.  max_per_sample: host bound of the longest
+    cloud, at most 2^24 - it is trusted, a cloud LONGER than it is reduced from its first max_per_sample rows.  The result is the same
+    bits in every call and batch.  chunk (tests, tools): the chunk length of the split sort, 0 = automatic; the result does not depend
+    on it.  No host read, no synchronisation; runs on the current stream."""
+    max_per_sample, chunk = _voxel_args(points, max_per_sample, counts, _offsets_shape(offsets, "offsets"), chunk)
+    lo3, v3, dims3 = _voxel_grid_arg(grid)
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.contiguous()
+    points = _f32c(points)
+    T, dev = points.shape[0], points.device
+    out = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    cnt = torch.empty(T, device=dev, dtype=torch.int32) if return_count else None
+    first = torch.empty(T, device=dev, dtype=torch.int64) if return_first else None
+    cells = torch.empty(T, 3, device=dev, dtype=torch.int32) if return_cells else None
+    inverse = torch.empty(T, device=dev, dtype=torch.int64) if return_inverse else None
+    L = lib()
+    nbytes = _nbytes(L.rald_op_voxel_scratch_bytes(B, T, max_per_sample, chunk) if chunk else L.rald_post_voxel_scratch_bytes(B, T, max_per_sample))
+    scratch = _scratch(nbytes, dev)
+    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, out.data_ptr(), out_offsets.data_ptr(),
+            _opt(cnt), _opt(first), _opt(cells), _opt(inverse), scratch.data_ptr(), nbytes)
+    check(L.rald_op_voxel_downsample_ragged(*head, chunk, _stream()) if chunk else L.rald_post_voxel_downsample_ragged(*head, _stream()))
+    return (out, out_offsets) + tuple(t for t in (cnt, first, cells, inverse) if t is not None)
+
+
+def voxel_downsample(points: torch.Tensor, voxel, lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """One cloud [N,3] -> [m,3], one centroid per occupied cell of edge `voxel` (a number or 3), in ascending cell-key order: the device
+    counterpart of Open3D's voxel_down_sample on the grid voxel_grid(lo, hi, voxel).  Without lo / hi the grid spans the cloud's own
+    minimum and maximum - that costs one host read of six numbers (and the cloud must be finite); the result's length is a second
+    host read in either case."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [N, 3]")
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi come together")
+    if lo is not None:
+        grid = voxel_grid(lo, hi, voxel)
+    else:
+        voxel_grid((0, 0, 0), (0, 0, 0), voxel)                                       # the edge's own rules, before anything is read
+    N = points.shape[0]
+    if N == 0:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _need_cuda(points, "points")
+    points = _f32c(points)
+    if lo is None:
+        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
+        grid = voxel_grid(ext[:3], ext[3:], voxel)
+    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    out, off = voxel_downsample_ragged(points, offsets, grid, N)
+    return out[:int(off[1].item())]
