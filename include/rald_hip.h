@@ -376,6 +376,57 @@ int rald_op_voxel_downsample_ragged(const float* points, const int64_t* offsets,
                                     int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                     const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
                                     int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
+/* ---- fixed-radius neighbours inside a cloud and the radius outlier filter.  Defined to the bit, so the result
+ * is the same in every call, in every batch, for every chunk length and for every cell edge the call accepts:
+ *   Layout and grid are those of rald_post_voxel_downsample_ragged: points fp32 [n_total,3]; offsets DEVICE int64 [batch+1], or NULL
+ *   for dense clouds of n_dense rows; counts DEVICE int32 [batch] or NULL; max_per_sample a trusted HOST bound, 1 .. 16777216 (a
+ *   LONGER cloud is treated as its FIRST max_per_sample rows, silently); a cloud's span is clamped into [0, n_total] on the device.
+ *   lo3_host, v3_host, dims3_host as there, cells <= 2^31 - 1.  A row is INSIDE iff 0 <= c < (float)dims on all three axes, with
+ *   c = floorf(fl(fl(p - lo) / v)) in fp32 without contraction.  Rows outside (NaN and +-inf included) take no part: they are
+ *   nobody's neighbour, their own count is -1, their nearest is -1 / +inf, and the filter drops them.
+ *   radius: a HOST float, finite and > 0, and v >= radius on every axis (else the call is refused); r2 = fl(radius * radius) in fp32.
+ *   d2(i, j) = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), dx = fl(p_j.x - p_i.x) ...: fp32, round to nearest, no contraction.
+ *   count[i] = the number of inside rows j != i of the same cloud with d2(i, j) <= r2.  j != i is by row index: a duplicate of row i
+ *   counts.  With max_count = m > 0 the value is min(count, m) (the search of a row stops there); max_count = 0: no cap.
+ *   Nearest other row (out_nn_idx, out_nn_dist2: each may be NULL; either one requires max_count = 0): out_nn_idx int64 = the j of the
+ *   smallest d2 among the counted rows, the SMALLEST row index on equal d2, counted from the cloud's first row, -1 when count = 0;
+ *   out_nn_dist2 fp32 = that d2, +inf when there is none.
+ *   The three per-row outputs are laid out like points (row offsets[b] + i); rows outside every cloud's span are not written.
+ *   Filter: row i is kept iff it is inside and count[i] >= min_neighbors (>= 1; 0 is refused).  Kept rows come out in their ORIGINAL
+ *   row order, the clouds packed one behind the other as rald_post_occupied_points_ragged packs them: out_points fp32 [n_total,3] (the
+ *   input row's bits), out_offsets DEVICE int64 [batch+1], optional out_index int64 [n_total] (the kept row's index from its cloud's
+ *   first row), optional out_count int32 per INPUT row (min(count, min_neighbors), -1 outside).  Rows from out_offsets[batch] on are
+ *   not written.
+ * Every output is a function of the cloud's own rows, radius, lo3 and dims3 alone: v3 beyond v >= radius, the chunk, the batch and the
+ * call do not show.  The grid is the index of the search, a stable radix sort of (cell key, row) - the one of the voxel call.  One
+ * lane per sorted position scans, per axis, the cells cell(nextafterf(fl(p - rs), -inf)) .. cell(nextafterf(fl(p + rs), +inf)),
+ * rs = fl(radius * (1 + 2^-20)), clamped to the grid, with the same cell function: fl(dx*dx) <= d2 <= r2 bounds the real offset per
+ * axis by radius * (1 + 2^-22), the nextafter makes the bound hold at any magnitude, and the cell function is monotone, so no row
+ * within r2 lies outside the scan; with v >= radius that is at most 4 cells per axis where a cell is wider than the coordinates' ulp.
+ * No atomics, no kernel waits on another workgroup.  Without a cap a row's time grows with the rows around it: a cloud with ALL n
+ * rows in one cell costs n * n distances; with a cap (the filter always has one) the walk stops at the cap.
+ * scratch: rald_post_radius_scratch_bytes of the same batch, n_total and bound (one size serves both calls), 16-byte aligned, never
+ * NULL; -1 (and rald_last_error) for sizes the calls refuse.  Every invalid argument is refused with a status before any GPU work.
+ * rald_op_*: test-facing, with the chunk length of the split sort: 0 = automatic (what rald_post_* uses), else a multiple of 1024; a
+ * chunk >= max_per_sample forces the one-workgroup sort.  The result does not depend on it. */
+int64_t rald_post_radius_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample);
+int rald_post_radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                  const int32_t* dims3_host, float radius, int32_t max_count, int32_t* out_count, int64_t* out_nn_idx,
+                                  float* out_nn_dist2, void* scratch, int64_t scratch_bytes, void* stream);
+int rald_post_radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                   int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                   const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
+                                   int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t rald_op_radius_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int rald_op_radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                const int32_t* dims3_host, float radius, int32_t max_count, int32_t* out_count, int64_t* out_nn_idx,
+                                float* out_nn_dist2, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
+int rald_op_radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                 int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                 const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
+                                 int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

@@ -447,6 +447,46 @@ int rald_op_voxel_downsample_ragged(const float* points, const int64_t* offsets,
                                    out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, chunk, (hipStream_t)stream);
 }
 
+// ---- fixed-radius neighbours and the radius outlier filter ------------------------------
+int64_t rald_post_radius_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample) {
+    const int64_t n = radius_scratch_bytes(batch, n_total, max_per_sample, 0);
+    if (n < 0) set_error(std::string("rald_post_radius_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int64_t rald_op_radius_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t n = radius_scratch_bytes(batch, n_total, max_per_sample, chunk);
+    if (n < 0) set_error(std::string("rald_op_radius_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int rald_post_radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                  const int32_t* dims3_host, float radius, int32_t max_count, int32_t* out_count, int64_t* out_nn_idx,
+                                  float* out_nn_dist2, void* scratch, int64_t scratch_bytes, void* stream) {
+    return radius_count_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius, max_count,
+                               out_count, out_nn_idx, out_nn_dist2, scratch, scratch_bytes, 0, (hipStream_t)stream);
+}
+int rald_op_radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                const int32_t* dims3_host, float radius, int32_t max_count, int32_t* out_count, int64_t* out_nn_idx,
+                                float* out_nn_dist2, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return radius_count_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius, max_count,
+                               out_count, out_nn_idx, out_nn_dist2, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+}
+int rald_post_radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                   int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                   const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
+                                   int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, void* stream) {
+    return radius_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius,
+                                min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, 0, (hipStream_t)stream);
+}
+int rald_op_radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                 int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                 const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
+                                 int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return radius_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius,
+                                min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

@@ -3,6 +3,7 @@
 //   cell   c = floorf(fl(fl(p - lo) / v)) per axis, fp32, no contraction, inside iff 0 <= c < dims in float (NaN fails both)
 //   key    (c0 * dims1 + c1) * dims2 + c2, `cells` for a row outside the grid (the largest key: outside rows sort behind every voxel)
 //   voxel  a run of equal keys < cells after a STABLE sort of (key, row): its rows stand in ascending row order
+// The key and sort phases (vox_keys and the two sort routes) are also the spatial index of radius_search.hip, behind voxel_sort_ragged.
 // Launches, all on one stream, none waits on another workgroup:
 //   vox_keys        (256-row block, cloud)   key and row index of every row; out_inverse = -1 for outside rows
 //   the sort, `passes` = ceil(bits(cells) / 8) LSD passes of 8 bits between the ping and the pong buffer:
@@ -58,22 +59,12 @@ struct VoxelArgs {
     float* out_points; int64_t* out_offsets; int32_t* out_count; int64_t* out_first; int32_t* out_cells; int64_t* out_inverse;
 };
 
-__device__ __forceinline__ unsigned long long vox_lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
-// the cloud's first row and its number of rows: the segment, capped by counts and by the host bound, clamped into [0, n_total]
+// the cloud's first row and its number of rows (kernels.h: the layout is shared with radius_search.hip)
 __device__ __forceinline__ int vox_span(const VoxelArgs& a, int b, int64_t& row0) {
-    int64_t len;
-    if (a.offsets) { row0 = a.offsets[b]; len = a.offsets[b + 1] - row0; }
-    else { row0 = (int64_t)b * a.n_dense; len = a.n_dense; }
-    if (a.counts) { const int64_t c = a.counts[b]; len = c < len ? c : len; }
-    len = len < a.max_per_sample ? len : a.max_per_sample;
-    if (row0 < 0 || row0 > a.n_total) { row0 = 0; len = 0; }
-    len = len < a.n_total - row0 ? len : a.n_total - row0;
-    return len > 0 ? (int)len : 0;                           // <= 2^24
+    return ragged_span(a.offsets, a.counts, a.n_dense, a.n_total, a.max_per_sample, b, row0);
 }
 
 __global__ __launch_bounds__(VOX_KT) void vox_keys(VoxelArgs a) {
-#pragma clang fp contract(off)
     const int b = blockIdx.y;
     int64_t row0;
     const int n = vox_span(a, b, row0);
@@ -85,7 +76,7 @@ __global__ __launch_bounds__(VOX_KT) void vox_keys(VoxelArgs a) {
     bool in = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float cf = floorf((p[k] - a.lo[k]) / a.v[k]);
+        const float cf = voxel_cell(p[k], a.lo[k], a.v[k]);
         in = in && cf >= 0.f && cf < (float)a.dims[k];       // NaN fails both
         c[k] = in ? (int)cf : 0;
     }
@@ -154,28 +145,6 @@ __global__ __launch_bounds__(VOX_CT) void vox_hist(VoxelArgs a, int pass) {
     for (int64_t j = c0 + tid; j < c1; j += VOX_CT) atomicAdd(&h[(ks[j] >> shift) & 255u], 1u);
     __syncthreads();
     a.hist[(int64_t)b * 256 * a.nch_max + (int64_t)tid * nch + chunk] = h[tid];
-}
-
-// exclusive prefix over the workgroup of one value per thread; *total the sum.  sh: NT / 64 ints
-template <int NT>
-__device__ __forceinline__ int vox_block_excl(int v, int* sh, int tid, int* total) {
-    const int lane = tid & 63, w = tid >> 6;
-    int incl = v;
-    for (int s = 1; s < 64; s <<= 1) {
-        const int t = __shfl_up(incl, s);
-        if (lane >= s) incl += t;
-    }
-    if (lane == 63) sh[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < NT / 64; ++i) {
-        const int x = sh[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
 }
 
 // thread d owns digit d: its nch chunk counts are contiguous, so the digit-major scan is a plain scan of 256 * nch values
@@ -420,43 +389,55 @@ int voxel_passes(int64_t cells) {
     return (bits + 7) / 8;
 }
 
-int64_t voxel_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+int64_t voxel_sort_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
     if (!vox_sizes_ok(B, n_total, max_per_sample, chunk)) return -1;
     // automatic: sized for the smallest chunk the rule picks, so the size grows with every argument whatever the rule chooses
     const int64_t ch = chunk > 0 ? chunk : VOX_MIN_AUTO_CHUNK;
-    const int64_t nch = (max_per_sample + ch - 1) / ch, nseg = (max_per_sample + VOX_SEG - 1) / VOX_SEG;
-    return 4 * vox_align16(n_total * 4) + vox_align16((int64_t)B * 256 * nch * 4) + vox_align16((int64_t)B * nseg * 4) + vox_align16((int64_t)B * 4);
+    const int64_t nch = (max_per_sample + ch - 1) / ch;
+    return 4 * vox_align16(n_total * 4) + vox_align16((int64_t)B * 256 * nch * 4);
 }
 
-int voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                            int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float* out_points,
-                            int64_t* out_offsets, int32_t* out_count, int64_t* out_first, int32_t* out_cells, int64_t* out_inverse,
-                            void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
-    RALD_CHECK(points && out_points && out_offsets, "voxel_downsample_ragged: null pointer (points, out_points, out_offsets)");
-    RALD_CHECK(lo3_host && v3_host && dims3_host, "voxel_downsample_ragged: null grid (lo3, v3, dims3)");
-    RALD_CHECK(B >= 1 && B <= VOX_MAX_BATCH, "voxel_downsample_ragged: batch must be 1 .. 65535");
-    RALD_CHECK(offsets || n_dense >= 0, "voxel_downsample_ragged: n_dense must be >= 0 without offsets");
-    RALD_CHECK(n_total >= 0 && n_total <= VOX_MAX_TOTAL, "voxel_downsample_ragged: n_total must be 0 .. 2^31 - 1");
-    RALD_CHECK(max_per_sample >= 1 && max_per_sample <= VOX_MAX_POINTS, "voxel_downsample_ragged: max_per_sample must be 1 .. 16777216");
-    RALD_CHECK(chunk >= 0 && chunk % 1024 == 0, "voxel_downsample_ragged: chunk must be 0 (automatic) or a multiple of 1024");
+int64_t voxel_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t sort = voxel_sort_scratch_bytes(B, n_total, max_per_sample, chunk);
+    if (sort < 0) return -1;
+    const int64_t nseg = (max_per_sample + VOX_SEG - 1) / VOX_SEG;
+    return sort + vox_align16((int64_t)B * nseg * 4) + vox_align16((int64_t)B * 4);
+}
+
+namespace {
+
+// the layout and grid rules of both entries
+int vox_check(const std::string& who, const int64_t* offsets, int B, int64_t n_dense, int64_t n_total, int64_t max_per_sample,
+              const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int64_t chunk) {
+    RALD_CHECK(lo3_host && v3_host && dims3_host, who + ": null grid (lo3, v3, dims3)");
+    RALD_CHECK(B >= 1 && B <= VOX_MAX_BATCH, who + ": batch must be 1 .. 65535");
+    RALD_CHECK(offsets || n_dense >= 0, who + ": n_dense must be >= 0 without offsets");
+    RALD_CHECK(n_total >= 0 && n_total <= VOX_MAX_TOTAL, who + ": n_total must be 0 .. 2^31 - 1");
+    RALD_CHECK(max_per_sample >= 1 && max_per_sample <= VOX_MAX_POINTS, who + ": max_per_sample must be 1 .. 16777216");
+    RALD_CHECK(chunk >= 0 && chunk % 1024 == 0, who + ": chunk must be 0 (automatic) or a multiple of 1024");
     int64_t cells = 1;
     for (int k = 0; k < 3; ++k) {
-        RALD_CHECK(dims3_host[k] >= 1, "voxel_downsample_ragged: every dim must be >= 1");
+        RALD_CHECK(dims3_host[k] >= 1, who + ": every dim must be >= 1");
         cells *= dims3_host[k];                              // <= (2^31 - 1)^2 after two factors: checked before the third
-        RALD_CHECK(cells <= VOX_MAX_TOTAL, "voxel_downsample_ragged: the grid must have at most 2^31 - 1 cells");
-        RALD_CHECK(std::isfinite(v3_host[k]) && v3_host[k] > 0.f, "voxel_downsample_ragged: every cell edge must be finite and > 0");
-        RALD_CHECK(std::isfinite(lo3_host[k]), "voxel_downsample_ragged: lo must be finite");
+        RALD_CHECK(cells <= VOX_MAX_TOTAL, who + ": the grid must have at most 2^31 - 1 cells");
+        RALD_CHECK(std::isfinite(v3_host[k]) && v3_host[k] > 0.f, who + ": every cell edge must be finite and > 0");
+        RALD_CHECK(std::isfinite(lo3_host[k]), who + ": lo must be finite");
     }
-    const int64_t need = voxel_scratch_bytes(B, n_total, max_per_sample, chunk);
-    RALD_CHECK(scratch_bytes >= need, "voxel_downsample_ragged: scratch too small");
-    RALD_CHECK(scratch && (uintptr_t)scratch % 16 == 0, "voxel_downsample_ragged: null or unaligned scratch");
-    VoxelArgs a;
+    return 0;
+}
+
+// the sort's part of the arguments (checked ones) -> the scratch behind the sort's share
+char* vox_sort_args(VoxelArgs& a, const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                    int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, void* scratch,
+                    int64_t chunk) {
+    a = VoxelArgs{};
     a.points = points; a.offsets = offsets; a.counts = counts;
     a.n_dense = n_dense; a.n_total = n_total; a.max_per_sample = max_per_sample;
     a.chunk = vox_pick_chunk(B, max_per_sample, chunk);
     a.nch_max = (max_per_sample + a.chunk - 1) / a.chunk;
     a.nseg_max = (max_per_sample + VOX_SEG - 1) / VOX_SEG;
     for (int k = 0; k < 3; ++k) { a.lo[k] = lo3_host[k]; a.v[k] = v3_host[k]; a.dims[k] = dims3_host[k]; }
+    const int64_t cells = (int64_t)a.dims[0] * a.dims[1] * a.dims[2];
     a.cells = (unsigned)cells;
     a.passes = voxel_passes(cells);
     char* s = (char*)scratch;
@@ -466,23 +447,60 @@ int voxel_downsample_ragged(const float* points, const int64_t* offsets, const i
     a.idx[0] = (int*)s; s += row_bytes;
     a.idx[1] = (int*)s; s += row_bytes;
     a.hist = (unsigned*)s; s += vox_align16((int64_t)B * 256 * a.nch_max * 4);
-    a.heads = (int*)s; s += vox_align16((int64_t)B * a.nseg_max * 4);
-    a.total = (int*)s;
     a.batch = B;
-    a.out_points = out_points; a.out_offsets = out_offsets; a.out_count = out_count; a.out_first = out_first; a.out_cells = out_cells;
-    a.out_inverse = out_inverse;
-    const dim3 by_cloud(B);
-    hipLaunchKernelGGL(vox_keys, dim3((unsigned)((max_per_sample + VOX_KT - 1) / VOX_KT), B), dim3(VOX_KT), 0, st, a);
+    return s;
+}
+
+// vox_keys and the sort: the sorted pairs end in key[passes & 1], idx[passes & 1]
+void vox_launch_sort(const VoxelArgs& a, hipStream_t st) {
+    const int B = a.batch;
+    hipLaunchKernelGGL(vox_keys, dim3((unsigned)((a.max_per_sample + VOX_KT - 1) / VOX_KT), B), dim3(VOX_KT), 0, st, a);
     if (a.nch_max == 1) {
-        hipLaunchKernelGGL(vox_sort_one, by_cloud, dim3(VOX_OT), 0, st, a);
+        hipLaunchKernelGGL(vox_sort_one, dim3(B), dim3(VOX_OT), 0, st, a);
     } else {
         const dim3 by_chunk((unsigned)a.nch_max, B);
         for (int pass = 0; pass < a.passes; ++pass) {
             hipLaunchKernelGGL(vox_hist, by_chunk, dim3(VOX_CT), 0, st, a, pass);
-            hipLaunchKernelGGL(vox_scan, by_cloud, dim3(256), 0, st, a);
+            hipLaunchKernelGGL(vox_scan, dim3(B), dim3(256), 0, st, a);
             hipLaunchKernelGGL(vox_scatter, by_chunk, dim3(VOX_CT), 0, st, a, pass);
         }
     }
+}
+
+}  // namespace
+
+int voxel_sort_ragged(const char* who, const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense,
+                      int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host,
+                      int64_t* out_inverse, void* scratch, int64_t chunk, hipStream_t st, VoxelSorted* out) {
+    RALD_TRY(vox_check(who, offsets, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, chunk));
+    VoxelArgs a;
+    vox_sort_args(a, points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, scratch, chunk);
+    a.out_inverse = out_inverse;
+    vox_launch_sort(a, st);
+    RALD_HIP(hipGetLastError());
+    out->key = a.key[a.passes & 1];
+    out->idx = a.idx[a.passes & 1];
+    out->cells = a.cells;
+    return 0;
+}
+
+int voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                            int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float* out_points,
+                            int64_t* out_offsets, int32_t* out_count, int64_t* out_first, int32_t* out_cells, int64_t* out_inverse,
+                            void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
+    RALD_CHECK(points && out_points && out_offsets, "voxel_downsample_ragged: null pointer (points, out_points, out_offsets)");
+    RALD_TRY(vox_check("voxel_downsample_ragged", offsets, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, chunk));
+    const int64_t need = voxel_scratch_bytes(B, n_total, max_per_sample, chunk);
+    RALD_CHECK(scratch_bytes >= need, "voxel_downsample_ragged: scratch too small");
+    RALD_CHECK(scratch && (uintptr_t)scratch % 16 == 0, "voxel_downsample_ragged: null or unaligned scratch");
+    VoxelArgs a;
+    char* s = vox_sort_args(a, points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, scratch, chunk);
+    a.heads = (int*)s; s += vox_align16((int64_t)B * a.nseg_max * 4);
+    a.total = (int*)s;
+    a.out_points = out_points; a.out_offsets = out_offsets; a.out_count = out_count; a.out_first = out_first; a.out_cells = out_cells;
+    a.out_inverse = out_inverse;
+    vox_launch_sort(a, st);
+    const dim3 by_cloud(B);
     const dim3 by_seg((unsigned)a.nseg_max, B);
     hipLaunchKernelGGL(vox_heads, by_seg, dim3(VOX_SEG), 0, st, a);
     hipLaunchKernelGGL(vox_head_scan, by_cloud, dim3(256), 0, st, a);

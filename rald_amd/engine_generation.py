@@ -5,6 +5,7 @@ inference tail (:250-322: query generation, helper points, refine pass, Chamfer)
 Data loading and PLY writing are out of scope."""
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -152,7 +153,7 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
                               normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                              thin=None):
+                              thin=None, denoise=None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
@@ -161,14 +162,21 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
     infer_point_clouds) the last two elements are the resampled clouds [B,k,3] and their row indices [B,k].  With `thin` (see
     infer_point_clouds) four elements come before those two: (thinned [T_cap,3], thin_offsets int64 [B+1], thin_count int32 [T_cap],
     thin_first int64 [T_cap]) - frame b's voxels are rows thin_offsets[b] .. thin_offsets[b+1]-1 - and the resample indices count rows
-    of the frame's thinned cloud."""
+    of the frame's thinned cloud.  With `denoise` (see infer_point_clouds) four elements come before those of `thin`: (denoised
+    [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64 [T_cap], cd_denoised float64 [B] or None), and with `metric_thresholds`
+    a fifth, the device dict of the denoised clouds' metrics (or None); thin and resample then run on the denoised clouds and their
+    indices count its rows."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
-    pts, off, cd, _, metrics, nrm, longest = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds,
-                                                             normals, surface_steps, surface_max_step)
+    denoise = _check_denoise(denoise, args)
+    pts, off, cd, _, metrics, nrm, longest, den = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
+                                                                  metric_thresholds, normals, surface_steps, surface_max_step, denoise)
     out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
     if nrm is not None:
         out = out + (nrm,)
+    if den is not None:
+        out = out + (den["points"], den["offsets"], den["index"], den["cd"]) + (() if metric_thresholds is None else (den["metrics"],))
+        pts, off = den["points"], den["offsets"]
     if grid is not None:
         thinned = _thin(pts, off, grid, longest)
         out = out + thinned
@@ -197,6 +205,23 @@ def _thin_grid(thin, args):
     return PP.voxel_grid(rng[:3], rng[3:], thin)
 
 
+def _check_denoise(denoise, args):
+    """`denoise` (None, or (radius, min_neighbors)) -> None or (radius, min_neighbors, grid): the search grid is _thin_grid's box with
+    the cell edge `radius`.  ValueError for anything else, and for a radius so small that the box has more than 2^31 - 1 cells, on the
+    host."""
+    if denoise is None:
+        return None
+    try:
+        radius, k = denoise
+    except (TypeError, ValueError):
+        raise ValueError("denoise must be None or (radius, min_neighbors)") from None
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
+        raise ValueError("denoise: radius must be a finite number > 0")
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or k < 1:
+        raise ValueError("denoise: min_neighbors must be an integer >= 1")
+    return float(radius), int(k), _thin_grid(float(radius), args)
+
+
 def _thin(pts: torch.Tensor, off: torch.Tensor, grid, longest: int):
     """The final clouds, one centroid per occupied cell -> (thinned [T,3], thin_offsets [B+1], thin_count [T], thin_first [T]); after
     the metric, which keeps the full cloud."""
@@ -214,10 +239,11 @@ def _resample(pts: torch.Tensor, off: torch.Tensor, k: int, longest: int):
 
 
 def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None, normals=False, surface_steps=0,
-                    surface_max_step=0.05):
+                    surface_max_step=0.05, denoise=None):
     """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None, normals or None) on the device: what
-    infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest; the
-    last element is the host bound of the longest final cloud."""
+    infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest; then
+    the host bound of the longest final cloud; the last element is None, or with `denoise` (_check_denoise's triple) the dict of the
+    denoised clouds: 'points', 'offsets', 'index', and 'cd' / 'metrics' (None where no metric is computed) against the same surfaces."""
     oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
@@ -271,7 +297,7 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         pts, nrm = PP.oriented_points_ragged(kept, grad, p_off, lidar.pc_range, aniso, iso, view_cone_mode=view_cone)
     elif view_cone:
         pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
-    cd, metrics = None, None
+    cd, metrics, den = None, None, None
     if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
         P = surfaces.shape[1]
         gt = PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso)   # :290
@@ -283,7 +309,16 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         else:
             metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
             cd = metrics["cd"]
-    return pts, p_off, cd, n_queries, metrics, nrm, longest
+    if denoise is not None:                                                                        # after the metric, which keeps the full cloud
+        d_pts, d_off, d_idx = PP.remove_radius_outliers_ragged(pts, p_off, denoise[0], denoise[1], denoise[2], max(1, int(longest)),
+                                                               return_index=True)
+        den = {"points": d_pts, "offsets": d_off, "index": d_idx, "cd": None, "metrics": None}
+        if cd is not None and metric_thresholds is None:
+            den["cd"] = PP.cal_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P)
+        elif cd is not None:
+            den["metrics"] = PP.cloud_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P, metric_thresholds)
+            den["cd"] = den["metrics"]["cd"]
+    return pts, p_off, cd, n_queries, metrics, nrm, longest, den
 
 
 def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
@@ -307,7 +342,7 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
                        surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                       thin=None) -> Dict[str, object]:
+                       thin=None, denoise=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -347,22 +382,39 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     before any GPU work.  The thinned offsets join the one host read.  With `resample` as well the sampler runs on the THINNED clouds
     and 'resample_index' counts rows of 'thinned'; a thinned cloud above 65536 voxels is still truncated to its first 65536 - now in
     cell-key order, a slab of the grid - so a coarser cell is the remedy.
+    `denoise` (None: today's calls, dict and host read; or (radius, min_neighbors) in the final clouds' coordinates): every final
+    cloud additionally without its isolated rows - a row stays iff at least min_neighbors OTHER rows of its frame lie within radius of
+    it, from postprocess.remove_radius_outliers_ragged on the box `thin` uses, cell edge = radius (a radius that
+    gives that box more than 2^31 - 1 cells raises ValueError before any GPU work).  'pred', 'cd' and 'metrics' stay on the full
+    cloud, untouched.  Added: 'denoised' a list of B tensors [m_b,3] (the kept rows in their order), 'denoise_index' a list of int64
+    [m_b] (rows of the frame's 'pred'), with normals / surface_steps 'denoised_normals' [m_b,3], with surfaces 'cd_denoised' (B floats,
+    None where no metric is computed) and with metric_thresholds 'metrics_denoised' (as 'metrics').  The denoised offsets and metrics
+    join the one host read.  `thin` and `resample` then run on the DENOISED clouds: 'thin_first' and (without thin) 'resample_index'
+    count rows of 'denoised', not of 'pred' - 'denoise_index' maps them back - and 'thinned_normals' are those of the rows thin_first
+    names in 'denoised'.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
     'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps, + 'resampled' and
-    'resample_index' with resample, + 'thinned', 'thin_count', 'thin_first' (and 'thinned_normals') with thin)."""
+    'resample_index' with resample, + 'thinned', 'thin_count', 'thin_first' (and 'thinned_normals') with thin, + 'denoised',
+    'denoise_index' (and 'denoised_normals', 'cd_denoised', 'metrics_denoised') with denoise)."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
-    pts, off, cd, nq, metrics, nrm, longest = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
-                                                              metric_thresholds, normals, surface_steps, surface_max_step)
+    denoise = _check_denoise(denoise, args)
+    pts, off, cd, nq, metrics, nrm, longest, den = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
+                                                                   metric_thresholds, normals, surface_steps, surface_max_step, denoise)
     B = sampled_tokens.shape[0]
-    s_pts, s_off, s_longest = pts, off, longest
+    s_pts, s_off, s_longest = (pts, off, longest) if den is None else (den["points"], den["offsets"], longest)
     if grid is not None:
-        t_pts, t_off, t_count, t_first = _thin(pts, off, grid, longest)
+        t_pts, t_off, t_count, t_first = _thin(s_pts, s_off, grid, longest)
         s_pts, s_off, s_longest = t_pts, t_off, _thin_bound(longest, grid)
     if resample is not None:
         resampled, resample_index = _resample(s_pts, s_off, resample, s_longest)
     extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
-    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + ([t_off.double()] if grid is not None else []))
+    d_extra = []
+    if den is not None:                                                                             # in front of the thinned offsets
+        d_extra = [den["offsets"].double()] + ([den["cd"]] if den["cd"] is not None else [])
+        d_extra += [den["metrics"][k].reshape(-1) for k in PP.METRIC_KEYS] if den["metrics"] is not None else []
+    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + d_extra
+                       + ([t_off.double()] if grid is not None else []))
     host = packed.cpu().tolist()                                                                    # the one host read
     o = [int(v) for v in host[:B + 1]]
     out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
@@ -372,12 +424,25 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         out["metrics"] = PP._metrics_to_host(host[3 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
     if nrm is not None:
         out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
+    if den is not None:
+        at = 2 * B + 1 + (B if cd is not None else 0) + sum(t.numel() for t in extra)
+        do = [int(v) for v in host[at:at + B + 1]]
+        out["denoised"] = [den["points"][do[b]:do[b + 1]] for b in range(B)]
+        out["denoise_index"] = [den["index"][do[b]:do[b + 1]] for b in range(B)]
+        if nrm is not None:
+            out["denoised_normals"] = [nrm[o[b] + out["denoise_index"][b]] for b in range(B)]
+        if surfaces is not None:
+            out["cd_denoised"] = host[at + B + 1:at + 2 * B + 1] if den["cd"] is not None else None
+        if metric_thresholds is not None:
+            out["metrics_denoised"] = (PP._metrics_to_host(host[at + 2 * B + 1:], B, len(metric_thresholds))
+                                       if den["metrics"] is not None else None)
     if grid is not None:
         to = [int(v) for v in host[len(host) - (B + 1):]]
         for key, t in (("thinned", t_pts), ("thin_count", t_count), ("thin_first", t_first)):
             out[key] = [t[to[b]:to[b + 1]] for b in range(B)]
         if nrm is not None:
-            out["thinned_normals"] = [nrm[o[b] + out["thin_first"][b]] for b in range(B)]
+            rows = out["thin_first"] if den is None else [out["denoise_index"][b][out["thin_first"][b]] for b in range(B)]
+            out["thinned_normals"] = [nrm[o[b] + rows[b]] for b in range(B)]
     if resample is not None:
         out["resampled"], out["resample_index"] = resampled, resample_index
     return out

@@ -8,8 +8,10 @@
 Beyond the reference's one metric: ``nearest_neighbors*`` and ``cloud_metrics*`` (exact nearest neighbours per point, and accuracy,
 completeness, both Chamfer variants, (modified) Hausdorff distance and precision / recall / F-score per frame),
 ``farthest_point_sample*`` / ``resample_points_ragged`` (k evenly spread points per cloud, the device counterpart of
-``torch_cluster.fps``), and ``voxel_grid`` / ``voxel_downsample*`` (one centroid per occupied cell of a fixed
-grid, the device counterpart of Open3D's ``voxel_down_sample``).
+``torch_cluster.fps``), ``voxel_grid`` / ``voxel_downsample*`` (one centroid per occupied cell of a fixed
+grid, the device counterpart of Open3D's ``voxel_down_sample``), and ``radius_neighbor_count_ragged`` /
+``remove_radius_outliers*`` (neighbours within a radius inside a cloud and the outlier filter on them, the device counterpart of
+Open3D's ``remove_radius_outlier``).
 """
 from __future__ import annotations
 
@@ -560,3 +562,140 @@ def voxel_downsample(points: torch.Tensor, voxel, lo: Optional[Sequence[float]] 
     offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
     out, off = voxel_downsample_ragged(points, offsets, grid, N)
     return out[:int(off[1].item())]
+
+
+def _radius_args(points, radius, grid, max_per_sample, counts, B: Optional[int], chunk, cap, cap_name: str, cap_min: int):
+    """The rules of the radius calls beyond the voxel calls' (ValueError, before anything asks where a tensor lives) -> (radius as the
+    float32 the kernels use, cap, max_per_sample, chunk, the grid's three ctypes arrays)."""
+    max_per_sample, chunk = _voxel_args(points, max_per_sample, counts, B, chunk)
+    arrays = _voxel_grid_arg(grid)
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
+        raise ValueError("radius must be a finite number > 0")
+    try:
+        radius = _f32(float(radius))
+    except OverflowError:
+        raise ValueError("radius must fit float32") from None
+    if not radius > 0 or not math.isfinite(radius):
+        raise ValueError("radius must fit float32")
+    if any(float(v) < radius for v in grid[1]):
+        raise ValueError("every cell edge of the grid must be >= radius (build it with voxel_grid(lo, hi, radius))")
+    if isinstance(cap, bool) or int(cap) != cap or cap < cap_min or cap > 2 ** 31 - 1:
+        raise ValueError(f"{cap_name} must be an integer >= {cap_min}")
+    return radius, int(cap), max_per_sample, chunk, arrays
+
+
+def _radius_scratch(B: int, T: int, max_per_sample: int, chunk: int, dev):
+    L = lib()
+    nbytes = _nbytes(L.rald_op_radius_scratch_bytes(B, T, max_per_sample, chunk) if chunk else L.rald_post_radius_scratch_bytes(B, T, max_per_sample))
+    return _scratch(nbytes, dev), nbytes
+
+
+def radius_neighbor_count_ragged(points: torch.Tensor, offsets: torch.Tensor, radius: float, grid, max_per_sample: int,
+                                 counts: Optional[torch.Tensor] = None, max_count: int = 0, return_nearest: bool = False, chunk: int = 0):
+    """Neighbours within `radius` inside each cloud of a ragged batch (rald_post_radius_count_ragged): points
+    [T,3], offsets int64 [B+1] on the device, grid = voxel_grid(lo, hi, voxel) with every cell edge >= radius (voxel=radius is the normal
+    use; the grid only indexes the search and does not show in the result beyond its box) -> count int32 [T], laid out like points:
+    the number of OTHER rows of the same cloud (by row index: a duplicate counts) with squared float32 distance <= float32(radius)^2,
+    min(count, max_count) with max_count > 0 (the search stops there), -1 for a row outside the grid's box (NaN and inf rows
+    included; such rows are nobody's neighbour).  return_nearest (needs max_count = 0) adds nn_idx int64 [T] (the nearest other row
+    within the radius, from the cloud's first row, the smallest index on equal distances, -1 when there is none) and nn_dist2 float32
+    [T] (its squared distance, +inf when there is none).  Rows past offsets[B] or behind counts / the bound are unspecified.
+    counts, max_per_sample, chunk: as voxel_downsample_ragged.  Defined to the bit: the same in every call, batch, chunk and grid.
+    No host read, no synchronisation; runs on the current stream."""
+    radius, max_count, max_per_sample, chunk, (lo3, v3, dims3) = _radius_args(points, radius, grid, max_per_sample, counts,
+                                                                            _offsets_shape(offsets, "offsets"), chunk, max_count, "max_count", 0)
+    if return_nearest and max_count:
+        raise ValueError("return_nearest needs max_count = 0")
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.contiguous()
+    points = _f32c(points)
+    T, dev = points.shape[0], points.device
+    cnt = torch.empty(T, device=dev, dtype=torch.int32)
+    nn_idx = torch.empty(T, device=dev, dtype=torch.int64) if return_nearest else None
+    nn_dist2 = torch.empty(T, device=dev, dtype=torch.float32) if return_nearest else None
+    scratch, nbytes = _radius_scratch(B, T, max_per_sample, chunk, dev)
+    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, radius, max_count, cnt.data_ptr(),
+            _opt(nn_idx), _opt(nn_dist2), scratch.data_ptr(), nbytes)
+    L = lib()
+    check(L.rald_op_radius_count_ragged(*head, chunk, _stream()) if chunk else L.rald_post_radius_count_ragged(*head, _stream()))
+    return (cnt, nn_idx, nn_dist2) if return_nearest else cnt
+
+
+def remove_radius_outliers_ragged(points: torch.Tensor, offsets: torch.Tensor, radius: float, min_neighbors: int, grid, max_per_sample: int,
+                                  counts: Optional[torch.Tensor] = None, return_index: bool = False, return_count: bool = False,
+                                  chunk: int = 0):
+    """Radius outlier removal per cloud of a ragged batch (rald_post_radius_filter_ragged): a row stays iff it
+    lies inside the grid's box and at least min_neighbors (>= 1) OTHER rows of its cloud lie within `radius` of it
+    (radius_neighbor_count_ragged's count).  -> (points [T,3], out_offsets int64 [B+1], ...) on the device, sized for the worst case:
+    cloud b's kept rows are rows out_offsets[b] .. out_offsets[b+1]-1 in their ORIGINAL order, bit for bit the input rows; rows past
+    out_offsets[B] are unspecified.  Then, for every flag set: index int64 [T] (per kept row, its row in its cloud), count int32 [T]
+    (per INPUT row: min(count, min_neighbors), -1 outside the box).  Arguments as radius_neighbor_count_ragged.
+    No host read, no synchronisation; runs on the current stream."""
+    radius, min_neighbors, max_per_sample, chunk, (lo3, v3, dims3) = _radius_args(points, radius, grid, max_per_sample, counts,
+                                                                                _offsets_shape(offsets, "offsets"), chunk, min_neighbors,
+                                                                                "min_neighbors", 1)
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.contiguous()
+    points = _f32c(points)
+    T, dev = points.shape[0], points.device
+    out = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    index = torch.empty(T, device=dev, dtype=torch.int64) if return_index else None
+    cnt = torch.empty(T, device=dev, dtype=torch.int32) if return_count else None
+    scratch, nbytes = _radius_scratch(B, T, max_per_sample, chunk, dev)
+    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, radius, min_neighbors, out.data_ptr(),
+            out_offsets.data_ptr(), _opt(index), _opt(cnt), scratch.data_ptr(), nbytes)
+    L = lib()
+    check(L.rald_op_radius_filter_ragged(*head, chunk, _stream()) if chunk else L.rald_post_radius_filter_ragged(*head, _stream()))
+    return (out, out_offsets) + tuple(t for t in (index, cnt) if t is not None)
+
+
+def remove_radius_outliers(points: torch.Tensor, radius: float, min_neighbors: int, lo: Optional[Sequence[float]] = None,
+                           hi: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """One cloud [N,3] -> [m,3]: the rows with at least min_neighbors other rows within `radius`, in their order - the device
+    counterpart of a radius outlier filter.  lo / hi: the box of the search grid (rows outside it are dropped); without them the box is
+    the cloud's own minimum and maximum - that costs one host read of six numbers (and the cloud must be finite); the result's length
+    is a second host read in either case.  Where the box would need more than 2^31 - 1 cells of edge `radius` the cells are made
+    larger; the result does not depend on that."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [N, 3]")
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi come together")
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
+        raise ValueError("radius must be a finite number > 0")
+    if isinstance(min_neighbors, bool) or int(min_neighbors) != min_neighbors or min_neighbors < 1:
+        raise ValueError("min_neighbors must be an integer >= 1")
+    if lo is not None:
+        grid = _radius_grid(lo, hi, radius)
+    N = points.shape[0]
+    if N == 0:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _need_cuda(points, "points")
+    points = _f32c(points)
+    if lo is None:
+        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
+        grid = _radius_grid(ext[:3], ext[3:], radius)
+    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    out, off = remove_radius_outliers_ragged(points, offsets, radius, int(min_neighbors), grid, N)
+    return out[:int(off[1].item())]
+
+
+def _radius_grid(lo, hi, radius):
+    """voxel_grid(lo, hi, edge) with the smallest edge radius * 2^k (k >= 0) that keeps the grid within 2^31 - 1 cells."""
+    edge = float(radius)
+    for _ in range(64):
+        try:
+            return voxel_grid(lo, hi, edge)
+        except ValueError as e:
+            if "cells" not in str(e):
+                raise
+        edge *= 2.0
+    raise ValueError("no grid of at most 2^31 - 1 cells covers lo .. hi")
