@@ -427,6 +427,71 @@ int rald_op_radius_filter_ragged(const float* points, const int64_t* offsets, co
                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                  const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
                                  int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
+/* ---- k nearest other rows inside a cloud and the statistical outlier filter.  Defined to the bit, so the
+ * result is the same in every call, in every batch, for every chunk length and for every grid over the same box:
+ *   Layout, grid, INSIDE and d2(i, j) are exactly those of rald_post_radius_count_ragged: points fp32 [n_total,3]; offsets DEVICE int64
+ *   [batch+1], or NULL with n_dense; counts optional; max_per_sample a trusted HOST bound, 1 .. 16777216; lo3_host, v3_host, dims3_host
+ *   with cells <= 2^31 - 1; d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in fp32 without contraction; rows outside the box (NaN,
+ *   +-inf) take no part.
+ *   k: a HOST value, 1 .. 32.  max_radius: a HOST float, 0 = none, otherwise finite and > 0, r2max = fl(max_radius * max_radius).
+ *   The CANDIDATES of an inside row i are the inside rows j != i of its cloud (by row index: a duplicate of row i is a candidate at
+ *   distance 0), with max_radius only those with d2(i, j) <= r2max, ordered by the pair (d2(i, j), j) ascending - on equal distances
+ *   the SMALLER row index comes first.
+ *   Outputs per INPUT row, laid out like points: out_idx int64 [n_total,k], slot s = the s-th candidate's row index from the cloud's
+ *   first row; out_dist2 fp32 [n_total,k] (may be NULL) its d2; out_found int32 [n_total] (may be NULL) = min(k, number of candidates),
+ *   -1 for a row outside.  Slots from `found` on hold -1 / +inf; a row outside holds that in every slot.  Rows outside every cloud's
+ *   span are not written.
+ *   Every output is a function of the cloud's own rows, k, max_radius and the box (through which rows are inside) alone: the cell
+ *   edge, the chunk, the batch and the call do not show, and no relation between v3 and max_radius is asked for.
+ * Statistical outlier removal: k and max_radius as above; std_ratio a HOST double, finite and >= 0.
+ *   m[i] (float64) = the sum over the slots s = 0 .. found-1, in that order, of sqrt((double)dist2[s]), divided by (double)found; the
+ *   square root and the division correctly rounded.  found = 0: m = +inf.  A row outside: NaN.
+ *   F = the inside rows of the cloud with found >= 1, n_f = |F|.  Cloud sums have ONE FIXED SHAPE, so that they depend on the cloud
+ *   alone: the cloud's rows in row order, a row not in F as +0.0, padded with +0.0 to a multiple of 1024; inside block g (rows 1024g ..
+ *   1024g+1023) for h = 512, 256, .., 1: v[t] += v[t+h] for t < h; the cloud's sum is s = 0.0; s += v_g[0] for g ascending.
+ *   mu = SUM(m) / n_f; sigma = n_f >= 2 ? sqrt(SUM((m - mu) * (m - mu)) / (n_f - 1)) : 0; thr = fl(mu + fl(std_ratio * sigma)); all
+ *   float64 without contraction.  Row i is KEPT iff it is in F and m[i] <= thr.  n_f = 0: nothing is kept, mu = sigma = thr = NaN.
+ *   Outputs as the radius filter's: out_points (the kept rows in their order, the input row's bits), out_offsets DEVICE int64
+ *   [batch+1], optional out_index int64 [n_total]; optional out_mean float64 [n_total] (m per INPUT row), optional out_stats float64
+ *   [batch,3] = mu, sigma, thr.
+ *   Where this differs from the usual libraries (Open3D remove_statistical_outlier, PCL StatisticalOutlierRemoval; neither is
+ *   available to check against, so their conventions are stated from their documentation, unchecked): k counts OTHER rows, where
+ *   Open3D's nb_neighbors includes the point itself; the filter keeps m <= thr, so a cloud of equal means is kept whole; the
+ *   deviation divides by n_f - 1.
+ * One lane per sorted position keeps its best-k list in LDS and scans a growing box of cells of the radius search's index; it stops
+ * when the scanned box holds, on all three axes, the radius search's scan range for a float r with fl(r * r) >= w - w the list's worst
+ * d2 once it holds k entries, else r2max - or the whole grid (DESIGN.md section 23 has the proof).  A row far from all others scans
+ * the grid: its time grows with the grid's x extent and the rows of the cloud.  No atomics, no kernel waits on another workgroup.
+ * The filter never holds the [n_total,k] tables: its scratch does not depend on k.
+ * found = -2 cannot occur: it would say that the search ran out of its bound of 40 boxes (at most 35 are possible) before its list
+ * was final, and such a row counts as outside.
+ * n_total = 0 is accepted (nothing is written but out_offsets and out_stats), but points and the required outputs must still be
+ * non-NULL pointers.
+ * scratch: rald_post_knn_scratch_bytes / rald_post_statistical_scratch_bytes of the same batch, n_total and bound, 16-byte aligned,
+ * never NULL; -1 (and rald_last_error) for sizes the calls refuse.  Every invalid argument is refused with a status before any GPU
+ * work.  rald_op_*: test-facing, with the chunk length of the split sort as in the radius calls. */
+int64_t rald_post_knn_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample);
+int rald_post_knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
+                         int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
+                         float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes,
+                         void* stream);
+int64_t rald_post_statistical_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample);
+int rald_post_statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                        int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                        const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
+                                        int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
+                                        int64_t scratch_bytes, void* stream);
+int64_t rald_op_knn_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int rald_op_knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
+                       int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
+                       float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes,
+                       int64_t chunk, void* stream);
+int64_t rald_op_statistical_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int rald_op_statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                      int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                      const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
+                                      int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
+                                      int64_t scratch_bytes, int64_t chunk, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

@@ -487,6 +487,60 @@ int rald_op_radius_filter_ragged(const float* points, const int64_t* offsets, co
                                 min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, chunk, (hipStream_t)stream);
 }
 
+// ---- k nearest neighbours and the statistical outlier filter ------------------------------
+int64_t rald_post_knn_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample) {
+    const int64_t n = knn_scratch_bytes(batch, n_total, max_per_sample, 0);
+    if (n < 0) set_error(std::string("rald_post_knn_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int64_t rald_op_knn_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t n = knn_scratch_bytes(batch, n_total, max_per_sample, chunk);
+    if (n < 0) set_error(std::string("rald_op_knn_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int64_t rald_post_statistical_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample) {
+    const int64_t n = statistical_scratch_bytes(batch, n_total, max_per_sample, 0);
+    if (n < 0) set_error(std::string("rald_post_statistical_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int64_t rald_op_statistical_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t n = statistical_scratch_bytes(batch, n_total, max_per_sample, chunk);
+    if (n < 0) set_error(std::string("rald_op_statistical_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int rald_post_knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
+                         int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
+                         float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes,
+                         void* stream) {
+    return knn_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k, max_radius, out_idx,
+                      out_dist2, out_found, scratch, scratch_bytes, 0, (hipStream_t)stream);
+}
+int rald_op_knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
+                       int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
+                       float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes,
+                       int64_t chunk, void* stream) {
+    return knn_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k, max_radius, out_idx,
+                      out_dist2, out_found, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+}
+int rald_post_statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                        int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                        const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
+                                        int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
+                                        int64_t scratch_bytes, void* stream) {
+    return statistical_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k,
+                                     max_radius, std_ratio, out_points, out_offsets, out_index, out_mean, out_stats, scratch, scratch_bytes, 0,
+                                     (hipStream_t)stream);
+}
+int rald_op_statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                      int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                      const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
+                                      int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
+                                      int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return statistical_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k,
+                                     max_radius, std_ratio, out_points, out_offsets, out_index, out_mean, out_stats, scratch, scratch_bytes,
+                                     chunk, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

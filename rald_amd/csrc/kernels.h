@@ -419,6 +419,41 @@ int radius_filter_ragged(const float* points, const int64_t* offsets, const int3
                          int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float radius,
                          int min_neighbors, float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_count, void* scratch,
                          int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+// the parts knn_search.hip shares; no argument is checked, the layout is the one the sort has accepted
+// srow[row0 + j] = x, y, z and the row's index (its bits) of sorted position j, 16 bytes a row
+void radius_gather_sorted(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                          int64_t max_per_sample, const int* sidx, float4* srow, hipStream_t st);
+// the compaction in row order: row i of a cloud is kept iff cnt[row0 + i] >= min_neighbors.  scratch: radius_compact_scratch_bytes
+int64_t radius_compact_scratch_bytes(int B, int64_t max_per_sample);
+void radius_compact_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                           int64_t max_per_sample, const int32_t* cnt, int min_neighbors, float* out_points, int64_t* out_offsets,
+                           int64_t* out_index, void* scratch, hipStream_t st);
+__device__ __forceinline__ int rad_clamp(int r, int n) { return r < 0 ? 0 : (r < n ? r : n - 1); }
+// the cell of a scan bound as an index of the grid: the cell function of the keys, clamped in float (a NaN cannot occur: p is finite)
+__device__ __forceinline__ int rad_cell(float p, float lo, float v, int dims) {
+    float cf = voxel_cell(p, lo, v);
+    cf = fminf(fmaxf(cf, 0.f), 2147483520.f);                // the largest float below 2^31
+    const int c = (int)cf;
+    return c < dims ? c : dims - 1;
+}
+__device__ __forceinline__ float rad_d2(const float4& p, const float4& q) {
+#pragma clang fp contract(off)
+    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// ---------------------------------------------------------------- knn_search.hip
+// k nearest other rows inside each cloud of a ragged batch, and the statistical outlier filter on their mean distance
+// (include/rald_hip.h); chunk as above
+int64_t knn_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+               int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k, float max_radius,
+               int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+int64_t statistical_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                              int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k,
+                              float max_radius, double std_ratio, float* out_points, int64_t* out_offsets, int64_t* out_index,
+                              double* out_mean, double* out_stats, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
 
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);

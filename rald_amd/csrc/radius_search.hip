@@ -18,6 +18,8 @@
 //   rad_block_scan  (cloud)              exclusive scan of the block counts in place, the cloud's kept rows
 //   rad_offsets     one workgroup        out_offsets = exclusive scan of the kept counts over the batch
 //   rad_compact     (1024 rows, cloud)   a kept row to out_offsets[b] + its rank
+// knn_search.hip uses rad_gather and the four compaction kernels through radius_gather_sorted and
+// radius_compact_ragged (kernels.h), and the device helpers rad_clamp / rad_cell / rad_d2 that live there.
 // No atomics at all.  Every loop is bounded by the cloud's length (<= max_per_sample, a host value), by the grid's dims (host values) or
 // by 32.  A row index read from the scratch is clamped into the cloud before it addresses anything.
 #include <cmath>
@@ -55,8 +57,6 @@ __device__ __forceinline__ int rad_span(const RadiusArgs& a, int b, int64_t& row
     return ragged_span(a.offsets, a.counts, a.n_dense, a.n_total, a.max_per_sample, b, row0);
 }
 
-__device__ __forceinline__ int rad_clamp(int r, int n) { return r < 0 ? 0 : (r < n ? r : n - 1); }
-
 __global__ __launch_bounds__(RAD_T) void rad_gather(RadiusArgs a) {
     const int b = blockIdx.y;
     int64_t row0;
@@ -66,20 +66,6 @@ __global__ __launch_bounds__(RAD_T) void rad_gather(RadiusArgs a) {
     const int r = rad_clamp(a.sidx[row0 + j], n);
     const float* p = a.points + (row0 + r) * 3;
     a.srow[row0 + j] = make_float4(p[0], p[1], p[2], __int_as_float(r));
-}
-
-// the cell of a scan bound as an index of the grid: the cell function of the keys, clamped in float (a NaN cannot occur: p is finite)
-__device__ __forceinline__ int rad_cell(float p, float lo, float v, int dims) {
-    float cf = voxel_cell(p, lo, v);
-    cf = fminf(fmaxf(cf, 0.f), 2147483520.f);                // the largest float below 2^31
-    const int c = (int)cf;
-    return c < dims ? c : dims - 1;
-}
-
-__device__ __forceinline__ float rad_d2(const float4& p, const float4& q) {
-#pragma clang fp contract(off)
-    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-    return (dx * dx + dy * dy) + dz * dz;
 }
 
 __global__ __launch_bounds__(RAD_T) void rad_count(RadiusArgs a) {
@@ -219,6 +205,14 @@ __global__ __launch_bounds__(RAD_SEG) void rad_compact(RadiusArgs a) {
 
 inline int64_t rad_align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
 
+void rad_layout(RadiusArgs& a, const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                int64_t max_per_sample) {
+    a.points = points; a.offsets = offsets; a.counts = counts;
+    a.n_dense = n_dense; a.n_total = n_total; a.max_per_sample = max_per_sample;
+    a.nseg_max = (max_per_sample + RAD_SEG - 1) / RAD_SEG;
+    a.batch = B;
+}
+
 // the checks of both entries that the sort does not make, then the sort and the two search launches
 int rad_search(const std::string& who, RadiusArgs& a, const float* points, const int64_t* offsets, const int32_t* counts, int B,
                int64_t n_dense, int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
@@ -235,9 +229,7 @@ int rad_search(const std::string& who, RadiusArgs& a, const float* points, const
     VoxelSorted sorted;
     RALD_TRY(voxel_sort_ragged(who.c_str(), points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host,
                                nullptr, scratch, chunk, st, &sorted));
-    a.points = points; a.offsets = offsets; a.counts = counts;
-    a.n_dense = n_dense; a.n_total = n_total; a.max_per_sample = max_per_sample;
-    a.nseg_max = (max_per_sample + RAD_SEG - 1) / RAD_SEG;
+    rad_layout(a, points, offsets, counts, B, n_dense, n_total, max_per_sample);
     for (int k = 0; k < 3; ++k) { a.lo[k] = lo3_host[k]; a.v[k] = v3_host[k]; a.dims[k] = dims3_host[k]; }
     a.cells = sorted.cells;
     a.r2 = radius * radius;
@@ -247,9 +239,7 @@ int rad_search(const std::string& who, RadiusArgs& a, const float* points, const
     char* s = (char*)scratch + voxel_sort_scratch_bytes(B, n_total, max_per_sample, chunk);
     a.srow = (float4*)s; s += rad_align16(n_total * 16);
     a.cnt = cnt_or_null ? cnt_or_null : (int32_t*)s; s += rad_align16(n_total * 4);
-    a.blocks = (int*)s; s += rad_align16((int64_t)B * a.nseg_max * 4);
-    a.total = (int*)s;
-    a.batch = B;
+    a.blocks = (int*)s;                                      // the compaction's share: radius_compact_ragged lays it out
     const dim3 by_pos((unsigned)((max_per_sample + RAD_T - 1) / RAD_T), B);
     hipLaunchKernelGGL(rad_gather, by_pos, dim3(RAD_T), 0, st, a);
     hipLaunchKernelGGL(rad_count, by_pos, dim3(RAD_T), 0, st, a);
@@ -258,11 +248,39 @@ int rad_search(const std::string& who, RadiusArgs& a, const float* points, const
 
 }  // namespace
 
+void radius_gather_sorted(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                          int64_t max_per_sample, const int* sidx, float4* srow, hipStream_t st) {
+    RadiusArgs a{};
+    rad_layout(a, points, offsets, counts, B, n_dense, n_total, max_per_sample);
+    a.sidx = sidx; a.srow = srow;
+    hipLaunchKernelGGL(rad_gather, dim3((unsigned)((max_per_sample + RAD_T - 1) / RAD_T), B), dim3(RAD_T), 0, st, a);
+}
+
+int64_t radius_compact_scratch_bytes(int B, int64_t max_per_sample) {
+    const int64_t nseg = (max_per_sample + RAD_SEG - 1) / RAD_SEG;
+    return rad_align16((int64_t)B * nseg * 4) + rad_align16((int64_t)B * 4);
+}
+
+void radius_compact_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
+                           int64_t max_per_sample, const int32_t* cnt, int min_neighbors, float* out_points, int64_t* out_offsets,
+                           int64_t* out_index, void* scratch, hipStream_t st) {
+    RadiusArgs a{};
+    rad_layout(a, points, offsets, counts, B, n_dense, n_total, max_per_sample);
+    a.cnt = const_cast<int32_t*>(cnt); a.min_neighbors = min_neighbors;
+    a.out_points = out_points; a.out_offsets = out_offsets; a.out_index = out_index;
+    a.blocks = (int*)scratch;
+    a.total = (int*)((char*)scratch + rad_align16((int64_t)B * a.nseg_max * 4));
+    const dim3 by_seg((unsigned)a.nseg_max, B);
+    hipLaunchKernelGGL(rad_flags, by_seg, dim3(RAD_SEG), 0, st, a);
+    hipLaunchKernelGGL(rad_block_scan, dim3(B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rad_offsets, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rad_compact, by_seg, dim3(RAD_SEG), 0, st, a);
+}
+
 int64_t radius_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
     const int64_t sort = voxel_sort_scratch_bytes(B, n_total, max_per_sample, chunk);
     if (sort < 0) return -1;
-    const int64_t nseg = (max_per_sample + RAD_SEG - 1) / RAD_SEG;
-    return sort + rad_align16(n_total * 16) + rad_align16(n_total * 4) + rad_align16((int64_t)B * nseg * 4) + rad_align16((int64_t)B * 4);
+    return sort + rad_align16(n_total * 16) + rad_align16(n_total * 4) + radius_compact_scratch_bytes(B, max_per_sample);
 }
 
 int radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
@@ -287,15 +305,10 @@ int radius_filter_ragged(const float* points, const int64_t* offsets, const int3
     RALD_CHECK(points && out_points && out_offsets, "radius_filter_ragged: null pointer (points, out_points, out_offsets)");
     RALD_CHECK(min_neighbors >= 1, "radius_filter_ragged: min_neighbors must be >= 1");
     RadiusArgs a{};
-    a.min_neighbors = min_neighbors;
-    a.out_points = out_points; a.out_offsets = out_offsets; a.out_index = out_index;
     RALD_TRY(rad_search("radius_filter_ragged", a, points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host,
                         dims3_host, radius, min_neighbors, out_count, scratch, scratch_bytes, chunk, st));
-    const dim3 by_seg((unsigned)a.nseg_max, B);
-    hipLaunchKernelGGL(rad_flags, by_seg, dim3(RAD_SEG), 0, st, a);
-    hipLaunchKernelGGL(rad_block_scan, dim3(B), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(rad_offsets, dim3(1), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(rad_compact, by_seg, dim3(RAD_SEG), 0, st, a);
+    radius_compact_ragged(points, offsets, counts, B, n_dense, n_total, max_per_sample, a.cnt, min_neighbors, out_points, out_offsets, out_index,
+                          a.blocks, st);
     RALD_HIP(hipGetLastError());
     return 0;
 }

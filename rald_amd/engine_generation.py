@@ -153,7 +153,7 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
                               normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                              thin=None, denoise=None):
+                              thin=None, denoise=None, denoise_statistical=None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
@@ -165,10 +165,11 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
     of the frame's thinned cloud.  With `denoise` (see infer_point_clouds) four elements come before those of `thin`: (denoised
     [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64 [T_cap], cd_denoised float64 [B] or None), and with `metric_thresholds`
     a fifth, the device dict of the denoised clouds' metrics (or None); thin and resample then run on the denoised clouds and their
-    indices count its rows."""
+    indices count its rows.  `denoise_statistical` (see infer_point_clouds) fills the same positions and adds one element behind them:
+    denoise_stats float64 [B,3] (mu, sigma, the threshold)."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
-    denoise = _check_denoise(denoise, args)
+    denoise = _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args)
     pts, off, cd, _, metrics, nrm, longest, den = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
                                                                   metric_thresholds, normals, surface_steps, surface_max_step, denoise)
     out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
@@ -176,6 +177,8 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
         out = out + (nrm,)
     if den is not None:
         out = out + (den["points"], den["offsets"], den["index"], den["cd"]) + (() if metric_thresholds is None else (den["metrics"],))
+        if den.get("stats") is not None:
+            out = out + (den["stats"],)
         pts, off = den["points"], den["offsets"]
     if grid is not None:
         thinned = _thin(pts, off, grid, longest)
@@ -222,6 +225,31 @@ def _check_denoise(denoise, args):
     return float(radius), int(k), _thin_grid(float(radius), args)
 
 
+def _check_denoise_statistical(stat, denoise, args):
+    """`denoise_statistical` (None, or (k, std_ratio, cell) or (k, std_ratio, cell, max_radius)) -> None or ('statistical', k, std_ratio,
+    grid, max_radius or None): the search grid is _thin_grid's box with the cell edge `cell`.  ValueError for anything else, for a cell
+    that gives the box more than 2^31 - 1 cells, and for `denoise` given as well (chaining the two filters is not offered), on the host."""
+    if stat is None:
+        return None
+    if denoise is not None:
+        raise ValueError("denoise and denoise_statistical exclude each other")
+    try:
+        k, ratio, cell = stat[:3]
+        max_radius = stat[3] if len(stat) == 4 else None
+        ok = len(stat) in (3, 4)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("denoise_statistical must be None, (k, std_ratio, cell) or (k, std_ratio, cell, max_radius)")
+    k, ratio = PP._knn_k(k), PP._knn_ratio(ratio)
+    if max_radius is not None:
+        PP._knn_radius(max_radius)
+        max_radius = float(max_radius)
+    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0:
+        raise ValueError("denoise_statistical: cell must be a finite number > 0")
+    return "statistical", k, ratio, _thin_grid(float(cell), args), max_radius
+
+
 def _thin(pts: torch.Tensor, off: torch.Tensor, grid, longest: int):
     """The final clouds, one centroid per occupied cell -> (thinned [T,3], thin_offsets [B+1], thin_count [T], thin_first [T]); after
     the metric, which keeps the full cloud."""
@@ -242,8 +270,9 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
                     surface_max_step=0.05, denoise=None):
     """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None, normals or None) on the device: what
     infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest; then
-    the host bound of the longest final cloud; the last element is None, or with `denoise` (_check_denoise's triple) the dict of the
-    denoised clouds: 'points', 'offsets', 'index', and 'cd' / 'metrics' (None where no metric is computed) against the same surfaces."""
+    the host bound of the longest final cloud; the last element is None, or with `denoise` (_check_denoise's triple, or
+    _check_denoise_statistical's tuple) the dict of the denoised clouds: 'points', 'offsets', 'index', and 'cd' / 'metrics' (None where
+    no metric is computed) against the same surfaces; with the statistical filter 'stats' [B,3] as well."""
     oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
@@ -310,9 +339,15 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
             metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
             cd = metrics["cd"]
     if denoise is not None:                                                                        # after the metric, which keeps the full cloud
-        d_pts, d_off, d_idx = PP.remove_radius_outliers_ragged(pts, p_off, denoise[0], denoise[1], denoise[2], max(1, int(longest)),
-                                                               return_index=True)
-        den = {"points": d_pts, "offsets": d_off, "index": d_idx, "cd": None, "metrics": None}
+        d_stats = None
+        if denoise[0] == "statistical":
+            d_pts, d_off, d_idx, d_stats = PP.remove_statistical_outliers_ragged(pts, p_off, denoise[1], denoise[2], denoise[3],
+                                                                                 max(1, int(longest)), max_radius=denoise[4],
+                                                                                 return_index=True, return_stats=True)
+        else:
+            d_pts, d_off, d_idx = PP.remove_radius_outliers_ragged(pts, p_off, denoise[0], denoise[1], denoise[2], max(1, int(longest)),
+                                                                   return_index=True)
+        den = {"points": d_pts, "offsets": d_off, "index": d_idx, "cd": None, "metrics": None, "stats": d_stats}
         if cd is not None and metric_thresholds is None:
             den["cd"] = PP.cal_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P)
         elif cd is not None:
@@ -342,7 +377,7 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
                        surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                       thin=None, denoise=None) -> Dict[str, object]:
+                       thin=None, denoise=None, denoise_statistical=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -392,13 +427,22 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     join the one host read.  `thin` and `resample` then run on the DENOISED clouds: 'thin_first' and (without thin) 'resample_index'
     count rows of 'denoised', not of 'pred' - 'denoise_index' maps them back - and 'thinned_normals' are those of the rows thin_first
     names in 'denoised'.
+    `denoise_statistical` (None: today's calls, dict and host read; or (k, std_ratio, cell) or (k, std_ratio, cell, max_radius)): the
+    statistical outlier filter in `denoise`'s place - a row stays iff the mean distance to its k nearest other rows of its frame (within
+    max_radius, if given) is at most mu + std_ratio * sigma of its frame's means, from postprocess.remove_statistical_outliers_ragged
+    (DESIGN section 23); it adapts to the cloud's density, which thins out with range, where `denoise` needs one radius in metres.
+    `cell` is the search grid's edge over the box `thin` uses (it does not show in the result; k / 8 to k rows per cell is a good edge; a
+    cell that gives the box more than 2^31 - 1 cells raises ValueError before any GPU work).  It fills the keys of `denoise` - 'denoised',
+    'denoise_index', 'denoised_normals', 'cd_denoised', 'metrics_denoised' - feeds `thin` and `resample` as `denoise` does, and adds
+    'denoise_stats': B triples (mu, sigma, threshold) as floats, NaN for a frame without a row that has a neighbour, carried in the
+    one host read.  Given together with `denoise` it raises ValueError: the two filters are not chained.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
     'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps, + 'resampled' and
     'resample_index' with resample, + 'thinned', 'thin_count', 'thin_first' (and 'thinned_normals') with thin, + 'denoised',
     'denoise_index' (and 'denoised_normals', 'cd_denoised', 'metrics_denoised') with denoise)."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
-    denoise = _check_denoise(denoise, args)
+    denoise = _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args)
     pts, off, cd, nq, metrics, nrm, longest, den = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
                                                                    metric_thresholds, normals, surface_steps, surface_max_step, denoise)
     B = sampled_tokens.shape[0]
@@ -413,6 +457,8 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     if den is not None:                                                                             # in front of the thinned offsets
         d_extra = [den["offsets"].double()] + ([den["cd"]] if den["cd"] is not None else [])
         d_extra += [den["metrics"][k].reshape(-1) for k in PP.METRIC_KEYS] if den["metrics"] is not None else []
+        if den.get("stats") is not None:                                                            # behind everything else of the filter
+            d_extra += [den["stats"].reshape(-1)]
     packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + d_extra
                        + ([t_off.double()] if grid is not None else []))
     host = packed.cpu().tolist()                                                                    # the one host read
@@ -436,6 +482,9 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         if metric_thresholds is not None:
             out["metrics_denoised"] = (PP._metrics_to_host(host[at + 2 * B + 1:], B, len(metric_thresholds))
                                        if den["metrics"] is not None else None)
+        if den.get("stats") is not None:
+            st = at + sum(t.numel() for t in d_extra[:-1])
+            out["denoise_stats"] = [tuple(host[st + 3 * b:st + 3 * b + 3]) for b in range(B)]
     if grid is not None:
         to = [int(v) for v in host[len(host) - (B + 1):]]
         for key, t in (("thinned", t_pts), ("thin_count", t_count), ("thin_first", t_first)):

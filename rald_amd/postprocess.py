@@ -688,6 +688,181 @@ def remove_radius_outliers(points: torch.Tensor, radius: float, min_neighbors: i
     return out[:int(off[1].item())]
 
 
+KNN_MAX_K = 32                                           # the largest k of rald_post_knn_ragged
+
+
+def _knn_args(points, k, grid, max_per_sample, counts, B: Optional[int], chunk, max_radius):
+    """The rules of the k-NN calls beyond the voxel calls' (ValueError, before anything asks where a tensor lives) -> (k, max_radius as
+    the float32 the kernels use with 0.0 for None, max_per_sample, chunk, the grid's three ctypes arrays)."""
+    max_per_sample, chunk = _voxel_args(points, max_per_sample, counts, B, chunk)
+    arrays = _voxel_grid_arg(grid)
+    k = _knn_k(k)
+    return k, _knn_radius(max_radius), max_per_sample, chunk, arrays
+
+
+def _knn_k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or not math.isfinite(k) or int(k) != k or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must be an integer in 1 .. {KNN_MAX_K}")
+    return int(k)
+
+
+def _knn_radius(max_radius) -> float:
+    if max_radius is None:
+        return 0.0
+    if isinstance(max_radius, bool) or not isinstance(max_radius, (int, float)) or not math.isfinite(max_radius) or max_radius <= 0:
+        raise ValueError("max_radius must be None or a finite number > 0")
+    try:
+        r = _f32(float(max_radius))
+    except OverflowError:
+        raise ValueError("max_radius must fit float32") from None
+    if not r > 0 or not math.isfinite(r):
+        raise ValueError("max_radius must fit float32")
+    return r
+
+
+def _knn_ratio(std_ratio) -> float:
+    if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float)) or not math.isfinite(std_ratio) or std_ratio < 0:
+        raise ValueError("std_ratio must be a finite number >= 0")
+    return float(std_ratio)
+
+
+def knn_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, grid, max_per_sample: int, counts: Optional[torch.Tensor] = None,
+               max_radius: Optional[float] = None, return_dist2: bool = True, return_found: bool = False, chunk: int = 0):
+    """The k nearest OTHER rows of every row inside its own cloud of a ragged batch (rald_post_knn_ragged):
+    points [T,3], offsets int64 [B+1] on the device, 1 <= k <= 32, grid = voxel_grid(lo, hi, cell) - any cell edge: the grid only
+    indexes the search and does not show in the result beyond its box; k / 8 to k rows per cell is a good edge -> idx int64 [T,k], laid
+    out like points: slot s of row i is the row (from the cloud's first row) of its s-th candidate in the order (squared float32
+    distance, row index) ascending, so equal distances come by row index and a duplicate is a neighbour at distance 0; -1 from the
+    number of candidates on, and in every slot of a row outside the grid's box (NaN and inf rows included; such rows are nobody's
+    neighbour).  max_radius: only rows with squared distance <= float32(max_radius)^2 are candidates.  Then, for every flag set:
+    dist2 float32 [T,k] (+inf in the empty slots), found int32 [T] (min(k, candidates), -1 outside).  Rows past offsets[B] or behind
+    counts / the bound are unspecified.  counts, max_per_sample, chunk: as voxel_downsample_ragged.  Defined to the bit: the same in
+    every call, batch, chunk and grid.  No host read, no synchronisation; runs on the current stream."""
+    k, max_radius, max_per_sample, chunk, (lo3, v3, dims3) = _knn_args(points, k, grid, max_per_sample, counts,
+                                                                      _offsets_shape(offsets, "offsets"), chunk, max_radius)
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.contiguous()
+    points = _f32c(points)
+    T, dev = points.shape[0], points.device
+    idx = torch.empty(T, k, device=dev, dtype=torch.int64)
+    dist2 = torch.empty(T, k, device=dev, dtype=torch.float32) if return_dist2 else None
+    found = torch.empty(T, device=dev, dtype=torch.int32) if return_found else None
+    if T:                                                                            # no rows: an empty tensor has no address to pass
+        _knn_call(points, offsets, counts, B, T, max_per_sample, lo3, v3, dims3, k, max_radius, idx, dist2, found, chunk)
+    out = (idx,) + tuple(t for t in (dist2, found) if t is not None)
+    return out if len(out) > 1 else idx
+
+
+def _knn_call(points, offsets, counts, B, T, max_per_sample, lo3, v3, dims3, k, max_radius, idx, dist2, found, chunk):
+    dev = points.device
+    L = lib()
+    nbytes = _nbytes(L.rald_op_knn_scratch_bytes(B, T, max_per_sample, chunk) if chunk else L.rald_post_knn_scratch_bytes(B, T, max_per_sample))
+    scratch = _scratch(nbytes, dev)
+    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, k, max_radius, idx.data_ptr(),
+            _opt(dist2), _opt(found), scratch.data_ptr(), nbytes)
+    check(L.rald_op_knn_ragged(*head, chunk, _stream()) if chunk else L.rald_post_knn_ragged(*head, _stream()))
+
+
+def remove_statistical_outliers_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, std_ratio: float, grid, max_per_sample: int,
+                                       counts: Optional[torch.Tensor] = None, max_radius: Optional[float] = None, return_index: bool = False,
+                                       return_mean: bool = False, return_stats: bool = False, chunk: int = 0):
+    """Statistical outlier removal per cloud of a ragged batch (rald_post_statistical_filter_ragged): m[i] is
+    the mean distance (float64) from row i to its k nearest other rows (knn_ragged's, fewer where the cloud or max_radius leaves
+    fewer); over the rows that have at least one, mu is the mean and sigma the deviation (divided by n - 1) of m; a row stays iff it
+    has a neighbour and m[i] <= mu + std_ratio * sigma.  It adapts to the cloud's density, where the radius filter needs a radius.
+    -> (points [T,3], out_offsets int64 [B+1], ...) on the device, sized for the worst case: cloud b's kept rows are rows
+    out_offsets[b] .. out_offsets[b+1]-1 in their ORIGINAL order, bit for bit the input rows; rows past out_offsets[B] are
+    unspecified.  Then, for every flag set: index int64 [T] (per kept row, its row in its cloud), mean float64 [T] (per INPUT row: m,
+    +inf without a neighbour, NaN outside the box), stats float64 [B,3] (mu, sigma, the threshold; NaN for a cloud without a row that
+    counts).  Unlike Open3D's remove_statistical_outlier, k counts OTHER rows.  Arguments as knn_ragged; std_ratio finite, >= 0.
+    Defined to the bit (the sums have one fixed shape): the same in every call, batch, chunk and grid.
+    No host read, no synchronisation; runs on the current stream."""
+    k, max_radius, max_per_sample, chunk, (lo3, v3, dims3) = _knn_args(points, k, grid, max_per_sample, counts,
+                                                                      _offsets_shape(offsets, "offsets"), chunk, max_radius)
+    std_ratio = _knn_ratio(std_ratio)
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.contiguous()
+    points = _f32c(points)
+    T, dev = points.shape[0], points.device
+    out = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    index = torch.empty(T, device=dev, dtype=torch.int64) if return_index else None
+    mean = torch.empty(T, device=dev, dtype=torch.float64) if return_mean else None
+    stats = torch.empty(B, 3, device=dev, dtype=torch.float64) if return_stats else None
+    if T == 0:                                                                       # no rows: an empty tensor has no address to pass
+        out_offsets.zero_()
+        if stats is not None:
+            stats.fill_(float("nan"))
+        return (out, out_offsets) + tuple(t for t in (index, mean, stats) if t is not None)
+    L = lib()
+    nbytes = _nbytes(L.rald_op_statistical_scratch_bytes(B, T, max_per_sample, chunk) if chunk
+                     else L.rald_post_statistical_scratch_bytes(B, T, max_per_sample))
+    scratch = _scratch(nbytes, dev)
+    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, k, max_radius, std_ratio,
+            out.data_ptr(), out_offsets.data_ptr(), _opt(index), _opt(mean), _opt(stats), scratch.data_ptr(), nbytes)
+    check(L.rald_op_statistical_filter_ragged(*head, chunk, _stream()) if chunk else L.rald_post_statistical_filter_ragged(*head, _stream()))
+    return (out, out_offsets) + tuple(t for t in (index, mean, stats) if t is not None)
+
+
+def remove_statistical_outliers(points: torch.Tensor, k: int, std_ratio: float, lo: Optional[Sequence[float]] = None,
+                                hi: Optional[Sequence[float]] = None, cell: Optional[float] = None) -> torch.Tensor:
+    """One cloud [N,3] -> [m,3]: remove_statistical_outliers_ragged's kept rows, in their order.  lo / hi: the box of the search grid
+    (rows outside it are dropped); without them the box is the cloud's own minimum and maximum - that costs one host read of six
+    numbers (and the cloud must be finite); the result's length is a second host read in either case.  cell: the search grid's edge;
+    without it half the edge that gives k rows per cell of the box (about k / 8 rows per cell).  The edge grows until the grid fits 2^31 - 1 cells; the result
+    does not depend on it for a cloud within lo .. hi (the last cell of voxel_grid reaches beyond hi by less than one edge: a row
+    out there is inside for one edge and outside for another)."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [N, 3]")
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi come together")
+    k, std_ratio = _knn_k(k), _knn_ratio(std_ratio)
+    if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0):
+        raise ValueError("cell must be None or a finite number > 0")
+    N = points.shape[0]
+    if lo is not None:
+        grid = _knn_grid(lo, hi, max(N, 1), k, cell)
+    if N == 0:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _need_cuda(points, "points")
+    points = _f32c(points)
+    if lo is None:
+        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
+        grid = _knn_grid(ext[:3], ext[3:], N, k, cell)
+    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    out, off = remove_statistical_outliers_ragged(points, offsets, k, std_ratio, grid, N)
+    return out[:int(off[1].item())]
+
+
+def _knn_grid(lo, hi, n: int, k: int, cell=None):
+    """voxel_grid(lo, hi, edge) for a k-NN search of n rows: edge = `cell`, or HALF the edge at which a cell of the box holds k rows -
+    (volume * k / n)^(1/3) / 2 over the axes that have an extent (1.0 for a box of no extent), about k / 8 rows per cell, the fastest
+    of k / 8, k and 8 k rows per cell where it was measured; then the smallest edge * 2^j (j >= 0) that keeps
+    the grid within 2^31 - 1 cells."""
+    try:
+        voxel_grid(lo, hi, 1.0)                                                        # the box's own rules
+    except ValueError as e:
+        if "cells" not in str(e):
+            raise
+    if cell is None:
+        ext = [float(h) - float(l) for l, h in zip(lo, hi)]
+        ext = [e for e in ext if e > 0]
+        cell = 0.5 * (math.prod(ext) * k / n) ** (1.0 / len(ext)) if ext else 1.0
+        tiny = max(abs(float(x)) for x in list(lo) + list(hi)) * 2.0 ** -20            # never below the coordinates' resolution
+        cell = max(cell, tiny, 1e-30)
+        if not math.isfinite(cell):
+            cell = max(ext)
+    return _radius_grid(lo, hi, cell)
+
+
 def _radius_grid(lo, hi, radius):
     """voxel_grid(lo, hi, edge) with the smallest edge radius * 2^k (k >= 0) that keeps the grid within 2^31 - 1 cells."""
     edge = float(radius)
