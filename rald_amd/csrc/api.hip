@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "ae.h"
+#include "cloud_index.h"
 #include "dit.h"
 #include "lidar.h"
 #include "radar_dsp.h"
@@ -426,8 +427,9 @@ int rald_post_voxel_downsample_ragged(const float* points, const int64_t* offset
                                       int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                       const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
                                       int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, void* stream) {
-    return voxel_downsample_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, out_points,
-                                   out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, 0, (hipStream_t)stream);
+    return voxel_downsample_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                   out_points, out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, 0,
+                                   (hipStream_t)stream);
 }
 int64_t rald_op_voxel_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
     const int64_t n = voxel_scratch_bytes(batch, n_total, max_per_sample, chunk);
@@ -443,8 +445,9 @@ int rald_op_voxel_downsample_ragged(const float* points, const int64_t* offsets,
                                     int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                     const int32_t* dims3_host, float* out_points, int64_t* out_offsets, int32_t* out_count, int64_t* out_first,
                                     int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
-    return voxel_downsample_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, out_points,
-                                   out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+    return voxel_downsample_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                   out_points, out_offsets, out_count, out_first, out_cells, out_inverse, scratch, scratch_bytes, chunk,
+                                   (hipStream_t)stream);
 }
 
 // ---- fixed-radius neighbours and the radius outlier filter ------------------------------
@@ -462,29 +465,30 @@ int rald_post_radius_count_ragged(const float* points, const int64_t* offsets, c
                                   int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                   const int32_t* dims3_host, float radius, int32_t max_count, int32_t* out_count, int64_t* out_nn_idx,
                                   float* out_nn_dist2, void* scratch, int64_t scratch_bytes, void* stream) {
-    return radius_count_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius, max_count,
-                               out_count, out_nn_idx, out_nn_dist2, scratch, scratch_bytes, 0, (hipStream_t)stream);
+    return radius_count_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                               radius, max_count, out_count, out_nn_idx, out_nn_dist2, scratch, scratch_bytes, 0, (hipStream_t)stream);
 }
 int rald_op_radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
                                 int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                 const int32_t* dims3_host, float radius, int32_t max_count, int32_t* out_count, int64_t* out_nn_idx,
                                 float* out_nn_dist2, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
-    return radius_count_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius, max_count,
-                               out_count, out_nn_idx, out_nn_dist2, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+    return radius_count_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                               radius, max_count, out_count, out_nn_idx, out_nn_dist2, scratch, scratch_bytes, chunk, (hipStream_t)stream);
 }
 int rald_post_radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                    const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
                                    int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, void* stream) {
-    return radius_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius,
-                                min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, 0, (hipStream_t)stream);
+    return radius_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                radius, min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, 0, (hipStream_t)stream);
 }
 int rald_op_radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                  const int32_t* dims3_host, float radius, int32_t min_neighbors, float* out_points, int64_t* out_offsets,
                                  int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
-    return radius_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, radius,
-                                min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+    return radius_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                radius, min_neighbors, out_points, out_offsets, out_index, out_count, scratch, scratch_bytes, chunk,
+                                (hipStream_t)stream);
 }
 
 // ---- k nearest neighbours and the statistical outlier filter ------------------------------
@@ -512,23 +516,23 @@ int rald_post_knn_ragged(const float* points, const int64_t* offsets, const int3
                          int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
                          float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes,
                          void* stream) {
-    return knn_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k, max_radius, out_idx,
-                      out_dist2, out_found, scratch, scratch_bytes, 0, (hipStream_t)stream);
+    return knn_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                      k, max_radius, out_idx, out_dist2, out_found, scratch, scratch_bytes, 0, (hipStream_t)stream);
 }
 int rald_op_knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
                        int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
                        float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes,
                        int64_t chunk, void* stream) {
-    return knn_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k, max_radius, out_idx,
-                      out_dist2, out_found, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+    return knn_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                      k, max_radius, out_idx, out_dist2, out_found, scratch, scratch_bytes, chunk, (hipStream_t)stream);
 }
 int rald_post_statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
                                         int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
                                         const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
                                         int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
                                         int64_t scratch_bytes, void* stream) {
-    return statistical_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k,
-                                     max_radius, std_ratio, out_points, out_offsets, out_index, out_mean, out_stats, scratch, scratch_bytes, 0,
+    return statistical_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                     k, max_radius, std_ratio, out_points, out_offsets, out_index, out_mean, out_stats, scratch, scratch_bytes, 0,
                                      (hipStream_t)stream);
 }
 int rald_op_statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
@@ -536,9 +540,9 @@ int rald_op_statistical_filter_ragged(const float* points, const int64_t* offset
                                       const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
                                       int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
                                       int64_t scratch_bytes, int64_t chunk, void* stream) {
-    return statistical_filter_ragged(points, offsets, counts, batch, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k,
-                                     max_radius, std_ratio, out_points, out_offsets, out_index, out_mean, out_stats, scratch, scratch_bytes,
-                                     chunk, (hipStream_t)stream);
+    return statistical_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                     k, max_radius, std_ratio, out_points, out_offsets, out_index, out_mean, out_stats, scratch, scratch_bytes, chunk,
+                                     (hipStream_t)stream);
 }
 
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,

@@ -348,112 +348,32 @@ int fps_ragged(const float* points, const int64_t* offsets, const int32_t* count
                const int64_t* start, const float* scale3_host, int64_t* out_idx, float* out_dist2, void* scratch, int64_t scratch_bytes, int form,
                hipStream_t st);
 
-// ---------------------------------------------------------------- voxel_reduce.hip
-// voxel-grid down-sampling of a ragged batch: one centroid per occupied cell, ascending key; chunk 0 = automatic, else a multiple of 1024
+// ---------------------------------------------------------------- voxel_reduce.hip, radius_search.hip, knn_search.hip
+// the grid-indexed operations on ragged clouds (include/rald_hip.h, DESIGN.md sections 21 - 23).  The layout and the grid come as the
+// two structs of cloud_index.h, which also holds the index, the compaction and the device helpers they share; chunk 0 = automatic, else
+// a multiple of 1024; every *_scratch_bytes is -1 for sizes the calls refuse
+struct RaggedCloud;
+struct GridSpec;
 int voxel_passes(int64_t cells);                   // radix passes of 8 bits for keys 0 .. cells; -1 outside 1 .. 2^31 - 1
+// voxel-grid down-sampling: one centroid per occupied cell, ascending key
 int64_t voxel_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
-int voxel_downsample_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                            int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float* out_points,
-                            int64_t* out_offsets, int32_t* out_count, int64_t* out_first, int32_t* out_cells, int64_t* out_inverse,
-                            void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
-// the key and sort phases alone, for radius_search.hip: the layout and grid rules of voxel_downsample_ragged are checked (messages
-// start with `who`), then vox_keys and the stable radix sort run.  *out: every cloud's (key, row) pairs in ascending key order at its own
-// span of the two arrays, the key `cells` for a row outside the grid.  scratch: voxel_sort_scratch_bytes, 16-byte aligned, the caller's
-// to check (the sort's share comes first in the caller's scratch).  out_inverse (nullable): -1 for every outside row.
-struct VoxelSorted { const unsigned* key; const int* idx; unsigned cells; };
-int64_t voxel_sort_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);   // -1 for sizes the calls refuse
-int voxel_sort_ragged(const char* who, const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense,
-                      int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host,
-                      int64_t* out_inverse, void* scratch, int64_t chunk, hipStream_t st, VoxelSorted* out);
-
-// device parts the two files share
-// the cloud's first row and its number of rows: the segment, capped by counts and by the host bound, clamped into [0, n_total]
-__device__ __forceinline__ int ragged_span(const int64_t* offsets, const int32_t* counts, int64_t n_dense, int64_t n_total,
-                                           int64_t max_per_sample, int b, int64_t& row0) {
-    int64_t len;
-    if (offsets) { row0 = offsets[b]; len = offsets[b + 1] - row0; }
-    else { row0 = (int64_t)b * n_dense; len = n_dense; }
-    if (counts) { const int64_t c = counts[b]; len = c < len ? c : len; }
-    len = len < max_per_sample ? len : max_per_sample;
-    if (row0 < 0 || row0 > n_total) { row0 = 0; len = 0; }
-    len = len < n_total - row0 ? len : n_total - row0;
-    return len > 0 ? (int)len : 0;                           // <= 2^24
-}
-// the cell of a coordinate, in float: floorf(fl(fl(p - lo) / v)), no contraction; monotone in p
-__device__ __forceinline__ float voxel_cell(float p, float lo, float v) {
-#pragma clang fp contract(off)
-    return floorf((p - lo) / v);
-}
-__device__ __forceinline__ unsigned long long vox_lanes_below(int lane) { return (1ull << lane) - 1ull; }
-// exclusive prefix over the workgroup of one value per thread; *total the sum.  sh: NT / 64 ints
-template <int NT>
-__device__ __forceinline__ int vox_block_excl(int v, int* sh, int tid, int* total) {
-    const int lane = tid & 63, w = tid >> 6;
-    int incl = v;
-    for (int s = 1; s < 64; s <<= 1) {
-        const int t = __shfl_up(incl, s);
-        if (lane >= s) incl += t;
-    }
-    if (lane == 63) sh[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < NT / 64; ++i) {
-        const int x = sh[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-
-// ---------------------------------------------------------------- radius_search.hip
-// fixed-radius neighbour counts (and the nearest other row) inside each cloud of a ragged batch, and the radius outlier filter on them
-// (include/rald_hip.h); chunk as above
+int voxel_downsample_ragged(const RaggedCloud& c, const GridSpec& grid, float* out_points, int64_t* out_offsets, int32_t* out_count,
+                            int64_t* out_first, int32_t* out_cells, int64_t* out_inverse, void* scratch, int64_t scratch_bytes, int64_t chunk,
+                            hipStream_t st);
+// fixed-radius neighbour counts (and the nearest other row) inside each cloud, and the radius outlier filter on them
 int64_t radius_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
-int radius_count_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                        int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float radius,
-                        int max_count, int32_t* out_count, int64_t* out_nn_idx, float* out_nn_dist2, void* scratch, int64_t scratch_bytes,
-                        int64_t chunk, hipStream_t st);
-int radius_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                         int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, float radius,
-                         int min_neighbors, float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_count, void* scratch,
-                         int64_t scratch_bytes, int64_t chunk, hipStream_t st);
-// the parts knn_search.hip shares; no argument is checked, the layout is the one the sort has accepted
-// srow[row0 + j] = x, y, z and the row's index (its bits) of sorted position j, 16 bytes a row
-void radius_gather_sorted(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                          int64_t max_per_sample, const int* sidx, float4* srow, hipStream_t st);
-// the compaction in row order: row i of a cloud is kept iff cnt[row0 + i] >= min_neighbors.  scratch: radius_compact_scratch_bytes
-int64_t radius_compact_scratch_bytes(int B, int64_t max_per_sample);
-void radius_compact_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                           int64_t max_per_sample, const int32_t* cnt, int min_neighbors, float* out_points, int64_t* out_offsets,
-                           int64_t* out_index, void* scratch, hipStream_t st);
-__device__ __forceinline__ int rad_clamp(int r, int n) { return r < 0 ? 0 : (r < n ? r : n - 1); }
-// the cell of a scan bound as an index of the grid: the cell function of the keys, clamped in float (a NaN cannot occur: p is finite)
-__device__ __forceinline__ int rad_cell(float p, float lo, float v, int dims) {
-    float cf = voxel_cell(p, lo, v);
-    cf = fminf(fmaxf(cf, 0.f), 2147483520.f);                // the largest float below 2^31
-    const int c = (int)cf;
-    return c < dims ? c : dims - 1;
-}
-__device__ __forceinline__ float rad_d2(const float4& p, const float4& q) {
-#pragma clang fp contract(off)
-    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// ---------------------------------------------------------------- knn_search.hip
-// k nearest other rows inside each cloud of a ragged batch, and the statistical outlier filter on their mean distance
-// (include/rald_hip.h); chunk as above
+int radius_count_ragged(const RaggedCloud& c, const GridSpec& grid, float radius, int max_count, int32_t* out_count, int64_t* out_nn_idx,
+                        float* out_nn_dist2, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+int radius_filter_ragged(const RaggedCloud& c, const GridSpec& grid, float radius, int min_neighbors, float* out_points, int64_t* out_offsets,
+                         int64_t* out_index, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+// k nearest other rows inside each cloud, and the statistical outlier filter on their mean distance
 int64_t knn_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
-int knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-               int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k, float max_radius,
-               int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+int knn_ragged(const RaggedCloud& c, const GridSpec& grid, int k, float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found,
+               void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
 int64_t statistical_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
-int statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                              int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k,
-                              float max_radius, double std_ratio, float* out_points, int64_t* out_offsets, int64_t* out_index,
-                              double* out_mean, double* out_stats, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+int statistical_filter_ragged(const RaggedCloud& c, const GridSpec& grid, int k, float max_radius, double std_ratio, float* out_points,
+                              int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
+                              int64_t scratch_bytes, int64_t chunk, hipStream_t st);
 
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);

@@ -6,24 +6,22 @@
 //   m[i]             float64: sum over the slots in order of sqrt((double)d2) / found; +inf with found = 0, NaN outside
 //   filter           keep row i iff found >= 1 and m[i] <= thr = mu + std_ratio * sigma, mu and sigma over the rows with found >= 1,
 //                    their sums in one fixed shape: 1024-row blocks in row order, a halving tree inside a block, the blocks left to right
-// The index is voxel_sort_ragged's (cell key, row) order and radius_search.hip's sorted copy of the rows.  Launches behind them, all on
+// The index is cloud_index_build's (cell key, row) order and its sorted copy of the rows (cloud_index.h).  Launches behind it, all on
 // one stream, none waits on another workgroup, no atomics:
 //   knn_search       (128 sorted positions, cloud)  one lane per SORTED position; its best-k list lies in LDS ([slot][lane], k * 8 bytes
 //                                                   a lane), ordered by (d2, j).  It scans a first box, then the box of cells
 //                                                   that the termination rule asks for (or, with no bound yet, one twice as wide), only
 //                                                   the rows of the new shell, until the scanned box holds the scan range of
-//                                                   radius_search.hip for a float r with fl(r * r) >= the list's worst d2 (or r2max)
+//                                                   cloud_index.h for a float r with fl(r * r) >= the list's worst d2 (or r2max)
 //                                                   or is the whole grid.  Per x plane of the box ONE lower bound; the walk jumps
 //                                                   over the keys between two columns' z ranges by a lower bound, and over empty planes.
 //   the filter only, over ROW order:
 //   knn_block_sums   (1024 rows, cloud)  the block's tree sum of m (pass 0) or (m - mu)^2 (pass 1), and its rows that count
 //   knn_cloud_stats  one lane per cloud  the blocks left to right: mu (pass 0), sigma and thr (pass 1)
-//   knn_flags        (256 rows, cloud)   1 for a kept row, 0 else, where `found` was; then radius_search.hip's compaction on it
+//   knn_flags        (256 rows, cloud)   1 for a kept row, 0 else, where `found` was; then cloud_index.hip's compaction on that flag
 // Every loop is bounded by the cloud's length (<= max_per_sample, a host value), by the grid's dims, by k or by a constant.  A row
 // index read from the scratch is clamped into the cloud before it addresses anything.
-#include <cmath>
-
-#include "common.h"
+#include "cloud_index.h"
 #include "kernels.h"
 
 namespace rald {
@@ -36,11 +34,9 @@ constexpr int KNN_AHEAD = 4;                                 // rows of a key in
 constexpr int KNN_PASSES = 40;                               // boxes per lane: the own cell, <= 32 doublings, two boxes by the rule
 
 struct KnnArgs {
-    const int64_t* offsets; const int32_t* counts;
-    int64_t n_dense, n_total, max_per_sample, nseg_max;
-    float lo[3], v[3];
-    int dims[3];
-    unsigned cells;
+    RaggedCloud c;
+    CellGrid g;
+    int64_t nseg_max;
     int k;
     float r2lim;                                             // r2max, +inf without max_radius
     int bounded;                                             // max_radius given
@@ -51,27 +47,13 @@ struct KnnArgs {
     double* bsum; int* bcnt;                                 // [batch][nseg_max]
     double* stats;                                           // [batch][4] mu, sigma, thr, n_f
     double* out_stats;                                       // [batch][3], nullable
-    int batch;
+    BlockScan sc;                                            // the filter's compaction
 };
-
-__device__ __forceinline__ int knn_span(const KnnArgs& a, int b, int64_t& row0) {
-    return ragged_span(a.offsets, a.counts, a.n_dense, a.n_total, a.max_per_sample, b, row0);
-}
 
 // (d, j) comes before (wd, wj)
 __device__ __forceinline__ bool knn_before(float d, int j, float wd, int wj) { return d < wd || (d == wd && j < wj); }
 
-// the first position in [lo, hi) with key >= t
-__device__ __forceinline__ int knn_lower_bound(const unsigned* sk, int lo, int hi, unsigned t) {
-    for (int s = 0; s < 32 && lo < hi; ++s) {
-        const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-        if (sk[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// the cells that hold every row with d2 <= w: radius_search.hip's scan range for a float r with fl(r * r) >= w
+// the cells that hold every row with d2 <= w: the scan range for a float r with fl(r * r) >= w
 __device__ __forceinline__ void knn_need(const KnnArgs& a, const float* pc, float w, int* n0, int* n1) {
 #pragma clang fp contract(off)
     float r = sqrtf(w);
@@ -81,12 +63,7 @@ __device__ __forceinline__ void knn_need(const KnnArgs& a, const float* pc, floa
         else r = nextafterf(r, INFINITY);
     }
     if (!ok) r = INFINITY;                                   // the whole grid
-    const float rs = r * (1.f + 9.5367431640625e-07f);       // 2^-20
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        n0[k] = rad_cell(nextafterf(pc[k] - rs, -INFINITY), a.lo[k], a.v[k], a.dims[k]);
-        n1[k] = rad_cell(nextafterf(pc[k] + rs, INFINITY), a.lo[k], a.v[k], a.dims[k]);
-    }
+    scan_range(a.g, pc, scan_reach(r), n0, n1);
 }
 
 __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
@@ -95,7 +72,7 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
     int* J = (int*)(knn_lds + a.k * KNN_T) + threadIdx.x;
     const int b = blockIdx.y;
     int64_t row0;
-    const int n = knn_span(a, b, row0);
+    const int n = ragged_span(a.c, b, row0);
     const int64_t j = (int64_t)blockIdx.x * KNN_T + threadIdx.x;
     if (j >= n) return;                                      // no barrier below
     const unsigned* sk = a.skey + row0;
@@ -106,12 +83,12 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
     const int64_t g = row0 + i;
     const int k = a.k;
     int cnt = -1;
-    if (key < a.cells) {
+    if (key < a.g.cells) {
         cnt = 0;
         float wd = INFINITY;                                 // the list's worst pair once it is full; before, everything enters
         int wj = 0x7fffffff;
         const float pc[3] = {me.x, me.y, me.z};
-        const unsigned d2u = (unsigned)a.dims[2], plane = (unsigned)a.dims[1] * d2u;
+        const unsigned d2u = (unsigned)a.g.dims[2], plane = (unsigned)a.g.dims[1] * d2u;
         int c[3];
         c[0] = (int)(key / plane);
         const unsigned rem = key - (unsigned)c[0] * plane;
@@ -126,7 +103,7 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             c0[t] = c[t] - R > 0 ? (int)(c[t] - R) : 0;
-            c1[t] = c[t] + R < a.dims[t] ? (int)(c[t] + R) : a.dims[t] - 1;
+            c1[t] = c[t] + R < a.g.dims[t] ? (int)(c[t] + R) : a.g.dims[t] - 1;
         }
         // at most 1 + 32 + 2 boxes (the first box, the doublings, two boxes by the rule), so KNN_PASSES never
         // runs out; if a change to the sequence of boxes made it, the row says so with found = -2 instead of a list that is not final
@@ -140,7 +117,7 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
                 int y = c0[1];
                 unsigned cur_lo = pbase + (unsigned)y * d2u + (unsigned)c0[2], cur_hi = cur_lo + zspan;
                 const bool xold = x >= o0[0] && x <= o1[0];
-                q = knn_lower_bound(sk, q, n, cur_lo);
+                q = sorted_lower_bound(sk, q, n, cur_lo);
                 while (q < n) {                              // every turn moves q on, or lands on a row it then takes
                     const unsigned kq = sk[q];
                     if (kq > cur_hi) {
@@ -151,7 +128,7 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
                         y = (int)yk;
                         cur_lo = pbase + yk * d2u + (unsigned)c0[2];
                         cur_hi = cur_lo + zspan;
-                        if (kq < cur_lo) q = knn_lower_bound(sk, q + 1, n, cur_lo);
+                        if (kq < cur_lo) q = sorted_lower_bound(sk, q + 1, n, cur_lo);
                         continue;
                     }
                     // up to KNN_AHEAD rows of this key interval at a time, their loads in flight together (a row far from the rest walks
@@ -202,7 +179,7 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
             // the rule: stop when the scanned box holds the scan range of the bound on the wanted candidates, or the whole grid
             bool whole = true;
 #pragma unroll
-            for (int t = 0; t < 3; ++t) whole = whole && c0[t] == 0 && c1[t] == a.dims[t] - 1;
+            for (int t = 0; t < 3; ++t) whole = whole && c0[t] == 0 && c1[t] == a.g.dims[t] - 1;
             if (whole) { settled = true; break; }
             int m0[3], m1[3];
             const bool bound = cnt == k || a.bounded;
@@ -223,7 +200,7 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
                     const int w0 = c[t] - R > 0 ? (int)(c[t] - R) : 0;
-                    const int w1 = c[t] + R < a.dims[t] ? (int)(c[t] + R) : a.dims[t] - 1;
+                    const int w1 = c[t] + R < a.g.dims[t] ? (int)(c[t] + R) : a.g.dims[t] - 1;
                     m0[t] = bound && m0[t] > w0 ? m0[t] : w0;
                     m1[t] = bound && m1[t] < w1 ? m1[t] : w1;
                 }
@@ -260,7 +237,7 @@ __global__ __launch_bounds__(KNN_SEG) void knn_block_sums(KnnArgs a, int pass) {
     __shared__ int sh[KNN_SEG / 64];
     const int b = blockIdx.y, tid = threadIdx.x;
     int64_t row0;
-    const int n = knn_span(a, b, row0);
+    const int n = ragged_span(a.c, b, row0);
     const int64_t j = (int64_t)blockIdx.x * KNN_SEG + tid;
     if ((int64_t)blockIdx.x * KNN_SEG >= n) return;          // the whole workgroup
     const bool counts = j < n && a.found[row0 + j] >= 1;
@@ -291,9 +268,9 @@ __global__ __launch_bounds__(KNN_SEG) void knn_block_sums(KnnArgs a, int pass) {
 __global__ __launch_bounds__(64) void knn_cloud_stats(KnnArgs a, int pass) {
 #pragma clang fp contract(off)
     const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= a.batch) return;
+    if (b >= a.c.batch) return;
     int64_t row0;
-    const int n = knn_span(a, b, row0);
+    const int n = ragged_span(a.c, b, row0);
     const int nseg = (n + KNN_SEG - 1) / KNN_SEG;
     double* st = a.stats + b * 4;
     double s = 0.0;
@@ -324,109 +301,89 @@ __global__ __launch_bounds__(64) void knn_cloud_stats(KnnArgs a, int pass) {
 __global__ __launch_bounds__(256) void knn_flags(KnnArgs a) {
     const int b = blockIdx.y;
     int64_t row0;
-    const int n = knn_span(a, b, row0);
+    const int n = ragged_span(a.c, b, row0);
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const int64_t g = row0 + j;
     a.found[g] = a.found[g] >= 1 && a.mean[g] <= a.stats[b * 4 + 2] ? 1 : 0;
 }
 
-inline int64_t knn_align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
+void knn_layout(KnnArgs& a, CloudIndex& ix, Carver& s, int64_t chunk) { cloud_index_layout(ix, a.c, s, chunk, true); }
 
-// the checks of both entries that the sort does not make, then the sort, the gather and the search
-int knn_run(const std::string& who, KnnArgs& a, const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense,
-            int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k,
-            float max_radius, int64_t need, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st, char** rest) {
-    RALD_CHECK(lo3_host && v3_host && dims3_host, who + ": null grid (lo3, v3, dims3)");
+void stat_layout(KnnArgs& a, CloudIndex& ix, Carver& s, int64_t chunk) {
+    knn_layout(a, ix, s, chunk);
+    a.nseg_max = (a.c.max_per_sample + KNN_SEG - 1) / KNN_SEG;
+    a.mean = s.take<double>(a.c.n_total);
+    a.found = s.take<int32_t>(a.c.n_total);
+    block_scan_layout(a.sc, a.c, s);
+    a.bsum = s.take<double>(a.c.batch * a.nseg_max);
+    a.bcnt = s.take<int>(a.c.batch * a.nseg_max);
+    a.stats = s.take<double>((int64_t)a.c.batch * 4);
+}
+
+// the checks of both entries that the index does not make, then the scratch by the entry's layout, the index and the search
+template <typename Layout>
+int knn_run(const std::string& who, KnnArgs& a, const RaggedCloud& c, const GridSpec& grid, int k, float max_radius, Layout layout, int64_t need,
+            double* out_mean, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
+    RALD_CHECK(grid.lo && grid.v && grid.dims, who + ": null grid (lo3, v3, dims3)");
     RALD_CHECK(k >= 1 && k <= 32, who + ": k must be 1 .. 32");
     RALD_CHECK(max_radius == 0.f || (std::isfinite(max_radius) && max_radius > 0.f), who + ": max_radius must be 0 (none) or finite and > 0");
-    if (need >= 0) {                                         // else the sort names the size it refuses
-        RALD_CHECK(scratch_bytes >= need, who + ": scratch too small");
-        RALD_CHECK(scratch && (uintptr_t)scratch % 16 == 0, who + ": null or unaligned scratch");
-    }
-    VoxelSorted sorted;
-    RALD_TRY(voxel_sort_ragged(who.c_str(), points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host,
-                               nullptr, scratch, chunk, st, &sorted));
-    a.offsets = offsets; a.counts = counts;
-    a.n_dense = n_dense; a.n_total = n_total; a.max_per_sample = max_per_sample;
-    a.nseg_max = (max_per_sample + KNN_SEG - 1) / KNN_SEG;
-    for (int t = 0; t < 3; ++t) { a.lo[t] = lo3_host[t]; a.v[t] = v3_host[t]; a.dims[t] = dims3_host[t]; }
-    a.cells = sorted.cells;
+    RALD_TRY(scratch_check(who, scratch, scratch_bytes, need));
+    RALD_TRY(cloud_grid_check(who, c, grid, chunk, &a.g));
+    a.c = c;
+    CloudIndex ix;
+    Carver s{(char*)scratch, 0};
+    layout(a, ix, s, chunk);
+    if (out_mean) a.mean = out_mean;
     a.k = k;
     a.bounded = max_radius > 0.f;
     a.r2lim = a.bounded ? max_radius * max_radius : INFINITY;
-    a.skey = sorted.key;
-    a.batch = B;
-    char* s = (char*)scratch + voxel_sort_scratch_bytes(B, n_total, max_per_sample, chunk);
-    float4* srow = (float4*)s; s += knn_align16(n_total * 16);
-    a.srow = srow;
-    *rest = s;
-    radius_gather_sorted(points, offsets, counts, B, n_dense, n_total, max_per_sample, sorted.idx, srow, st);
+    const SortedCloud sorted = cloud_index_build(ix, a.g, nullptr, st);
+    a.skey = sorted.key; a.srow = sorted.rows;
+    const dim3 by_pos((unsigned)((c.max_per_sample + KNN_T - 1) / KNN_T), c.batch);
+    hipLaunchKernelGGL(knn_search, by_pos, dim3(KNN_T), (size_t)k * KNN_T * 8, st, a);
     return 0;
-}
-
-void knn_launch_search(const KnnArgs& a, int B, hipStream_t st) {
-    const dim3 by_pos((unsigned)((a.max_per_sample + KNN_T - 1) / KNN_T), B);
-    hipLaunchKernelGGL(knn_search, by_pos, dim3(KNN_T), (size_t)a.k * KNN_T * 8, st, a);
 }
 
 }  // namespace
 
 int64_t knn_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
-    const int64_t sort = voxel_sort_scratch_bytes(B, n_total, max_per_sample, chunk);
-    if (sort < 0) return -1;
-    return sort + knn_align16(n_total * 16);
+    return layout_bytes<KnnArgs>(B, n_total, max_per_sample, chunk, knn_layout);
 }
 
 int64_t statistical_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
-    const int64_t knn = knn_scratch_bytes(B, n_total, max_per_sample, chunk);
-    if (knn < 0) return -1;
-    const int64_t nseg = (max_per_sample + KNN_SEG - 1) / KNN_SEG;
-    return knn + knn_align16(n_total * 8) + knn_align16(n_total * 4) + radius_compact_scratch_bytes(B, max_per_sample) +
-           knn_align16((int64_t)B * nseg * 8) + knn_align16((int64_t)B * nseg * 4) + knn_align16((int64_t)B * 32);
+    return layout_bytes<KnnArgs>(B, n_total, max_per_sample, chunk, stat_layout);
 }
 
-int knn_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-               int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k, float max_radius,
-               int64_t* out_idx, float* out_dist2, int32_t* out_found, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
-    RALD_CHECK(points && out_idx, "knn_ragged: null pointer (points, out_idx)");
+int knn_ragged(const RaggedCloud& c, const GridSpec& grid, int k, float max_radius, int64_t* out_idx, float* out_dist2, int32_t* out_found,
+               void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
+    RALD_CHECK(c.points && out_idx, "knn_ragged: null pointer (points, out_idx)");
     KnnArgs a{};
     a.out_idx = out_idx; a.out_dist2 = out_dist2; a.out_found = out_found;
-    char* rest;
-    RALD_TRY(knn_run("knn_ragged", a, points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host, k, max_radius,
-                     knn_scratch_bytes(B, n_total, max_per_sample, chunk), scratch, scratch_bytes, chunk, st, &rest));
-    knn_launch_search(a, B, st);
+    RALD_TRY(knn_run("knn_ragged", a, c, grid, k, max_radius, knn_layout, knn_scratch_bytes(c.batch, c.n_total, c.max_per_sample, chunk), nullptr,
+                     scratch, scratch_bytes, chunk, st));
     RALD_HIP(hipGetLastError());
     return 0;
 }
 
-int statistical_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int B, int64_t n_dense, int64_t n_total,
-                              int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int k,
-                              float max_radius, double std_ratio, float* out_points, int64_t* out_offsets, int64_t* out_index,
-                              double* out_mean, double* out_stats, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
-    RALD_CHECK(points && out_points && out_offsets, "statistical_filter_ragged: null pointer (points, out_points, out_offsets)");
+int statistical_filter_ragged(const RaggedCloud& c, const GridSpec& grid, int k, float max_radius, double std_ratio, float* out_points,
+                              int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
+                              int64_t scratch_bytes, int64_t chunk, hipStream_t st) {
+    RALD_CHECK(c.points && out_points && out_offsets, "statistical_filter_ragged: null pointer (points, out_points, out_offsets)");
     RALD_CHECK(std::isfinite(std_ratio) && std_ratio >= 0.0, "statistical_filter_ragged: std_ratio must be finite and >= 0");
     KnnArgs a{};
     a.std_ratio = std_ratio;
     a.out_stats = out_stats;
-    char* s;
-    RALD_TRY(knn_run("statistical_filter_ragged", a, points, offsets, counts, B, n_dense, n_total, max_per_sample, lo3_host, v3_host, dims3_host,
-                     k, max_radius, statistical_scratch_bytes(B, n_total, max_per_sample, chunk), scratch, scratch_bytes, chunk, st, &s));
-    a.mean = out_mean ? out_mean : (double*)s; s += knn_align16(n_total * 8);
-    a.found = (int32_t*)s; s += knn_align16(n_total * 4);
-    void* compact = s; s += radius_compact_scratch_bytes(B, max_per_sample);
-    a.bsum = (double*)s; s += knn_align16((int64_t)B * a.nseg_max * 8);
-    a.bcnt = (int*)s; s += knn_align16((int64_t)B * a.nseg_max * 4);
-    a.stats = (double*)s;
-    knn_launch_search(a, B, st);
-    const dim3 by_seg((unsigned)a.nseg_max, B);
+    RALD_TRY(knn_run("statistical_filter_ragged", a, c, grid, k, max_radius, stat_layout,
+                     statistical_scratch_bytes(c.batch, c.n_total, c.max_per_sample, chunk), out_mean, scratch, scratch_bytes, chunk, st));
+    const dim3 by_seg((unsigned)a.nseg_max, c.batch);
     for (int pass = 0; pass < 2; ++pass) {
         hipLaunchKernelGGL(knn_block_sums, by_seg, dim3(KNN_SEG), 0, st, a, pass);
-        hipLaunchKernelGGL(knn_cloud_stats, dim3((B + 63) / 64), dim3(64), 0, st, a, pass);
+        hipLaunchKernelGGL(knn_cloud_stats, dim3((c.batch + 63) / 64), dim3(64), 0, st, a, pass);
     }
-    hipLaunchKernelGGL(knn_flags, dim3((unsigned)((max_per_sample + 255) / 256), B), dim3(256), 0, st, a);
-    radius_compact_ragged(points, offsets, counts, B, n_dense, n_total, max_per_sample, a.found, 1, out_points, out_offsets, out_index, compact,
-                          st);
+    hipLaunchKernelGGL(knn_flags, dim3((unsigned)((c.max_per_sample + 255) / 256), c.batch), dim3(256), 0, st, a);
+    a.sc.out_offsets = out_offsets;
+    compact_rows_ragged(c, a.sc, a.found, 1, out_points, out_index, st);
     RALD_HIP(hipGetLastError());
     return 0;
 }

@@ -495,6 +495,57 @@ def _voxel_args(points, max_per_sample, counts, B: Optional[int], chunk):
     return int(max_per_sample), int(chunk)
 
 
+def _cloud_batch(points, offsets, counts):
+    """What the grid-indexed ragged calls do once their ValueErrors are behind them: every tensor on the device, points as contiguous
+    float32 -> (points, counts, B, T, the device)."""
+    _need_cuda(points, "points")
+    B = _ragged_batch(offsets, "offsets")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.contiguous()
+    points = _f32c(points)
+    return points, counts, B, points.shape[0], points.device
+
+
+def _cloud_call(entry: str, sizes: str, points, offsets, counts, B: int, T: int, dev, max_per_sample: int, grid3, args, chunk: int) -> None:
+    """rald_op_<entry> with a chunk, rald_post_<entry> without one, on scratch of the matching rald_*_<sizes>_scratch_bytes; args: the
+    entry's own arguments between the grid and the scratch."""
+    L = lib()
+    pre, tail = ("rald_op_", (chunk,)) if chunk else ("rald_post_", ())
+    nbytes = _nbytes(getattr(L, pre + sizes + "_scratch_bytes")(B, T, max_per_sample, *tail))
+    scratch = _scratch(nbytes, dev)
+    check(getattr(L, pre + entry)(points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, *grid3, *args,
+                                  scratch.data_ptr(), nbytes, *tail, _stream()))
+
+
+def _one_cloud_check(points, lo, hi) -> None:
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [N, 3]")
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi come together")
+
+
+def _one_cloud(points, lo, hi, grid_of, run_ragged) -> torch.Tensor:
+    """The one-cloud conveniences behind _one_cloud_check and their own rules: grid_of(lo, hi, rows) on the box given (before anything
+    else, an empty cloud included) or on the cloud's own minimum and maximum (one host read of six numbers), then
+    run_ragged(points, offsets, grid, N) on offsets [0, N] and its first cloud's rows (the second host read)."""
+    N = points.shape[0]
+    if lo is not None:
+        grid = grid_of(lo, hi, max(N, 1))
+    if N == 0:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _need_cuda(points, "points")
+    points = _f32c(points)
+    if lo is None:
+        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
+        grid = grid_of(ext[:3], ext[3:], N)
+    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    out, off = run_ragged(points, offsets, grid, N)
+    return out[:int(off[1].item())]
+
+
 def voxel_downsample_ragged(points: torch.Tensor, offsets: torch.Tensor, grid, max_per_sample: int, counts: Optional[torch.Tensor] = None,
                             return_count: bool = False, return_first: bool = False, return_cells: bool = False, return_inverse: bool = False,
                             chunk: int = 0):
@@ -513,26 +564,16 @@ def voxel_downsample_ragged(points: torch.Tensor, offsets: torch.Tensor, grid, m
     bits in every call and batch.  chunk (tests, tools): the chunk length of the split sort, 0 = automatic; the result does not depend
     on it.  No host read, no synchronisation; runs on the current stream."""
     max_per_sample, chunk = _voxel_args(points, max_per_sample, counts, _offsets_shape(offsets, "offsets"), chunk)
-    lo3, v3, dims3 = _voxel_grid_arg(grid)
-    _need_cuda(points, "points")
-    B = _ragged_batch(offsets, "offsets")
-    if counts is not None:
-        _need_cuda(counts, "counts")
-        counts = counts.contiguous()
-    points = _f32c(points)
-    T, dev = points.shape[0], points.device
+    grid3 = _voxel_grid_arg(grid)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
     out = torch.empty(T, 3, device=dev, dtype=torch.float32)
     out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
     cnt = torch.empty(T, device=dev, dtype=torch.int32) if return_count else None
     first = torch.empty(T, device=dev, dtype=torch.int64) if return_first else None
     cells = torch.empty(T, 3, device=dev, dtype=torch.int32) if return_cells else None
     inverse = torch.empty(T, device=dev, dtype=torch.int64) if return_inverse else None
-    L = lib()
-    nbytes = _nbytes(L.rald_op_voxel_scratch_bytes(B, T, max_per_sample, chunk) if chunk else L.rald_post_voxel_scratch_bytes(B, T, max_per_sample))
-    scratch = _scratch(nbytes, dev)
-    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, out.data_ptr(), out_offsets.data_ptr(),
-            _opt(cnt), _opt(first), _opt(cells), _opt(inverse), scratch.data_ptr(), nbytes)
-    check(L.rald_op_voxel_downsample_ragged(*head, chunk, _stream()) if chunk else L.rald_post_voxel_downsample_ragged(*head, _stream()))
+    _cloud_call("voxel_downsample_ragged", "voxel", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                (out.data_ptr(), out_offsets.data_ptr(), _opt(cnt), _opt(first), _opt(cells), _opt(inverse)), chunk)
     return (out, out_offsets) + tuple(t for t in (cnt, first, cells, inverse) if t is not None)
 
 
@@ -541,27 +582,10 @@ def voxel_downsample(points: torch.Tensor, voxel, lo: Optional[Sequence[float]] 
     counterpart of Open3D's voxel_down_sample on the grid voxel_grid(lo, hi, voxel).  Without lo / hi the grid spans the cloud's own
     minimum and maximum - that costs one host read of six numbers (and the cloud must be finite); the result's length is a second
     host read in either case."""
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
-        raise ValueError("points must be a floating-point tensor [N, 3]")
-    if (lo is None) != (hi is None):
-        raise ValueError("lo and hi come together")
-    if lo is not None:
-        grid = voxel_grid(lo, hi, voxel)
-    else:
-        voxel_grid((0, 0, 0), (0, 0, 0), voxel)                                       # the edge's own rules, before anything is read
-    N = points.shape[0]
-    if N == 0:
-        return points.new_zeros(0, 3, dtype=torch.float32)
-    if N > VOXEL_MAX_POINTS:
-        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
-    _need_cuda(points, "points")
-    points = _f32c(points)
+    _one_cloud_check(points, lo, hi)
     if lo is None:
-        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
-        grid = voxel_grid(ext[:3], ext[3:], voxel)
-    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
-    out, off = voxel_downsample_ragged(points, offsets, grid, N)
-    return out[:int(off[1].item())]
+        voxel_grid((0, 0, 0), (0, 0, 0), voxel)                                       # the edge's own rules, before anything is read
+    return _one_cloud(points, lo, hi, lambda l, h, n: voxel_grid(l, h, voxel), voxel_downsample_ragged)
 
 
 def _radius_args(points, radius, grid, max_per_sample, counts, B: Optional[int], chunk, cap, cap_name: str, cap_min: int):
@@ -584,12 +608,6 @@ def _radius_args(points, radius, grid, max_per_sample, counts, B: Optional[int],
     return radius, int(cap), max_per_sample, chunk, arrays
 
 
-def _radius_scratch(B: int, T: int, max_per_sample: int, chunk: int, dev):
-    L = lib()
-    nbytes = _nbytes(L.rald_op_radius_scratch_bytes(B, T, max_per_sample, chunk) if chunk else L.rald_post_radius_scratch_bytes(B, T, max_per_sample))
-    return _scratch(nbytes, dev), nbytes
-
-
 def radius_neighbor_count_ragged(points: torch.Tensor, offsets: torch.Tensor, radius: float, grid, max_per_sample: int,
                                  counts: Optional[torch.Tensor] = None, max_count: int = 0, return_nearest: bool = False, chunk: int = 0):
     """Neighbours within `radius` inside each cloud of a ragged batch (rald_post_radius_count_ragged): points
@@ -602,25 +620,16 @@ def radius_neighbor_count_ragged(points: torch.Tensor, offsets: torch.Tensor, ra
     [T] (its squared distance, +inf when there is none).  Rows past offsets[B] or behind counts / the bound are unspecified.
     counts, max_per_sample, chunk: as voxel_downsample_ragged.  Defined to the bit: the same in every call, batch, chunk and grid.
     No host read, no synchronisation; runs on the current stream."""
-    radius, max_count, max_per_sample, chunk, (lo3, v3, dims3) = _radius_args(points, radius, grid, max_per_sample, counts,
-                                                                            _offsets_shape(offsets, "offsets"), chunk, max_count, "max_count", 0)
+    radius, max_count, max_per_sample, chunk, grid3 = _radius_args(points, radius, grid, max_per_sample, counts,
+                                                                   _offsets_shape(offsets, "offsets"), chunk, max_count, "max_count", 0)
     if return_nearest and max_count:
         raise ValueError("return_nearest needs max_count = 0")
-    _need_cuda(points, "points")
-    B = _ragged_batch(offsets, "offsets")
-    if counts is not None:
-        _need_cuda(counts, "counts")
-        counts = counts.contiguous()
-    points = _f32c(points)
-    T, dev = points.shape[0], points.device
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
     cnt = torch.empty(T, device=dev, dtype=torch.int32)
     nn_idx = torch.empty(T, device=dev, dtype=torch.int64) if return_nearest else None
     nn_dist2 = torch.empty(T, device=dev, dtype=torch.float32) if return_nearest else None
-    scratch, nbytes = _radius_scratch(B, T, max_per_sample, chunk, dev)
-    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, radius, max_count, cnt.data_ptr(),
-            _opt(nn_idx), _opt(nn_dist2), scratch.data_ptr(), nbytes)
-    L = lib()
-    check(L.rald_op_radius_count_ragged(*head, chunk, _stream()) if chunk else L.rald_post_radius_count_ragged(*head, _stream()))
+    _cloud_call("radius_count_ragged", "radius", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                (radius, max_count, cnt.data_ptr(), _opt(nn_idx), _opt(nn_dist2)), chunk)
     return (cnt, nn_idx, nn_dist2) if return_nearest else cnt
 
 
@@ -634,25 +643,15 @@ def remove_radius_outliers_ragged(points: torch.Tensor, offsets: torch.Tensor, r
     out_offsets[B] are unspecified.  Then, for every flag set: index int64 [T] (per kept row, its row in its cloud), count int32 [T]
     (per INPUT row: min(count, min_neighbors), -1 outside the box).  Arguments as radius_neighbor_count_ragged.
     No host read, no synchronisation; runs on the current stream."""
-    radius, min_neighbors, max_per_sample, chunk, (lo3, v3, dims3) = _radius_args(points, radius, grid, max_per_sample, counts,
-                                                                                _offsets_shape(offsets, "offsets"), chunk, min_neighbors,
-                                                                                "min_neighbors", 1)
-    _need_cuda(points, "points")
-    B = _ragged_batch(offsets, "offsets")
-    if counts is not None:
-        _need_cuda(counts, "counts")
-        counts = counts.contiguous()
-    points = _f32c(points)
-    T, dev = points.shape[0], points.device
+    radius, min_neighbors, max_per_sample, chunk, grid3 = _radius_args(points, radius, grid, max_per_sample, counts,
+                                                                       _offsets_shape(offsets, "offsets"), chunk, min_neighbors, "min_neighbors", 1)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
     out = torch.empty(T, 3, device=dev, dtype=torch.float32)
     out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
     index = torch.empty(T, device=dev, dtype=torch.int64) if return_index else None
     cnt = torch.empty(T, device=dev, dtype=torch.int32) if return_count else None
-    scratch, nbytes = _radius_scratch(B, T, max_per_sample, chunk, dev)
-    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, radius, min_neighbors, out.data_ptr(),
-            out_offsets.data_ptr(), _opt(index), _opt(cnt), scratch.data_ptr(), nbytes)
-    L = lib()
-    check(L.rald_op_radius_filter_ragged(*head, chunk, _stream()) if chunk else L.rald_post_radius_filter_ragged(*head, _stream()))
+    _cloud_call("radius_filter_ragged", "radius", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                (radius, min_neighbors, out.data_ptr(), out_offsets.data_ptr(), _opt(index), _opt(cnt)), chunk)
     return (out, out_offsets) + tuple(t for t in (index, cnt) if t is not None)
 
 
@@ -663,29 +662,13 @@ def remove_radius_outliers(points: torch.Tensor, radius: float, min_neighbors: i
     the cloud's own minimum and maximum - that costs one host read of six numbers (and the cloud must be finite); the result's length
     is a second host read in either case.  Where the box would need more than 2^31 - 1 cells of edge `radius` the cells are made
     larger; the result does not depend on that."""
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
-        raise ValueError("points must be a floating-point tensor [N, 3]")
-    if (lo is None) != (hi is None):
-        raise ValueError("lo and hi come together")
+    _one_cloud_check(points, lo, hi)
     if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
         raise ValueError("radius must be a finite number > 0")
     if isinstance(min_neighbors, bool) or int(min_neighbors) != min_neighbors or min_neighbors < 1:
         raise ValueError("min_neighbors must be an integer >= 1")
-    if lo is not None:
-        grid = _radius_grid(lo, hi, radius)
-    N = points.shape[0]
-    if N == 0:
-        return points.new_zeros(0, 3, dtype=torch.float32)
-    if N > VOXEL_MAX_POINTS:
-        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
-    _need_cuda(points, "points")
-    points = _f32c(points)
-    if lo is None:
-        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
-        grid = _radius_grid(ext[:3], ext[3:], radius)
-    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
-    out, off = remove_radius_outliers_ragged(points, offsets, radius, int(min_neighbors), grid, N)
-    return out[:int(off[1].item())]
+    return _one_cloud(points, lo, hi, lambda l, h, n: _radius_grid(l, h, radius),
+                      lambda p, off, grid, n: remove_radius_outliers_ragged(p, off, radius, int(min_neighbors), grid, n))
 
 
 KNN_MAX_K = 32                                           # the largest k of rald_post_knn_ragged
@@ -738,32 +721,17 @@ def knn_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, grid, max_pe
     dist2 float32 [T,k] (+inf in the empty slots), found int32 [T] (min(k, candidates), -1 outside).  Rows past offsets[B] or behind
     counts / the bound are unspecified.  counts, max_per_sample, chunk: as voxel_downsample_ragged.  Defined to the bit: the same in
     every call, batch, chunk and grid.  No host read, no synchronisation; runs on the current stream."""
-    k, max_radius, max_per_sample, chunk, (lo3, v3, dims3) = _knn_args(points, k, grid, max_per_sample, counts,
-                                                                      _offsets_shape(offsets, "offsets"), chunk, max_radius)
-    _need_cuda(points, "points")
-    B = _ragged_batch(offsets, "offsets")
-    if counts is not None:
-        _need_cuda(counts, "counts")
-        counts = counts.contiguous()
-    points = _f32c(points)
-    T, dev = points.shape[0], points.device
+    k, max_radius, max_per_sample, chunk, grid3 = _knn_args(points, k, grid, max_per_sample, counts, _offsets_shape(offsets, "offsets"), chunk,
+                                                            max_radius)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
     idx = torch.empty(T, k, device=dev, dtype=torch.int64)
     dist2 = torch.empty(T, k, device=dev, dtype=torch.float32) if return_dist2 else None
     found = torch.empty(T, device=dev, dtype=torch.int32) if return_found else None
     if T:                                                                            # no rows: an empty tensor has no address to pass
-        _knn_call(points, offsets, counts, B, T, max_per_sample, lo3, v3, dims3, k, max_radius, idx, dist2, found, chunk)
+        _cloud_call("knn_ragged", "knn", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                    (k, max_radius, idx.data_ptr(), _opt(dist2), _opt(found)), chunk)
     out = (idx,) + tuple(t for t in (dist2, found) if t is not None)
     return out if len(out) > 1 else idx
-
-
-def _knn_call(points, offsets, counts, B, T, max_per_sample, lo3, v3, dims3, k, max_radius, idx, dist2, found, chunk):
-    dev = points.device
-    L = lib()
-    nbytes = _nbytes(L.rald_op_knn_scratch_bytes(B, T, max_per_sample, chunk) if chunk else L.rald_post_knn_scratch_bytes(B, T, max_per_sample))
-    scratch = _scratch(nbytes, dev)
-    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, k, max_radius, idx.data_ptr(),
-            _opt(dist2), _opt(found), scratch.data_ptr(), nbytes)
-    check(L.rald_op_knn_ragged(*head, chunk, _stream()) if chunk else L.rald_post_knn_ragged(*head, _stream()))
 
 
 def remove_statistical_outliers_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, std_ratio: float, grid, max_per_sample: int,
@@ -780,16 +748,10 @@ def remove_statistical_outliers_ragged(points: torch.Tensor, offsets: torch.Tens
     counts).  Unlike Open3D's remove_statistical_outlier, k counts OTHER rows.  Arguments as knn_ragged; std_ratio finite, >= 0.
     Defined to the bit (the sums have one fixed shape): the same in every call, batch, chunk and grid.
     No host read, no synchronisation; runs on the current stream."""
-    k, max_radius, max_per_sample, chunk, (lo3, v3, dims3) = _knn_args(points, k, grid, max_per_sample, counts,
-                                                                      _offsets_shape(offsets, "offsets"), chunk, max_radius)
+    k, max_radius, max_per_sample, chunk, grid3 = _knn_args(points, k, grid, max_per_sample, counts, _offsets_shape(offsets, "offsets"), chunk,
+                                                            max_radius)
     std_ratio = _knn_ratio(std_ratio)
-    _need_cuda(points, "points")
-    B = _ragged_batch(offsets, "offsets")
-    if counts is not None:
-        _need_cuda(counts, "counts")
-        counts = counts.contiguous()
-    points = _f32c(points)
-    T, dev = points.shape[0], points.device
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
     out = torch.empty(T, 3, device=dev, dtype=torch.float32)
     out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
     index = torch.empty(T, device=dev, dtype=torch.int64) if return_index else None
@@ -800,13 +762,8 @@ def remove_statistical_outliers_ragged(points: torch.Tensor, offsets: torch.Tens
         if stats is not None:
             stats.fill_(float("nan"))
         return (out, out_offsets) + tuple(t for t in (index, mean, stats) if t is not None)
-    L = lib()
-    nbytes = _nbytes(L.rald_op_statistical_scratch_bytes(B, T, max_per_sample, chunk) if chunk
-                     else L.rald_post_statistical_scratch_bytes(B, T, max_per_sample))
-    scratch = _scratch(nbytes, dev)
-    head = (points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, lo3, v3, dims3, k, max_radius, std_ratio,
-            out.data_ptr(), out_offsets.data_ptr(), _opt(index), _opt(mean), _opt(stats), scratch.data_ptr(), nbytes)
-    check(L.rald_op_statistical_filter_ragged(*head, chunk, _stream()) if chunk else L.rald_post_statistical_filter_ragged(*head, _stream()))
+    _cloud_call("statistical_filter_ragged", "statistical", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                (k, max_radius, std_ratio, out.data_ptr(), out_offsets.data_ptr(), _opt(index), _opt(mean), _opt(stats)), chunk)
     return (out, out_offsets) + tuple(t for t in (index, mean, stats) if t is not None)
 
 
@@ -818,28 +775,12 @@ def remove_statistical_outliers(points: torch.Tensor, k: int, std_ratio: float, 
     without it half the edge that gives k rows per cell of the box (about k / 8 rows per cell).  The edge grows until the grid fits 2^31 - 1 cells; the result
     does not depend on it for a cloud within lo .. hi (the last cell of voxel_grid reaches beyond hi by less than one edge: a row
     out there is inside for one edge and outside for another)."""
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
-        raise ValueError("points must be a floating-point tensor [N, 3]")
-    if (lo is None) != (hi is None):
-        raise ValueError("lo and hi come together")
+    _one_cloud_check(points, lo, hi)
     k, std_ratio = _knn_k(k), _knn_ratio(std_ratio)
     if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0):
         raise ValueError("cell must be None or a finite number > 0")
-    N = points.shape[0]
-    if lo is not None:
-        grid = _knn_grid(lo, hi, max(N, 1), k, cell)
-    if N == 0:
-        return points.new_zeros(0, 3, dtype=torch.float32)
-    if N > VOXEL_MAX_POINTS:
-        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
-    _need_cuda(points, "points")
-    points = _f32c(points)
-    if lo is None:
-        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
-        grid = _knn_grid(ext[:3], ext[3:], N, k, cell)
-    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
-    out, off = remove_statistical_outliers_ragged(points, offsets, k, std_ratio, grid, N)
-    return out[:int(off[1].item())]
+    return _one_cloud(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell),
+                      lambda p, off, grid, n: remove_statistical_outliers_ragged(p, off, k, std_ratio, grid, n))
 
 
 def _knn_grid(lo, hi, n: int, k: int, cell=None):

@@ -331,6 +331,30 @@ def test_results_do_not_depend_on_stale_state():
     _check_filter(first, ref, 4)
 
 
+# ---- 9. past the scans' 256 lanes --------------------------------------------------------------------------------------------------------------
+@gpu
+def test_257_clouds_cross_the_batch_scan():
+    """257 clouds are one more than the 256 lanes of the scan that makes out_offsets over the batch: its second turn starts from the
+    first one's carry.  Lengths cycle 0, 1, 2, 3, 5 rows; the down-sampler, the radius filter and the statistical filter, every output
+    against its reference."""
+    import test_gpu_radius_filter as RAD
+    import test_gpu_voxel_downsample as VOX
+    import voxel_ref as VREF
+    B = 257
+    off = _offsets([(0, 1, 2, 3, 5)[b % 5] for b in range(B)])
+    p = np.random.RandomState(41).uniform(0.02, 0.98, size=(off[-1], 3)).astype(F32)
+    grid = RREF.cube_grid(0.0, 1.0, 0.5)
+    vox = VREF.voxel_ragged(p, off, *grid, 5)
+    assert vox["offsets"][B] == vox["offsets"][B - 1] + 1 > 256             # the last cloud's one row: a voxel behind the carry
+    VOX._check(VOX._run(p, off, grid, 5), vox, B)
+    rad = RREF.filter_ragged(p, off, grid, 0.5, 1, 5)
+    assert 256 < rad["offsets"][B - 1] == rad["offsets"][B] < off[-1]       # the last cloud's one row has no neighbour: not kept
+    RAD._check_filter(RAD._run(p, off, grid, 0.5, 5, min_neighbors=1), rad, B)
+    stat = REF.statistical_ragged(p, off, grid, 2, 0.5, 5)
+    assert 256 < stat["offsets"][B - 1] == stat["offsets"][B] < off[-1]
+    _check_filter(_run(p, off, grid, 2, 5, std_ratio=0.5), stat, B)
+
+
 # ---- the Python layer ------------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_python_layer():

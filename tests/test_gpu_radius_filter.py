@@ -287,6 +287,35 @@ def test_results_do_not_depend_on_stale_state():
             assert _same(first, _run(p, off, grid, r, 2049, chunk=chunk, **kw))
 
 
+# ---- 8. past the scans' 256 lanes --------------------------------------------------------------------------------------------------------------
+@gpu
+def test_filter_one_cloud_of_257_row_blocks():
+    """262 145 rows are 257 blocks of 1024 rows, one more than the 256 lanes of the per-cloud scan of the block counts: its second turn
+    starts from the first one's carry.  The reference is by construction (the brute force is quadratic): every row has its own integer
+    x in 0 .. 262144 (exact in float32), z = 0, and y = 0 except for a seeded set of lifted rows - single ones and short runs in x - at
+    y = 10, so with radius 1 a row's neighbours are the rows at x - 1 and x + 1 on its own level, at d2 = 1 = r2 exactly.  The rows
+    come in a seeded random order."""
+    from rald_amd.postprocess import voxel_grid
+    n = 256 * 1024 + 1
+    rs = np.random.RandomState(33)
+    lifted = np.zeros(n, bool)
+    lifted[rs.randint(0, n, size=3000)] = True                       # single rows (where two meet, a run)
+    for start, length in zip(rs.randint(0, n - 8, size=2000), rs.randint(2, 8, size=2000)):
+        lifted[start:start + length] = True
+    same = lifted[1:] == lifted[:-1]                                  # x and x + 1 on one level
+    by_x = np.concatenate([[False], same]).astype(np.int32) + np.concatenate([same, [False]])
+    x = rs.permutation(n)
+    p = np.stack([x, np.where(lifted[x], 10.0, 0.0), np.zeros(n)], axis=1).astype(F32)
+    assert np.array_equal(p[:, 0].astype(np.int64), x)
+    count = by_x[x].astype(np.int32)
+    kept = np.nonzero(count >= 2)[0]
+    assert (count == 0).sum() > 500 and (count == 1).sum() > 4000 and 0.9 * n < len(kept) < n - 5000
+    ref = dict(points=p[kept], offsets=np.array([0, len(kept)], np.int64), index=kept.astype(np.int64), count=count, untouched=np.zeros(n, bool))
+    grid = voxel_grid((0, -1, -1), (262144, 11, 1), 1.0)
+    assert grid[2] == (262145, 13, 3)
+    _check_filter(_run(p, [0, n], grid, 1.0, n, min_neighbors=2), ref, 1)
+
+
 # ---- the Python layer ------------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_python_layer():

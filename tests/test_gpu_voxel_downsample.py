@@ -330,6 +330,20 @@ def test_bounds_and_counts():
     _check(_run(p, off, grid, 1200, counts=[300, 1300, 0, 1150, 5]), REF.voxel_ragged(p, off, *grid, 1200, counts=[300, 1300, 0, 1150, 5]), 5)
 
 
+# ---- 8. past the scans' 256 lanes --------------------------------------------------------------------------------------------------------------
+@gpu
+def test_one_cloud_of_257_segment_blocks():
+    """262 145 rows are 257 blocks of 1024 sorted positions, one more than the 256 lanes of the per-cloud scan of the block counts:
+    its second turn starts from the first one's carry.  Rows uniform in a box of 45^3 cells, about three per occupied cell; the
+    automatic chunk."""
+    n = 256 * 1024 + 1
+    p = np.random.RandomState(21).uniform(0.0, 44.0, size=(n, 3)).astype(F32)
+    grid = _grid((0,) * 3, (44,) * 3, 1.0)
+    ref = REF.voxel_ragged(p, [0, n], *grid, n)
+    assert -(-n // 1024) == 257 and 2.5 < ref["count"].mean() < 4 and ref["offsets"][1] > 256 * 256
+    _check(_run(p, [0, n], grid, n), ref, 1)
+
+
 # ---- the Python layer ------------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_python_layer():
@@ -359,7 +373,7 @@ def test_python_layer():
         PP.voxel_downsample_ragged(torch.from_numpy(p), doff, s["grid"], 4099)
 
 
-# ---- 8. the tail -----------------------------------------------------------------------------------------------------------------------------
+# ---- 9. the tail -----------------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_infer_point_clouds_thin():
     """infer_point_clouds(..., thin=0.5) on the 4-frame setup of tests/test_gpu_infer_batch.py (view cone: the cube of +-15.8 m), alone,
