@@ -492,6 +492,72 @@ int rald_op_statistical_filter_ragged(const float* points, const int64_t* offset
                                       const int32_t* dims3_host, int32_t k, float max_radius, double std_ratio, float* out_points,
                                       int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
                                       int64_t scratch_bytes, int64_t chunk, void* stream);
+/* ---- PCA normals, surface variation and covariance eigenvalues of every row from its k nearest other rows, and the normal consistency
+ * of two ragged batches with normals.  Defined to the bit, so the result is the same in every call, in every
+ * batch, for every chunk length and for every grid over the same box:
+ *   Layout, grid, INSIDE, k (1 .. 32), max_radius (0 = none) and the candidates in their order (d2, j) are exactly those of
+ *   rald_post_knn_ragged; `found` is its out_found.
+ *   The NEIGHBOURHOOD of an inside row i with found >= 2 is row i first, then its found neighbours in slot order: m = found + 1 points.
+ *   All arithmetic below is float64 on the fp32 coordinates, one rounded operation at a time, no contraction; every sum starts from
+ *   +0.0 and adds its terms in the order given.
+ *   mean c = (sum of the points in that order) / m, per coordinate.
+ *   moments xx, xy, xz, yy, yz, zz: with d = p - c per coordinate, the sum over the points in that order of dx*dx, dx*dy, dx*dz, dy*dy,
+ *   dy*dz, dz*dz, each divided by m.  A = the symmetric matrix of them (axes 0, 1, 2), V = the identity.
+ *   Eigen-decomposition: SIX sweeps, each the pairs (p, q) = (0, 1), (0, 2), (1, 2) in that order, r the third axis.  A pair whose
+ *   a_pq is exactly 0 is skipped; otherwise
+ *     theta = (a_qq - a_pp) / (2 * a_pq);  t = sgn / (|theta| + sqrt(theta * theta + 1)), sgn = -1 for theta < 0, else +1;
+ *     c = 1 / sqrt(t * t + 1);  s = t * c;  h = t * a_pq;
+ *     a_pp = a_pp - h;  a_qq = a_qq + h;  a_pq = 0;
+ *     (a_rp, a_rq) = (c * a_rp - s * a_rq, s * a_rp + c * a_rq);
+ *     for every row u = 0, 1, 2 of V: (v_up, v_uq) = (c * v_up - s * v_uq, s * v_up + c * v_uq).
+ *   There is no data-dependent stop.  (An overflowing theta gives t = 0: no rotation.)
+ *   The eigenvalues are the diagonal, column u of V the vector of a_uu.  They are ordered ascending by three exchanges of neighbours -
+ *   (0, 1), (1, 2), (0, 1), an exchange iff the first is GREATER - so equal eigenvalues keep the lower column first.  l0 <= l1 <= l2.
+ *   out_eigenvalues fp32 [n_total,3] (may be NULL): l0, l1, l2 rounded to fp32.
+ *   out_curvature fp32 [n_total] (may be NULL): the surface variation l0 / ((l0 + l1) + l2), 0 where that sum is 0.
+ *   out_normals fp32 [n_total,3]: n = the column of l0, every component divided by sqrt((x*x + y*y) + z*z), then the sign, then fp32.
+ *   Sign: with view3_host (3 HOST floats, finite; may be NULL) s = (n0 * (view0 - p0) + n1 * (view1 - p1)) + n2 * (view2 - p2), view
+ *   and the row p converted to float64 first; n is negated iff s < 0.  Without a view, or with s == 0: the component of the largest
+ *   magnitude (the lowest axis on equal magnitudes) is made positive.
+ *   UNDEFINED rows - outside the box, found < 2, found = -2 - get the normal (0, 0, 0) and NaN for curvature and eigenvalues.
+ *   out_found int32 [n_total] (may be NULL) = the search's found.  Rows outside every cloud's span are not written.
+ *   Where this differs from the usual libraries (Open3D estimate_normals with KDTreeSearchParamKNN and
+ *   orient_normals_towards_camera_location, PCL NormalEstimation; stated from their documentation, UNCHECKED): k counts OTHER rows
+ *   here, and the row itself is always part of its neighbourhood, so k = 15 here is knn = 16 there; PCL's curvature is the same
+ *   surface variation; neither defines its eigen-solver, so their normals agree with these only to rounding, and in sign only where
+ *   s is not 0.
+ * The search is rald_post_knn_ragged's, one lane per sorted position; the lane then walks its own list and leaves the six moments and
+ * found per row in the scratch: no [n_total,k] table exists, and the scratch does not depend on k.
+ * Normal consistency of two ragged batches A = pred and B = gt with normals (layout of rald_post_nn_ragged: DEVICE int64 offsets
+ * [batch+1], HOST bounds max_pred / max_gt of the longest segment, trusted as there; n_pred_total / n_gt_total: the rows of the
+ * tensors of either side, which size the scratch, 0 .. 2^31 - 1 - a frame's span is clamped into them):
+ *   for every row a of A: nn(a) = its exact nearest row of B in the same frame (rald_post_nn_ragged's, the lowest index on equal
+ *   distances); term = |(n_a.x * n_nn.x + n_a.y * n_nn.y) + n_a.z * n_nn.z| in float64 on the fp32 normals.  The row COUNTS iff
+ *   both normals are finite and not (0, 0, 0) and the frame has B rows.
+ *   nc(A->B) = the sum of the terms of the counting rows in the fixed sum shape of the statistical filter (the frame's rows in row
+ *   order, a row that does not count as +0.0, blocks of 1024, the halving tree, the blocks left to right) divided by their number;
+ *   NaN for none.
+ *   out_nc float64 [batch,3] = nc(pred->gt), nc(gt->pred), (nc(pred->gt) + nc(gt->pred)) / 2; out_counts int64 [batch,2] = the
+ *   counting rows of either direction.
+ * No atomics, one stream, no kernel waits on another workgroup.  n_total = 0 (and a total of 0) is accepted with non-NULL pointers.
+ * scratch: the *_scratch_bytes of the same sizes, 16-byte aligned, never NULL; -1 (and rald_last_error) for sizes the calls refuse.
+ * Every invalid argument is refused with a status before any GPU work.  rald_op_*: test-facing, with the chunk length of the split
+ * sort as in the radius calls. */
+int64_t rald_post_normals_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample);
+int rald_post_normals_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                             int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host,
+                             int32_t k, float max_radius, const float* view3_host, float* out_normals, float* out_curvature,
+                             float* out_eigenvalues, int32_t* out_found, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t rald_op_normals_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int rald_op_normals_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
+                           int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
+                           float max_radius, const float* view3_host, float* out_normals, float* out_curvature, float* out_eigenvalues,
+                           int32_t* out_found, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
+int64_t rald_post_normal_consistency_scratch_bytes(int32_t batch, int64_t n_pred_total, int64_t n_gt_total, int64_t max_pred, int64_t max_gt);
+int rald_post_normal_consistency_ragged(const float* pred, const float* pred_normals, const int64_t* pred_offsets, int64_t n_pred_total,
+                                        const float* gt, const float* gt_normals, const int64_t* gt_offsets, int64_t n_gt_total, int32_t batch,
+                                        int64_t max_pred, int64_t max_gt, double* out_nc, int64_t* out_counts, void* scratch,
+                                        int64_t scratch_bytes, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

@@ -545,6 +545,46 @@ int rald_op_statistical_filter_ragged(const float* points, const int64_t* offset
                                      (hipStream_t)stream);
 }
 
+// ---- PCA normals and normal consistency ------------------------------------------------
+int64_t rald_post_normals_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample) {
+    const int64_t n = normals_scratch_bytes(batch, n_total, max_per_sample, 0);
+    if (n < 0) set_error(std::string("rald_post_normals_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int64_t rald_op_normals_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t n = normals_scratch_bytes(batch, n_total, max_per_sample, chunk);
+    if (n < 0) set_error(std::string("rald_op_normals_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int rald_post_normals_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                             int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host,
+                             int32_t k, float max_radius, const float* view3_host, float* out_normals, float* out_curvature,
+                             float* out_eigenvalues, int32_t* out_found, void* scratch, int64_t scratch_bytes, void* stream) {
+    return normals_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host}, k,
+                          max_radius, view3_host, out_normals, out_curvature, out_eigenvalues, out_found, scratch, scratch_bytes, 0,
+                          (hipStream_t)stream);
+}
+int rald_op_normals_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense, int64_t n_total,
+                           int64_t max_per_sample, const float* lo3_host, const float* v3_host, const int32_t* dims3_host, int32_t k,
+                           float max_radius, const float* view3_host, float* out_normals, float* out_curvature, float* out_eigenvalues,
+                           int32_t* out_found, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return normals_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host}, k,
+                          max_radius, view3_host, out_normals, out_curvature, out_eigenvalues, out_found, scratch, scratch_bytes, chunk,
+                          (hipStream_t)stream);
+}
+int64_t rald_post_normal_consistency_scratch_bytes(int32_t batch, int64_t n_pred_total, int64_t n_gt_total, int64_t max_pred, int64_t max_gt) {
+    const int64_t n = normal_consistency_scratch_bytes(batch, n_pred_total, n_gt_total, max_pred, max_gt);
+    if (n < 0) set_error("rald_post_normal_consistency_scratch_bytes: batch 1 .. 65535, the totals and the bounds 0 .. 2^31 - 1");
+    return n;
+}
+int rald_post_normal_consistency_ragged(const float* pred, const float* pred_normals, const int64_t* pred_offsets, int64_t n_pred_total,
+                                        const float* gt, const float* gt_normals, const int64_t* gt_offsets, int64_t n_gt_total, int32_t batch,
+                                        int64_t max_pred, int64_t max_gt, double* out_nc, int64_t* out_counts, void* scratch,
+                                        int64_t scratch_bytes, void* stream) {
+    return normal_consistency_ragged(pred, pred_normals, pred_offsets, n_pred_total, gt, gt_normals, gt_offsets, n_gt_total, batch, max_pred,
+                                     max_gt, out_nc, out_counts, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

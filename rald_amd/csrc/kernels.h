@@ -375,6 +375,18 @@ int statistical_filter_ragged(const RaggedCloud& c, const GridSpec& grid, int k,
                               int64_t* out_offsets, int64_t* out_index, double* out_mean, double* out_stats, void* scratch,
                               int64_t scratch_bytes, int64_t chunk, hipStream_t st);
 
+// ---------------------------------------------------------------- cloud_normals.hip
+// PCA normals, surface variation and covariance eigenvalues from the k nearest other rows (the search of knn_search.h, no [n, k] table),
+// and the normal consistency of two ragged batches with normals on cloud_nn_ragged's neighbours
+int64_t normals_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int normals_ragged(const RaggedCloud& c, const GridSpec& grid, int k, float max_radius, const float* view3_host, float* out_normals,
+                   float* out_curvature, float* out_eigenvalues, int32_t* out_found, void* scratch, int64_t scratch_bytes, int64_t chunk,
+                   hipStream_t st);
+int64_t normal_consistency_scratch_bytes(int B, int64_t n_pred_total, int64_t n_gt_total, int64_t max_pred, int64_t max_gt);
+int normal_consistency_ragged(const float* pred, const float* pred_normals, const int64_t* pred_off, int64_t n_pred_total, const float* gt,
+                              const float* gt_normals, const int64_t* gt_off, int64_t n_gt_total, int B, int64_t max_pred, int64_t max_gt,
+                              double* out_nc, int64_t* out_counts, void* scratch, int64_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

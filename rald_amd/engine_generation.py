@@ -153,7 +153,7 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
                               normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                              thin=None, denoise=None, denoise_statistical=None):
+                              thin=None, denoise=None, denoise_statistical=None, normal_consistency=None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
@@ -166,15 +166,20 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
     [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64 [T_cap], cd_denoised float64 [B] or None), and with `metric_thresholds`
     a fifth, the device dict of the denoised clouds' metrics (or None); thin and resample then run on the denoised clouds and their
     indices count its rows.  `denoise_statistical` (see infer_point_clouds) fills the same positions and adds one element behind them:
-    denoise_stats float64 [B,3] (mu, sigma, the threshold)."""
+    denoise_stats float64 [B,3] (mu, sigma, the threshold).  With `normal_consistency` (see infer_point_clouds) two elements follow the
+    normals: normal_consistency float64 [B,3] and the surfaces' estimated normals [B*P,3]."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
     denoise = _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args)
-    pts, off, cd, _, metrics, nrm, longest, den = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
-                                                                  metric_thresholds, normals, surface_steps, surface_max_step, denoise)
+    ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
+    pts, off, cd, _, metrics, nrm, longest, den, ncd = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
+                                                                       metric_thresholds, normals, surface_steps, surface_max_step, denoise,
+                                                                       ncons)
     out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
     if nrm is not None:
         out = out + (nrm,)
+    if ncd is not None:
+        out = out + (ncd["nc"], ncd["normals"])
     if den is not None:
         out = out + (den["points"], den["offsets"], den["index"], den["cd"]) + (() if metric_thresholds is None else (den["metrics"],))
         if den.get("stats") is not None:
@@ -250,6 +255,26 @@ def _check_denoise_statistical(stat, denoise, args):
     return "statistical", k, ratio, _thin_grid(float(cell), args), max_radius
 
 
+def _check_normal_consistency(nc, args, surfaces, normals, surface_steps):
+    """`normal_consistency` (None, or (k, cell)) -> None or (k, grid): the search grid of the surfaces' normals is _thin_grid's box with
+    the cell edge `cell`.  ValueError for anything else, for a cell that gives the box more than 2^31 - 1 cells, and where the tail has
+    no `surfaces` to estimate normals on or no predicted normals (`normals` / `surface_steps`) to compare them with, on the host."""
+    if nc is None:
+        return None
+    try:
+        k, cell = nc
+    except (TypeError, ValueError):
+        raise ValueError("normal_consistency must be None or (k, cell)") from None
+    k = PP._knn_k(k)
+    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0:
+        raise ValueError("normal_consistency: cell must be a finite number > 0")
+    if surfaces is None:
+        raise ValueError("normal_consistency needs surfaces")
+    if not (bool(normals) or int(surface_steps) > 0):
+        raise ValueError("normal_consistency needs the predicted normals: normals=True or surface_steps > 0")
+    return k, _thin_grid(float(cell), args)
+
+
 def _thin(pts: torch.Tensor, off: torch.Tensor, grid, longest: int):
     """The final clouds, one centroid per occupied cell -> (thinned [T,3], thin_offsets [B+1], thin_count [T], thin_first [T]); after
     the metric, which keeps the full cloud."""
@@ -267,12 +292,13 @@ def _resample(pts: torch.Tensor, off: torch.Tensor, k: int, longest: int):
 
 
 def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None, normals=False, surface_steps=0,
-                    surface_max_step=0.05, denoise=None):
+                    surface_max_step=0.05, denoise=None, ncons=None):
     """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None, normals or None) on the device: what
     infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest; then
     the host bound of the longest final cloud; the last element is None, or with `denoise` (_check_denoise's triple, or
     _check_denoise_statistical's tuple) the dict of the denoised clouds: 'points', 'offsets', 'index', and 'cd' / 'metrics' (None where
-    no metric is computed) against the same surfaces; with the statistical filter 'stats' [B,3] as well."""
+    no metric is computed) against the same surfaces; with the statistical filter 'stats' [B,3] as well; behind it None, or with `ncons`
+    (_check_normal_consistency's pair) the dict 'nc' float64 [B,3] and 'normals' [B*P,3], the surfaces' estimated normals."""
     oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
@@ -326,13 +352,18 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         pts, nrm = PP.oriented_points_ragged(kept, grad, p_off, lidar.pc_range, aniso, iso, view_cone_mode=view_cone)
     elif view_cone:
         pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
-    cd, metrics, den = None, None, None
-    if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
+    cd, metrics, den, ncd = None, None, None, None
+    with_metric = surfaces is not None and not _get(args.eval, "skip_eval_metric", False)
+    if with_metric or ncons is not None:
         P = surfaces.shape[1]
         gt = PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso)   # :290
         if view_cone:
             gt = PP.polar2cartesian(gt)
         gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
+    if ncons is not None:                                                                          # the sensor sits at the origin of the final frame
+        gt_nrm = PP.estimate_normals_ragged(gt, gt_off, ncons[0], ncons[1], max(1, int(P)), view=(0.0, 0.0, 0.0))
+        ncd = {"nc": PP.normal_consistency_ragged(pts, nrm, p_off, gt, gt_nrm, gt_off, longest, P)[0], "normals": gt_nrm}
+    if with_metric:
         if metric_thresholds is None:
             cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, longest, P)                         # :320
         else:
@@ -353,7 +384,7 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         elif cd is not None:
             den["metrics"] = PP.cloud_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P, metric_thresholds)
             den["cd"] = den["metrics"]["cd"]
-    return pts, p_off, cd, n_queries, metrics, nrm, longest, den
+    return pts, p_off, cd, n_queries, metrics, nrm, longest, den, ncd
 
 
 def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
@@ -377,7 +408,7 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
                        surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                       thin=None, denoise=None, denoise_statistical=None) -> Dict[str, object]:
+                       thin=None, denoise=None, denoise_statistical=None, normal_consistency=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -436,6 +467,14 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     'denoise_index', 'denoised_normals', 'cd_denoised', 'metrics_denoised' - feeds `thin` and `resample` as `denoise` does, and adds
     'denoise_stats': B triples (mu, sigma, threshold) as floats, NaN for a frame without a row that has a neighbour, carried in the
     one host read.  Given together with `denoise` it raises ValueError: the two filters are not chained.
+    `normal_consistency` (None: today's calls, dict and host read; or (k, cell)): the third standard metric of occupancy-field work
+    beside Chamfer and F-score.  It needs `surfaces` and the predicted normals (`normals` or `surface_steps`), else ValueError before
+    any GPU work.  The ground-truth clouds carry coordinates only, so their normals are estimated first - PCA over each row's k nearest
+    other rows and itself, turned towards the sensor at the origin, from postprocess.estimate_normals_ragged over the
+    box `thin` uses with the search cell `cell` (it does not show in the result) - and then compared with the normals of 'pred' by
+    postprocess.normal_consistency_ragged: |n . n'| with the nearest row of the other cloud, averaged per direction.  Computed on the
+    full cloud, skip_eval_metric or not.  Added: 'normal_consistency', B triples (pred -> gt, gt -> pred, their mean; NaN where no row
+    has two usable normals) carried in the one host read, and 'surface_normals', a list of B tensors [P,3] on the device.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
     'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps, + 'resampled' and
     'resample_index' with resample, + 'thinned', 'thin_count', 'thin_first' (and 'thinned_normals') with thin, + 'denoised',
@@ -443,8 +482,10 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
     denoise = _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args)
-    pts, off, cd, nq, metrics, nrm, longest, den = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
-                                                                   metric_thresholds, normals, surface_steps, surface_max_step, denoise)
+    ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
+    pts, off, cd, nq, metrics, nrm, longest, den, ncd = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
+                                                                        metric_thresholds, normals, surface_steps, surface_max_step, denoise,
+                                                                        ncons)
     B = sampled_tokens.shape[0]
     s_pts, s_off, s_longest = (pts, off, longest) if den is None else (den["points"], den["offsets"], longest)
     if grid is not None:
@@ -460,6 +501,7 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         if den.get("stats") is not None:                                                            # behind everything else of the filter
             d_extra += [den["stats"].reshape(-1)]
     packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + d_extra
+                       + ([ncd["nc"].reshape(-1)] if ncd is not None else [])               # in front of the thinned offsets
                        + ([t_off.double()] if grid is not None else []))
     host = packed.cpu().tolist()                                                                    # the one host read
     o = [int(v) for v in host[:B + 1]]
@@ -485,6 +527,11 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         if den.get("stats") is not None:
             st = at + sum(t.numel() for t in d_extra[:-1])
             out["denoise_stats"] = [tuple(host[st + 3 * b:st + 3 * b + 3]) for b in range(B)]
+    if ncd is not None:
+        at = len(host) - (B + 1 if grid is not None else 0) - 3 * B
+        P = surfaces.shape[1]
+        out["normal_consistency"] = [tuple(host[at + 3 * b:at + 3 * b + 3]) for b in range(B)]
+        out["surface_normals"] = [ncd["normals"][b * P:(b + 1) * P] for b in range(B)]
     if grid is not None:
         to = [int(v) for v in host[len(host) - (B + 1):]]
         for key, t in (("thinned", t_pts), ("thin_count", t_count), ("thin_first", t_first)):

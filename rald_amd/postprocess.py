@@ -11,7 +11,10 @@ completeness, both Chamfer variants, (modified) Hausdorff distance and precision
 ``torch_cluster.fps``), ``voxel_grid`` / ``voxel_downsample*`` (one centroid per occupied cell of a fixed
 grid, the device counterpart of Open3D's ``voxel_down_sample``), and ``radius_neighbor_count_ragged`` /
 ``remove_radius_outliers*`` (neighbours within a radius inside a cloud and the outlier filter on them, the device counterpart of
-Open3D's ``remove_radius_outlier``).
+Open3D's ``remove_radius_outlier``), ``knn_ragged`` / ``remove_statistical_outliers*`` (the k nearest other rows
+inside a cloud and the outlier filter on their mean distance), and ``estimate_normals*`` /
+``normal_consistency*`` (PCA normals, surface variation and eigenvalues from those neighbours, and the normal-consistency metric of two
+clouds with normals).
 """
 from __future__ import annotations
 
@@ -781,6 +784,117 @@ def remove_statistical_outliers(points: torch.Tensor, k: int, std_ratio: float, 
         raise ValueError("cell must be None or a finite number > 0")
     return _one_cloud(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell),
                       lambda p, off, grid, n: remove_statistical_outliers_ragged(p, off, k, std_ratio, grid, n))
+
+
+def _view_arg(view):
+    """view=None -> None; else three finite numbers that fit float32 -> a ctypes float[3]."""
+    import ctypes as C
+    if view is None:
+        return None
+    try:
+        v = [float(x) for x in view]
+    except (TypeError, ValueError):
+        raise ValueError("view must be None or 3 finite numbers") from None
+    if len(v) != 3 or any(not math.isfinite(x) for x in v):
+        raise ValueError("view must be None or 3 finite numbers")
+    try:
+        v = [_f32(x) for x in v]
+    except OverflowError:
+        raise ValueError("view must fit float32") from None
+    if any(not math.isfinite(x) for x in v):
+        raise ValueError("view must fit float32")
+    return (C.c_float * 3)(*v)
+
+
+def estimate_normals_ragged(points: torch.Tensor, offsets: torch.Tensor, k: int, grid, max_per_sample: int, counts: Optional[torch.Tensor] = None,
+                            max_radius: Optional[float] = None, view: Optional[Sequence[float]] = None, return_curvature: bool = False,
+                            return_eigenvalues: bool = False, return_found: bool = False, chunk: int = 0):
+    """PCA normals of every row of a ragged batch from its k nearest OTHER rows and itself (rald_post_normals_ragged, DESIGN.md section
+    24): points [T,3], offsets int64 [B+1] on the device, k, grid, counts, max_per_sample, max_radius and chunk as knn_ragged ->
+    normals float32 [T,3], laid out like points: the unit eigenvector of the smallest eigenvalue of the covariance (float64, a fixed
+    six-sweep Jacobi iteration) of the row and its neighbours, turned towards `view` (3 numbers, the sensor's position in the frame of
+    the points), without a view (or for a view in the row's tangent plane) so that its largest component is positive.  A row outside
+    the grid's box or with fewer than 2 neighbours gets (0, 0, 0).  Then, for every flag set: curvature float32 [T] (the surface
+    variation l0 / (l0 + l1 + l2); NaN for such a row), eigenvalues float32 [T,3] (ascending; NaN), found int32 [T] (knn_ragged's).
+    Unlike Open3D's estimate_normals, k counts OTHER rows: k = 15 here is knn = 16 there.  Rows past offsets[B] or behind counts / the
+    bound are unspecified.  Defined to the bit: the same in every call, batch, chunk and grid; no [T,k] table is built.
+    No host read, no synchronisation; runs on the current stream."""
+    k, max_radius, max_per_sample, chunk, grid3 = _knn_args(points, k, grid, max_per_sample, counts, _offsets_shape(offsets, "offsets"), chunk,
+                                                            max_radius)
+    view3 = _view_arg(view)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
+    normals = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    curv = torch.empty(T, device=dev, dtype=torch.float32) if return_curvature else None
+    eig = torch.empty(T, 3, device=dev, dtype=torch.float32) if return_eigenvalues else None
+    found = torch.empty(T, device=dev, dtype=torch.int32) if return_found else None
+    if T:                                                                            # no rows: an empty tensor has no address to pass
+        _cloud_call("normals_ragged", "normals", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                    (k, max_radius, view3, normals.data_ptr(), _opt(curv), _opt(eig), _opt(found)), chunk)
+    out = (normals,) + tuple(t for t in (curv, eig, found) if t is not None)
+    return out if len(out) > 1 else normals
+
+
+def estimate_normals(points: torch.Tensor, k: int, view: Optional[Sequence[float]] = None, lo: Optional[Sequence[float]] = None,
+                     hi: Optional[Sequence[float]] = None, cell: Optional[float] = None) -> torch.Tensor:
+    """One cloud [N,3] -> its normals float32 [N,3] (estimate_normals_ragged's): the device counterpart of Open3D's estimate_normals
+    followed by orient_normals_towards_camera_location(view).  lo / hi: the box of the search grid (rows outside it get (0, 0, 0));
+    without them the box is the cloud's own minimum and maximum - that costs one host read of six numbers (and the cloud must be
+    finite).  cell: the search grid's edge, as in remove_statistical_outliers; the result does not depend on it."""
+    _one_cloud_check(points, lo, hi)
+    k = _knn_k(k)
+    _view_arg(view)
+    if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0):
+        raise ValueError("cell must be None or a finite number > 0")
+    return _one_cloud(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell),
+                      lambda p, off, grid, n: (estimate_normals_ragged(p, off, k, grid, n, view=view), off))
+
+
+def _normals_of(t, points, what: str) -> None:
+    if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == 3 and t.shape[0] == points.shape[0]):
+        raise ValueError(f"{what} must be a tensor [n, 3] with one row per point")
+
+
+def normal_consistency_ragged(y_pred: torch.Tensor, pred_normals: torch.Tensor, pred_offsets: torch.Tensor, y_gt: torch.Tensor,
+                              gt_normals: torch.Tensor, gt_offsets: torch.Tensor, max_pred: int, max_gt: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Normal consistency per frame of two ragged batches with normals (rald_post_normal_consistency_ragged):
+    for every row of one side, |n . n'| (float64) with the normal n' of its exact nearest row of the other side in the same frame
+    (nearest_neighbors_ragged's), averaged over the rows whose two normals are finite and not zero -> (nc float64 [B,3]: pred -> gt,
+    gt -> pred and their mean; counts int64 [B,2]: the rows that counted), on the device.  NaN where no row counts.  max_pred /
+    max_gt as in cloud_metrics_ragged.  The sums have one fixed shape: a frame's values are the same bits alone and in any batch.
+    No host read, no synchronisation; runs on the current stream."""
+    max_pred, max_gt = _bound(max_pred, "max_pred"), _bound(max_gt, "max_gt")
+    _xyz(y_pred, "y_pred")
+    _xyz(y_gt, "y_gt")
+    _normals_of(pred_normals, y_pred, "pred_normals")
+    _normals_of(gt_normals, y_gt, "gt_normals")
+    B = _ragged_pair(y_pred, pred_offsets, y_gt, gt_offsets, ("y_pred", "pred_offsets", "y_gt", "gt_offsets"))
+    dev = y_pred.device
+    y_pred, y_gt = _f32c(y_pred), _f32c(y_gt).to(dev)
+    pred_normals, gt_normals = _f32c(pred_normals).to(dev), _f32c(gt_normals).to(dev)
+    nc = torch.empty(B, 3, device=dev, dtype=torch.float64)
+    cnt = torch.empty(B, 2, device=dev, dtype=torch.int64)
+    Tp, Tg = y_pred.shape[0], y_gt.shape[0]
+    if Tp == 0 or Tg == 0:                                                           # a side without a row: an empty tensor has no address to pass
+        nc.fill_(float("nan"))
+        cnt.zero_()
+        return nc, cnt
+    nbytes = _nbytes(lib().rald_post_normal_consistency_scratch_bytes(B, Tp, Tg, max_pred, max_gt))
+    scratch = _scratch(nbytes, dev)
+    check(lib().rald_post_normal_consistency_ragged(y_pred.data_ptr(), pred_normals.data_ptr(), pred_offsets.data_ptr(), Tp, y_gt.data_ptr(),
+                                                    gt_normals.data_ptr(), gt_offsets.data_ptr(), Tg, B, max_pred, max_gt, nc.data_ptr(),
+                                                    cnt.data_ptr(), scratch.data_ptr(), nbytes, _stream()))
+    return nc, cnt
+
+
+def normal_consistency(y_pred: torch.Tensor, pred_normals: torch.Tensor, y_gt: torch.Tensor, gt_normals: torch.Tensor) -> dict:
+    """normal_consistency_ragged for one frame, read to the host: {'pred_to_gt', 'gt_to_pred', 'mean'} as Python floats."""
+    _xyz(y_pred, "y_pred")
+    _xyz(y_gt, "y_gt")
+    _need_cuda(y_pred, "y_pred")
+    off = torch.tensor([[0, y_pred.shape[0]], [0, y_gt.shape[0]]], dtype=torch.int64, device=y_pred.device)
+    nc, _ = normal_consistency_ragged(y_pred, pred_normals, off[0], y_gt, gt_normals, off[1], y_pred.shape[0], y_gt.shape[0])
+    host = nc[0].cpu().tolist()
+    return {"pred_to_gt": host[0], "gt_to_pred": host[1], "mean": host[2]}
 
 
 def _knn_grid(lo, hi, n: int, k: int, cell=None):
