@@ -558,6 +558,58 @@ int rald_post_normal_consistency_ragged(const float* pred, const float* pred_nor
                                         const float* gt, const float* gt_normals, const int64_t* gt_offsets, int64_t n_gt_total, int32_t batch,
                                         int64_t max_pred, int64_t max_gt, double* out_nc, int64_t* out_counts, void* scratch,
                                         int64_t scratch_bytes, void* stream);
+/* ---- density clustering (DBSCAN) inside a cloud and the removal of small clusters.  Defined to the bit, so
+ * the result is the same in every call, in every batch, for every chunk length and for every grid the call accepts:
+ *   Layout, grid, INSIDE, d2(i, j) and r2 = fl(eps * eps) are exactly those of rald_post_radius_count_ragged (eps in radius' place: a
+ *   HOST float, finite and > 0, v >= eps on every axis); min_points a HOST value >= 0.
+ *   count[i] = the number of OTHER inside rows j of the same cloud with d2(i, j) <= r2, capped at min_points (-1 outside the box).
+ *   CORE: an inside row with count[i] >= min_points.  min_points counts OTHER rows: Open3D's min_points = m is m - 1 here.  With
+ *   min_points = 0 every inside row is core (Euclidean cluster extraction) and count is 0 for every inside row.
+ *   CLUSTER: a connected component of the graph on the core rows with an edge where d2(i, j) <= r2 (d2 is symmetric in fp32:
+ *   fl(a - b) = -fl(b - a)).  Its representative is its smallest row index; a cloud's clusters are numbered 0 .. C - 1 in ascending
+ *   order of representative.
+ *   BORDER: an inside row that is not core with a core row within r2.  It takes the cluster of the core row of the smallest d2, the
+ *   smallest row index on equal d2 - a rule of the rows alone, where textbook DBSCAN depends on the order of the visit.
+ *   out_labels int32 [n_total], laid out like points: the cluster for core and border rows, -1 for noise (inside, neither), -2 for a
+ *   row outside the box (NaN and +-inf rows included; such rows are nobody's neighbour).  Rows outside every cloud's span (past
+ *   offsets[batch], behind counts or the bound) are not written.
+ *   out_num_clusters int32 [batch] = C.  out_sizes (nullable) int32 [n_total]: cloud b's cluster c at row offsets[b] + c = its core
+ *   AND border rows, 0 at c >= C inside the span, not written outside the spans.  out_count (nullable) int32 [n_total] per row.
+ *   Filter: row i is kept iff label[i] >= 0 and sizes[label[i]] >= min_cluster_size (>= 1); with largest_only != 0 the label must
+ *   also be the cluster of the largest size, the smallest id on equal sizes.  Kept rows come out as the radius filter's: out_points
+ *   (original order, the input row's bits), out_offsets DEVICE int64 [batch+1], optional out_index int64 [n_total]; out_labels int32
+ *   [n_total] per KEPT row = its ORIGINAL cluster id (not renumbered), out_num_clusters int32 [batch] = C before the filter.  Rows
+ *   from out_offsets[batch] on are not written.
+ * Launches behind the index: the capped count (skipped for min_points = 0), a second walk that joins every core row with its core
+ * neighbours of smaller row index in a concurrent union-find and notes a border row's nearest core row, a flatten, the block scans
+ * of the compaction over the flags "core root" (the rank of a root is its cluster id), the labels and sizes, and for the filter an
+ * argmax per cloud, the keep flags, the compaction and a gather of the kept rows' labels.  The union-find hooks the LARGER root under
+ * the smaller with a device-scope compare-and-swap, so parent[x] <= x always, a component's final root is its smallest row, and no
+ * result depends on the order in which workgroups arrive; inside that kernel every read of a parent is a device-scope atomic load.
+ * Integer atomics only (compare-and-swap and min on the parents, add on the sizes); every loop is bounded by the cloud's length.
+ * scratch: rald_post_cluster_scratch_bytes of the same batch, n_total and bound (one size serves both calls), 16-byte aligned, never
+ * NULL; -1 (and rald_last_error) for sizes the calls refuse.  Every invalid argument is refused with a status before any GPU work,
+ * eps before the grid.  rald_op_*: test-facing, with the chunk length of the split sort as in the radius calls. */
+int64_t rald_post_cluster_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample);
+int rald_post_cluster_labels_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                    const int32_t* dims3_host, float eps, int32_t min_points, int32_t* out_labels, int32_t* out_num_clusters,
+                                    int32_t* out_sizes, int32_t* out_count, void* scratch, int64_t scratch_bytes, void* stream);
+int rald_post_cluster_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                    const int32_t* dims3_host, float eps, int32_t min_points, int32_t min_cluster_size, int32_t largest_only,
+                                    float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
+                                    void* scratch, int64_t scratch_bytes, void* stream);
+int64_t rald_op_cluster_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int rald_op_cluster_labels_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                  const int32_t* dims3_host, float eps, int32_t min_points, int32_t* out_labels, int32_t* out_num_clusters,
+                                  int32_t* out_sizes, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
+int rald_op_cluster_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                  const int32_t* dims3_host, float eps, int32_t min_points, int32_t min_cluster_size, int32_t largest_only,
+                                  float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
+                                  void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

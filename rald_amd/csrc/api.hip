@@ -585,6 +585,52 @@ int rald_post_normal_consistency_ragged(const float* pred, const float* pred_nor
                                      max_gt, out_nc, out_counts, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// ---- density clustering and small-cluster removal ----------------------------------------
+int64_t rald_post_cluster_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample) {
+    const int64_t n = cluster_scratch_bytes(batch, n_total, max_per_sample, 0);
+    if (n < 0) set_error(std::string("rald_post_cluster_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int64_t rald_op_cluster_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int64_t chunk) {
+    const int64_t n = cluster_scratch_bytes(batch, n_total, max_per_sample, chunk);
+    if (n < 0) set_error(std::string("rald_op_cluster_scratch_bytes") + kVoxelSizes);
+    return n;
+}
+int rald_post_cluster_labels_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                    const int32_t* dims3_host, float eps, int32_t min_points, int32_t* out_labels, int32_t* out_num_clusters,
+                                    int32_t* out_sizes, int32_t* out_count, void* scratch, int64_t scratch_bytes, void* stream) {
+    return cluster_labels_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                 eps, min_points, out_labels, out_num_clusters, out_sizes, out_count, scratch, scratch_bytes, 0,
+                                 (hipStream_t)stream);
+}
+int rald_op_cluster_labels_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                  const int32_t* dims3_host, float eps, int32_t min_points, int32_t* out_labels, int32_t* out_num_clusters,
+                                  int32_t* out_sizes, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return cluster_labels_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                 eps, min_points, out_labels, out_num_clusters, out_sizes, out_count, scratch, scratch_bytes, chunk,
+                                 (hipStream_t)stream);
+}
+int rald_post_cluster_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                    int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                    const int32_t* dims3_host, float eps, int32_t min_points, int32_t min_cluster_size, int32_t largest_only,
+                                    float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
+                                    void* scratch, int64_t scratch_bytes, void* stream) {
+    return cluster_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                 eps, min_points, min_cluster_size, largest_only, out_points, out_offsets, out_index, out_labels,
+                                 out_num_clusters, scratch, scratch_bytes, 0, (hipStream_t)stream);
+}
+int rald_op_cluster_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, const float* lo3_host, const float* v3_host,
+                                  const int32_t* dims3_host, float eps, int32_t min_points, int32_t min_cluster_size, int32_t largest_only,
+                                  float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
+                                  void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream) {
+    return cluster_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), {lo3_host, v3_host, dims3_host},
+                                 eps, min_points, min_cluster_size, largest_only, out_points, out_offsets, out_index, out_labels,
+                                 out_num_clusters, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

@@ -387,6 +387,16 @@ int normal_consistency_ragged(const float* pred, const float* pred_normals, cons
                               const float* gt_normals, const int64_t* gt_off, int64_t n_gt_total, int B, int64_t max_pred, int64_t max_gt,
                               double* out_nc, int64_t* out_counts, void* scratch, int64_t scratch_bytes, hipStream_t st);
 
+// ---------------------------------------------------------------- cloud_cluster.hip
+// density clustering (DBSCAN) on the radius search's neighbourhoods: labels in a canonical numbering, and the filter that keeps the
+// clusters of at least min_cluster_size rows or the largest one
+int64_t cluster_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int64_t chunk);
+int cluster_labels_ragged(const RaggedCloud& c, const GridSpec& grid, float eps, int min_points, int32_t* out_labels, int32_t* out_num_clusters,
+                          int32_t* out_sizes, int32_t* out_count, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+int cluster_filter_ragged(const RaggedCloud& c, const GridSpec& grid, float eps, int min_points, int min_cluster_size, int largest_only,
+                          float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
+                          void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

@@ -153,7 +153,7 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
                               normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                              thin=None, denoise=None, denoise_statistical=None, normal_consistency=None):
+                              thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None):
     """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
     device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
     read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
@@ -166,11 +166,13 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
     [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64 [T_cap], cd_denoised float64 [B] or None), and with `metric_thresholds`
     a fifth, the device dict of the denoised clouds' metrics (or None); thin and resample then run on the denoised clouds and their
     indices count its rows.  `denoise_statistical` (see infer_point_clouds) fills the same positions and adds one element behind them:
-    denoise_stats float64 [B,3] (mu, sigma, the threshold).  With `normal_consistency` (see infer_point_clouds) two elements follow the
+    denoise_stats float64 [B,3] (mu, sigma, the threshold); `denoise_cluster` (see infer_point_clouds) fills them too and adds two:
+    denoise_labels int32 [T_cap] (per row of `denoised`) and n_clusters int32 [B].  With `normal_consistency` (see infer_point_clouds) two elements follow the
     normals: normal_consistency float64 [B,3] and the surfaces' estimated normals [B*P,3]."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
-    denoise = _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args)
+    denoise = (_check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
+               or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
     ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
     pts, off, cd, _, metrics, nrm, longest, den, ncd = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
                                                                        metric_thresholds, normals, surface_steps, surface_max_step, denoise,
@@ -184,6 +186,8 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
         out = out + (den["points"], den["offsets"], den["index"], den["cd"]) + (() if metric_thresholds is None else (den["metrics"],))
         if den.get("stats") is not None:
             out = out + (den["stats"],)
+        if den.get("labels") is not None:
+            out = out + (den["labels"], den["n_clusters"])
         pts, off = den["points"], den["offsets"]
     if grid is not None:
         thinned = _thin(pts, off, grid, longest)
@@ -253,6 +257,32 @@ def _check_denoise_statistical(stat, denoise, args):
     if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0:
         raise ValueError("denoise_statistical: cell must be a finite number > 0")
     return "statistical", k, ratio, _thin_grid(float(cell), args), max_radius
+
+
+def _check_denoise_cluster(clu, denoise, stat, args):
+    """`denoise_cluster` (None, or (eps, min_points, min_cluster_size) or (eps, min_points, min_cluster_size, largest_only)) -> None or
+    ('cluster', eps, min_points, min_cluster_size, largest_only, grid): the search grid is _thin_grid's box with the cell edge eps.
+    ValueError for anything else, for an eps that gives the box more than 2^31 - 1 cells, and for `denoise` or `denoise_statistical`
+    given as well (chaining the filters is not offered), on the host."""
+    if clu is None:
+        return None
+    if denoise is not None or stat is not None:
+        raise ValueError("denoise_cluster excludes denoise and denoise_statistical")
+    try:
+        eps, min_points, min_size = clu[:3]
+        largest = clu[3] if len(clu) == 4 else False
+        ok = len(clu) in (3, 4)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("denoise_cluster must be None, (eps, min_points, min_cluster_size) or (eps, min_points, min_cluster_size, largest_only)")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or eps <= 0:
+        raise ValueError("denoise_cluster: eps must be a finite number > 0")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, float)) or int(min_points) != min_points or min_points < 0:
+        raise ValueError("denoise_cluster: min_points must be an integer >= 0")
+    if not isinstance(largest, (bool, int)):
+        raise ValueError("denoise_cluster: largest_only must be a bool")
+    return "cluster", float(eps), int(min_points), PP._cluster_size(min_size), bool(largest), _thin_grid(float(eps), args)
 
 
 def _check_normal_consistency(nc, args, surfaces, normals, surface_steps):
@@ -370,15 +400,20 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
             metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
             cd = metrics["cd"]
     if denoise is not None:                                                                        # after the metric, which keeps the full cloud
-        d_stats = None
-        if denoise[0] == "statistical":
+        d_stats, d_lab, d_num = None, None, None
+        if denoise[0] == "cluster":
+            d_pts, d_off, d_idx, d_lab, d_num = PP.remove_small_clusters_ragged(pts, p_off, denoise[1], denoise[2], denoise[3], denoise[5],
+                                                                                max(1, int(longest)), largest_only=denoise[4],
+                                                                                return_index=True, return_labels=True)
+        elif denoise[0] == "statistical":
             d_pts, d_off, d_idx, d_stats = PP.remove_statistical_outliers_ragged(pts, p_off, denoise[1], denoise[2], denoise[3],
                                                                                  max(1, int(longest)), max_radius=denoise[4],
                                                                                  return_index=True, return_stats=True)
         else:
             d_pts, d_off, d_idx = PP.remove_radius_outliers_ragged(pts, p_off, denoise[0], denoise[1], denoise[2], max(1, int(longest)),
                                                                    return_index=True)
-        den = {"points": d_pts, "offsets": d_off, "index": d_idx, "cd": None, "metrics": None, "stats": d_stats}
+        den = {"points": d_pts, "offsets": d_off, "index": d_idx, "cd": None, "metrics": None, "stats": d_stats, "labels": d_lab,
+               "n_clusters": d_num}
         if cd is not None and metric_thresholds is None:
             den["cd"] = PP.cal_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P)
         elif cd is not None:
@@ -408,7 +443,7 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
                        surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                       thin=None, denoise=None, denoise_statistical=None, normal_consistency=None) -> Dict[str, object]:
+                       thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -467,6 +502,15 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     'denoise_index', 'denoised_normals', 'cd_denoised', 'metrics_denoised' - feeds `thin` and `resample` as `denoise` does, and adds
     'denoise_stats': B triples (mu, sigma, threshold) as floats, NaN for a frame without a row that has a neighbour, carried in the
     one host read.  Given together with `denoise` it raises ValueError: the two filters are not chained.
+    `denoise_cluster` (None: today's calls, dict and host read; or (eps, min_points, min_cluster_size) or (eps, min_points,
+    min_cluster_size, largest_only)): small-cluster removal in `denoise`'s place - the frame's rows are clustered by density (a row with
+    at least min_points OTHER rows within eps is a core row, core rows within eps of each other share a cluster, other rows join their
+    nearest core row's) and a row stays iff its cluster has at least min_cluster_size rows, with largest_only only the frame's largest
+    cluster, from postprocess.remove_small_clusters_ragged on the box `thin` uses, cell edge = eps.  It drops the
+    floating blobs that both other filters keep, because inside a blob every row has ordinary neighbours.  It fills the keys of
+    `denoise`, feeds `thin` and `resample` as `denoise` does, and adds 'denoise_labels', a list of int32 [m_b] (per row of 'denoised'
+    its cluster in the frame's numbering before the filter), and 'n_clusters', B ints carried in the one host read.  Given together
+    with `denoise` or `denoise_statistical` it raises ValueError.
     `normal_consistency` (None: today's calls, dict and host read; or (k, cell)): the third standard metric of occupancy-field work
     beside Chamfer and F-score.  It needs `surfaces` and the predicted normals (`normals` or `surface_steps`), else ValueError before
     any GPU work.  The ground-truth clouds carry coordinates only, so their normals are estimated first - PCA over each row's k nearest
@@ -481,7 +525,8 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     'denoise_index' (and 'denoised_normals', 'cd_denoised', 'metrics_denoised') with denoise)."""
     resample = _check_resample(resample)
     grid = _thin_grid(thin, args)
-    denoise = _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args)
+    denoise = (_check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
+               or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
     ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
     pts, off, cd, nq, metrics, nrm, longest, den, ncd = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
                                                                         metric_thresholds, normals, surface_steps, surface_max_step, denoise,
@@ -500,6 +545,8 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         d_extra += [den["metrics"][k].reshape(-1) for k in PP.METRIC_KEYS] if den["metrics"] is not None else []
         if den.get("stats") is not None:                                                            # behind everything else of the filter
             d_extra += [den["stats"].reshape(-1)]
+        if den.get("n_clusters") is not None:
+            d_extra += [den["n_clusters"].double()]
     packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + d_extra
                        + ([ncd["nc"].reshape(-1)] if ncd is not None else [])               # in front of the thinned offsets
                        + ([t_off.double()] if grid is not None else []))
@@ -527,6 +574,10 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         if den.get("stats") is not None:
             st = at + sum(t.numel() for t in d_extra[:-1])
             out["denoise_stats"] = [tuple(host[st + 3 * b:st + 3 * b + 3]) for b in range(B)]
+        if den.get("labels") is not None:
+            st = at + sum(t.numel() for t in d_extra[:-1])
+            out["denoise_labels"] = [den["labels"][do[b]:do[b + 1]] for b in range(B)]
+            out["n_clusters"] = [int(v) for v in host[st:st + B]]
     if ncd is not None:
         at = len(host) - (B + 1 if grid is not None else 0) - 3 * B
         P = surfaces.shape[1]

@@ -674,6 +674,116 @@ def remove_radius_outliers(points: torch.Tensor, radius: float, min_neighbors: i
                       lambda p, off, grid, n: remove_radius_outliers_ragged(p, off, radius, int(min_neighbors), grid, n))
 
 
+def _cluster_size(min_cluster_size) -> int:
+    if isinstance(min_cluster_size, bool) or not isinstance(min_cluster_size, (int, float)) or int(min_cluster_size) != min_cluster_size \
+            or not 1 <= min_cluster_size <= 2 ** 31 - 1:
+        raise ValueError("min_cluster_size must be an integer >= 1")
+    return int(min_cluster_size)
+
+
+def cluster_dbscan_ragged(points: torch.Tensor, offsets: torch.Tensor, eps: float, min_points: int, grid, max_per_sample: int,
+                          counts: Optional[torch.Tensor] = None, return_sizes: bool = False, return_count: bool = False, chunk: int = 0):
+    """Density clustering (DBSCAN) per cloud of a ragged batch (rald_post_cluster_labels_ragged): points [T,3],
+    offsets int64 [B+1] on the device, grid = voxel_grid(lo, hi, voxel) with every cell edge >= eps (the grid only indexes the search
+    and does not show in the result beyond its box) -> (labels int32 [T], num_clusters int32 [B], ...) on the device.
+    A row is CORE iff it lies inside the box and at least min_points (>= 0) OTHER rows of its cloud lie within eps of it
+    (radius_neighbor_count_ragged's count: Open3D's min_points = m is m - 1 here; 0 makes every inside row core, which is Euclidean
+    cluster extraction).  A cluster is a connected component of the core rows under "within eps"; a cloud's clusters are numbered
+    0 .. C-1 in ascending order of their smallest row index.  A row that is not core but has a core row within eps is a BORDER row of
+    the cluster of its NEAREST core row (the smallest row index on equal distances), so the labels are a function of the rows alone.
+    labels, laid out like points: the cluster, -1 for noise, -2 for a row outside the box (NaN and inf rows included; such rows are
+    nobody's neighbour).  Then, for every flag set: sizes int32 [T] (cloud b's cluster c at row offsets[b] + c: its core and border
+    rows; 0 behind the last cluster), count int32 [T] (per row: min(count, min_points), -1 outside the box).  Rows past offsets[B] or
+    behind counts / the bound are unspecified.  counts, max_per_sample, chunk: as voxel_downsample_ragged.  Defined to the bit: the
+    same in every call, batch, chunk and grid.  No host read, no synchronisation; runs on the current stream."""
+    eps, min_points, max_per_sample, chunk, grid3 = _radius_args(points, eps, grid, max_per_sample, counts, _offsets_shape(offsets, "offsets"),
+                                                                 chunk, min_points, "min_points", 0)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
+    labels = torch.empty(T, device=dev, dtype=torch.int32)
+    num = torch.empty(B, device=dev, dtype=torch.int32)
+    sizes = torch.empty(T, device=dev, dtype=torch.int32) if return_sizes else None
+    cnt = torch.empty(T, device=dev, dtype=torch.int32) if return_count else None
+    if T == 0:                                                                       # no rows: an empty tensor has no address to pass
+        num.zero_()
+    else:
+        _cloud_call("cluster_labels_ragged", "cluster", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                    (eps, min_points, labels.data_ptr(), num.data_ptr(), _opt(sizes), _opt(cnt)), chunk)
+    return (labels, num) + tuple(t for t in (sizes, cnt) if t is not None)
+
+
+def remove_small_clusters_ragged(points: torch.Tensor, offsets: torch.Tensor, eps: float, min_points: int, min_cluster_size: int, grid,
+                                 max_per_sample: int, counts: Optional[torch.Tensor] = None, largest_only: bool = False,
+                                 return_index: bool = False, return_labels: bool = False, chunk: int = 0):
+    """Small-cluster removal per cloud of a ragged batch (rald_post_cluster_filter_ragged): a row stays iff
+    cluster_dbscan_ragged gives it a cluster (core or border) of at least min_cluster_size (>= 1) rows, with largest_only only the
+    cloud's largest cluster (the smallest id on equal sizes).  It drops the floating blobs that the radius and the statistical filter
+    keep.  -> (points [T,3], out_offsets int64 [B+1], ...) on the device, sized for the worst case: cloud b's kept rows are rows
+    out_offsets[b] .. out_offsets[b+1]-1 in their ORIGINAL order, bit for bit the input rows; rows past out_offsets[B] are unspecified.
+    Then, for every flag set: index int64 [T] (per kept row, its row in its cloud), (labels int32 [T], num_clusters int32 [B]) (per
+    kept row its cluster in cluster_dbscan_ragged's numbering, NOT renumbered; the clusters before the filter).  Arguments as
+    cluster_dbscan_ragged.  No host read, no synchronisation; runs on the current stream."""
+    eps, min_points, max_per_sample, chunk, grid3 = _radius_args(points, eps, grid, max_per_sample, counts, _offsets_shape(offsets, "offsets"),
+                                                                 chunk, min_points, "min_points", 0)
+    min_cluster_size = _cluster_size(min_cluster_size)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
+    out = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    index = torch.empty(T, device=dev, dtype=torch.int64) if return_index else None
+    labels = torch.empty(T, device=dev, dtype=torch.int32)
+    num = torch.empty(B, device=dev, dtype=torch.int32)
+    if T == 0:
+        out_offsets.zero_()
+        num.zero_()
+    else:
+        _cloud_call("cluster_filter_ragged", "cluster", points, offsets, counts, B, T, dev, max_per_sample, grid3,
+                    (eps, min_points, min_cluster_size, int(bool(largest_only)), out.data_ptr(), out_offsets.data_ptr(), _opt(index),
+                     labels.data_ptr(), num.data_ptr()), chunk)
+    return (out, out_offsets) + ((index,) if return_index else ()) + ((labels, num) if return_labels else ())
+
+
+def _cluster_one_args(points, eps, min_points, lo, hi) -> None:
+    _one_cloud_check(points, lo, hi)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or eps <= 0:
+        raise ValueError("eps must be a finite number > 0")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, float)) or int(min_points) != min_points or min_points < 0:
+        raise ValueError("min_points must be an integer >= 0")
+
+
+def cluster_dbscan(points: torch.Tensor, eps: float, min_points: int, lo: Optional[Sequence[float]] = None,
+                   hi: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """One cloud [N,3] -> labels int32 [N] on the device: cluster_dbscan_ragged's - the device counterpart of Open3D's cluster_dbscan
+    with min_points counting OTHER rows (Open3D's m is m - 1 here), a canonical numbering and -2 for rows outside the box.  lo / hi:
+    the box of the search grid; without them the box is the cloud's own minimum and maximum - that costs one host read of six numbers
+    (and the cloud must be finite).  Where the box would need more than 2^31 - 1 cells of edge eps the cells are made larger; the
+    result does not depend on that."""
+    _cluster_one_args(points, eps, min_points, lo, hi)
+    N = points.shape[0]
+    if lo is not None:
+        grid = _radius_grid(lo, hi, eps)
+    if N == 0:
+        return torch.zeros(0, dtype=torch.int32, device=points.device)
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _need_cuda(points, "points")
+    points = _f32c(points)
+    if lo is None:
+        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
+        grid = _radius_grid(ext[:3], ext[3:], eps)
+    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    return cluster_dbscan_ragged(points, offsets, eps, int(min_points), grid, N)[0]
+
+
+def remove_small_clusters(points: torch.Tensor, eps: float, min_points: int, min_cluster_size: int, largest_only: bool = False,
+                          lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """One cloud [N,3] -> [m,3]: remove_small_clusters_ragged's kept rows, in their order.  lo / hi as cluster_dbscan; the result's
+    length is a second host read in either case."""
+    _cluster_one_args(points, eps, min_points, lo, hi)
+    min_cluster_size = _cluster_size(min_cluster_size)
+    return _one_cloud(points, lo, hi, lambda l, h, n: _radius_grid(l, h, eps),
+                      lambda p, off, grid, n: remove_small_clusters_ragged(p, off, eps, int(min_points), min_cluster_size, grid, n,
+                                                                           largest_only=largest_only))
+
+
 KNN_MAX_K = 32                                           # the largest k of rald_post_knn_ragged
 
 
