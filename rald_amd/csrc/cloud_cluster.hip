@@ -23,8 +23,7 @@
 // Inside clu_link every read of parent is a relaxed device-scope atomic load (the XCDs' L2s are not coherent for plain loads); the
 // kernels behind it may use plain loads.  Every loop is bounded by the cloud's length (<= max_per_sample, a host value), by the
 // grid's dims or by 32; a lane that exhausts a bound stops.  A row index read from the scratch is clamped into the cloud before it
-// addresses anything.  The walk repeats rad_count's loop here, once for both kernels, so radius_search.hip and its code object stay as
-// they are.
+// addresses anything.  clu_count and clu_link walk with radius_walk of cloud_index.h, as rad_count does.
 #include "cloud_index.h"
 #include "kernels.h"
 
@@ -53,31 +52,6 @@ struct ClusterArgs {
     BlockScan num, sc;                                       // the numbering of the core roots, the filter's compaction
 };
 
-// the walk of rad_count (radius_search.hip) around the sorted row `me`: visit(q, row, d2) for every sorted position q of the scan range,
-// in ascending key order, until it returns true
-template <typename Visit>
-__device__ __forceinline__ void clu_walk(const CellGrid& g, float rs, const unsigned* sk, const float4* sr, int n, const float4& me,
-                                         Visit visit) {
-    const float pc[3] = {me.x, me.y, me.z};
-    int c0[3], c1[3];
-    scan_range(g, pc, rs, c0, c1);
-    int from = 0;                                            // the columns come in ascending key order: a column starts behind the last
-    bool done = false;
-    for (int x = c0[0]; x <= c1[0] && !done; ++x) {
-        for (int y = c0[1]; y <= c1[1] && !done; ++y) {
-            const unsigned base = (unsigned)(((int64_t)x * g.dims[1] + y) * g.dims[2]);
-            const unsigned klo = base + (unsigned)c0[2], khi = base + (unsigned)c1[2];
-            int q = sorted_lower_bound(sk, from, n, klo);
-            for (; q < n; ++q) {
-                if (sk[q] > khi) break;
-                const float4 o = sr[q];
-                if (visit(q, o, rad_d2(me, o))) { done = true; break; }
-            }
-            from = q < n ? q : n;
-        }
-    }
-}
-
 __global__ __launch_bounds__(CLU_T) void clu_init(ClusterArgs a) {
     const int b = blockIdx.y;
     int64_t row0;
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(CLU_T) void clu_count(ClusterArgs a) {
         count = 0;
         const float r2 = a.r2;
         const int cap = a.min_points;
-        clu_walk(a.g, a.rs, sk, sr, n, me, [&](int, const float4& o, float d2) {
+        radius_walk(a.g, a.rs, sk, sr, n, me,[&](int, const float4& o, float d2) {
             if (__float_as_int(o.w) != i && d2 <= r2) return ++count == cap;
             return false;
         });
@@ -159,7 +133,7 @@ __global__ __launch_bounds__(CLU_T) void clu_link(ClusterArgs a) {
         const float r2 = a.r2;
         int bestj = -1, top = i;                             // top: a row of i's tree, its root when this lane last saw it
         float best = INFINITY;
-        clu_walk(a.g, a.rs, sk, sr, n, me, [&](int q, const float4& o, float d2) {
+        radius_walk(a.g, a.rs, sk, sr, n, me,[&](int q, const float4& o, float d2) {
             const int jr = rad_clamp(__float_as_int(o.w), n);
             if (jr != i && d2 <= r2 && (all || core[q])) {
                 if (mine) {

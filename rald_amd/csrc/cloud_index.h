@@ -1,6 +1,6 @@
 // What the grid-indexed operations on ragged clouds share (cloud_index.hip; voxel_reduce.hip, radius_search.hip, knn_search.hip use it;
 // DESIGN.md section 21): the layout and the grid as two plain structs, the scratch carver, the spatial index, the compaction in row
-// order, and the device helpers of the cell rule, the scan range and the block scans.
+// order, and the device helpers of the cell rule, the scan range, the radius walk and the block scans.
 #pragma once
 #include <cmath>
 
@@ -149,6 +149,31 @@ __device__ __forceinline__ int sorted_lower_bound(const unsigned* sk, int lo, in
         else hi = mid;
     }
     return lo;
+}
+// the radius walk around the sorted row `me` of a cloud of n rows (sk, sr: its sorted keys and rows; rs = scan_reach(radius)):
+// visit(q, row, d2) for every sorted position q of the scan range, in ascending key order, until it returns true.  Per (x, y) column of
+// the range the z range is one key interval: a lower bound on the sorted keys, then a walk while key <= hi
+template <typename Visit>
+__device__ __forceinline__ void radius_walk(const CellGrid& g, float rs, const unsigned* sk, const float4* sr, int n, const float4& me,
+                                            Visit visit) {
+    const float pc[3] = {me.x, me.y, me.z};
+    int c0[3], c1[3];
+    scan_range(g, pc, rs, c0, c1);
+    int from = 0;                                            // the columns come in ascending key order: a column starts behind the last
+    bool done = false;
+    for (int x = c0[0]; x <= c1[0] && !done; ++x) {
+        for (int y = c0[1]; y <= c1[1] && !done; ++y) {
+            const unsigned base = (unsigned)(((int64_t)x * g.dims[1] + y) * g.dims[2]);
+            const unsigned klo = base + (unsigned)c0[2], khi = base + (unsigned)c1[2];
+            int q = sorted_lower_bound(sk, from, n, klo);
+            for (; q < n; ++q) {
+                if (sk[q] > khi) break;
+                const float4 o = sr[q];
+                if (visit(q, o, rad_d2(me, o))) { done = true; break; }
+            }
+            from = q < n ? q : n;
+        }
+    }
 }
 __device__ __forceinline__ unsigned long long vox_lanes_below(int lane) { return (1ull << lane) - 1ull; }
 // exclusive prefix over the workgroup of one value per thread; *total the sum.  sh: NT / 64 ints

@@ -8,10 +8,9 @@
 // The grid is only the index: cloud_index_build leaves every cloud's cell keys in ascending order and the rows in that order, 16 bytes
 // a row.  One launch behind it, then for the filter the compaction of cloud_index.hip on count >= min_neighbors:
 //   rad_count       (256 sorted positions, cloud)  one lane per SORTED position, so a wave's lanes are neighbours in space and walk the
-//                                                  same lines.  The lane's scan range per axis is that of cloud_index.h for the
-//                                                  radius; per (x, y) column of it the z range is one key interval: a lower bound on
-//                                                  the cloud's sorted keys, then a walk while key <= hi.  The result goes back to the
-//                                                  row's place.
+//                                                  same lines.  The walk is radius_walk of cloud_index.h, which the cluster kernels
+//                                                  share; the visitor here counts, keeps the nearest row and stops at the cap.  The
+//                                                  result goes back to the row's place.
 // No atomics at all.  Every loop is bounded by the cloud's length (<= max_per_sample, a host value), by the grid's dims (host values) or
 // by 32.  A row index read from the scratch is clamped into the cloud before it addresses anything.
 #include "cloud_index.h"
@@ -50,30 +49,14 @@ __global__ __launch_bounds__(RAD_T) void rad_count(RadiusArgs a) {
     float best = INFINITY;
     if (key < a.g.cells) {
         count = 0;
-        const float pc[3] = {me.x, me.y, me.z};
-        int c0[3], c1[3];
-        scan_range(a.g, pc, a.rs, c0, c1);
-        int from = 0;                                        // the columns come in ascending key order: a column starts behind the last
-        bool done = false;
-        for (int x = c0[0]; x <= c1[0] && !done; ++x) {
-            for (int y = c0[1]; y <= c1[1] && !done; ++y) {
-                const unsigned base = (unsigned)(((int64_t)x * a.g.dims[1] + y) * a.g.dims[2]);
-                const unsigned klo = base + (unsigned)c0[2], khi = base + (unsigned)c1[2];
-                int q = sorted_lower_bound(sk, from, n, klo);
-                for (; q < n; ++q) {
-                    if (sk[q] > khi) break;
-                    const float4 o = sr[q];
-                    const int jr = __float_as_int(o.w);
-                    const float d2 = rad_d2(me, o);
-                    if (jr != i && d2 <= a.r2) {
-                        ++count;
-                        if (d2 < best || (d2 == best && jr < bestj)) { best = d2; bestj = jr; }
-                        if (count == a.cap) { done = true; break; }
-                    }
-                }
-                from = q < n ? q : n;
-            }
-        }
+        const float r2 = a.r2;
+        const int cap = a.cap;
+        radius_walk(a.g, a.rs, sk, sr, n, me, [&](int, const float4& o, float d2) {
+            const int jr = __float_as_int(o.w);
+            if (jr == i || !(d2 <= r2)) return false;
+            if (d2 < best || (d2 == best && jr < bestj)) { best = d2; bestj = jr; }
+            return ++count == cap;
+        });
     }
     a.cnt[g] = count;
     if (a.nn_idx) a.nn_idx[g] = bestj;

@@ -5,8 +5,8 @@ inference tail (:250-322: query generation, helper points, refine pass, Chamfer)
 Data loading and PLY writing are out of scope."""
 from __future__ import annotations
 
-import math
-from typing import Callable, Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -14,6 +14,7 @@ import torch
 from . import distributed as D
 from . import postprocess as PP
 from . import query_points as QP
+from .postprocess import _positive, _whole
 
 
 @torch.no_grad()
@@ -154,46 +155,73 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
                               normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
                               thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None):
-    """infer_point_clouds without its readback: -> (points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None), all on the
-    device; frame b's prediction is points[offsets[b]:offsets[b+1]].  With a device generator (`rng`) or explicit `draws` nothing is
-    read to the host and the device is not synchronised.  With `metric_thresholds` (a sequence of distances, () included) a fourth
-    element follows: the device dict of postprocess.cloud_metrics_ragged (None where no metric is computed), whose 'cd' is the third.
-    With `normals` or `surface_steps` (see infer_point_clouds) the unit normals [T_cap,3] follow.  With `resample=k` (see
-    infer_point_clouds) the last two elements are the resampled clouds [B,k,3] and their row indices [B,k].  With `thin` (see
-    infer_point_clouds) four elements come before those two: (thinned [T_cap,3], thin_offsets int64 [B+1], thin_count int32 [T_cap],
-    thin_first int64 [T_cap]) - frame b's voxels are rows thin_offsets[b] .. thin_offsets[b+1]-1 - and the resample indices count rows
-    of the frame's thinned cloud.  With `denoise` (see infer_point_clouds) four elements come before those of `thin`: (denoised
-    [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64 [T_cap], cd_denoised float64 [B] or None), and with `metric_thresholds`
-    a fifth, the device dict of the denoised clouds' metrics (or None); thin and resample then run on the denoised clouds and their
-    indices count its rows.  `denoise_statistical` (see infer_point_clouds) fills the same positions and adds one element behind them:
-    denoise_stats float64 [B,3] (mu, sigma, the threshold); `denoise_cluster` (see infer_point_clouds) fills them too and adds two:
-    denoise_labels int32 [T_cap] (per row of `denoised`) and n_clusters int32 [B].  With `normal_consistency` (see infer_point_clouds) two elements follow the
-    normals: normal_consistency float64 [B,3] and the surfaces' estimated normals [B*P,3]."""
-    resample = _check_resample(resample)
-    grid = _thin_grid(thin, args)
-    denoise = (_check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
-               or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
-    ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
-    pts, off, cd, _, metrics, nrm, longest, den, ncd = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
-                                                                       metric_thresholds, normals, surface_steps, surface_max_step, denoise,
-                                                                       ncons)
-    out = (pts, off, cd) if metric_thresholds is None else (pts, off, cd, metrics)
-    if nrm is not None:
-        out = out + (nrm,)
-    if ncd is not None:
-        out = out + (ncd["nc"], ncd["normals"])
+    """infer_point_clouds (see there for the options) without its readback -> a tuple, all on the device, in this order:
+    points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None: frame b's prediction is points[offsets[b]:offsets[b+1]];
+    with `metric_thresholds` (a sequence of distances, () included) the dict of postprocess.cloud_metrics_ragged (None where no metric
+    is computed), whose 'cd' is the third element; with `normals` or `surface_steps` the unit normals [T_cap,3]; with
+    `normal_consistency` normal_consistency float64 [B,3] and the surfaces' estimated normals [B*P,3];
+    with `denoise`, `denoise_statistical` or `denoise_cluster`: denoised [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64
+    [T_cap], cd_denoised float64 [B] or None and, with `metric_thresholds`, the dict of the denoised clouds' metrics (or None); behind
+    them denoise_stats float64 [B,3] (mu, sigma, the threshold) of the statistical filter, or denoise_labels int32 [T_cap] (per row of
+    `denoised`) and n_clusters int32 [B] of the cluster filter; thin and resample then run on the denoised clouds, their indices count its rows;
+    with `thin`: thinned [T_cap,3], thin_offsets int64 [B+1], thin_count int32 [T_cap], thin_first int64 [T_cap] - frame b's voxels are
+    rows thin_offsets[b] .. thin_offsets[b+1]-1; with `resample=k`, last, the resampled clouds [B,k,3] and their row indices [B,k]
+    (rows of the frame's thinned cloud with `thin`).  With a device generator (`rng`) or explicit `draws` nothing is read to the host
+    and the device is not synchronised."""
+    t, thinned, resampled = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals,
+                                            surface_steps, surface_max_step, resample, thin, denoise, denoise_statistical, normal_consistency,
+                                            denoise_cluster)
+    with_metrics, den = metric_thresholds is not None, t.denoised
+    out = (t.points, t.offsets, t.cd) + ((t.metrics,) if with_metrics else ()) + ((t.normals,) if t.normals is not None else ()) + (t.ncons or ())
     if den is not None:
-        out = out + (den["points"], den["offsets"], den["index"], den["cd"]) + (() if metric_thresholds is None else (den["metrics"],))
-        if den.get("stats") is not None:
-            out = out + (den["stats"],)
-        if den.get("labels") is not None:
-            out = out + (den["labels"], den["n_clusters"])
-        pts, off = den["points"], den["offsets"]
-    if grid is not None:
-        thinned = _thin(pts, off, grid, longest)
-        out = out + thinned
-        pts, off, longest = thinned[0], thinned[1], _thin_bound(longest, grid)
-    return out + _resample(pts, off, resample, longest) if resample is not None else out
+        out += (den.points, den.offsets, den.index, den.cd) + ((den.metrics,) if with_metrics else ())
+        out += ((den.stats,) if den.stats is not None else ()) + ((den.labels, den.n_clusters) if den.labels is not None else ())
+    return out + (thinned or ()) + (resampled or ())
+
+
+@dataclass
+class _Denoised:
+    """The tail's clouds behind one of the three filters, on the device: the kept rows, their offsets int64 [B+1], their rows in the full
+    cloud, cd / metrics against the same surfaces; stats float64 [B,3] (statistical), labels int32 per kept row, n_clusters int32 [B] (cluster)."""
+    points: torch.Tensor; offsets: torch.Tensor; index: torch.Tensor; cd: Optional[torch.Tensor] = None; metrics: Optional[dict] = None
+    stats: Optional[torch.Tensor] = None; labels: Optional[torch.Tensor] = None; n_clusters: Optional[torch.Tensor] = None
+
+
+@dataclass
+class _Tail:
+    """The batched tail's results on the device: the final clouds, their offsets int64 [B+1], cd float64 [B], the frames' query counts int64
+    [B], cloud_metrics_ragged's dict, the unit normals, the host bound of the longest final cloud, the denoised clouds, the pair (normal
+    consistency float64 [B,3], the surfaces' estimated normals); None for what was not asked for or not computed."""
+    points: torch.Tensor; offsets: torch.Tensor; cd: Optional[torch.Tensor]; n_queries: torch.Tensor
+    metrics: Optional[dict]; normals: Optional[torch.Tensor]; longest: int; denoised: Optional[_Denoised]; ncons: Optional[tuple]
+
+
+# the three filters as _check_denoise, _check_denoise_statistical and _check_denoise_cluster return them, plain tuples with names: each
+# run(points, offsets, bound) -> the _Denoised clouds, with the kept rows' indices and what its filter adds
+class _RadiusFilter(NamedTuple):
+    radius: float; min_neighbors: int; grid: tuple
+
+    def run(self, points, offsets, bound) -> _Denoised:
+        return _Denoised(*PP.remove_radius_outliers_ragged(points, offsets, self.radius, self.min_neighbors, self.grid, bound, return_index=True))
+
+
+class _StatisticalFilter(NamedTuple):
+    kind: str; k: int; std_ratio: float; grid: tuple; max_radius: Optional[float]
+
+    def run(self, points, offsets, bound) -> _Denoised:
+        pts, off, idx, stats = PP.remove_statistical_outliers_ragged(points, offsets, self.k, self.std_ratio, self.grid, bound,
+                                                                     max_radius=self.max_radius, return_index=True, return_stats=True)
+        return _Denoised(pts, off, idx, stats=stats)
+
+
+class _ClusterFilter(NamedTuple):
+    kind: str; eps: float; min_points: int; min_cluster_size: int; largest_only: bool; grid: tuple
+
+    def run(self, points, offsets, bound) -> _Denoised:
+        pts, off, idx, labels, num = PP.remove_small_clusters_ragged(points, offsets, self.eps, self.min_points, self.min_cluster_size,
+                                                                     self.grid, bound, largest_only=self.largest_only, return_index=True,
+                                                                     return_labels=True)
+        return _Denoised(pts, off, idx, labels=labels, n_clusters=num)
 
 
 def _check_resample(resample) -> Optional[int]:
@@ -227,11 +255,19 @@ def _check_denoise(denoise, args):
         radius, k = denoise
     except (TypeError, ValueError):
         raise ValueError("denoise must be None or (radius, min_neighbors)") from None
-    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
-        raise ValueError("denoise: radius must be a finite number > 0")
-    if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or k < 1:
-        raise ValueError("denoise: min_neighbors must be an integer >= 1")
-    return float(radius), int(k), _thin_grid(float(radius), args)
+    radius = _positive(radius, "denoise: radius must be a finite number > 0")
+    return _RadiusFilter(radius, _whole(k, 1, None, "denoise: min_neighbors must be an integer >= 1"), _thin_grid(radius, args))
+
+
+def _three_or_four(option, fourth, message: str):
+    """A sequence of three or four -> its four values, `fourth` where it has three; ValueError(message) for anything else."""
+    try:
+        a, b, c = option[:3]
+        if len(option) in (3, 4):
+            return a, b, c, (option[3] if len(option) == 4 else fourth)
+    except (TypeError, ValueError):
+        pass
+    raise ValueError(message)
 
 
 def _check_denoise_statistical(stat, denoise, args):
@@ -242,21 +278,14 @@ def _check_denoise_statistical(stat, denoise, args):
         return None
     if denoise is not None:
         raise ValueError("denoise and denoise_statistical exclude each other")
-    try:
-        k, ratio, cell = stat[:3]
-        max_radius = stat[3] if len(stat) == 4 else None
-        ok = len(stat) in (3, 4)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError("denoise_statistical must be None, (k, std_ratio, cell) or (k, std_ratio, cell, max_radius)")
+    k, ratio, cell, max_radius = _three_or_four(stat, None, "denoise_statistical must be None, (k, std_ratio, cell) or "
+                                                            "(k, std_ratio, cell, max_radius)")
     k, ratio = PP._knn_k(k), PP._knn_ratio(ratio)
     if max_radius is not None:
         PP._knn_radius(max_radius)
         max_radius = float(max_radius)
-    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0:
-        raise ValueError("denoise_statistical: cell must be a finite number > 0")
-    return "statistical", k, ratio, _thin_grid(float(cell), args), max_radius
+    cell = _positive(cell, "denoise_statistical: cell must be a finite number > 0")
+    return _StatisticalFilter("statistical", k, ratio, _thin_grid(cell, args), max_radius)
 
 
 def _check_denoise_cluster(clu, denoise, stat, args):
@@ -268,21 +297,13 @@ def _check_denoise_cluster(clu, denoise, stat, args):
         return None
     if denoise is not None or stat is not None:
         raise ValueError("denoise_cluster excludes denoise and denoise_statistical")
-    try:
-        eps, min_points, min_size = clu[:3]
-        largest = clu[3] if len(clu) == 4 else False
-        ok = len(clu) in (3, 4)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError("denoise_cluster must be None, (eps, min_points, min_cluster_size) or (eps, min_points, min_cluster_size, largest_only)")
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or eps <= 0:
-        raise ValueError("denoise_cluster: eps must be a finite number > 0")
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, float)) or int(min_points) != min_points or min_points < 0:
-        raise ValueError("denoise_cluster: min_points must be an integer >= 0")
+    eps, min_points, min_size, largest = _three_or_four(clu, False, "denoise_cluster must be None, (eps, min_points, min_cluster_size) or "
+                                                                    "(eps, min_points, min_cluster_size, largest_only)")
+    eps = _positive(eps, "denoise_cluster: eps must be a finite number > 0")
+    min_points = _whole(min_points, 0, None, "denoise_cluster: min_points must be an integer >= 0")
     if not isinstance(largest, (bool, int)):
         raise ValueError("denoise_cluster: largest_only must be a bool")
-    return "cluster", float(eps), int(min_points), PP._cluster_size(min_size), bool(largest), _thin_grid(float(eps), args)
+    return _ClusterFilter("cluster", eps, min_points, PP._cluster_size(min_size), bool(largest), _thin_grid(eps, args))
 
 
 def _check_normal_consistency(nc, args, surfaces, normals, surface_steps):
@@ -296,8 +317,7 @@ def _check_normal_consistency(nc, args, surfaces, normals, surface_steps):
     except (TypeError, ValueError):
         raise ValueError("normal_consistency must be None or (k, cell)") from None
     k = PP._knn_k(k)
-    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0:
-        raise ValueError("normal_consistency: cell must be a finite number > 0")
+    cell = _positive(cell, "normal_consistency: cell must be a finite number > 0")
     if surfaces is None:
         raise ValueError("normal_consistency needs surfaces")
     if not (bool(normals) or int(surface_steps) > 0):
@@ -321,14 +341,44 @@ def _resample(pts: torch.Tensor, off: torch.Tensor, k: int, longest: int):
     return PP.resample_points_ragged(pts, off, k, max(1, min(int(longest), PP.FPS_MAX_POINTS)), return_index=True)
 
 
-def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds=None, normals=False, surface_steps=0,
-                    surface_max_step=0.05, denoise=None, ncons=None):
-    """The batched tail -> (points, offsets, cd or None, n_queries int64 [B], metrics dict or None, normals or None) on the device: what
-    infer_point_clouds_device returns plus the frames' query counts, which infer_point_clouds copies to the host with the rest; then
-    the host bound of the longest final cloud; the last element is None, or with `denoise` (_check_denoise's triple, or
-    _check_denoise_statistical's tuple) the dict of the denoised clouds: 'points', 'offsets', 'index', and 'cd' / 'metrics' (None where
-    no metric is computed) against the same surfaces; with the statistical filter 'stats' [B,3] as well; behind it None, or with `ncons`
-    (_check_normal_consistency's pair) the dict 'nc' float64 [B,3] and 'normals' [B*P,3], the surfaces' estimated normals."""
+def _metric(pts, off, gt, gt_off, max_pred, max_gt, thresholds):
+    """The tail's metric stage -> (cd float64 [B], metrics): Chamfer alone, or with thresholds cloud_metrics_ragged's dict and its 'cd'."""
+    if thresholds is None:
+        return PP.cal_metrics_ragged(pts, off, gt, gt_off, max_pred, max_gt), None                 # :320
+    metrics = PP.cloud_metrics_ragged(pts, off, gt, gt_off, max_pred, max_gt, thresholds)
+    return metrics["cd"], metrics
+
+
+class _HostPack:
+    """One host read of many small device tensors: add(name, group) (or a keyword each) collects them - a tensor, cloud_metrics_ragged's
+    dict (its METRIC_KEYS in order) or None (not computed: no group) - and read() makes the one copy (everything as float64,
+    concatenated) -> {name: the flat list of its values as floats}; integer groups are cast back by the caller."""
+    def __init__(self, **groups):
+        self.groups = {}
+        for name, group in groups.items():
+            self.add(name, group)
+
+    def add(self, name: str, group) -> None:
+        if group is not None:
+            tensors = [group[k] for k in PP.METRIC_KEYS] if isinstance(group, dict) else [group]
+            self.groups[name] = [t.reshape(-1).double() for t in tensors]
+
+    def read(self) -> Dict[str, list]:
+        host = torch.cat([t for group in self.groups.values() for t in group]).cpu().tolist()       # the one host read
+        ends = np.cumsum([sum(t.numel() for t in group) for group in self.groups.values()]).tolist()
+        return {name: host[lo:hi] for name, lo, hi in zip(self.groups, [0] + ends, ends)}
+
+
+def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals, surface_steps, surface_max_step,
+                    resample, thin, denoise, denoise_statistical, normal_consistency, denoise_cluster):
+    """What both batched entry points do, with their arguments -> (_Tail, _thin's four or None, _resample's pair or None): every option
+    checked on the host, the batched tail on the device, the filter chosen behind the metric of the full cloud with a metric of its own,
+    then the finishing chain on the denoised clouds if there are any, else on the full ones: thin, then resample."""
+    resample, thin_grid = _check_resample(resample), _thin_grid(thin, args)
+    # at most one of the three filters: each check refuses the ones named before it ("exclude each other" / "excludes")
+    denoise = (_check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
+               or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
+    ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
     oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
@@ -382,7 +432,7 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         pts, nrm = PP.oriented_points_ragged(kept, grad, p_off, lidar.pc_range, aniso, iso, view_cone_mode=view_cone)
     elif view_cone:
         pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
-    cd, metrics, den, ncd = None, None, None, None
+    cd = metrics = den = ncd = thinned = resampled = None
     with_metric = surfaces is not None and not _get(args.eval, "skip_eval_metric", False)
     if with_metric or ncons is not None:
         P = surfaces.shape[1]
@@ -392,34 +442,22 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
     if ncons is not None:                                                                          # the sensor sits at the origin of the final frame
         gt_nrm = PP.estimate_normals_ragged(gt, gt_off, ncons[0], ncons[1], max(1, int(P)), view=(0.0, 0.0, 0.0))
-        ncd = {"nc": PP.normal_consistency_ragged(pts, nrm, p_off, gt, gt_nrm, gt_off, longest, P)[0], "normals": gt_nrm}
+        ncd = (PP.normal_consistency_ragged(pts, nrm, p_off, gt, gt_nrm, gt_off, longest, P)[0], gt_nrm)
     if with_metric:
-        if metric_thresholds is None:
-            cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, longest, P)                         # :320
-        else:
-            metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
-            cd = metrics["cd"]
+        cd, metrics = _metric(pts, p_off, gt, gt_off, longest, P, metric_thresholds)
     if denoise is not None:                                                                        # after the metric, which keeps the full cloud
-        d_stats, d_lab, d_num = None, None, None
-        if denoise[0] == "cluster":
-            d_pts, d_off, d_idx, d_lab, d_num = PP.remove_small_clusters_ragged(pts, p_off, denoise[1], denoise[2], denoise[3], denoise[5],
-                                                                                max(1, int(longest)), largest_only=denoise[4],
-                                                                                return_index=True, return_labels=True)
-        elif denoise[0] == "statistical":
-            d_pts, d_off, d_idx, d_stats = PP.remove_statistical_outliers_ragged(pts, p_off, denoise[1], denoise[2], denoise[3],
-                                                                                 max(1, int(longest)), max_radius=denoise[4],
-                                                                                 return_index=True, return_stats=True)
-        else:
-            d_pts, d_off, d_idx = PP.remove_radius_outliers_ragged(pts, p_off, denoise[0], denoise[1], denoise[2], max(1, int(longest)),
-                                                                   return_index=True)
-        den = {"points": d_pts, "offsets": d_off, "index": d_idx, "cd": None, "metrics": None, "stats": d_stats, "labels": d_lab,
-               "n_clusters": d_num}
-        if cd is not None and metric_thresholds is None:
-            den["cd"] = PP.cal_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P)
-        elif cd is not None:
-            den["metrics"] = PP.cloud_metrics_ragged(d_pts, d_off, gt, gt_off, longest, P, metric_thresholds)
-            den["cd"] = den["metrics"]["cd"]
-    return pts, p_off, cd, n_queries, metrics, nrm, longest, den, ncd
+        den = denoise.run(pts, p_off, max(1, int(longest)))
+        if with_metric:
+            den.cd, den.metrics = _metric(den.points, den.offsets, gt, gt_off, longest, P, metric_thresholds)
+    tail = _Tail(pts, p_off, cd, n_queries, metrics, nrm, longest, den, ncd)
+    if den is not None:
+        pts, p_off = den.points, den.offsets
+    if thin_grid is not None:
+        thinned = _thin(pts, p_off, thin_grid, longest)
+        pts, p_off, longest = thinned[0], thinned[1], _thin_bound(longest, thin_grid)
+    if resample is not None:
+        resampled = _resample(pts, p_off, resample, longest)
+    return tail, thinned, resampled
 
 
 def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> dict:
@@ -457,141 +495,110 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     that mode reads the B positive counts to the host once more, before it draws (numpy's draw sizes depend on them).
 
     A frame whose first decode has no positive gets no refine queries and ends with an empty prediction and cd = inf; the
-    single-frame infer_point_cloud raises there.  Shape and length errors raise ValueError before any GPU work.
+    single-frame infer_point_cloud raises there.  Shape and length errors raise ValueError before any GPU work.  Every option below is
+    off by default (None, False, 0) and then changes neither the calls, the dict nor the host read; none of them adds a host read.
     `metric_thresholds` (None, or a sequence of up to 8 distances, () included): when given, the metric comes from
     postprocess.cloud_metrics_ragged instead of cal_metrics_ragged - 'cd' keeps its meaning, and 'metrics' holds one dict per frame
     (postprocess.cloud_metrics' keys: accuracy, completeness, cd, cd_l2, hausdorff, mhd as floats; precision, recall, f_score as lists
     per threshold), copied in the same single host read; None where no metric is computed.
-    `normals` / `surface_steps` (off by default: today's path and today's dict): with either, the queries that the last thresholding
-    kept are gathered in normalised coordinates, moved onto the decoder's surface by `surface_steps` Newton steps of at most
-    `surface_max_step` (query_points.project_to_surface_ragged; 0 = left where they are), and decoded once more with the logit's
-    gradient (KLAutoEncoder.decode_ragged_with_gradient); 'pred' then holds those points and a new 'normals' list one unit vector per
-    point [n_b,3] (occupied -> empty; zero where undefined), both from postprocess.oriented_points_ragged, and the metric is computed
-    on those points.  No host read is added.
-    `resample` (None: today's dict; or k >= 1): every final cloud additionally as exactly k evenly spread points - 'resampled' [B,k,3]
-    (metric coordinates, on the device) and 'resample_index' int64 [B,k] (rows of the frame's 'pred'; -1 in padded slots), from
+    `normals` / `surface_steps`: with either, the queries that the last thresholding kept are gathered in normalised coordinates, moved
+    onto the decoder's surface by `surface_steps` Newton steps of at most `surface_max_step` (query_points.project_to_surface_ragged;
+    0 = left where they are), and decoded once more with the logit's gradient (KLAutoEncoder.decode_ragged_with_gradient); 'pred' then
+    holds those points and a new 'normals' list one unit vector per point [n_b,3] (occupied -> empty; zero where undefined), both from
+    postprocess.oriented_points_ragged, and the metric is computed on those points.
+    `resample` (None, or k >= 1): every final cloud additionally as exactly k evenly spread points - 'resampled' [B,k,3] (metric
+    coordinates, on the device) and 'resample_index' int64 [B,k] (rows of the frame's 'pred'; -1 in padded slots), from
     postprocess.resample_points_ragged (farthest-point sampling from row 0) after the metric, which stays on the full
     cloud.  A frame with fewer than k points repeats its points in order, an empty one gives NaN rows.  The sampler takes clouds of
     up to 65536 points: a frame LONGER than that is sampled from its first 65536 rows only (the rows are in query order, so that is a
-    spatial bias) - a caller who expects such frames thins first, with `thin`.  No host read is added.
-    `thin` (None: today's calls, dict and host read; or the cell edge in the final clouds' coordinates, a number or 3): every final
-    cloud additionally with one point per occupied cell of a fixed grid - the cube [-r_max, r_max]^3, r_max = pc_range[3], in
-    view_cone_mode, else pc_range - from postprocess.voxel_downsample_ragged after the metric, which stays on the
-    full cloud: 'thinned' a list of B tensors [m_b,3] (the cells' centroids in ascending cell-key order), 'thin_count' a list of int32
-    [m_b] (rows per cell), 'thin_first' a list of int64 [m_b] (the cell's first row of the frame's 'pred'), and with normals /
-    surface_steps 'thinned_normals' [m_b,3], the normals of the thin_first rows.  Too many cells (more than 2^31 - 1) raise ValueError
-    before any GPU work.  The thinned offsets join the one host read.  With `resample` as well the sampler runs on the THINNED clouds
-    and 'resample_index' counts rows of 'thinned'; a thinned cloud above 65536 voxels is still truncated to its first 65536 - now in
-    cell-key order, a slab of the grid - so a coarser cell is the remedy.
-    `denoise` (None: today's calls, dict and host read; or (radius, min_neighbors) in the final clouds' coordinates): every final
-    cloud additionally without its isolated rows - a row stays iff at least min_neighbors OTHER rows of its frame lie within radius of
-    it, from postprocess.remove_radius_outliers_ragged on the box `thin` uses, cell edge = radius (a radius that
-    gives that box more than 2^31 - 1 cells raises ValueError before any GPU work).  'pred', 'cd' and 'metrics' stay on the full
-    cloud, untouched.  Added: 'denoised' a list of B tensors [m_b,3] (the kept rows in their order), 'denoise_index' a list of int64
-    [m_b] (rows of the frame's 'pred'), with normals / surface_steps 'denoised_normals' [m_b,3], with surfaces 'cd_denoised' (B floats,
-    None where no metric is computed) and with metric_thresholds 'metrics_denoised' (as 'metrics').  The denoised offsets and metrics
-    join the one host read.  `thin` and `resample` then run on the DENOISED clouds: 'thin_first' and (without thin) 'resample_index'
-    count rows of 'denoised', not of 'pred' - 'denoise_index' maps them back - and 'thinned_normals' are those of the rows thin_first
-    names in 'denoised'.
-    `denoise_statistical` (None: today's calls, dict and host read; or (k, std_ratio, cell) or (k, std_ratio, cell, max_radius)): the
-    statistical outlier filter in `denoise`'s place - a row stays iff the mean distance to its k nearest other rows of its frame (within
-    max_radius, if given) is at most mu + std_ratio * sigma of its frame's means, from postprocess.remove_statistical_outliers_ragged
-    (DESIGN section 23); it adapts to the cloud's density, which thins out with range, where `denoise` needs one radius in metres.
-    `cell` is the search grid's edge over the box `thin` uses (it does not show in the result; k / 8 to k rows per cell is a good edge; a
-    cell that gives the box more than 2^31 - 1 cells raises ValueError before any GPU work).  It fills the keys of `denoise` - 'denoised',
-    'denoise_index', 'denoised_normals', 'cd_denoised', 'metrics_denoised' - feeds `thin` and `resample` as `denoise` does, and adds
-    'denoise_stats': B triples (mu, sigma, threshold) as floats, NaN for a frame without a row that has a neighbour, carried in the
-    one host read.  Given together with `denoise` it raises ValueError: the two filters are not chained.
-    `denoise_cluster` (None: today's calls, dict and host read; or (eps, min_points, min_cluster_size) or (eps, min_points,
-    min_cluster_size, largest_only)): small-cluster removal in `denoise`'s place - the frame's rows are clustered by density (a row with
-    at least min_points OTHER rows within eps is a core row, core rows within eps of each other share a cluster, other rows join their
-    nearest core row's) and a row stays iff its cluster has at least min_cluster_size rows, with largest_only only the frame's largest
-    cluster, from postprocess.remove_small_clusters_ragged on the box `thin` uses, cell edge = eps.  It drops the
-    floating blobs that both other filters keep, because inside a blob every row has ordinary neighbours.  It fills the keys of
-    `denoise`, feeds `thin` and `resample` as `denoise` does, and adds 'denoise_labels', a list of int32 [m_b] (per row of 'denoised'
-    its cluster in the frame's numbering before the filter), and 'n_clusters', B ints carried in the one host read.  Given together
-    with `denoise` or `denoise_statistical` it raises ValueError.
-    `normal_consistency` (None: today's calls, dict and host read; or (k, cell)): the third standard metric of occupancy-field work
-    beside Chamfer and F-score.  It needs `surfaces` and the predicted normals (`normals` or `surface_steps`), else ValueError before
-    any GPU work.  The ground-truth clouds carry coordinates only, so their normals are estimated first - PCA over each row's k nearest
+    spatial bias) - a caller who expects such frames thins first, with `thin`.
+    `thin` (None, or the cell edge in the final clouds' coordinates, a number or 3): every final cloud additionally with one point per
+    occupied cell of a fixed grid - the cube [-r_max, r_max]^3, r_max = pc_range[3], in view_cone_mode, else pc_range - from
+    postprocess.voxel_downsample_ragged after the metric, which stays on the full cloud: 'thinned' a list of B
+    tensors [m_b,3] (the cells' centroids in ascending cell-key order), 'thin_count' a list of int32 [m_b] (rows per cell), 'thin_first'
+    a list of int64 [m_b] (the cell's first row of the frame's 'pred'), and with normals / surface_steps 'thinned_normals' [m_b,3], the
+    normals of the thin_first rows.  Too many cells (more than 2^31 - 1) raise ValueError before any GPU work.  The thinned offsets join
+    the one host read.  With `resample` as well the sampler runs on the THINNED clouds and 'resample_index' counts rows of 'thinned'; a
+    thinned cloud above 65536 voxels is still truncated to its first 65536 - now in cell-key order, a slab of the grid - so a coarser
+    cell is the remedy.
+    `denoise` (None, or (radius, min_neighbors) in the final clouds' coordinates): every final cloud additionally without its isolated
+    rows - a row stays iff at least min_neighbors OTHER rows of its frame lie within radius of it, from
+    postprocess.remove_radius_outliers_ragged on the box `thin` uses, cell edge = radius (a radius that gives that
+    box more than 2^31 - 1 cells raises ValueError before any GPU work).  'pred', 'cd' and 'metrics' stay on the full cloud, untouched.
+    Added: 'denoised' a list of B tensors [m_b,3] (the kept rows in their order), 'denoise_index' a list of int64 [m_b] (rows of the
+    frame's 'pred'), with normals / surface_steps 'denoised_normals' [m_b,3], with surfaces 'cd_denoised' (B floats, None where no
+    metric is computed) and with metric_thresholds 'metrics_denoised' (as 'metrics').  The denoised offsets and metrics join the one
+    host read.  `thin` and `resample` then run on the DENOISED clouds: 'thin_first' and (without thin) 'resample_index' count rows of
+    'denoised', not of 'pred' - 'denoise_index' maps them back - and 'thinned_normals' are those of the rows thin_first names in 'denoised'.
+    `denoise_statistical` (None, or (k, std_ratio, cell) or (k, std_ratio, cell, max_radius)): the statistical outlier filter in
+    `denoise`'s place - a row stays iff the mean distance to its k nearest other rows of its frame (within max_radius, if given) is at
+    most mu + std_ratio * sigma of its frame's means, from postprocess.remove_statistical_outliers_ragged; it adapts
+    to the cloud's density, which thins out with range, where `denoise` needs one radius in metres.  `cell` is the search grid's edge
+    over the box `thin` uses (it does not show in the result; k / 8 to k rows per cell is a good edge; a cell that gives the box more
+    than 2^31 - 1 cells raises ValueError before any GPU work).  It fills the keys of `denoise` - 'denoised', 'denoise_index',
+    'denoised_normals', 'cd_denoised', 'metrics_denoised' - feeds `thin` and `resample` as `denoise` does, and adds 'denoise_stats': B
+    triples (mu, sigma, threshold) as floats, NaN for a frame without a row that has a neighbour, carried in the one host read.  Given
+    together with `denoise` it raises ValueError: the two filters are not chained.
+    `denoise_cluster` (None, or (eps, min_points, min_cluster_size) or (eps, min_points, min_cluster_size, largest_only)): small-cluster
+    removal in `denoise`'s place - the frame's rows are clustered by density (a row with at least min_points OTHER rows within eps is a
+    core row, core rows within eps of each other share a cluster, other rows join their nearest core row's) and a row stays iff its
+    cluster has at least min_cluster_size rows, with largest_only only the frame's largest cluster, from
+    postprocess.remove_small_clusters_ragged on the box `thin` uses, cell edge = eps.  It drops the floating blobs
+    that both other filters keep, because inside a blob every row has ordinary neighbours.  It fills the keys of `denoise`, feeds `thin`
+    and `resample` as `denoise` does, and adds 'denoise_labels', a list of int32 [m_b] (per row of 'denoised' its cluster in the frame's
+    numbering before the filter), and 'n_clusters', B ints carried in the one host read.  Given together with `denoise` or
+    `denoise_statistical` it raises ValueError.
+    `normal_consistency` (None, or (k, cell)): the third standard metric of occupancy-field work beside Chamfer and F-score.  It needs
+    `surfaces` and the predicted normals (`normals` or `surface_steps`), else ValueError before any GPU work.  The ground-truth clouds
+    carry coordinates only, so their normals are estimated first - PCA over each row's k nearest
     other rows and itself, turned towards the sensor at the origin, from postprocess.estimate_normals_ragged over the
     box `thin` uses with the search cell `cell` (it does not show in the result) - and then compared with the normals of 'pred' by
     postprocess.normal_consistency_ragged: |n . n'| with the nearest row of the other cloud, averaged per direction.  Computed on the
     full cloud, skip_eval_metric or not.  Added: 'normal_consistency', B triples (pred -> gt, gt -> pred, their mean; NaN where no row
     has two usable normals) carried in the one host read, and 'surface_normals', a list of B tensors [P,3] on the device.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
-    'n_queries': list of B ints} (+ 'metrics' with metric_thresholds, + 'normals' with normals / surface_steps, + 'resampled' and
-    'resample_index' with resample, + 'thinned', 'thin_count', 'thin_first' (and 'thinned_normals') with thin, + 'denoised',
-    'denoise_index' (and 'denoised_normals', 'cd_denoised', 'metrics_denoised') with denoise)."""
-    resample = _check_resample(resample)
-    grid = _thin_grid(thin, args)
-    denoise = (_check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
-               or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
-    ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
-    pts, off, cd, nq, metrics, nrm, longest, den, ncd = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws,
-                                                                        metric_thresholds, normals, surface_steps, surface_max_step, denoise,
-                                                                        ncons)
-    B = sampled_tokens.shape[0]
-    s_pts, s_off, s_longest = (pts, off, longest) if den is None else (den["points"], den["offsets"], longest)
-    if grid is not None:
-        t_pts, t_off, t_count, t_first = _thin(s_pts, s_off, grid, longest)
-        s_pts, s_off, s_longest = t_pts, t_off, _thin_bound(longest, grid)
-    if resample is not None:
-        resampled, resample_index = _resample(s_pts, s_off, resample, s_longest)
-    extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
-    d_extra = []
-    if den is not None:                                                                             # in front of the thinned offsets
-        d_extra = [den["offsets"].double()] + ([den["cd"]] if den["cd"] is not None else [])
-        d_extra += [den["metrics"][k].reshape(-1) for k in PP.METRIC_KEYS] if den["metrics"] is not None else []
-        if den.get("stats") is not None:                                                            # behind everything else of the filter
-            d_extra += [den["stats"].reshape(-1)]
-        if den.get("n_clusters") is not None:
-            d_extra += [den["n_clusters"].double()]
-    packed = torch.cat([off.double(), nq.double()] + ([cd] if cd is not None else []) + extra + d_extra
-                       + ([ncd["nc"].reshape(-1)] if ncd is not None else [])               # in front of the thinned offsets
-                       + ([t_off.double()] if grid is not None else []))
-    host = packed.cpu().tolist()                                                                    # the one host read
-    o = [int(v) for v in host[:B + 1]]
-    out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
-           "cd": host[2 * B + 1:3 * B + 1] if cd is not None else None,
-           "n_queries": [int(v) for v in host[B + 1:2 * B + 1]]}
-    if metric_thresholds is not None:
-        out["metrics"] = PP._metrics_to_host(host[3 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
-    if nrm is not None:
-        out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
+    'n_queries': list of B ints} and the keys that the options above add."""
+    t, thinned, resampled = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals,
+                                            surface_steps, surface_max_step, resample, thin, denoise, denoise_statistical, normal_consistency,
+                                            denoise_cluster)
+    B, den, nrm = sampled_tokens.shape[0], t.denoised, t.normals
+    groups = {"offsets": t.offsets, "n_queries": t.n_queries, "cd": t.cd, "metrics": t.metrics,
+              "normal_consistency": t.ncons and t.ncons[0], "thin_offsets": thinned and thinned[1]}
     if den is not None:
-        at = 2 * B + 1 + (B if cd is not None else 0) + sum(t.numel() for t in extra)
-        do = [int(v) for v in host[at:at + B + 1]]
-        out["denoised"] = [den["points"][do[b]:do[b + 1]] for b in range(B)]
-        out["denoise_index"] = [den["index"][do[b]:do[b + 1]] for b in range(B)]
+        groups.update(denoise_offsets=den.offsets, cd_denoised=den.cd, metrics_denoised=den.metrics, denoise_stats=den.stats, n_clusters=den.n_clusters)
+    host = _HostPack(**groups).read()
+    ints = lambda name: [int(v) for v in host[name]]
+    frames = lambda rows, name: [rows[lo:hi] for lo, hi in zip(ints(name), ints(name)[1:])]         # a ragged tensor by its offsets' host copy
+    triples = lambda name: [tuple(host[name][3 * b:3 * b + 3]) for b in range(B)]
+    frame_metrics = lambda name: PP._metrics_to_host(host[name], B, len(metric_thresholds)) if name in host else None
+    o = ints("offsets")
+    out = {"pred": frames(t.points, "offsets"), "cd": host.get("cd"), "n_queries": ints("n_queries")}
+    if metric_thresholds is not None:
+        out["metrics"] = frame_metrics("metrics")
+    if nrm is not None:
+        out["normals"] = frames(nrm, "offsets")
+    if den is not None:
+        out["denoised"], out["denoise_index"] = frames(den.points, "denoise_offsets"), frames(den.index, "denoise_offsets")
         if nrm is not None:
             out["denoised_normals"] = [nrm[o[b] + out["denoise_index"][b]] for b in range(B)]
         if surfaces is not None:
-            out["cd_denoised"] = host[at + B + 1:at + 2 * B + 1] if den["cd"] is not None else None
+            out["cd_denoised"] = host.get("cd_denoised")
         if metric_thresholds is not None:
-            out["metrics_denoised"] = (PP._metrics_to_host(host[at + 2 * B + 1:], B, len(metric_thresholds))
-                                       if den["metrics"] is not None else None)
-        if den.get("stats") is not None:
-            st = at + sum(t.numel() for t in d_extra[:-1])
-            out["denoise_stats"] = [tuple(host[st + 3 * b:st + 3 * b + 3]) for b in range(B)]
-        if den.get("labels") is not None:
-            st = at + sum(t.numel() for t in d_extra[:-1])
-            out["denoise_labels"] = [den["labels"][do[b]:do[b + 1]] for b in range(B)]
-            out["n_clusters"] = [int(v) for v in host[st:st + B]]
-    if ncd is not None:
-        at = len(host) - (B + 1 if grid is not None else 0) - 3 * B
-        P = surfaces.shape[1]
-        out["normal_consistency"] = [tuple(host[at + 3 * b:at + 3 * b + 3]) for b in range(B)]
-        out["surface_normals"] = [ncd["normals"][b * P:(b + 1) * P] for b in range(B)]
-    if grid is not None:
-        to = [int(v) for v in host[len(host) - (B + 1):]]
-        for key, t in (("thinned", t_pts), ("thin_count", t_count), ("thin_first", t_first)):
-            out[key] = [t[to[b]:to[b + 1]] for b in range(B)]
+            out["metrics_denoised"] = frame_metrics("metrics_denoised")
+        if den.stats is not None:
+            out["denoise_stats"] = triples("denoise_stats")
+        if den.labels is not None:
+            out["denoise_labels"], out["n_clusters"] = frames(den.labels, "denoise_offsets"), ints("n_clusters")
+    if t.ncons is not None:
+        out["normal_consistency"], out["surface_normals"] = triples("normal_consistency"), list(t.ncons[1].split(surfaces.shape[1]))
+    if thinned is not None:
+        for key, rows in zip(("thinned", "thin_count", "thin_first"), (thinned[0], thinned[2], thinned[3])):
+            out[key] = frames(rows, "thin_offsets")
         if nrm is not None:
             rows = out["thin_first"] if den is None else [out["denoise_index"][b][out["thin_first"][b]] for b in range(B)]
             out["thinned_normals"] = [nrm[o[b] + rows[b]] for b in range(B)]
-    if resample is not None:
-        out["resampled"], out["resample_index"] = resampled, resample_index
+    if resampled is not None:
+        out["resampled"], out["resample_index"] = resampled
     return out
 
 
@@ -653,22 +660,13 @@ def scan_point_clouds(vae, sampled_tokens: torch.Tensor, args, az_deg, el_deg, n
         P = surfaces.shape[1]
         gt = PP.polar2cartesian(PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso))
         gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
-        if metric_thresholds is None:
-            cd = PP.cal_metrics_ragged(pts, p_off, gt, gt_off, R, P)
-        else:
-            metrics = PP.cloud_metrics_ragged(pts, p_off, gt, gt_off, R, P, metric_thresholds)
-            cd = metrics["cd"]
-    extra = [metrics[k].reshape(-1) for k in PP.METRIC_KEYS] if metrics is not None else []
-    packed = torch.cat([p_off.double()] + ([cd] if cd is not None else []) + extra)
-    host = packed.cpu().tolist()                                                                    # the one host read
-    o = [int(v) for v in host[:B + 1]]
-    out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)],
-           "range": rng_m,
-           "beam_index": [p_idx[o[b]:o[b + 1]] for b in range(B)],
-           "cd": host[B + 1:2 * B + 1] if cd is not None else None,
-           "n_queries": [R * (n_steps + 1 + n_refine)] * B}
+        cd, metrics = _metric(pts, p_off, gt, gt_off, R, P, metric_thresholds)
+    host = _HostPack(offsets=p_off, cd=cd, metrics=metrics).read()
+    o = [int(v) for v in host["offsets"]]
+    out = {"pred": [pts[o[b]:o[b + 1]] for b in range(B)], "range": rng_m, "beam_index": [p_idx[o[b]:o[b + 1]] for b in range(B)],
+           "cd": host.get("cd"), "n_queries": [R * (n_steps + 1 + n_refine)] * B}
     if metric_thresholds is not None:
-        out["metrics"] = PP._metrics_to_host(host[2 * B + 1:], B, len(metric_thresholds)) if metrics is not None else None
+        out["metrics"] = PP._metrics_to_host(host["metrics"], B, len(metric_thresholds)) if metrics is not None else None
     if nrm is not None:
         out["normals"] = [nrm[o[b]:o[b + 1]] for b in range(B)]
     return out

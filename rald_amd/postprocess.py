@@ -175,6 +175,20 @@ def _offsets_shape(t, what: str) -> int:
     return t.numel() - 1
 
 
+def _positive(x, message: str) -> float:
+    """A finite number > 0 (no bool, no string) -> float; else ValueError(message)."""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x <= 0:
+        raise ValueError(message)
+    return float(x)
+
+
+def _whole(x, lo: int, hi, message: str) -> int:
+    """A number (no bool, no string) that is a whole number in lo .. hi (hi None: no upper end) -> int; else ValueError(message)."""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or int(x) != x or x < lo or (hi is not None and x > hi):
+        raise ValueError(message)
+    return int(x)
+
+
 def _bound(v, what: str) -> int:
     if int(v) != v or v < 0:
         raise ValueError(f"{what} must be a non-negative integer")
@@ -435,8 +449,12 @@ VOXEL_MAX_CELLS = (1 << 31) - 1
 
 
 def _f32(v: float) -> float:
+    """v rounded to float32; +-inf where it does not fit, which every caller refuses as it refuses a non-finite result."""
     import struct
-    return struct.unpack("f", struct.pack("f", v))[0]
+    try:
+        return struct.unpack("f", struct.pack("f", v))[0]
+    except OverflowError:
+        return math.copysign(math.inf, v)
 
 
 def voxel_grid(lo: Sequence[float], hi: Sequence[float], voxel) -> Tuple[Tuple[float, ...], Tuple[float, ...], Tuple[int, ...]]:
@@ -455,10 +473,7 @@ def voxel_grid(lo: Sequence[float], hi: Sequence[float], voxel) -> Tuple[Tuple[f
         raise ValueError("lo and hi must be finite with lo <= hi")
     if any(not math.isfinite(x) or x <= 0 for x in v):
         raise ValueError("the cell edge must be finite and > 0")
-    try:
-        lo3, v3 = tuple(_f32(x) for x in lo), tuple(_f32(x) for x in v)
-    except OverflowError:
-        raise ValueError("lo and the cell edge must fit float32") from None
+    lo3, v3 = tuple(_f32(x) for x in lo), tuple(_f32(x) for x in v)
     if any(x <= 0 or not math.isfinite(x) for x in v3) or any(not math.isfinite(x) for x in lo3):
         raise ValueError("lo and the cell edge must fit float32")
     dims = tuple(int(math.floor((h - l) / x)) + 1 for l, h, x in zip(lo, hi, v))
@@ -528,15 +543,15 @@ def _one_cloud_check(points, lo, hi) -> None:
         raise ValueError("lo and hi come together")
 
 
-def _one_cloud(points, lo, hi, grid_of, run_ragged) -> torch.Tensor:
-    """The one-cloud conveniences behind _one_cloud_check and their own rules: grid_of(lo, hi, rows) on the box given (before anything
-    else, an empty cloud included) or on the cloud's own minimum and maximum (one host read of six numbers), then
-    run_ragged(points, offsets, grid, N) on offsets [0, N] and its first cloud's rows (the second host read)."""
+def _one_cloud(points, lo, hi, grid_of):
+    """What the one-cloud conveniences share behind _one_cloud_check and their own rules: grid_of(lo, hi, rows) on the box given (before
+    anything else, an empty cloud included) or on the cloud's own minimum and maximum (one host read of six numbers) -> the ragged call's
+    (points, offsets [0, N], grid, N); None for an empty cloud."""
     N = points.shape[0]
     if lo is not None:
         grid = grid_of(lo, hi, max(N, 1))
     if N == 0:
-        return points.new_zeros(0, 3, dtype=torch.float32)
+        return None
     if N > VOXEL_MAX_POINTS:
         raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
     _need_cuda(points, "points")
@@ -544,8 +559,15 @@ def _one_cloud(points, lo, hi, grid_of, run_ragged) -> torch.Tensor:
     if lo is None:
         ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
         grid = grid_of(ext[:3], ext[3:], N)
-    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
-    out, off = run_ragged(points, offsets, grid, N)
+    return points, torch.tensor([0, N], dtype=torch.int64, device=points.device), grid, N
+
+
+def _one_cloud_rows(points, lo, hi, grid_of, run_ragged) -> torch.Tensor:
+    """A filter on one cloud: run_ragged(points, offsets, grid, N) -> (rows, out_offsets) and its first cloud's rows (the second host read)."""
+    one = _one_cloud(points, lo, hi, grid_of)
+    if one is None:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    out, off = run_ragged(*one)
     return out[:int(off[1].item())]
 
 
@@ -588,7 +610,7 @@ def voxel_downsample(points: torch.Tensor, voxel, lo: Optional[Sequence[float]] 
     _one_cloud_check(points, lo, hi)
     if lo is None:
         voxel_grid((0, 0, 0), (0, 0, 0), voxel)                                       # the edge's own rules, before anything is read
-    return _one_cloud(points, lo, hi, lambda l, h, n: voxel_grid(l, h, voxel), voxel_downsample_ragged)
+    return _one_cloud_rows(points, lo, hi, lambda l, h, n: voxel_grid(l, h, voxel), voxel_downsample_ragged)
 
 
 def _radius_args(points, radius, grid, max_per_sample, counts, B: Optional[int], chunk, cap, cap_name: str, cap_min: int):
@@ -596,12 +618,7 @@ def _radius_args(points, radius, grid, max_per_sample, counts, B: Optional[int],
     float32 the kernels use, cap, max_per_sample, chunk, the grid's three ctypes arrays)."""
     max_per_sample, chunk = _voxel_args(points, max_per_sample, counts, B, chunk)
     arrays = _voxel_grid_arg(grid)
-    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
-        raise ValueError("radius must be a finite number > 0")
-    try:
-        radius = _f32(float(radius))
-    except OverflowError:
-        raise ValueError("radius must fit float32") from None
+    radius = _f32(_positive(radius, "radius must be a finite number > 0"))
     if not radius > 0 or not math.isfinite(radius):
         raise ValueError("radius must fit float32")
     if any(float(v) < radius for v in grid[1]):
@@ -666,19 +683,15 @@ def remove_radius_outliers(points: torch.Tensor, radius: float, min_neighbors: i
     is a second host read in either case.  Where the box would need more than 2^31 - 1 cells of edge `radius` the cells are made
     larger; the result does not depend on that."""
     _one_cloud_check(points, lo, hi)
-    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
-        raise ValueError("radius must be a finite number > 0")
+    _positive(radius, "radius must be a finite number > 0")
     if isinstance(min_neighbors, bool) or int(min_neighbors) != min_neighbors or min_neighbors < 1:
         raise ValueError("min_neighbors must be an integer >= 1")
-    return _one_cloud(points, lo, hi, lambda l, h, n: _radius_grid(l, h, radius),
-                      lambda p, off, grid, n: remove_radius_outliers_ragged(p, off, radius, int(min_neighbors), grid, n))
+    return _one_cloud_rows(points, lo, hi, lambda l, h, n: _radius_grid(l, h, radius),
+                           lambda p, off, grid, n: remove_radius_outliers_ragged(p, off, radius, int(min_neighbors), grid, n))
 
 
 def _cluster_size(min_cluster_size) -> int:
-    if isinstance(min_cluster_size, bool) or not isinstance(min_cluster_size, (int, float)) or int(min_cluster_size) != min_cluster_size \
-            or not 1 <= min_cluster_size <= 2 ** 31 - 1:
-        raise ValueError("min_cluster_size must be an integer >= 1")
-    return int(min_cluster_size)
+    return _whole(min_cluster_size, 1, 2 ** 31 - 1, "min_cluster_size must be an integer >= 1")
 
 
 def cluster_dbscan_ragged(points: torch.Tensor, offsets: torch.Tensor, eps: float, min_points: int, grid, max_per_sample: int,
@@ -743,10 +756,8 @@ def remove_small_clusters_ragged(points: torch.Tensor, offsets: torch.Tensor, ep
 
 def _cluster_one_args(points, eps, min_points, lo, hi) -> None:
     _one_cloud_check(points, lo, hi)
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or eps <= 0:
-        raise ValueError("eps must be a finite number > 0")
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, float)) or int(min_points) != min_points or min_points < 0:
-        raise ValueError("min_points must be an integer >= 0")
+    _positive(eps, "eps must be a finite number > 0")
+    _whole(min_points, 0, None, "min_points must be an integer >= 0")
 
 
 def cluster_dbscan(points: torch.Tensor, eps: float, min_points: int, lo: Optional[Sequence[float]] = None,
@@ -757,20 +768,11 @@ def cluster_dbscan(points: torch.Tensor, eps: float, min_points: int, lo: Option
     (and the cloud must be finite).  Where the box would need more than 2^31 - 1 cells of edge eps the cells are made larger; the
     result does not depend on that."""
     _cluster_one_args(points, eps, min_points, lo, hi)
-    N = points.shape[0]
-    if lo is not None:
-        grid = _radius_grid(lo, hi, eps)
-    if N == 0:
+    one = _one_cloud(points, lo, hi, lambda l, h, n: _radius_grid(l, h, eps))
+    if one is None:
         return torch.zeros(0, dtype=torch.int32, device=points.device)
-    if N > VOXEL_MAX_POINTS:
-        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
-    _need_cuda(points, "points")
-    points = _f32c(points)
-    if lo is None:
-        ext = torch.cat([points.min(dim=0).values, points.max(dim=0).values]).tolist()   # the host read
-        grid = _radius_grid(ext[:3], ext[3:], eps)
-    offsets = torch.tensor([0, N], dtype=torch.int64, device=points.device)
-    return cluster_dbscan_ragged(points, offsets, eps, int(min_points), grid, N)[0]
+    p, off, grid, N = one
+    return cluster_dbscan_ragged(p, off, eps, int(min_points), grid, N)[0]
 
 
 def remove_small_clusters(points: torch.Tensor, eps: float, min_points: int, min_cluster_size: int, largest_only: bool = False,
@@ -779,9 +781,9 @@ def remove_small_clusters(points: torch.Tensor, eps: float, min_points: int, min
     length is a second host read in either case."""
     _cluster_one_args(points, eps, min_points, lo, hi)
     min_cluster_size = _cluster_size(min_cluster_size)
-    return _one_cloud(points, lo, hi, lambda l, h, n: _radius_grid(l, h, eps),
-                      lambda p, off, grid, n: remove_small_clusters_ragged(p, off, eps, int(min_points), min_cluster_size, grid, n,
-                                                                           largest_only=largest_only))
+    return _one_cloud_rows(points, lo, hi, lambda l, h, n: _radius_grid(l, h, eps),
+                           lambda p, off, grid, n: remove_small_clusters_ragged(p, off, eps, int(min_points), min_cluster_size, grid, n,
+                                                                                largest_only=largest_only))
 
 
 KNN_MAX_K = 32                                           # the largest k of rald_post_knn_ragged
@@ -797,20 +799,13 @@ def _knn_args(points, k, grid, max_per_sample, counts, B: Optional[int], chunk, 
 
 
 def _knn_k(k) -> int:
-    if isinstance(k, bool) or not isinstance(k, (int, float)) or not math.isfinite(k) or int(k) != k or not 1 <= k <= KNN_MAX_K:
-        raise ValueError(f"k must be an integer in 1 .. {KNN_MAX_K}")
-    return int(k)
+    return _whole(k, 1, KNN_MAX_K, f"k must be an integer in 1 .. {KNN_MAX_K}")
 
 
 def _knn_radius(max_radius) -> float:
     if max_radius is None:
         return 0.0
-    if isinstance(max_radius, bool) or not isinstance(max_radius, (int, float)) or not math.isfinite(max_radius) or max_radius <= 0:
-        raise ValueError("max_radius must be None or a finite number > 0")
-    try:
-        r = _f32(float(max_radius))
-    except OverflowError:
-        raise ValueError("max_radius must fit float32") from None
+    r = _f32(_positive(max_radius, "max_radius must be None or a finite number > 0"))
     if not r > 0 or not math.isfinite(r):
         raise ValueError("max_radius must fit float32")
     return r
@@ -890,10 +885,10 @@ def remove_statistical_outliers(points: torch.Tensor, k: int, std_ratio: float, 
     out there is inside for one edge and outside for another)."""
     _one_cloud_check(points, lo, hi)
     k, std_ratio = _knn_k(k), _knn_ratio(std_ratio)
-    if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0):
-        raise ValueError("cell must be None or a finite number > 0")
-    return _one_cloud(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell),
-                      lambda p, off, grid, n: remove_statistical_outliers_ragged(p, off, k, std_ratio, grid, n))
+    if cell is not None:
+        _positive(cell, "cell must be None or a finite number > 0")
+    return _one_cloud_rows(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell),
+                           lambda p, off, grid, n: remove_statistical_outliers_ragged(p, off, k, std_ratio, grid, n))
 
 
 def _view_arg(view):
@@ -907,10 +902,7 @@ def _view_arg(view):
         raise ValueError("view must be None or 3 finite numbers") from None
     if len(v) != 3 or any(not math.isfinite(x) for x in v):
         raise ValueError("view must be None or 3 finite numbers")
-    try:
-        v = [_f32(x) for x in v]
-    except OverflowError:
-        raise ValueError("view must fit float32") from None
+    v = [_f32(x) for x in v]
     if any(not math.isfinite(x) for x in v):
         raise ValueError("view must fit float32")
     return (C.c_float * 3)(*v)
@@ -953,10 +945,13 @@ def estimate_normals(points: torch.Tensor, k: int, view: Optional[Sequence[float
     _one_cloud_check(points, lo, hi)
     k = _knn_k(k)
     _view_arg(view)
-    if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float)) or not math.isfinite(cell) or cell <= 0):
-        raise ValueError("cell must be None or a finite number > 0")
-    return _one_cloud(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell),
-                      lambda p, off, grid, n: (estimate_normals_ragged(p, off, k, grid, n, view=view), off))
+    if cell is not None:
+        _positive(cell, "cell must be None or a finite number > 0")
+    one = _one_cloud(points, lo, hi, lambda l, h, n: _knn_grid(l, h, n, k, cell))
+    if one is None:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    p, off, grid, N = one
+    return estimate_normals_ragged(p, off, k, grid, N, view=view)
 
 
 def _normals_of(t, points, what: str) -> None:

@@ -228,6 +228,36 @@ def test_results_do_not_depend_on_stale_state():
             assert _same(first, _run(p, off, grid, e, bound=2049, chunk=chunk, **kw))
 
 
+# ---- 6. one walk, one early stop -------------------------------------------------------------------------------------------------------------
+@gpu
+def test_capped_count_equals_the_radius_count():
+    """rad_count and clu_count run the same radius_walk (cloud_index.h) and must stop it at the same cap: for caps 1 and 3 the capped
+    count of radius_neighbor_count_ragged, cluster_dbscan_ragged's count and the brute-force reference are equal, on one ragged batch
+    of 0, 257 and 1025 rows (one past rad_count's workgroup of 256 positions, one past a CLOUD_SEG of 1024): a lattice of 11^3 sites of
+    edge = cell = radius (face neighbours at exactly r2, duplicates) with a few rows outside the box, NaN and inf included."""
+    from rald_amd import postprocess as PP
+    e, side = 0.125, 11
+    off = _offsets([0, 257, 1025])
+    rs = np.random.RandomState(27)
+    p = (rs.randint(0, side, size=(off[-1], 3)).astype(F32) * F32(e)).astype(F32)
+    bad = np.concatenate([rs.choice(257, 8, replace=False), 257 + rs.choice(1025, 8, replace=False)])
+    for rows, value in ((bad[0::4], np.nan), (bad[1::4], np.inf), (bad[2::4], -e), (bad[3::4], (side + 1) * e)):
+        p[rows, rs.randint(0, 3, len(rows))] = F32(value)
+    grid = radius_ref.cube_grid(0.0, side * e, e)
+    free = radius_ref.radius_ragged(p, off, grid, e, 1025)["count"]
+    sites = {tuple(s) for s in np.round(np.delete(p, bad, axis=0) / F32(e)).astype(int).tolist()}
+    assert (free[bad] == -1).all() and (np.delete(free, bad) >= 0).all() and len(sites) < len(p) - len(bad)          # duplicates
+    dp, doff = torch.from_numpy(p).cuda(), torch.tensor(off, device="cuda")
+    for cap in (1, 3):
+        ref = radius_ref.radius_ragged(p, off, grid, e, 1025, max_count=cap)["count"]
+        for lo, hi in zip(off[1:], off[2:]):                                  # in each cloud the cap bites for some rows and not for others
+            assert (free[lo:hi] > cap).any() and ((free[lo:hi] >= 0) & (free[lo:hi] < cap)).any()
+        rad = PP.radius_neighbor_count_ragged(dp, doff, e, grid, 1025, max_count=cap).cpu().numpy()
+        clu = PP.cluster_dbscan_ragged(dp, doff, e, cap, grid, 1025, return_count=True)[2].cpu().numpy()
+        assert rad.dtype == clu.dtype == ref.dtype == np.int32
+        assert np.array_equal(rad, ref) and np.array_equal(clu, ref) and np.array_equal(rad, clu)
+
+
 # ---- the Python layer ------------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_python_layer():
