@@ -610,6 +610,61 @@ int rald_op_cluster_filter_ragged(const float* points, const int64_t* offsets, c
                                   const int32_t* dims3_host, float eps, int32_t min_points, int32_t min_cluster_size, int32_t largest_only,
                                   float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
                                   void* scratch, int64_t scratch_bytes, int64_t chunk, void* stream);
+/* ---- RANSAC plane segmentation inside a cloud and the removal (or extraction) of its planes.  Defined to the
+ * bit: the result is a function of (rows, parameters, seed) alone, the same in every call and at every batch position.
+ *   Layout: points / offsets / counts / n_dense / n_total / max_per_sample are those of the other ragged calls.  There is no grid.
+ *   USABLE: a row whose three coordinates are finite.
+ *   HOST parameters: threshold t finite and > 0; num_hypotheses H in 1 .. 65536; max_planes K in 1 .. 8; min_inliers >= 3; refine 0 or
+ *   1; seed int64; view3_host NULL (= 0, 0, 0) or three finite floats.
+ *   ROUNDS: for round j = 0 .. K - 1, LIVE_j is the list of the cloud's usable rows that no earlier round labelled, in row order, m its
+ *   length.  m < 3: the cloud is finished.
+ *   HYPOTHESIS h of round j: philox4x32_10(counter = (h, j, 0, 0), key = (seed mod 2^32, 2)) -> words w0 .. w3 (key tags 0 and 1 are the
+ *   sampler's; the cloud's index is NOT in the counter).  Rows i_k = LIVE_j[(w_k * m) >> 32], k = 0, 1, 2 (a 64-bit integer product) with
+ *   coordinates p0, p1, p2.  All in fp32, every operation rounded once, no contraction: e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2 (each
+ *   component fl(fl(a * b) - fl(c * d)): nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z, nz = e1x e2y - e1y e2x), len2 = fl(fl(fl(nx *
+ *   nx) + fl(ny * ny)) + fl(nz * nz)).  INVALID if two of the three positions in LIVE_j coincide or len2 is not finite or not > 0.
+ *   INLIER: a row p of LIVE_j with fl(s * s) <= fl(fl(t * t) * len2), s = fl(fl(fl(nx * dx) + fl(ny * dy)) + fl(nz * dz)), d = p - p0
+ *   per component.  No square root, no division.  score[h] = the number of inliers, -1 for an invalid hypothesis.
+ *   BEST: the largest score, the smallest h on equal scores.  No valid hypothesis or a best score below min_inliers: finished.
+ *   PLANE, refine = 0: in float64, (x, y, z) = n / sqrt((nx nx + ny ny) + nz nz) from the fp32 n, c0 = p0.
+ *   PLANE, refine = 1: over LIVE_j, a row that is no inlier of the best hypothesis contributing +0.0, in the FIXED SUM SHAPE - blocks of
+ *   1024 consecutive positions of LIVE_j, inside a block the halving tree v[i] += v[i + h] for h = 512, 256 .. 1 over the 1024 values (the
+ *   padding is +0.0), the blocks' sums added left to right from +0.0 - the float64 sums of x, y, z, divided by the inlier count: the
+ *   centroid c; then in the same shape the six sums of (p - c)(p - c)^T (xx, xy, xz, yy, yz, zz), divided by the count; six cyclic
+ *   Jacobi sweeps, the three exchanges and the renormalisation exactly as rald_post_normals_ragged's: (x, y, z) is the column of the
+ *   smallest eigenvalue divided by its length, c0 = c.  Round j's inliers are then the rows of LIVE_j with
+ *   |fl64(fl64(x * (px - c0x) + y * (py - c0y)) + z * (pz - c0z))| <= (double)t, x y z after the sign rule; fewer than min_inliers of
+ *   them: the cloud is finished and plane j is not written.
+ *   SIGN: sgn = (x * (vx - c0x) + y * (vy - c0y)) + z * (vz - c0z) in float64; (x, y, z) is negated iff sgn < 0, or sgn == 0 and the
+ *   first non-zero of (x, y, z) is negative.  The plane is (a, b, c, d) = (x, y, z, -((x * c0x + y * c0y) + z * c0z)).
+ *   out_planes double [batch, K, 4]: NaN for planes not found.  out_num_planes int32 [batch].  out_inliers (nullable) int32 [batch, K]:
+ *   0 for planes not found.  out_best (nullable) int32 [batch, K]: the winning h of a plane that was written, -1 else.
+ *   out_labels int32 [n_total], laid out like points: the round that took the row, -1 for a usable row that no plane took, -2 for an
+ *   unusable row.  Rows outside every cloud's span (past offsets[batch], behind counts or the bound) are not written.
+ *   Filter: keep_planes != 0 keeps the rows with label >= 0, keep_planes = 0 those with label -1 (ground removal at K = 1); unusable
+ *   rows are never kept.  Kept rows come out as the radius filter's: out_points (original order, the input row's bits), out_offsets
+ *   DEVICE int64 [batch+1], optional out_index int64 [n_total]; out_labels int32 [n_total] per KEPT row, out_planes and out_num_planes
+ *   as above.  Rows from out_offsets[batch] on are not written.
+ * Launches (cloud_plane.hip): an init, then per round the row-order compaction of the live rows, one lane per hypothesis (Philox, the
+ * three rows, eight floats), the scoring kernel rows x hypotheses (a tile of 1024 live rows per workgroup in registers, the hypotheses
+ * uniform per wave; ballot and popcount per wave, LDS per workgroup, one integer atomicAdd per workgroup and hypothesis), an argmax per
+ * cloud, the inlier flags and block sums, one lane per cloud for the sums, the sweeps and the plane, the float64 flags, and the
+ * labels.  The K rounds are a host loop with no host read; a finished cloud's later rounds do nothing.  Integer atomics only; every
+ * loop is bounded by H, K, the cloud's length or 64; every index read from the scratch is clamped before it addresses anything.
+ * scratch: rald_post_plane_scratch_bytes of the same batch, n_total, bound, H and K (one size serves both calls), 16-byte aligned,
+ * never NULL; -1 (and rald_last_error) for sizes the calls refuse.  Every invalid argument is refused with a status before any GPU
+ * work. */
+int64_t rald_post_plane_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int32_t num_hypotheses, int32_t max_planes);
+int rald_post_plane_segment_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                   int64_t n_total, int64_t max_per_sample, float threshold, int32_t num_hypotheses, int32_t max_planes,
+                                   int32_t min_inliers, int32_t refine, int64_t seed, const float* view3_host, int32_t* out_labels,
+                                   double* out_planes, int32_t* out_num_planes, int32_t* out_inliers, int32_t* out_best, void* scratch,
+                                   int64_t scratch_bytes, void* stream);
+int rald_post_plane_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, float threshold, int32_t num_hypotheses, int32_t max_planes,
+                                  int32_t min_inliers, int32_t refine, int64_t seed, const float* view3_host, int32_t keep_planes,
+                                  float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, double* out_planes,
+                                  int32_t* out_num_planes, void* scratch, int64_t scratch_bytes, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

@@ -631,6 +631,33 @@ int rald_op_cluster_filter_ragged(const float* points, const int64_t* offsets, c
                                  out_num_clusters, scratch, scratch_bytes, chunk, (hipStream_t)stream);
 }
 
+// ---- RANSAC plane segmentation and plane removal ------------------------------------------
+int64_t rald_post_plane_scratch_bytes(int32_t batch, int64_t n_total, int64_t max_per_sample, int32_t num_hypotheses, int32_t max_planes) {
+    const int64_t n = plane_scratch_bytes(batch, n_total, max_per_sample, num_hypotheses, max_planes);
+    if (n < 0)
+        set_error("rald_post_plane_scratch_bytes: batch 1 .. 65535, n_total 0 .. 2^31 - 1, max_per_sample 1 .. 2^24, num_hypotheses 1 .. 65536, "
+                  "max_planes 1 .. 8");
+    return n;
+}
+int rald_post_plane_segment_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                   int64_t n_total, int64_t max_per_sample, float threshold, int32_t num_hypotheses, int32_t max_planes,
+                                   int32_t min_inliers, int32_t refine, int64_t seed, const float* view3_host, int32_t* out_labels,
+                                   double* out_planes, int32_t* out_num_planes, int32_t* out_inliers, int32_t* out_best, void* scratch,
+                                   int64_t scratch_bytes, void* stream) {
+    return plane_segment_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), threshold, num_hypotheses,
+                                max_planes, min_inliers, refine, seed, view3_host, out_labels, out_planes, out_num_planes, out_inliers, out_best,
+                                scratch, scratch_bytes, (hipStream_t)stream);
+}
+int rald_post_plane_filter_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                  int64_t n_total, int64_t max_per_sample, float threshold, int32_t num_hypotheses, int32_t max_planes,
+                                  int32_t min_inliers, int32_t refine, int64_t seed, const float* view3_host, int32_t keep_planes,
+                                  float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, double* out_planes,
+                                  int32_t* out_num_planes, void* scratch, int64_t scratch_bytes, void* stream) {
+    return plane_filter_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), threshold, num_hypotheses,
+                               max_planes, min_inliers, refine, seed, view3_host, keep_planes, out_points, out_offsets, out_index, out_labels,
+                               out_planes, out_num_planes, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

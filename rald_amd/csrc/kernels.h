@@ -397,6 +397,17 @@ int cluster_filter_ragged(const RaggedCloud& c, const GridSpec& grid, float eps,
                           float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, int32_t* out_num_clusters,
                           void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
 
+// ---------------------------------------------------------------- cloud_plane.hip
+// RANSAC plane segmentation with a fixed number of counter-based hypotheses, up to max_planes planes peeled in turn, and the filter that
+// keeps the planes' rows or everything else
+int64_t plane_scratch_bytes(int B, int64_t n_total, int64_t max_per_sample, int num_hypotheses, int max_planes);
+int plane_segment_ragged(const RaggedCloud& c, float threshold, int num_hypotheses, int max_planes, int min_inliers, int refine, int64_t seed,
+                         const float* view3_host, int32_t* out_labels, double* out_planes, int32_t* out_num_planes, int32_t* out_inliers,
+                         int32_t* out_best, void* scratch, int64_t scratch_bytes, hipStream_t st);
+int plane_filter_ragged(const RaggedCloud& c, float threshold, int num_hypotheses, int max_planes, int min_inliers, int refine, int64_t seed,
+                        const float* view3_host, int keep_planes, float* out_points, int64_t* out_offsets, int64_t* out_index,
+                        int32_t* out_labels, double* out_planes, int32_t* out_num_planes, void* scratch, int64_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

@@ -154,7 +154,8 @@ def _batch_queries(grid: torch.Tensor, n_grid, helpers: List[Optional[torch.Tens
 def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                               rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None,
                               normals: bool = False, surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                              thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None):
+                              thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None,
+                              remove_planes=None):
     """infer_point_clouds (see there for the options) without its readback -> a tuple, all on the device, in this order:
     points [T_cap,3], offsets int64 [B+1], cd float64 [B] or None: frame b's prediction is points[offsets[b]:offsets[b+1]];
     with `metric_thresholds` (a sequence of distances, () included) the dict of postprocess.cloud_metrics_ragged (None where no metric
@@ -163,28 +164,32 @@ def infer_point_clouds_device(vae, sampled_tokens: torch.Tensor, args, helper_po
     with `denoise`, `denoise_statistical` or `denoise_cluster`: denoised [T_cap,3], denoise_offsets int64 [B+1], denoise_index int64
     [T_cap], cd_denoised float64 [B] or None and, with `metric_thresholds`, the dict of the denoised clouds' metrics (or None); behind
     them denoise_stats float64 [B,3] (mu, sigma, the threshold) of the statistical filter, or denoise_labels int32 [T_cap] (per row of
-    `denoised`) and n_clusters int32 [B] of the cluster filter; thin and resample then run on the denoised clouds, their indices count its rows;
+    `denoised`) and n_clusters int32 [B] of the cluster filter, or with `remove_planes` denoise_labels int32 [T_cap], planes float64
+    [B, max_planes, 4] and num_planes int32 [B]; thin and resample then run on the denoised clouds, their indices count its rows;
     with `thin`: thinned [T_cap,3], thin_offsets int64 [B+1], thin_count int32 [T_cap], thin_first int64 [T_cap] - frame b's voxels are
     rows thin_offsets[b] .. thin_offsets[b+1]-1; with `resample=k`, last, the resampled clouds [B,k,3] and their row indices [B,k]
     (rows of the frame's thinned cloud with `thin`).  With a device generator (`rng`) or explicit `draws` nothing is read to the host
     and the device is not synchronised."""
     t, thinned, resampled = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals,
                                             surface_steps, surface_max_step, resample, thin, denoise, denoise_statistical, normal_consistency,
-                                            denoise_cluster)
+                                            denoise_cluster, remove_planes)
     with_metrics, den = metric_thresholds is not None, t.denoised
     out = (t.points, t.offsets, t.cd) + ((t.metrics,) if with_metrics else ()) + ((t.normals,) if t.normals is not None else ()) + (t.ncons or ())
     if den is not None:
         out += (den.points, den.offsets, den.index, den.cd) + ((den.metrics,) if with_metrics else ())
-        out += ((den.stats,) if den.stats is not None else ()) + ((den.labels, den.n_clusters) if den.labels is not None else ())
+        out += ((den.stats,) if den.stats is not None else ()) + ((den.labels, den.n_clusters) if den.n_clusters is not None else ())
+        out += (den.labels, den.planes, den.n_planes) if den.planes is not None else ()
     return out + (thinned or ()) + (resampled or ())
 
 
 @dataclass
 class _Denoised:
-    """The tail's clouds behind one of the three filters, on the device: the kept rows, their offsets int64 [B+1], their rows in the full
-    cloud, cd / metrics against the same surfaces; stats float64 [B,3] (statistical), labels int32 per kept row, n_clusters int32 [B] (cluster)."""
+    """The tail's clouds behind one of the four filters, on the device: the kept rows, their offsets int64 [B+1], their rows in the full
+    cloud, cd / metrics against the same surfaces; stats float64 [B,3] (statistical), labels int32 per kept row (cluster, plane),
+    n_clusters int32 [B] (cluster), planes float64 [B,K,4] and n_planes int32 [B] (plane)."""
     points: torch.Tensor; offsets: torch.Tensor; index: torch.Tensor; cd: Optional[torch.Tensor] = None; metrics: Optional[dict] = None
     stats: Optional[torch.Tensor] = None; labels: Optional[torch.Tensor] = None; n_clusters: Optional[torch.Tensor] = None
+    planes: Optional[torch.Tensor] = None; n_planes: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -196,7 +201,8 @@ class _Tail:
     metrics: Optional[dict]; normals: Optional[torch.Tensor]; longest: int; denoised: Optional[_Denoised]; ncons: Optional[tuple]
 
 
-# the three filters as _check_denoise, _check_denoise_statistical and _check_denoise_cluster return them, plain tuples with names: each
+# the four filters as _check_denoise, _check_denoise_statistical, _check_denoise_cluster and _check_remove_planes return them, plain
+# tuples with names: each
 # run(points, offsets, bound) -> the _Denoised clouds, with the kept rows' indices and what its filter adds
 class _RadiusFilter(NamedTuple):
     radius: float; min_neighbors: int; grid: tuple
@@ -222,6 +228,16 @@ class _ClusterFilter(NamedTuple):
                                                                      self.grid, bound, largest_only=self.largest_only, return_index=True,
                                                                      return_labels=True)
         return _Denoised(pts, off, idx, labels=labels, n_clusters=num)
+
+
+class _PlaneFilter(NamedTuple):
+    kind: str; threshold: float; num_hypotheses: int; max_planes: int; keep_planes: bool; seed: int
+
+    def run(self, points, offsets, bound) -> _Denoised:
+        pts, off, idx, labels, planes, num = PP.remove_planes_ragged(points, offsets, self.threshold, bound, self.num_hypotheses,
+                                                                     self.max_planes, seed=self.seed, view=(0.0, 0.0, 0.0),
+                                                                     keep_planes=self.keep_planes, return_index=True, return_labels=True)
+        return _Denoised(pts, off, idx, labels=labels, planes=planes, n_planes=num)
 
 
 def _check_resample(resample) -> Optional[int]:
@@ -306,6 +322,33 @@ def _check_denoise_cluster(clu, denoise, stat, args):
     return _ClusterFilter("cluster", eps, min_points, PP._cluster_size(min_size), bool(largest), _thin_grid(eps, args))
 
 
+def _check_remove_planes(rp, denoise, stat, clu, rng):
+    """`remove_planes` (None, or (threshold, num_hypotheses), (threshold, num_hypotheses, max_planes) or (threshold, num_hypotheses,
+    max_planes, keep_planes)) -> None or ('plane', threshold, num_hypotheses, max_planes, keep_planes, seed): the seed is the low 32 bits
+    of `rng`'s initial seed (a host value) if the call has a generator, else 0.  ValueError for anything else and for any of the three
+    other filters given as well (chaining the filters is not offered), on the host."""
+    if rp is None:
+        return None
+    if denoise is not None or stat is not None or clu is not None:
+        raise ValueError("remove_planes excludes denoise, denoise_statistical and denoise_cluster")
+    message = ("remove_planes must be None, (threshold, num_hypotheses), (threshold, num_hypotheses, max_planes) or "
+               "(threshold, num_hypotheses, max_planes, keep_planes)")
+    try:
+        rp = tuple(rp)
+    except TypeError:
+        raise ValueError(message) from None
+    if len(rp) not in (2, 3, 4):
+        raise ValueError(message)
+    threshold, H = rp[:2]
+    K, keep = (rp[2] if len(rp) >= 3 else 1), (rp[3] if len(rp) == 4 else False)
+    threshold = _positive(threshold, "remove_planes: threshold must be a finite number > 0")
+    H = _whole(H, 1, PP.PLANE_MAX_HYPOTHESES, f"remove_planes: num_hypotheses must be an integer in 1 .. {PP.PLANE_MAX_HYPOTHESES}")
+    K = _whole(K, 1, PP.PLANE_MAX_PLANES, f"remove_planes: max_planes must be an integer in 1 .. {PP.PLANE_MAX_PLANES}")
+    if not isinstance(keep, (bool, int)) or keep not in (0, 1):
+        raise ValueError("remove_planes: keep_planes must be a bool")
+    return _PlaneFilter("plane", threshold, H, K, bool(keep), int(rng.initial_seed()) & 0xFFFFFFFF if rng is not None else 0)
+
+
 def _check_normal_consistency(nc, args, surfaces, normals, surface_steps):
     """`normal_consistency` (None, or (k, cell)) -> None or (k, grid): the search grid of the surfaces' normals is _thin_grid's box with
     the cell edge `cell`.  ValueError for anything else, for a cell that gives the box more than 2^31 - 1 cells, and where the tail has
@@ -370,13 +413,14 @@ class _HostPack:
 
 
 def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals, surface_steps, surface_max_step,
-                    resample, thin, denoise, denoise_statistical, normal_consistency, denoise_cluster):
+                    resample, thin, denoise, denoise_statistical, normal_consistency, denoise_cluster, remove_planes=None):
     """What both batched entry points do, with their arguments -> (_Tail, _thin's four or None, _resample's pair or None): every option
     checked on the host, the batched tail on the device, the filter chosen behind the metric of the full cloud with a metric of its own,
     then the finishing chain on the denoised clouds if there are any, else on the full ones: thin, then resample."""
     resample, thin_grid = _check_resample(resample), _thin_grid(thin, args)
-    # at most one of the three filters: each check refuses the ones named before it ("exclude each other" / "excludes")
-    denoise = (_check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
+    # at most one of the four filters: each check refuses the ones named before it ("exclude each other" / "excludes")
+    denoise = (_check_remove_planes(remove_planes, denoise, denoise_statistical, denoise_cluster, rng)
+               or _check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
                or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
     ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
     oriented = bool(normals) or int(surface_steps) > 0
@@ -481,7 +525,8 @@ def _numpy_refine_draws(p_off: torch.Tensor, aug_num: int, scale: int, dev) -> d
 def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=None, surfaces: Optional[torch.Tensor] = None,
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
                        surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
-                       thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None) -> Dict[str, object]:
+                       thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None,
+                       remove_planes=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -548,6 +593,16 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     and `resample` as `denoise` does, and adds 'denoise_labels', a list of int32 [m_b] (per row of 'denoised' its cluster in the frame's
     numbering before the filter), and 'n_clusters', B ints carried in the one host read.  Given together with `denoise` or
     `denoise_statistical` it raises ValueError.
+    `remove_planes` (None, or (threshold, num_hypotheses), (threshold, num_hypotheses, max_planes) or (threshold, num_hypotheses,
+    max_planes, keep_planes)): RANSAC plane removal in `denoise`'s place - up to max_planes (default 1) planes are found in turn, each
+    the best of num_hypotheses (a fixed number) three-row hypotheses by its rows within `threshold`, re-fitted to them, from
+    postprocess.remove_planes_ragged (min_inliers 3, the planes turned towards the sensor at the origin) - and the
+    rows of no plane stay (ground removal), with keep_planes the rows of the planes (the faces of an indoor scene).  The hypotheses'
+    seed is the low 32 bits of `rng.initial_seed()` when the call has a generator `rng`, else 0: the same call gives the same planes.
+    It fills the keys of `denoise`, feeds `thin` and `resample` as `denoise` does, and adds 'denoise_labels', a list of int32 [m_b]
+    (per row of 'denoised' the plane that took it, -1 for none), 'planes', per frame the list of its planes found as 4-tuples (a, b, c,
+    d) of floats, and 'num_planes', B ints, both carried in the one host read.  Given together with any of the three other filters it
+    raises ValueError.
     `normal_consistency` (None, or (k, cell)): the third standard metric of occupancy-field work beside Chamfer and F-score.  It needs
     `surfaces` and the predicted normals (`normals` or `surface_steps`), else ValueError before any GPU work.  The ground-truth clouds
     carry coordinates only, so their normals are estimated first - PCA over each row's k nearest
@@ -560,12 +615,13 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     'n_queries': list of B ints} and the keys that the options above add."""
     t, thinned, resampled = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals,
                                             surface_steps, surface_max_step, resample, thin, denoise, denoise_statistical, normal_consistency,
-                                            denoise_cluster)
+                                            denoise_cluster, remove_planes)
     B, den, nrm = sampled_tokens.shape[0], t.denoised, t.normals
     groups = {"offsets": t.offsets, "n_queries": t.n_queries, "cd": t.cd, "metrics": t.metrics,
               "normal_consistency": t.ncons and t.ncons[0], "thin_offsets": thinned and thinned[1]}
     if den is not None:
-        groups.update(denoise_offsets=den.offsets, cd_denoised=den.cd, metrics_denoised=den.metrics, denoise_stats=den.stats, n_clusters=den.n_clusters)
+        groups.update(denoise_offsets=den.offsets, cd_denoised=den.cd, metrics_denoised=den.metrics, denoise_stats=den.stats, n_clusters=den.n_clusters,
+                      planes=den.planes, num_planes=den.n_planes)
     host = _HostPack(**groups).read()
     ints = lambda name: [int(v) for v in host[name]]
     frames = lambda rows, name: [rows[lo:hi] for lo, hi in zip(ints(name), ints(name)[1:])]         # a ragged tensor by its offsets' host copy
@@ -588,7 +644,13 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
         if den.stats is not None:
             out["denoise_stats"] = triples("denoise_stats")
         if den.labels is not None:
-            out["denoise_labels"], out["n_clusters"] = frames(den.labels, "denoise_offsets"), ints("n_clusters")
+            out["denoise_labels"] = frames(den.labels, "denoise_offsets")
+        if den.n_clusters is not None:
+            out["n_clusters"] = ints("n_clusters")
+        if den.planes is not None:
+            K, flat = den.planes.shape[1], host["planes"]
+            out["num_planes"] = ints("num_planes")
+            out["planes"] = [[tuple(flat[(b * K + k) * 4:(b * K + k) * 4 + 4]) for k in range(out["num_planes"][b])] for b in range(B)]
     if t.ncons is not None:
         out["normal_consistency"], out["surface_normals"] = triples("normal_consistency"), list(t.ncons[1].split(surfaces.shape[1]))
     if thinned is not None:

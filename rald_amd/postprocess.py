@@ -14,7 +14,9 @@ grid, the device counterpart of Open3D's ``voxel_down_sample``; DESIGN.md sectio
 Open3D's ``remove_radius_outlier``), ``knn_ragged`` / ``remove_statistical_outliers*`` (the k nearest other rows
 inside a cloud and the outlier filter on their mean distance), and ``estimate_normals*`` /
 ``normal_consistency*`` (PCA normals, surface variation and eigenvalues from those neighbours, and the normal-consistency metric of two
-clouds with normals).
+clouds with normals), ``cluster_dbscan*`` / ``remove_small_clusters*`` (density clustering; DESIGN.md section
+25), and ``segment_plane*`` / ``remove_planes*`` (RANSAC plane segmentation with a fixed number of counter-based hypotheses, the device
+counterpart of Open3D's ``segment_plane``, and plane removal).
 """
 from __future__ import annotations
 
@@ -952,6 +954,141 @@ def estimate_normals(points: torch.Tensor, k: int, view: Optional[Sequence[float
         return points.new_zeros(0, 3, dtype=torch.float32)
     p, off, grid, N = one
     return estimate_normals_ragged(p, off, k, grid, N, view=view)
+
+
+PLANE_MAX_HYPOTHESES = 65536                             # the largest num_hypotheses and max_planes of rald_post_plane_segment_ragged
+PLANE_MAX_PLANES = 8
+
+
+def _plane_args(points, threshold, max_per_sample, num_hypotheses, max_planes, min_inliers, refine, seed, view, counts, B: Optional[int]):
+    """The rules of the plane calls (ValueError, before anything asks where a tensor lives) -> (threshold as the float32 the kernels use,
+    max_per_sample, H, K, min_inliers, refine as 0 / 1, seed, the view's ctypes array or None)."""
+    max_per_sample, _ = _voxel_args(points, max_per_sample, counts, B, 0)
+    threshold = _f32(_positive(threshold, "threshold must be a finite number > 0"))
+    if not threshold > 0 or not math.isfinite(threshold):
+        raise ValueError("threshold must fit float32")
+    H = _whole(num_hypotheses, 1, PLANE_MAX_HYPOTHESES, f"num_hypotheses must be an integer in 1 .. {PLANE_MAX_HYPOTHESES}")
+    K = _whole(max_planes, 1, PLANE_MAX_PLANES, f"max_planes must be an integer in 1 .. {PLANE_MAX_PLANES}")
+    min_inliers = _whole(min_inliers, 3, 2 ** 31 - 1, "min_inliers must be an integer >= 3")
+    if not isinstance(refine, (bool, int)) or refine not in (0, 1):
+        raise ValueError("refine must be a bool")
+    seed = _whole(seed, -2 ** 63, 2 ** 63 - 1, "seed must be an integer that fits int64")
+    return threshold, max_per_sample, H, K, min_inliers, int(refine), seed, _view_arg(view)
+
+
+def _plane_call(entry: str, points, offsets, counts, B: int, T: int, dev, max_per_sample: int, H: int, K: int, args) -> None:
+    L = lib()
+    nbytes = _nbytes(L.rald_post_plane_scratch_bytes(B, T, max_per_sample, H, K))
+    scratch = _scratch(nbytes, dev)
+    check(getattr(L, entry)(points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample, *args, scratch.data_ptr(), nbytes,
+                            _stream()))
+
+
+def segment_planes_ragged(points: torch.Tensor, offsets: torch.Tensor, threshold: float, max_per_sample: int, num_hypotheses: int = 1024,
+                          max_planes: int = 1, min_inliers: int = 3, refine: bool = True, seed: int = 0,
+                          view: Optional[Sequence[float]] = None, counts: Optional[torch.Tensor] = None, return_best: bool = False):
+    """RANSAC plane segmentation per cloud of a ragged batch (rald_post_plane_segment_ragged), the device
+    counterpart of Open3D's segment_plane, repeated up to max_planes (1 .. 8) times on what the earlier planes left: points [T,3],
+    offsets int64 [B+1] on the device -> (labels int32 [T], planes float64 [B, max_planes, 4], num_planes int32 [B], inliers int32
+    [B, max_planes]) on the device.  Every round draws num_hypotheses (1 .. 65536, a FIXED number: no early termination) triples of
+    the rows still unlabelled from a counter-based Philox generator keyed by `seed` (mod 2^32) - the same triples in every cloud of
+    the same length, in every call - counts for each the rows within `threshold` of its plane (fp32, without a root or a division),
+    and takes the hypothesis of the most inliers (the smallest number on equal counts) if it has at least min_inliers (>= 3).  refine
+    re-fits the plane to those inliers (float64 centroid and covariance, the smallest eigenvector) and re-marks the inliers in
+    float64.  A plane is (a, b, c, d) with a unit normal turned towards `view` (3 numbers, default the origin) and a x + b y + c z +
+    d = 0; rows of planes not found are NaN, their inliers 0.  labels, laid out like points: the round that took the row, -1 for a row
+    no plane took, -2 for a row with a NaN or an inf.  return_best adds best int32 [B, max_planes], the winning hypothesis of each
+    plane (-1: none).  Rows past offsets[B] or behind counts / the bound are unspecified.  counts, max_per_sample: as
+    voxel_downsample_ragged.  Defined to the bit: a function of the rows, the arguments and the seed alone.  No host read, no
+    synchronisation; runs on the current stream."""
+    t, max_per_sample, H, K, min_inliers, refine, seed, view3 = _plane_args(points, threshold, max_per_sample, num_hypotheses, max_planes,
+                                                                            min_inliers, refine, seed, view, counts,
+                                                                            _offsets_shape(offsets, "offsets"))
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
+    labels = torch.empty(T, device=dev, dtype=torch.int32)
+    planes = torch.empty(B, K, 4, device=dev, dtype=torch.float64)
+    num = torch.empty(B, device=dev, dtype=torch.int32)
+    inliers = torch.empty(B, K, device=dev, dtype=torch.int32)
+    best = torch.empty(B, K, device=dev, dtype=torch.int32)
+    if T == 0:                                                                       # no rows: an empty tensor has no address to pass
+        planes.fill_(float("nan"))
+        num.zero_()
+        inliers.zero_()
+        best.fill_(-1)
+    else:
+        _plane_call("rald_post_plane_segment_ragged", points, offsets, counts, B, T, dev, max_per_sample, H, K,
+                    (t, H, K, min_inliers, refine, seed, view3, labels.data_ptr(), planes.data_ptr(), num.data_ptr(), inliers.data_ptr(),
+                     best.data_ptr()))
+    return (labels, planes, num, inliers) + ((best,) if return_best else ())
+
+
+def remove_planes_ragged(points: torch.Tensor, offsets: torch.Tensor, threshold: float, max_per_sample: int, num_hypotheses: int = 1024,
+                         max_planes: int = 1, min_inliers: int = 3, refine: bool = True, seed: int = 0,
+                         view: Optional[Sequence[float]] = None, counts: Optional[torch.Tensor] = None, keep_planes: bool = False,
+                         return_index: bool = False, return_labels: bool = False):
+    """Plane removal per cloud of a ragged batch (rald_post_plane_filter_ragged): segment_planes_ragged, then
+    the rows that no plane took stay (ground removal at max_planes = 1) or, with keep_planes, the rows of the planes; rows with a NaN
+    or an inf never stay.  -> (points [T,3], out_offsets int64 [B+1], ...) on the device, sized for the worst case: cloud b's kept
+    rows are rows out_offsets[b] .. out_offsets[b+1]-1 in their ORIGINAL order, bit for bit the input rows; rows past out_offsets[B]
+    are unspecified.  Then, for every flag set: index int64 [T] (per kept row, its row in its cloud), (labels int32 [T], planes
+    float64 [B, max_planes, 4], num_planes int32 [B]) (per kept row its label of segment_planes_ragged; the planes and their number).
+    Arguments as segment_planes_ragged.  No host read, no synchronisation; runs on the current stream."""
+    t, max_per_sample, H, K, min_inliers, refine, seed, view3 = _plane_args(points, threshold, max_per_sample, num_hypotheses, max_planes,
+                                                                            min_inliers, refine, seed, view, counts,
+                                                                            _offsets_shape(offsets, "offsets"))
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
+    out = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    out_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    index = torch.empty(T, device=dev, dtype=torch.int64) if return_index else None
+    labels = torch.empty(T, device=dev, dtype=torch.int32)
+    planes = torch.empty(B, K, 4, device=dev, dtype=torch.float64)
+    num = torch.empty(B, device=dev, dtype=torch.int32)
+    if T == 0:
+        out_offsets.zero_()
+        planes.fill_(float("nan"))
+        num.zero_()
+    else:
+        _plane_call("rald_post_plane_filter_ragged", points, offsets, counts, B, T, dev, max_per_sample, H, K,
+                    (t, H, K, min_inliers, refine, seed, view3, int(bool(keep_planes)), out.data_ptr(), out_offsets.data_ptr(), _opt(index),
+                     labels.data_ptr(), planes.data_ptr(), num.data_ptr()))
+    return (out, out_offsets) + ((index,) if return_index else ()) + ((labels, planes, num) if return_labels else ())
+
+
+def _plane_one(points, threshold, num_hypotheses, max_planes, min_inliers, refine, seed, view):
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [N, 3]")
+    if points.shape[0] > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _plane_args(points, threshold, 1, num_hypotheses, max_planes, min_inliers, refine, seed, view, None, None)
+
+
+def segment_plane(points: torch.Tensor, threshold: float, num_hypotheses: int = 1024, min_inliers: int = 3, refine: bool = True,
+                  seed: int = 0, view: Optional[Sequence[float]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One cloud [N,3] -> (plane float64 [4], inlier index int64 [m]) on the device, Open3D's shape of segment_plane's result
+    (distance_threshold = threshold, num_iterations = num_hypotheses, ransac_n = 3): segment_planes_ragged's one plane and the rows
+    it took, ascending.  Without a plane: NaN and no rows.  The index's length is a host read."""
+    _plane_one(points, threshold, num_hypotheses, 1, min_inliers, refine, seed, view)
+    N = points.shape[0]
+    if N == 0:
+        return torch.full((4,), float("nan"), dtype=torch.float64, device=points.device), torch.zeros(0, dtype=torch.int64, device=points.device)
+    _need_cuda(points, "points")
+    off = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    labels, planes, _, _ = segment_planes_ragged(points, off, threshold, N, num_hypotheses, 1, min_inliers, refine, seed, view)
+    return planes[0, 0], torch.nonzero(labels == 0).reshape(-1)
+
+
+def remove_planes(points: torch.Tensor, threshold: float, num_hypotheses: int = 1024, max_planes: int = 1, min_inliers: int = 3,
+                  refine: bool = True, seed: int = 0, view: Optional[Sequence[float]] = None, keep_planes: bool = False) -> torch.Tensor:
+    """One cloud [N,3] -> [m,3]: remove_planes_ragged's kept rows, in their order.  The result's length is a host read."""
+    _plane_one(points, threshold, num_hypotheses, max_planes, min_inliers, refine, seed, view)
+    N = points.shape[0]
+    if N == 0:
+        return points.new_zeros(0, 3, dtype=torch.float32)
+    _need_cuda(points, "points")
+    off = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    out, out_off = remove_planes_ragged(points, off, threshold, N, num_hypotheses, max_planes, min_inliers, refine, seed, view,
+                                        keep_planes=keep_planes)
+    return out[:int(out_off[1].item())]
 
 
 def _normals_of(t, points, what: str) -> None:
