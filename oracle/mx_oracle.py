@@ -10,7 +10,18 @@ import torch
 
 
 def quantize_mx8(x):
-    """x [..., K] float -> (q uint8 e4m3 bytes [..., K], scales uint8 e8m0 [..., K/32])."""
+    """x [..., K] float -> (q uint8 e4m3 bytes [..., K], scales uint8 e8m0 [..., K/32]).
+
+    Pinned byte for byte by the float64 reference of tests/test_mx8_host.py (a table of the e4m3 magnitudes, no float8 type) at every
+    rounding and scale boundary, fp32-subnormal blocks included (nothing flushes).
+
+    Non-finite inputs are outside the format's contract (e4m3fn has no infinity, and the e8m0 NaN byte 255 is never written).  What each
+    side does with them all the same:
+      +-Inf: this oracle and the HIP quantiser (csrc/mx8.h) agree - the block's scale byte is 247, the element is +-448 and the block's
+        finite elements are taken at 2^-120 (tests/test_gpu_mx8.py::test_quantize_non_finite_inputs);
+      NaN: this oracle gives the element 0x7F (NaN) and the block scale byte 247, because amax is NaN; the HIP quantiser drops the NaN
+        from amax (fmaxf), keeps the scale of the block's finite elements and writes -448 (0xFE) for the element (the clamp's fmaxf /
+        fminf).  Neither touches another block."""
     x = torch.as_tensor(x, dtype=torch.float32)
     K = x.shape[-1]
     blk = x.reshape(*x.shape[:-1], K // 32, 32)
@@ -24,10 +35,12 @@ def quantize_mx8(x):
     return q.reshape(x.shape), sb.to(torch.uint8)
 
 
-def dequantize_mx8(q, scales):
-    q = torch.as_tensor(q).view(torch.float8_e4m3fn).to(torch.float32)
+def dequantize_mx8(q, scales, dtype=torch.float32):
+    """element x 2^(scale byte - 127) in `dtype`.  float32 holds every value the quantiser above produces from float32 input; bytes built by
+    hand can exceed it (4 x 2^127 at scale byte 254): float64 holds them all."""
+    q = torch.as_tensor(q).view(torch.float8_e4m3fn).to(dtype)
     K = q.shape[-1]
-    s = torch.pow(2.0, torch.as_tensor(scales).to(torch.float32) - 127.0)
+    s = torch.pow(2.0, torch.as_tensor(scales).to(dtype) - 127.0)
     return (q.reshape(*q.shape[:-1], K // 32, 32) * s[..., None]).reshape(q.shape)
 
 

@@ -903,16 +903,17 @@ def op_quantize_mx8(x: torch.Tensor):
 
 
 def op_gemm_mx8(A8: torch.Tensor, sA: torch.Tensor, B8: torch.Tensor, sB: torch.Tensor, bias: Optional[torch.Tensor] = None,
-                epilogue: int = 0, C_inout: Optional[torch.Tensor] = None, alpha: float = 1.0) -> torch.Tensor:
+                epilogue: int = 0, C_inout: Optional[torch.Tensor] = None, alpha: float = 1.0, alpha_ncols: int = 1 << 30) -> torch.Tensor:
     """A8 [batch?,M,K] / B8 [batch?,N,K] uint8 (e4m3) with scales [.., K/32] uint8 (e8m0) -> C = alpha*A.B^T + bias.
-    epilogue 0 bf16, 1 f32, 2 f32 accumulate into C_inout."""
+    epilogue 0 bf16, 1 f32, 2 f32 accumulate into C_inout (with 0 / 1 a given C_inout is the output buffer, of the epilogue's type);
+    alpha applies to the columns n < alpha_ncols only."""
     batched = A8.dim() == 3 or B8.dim() == 3
     batch = (A8.shape[0] if A8.dim() == 3 else B8.shape[0]) if batched else 1
     M, K = A8.shape[-2], A8.shape[-1]
     N = B8.shape[-2]
     if B8.shape[-1] != K or sA.shape[-1] != K // 32 or sB.shape[-1] != K // 32 or not (sA.is_contiguous() and sB.is_contiguous()):
         raise ValueError("op_gemm_mx8: operand / scale shapes do not match")
-    if epilogue == 2:
+    if epilogue == 2 or C_inout is not None:
         out = C_inout
     else:
         shape = (batch, M, N) if batched else (M, N)
@@ -921,7 +922,7 @@ def op_gemm_mx8(A8: torch.Tensor, sA: torch.Tensor, B8: torch.Tensor, sB: torch.
                                  sA.stride(0) if sA.dim() == 3 else 0, B8.data_ptr(), sB.data_ptr(), B8.stride(-2),
                                  B8.stride(0) if B8.dim() == 3 else 0, sB.stride(0) if sB.dim() == 3 else 0, out.data_ptr(),
                                  out.stride(-2), out.stride(0) if out.dim() == 3 else 0, _opt(bias),
-                                 M, N, K, batch, alpha, epilogue, _stream()))
+                                 M, N, K, batch, alpha, epilogue, _stream(), alpha_ncols))
     return out
 
 

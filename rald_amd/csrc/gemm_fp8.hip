@@ -86,9 +86,14 @@ int gemm_mx8(const Mx8Args& a0, int epi, hipStream_t st) {
     a.g.flags = GEMM_NT_STORE;                 // streamed (non-temporal) bf16 output, as in gemm_nt
     if (g.out8) RALD_CHECK(epi == EPI_GEGLU && g.outs && g.batch == 1 && g.M % 256 == 0 && g.N % 256 == 0 && (int64_t)(g.M / 256) * (g.N / 256) >= 256,
                            "gemm_mx8: the MXFP8 output form needs the GEGLU epilogue on full 256x256 tiles");
-    const int64_t wg256 = (int64_t)(g.M / 256) * (g.N / 256) * g.batch;
-    if (g.M % 256 == 0 && g.N % 256 == 0 && wg256 >= 256) return launch_mx8<256, 256, 4, 2>(a, epi, st);
+    if (gemm_mx8_tile(g.M, g.N, g.batch) == 256) return launch_mx8<256, 256, 4, 2>(a, epi, st);
     return launch_mx8<128, 128, 2, 2>(a, epi, st);
+}
+
+// The tile gemm_mx8 runs a problem on (rows = columns): 256 for full 256 x 256 tiles, at least 256 of them over the batch, else 128.
+int gemm_mx8_tile(int M, int N, int batch) {
+    const int64_t wg256 = (int64_t)(M / 256) * (N / 256) * batch;
+    return (M % 256 == 0 && N % 256 == 0 && wg256 >= 256) ? 256 : 128;
 }
 
 // =================================================================================================

@@ -427,6 +427,7 @@ struct Mx8Args {
     int64_t strideSA, strideSB;
 };
 int gemm_mx8(const Mx8Args& a, int epi, hipStream_t st);
+int gemm_mx8_tile(int M, int N, int batch);        // 256 or 128: the tile gemm_mx8 runs such a problem on
 int quantize_mx8(const void* in, int in_is_bf16, int64_t ld_in, unsigned char* q, int64_t ld_q, unsigned char* scales, int64_t rows, int K,
                  hipStream_t st);
 // small-M split-K residual GEMM + (optional) LayerNorm: see norm.hip.  splitk_for() = 0 when it does not pay.
