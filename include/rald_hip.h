@@ -665,6 +665,91 @@ int rald_post_plane_filter_ragged(const float* points, const int64_t* offsets, c
                                   int32_t min_inliers, int32_t refine, int64_t seed, const float* view3_host, int32_t keep_planes,
                                   float* out_points, int64_t* out_offsets, int64_t* out_index, int32_t* out_labels, double* out_planes,
                                   int32_t* out_num_planes, void* scratch, int64_t scratch_bytes, void* stream);
+/* ---- ICP registration of ragged clouds, point-to-point and point-to-plane, and the rigid transform of a ragged batch (DESIGN.md
+ * section 27).  Defined to the bit: the result is a function of (rows, normals, arguments) alone, the same in every call, at every batch
+ * position, for every chunk length and for every grid the call accepts over the same box.
+ *   PAIR b: the source cloud S_b (source / src_offsets / src_counts / src_n_dense / n_src_total / max_src: the layout of the other
+ *   ragged calls) and the target cloud T_b (the same with its own arrays) of the same batch position; mode 1: target_normals fp32
+ *   [n_tgt_total, 3], laid out like target (mode 0: ignored, may be NULL); init DEVICE float64 [batch, 12] = R row-major then t, NULL =
+ *   the identity.
+ *   HOST parameters: mode 0 = point, 1 = plane; max_distance finite and > 0; max_iterations 1 .. 64; tolerance a double >= 0;
+ *   min_correspondences >= 1; the grid lo3 / v3 / dims3 as in the radius calls, every cell edge >= max_distance.
+ *   The TARGET is indexed on the grid; a target row outside it (INSIDE is the radius calls' rule; NaN and +-inf rows are outside) is
+ *   nobody's candidate.  The grid does not show otherwise.
+ *   All float64 arithmetic below is one rounded operation at a time, no contraction, only + - * / and the correctly rounded square
+ *   root; brackets give the order.  For iteration i = 0 .. max_iterations - 1 of a pair that is not finished, with its (R, t):
+ *   1 MOVE.  A source row p is USABLE iff its three coordinates are finite.  p'_k = ((R_k0 px + R_k1 py) + R_k2 pz) + t_k, the
+ *     coordinates converted to float64 first; pf = fp32(p').
+ *   2 CORRESPOND.  q(p) = the inside target row of the smallest d2 = rad_d2(pf, q) = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), dx =
+ *     fl(q.x - pf.x), all fp32, among those with d2 <= fl(max_distance * max_distance); the LOWEST target row index (from the cloud's
+ *     first target row) on equal d2.  The scan range around pf is the radius calls' (scan_reach); it holds every such row.  The row
+ *     COUNTS iff it is usable, pf is finite (so p' did not overflow), q exists, and in mode 1 q's normal is finite and not (0, 0, 0).
+ *   3 ACCUMULATE.  q and n in float64, d = p' - q per coordinate.  One EQUATION (n): c = p' x n with c0 = fl(p'1 n2) - fl(p'2 n1), c1 =
+ *     fl(p'2 n0) - fl(p'0 n2), c2 = fl(p'0 n1) - fl(p'1 n0); J = (c0, c1, c2, n0, n1, n2); r = (n0 d0 + n1 d1) + n2 d2.  Its 28 PRODUCTS:
+ *     J_i J_j for i <= j (i ascending, j ascending inside i: 21), J_i r (6), r r.  Mode 1: the row's contribution is the products of
+ *     the equation of q's normal.  Mode 0: three equations, n = (1,0,0), (0,1,0), (0,0,1), computed by the same formulas (the
+ *     multiplications by 0 and 1 included); the contribution is (products(e0) + products(e1)) + products(e2) entry by entry.  The
+ *     29th entry is (d0 d0 + d1 d1) + d2 d2, once per row.  A row that does not count contributes +0.0 to every entry.
+ *     The 29 sums over the cloud's SOURCE rows in row order have the FIXED SUM SHAPE of the statistical filter: blocks of 1024 rows
+ *     from the cloud's first row, padded with +0.0, inside a block v[t] += v[t + h] for t < h, h = 512 .. 1, the blocks added left to
+ *     right from +0.0.  count = the counting rows.
+ *   4 SOLVE.  count < min_correspondences: FINISHED with status 2, (R, t) unchanged.  Else A = the symmetric 6 x 6 of the 21 sums, g
+ *     the 6.  Cholesky A = L L^T column by column, j = 0 .. 5: s = A_jj; s = s - L_jk L_jk for k = 0 .. j - 1.  The pivot is ACCEPTED
+ *     iff s is finite and s > A_jj * 2^-30; L_jj = sqrt(s); for i = j + 1 .. 5: t = A_ji; t = t - L_ik L_jk for k = 0 .. j - 1; L_ij =
+ *     t / L_jj.  Forward, i = 0 .. 5: s = -g_i; s = s - L_ik y_k for k = 0 .. i - 1; y_i = s / L_ii.  Back, i = 5 .. 0: s = y_i; s =
+ *     s - L_ki x_k for k = i + 1 .. 5; x_i = s / L_ii.  A refused pivot or an x_k that is not finite: FINISHED with status 3, (R, t)
+ *     unchanged.  (The floor 2^-30 A_jj stands between the rounding noise of s, about 2^-50 A_jj, and a column within 3e-5 rad of
+ *     the span of the earlier ones, which no registration can use: an exactly planar target in mode 1 is refused by rule.)
+ *   5 UPDATE.  x = (w, u), a = w * 0.5, aa = (a0 a0 + a1 a1) + a2 a2, den = 1 + aa, c = 1 - aa.  The Cayley rotation, every entry one
+ *     product, one sum, one division: dR = [ (c + w0 a0) / den, (w0 a1 - w2) / den, (w0 a2 + w1) / den ; (w1 a0 + w2) / den, (c + w1
+ *     a1) / den, (w1 a2 - w0) / den ; (w2 a0 - w1) / den, (w2 a1 + w0) / den, (c + w2 a2) / den ] - a rotation for every a, no sine,
+ *     no cosine.  R_ij <- (dR_i0 R_0j + dR_i1 R_1j) + dR_i2 R_2j; t_i <- ((dR_i0 t0 + dR_i1 t1) + dR_i2 t2) + u_i, both from the old
+ *     R and t.
+ *   6 FINISH.  step = max_k |x_k|; step <= tolerance, tested AFTER the update is applied: FINISHED with status 1.  A pair that ran
+ *     all iterations has status 0.  `iterations` = the number of updates applied (so 0 for a pair that finished with status 2 or 3
+ *     at iteration 0).
+ *   7 EVALUATE.  After the loop, for every pair, steps 1 - 3 once more with the final (R, t): fitness = count / usable source rows (0
+ *     for none), inlier_rmse = sqrt(SUM((d0 d0 + d1 d1) + d2 d2) / count) (0 for count 0).
+ *   out_transform float64 [batch, 16]: row-major 4 x 4, rows (R_k0, R_k1, R_k2, t_k), the last 0 0 0 1.  out_stats float64 [batch, 4] =
+ *   fitness, inlier_rmse, the last step (0 if no update was applied), the evaluation's sum of r r.  out_info int32 [batch, 3] = status,
+ *   iterations, the evaluation's count.  out_corr (nullable) int64 [n_src_total] per source row: q's index from the cloud's first
+ *   target row in the evaluation, -1 for none (q's normal does not show here).  out_moved (nullable) fp32 [n_src_total, 3]: pf of the final transform.  Rows outside every span are
+ *   not written.  An empty source or target: the initial transform, status 2, iterations 0, zeros.
+ *   Where this differs from Open3D registration_icp (stated from its documentation, UNCHECKED; it is not available to check against):
+ *   its point-to-point step is the closed-form SVD fit, this one is a Gauss-Newton step of the same objective, so the fixed points
+ *   agree and the paths do not; it stops on relative changes of fitness and RMSE, this one on the size of the update; its
+ *   correspondence has no tie rule.  Rigid motion only: no scale, no robust kernel, no multi-scale schedule, no global initialisation.
+ * Launches (cloud_icp.hip): the target's index once, and the same index build over the source under the initial transform, which only
+ * orders the lanes of the search (rows of one cell share a wave; no result depends on it); per iteration one lane per source row (the
+ * move and the radius walk over the target's index), one workgroup per 1024 source rows (the 29 block sums) and one wave per pair (a
+ * lane per sum for the blocks, then the solve, the update, the status); the same three once more for the evaluation.  The iterations are a host loop with no host read; a finished pair's later kernels
+ * return at once.  One stream, no kernel waits on another workgroup, no atomics; every loop is bounded by a cloud's length, the scan
+ * range or a constant; every index read from the scratch is clamped before it addresses anything.
+ * scratch: rald_post_icp_scratch_bytes of the same sizes, 16-byte aligned, never NULL; -1 (and rald_last_error) for sizes the calls
+ * refuse.  Every invalid argument is refused with a status before any GPU work.  rald_op_*: test-facing, with the chunk length of the
+ * target's split sort as in the radius calls.
+ * Rigid transform of a ragged batch: transforms DEVICE float64 [batch, transform_stride], transform_stride 12 (R row-major, then t) or
+ * 16 (row-major 4 x 4, the last row ignored).  out_points fp32 [n_total, 3] = step 1's pf of every row of a span (non-finite rows
+ * included: they come out as the arithmetic gives them); with normals fp32 [n_total, 3] (nullable, with out_normals) out_normals =
+ * step 1's pf of the normal with t = +0.0: the rotation alone.  In place (out_points == points) is allowed. */
+int64_t rald_post_icp_scratch_bytes(int32_t batch, int64_t n_src_total, int64_t max_src, int64_t n_tgt_total, int64_t max_tgt);
+int rald_post_icp_ragged(const float* source, const int64_t* src_offsets, const int32_t* src_counts, int64_t src_n_dense, int64_t n_src_total,
+                         int64_t max_src, const float* target, const int64_t* tgt_offsets, const int32_t* tgt_counts, int64_t tgt_n_dense,
+                         int64_t n_tgt_total, int64_t max_tgt, const float* target_normals, int32_t batch, const float* lo3_host,
+                         const float* v3_host, const int32_t* dims3_host, int32_t mode, float max_distance, int32_t max_iterations,
+                         double tolerance, int32_t min_correspondences, const double* init, double* out_transform, double* out_stats,
+                         int32_t* out_info, int64_t* out_corr, float* out_moved, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t rald_op_icp_scratch_bytes(int32_t batch, int64_t n_src_total, int64_t max_src, int64_t n_tgt_total, int64_t max_tgt, int64_t chunk);
+int rald_op_icp_ragged(const float* source, const int64_t* src_offsets, const int32_t* src_counts, int64_t src_n_dense, int64_t n_src_total,
+                       int64_t max_src, const float* target, const int64_t* tgt_offsets, const int32_t* tgt_counts, int64_t tgt_n_dense,
+                       int64_t n_tgt_total, int64_t max_tgt, const float* target_normals, int32_t batch, const float* lo3_host,
+                       const float* v3_host, const int32_t* dims3_host, int32_t mode, float max_distance, int32_t max_iterations,
+                       double tolerance, int32_t min_correspondences, const double* init, double* out_transform, double* out_stats,
+                       int32_t* out_info, int64_t* out_corr, float* out_moved, void* scratch, int64_t scratch_bytes, int64_t chunk,
+                       void* stream);
+int rald_post_rigid_transform_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                     int64_t n_total, int64_t max_per_sample, const double* transforms, int32_t transform_stride,
+                                     const float* normals, float* out_points, float* out_normals, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 

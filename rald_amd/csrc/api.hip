@@ -658,6 +658,47 @@ int rald_post_plane_filter_ragged(const float* points, const int64_t* offsets, c
                                out_planes, out_num_planes, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// ---- ICP registration and rigid transforms -------------------------------------------------
+int64_t rald_op_icp_scratch_bytes(int32_t batch, int64_t n_src_total, int64_t max_src, int64_t n_tgt_total, int64_t max_tgt, int64_t chunk) {
+    const int64_t n = icp_scratch_bytes(batch, n_src_total, max_src, n_tgt_total, max_tgt, chunk);
+    if (n < 0)
+        set_error("rald_post_icp_scratch_bytes: batch 1 .. 65535, n_src_total and n_tgt_total 0 .. 2^31 - 1, max_src and max_tgt 1 .. 2^24, "
+                  "chunk 0 or a multiple of 1024");
+    return n;
+}
+int64_t rald_post_icp_scratch_bytes(int32_t batch, int64_t n_src_total, int64_t max_src, int64_t n_tgt_total, int64_t max_tgt) {
+    return rald_op_icp_scratch_bytes(batch, n_src_total, max_src, n_tgt_total, max_tgt, 0);
+}
+int rald_op_icp_ragged(const float* source, const int64_t* src_offsets, const int32_t* src_counts, int64_t src_n_dense, int64_t n_src_total,
+                       int64_t max_src, const float* target, const int64_t* tgt_offsets, const int32_t* tgt_counts, int64_t tgt_n_dense,
+                       int64_t n_tgt_total, int64_t max_tgt, const float* target_normals, int32_t batch, const float* lo3_host,
+                       const float* v3_host, const int32_t* dims3_host, int32_t mode, float max_distance, int32_t max_iterations,
+                       double tolerance, int32_t min_correspondences, const double* init, double* out_transform, double* out_stats,
+                       int32_t* out_info, int64_t* out_corr, float* out_moved, void* scratch, int64_t scratch_bytes, int64_t chunk,
+                       void* stream) {
+    return icp_ragged(ragged_cloud(source, src_offsets, src_counts, batch, src_n_dense, n_src_total, max_src),
+                      ragged_cloud(target, tgt_offsets, tgt_counts, batch, tgt_n_dense, n_tgt_total, max_tgt), target_normals,
+                      {lo3_host, v3_host, dims3_host}, mode, max_distance, max_iterations, tolerance, min_correspondences, init, out_transform,
+                      out_stats, out_info, out_corr, out_moved, scratch, scratch_bytes, chunk, (hipStream_t)stream);
+}
+int rald_post_icp_ragged(const float* source, const int64_t* src_offsets, const int32_t* src_counts, int64_t src_n_dense, int64_t n_src_total,
+                         int64_t max_src, const float* target, const int64_t* tgt_offsets, const int32_t* tgt_counts, int64_t tgt_n_dense,
+                         int64_t n_tgt_total, int64_t max_tgt, const float* target_normals, int32_t batch, const float* lo3_host,
+                         const float* v3_host, const int32_t* dims3_host, int32_t mode, float max_distance, int32_t max_iterations,
+                         double tolerance, int32_t min_correspondences, const double* init, double* out_transform, double* out_stats,
+                         int32_t* out_info, int64_t* out_corr, float* out_moved, void* scratch, int64_t scratch_bytes, void* stream) {
+    return rald_op_icp_ragged(source, src_offsets, src_counts, src_n_dense, n_src_total, max_src, target, tgt_offsets, tgt_counts, tgt_n_dense,
+                              n_tgt_total, max_tgt, target_normals, batch, lo3_host, v3_host, dims3_host, mode, max_distance, max_iterations,
+                              tolerance, min_correspondences, init, out_transform, out_stats, out_info, out_corr, out_moved, scratch,
+                              scratch_bytes, 0, stream);
+}
+int rald_post_rigid_transform_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
+                                     int64_t n_total, int64_t max_per_sample, const double* transforms, int32_t transform_stride,
+                                     const float* normals, float* out_points, float* out_normals, void* stream) {
+    return rigid_transform_ragged(ragged_cloud(points, offsets, counts, batch, n_dense, n_total, max_per_sample), transforms, transform_stride,
+                                  normals, out_points, out_normals, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {

@@ -408,6 +408,16 @@ int plane_filter_ragged(const RaggedCloud& c, float threshold, int num_hypothese
                         const float* view3_host, int keep_planes, float* out_points, int64_t* out_offsets, int64_t* out_index,
                         int32_t* out_labels, double* out_planes, int32_t* out_num_planes, void* scratch, int64_t scratch_bytes, hipStream_t st);
 
+// ---------------------------------------------------------------- cloud_icp.hip
+// ICP registration of every source cloud onto the target cloud of the same batch position, point-to-point (mode 0) or point-to-plane
+// (mode 1), iterated on the device, and the rigid transform of a ragged batch by per-cloud float64 transforms
+int64_t icp_scratch_bytes(int B, int64_t n_src_total, int64_t max_src, int64_t n_tgt_total, int64_t max_tgt, int64_t chunk);
+int icp_ragged(const RaggedCloud& src, const RaggedCloud& tgt, const float* target_normals, const GridSpec& grid, int mode, float max_dist,
+               int max_iterations, double tolerance, int min_correspondences, const double* init, double* out_transform, double* out_stats,
+               int32_t* out_info, int64_t* out_corr, float* out_moved, void* scratch, int64_t scratch_bytes, int64_t chunk, hipStream_t st);
+int rigid_transform_ragged(const RaggedCloud& c, const double* transforms, int stride, const float* normals, float* out_points,
+                           float* out_normals, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,

@@ -199,6 +199,20 @@ class _Tail:
     consistency float64 [B,3], the surfaces' estimated normals); None for what was not asked for or not computed."""
     points: torch.Tensor; offsets: torch.Tensor; cd: Optional[torch.Tensor]; n_queries: torch.Tensor
     metrics: Optional[dict]; normals: Optional[torch.Tensor]; longest: int; denoised: Optional[_Denoised]; ncons: Optional[tuple]
+    aligned: Optional["_Aligned"] = None
+
+
+@dataclass
+class _Aligned:
+    """The final clouds registered onto their surfaces, on the device: register_icp_ragged's transform float64 [B,4,4], fitness and
+    inlier_rmse float64 [B], status int32 [B], the final clouds under the transform (laid out like the tail's points), and cd / metrics
+    of those against the same surfaces."""
+    transform: torch.Tensor; fitness: torch.Tensor; rmse: torch.Tensor; status: torch.Tensor; points: torch.Tensor
+    cd: Optional[torch.Tensor] = None; metrics: Optional[dict] = None
+
+
+class _Align(NamedTuple):
+    mode: int; max_distance: float; max_iterations: int; grid: tuple; normals_of: Optional[tuple]
 
 
 # the four filters as _check_denoise, _check_denoise_statistical, _check_denoise_cluster and _check_remove_planes return them, plain
@@ -368,6 +382,39 @@ def _check_normal_consistency(nc, args, surfaces, normals, surface_steps):
     return k, _thin_grid(float(cell), args)
 
 
+def _check_align(align, args, surfaces, normal_consistency):
+    """`align` (None, or (mode, max_distance), (mode, max_distance, max_iterations) or, for plane mode without `normal_consistency`,
+    (mode, max_distance, max_iterations, k, cell)) -> None or (mode 0 / 1, max_distance, max_iterations, grid, (k, normals grid) or
+    None): the search grid is _thin_grid's box with the cell edge max_distance; plane mode estimates the surfaces' normals from (k,
+    cell), its own or `normal_consistency`'s.  ValueError for anything else, for too many cells, and without `surfaces`, on the host."""
+    if align is None:
+        return None
+    message = "align must be None, (mode, max_distance), (mode, max_distance, max_iterations) or (mode, max_distance, max_iterations, k, cell)"
+    try:
+        align = tuple(align)
+    except TypeError:
+        raise ValueError(message) from None
+    if len(align) not in (2, 3, 5):
+        raise ValueError(message)
+    mode = PP._icp_mode(align[0])
+    max_distance = _positive(align[1], "align: max_distance must be a finite number > 0")
+    iterations = _whole(align[2] if len(align) >= 3 else 30, 1, PP.ICP_MAX_ITERATIONS,
+                        f"align: max_iterations must be an integer in 1 .. {PP.ICP_MAX_ITERATIONS}")
+    if surfaces is None:
+        raise ValueError("align needs surfaces")
+    normals_of = None
+    if mode == 1:
+        knn = align[3:] if len(align) == 5 else normal_consistency
+        if knn is None:
+            raise ValueError("align: plane mode needs (k, cell) for the surfaces' normals, as its fourth and fifth entry or from normal_consistency")
+        try:
+            k, cell = knn
+        except (TypeError, ValueError):
+            raise ValueError(message) from None
+        normals_of = (PP._knn_k(k), _thin_grid(_positive(cell, "align: cell must be a finite number > 0"), args))
+    return _Align(mode, max_distance, iterations, _thin_grid(max_distance, args), normals_of)
+
+
 def _thin(pts: torch.Tensor, off: torch.Tensor, grid, longest: int):
     """The final clouds, one centroid per occupied cell -> (thinned [T,3], thin_offsets [B+1], thin_count [T], thin_first [T]); after
     the metric, which keeps the full cloud."""
@@ -413,7 +460,7 @@ class _HostPack:
 
 
 def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals, surface_steps, surface_max_step,
-                    resample, thin, denoise, denoise_statistical, normal_consistency, denoise_cluster, remove_planes=None):
+                    resample, thin, denoise, denoise_statistical, normal_consistency, denoise_cluster, remove_planes=None, align=None):
     """What both batched entry points do, with their arguments -> (_Tail, _thin's four or None, _resample's pair or None): every option
     checked on the host, the batched tail on the device, the filter chosen behind the metric of the full cloud with a metric of its own,
     then the finishing chain on the denoised clouds if there are any, else on the full ones: thin, then resample."""
@@ -423,6 +470,7 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
                or _check_denoise_cluster(denoise_cluster, denoise, denoise_statistical, args)
                or _check_denoise_statistical(denoise_statistical, denoise, args) or _check_denoise(denoise, args))
     ncons = _check_normal_consistency(normal_consistency, args, surfaces, normals, surface_steps)
+    al = _check_align(align, args, surfaces, normal_consistency)
     oriented = bool(normals) or int(surface_steps) > 0
     if metric_thresholds is not None:
         metric_thresholds = PP._thresholds(metric_thresholds)
@@ -476,9 +524,9 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         pts, nrm = PP.oriented_points_ragged(kept, grad, p_off, lidar.pc_range, aniso, iso, view_cone_mode=view_cone)
     elif view_cone:
         pts = PP.polar2cartesian(pts)                                                              # :313-315 (rows past the last frame: unspecified)
-    cd = metrics = den = ncd = thinned = resampled = None
+    cd = metrics = den = ncd = thinned = resampled = aligned = None
     with_metric = surfaces is not None and not _get(args.eval, "skip_eval_metric", False)
-    if with_metric or ncons is not None:
+    if with_metric or ncons is not None or al is not None:
         P = surfaces.shape[1]
         gt = PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso)   # :290
         if view_cone:
@@ -493,7 +541,17 @@ def _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, dra
         den = denoise.run(pts, p_off, max(1, int(longest)))
         if with_metric:
             den.cd, den.metrics = _metric(den.points, den.offsets, gt, gt_off, longest, P, metric_thresholds)
-    tail = _Tail(pts, p_off, cd, n_queries, metrics, nrm, longest, den, ncd)
+    if al is not None:                                                                             # the full cloud onto its surfaces
+        gt_nrm = None
+        if al.mode == 1:
+            gt_nrm = ncd[1] if ncd is not None and al.normals_of == ncons else \
+                PP.estimate_normals_ragged(gt, gt_off, al.normals_of[0], al.normals_of[1], max(1, int(P)), view=(0.0, 0.0, 0.0))
+        reg = PP.register_icp_ragged(pts, p_off, gt, gt_off, al.max_distance, al.grid, max(1, int(longest)), max(1, int(P)),
+                                     target_normals=gt_nrm, max_iterations=al.max_iterations, mode=al.mode, return_moved=True)
+        aligned = _Aligned(reg["transform"], reg["fitness"], reg["inlier_rmse"], reg["status"], reg["moved"])
+        if with_metric:
+            aligned.cd, aligned.metrics = _metric(aligned.points, p_off, gt, gt_off, longest, P, metric_thresholds)
+    tail = _Tail(pts, p_off, cd, n_queries, metrics, nrm, longest, den, ncd, aligned)
     if den is not None:
         pts, p_off = den.points, den.offsets
     if thin_grid is not None:
@@ -526,7 +584,7 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
                        rng: Optional[torch.Generator] = None, draws: Optional[dict] = None, metric_thresholds=None, normals: bool = False,
                        surface_steps: int = 0, surface_max_step: float = 0.05, resample: Optional[int] = None,
                        thin=None, denoise=None, denoise_statistical=None, normal_consistency=None, denoise_cluster=None,
-                       remove_planes=None) -> Dict[str, object]:
+                       remove_planes=None, align=None) -> Dict[str, object]:
     """engine_generation.py:250-322 for a whole batch of frames, on the device from the sampler's latents to the metric:
     one query grid for the batch (the reference repeats its grid over the batch) [+ each frame's helper points] -> ragged decode ->
     positives per frame -> un-normalised polar points -> [refine: jittered copies per frame -> normalise -> ragged decode ->
@@ -611,17 +669,30 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
     postprocess.normal_consistency_ragged: |n . n'| with the nearest row of the other cloud, averaged per direction.  Computed on the
     full cloud, skip_eval_metric or not.  Added: 'normal_consistency', B triples (pred -> gt, gt -> pred, their mean; NaN where no row
     has two usable normals) carried in the one host read, and 'surface_normals', a list of B tensors [P,3] on the device.
+    `align` (None, or (mode, max_distance), (mode, max_distance, max_iterations) or (mode, max_distance, max_iterations, k, cell); mode
+    'point' or 'plane'): every final cloud is additionally registered onto its frame's `surfaces` cloud by ICP - a small extrinsic or
+    timing error between the sensors shows up in 'cd' as shape error; the metric after a rigid alignment tells the two apart - from
+    postprocess.register_icp_ragged over the box `thin` uses with the cell edge max_distance, at most
+    max_iterations (default 30) iterations, all on the device.  It needs `surfaces`, else ValueError before any GPU work.  Plane mode
+    estimates the surfaces' normals as `normal_consistency` does, from its own (k, cell) or, without them, from `normal_consistency`'s.
+    'pred', 'cd', 'metrics' and every other key stay untouched.  Added: 'align_transform' (B 4 x 4 nested lists of floats: surfaces ~ R
+    pred + t), 'align_fitness', 'align_rmse' (B floats), 'align_status' (B ints: postprocess.ICP_STATUS), 'aligned' (a list of B tensors
+    [n_b,3], 'pred' under the transform), 'cd_aligned' (B floats, None where no metric is computed) and with metric_thresholds
+    'metrics_aligned' (as 'metrics'), all host values carried in the one host read.
     Returns {'pred': list of B tensors [n_b,3] (metric coordinates, on the device), 'cd': list of B floats or None,
     'n_queries': list of B ints} and the keys that the options above add."""
     t, thinned, resampled = _tail_on_device(vae, sampled_tokens, args, helper_points, surfaces, rng, draws, metric_thresholds, normals,
                                             surface_steps, surface_max_step, resample, thin, denoise, denoise_statistical, normal_consistency,
-                                            denoise_cluster, remove_planes)
-    B, den, nrm = sampled_tokens.shape[0], t.denoised, t.normals
+                                            denoise_cluster, remove_planes, align)
+    B, den, nrm, al = sampled_tokens.shape[0], t.denoised, t.normals, t.aligned
     groups = {"offsets": t.offsets, "n_queries": t.n_queries, "cd": t.cd, "metrics": t.metrics,
               "normal_consistency": t.ncons and t.ncons[0], "thin_offsets": thinned and thinned[1]}
     if den is not None:
         groups.update(denoise_offsets=den.offsets, cd_denoised=den.cd, metrics_denoised=den.metrics, denoise_stats=den.stats, n_clusters=den.n_clusters,
                       planes=den.planes, num_planes=den.n_planes)
+    if al is not None:
+        groups.update(align_transform=al.transform, align_fitness=al.fitness, align_rmse=al.rmse, align_status=al.status, cd_aligned=al.cd,
+                      metrics_aligned=al.metrics)
     host = _HostPack(**groups).read()
     ints = lambda name: [int(v) for v in host[name]]
     frames = lambda rows, name: [rows[lo:hi] for lo, hi in zip(ints(name), ints(name)[1:])]         # a ragged tensor by its offsets' host copy
@@ -653,6 +724,13 @@ def infer_point_clouds(vae, sampled_tokens: torch.Tensor, args, helper_points=No
             out["planes"] = [[tuple(flat[(b * K + k) * 4:(b * K + k) * 4 + 4]) for k in range(out["num_planes"][b])] for b in range(B)]
     if t.ncons is not None:
         out["normal_consistency"], out["surface_normals"] = triples("normal_consistency"), list(t.ncons[1].split(surfaces.shape[1]))
+    if al is not None:
+        flat = host["align_transform"]
+        out["align_transform"] = [[flat[b * 16 + 4 * r:b * 16 + 4 * r + 4] for r in range(4)] for b in range(B)]
+        out["align_fitness"], out["align_rmse"], out["align_status"] = host["align_fitness"], host["align_rmse"], ints("align_status")
+        out["aligned"], out["cd_aligned"] = frames(al.points, "offsets"), host.get("cd_aligned")
+        if metric_thresholds is not None:
+            out["metrics_aligned"] = frame_metrics("metrics_aligned")
     if thinned is not None:
         for key, rows in zip(("thinned", "thin_count", "thin_first"), (thinned[0], thinned[2], thinned[3])):
             out[key] = frames(rows, "thin_offsets")

@@ -16,7 +16,9 @@ inside a cloud and the outlier filter on their mean distance; DESIGN.md section 
 ``normal_consistency*`` (PCA normals, surface variation and eigenvalues from those neighbours, and the normal-consistency metric of two
 clouds with normals), ``cluster_dbscan*`` / ``remove_small_clusters*`` (density clustering; DESIGN.md section
 25), and ``segment_plane*`` / ``remove_planes*`` (RANSAC plane segmentation with a fixed number of counter-based hypotheses, the device
-counterpart of Open3D's ``segment_plane``, and plane removal).
+counterpart of Open3D's ``segment_plane``, and plane removal), and ``register_icp*`` / ``transform_points*``
+(ICP registration of one ragged batch onto another, point-to-point and point-to-plane, iterated on the device, the device counterpart
+of Open3D's ``registration_icp``, and the rigid transform that applies its result).
 """
 from __future__ import annotations
 
@@ -1171,3 +1173,203 @@ def _radius_grid(lo, hi, radius):
                 raise
         edge *= 2.0
     raise ValueError("no grid of at most 2^31 - 1 cells covers lo .. hi")
+
+
+ICP_MAX_ITERATIONS = 64                                  # the largest max_iterations of rald_post_icp_ragged
+ICP_MODES = {"point": 0, "plane": 1, "point_to_point": 0, "point_to_plane": 1, 0: 0, 1: 1}
+ICP_STATUS = ("max_iterations", "converged", "too_few_correspondences", "degenerate")
+
+
+def _icp_mode(mode) -> int:
+    if isinstance(mode, bool) or not isinstance(mode, (str, int)) or mode not in ICP_MODES:
+        raise ValueError("mode must be 'point' (0) or 'plane' (1)")
+    return ICP_MODES[mode]
+
+
+def _icp_args(source, target, max_distance, grid, max_source, max_target, target_normals, init, mode, max_iterations, tolerance,
+              min_correspondences, source_counts, target_counts, B: Optional[int], chunk):
+    """The rules of the ICP calls (ValueError, before anything asks where a tensor lives) -> (max_distance as the float32 the kernels
+    use, max_source, max_target, mode, max_iterations, tolerance, min_correspondences, chunk, the grid's three ctypes arrays)."""
+    for t, what in ((source, "source"), (target, "target")):
+        if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[-1] == 3 and t.is_floating_point()):
+            raise ValueError(f"{what} must be a floating-point tensor [T, 3]")
+    max_source, chunk = _voxel_args(source, max_source, source_counts, B, chunk)
+    max_target, _ = _voxel_args(target, max_target, target_counts, B, 0)
+    max_distance = _f32(_positive(max_distance, "max_distance must be a finite number > 0"))
+    if not max_distance > 0 or not math.isfinite(max_distance):
+        raise ValueError("max_distance must fit float32")
+    grid3 = _voxel_grid_arg(grid)
+    if any(float(v) < max_distance for v in grid[1]):
+        raise ValueError("every cell edge of the grid must be >= max_distance (build it with voxel_grid(lo, hi, max_distance))")
+    mode = _icp_mode(mode)
+    if mode == 1:
+        if target_normals is None:
+            raise ValueError("plane mode needs target_normals")
+        _normals_of(target_normals, target, "target_normals")
+    if init is not None and not (isinstance(init, torch.Tensor) and init.dtype == torch.float64
+                                 and (B is None or tuple(init.shape) in ((B, 12), (B, 4, 4), (B, 16)))):
+        raise ValueError("init must be a float64 tensor [B, 12] (R row-major, then t), [B, 16] or [B, 4, 4]")
+    max_iterations = _whole(max_iterations, 1, ICP_MAX_ITERATIONS, f"max_iterations must be an integer in 1 .. {ICP_MAX_ITERATIONS}")
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not tolerance >= 0:
+        raise ValueError("tolerance must be a number >= 0")
+    min_correspondences = _whole(min_correspondences, 1, 2 ** 31 - 1, "min_correspondences must be an integer >= 1")
+    return max_distance, max_source, max_target, mode, max_iterations, float(tolerance), min_correspondences, chunk, grid3
+
+
+def _init12(init: torch.Tensor, B: int, dev) -> torch.Tensor:
+    """[B,12], [B,16] or [B,4,4] float64 -> contiguous [B,12] on the device (R row-major, then t)."""
+    init = init.detach().to(dev)
+    if init.dim() == 2 and init.shape[1] == 12:
+        return init.contiguous()
+    M = init.reshape(B, 4, 4)
+    return torch.cat([M[:, :3, :3].reshape(B, 9), M[:, :3, 3]], dim=1).contiguous()
+
+
+def register_icp_ragged(source: torch.Tensor, source_offsets: torch.Tensor, target: torch.Tensor, target_offsets: torch.Tensor,
+                        max_distance: float, grid, max_source: int, max_target: int, target_normals: Optional[torch.Tensor] = None,
+                        init: Optional[torch.Tensor] = None, max_iterations: int = 30, tolerance: float = 1e-6,
+                        min_correspondences: int = 6, mode=None, source_counts: Optional[torch.Tensor] = None,
+                        target_counts: Optional[torch.Tensor] = None, return_correspondences: bool = False, return_moved: bool = False,
+                        chunk: int = 0) -> Dict[str, torch.Tensor]:
+    """ICP registration of every source cloud onto the target cloud of the same batch position (rald_post_icp_ragged, DESIGN.md
+    section 27), the device counterpart of Open3D's registration_icp: source [Ts,3] / target [Tt,3] with int64 offsets [B+1] on the
+    device, grid = voxel_grid(lo, hi, max_distance) over the box of the TARGET (target rows outside it are nobody's match; the grid
+    does not show otherwise), max_source / max_target the host bounds of the longest cloud.  mode 'point' or 'plane' (default: plane
+    iff target_normals [Tt,3] are given).  Each iteration moves the source by the current transform (float64), takes for every row its
+    nearest target row within max_distance (float32 distances, the lowest row on equal ones), sums the normal equations of the
+    linearised objective in float64 in a fixed shape, solves them by Cholesky and applies the step as an exact rational rotation; it
+    stops when every component of the step is <= tolerance, when fewer than min_correspondences rows have a match, or when the
+    equations are degenerate (an exactly planar target in plane mode).  init: float64 [B,12] (R row-major then t), [B,16] or
+    [B,4,4] on the device.  -> dict of device tensors: 'transform' float64 [B,4,4] (target ~ R source + t), 'fitness' float64 [B]
+    (matched / usable source rows under the final transform), 'inlier_rmse' float64 [B], 'step' float64 [B] (the last step's
+    largest component), 'residual' float64 [B] (the final sum of squared residuals), 'status' int32 [B] (0 ran all iterations, 1
+    converged, 2 too few correspondences, 3 degenerate: ICP_STATUS), 'iterations' int32 [B] (updates applied), 'count' int32 [B];
+    with return_correspondences 'correspondences' int64 [Ts] (the target row from the cloud's first target row, -1 for none), with
+    return_moved 'moved' float32 [Ts,3] (the source under the final transform).  Rows past the offsets or behind counts / the bounds
+    are unspecified.  Defined to the bit: the same in every call, batch, chunk and grid.  All iterations run on the device: no host
+    read, no synchronisation; runs on the current stream."""
+    B = _offsets_shape(source_offsets, "source_offsets")
+    if _offsets_shape(target_offsets, "target_offsets") != B:
+        raise ValueError("source_offsets and target_offsets must describe the same batch")
+    if mode is None:
+        mode = "plane" if target_normals is not None else "point"
+    max_distance, max_source, max_target, mode, max_iterations, tolerance, min_correspondences, chunk, grid3 = _icp_args(
+        source, target, max_distance, grid, max_source, max_target, target_normals, init, mode, max_iterations, tolerance, min_correspondences,
+        source_counts, target_counts, B, chunk)
+    source, source_counts, _, Ts, dev = _cloud_batch(source, source_offsets, source_counts)
+    target, target_counts, _, Tt, _ = _cloud_batch(target, target_offsets, target_counts)
+    normals = _f32c(target_normals).to(dev) if mode == 1 else None
+    init = _init12(init, B, dev) if init is not None else None
+    transform = torch.empty(B, 4, 4, device=dev, dtype=torch.float64)
+    stats = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    info = torch.empty(B, 3, device=dev, dtype=torch.int32)
+    corr = torch.empty(Ts, device=dev, dtype=torch.int64) if return_correspondences else None
+    moved = torch.empty(Ts, 3, device=dev, dtype=torch.float32) if return_moved else None
+    L = lib()
+    pre, tail = ("rald_op_", (chunk,)) if chunk else ("rald_post_", ())
+    nbytes = _nbytes(getattr(L, pre + "icp_scratch_bytes")(B, Ts, max_source, Tt, max_target, *tail))
+    scratch = _scratch(nbytes, dev)
+    pad = torch.zeros(4, device=dev, dtype=torch.float32)                            # no rows: an empty tensor has no address to pass
+    check(getattr(L, pre + "icp_ragged")((source if Ts else pad).data_ptr(), source_offsets.data_ptr(), _opt(source_counts), 0, Ts, max_source,
+                                         (target if Tt else pad).data_ptr(), target_offsets.data_ptr(), _opt(target_counts), 0, Tt, max_target,
+                                         (normals if Tt else pad).data_ptr() if mode == 1 else None, B, *grid3, mode, max_distance,
+                                         max_iterations, tolerance, min_correspondences, _opt(init), transform.data_ptr(), stats.data_ptr(),
+                                         info.data_ptr(), _opt(corr) if Ts else None, _opt(moved) if Ts else None, scratch.data_ptr(), nbytes,
+                                         *tail, _stream()))
+    out = {"transform": transform, "fitness": stats[:, 0], "inlier_rmse": stats[:, 1], "step": stats[:, 2], "residual": stats[:, 3],
+           "status": info[:, 0], "iterations": info[:, 1], "count": info[:, 2]}
+    if return_correspondences:
+        out["correspondences"] = corr
+    if return_moved:
+        out["moved"] = moved
+    return out
+
+
+def register_icp(source: torch.Tensor, target: torch.Tensor, max_distance: float, target_normals: Optional[torch.Tensor] = None,
+                 init: Optional[torch.Tensor] = None, max_iterations: int = 30, tolerance: float = 1e-6, min_correspondences: int = 6,
+                 mode=None, lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None, return_correspondences: bool = False,
+                 return_moved: bool = False) -> Dict[str, torch.Tensor]:
+    """One pair: source [n,3] onto target [m,3] -> register_icp_ragged's dict without the batch dimension ('transform' float64 [4,4],
+    scalars as 0-d device tensors), the device counterpart of Open3D's registration_icp(source, target, max_distance, init).  init:
+    float64 [4,4] or [12].  lo / hi: the box of the target's search grid; without them the target's own minimum and maximum - that
+    costs one host read of six numbers (and the target must be finite).  Where the box would need more than 2^31 - 1 cells of edge
+    max_distance the cells are made larger; the result does not depend on that.  An empty source or target gives init, status 2."""
+    _one_cloud_check(target, lo, hi)
+    if mode is None:
+        mode = "plane" if target_normals is not None else "point"
+    if init is not None:
+        if not (isinstance(init, torch.Tensor) and init.dtype == torch.float64 and tuple(init.shape) in ((4, 4), (12,), (16,))):
+            raise ValueError("init must be a float64 tensor [4, 4] or [12]")
+        init = init.reshape(1, -1)
+    _icp_one_check(source, target, max_distance, target_normals, init, mode, max_iterations, tolerance, min_correspondences)
+    dev = source.device
+    n = source.shape[0]
+    one = _one_cloud(target, lo, hi, lambda l, h, rows: _radius_grid(l, h, max_distance))
+    if one is None:                                                                  # no target row: nothing to index
+        _need_cuda(source, "source")
+        grid, m = _radius_grid((0, 0, 0), (0, 0, 0), max_distance), 0
+        target = torch.zeros(0, 3, device=dev, dtype=torch.float32)
+    else:
+        target, _, grid, m = one
+    _need_cuda(source, "source")
+    off = torch.tensor([[0, n], [0, m]], dtype=torch.int64, device=dev)
+    out = register_icp_ragged(source, off[0], target, off[1], max_distance, grid, max(n, 1), max(m, 1), target_normals, init, max_iterations,
+                              tolerance, min_correspondences, mode, return_correspondences=return_correspondences, return_moved=return_moved)
+    return {k: (v[0] if k not in ("correspondences", "moved") else v) for k, v in out.items()}
+
+
+def _icp_one_check(source, target, max_distance, target_normals, init, mode, max_iterations, tolerance, min_correspondences) -> None:
+    """register_icp's ValueErrors: the ragged call's rules on a grid that every max_distance passes."""
+    edge = min(_positive(max_distance, "max_distance must be a finite number > 0") * 2.0, 1e30)
+    _icp_args(source, target, max_distance, ((0.0, 0.0, 0.0), (edge,) * 3, (1, 1, 1)), 1, 1, target_normals, init, mode, max_iterations,
+              tolerance, min_correspondences, None, None, 1, 0)
+    if source.shape[0] > VOXEL_MAX_POINTS or target.shape[0] > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points a cloud")
+
+
+def _transform_args(points, transforms, normals, max_per_sample, counts, B: Optional[int]) -> int:
+    """The rules of the rigid-transform calls (ValueError) -> max_per_sample."""
+    max_per_sample, _ = _voxel_args(points, max_per_sample, counts, B, 0)
+    if not (isinstance(transforms, torch.Tensor) and transforms.dtype == torch.float64
+            and (B is None or tuple(transforms.shape) in ((B, 12), (B, 16), (B, 4, 4)))):
+        raise ValueError("transforms must be a float64 tensor [B, 4, 4], [B, 16] or [B, 12] (R row-major, then t)")
+    if normals is not None:
+        _normals_of(normals, points, "normals")
+    return max_per_sample
+
+
+def transform_points_ragged(points: torch.Tensor, offsets: torch.Tensor, transforms: torch.Tensor, max_per_sample: int,
+                            normals: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None):
+    """The rigid transform of every cloud of a ragged batch by its own float64 transform (rald_post_rigid_transform_ragged, DESIGN.md
+    section 27): points [T,3], offsets int64 [B+1] and transforms float64 [B,4,4] / [B,16] / [B,12] on the device (register_icp_ragged's
+    'transform') -> points float32 [T,3]: R p + t in float64 in the order register_icp_ragged moves its source, rounded to float32
+    once, so the result is its 'moved'.  With normals [T,3] -> (points, normals): the normals rotated by R alone.  Rows past
+    offsets[B] or behind counts / the bound are unspecified.  No host read, no synchronisation; runs on the current stream."""
+    B = _offsets_shape(offsets, "offsets")
+    max_per_sample = _transform_args(points, transforms, normals, max_per_sample, counts, B)
+    points, counts, B, T, dev = _cloud_batch(points, offsets, counts)
+    transforms = transforms.detach().to(dev).reshape(B, -1).contiguous()
+    out = torch.empty(T, 3, device=dev, dtype=torch.float32)
+    out_normals = torch.empty(T, 3, device=dev, dtype=torch.float32) if normals is not None else None
+    if T:                                                                            # no rows: an empty tensor has no address to pass
+        nrm = _f32c(normals).to(dev) if normals is not None else None
+        check(lib().rald_post_rigid_transform_ragged(points.data_ptr(), offsets.data_ptr(), _opt(counts), B, 0, T, max_per_sample,
+                                                     transforms.data_ptr(), transforms.shape[1], _opt(nrm), out.data_ptr(), _opt(out_normals),
+                                                     _stream()))
+    return out if normals is None else (out, out_normals)
+
+
+def transform_points(points: torch.Tensor, transform: torch.Tensor, normals: Optional[torch.Tensor] = None):
+    """One cloud [N,3] and one float64 transform [4,4] (or [12]: R row-major, then t) on the device -> transform_points_ragged's
+    result for it."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[-1] == 3 and points.is_floating_point()):
+        raise ValueError("points must be a floating-point tensor [N, 3]")
+    if not (isinstance(transform, torch.Tensor) and transform.dtype == torch.float64 and tuple(transform.shape) in ((4, 4), (16,), (12,))):
+        raise ValueError("transform must be a float64 tensor [4, 4] or [12]")
+    N = points.shape[0]
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"at most {VOXEL_MAX_POINTS} points")
+    _transform_args(points, transform.reshape(1, -1), normals, 1, None, 1)
+    _need_cuda(points, "points")
+    off = torch.tensor([0, N], dtype=torch.int64, device=points.device)
+    return transform_points_ragged(points, off, transform.reshape(1, -1), max(N, 1), normals)
