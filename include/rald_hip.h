@@ -750,6 +750,44 @@ int rald_op_icp_ragged(const float* source, const int64_t* src_offsets, const in
 int rald_post_rigid_transform_ragged(const float* points, const int64_t* offsets, const int32_t* counts, int32_t batch, int64_t n_dense,
                                      int64_t n_total, int64_t max_per_sample, const double* transforms, int32_t transform_stride,
                                      const float* normals, float* out_points, float* out_normals, void* stream);
+/* ---- Isosurface meshing of a batch of dense volumes by naive surface nets: one vertex per sign-changing cell,
+ * one quad per sign-changing grid edge.  Defined to the bit: the result is a function of (values, iso, lo, spacing, dims) alone, the
+ * same in every call and at every batch position.
+ *   volume fp32 [batch, nx, ny, nz], z fastest.  Node (i, j, k) sits at fl(lo_a + fl((float)i_a * h_a)) per axis a (rald_query_grid
+ *   gives these positions).  HOST parameters: lo3 finite, spacing3 = h finite and > 0, dims3 = (nx, ny, nz) each 2 .. 1024, iso not a
+ *   NaN, batch 1 .. 65535 and batch * nx * ny * nz <= 357913941 = (2^31 - 1) / 6 (six triangles a node at most, counted in int32: a batch
+ *   of 8 volumes of 256^3 passes, one volume of 1024^3 does not).
+ *   INSIDE: a node is inside iff value > iso, the comparison of rald_post_occupied_points; a NaN is outside.
+ *   CELL (i, j, k), 0 <= i_a < n_a - 1, linear index (i * (ny - 1) + j) * (nz - 1) + k, ACTIVE iff its 8 corners are not all on one
+ *   side.  Its 12 edges: e = 4 * axis + 2 * p + q, p and q the 0 / 1 offsets along the two other axes in ascending axis order.  Edge e
+ *   CROSSES iff its two end nodes differ in INSIDE.
+ *   VERTEX of an active cell, all fp32, one rounded operation at a time, no contraction: for every crossing edge in ascending e, t =
+ *   fl(fl(iso - a) / fl(b - a)), a the value at the edge's lower node and b at its upper; a NaN t becomes 0; then t < 0 becomes 0 and
+ *   t > 1 becomes 1.  The edge's point in cell units is t on the edge's axis and (float)p, (float)q on the others.  u = the
+ *   per-component sum of these points, from +0.0 and in that order, divided by (float)count.  The vertex is fl(lo_a + fl(fl((float)i_a
+ *   + u_a) * h_a)).  Volume b's vertices are its active cells in ascending linear index, numbered from 0 inside the volume.
+ *   FACE: a grid edge along axis a from node n to n + e_a that crosses, (u, w) the other two axes in cyclic order (y, z), (z, x), (x,
+ *   y), makes a face only if n_u and n_w both lie in 1 .. dims - 2 (the four cells around the edge exist).  The cells by their (u, w)
+ *   offsets from n, the offset on axis a zero: c0 = (-1, -1), c1 = (0, -1), c2 = (0, 0), c3 = (-1, 0).  n inside: triangles (c0, c1,
+ *   c2), (c0, c2, c3); else (c0, c2, c1), (c0, c3, c2): counter-clockwise seen from the empty side.  Faces in ascending ((i * ny + j) *
+ *   nz + k) * 3 + a of (n, a), the two triangles in the order above; int32 vertex numbers local to the volume, never -1.
+ *   out_vertices fp32 [max_vertices, 3], out_faces int32 [max_faces, 3], out_cells (nullable) int32 [max_vertices]: each vertex's
+ *   linear cell index.  out_v_offsets, out_f_offsets DEVICE int64 [batch + 1]: volume b's rows are offsets[b] .. offsets[b + 1] - 1;
+ *   they always hold the TRUE counts.  max_vertices and max_faces (0 .. 2^40) are HOST capacities over the whole batch: a row at or
+ *   beyond its capacity is not written, a triangle is written whole or not at all.  out_vertices, out_faces NULL: that output is not
+ *   written; with both (and out_cells) NULL the call only counts.  Nothing outside these rows is written.
+ * Launches (surface_nets.hip): the volume is read once into one 64-bit word of INSIDE bits per run of 64 nodes along z; one lane per
+ * word makes the active mask (any & ~all over the four rows' words and their one-bit shifts), the face masks (XORs) and their
+ * popcounts; the two block scans of the ragged-cloud calls run over the words; one wave per word emits the vertices (eight loads
+ * per ACTIVE cell) and one the triangles (a vertex number is its word's base plus a popcount), visiting only the words that hold
+ * something.  One stream, no atomics, no kernel waits on another workgroup, every loop bounded by a constant; every row index derived
+ * from the scratch is checked against the capacity.
+ * scratch: rald_post_surface_scratch_bytes of the same batch and dims (about half a byte per node), 16-byte aligned, never NULL;
+ * -1 (and rald_last_error) for sizes the call refuses.  Every invalid argument is refused with a status before any GPU work. */
+int64_t rald_post_surface_scratch_bytes(int32_t batch, int32_t nx, int32_t ny, int32_t nz);
+int rald_post_surface_nets(const float* volume, int32_t batch, const int32_t* dims3_host, const float* lo3_host, const float* spacing3_host,
+                           float iso, float* out_vertices, int64_t* out_v_offsets, int64_t max_vertices, int32_t* out_faces,
+                           int64_t* out_f_offsets, int64_t max_faces, int32_t* out_cells, void* scratch, int64_t scratch_bytes, void* stream);
 /* pred = logits >= 0; accuracy[b] = mean(pred == labels); iou[b] = |pred & labels| / |pred | labels| + 1e-5 */
 int rald_post_iou(const float* logits, const float* labels, int32_t batch, int64_t n_queries, float* out_accuracy, float* out_iou, void* stream);
 
@@ -774,6 +812,11 @@ int rald_query_uniform_cart(const double* u3n, int64_t n, const double* pc_range
 /* norm_points (utils/utils.py:77-104) of a float32 array */
 int rald_query_norm_points(const float* points, int64_t n, const double* pc_range6_host, int32_t norm_anisotropy, int32_t norm_isotropy,
                            float* out_points, void* stream);
+/* The nodes of a regular grid, the positions rald_post_surface_nets gives its volume: x-planes i0 .. i0 + ni - 1 (inside 0 .. nx - 1) as
+ * out fp32 [ni * ny * nz, 3], z fastest; node (i, j, k) at fl(lo_a + fl((float)i_a * h_a)) per axis, fp32 without contraction.  lo3 finite,
+ * spacing3 finite and > 0, dims3 each 2 .. 1024, all HOST arrays. */
+int rald_query_grid(const float* lo3_host, const float* spacing3_host, const int32_t* dims3_host, int32_t i0, int32_t ni, float* out_points,
+                    void* stream);
 /* aug_query_helper (datasets/utils/query_helper.py:3-42) [+ norm_points when normalise != 0, as
  * engine_generation.py:292-297 does]: out [aug_num,3] = the first min(n_helper, aug_num) helper points, then
  * for g < aug_num - n_helper: clip(helper[sel_index[g]] + (2*u_bias[g,:]-1) * voxel_size * aug_scales[g]).

@@ -699,6 +699,19 @@ int rald_post_rigid_transform_ragged(const float* points, const int64_t* offsets
                                   normals, out_points, out_normals, (hipStream_t)stream);
 }
 
+// ---- isosurface meshing of dense volumes by surface nets ---------------------------------
+int64_t rald_post_surface_scratch_bytes(int32_t batch, int32_t nx, int32_t ny, int32_t nz) {
+    const int64_t n = surface_scratch_bytes(batch, nx, ny, nz);
+    if (n < 0) set_error("rald_post_surface_scratch_bytes: batch 1 .. 65535, dims 2 .. 1024 each, batch * nx * ny * nz <= 357913941");
+    return n;
+}
+int rald_post_surface_nets(const float* volume, int32_t batch, const int32_t* dims3_host, const float* lo3_host, const float* spacing3_host,
+                           float iso, float* out_vertices, int64_t* out_v_offsets, int64_t max_vertices, int32_t* out_faces,
+                           int64_t* out_f_offsets, int64_t max_faces, int32_t* out_cells, void* scratch, int64_t scratch_bytes, void* stream) {
+    return surface_nets(volume, batch, dims3_host, lo3_host, spacing3_host, iso, out_vertices, out_v_offsets, max_vertices, out_faces,
+                        out_f_offsets, max_faces, out_cells, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 int rald_radar_cube_prepare(const float* raw, int32_t batch, int32_t R, int32_t A, int32_t E, int32_t raw_channels, int32_t tgt_A,
                             int32_t tgt_E, int32_t norm_intensity, float max_intensity, int32_t norm_dopp, float max_dopp, float* out,
                             void* stream) {
@@ -817,6 +830,10 @@ int rald_query_norm_points(const float* points, int64_t n, const double* pc_rang
                            float* out_points, void* stream) {
     RALD_CHECK(pc_range6_host && (n == 0 || (points && out_points)), "rald_query_norm_points: null argument");
     return query_norm_points(points, n, pc_range6_host, norm_anisotropy, norm_isotropy, out_points, (hipStream_t)stream);
+}
+int rald_query_grid(const float* lo3_host, const float* spacing3_host, const int32_t* dims3_host, int32_t i0, int32_t ni, float* out_points,
+                    void* stream) {
+    return query_grid(lo3_host, spacing3_host, dims3_host, i0, ni, out_points, (hipStream_t)stream);
 }
 int rald_query_refine(const float* helper_points, int64_t n_helper, int64_t aug_num, const int64_t* sel_index, const int64_t* aug_scales,
                       const double* u_bias, const double* pc_range6_host, const double* voxel_size3_host, int32_t norm_anisotropy,

@@ -418,7 +418,17 @@ int icp_ragged(const RaggedCloud& src, const RaggedCloud& tgt, const float* targ
 int rigid_transform_ragged(const RaggedCloud& c, const double* transforms, int stride, const float* normals, float* out_points,
                            float* out_normals, hipStream_t st);
 
+// ---------------------------------------------------------------- surface_nets.hip
+// naive surface nets on a batch of dense volumes: one vertex per sign-changing cell, two triangles per sign-changing grid edge with four
+// cells around it, counted and ordered on 64-bit sign words
+int64_t surface_scratch_bytes(int B, int nx, int ny, int nz);
+int surface_nets(const float* volume, int B, const int32_t* dims3_host, const float* lo3_host, const float* spacing3_host, float iso,
+                 float* out_vertices, int64_t* out_v_offsets, int64_t max_vertices, int32_t* out_faces, int64_t* out_f_offsets,
+                 int64_t max_faces, int32_t* out_cells, void* scratch, int64_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- query.hip
+// the nodes of x-planes i0 .. i0 + ni - 1 of a regular grid, [ni * ny * nz, 3], z fastest
+int query_grid(const float* lo3_host, const float* spacing3_host, const int32_t* dims3_host, int i0, int ni, float* out, hipStream_t st);
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st);
 int query_uniform_cart(const double* u, int64_t n, const double* range_cart, const double* range_polar, int aniso, int iso, float* out,
                        int64_t* out_count, int* scratch, hipStream_t st);

@@ -226,7 +226,39 @@ __global__ void refine_ragged_kernel(RefineRaggedArgs a) {
     else for (int c = 0; c < 3; ++c) out[c] = p[c];
 }
 
+// ---- the nodes of a regular grid: node (i, j, k) at fl(lo + fl((float)i * h)) per axis, z fastest (the nodes of surface_nets.hip)
+struct GridArgs { float lo[3], h[3]; int ny, nz, i0; int64_t n; float* out; };
+
+__global__ __launch_bounds__(256) void query_grid_kernel(GridArgs a) {
+#pragma clang fp contract(off)
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.n) return;
+    const int64_t row = q / a.nz;
+    const int k = (int)(q - row * a.nz), i = (int)(row / a.ny), j = (int)(row - (int64_t)i * a.ny);
+    a.out[q * 3] = a.lo[0] + (float)(a.i0 + i) * a.h[0];
+    a.out[q * 3 + 1] = a.lo[1] + (float)j * a.h[1];
+    a.out[q * 3 + 2] = a.lo[2] + (float)k * a.h[2];
+}
+
 // ---- launchers ---------------------------------------------------------------------------------
+int query_grid(const float* lo3_host, const float* spacing3_host, const int32_t* dims3_host, int i0, int ni, float* out, hipStream_t st) {
+    RALD_CHECK(lo3_host && spacing3_host && dims3_host && out, "query_grid: null pointer");
+    for (int k = 0; k < 3; ++k) {
+        RALD_CHECK(dims3_host[k] >= 2 && dims3_host[k] <= 1024, "query_grid: dims must be 2 .. 1024 each");
+        RALD_CHECK(std::isfinite(lo3_host[k]) && std::isfinite(spacing3_host[k]) && spacing3_host[k] > 0.f,
+                   "query_grid: lo must be finite, spacing finite and > 0");
+    }
+    RALD_CHECK(i0 >= 0 && ni >= 1 && i0 <= dims3_host[0] - ni, "query_grid: planes i0 .. i0 + ni - 1 must lie in 0 .. nx - 1");
+    GridArgs a;
+    for (int k = 0; k < 3; ++k) { a.lo[k] = lo3_host[k]; a.h[k] = spacing3_host[k]; }
+    a.ny = dims3_host[1]; a.nz = dims3_host[2]; a.i0 = i0;
+    a.n = (int64_t)ni * a.ny * a.nz;                         // <= 2^30
+    a.out = out;
+    hipLaunchKernelGGL(query_grid_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a);
+    RALD_HIP(hipGetLastError());
+    return 0;
+}
+
 int query_uniform(const double* u, int64_t n, const double* pc_range, int aniso, int iso, float* out, hipStream_t st) {
     RALD_CHECK(n >= 0 && (aniso || iso), "query_uniform: n >= 0 and one of norm_anisotropy / norm_isotropy expected");
     if (n == 0) return 0;

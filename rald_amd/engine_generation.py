@@ -812,6 +812,97 @@ def scan_point_clouds(vae, sampled_tokens: torch.Tensor, args, az_deg, el_deg, n
     return out
 
 
+def _check_mesh_inputs(sampled_tokens, args, resolution, threshold, surface_steps, surface_max_step, capacity, surfaces, metric_thresholds):
+    """The argument rules of extract_meshes, all on the host: ValueError before any device use -> (the grid, threshold, surface_steps,
+    capacity, the metric's thresholds or None)."""
+    _check_batch_inputs(sampled_tokens, None, surfaces)
+    lidar = args.dataset.lidar
+    if not (lidar.norm_anisotropy or lidar.norm_isotropy):
+        raise ValueError("one of norm_anisotropy / norm_isotropy is required")
+    grid = QP.field_grid(resolution)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not np.isfinite(threshold):
+        raise ValueError("threshold must be a finite number")
+    surface_steps = _whole(surface_steps, 0, 64, "surface_steps must be an integer in 0 .. 64")
+    _positive(surface_max_step, "surface_max_step must be a finite number > 0")
+    B, (nx, ny, nz) = sampled_tokens.shape[0], grid[2]
+    if B > 65535 or B * nx * ny * nz > PP.SURFACE_MAX_NODES:
+        raise ValueError(f"batch * resolution^3 must be at most {PP.SURFACE_MAX_NODES} nodes and the batch at most 65535")
+    if capacity is not None:
+        try:
+            ok = len(capacity) == 2
+            capacity = (_whole(capacity[0], 0, 2 ** 31 - 1, ""), _whole(capacity[1], 0, 2 ** 40, ""))
+        except (TypeError, ValueError, IndexError):
+            ok = False
+        if not ok:
+            raise ValueError("capacity must be (max_vertices, max_faces), two non-negative integers (max_vertices below 2^31), or None")
+    thresholds = PP._thresholds(metric_thresholds) if metric_thresholds is not None and len(metric_thresholds) else None
+    return grid, float(threshold), surface_steps, capacity, thresholds
+
+
+@torch.no_grad()
+def extract_meshes(vae, sampled_tokens: torch.Tensor, args, resolution, threshold: float = 0.0, normals: bool = False, surface_steps: int = 0,
+                   surface_max_step: float = 0.05, capacity=None, surfaces: Optional[torch.Tensor] = None,
+                   metric_thresholds=()) -> List[Dict[str, object]]:
+    """Every frame's decoder field as a triangle mesh instead of the thresholded cloud of infer_point_clouds.
+
+    query_points.field_grid(resolution) (the node grid over the normalised box) -> KLAutoEncoder.decode_volume (the logits on its nodes,
+    decode's bit for bit) -> postprocess.extract_surface_batch (surface nets at logit = threshold) -> [surface_steps >
+    0: the vertices moved onto logit = 0 by that many clamped Newton steps, query_points.project_to_surface_ragged; the faces keep
+    their numbers] -> metric coordinates (cartesian in view-cone mode), the faces' winding kept counter-clockwise seen from the empty
+    side (postprocess.mesh_to_metric) -> [normals: the logit's gradient at the final vertices, postprocess.oriented_points_ragged] ->
+    [surfaces [B,P,3], the normalised ground truth: the Chamfer distance of the vertices, with metric_thresholds the whole
+    cloud_metrics_ragged row, unless skip_eval_metric].
+    capacity = (max_vertices, max_faces) over the batch: everything stays on the device until ONE host read at the end (the offsets and
+    the metric), and a capacity the meshes do not fit raises RuntimeError naming the counts.  capacity = None adds
+    extract_surface_batch's read of the two totals.  Argument errors raise ValueError before any device use.
+
+    Returns a list of B dicts {'vertices' [V_b,3] float32 metric, 'faces' [F_b,3] int32 into them} on the device (+ 'normals' [V_b,3]
+    unit vectors from occupied to empty, zero where undefined; + 'cd' a float, inf for an empty mesh; + 'metrics' with thresholds)."""
+    grid, threshold, surface_steps, capacity, thresholds = _check_mesh_inputs(sampled_tokens, args, resolution, threshold, surface_steps,
+                                                                              surface_max_step, capacity, surfaces, metric_thresholds)
+    lidar = args.dataset.lidar
+    aniso, iso = lidar.norm_anisotropy, lidar.norm_isotropy
+    view_cone = bool(_get(lidar, "view_cone_mode", False))
+    B, dev = sampled_tokens.shape[0], sampled_tokens.device
+    lo, spacing, dims = grid
+    volume = vae.decode_volume(sampled_tokens, lo, spacing, dims)
+    v, v_off, f, f_off = PP.extract_surface_batch(volume, threshold, lo, spacing, capacity)
+    cap_v, cap_f = v.shape[0], f.shape[0]
+    row_off = v_off.clamp(max=cap_v)                                                               # what the later stages may read
+    longest = max(1, min(cap_v, (dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1)))
+    nrm = None
+    if cap_v == 0:                                                                                 # no vertex anywhere: nothing to decode
+        normals, surface_steps, nrm = False, 0, (v if normals else None)
+    if normals or surface_steps > 0:
+        v, _, grad = QP.project_to_surface_ragged(vae, sampled_tokens, v, row_off, longest, surface_steps, surface_max_step)
+    pts, faces = PP.mesh_to_metric(v, f, lidar.pc_range, aniso, iso, view_cone)
+    if normals:
+        pts, nrm = PP.oriented_points_ragged(v, grad, row_off, lidar.pc_range, aniso, iso, view_cone_mode=view_cone)
+    cd = metrics = None
+    if surfaces is not None and not _get(args.eval, "skip_eval_metric", False):
+        P = surfaces.shape[1]
+        gt = PP.inverse_norm_points(surfaces.to(dev).reshape(-1, 3), lidar.pc_range, aniso, iso)
+        if view_cone:
+            gt = PP.polar2cartesian(gt)
+        gt_off = torch.arange(B + 1, dtype=torch.int64, device=dev) * P
+        cd, metrics = _metric(pts, row_off, gt, gt_off, longest, P, thresholds)
+    host = _HostPack(v_off=v_off, f_off=f_off, cd=cd, metrics=metrics).read()                      # the one host read
+    vo, fo = [int(x) for x in host["v_off"]], [int(x) for x in host["f_off"]]
+    if vo[B] > cap_v or fo[B] > cap_f:
+        raise RuntimeError(f"extract_meshes: the batch has {vo[B]} vertices and {fo[B]} faces, the capacity is ({cap_v}, {cap_f})")
+    out = []
+    for b in range(B):
+        mesh = {"vertices": pts[vo[b]:vo[b + 1]], "faces": faces[fo[b]:fo[b + 1]]}
+        if nrm is not None:
+            mesh["normals"] = nrm[vo[b]:vo[b + 1]]
+        if cd is not None:
+            mesh["cd"] = host["cd"][b]
+        if metrics is not None:
+            mesh["metrics"] = PP._metrics_to_host(host["metrics"], B, len(thresholds))[b]
+        out.append(mesh)
+    return out
+
+
 @torch.no_grad()
 def evaluate_sharded(model, vae, cubes: torch.Tensor, queries: torch.Tensor, eval_batch_size: int = 1,
                      metric_fn: Optional[Callable[[torch.Tensor, int], float]] = None,

@@ -86,6 +86,33 @@ class KLAutoEncoder(_HipBacked):
         h = self._handle()
         return h.decode_queries(self._context(x), queries).unsqueeze(-1)
 
+    def decode_volume(self, x, lo, spacing, dims, max_queries=1 << 22):
+        """The decoder field on a regular grid: x [B,M,latent_dim]; node (i, j, k) at lo + (i, j, k) * spacing, dims = (nx, ny, nz)
+        (query_points.field_grid / grid_queries) -> logits [B,nx,ny,nz], the volume postprocess.extract_surface_batch meshes.  Decoded in
+        slabs of whole x-planes of at most max_queries nodes per sample, through decode's path and its memoised context.  The decoder cuts
+        a query set into chunks of 64 from its first row, so a slab holds a multiple of 64 / gcd(64, ny * nz) planes (at least that many,
+        also where they exceed max_queries): every slab starts on a chunk boundary of the whole grid and every logit is decode's on
+        grid_queries(lo, spacing, dims), bit for bit."""
+        import math
+        from . import query_points as QP
+        from .postprocess import _grid_spec
+        lo3, h3, dims3 = _grid_spec(lo, spacing, dims)
+        if isinstance(max_queries, bool) or not isinstance(max_queries, int) or max_queries < 1:
+            raise ValueError("max_queries must be an integer >= 1")
+        if not (isinstance(x, torch.Tensor) and x.dim() == 3):
+            raise ValueError("x must be the latents [B, M, latent_dim]")
+        plane = dims3[1] * dims3[2]
+        step = 64 // math.gcd(64, plane)
+        per_slab = max(step, max_queries // plane // step * step)
+        h, ctx = self._handle(), self._context(x)
+        B = x.shape[0]
+        out = torch.empty(B, dims3[0] * plane, device=x.device, dtype=torch.float32)
+        for i0 in range(0, dims3[0], per_slab):
+            ni = min(per_slab, dims3[0] - i0)
+            q = QP.grid_queries(lo3, h3, dims3, i0, ni, device=out.device)
+            out[:, i0 * plane:(i0 + ni) * plane] = h.decode_queries(ctx, q.unsqueeze(0).expand(B, -1, -1))
+        return out.view(B, *dims3)
+
     def decode_ragged(self, x, queries, offsets, max_per_sample):
         """decode for query sets of different sizes: x [B,M,latent_dim], queries [T,3] = the B sets concatenated, offsets int64 [B+1]
         on the device, max_per_sample = a host upper bound of the longest set (too small a bound leaves the rows behind it undecoded,

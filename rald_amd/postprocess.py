@@ -18,7 +18,9 @@ clouds with normals), ``cluster_dbscan*`` / ``remove_small
 25), and ``segment_plane*`` / ``remove_planes*`` (RANSAC plane segmentation with a fixed number of counter-based hypotheses, the device
 counterpart of Open3D's ``segment_plane``, and plane removal), and ``register_icp*`` / ``transform_points*``
 (ICP registration of one ragged batch onto another, point-to-point and point-to-plane, iterated on the device, the device counterpart
-of Open3D's ``registration_icp``, and the rigid transform that applies its result).
+of Open3D's ``registration_icp``, and the rigid transform that applies its result), and ``extract_surface*`` /
+``mesh_to_metric`` (a dense volume, such as the decoder's field on a grid, to a triangle mesh by naive surface nets, and the mesh in
+metric coordinates).
 """
 from __future__ import annotations
 
@@ -1373,3 +1375,113 @@ def transform_points(points: torch.Tensor, transform: torch.Tensor, normals: Opt
     _need_cuda(points, "points")
     off = torch.tensor([0, N], dtype=torch.int64, device=points.device)
     return transform_points_ragged(points, off, transform.reshape(1, -1), max(N, 1), normals)
+
+
+# ---- isosurface meshing of dense volumes: naive surface nets ------------------------------------------------------
+SURFACE_MAX_DIM = 1024                                   # the largest node count per axis of rald_post_surface_nets
+SURFACE_MAX_NODES = (2 ** 31 - 1) // 6                   # batch * nx * ny * nz: six triangles a node at most, counted in int32
+
+
+def _grid_spec(lo, spacing, dims):
+    """The rules of a node grid (ValueError) -> (lo3, h3 as the float32 numbers the kernels use, dims3 as ints)."""
+    try:
+        lo3, h3 = [_f32(float(x)) for x in lo], [_f32(float(x)) for x in spacing]
+        ok = len(lo3) == 3 and len(h3) == 3 and len(dims) == 3 and all(not isinstance(d, bool) and int(d) == d for d in dims)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("lo and spacing must be 3 numbers each, dims 3 integers")
+    if any(not math.isfinite(x) for x in lo3) or any(not math.isfinite(x) or x <= 0 for x in h3):
+        raise ValueError("lo must be finite and spacing finite and > 0 in float32")
+    dims3 = [int(d) for d in dims]
+    if any(d < 2 or d > SURFACE_MAX_DIM for d in dims3):
+        raise ValueError(f"every dim must be in 2 .. {SURFACE_MAX_DIM}")
+    return lo3, h3, dims3
+
+
+def _surface_args(volume, iso, lo, spacing, capacity, dim: int):
+    """The rules of the surface calls (ValueError, before anything asks where the volume lives) -> (iso, lo3, h3, capacity or None)."""
+    if not (isinstance(volume, torch.Tensor) and volume.dim() == dim and volume.is_floating_point()):
+        raise ValueError("volume must be a floating-point tensor " + ("[B, nx, ny, nz]" if dim == 4 else "[nx, ny, nz]"))
+    shape = tuple(volume.shape[-3:])
+    B = volume.shape[0] if dim == 4 else 1
+    lo3, h3, _ = _grid_spec(lo, spacing, shape)
+    if B < 1 or B > 65535 or B * shape[0] * shape[1] * shape[2] > SURFACE_MAX_NODES:
+        raise ValueError(f"batch must be 1 .. 65535 and batch * nx * ny * nz at most {SURFACE_MAX_NODES}")
+    if isinstance(iso, bool) or not isinstance(iso, (int, float)) or math.isnan(iso):
+        raise ValueError("iso must be a number, not a NaN")
+    if capacity is not None:
+        try:
+            mv, mf = capacity
+            capacity = (_whole(mv, 0, 2 ** 40, ""), _whole(mf, 0, 2 ** 40, ""))
+        except (TypeError, ValueError):
+            raise ValueError("capacity must be (max_vertices, max_faces), two integers in 0 .. 2^40, or None") from None
+    return _f32(float(iso)), lo3, h3, capacity
+
+
+def _surface_call(volume, iso, lo3, h3, vertices, v_off, faces, f_off, cells) -> None:
+    import ctypes as C
+    B, dims = volume.shape[0], [int(d) for d in volume.shape[1:]]
+    L = lib()
+    nbytes = _nbytes(L.rald_post_surface_scratch_bytes(B, *dims))
+    scratch = _scratch(nbytes, volume.device)
+    check(L.rald_post_surface_nets(volume.data_ptr(), B, (C.c_int32 * 3)(*dims), (C.c_float * 3)(*lo3), (C.c_float * 3)(*h3), iso,
+                                   _opt(vertices), v_off.data_ptr(), 0 if vertices is None else vertices.shape[0], _opt(faces),
+                                   f_off.data_ptr(), 0 if faces is None else faces.shape[0], _opt(cells), scratch.data_ptr(), nbytes, _stream()))
+
+
+def extract_surface_batch(volume: torch.Tensor, iso: float = 0.0, lo: Sequence[float] = (0.0, 0.0, 0.0),
+                          spacing: Sequence[float] = (1.0, 1.0, 1.0), capacity: Optional[Tuple[int, int]] = None, return_cells: bool = False):
+    """The isosurface value = iso of every volume of a batch as a triangle mesh, by naive surface nets (rald_post_surface_nets, DESIGN.md
+    section 28): volume [B, nx, ny, nz] on the device, node (i, j, k) at lo + (i, j, k) * spacing -> (vertices float32 [V, 3], v_offsets
+    int64 [B+1], faces int32 [F, 3], f_offsets int64 [B+1][, cells int32 [V]]) on the device.  Volume b's vertices are rows v_offsets[b]
+    .. v_offsets[b+1]-1, one per cell whose corners are not all on one side of iso (inside iff value > iso; a NaN is outside), at the
+    mean of the cell's edge crossings, in ascending cell order; its triangles rows f_offsets[b] .. f_offsets[b+1]-1, two per grid edge
+    that crosses and has four cells around it, with vertex numbers local to the volume, counter-clockwise seen from the outside (value
+    <= iso), so normals point from occupied to empty.  A surface that does not touch the grid's border is closed.  cells: each vertex's
+    linear cell index (i * (ny - 1) + j) * (nz - 1) + k.
+    capacity = (max_vertices, max_faces) over the whole batch: one call, no host read; V, F are the capacities, the offsets hold the
+    TRUE counts (compare offsets[B] with the capacity: rows at or beyond it are not written, rows between offsets[B] and the capacity
+    are unspecified).  capacity = None: a counting call, ONE host read of the two totals, exact allocation, the full call.
+    Defined to the bit: a function of the values, iso, lo, spacing and the dims alone.  Runs on the current stream."""
+    iso, lo3, h3, capacity = _surface_args(volume, iso, lo, spacing, capacity, 4)
+    _need_cuda(volume, "volume")
+    volume = _f32c(volume)
+    B, dev = volume.shape[0], volume.device
+    v_off = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    f_off = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    if capacity is None:
+        _surface_call(volume, iso, lo3, h3, None, v_off, None, f_off, None)
+        capacity = tuple(int(x) for x in torch.stack((v_off[B], f_off[B])).tolist())          # the one host read
+    vertices = torch.empty(capacity[0], 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(capacity[1], 3, device=dev, dtype=torch.int32)
+    cells = torch.empty(capacity[0], device=dev, dtype=torch.int32) if return_cells else None
+    # an empty tensor has no address to pass: a NULL output is simply not written
+    _surface_call(volume, iso, lo3, h3, vertices if capacity[0] else None, v_off, faces if capacity[1] else None, f_off,
+                  cells if capacity[0] else None)
+    return (vertices, v_off, faces, f_off) + ((cells,) if return_cells else ())
+
+
+def extract_surface(volume: torch.Tensor, iso: float = 0.0, lo: Sequence[float] = (0.0, 0.0, 0.0), spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                    return_cells: bool = False):
+    """extract_surface_batch for one volume [nx, ny, nz] -> (vertices [V, 3], faces int32 [F, 3][, cells]), trimmed (one host read)."""
+    _surface_args(volume, iso, lo, spacing, None, 3)
+    out = extract_surface_batch(volume.unsqueeze(0), iso, lo, spacing, None, return_cells)
+    return (out[0], out[2]) + tuple(out[4:])
+
+
+def mesh_to_metric(vertices_norm: torch.Tensor, faces: torch.Tensor, lidar_pc_range, norm_anisotropy: bool, norm_isotropy: bool,
+                   view_cone_mode: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A mesh in the decoder's normalised coordinates -> (vertices, faces) in metric coordinates (cartesian if view_cone_mode): the
+    vertices by inverse_norm_points (+ polar2cartesian), bit for bit; the faces with the last two vertex numbers of every triangle
+    exchanged where the transform reverses orientation, so that they stay counter-clockwise seen from the empty side.  In view-cone
+    mode it does: the azimuth is -(y * pi / 180), so the Jacobian determinant of (r, az, el) -> (x, y, z) is negative wherever r > 0 and
+    |el| < 90.  Without it the transform is a positive scaling per axis and a shift, which keeps orientation."""
+    _xyz(vertices_norm, "vertices_norm")
+    if not (isinstance(faces, torch.Tensor) and faces.dim() == 2 and faces.shape[1] == 3 and not faces.is_floating_point()):
+        raise ValueError("faces must be an integer tensor [F, 3]")
+    if not (norm_anisotropy or norm_isotropy):
+        raise ValueError("one of norm_anisotropy / norm_isotropy is required")
+    _doubles(lidar_pc_range, 6, "pc_range", _PC_RANGE)
+    out = _transform(vertices_norm, lidar_pc_range, norm_anisotropy, norm_isotropy, bool(view_cone_mode))
+    return out, (faces[:, [0, 2, 1]].contiguous() if view_cone_mode else faces)

@@ -286,3 +286,40 @@ def beam_segments(args, az_deg, el_deg, r_min: Optional[float] = None, r_max: Op
     start = norm_points(torch.stack((torch.full_like(az, r0), az, el), dim=1), lidar.pc_range, lidar.norm_anisotropy, lidar.norm_isotropy)
     end = norm_points(torch.stack((torch.full_like(az, r1), az, el), dim=1), lidar.pc_range, lidar.norm_anisotropy, lidar.norm_isotropy)
     return start, end - start
+
+
+def field_grid(resolution) -> Tuple[Tuple[float, ...], Tuple[float, ...], Tuple[int, ...]]:
+    """The node grid over the decoder's normalised box [-1, 1]^3 -> (lo, spacing, dims): `resolution` nodes per axis (an int, or one per
+    axis; 2 .. 1024 each), the first at -1 and the last at 1 up to float32 rounding: spacing = float32(2 / (n - 1))."""
+    from .postprocess import SURFACE_MAX_DIM, _f32
+    res = (resolution,) * 3 if isinstance(resolution, int) and not isinstance(resolution, bool) else resolution
+    try:
+        ok = len(res) == 3 and all(isinstance(n, int) and not isinstance(n, bool) and 2 <= n <= SURFACE_MAX_DIM for n in res)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"resolution must be an integer, or three, in 2 .. {SURFACE_MAX_DIM}")
+    return (-1.0, -1.0, -1.0), tuple(_f32(2.0 / (n - 1)) for n in res), tuple(int(n) for n in res)
+
+
+def _grid_planes(dims3, i0, ni):
+    i0 = int(i0)
+    ni = dims3[0] - i0 if ni is None else int(ni)
+    if i0 < 0 or ni < 1 or i0 + ni > dims3[0]:
+        raise ValueError("planes i0 .. i0 + ni - 1 must lie in 0 .. nx - 1")
+    return i0, ni
+
+
+def grid_queries(lo, spacing, dims, i0: int = 0, ni: Optional[int] = None, device=None) -> torch.Tensor:
+    """The nodes of x-planes i0 .. i0 + ni - 1 (default: all) of a regular grid -> float32 [ni * ny * nz, 3] on the device, z fastest:
+    node (i, j, k) at lo + (i, j, k) * spacing, each product and sum rounded once in float32 (rald_query_grid) - the positions
+    postprocess.extract_surface_batch gives the values of a volume [nx, ny, nz]."""
+    import ctypes as C
+    from .postprocess import _grid_spec
+    lo3, h3, dims3 = _grid_spec(lo, spacing, dims)
+    i0, ni = _grid_planes(dims3, i0, ni)
+    device = _device(device, None)
+    out = torch.empty(ni * dims3[1] * dims3[2], 3, device=device, dtype=torch.float32)
+    with torch.cuda.device(device):
+        check(lib().rald_query_grid((C.c_float * 3)(*lo3), (C.c_float * 3)(*h3), (C.c_int32 * 3)(*dims3), i0, ni, out.data_ptr(), _stream()))
+    return out
