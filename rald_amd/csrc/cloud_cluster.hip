@@ -16,7 +16,7 @@
 //   cloud_block_scan, cloud_offsets              the scans of the compaction: the rank of a core root is its cluster id, the total C
 //   clu_number    (1024 rows, cloud)             a core root's cluster id to its row; sizes = 0
 //   clu_label     (256 rows, cloud)              labels, sizes (one integer atomicAdd per wave and label), num_clusters
-// and for the filter clu_argmax (cloud), clu_keep (256 rows, cloud), the compaction of cloud_index.hip and clu_kept_labels.
+// and for the filter clu_argmax (cloud), clu_keep (256 rows, cloud), the compaction of cloud_index.hip and its cloud_kept_labels.
 // The union-find keeps ONE invariant: parent[x] <= x, and parent[x] is in x's tree.  A union hooks the LARGER root under the smaller
 // with a device-scope compare-and-swap and, when that fails, finds both roots again: a root only ever moves down, so the final root
 // of a component is its smallest row whatever the order of arrival.  Path halving writes with atomicMin a value read from the chain.
@@ -48,7 +48,6 @@ struct ClusterArgs {
     int32_t* labels; int32_t* sizes; int32_t* nclu;          // the outputs of the labels call, or scratch
     int* best;                                               // [batch] the largest cluster
     int64_t* kept;                                           // [n_total] the kept rows' indices (out_index, or scratch)
-    int32_t* out_labels;                                     // [n_total] per kept row
     BlockScan num, sc;                                       // the numbering of the core roots, the filter's compaction
 };
 
@@ -231,15 +230,7 @@ __global__ __launch_bounds__(CLU_T) void clu_argmax(ClusterArgs a) {
         const int v = a.sizes[row0 + c];
         if (v > bv) { bv = v; bc = c; }
     }
-    sv[tid] = bv; sc[tid] = bc;
-    __syncthreads();
-    for (int s = CLU_T / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            const int v = sv[tid + s], c = sc[tid + s];
-            if (c >= 0 && (v > sv[tid] || (v == sv[tid] && c < sc[tid]))) { sv[tid] = v; sc[tid] = c; }
-        }
-        __syncthreads();
-    }
+    block_argmax<CLU_T>(bv, bc, sv, sc, tid);
     if (tid == 0) a.best[b] = sc[0];
 }
 
@@ -253,20 +244,6 @@ __global__ __launch_bounds__(CLU_T) void clu_keep(ClusterArgs a) {
     bool keep = label >= 0;
     if (keep) keep = a.sizes[row0 + rad_clamp(label, n)] >= a.min_size && (!a.largest || label == a.best[b]);
     a.root[row0 + j] = keep;
-}
-
-// behind the compaction: the label of every kept row, by the row index the compaction left
-__global__ __launch_bounds__(CLU_T) void clu_kept_labels(ClusterArgs a) {
-    const int b = blockIdx.y;
-    int64_t row0;
-    const int n = ragged_span(a.c, b, row0);
-    const int64_t j = (int64_t)blockIdx.x * CLU_T + threadIdx.x;
-    const int64_t o0 = a.sc.out_offsets[b];
-    if (j >= n || j >= a.sc.out_offsets[b + 1] - o0) return;
-    const int64_t vo = o0 + j;
-    if (vo < 0 || vo >= a.c.n_total) return;                 // cannot happen with offsets that do not overlap
-    const int64_t r = a.kept[vo];
-    a.out_labels[vo] = a.labels[row0 + (r < 0 ? 0 : (r < n ? r : n - 1))];
 }
 
 void clu_layout(ClusterArgs& a, CloudIndex& ix, Carver& s, int64_t chunk) {
@@ -350,14 +327,13 @@ int cluster_filter_ragged(const RaggedCloud& c, const GridSpec& grid, float eps,
                         chunk, st));
     a.min_size = min_cluster_size;
     a.largest = largest_only != 0;
-    a.out_labels = out_labels;
     if (out_index) a.kept = out_index;
     a.sc.out_offsets = out_offsets;
     const dim3 by_row((unsigned)((c.max_per_sample + CLU_T - 1) / CLU_T), c.batch);
     if (a.largest) hipLaunchKernelGGL(clu_argmax, dim3(c.batch), dim3(CLU_T), 0, st, a);
     hipLaunchKernelGGL(clu_keep, by_row, dim3(CLU_T), 0, st, a);
     compact_rows_ragged(c, a.sc, a.root, 1, out_points, a.kept, st);
-    hipLaunchKernelGGL(clu_kept_labels, by_row, dim3(CLU_T), 0, st, a);
+    cloud_kept_labels_ragged(c, out_offsets, a.kept, a.labels, out_labels, st);
     RALD_HIP(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,8 @@
-// What the grid-indexed operations on ragged clouds share (cloud_index.hip; voxel_reduce.hip, radius_search.hip, knn_search.hip use it;
-// DESIGN.md section 21): the layout and the grid as two plain structs, the scratch carver, the spatial index, the compaction in row
-// order, and the device helpers of the cell rule, the scan range, the radius walk and the block scans.
+// What the operations on ragged clouds share (cloud_index.hip; voxel_reduce.hip, radius_search.hip, knn_search.hip, cloud_normals.hip,
+// cloud_cluster.hip, cloud_plane.hip and cloud_icp.hip use it): the layout and the grid as two plain structs, the
+// scratch carver, the spatial index, the compaction in row order with the gather of the kept rows' labels, and the device helpers of
+// the cell rule, the scan range, the radius walk, the block scans, the fixed shape of the float64 sums and
+// the argmax of a workgroup.
 #pragma once
 #include <cmath>
 
@@ -29,7 +31,8 @@ struct CellGrid {
     unsigned cells;
 };
 
-constexpr int CLOUD_SEG = 1024;                              // rows (or sorted positions) per workgroup of a flag / rank kernel, one per thread
+// rows (or sorted positions) per workgroup of a flag / rank kernel, one per thread, and the block of the fixed sum shape (below)
+constexpr int CLOUD_SEG = 1024;
 
 // ---- scratch: every operation describes its buffers once, in a layout function that takes them from a carver in order; the function
 // runs on a null base for the size and on the caller's scratch for the call
@@ -93,6 +96,9 @@ void block_scan_launch(const RaggedCloud& c, const BlockScan& sc, hipStream_t st
 // checked: the layout is one cloud_grid_check has accepted
 void compact_rows_ragged(const RaggedCloud& c, BlockScan sc, const int32_t* keep, int at_least, float* out_points, int64_t* out_index,
                          hipStream_t st);
+// behind a compaction that left out_offsets and the kept rows' indices: out_labels[kept row] = labels[its row]
+void cloud_kept_labels_ragged(const RaggedCloud& c, const int64_t* out_offsets, const int64_t* kept, const int32_t* labels, int32_t* out_labels,
+                              hipStream_t st);
 
 // ---- device helpers
 // the cloud's first row and its number of rows: the segment, capped by counts and by the host bound, clamped into [0, n_total]
@@ -115,6 +121,7 @@ __device__ __forceinline__ float voxel_cell(float p, float lo, float v) {
     return floorf((p - lo) / v);
 }
 __device__ __forceinline__ int rad_clamp(int r, int n) { return r < 0 ? 0 : (r < n ? r : n - 1); }
+__device__ __forceinline__ int64_t rad_clamp(int64_t r, int64_t n) { return r < 0 ? 0 : (r < n ? r : n - 1); }
 // the cell of a scan bound as an index of the grid: the cell function of the keys, clamped in float (a NaN cannot occur: p is finite)
 __device__ __forceinline__ int rad_cell(float p, float lo, float v, int dims) {
     float cf = voxel_cell(p, lo, v);
@@ -213,6 +220,60 @@ __device__ __forceinline__ int block_rank(bool f, int* sh, int tid, int* total) 
     int rank = __popcll(bm & vox_lanes_below(lane));
     for (int i = 0; i < w; ++i) rank += sh[i];
     return rank;
+}
+
+// ---- the fixed sum shape of a cloud's float64 sums (include/rald_hip.h): blocks of CLOUD_SEG consecutive rows, a
+// row that does not count as +0.0; inside a block the halving tree v[i] += v[i + h], h = NT / 2 .. 1; the blocks' sums added left to
+// right from +0.0.  No contraction anywhere.  icp_sums and icp_solve (cloud_icp.hip) are the hand-scheduled instance of the same
+// shape - two tree levels in registers, sixteen block sums in flight - which tests/test_gpu_icp.py pins against this one by bits.
+// The tree over one value per thread -> v[0], in every thread.  v: NT doubles; every thread of the workgroup calls it; the barrier
+// behind the read lets the next call reuse v
+template <int NT>
+__device__ __forceinline__ double block_tree_sum(double x, double* v, int tid) {
+#pragma clang fp contract(off)
+    v[tid] = x;
+    __syncthreads();
+    for (int h = NT / 2; h >= 1; h >>= 1) {
+        if (tid < h) v[tid] += v[tid + h];
+        __syncthreads();
+    }
+    const double r = v[0];
+    __syncthreads();
+    return r;
+}
+// the blocks left to right: bs[0], bs[stride], .. of nseg blocks; the counts of their rows likewise
+__device__ __forceinline__ double fold_blocks(const double* bs, int nseg, int64_t stride) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    int g = 0;
+    for (; g + 16 <= nseg; g += 16) {                        // sixteen loads in flight, then their adds in order: one lane runs this
+        double v[16];                                        // loop, and a load behind every add would leave it waiting on each
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = bs[(g + u) * stride];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) s = s + v[u];
+    }
+    for (; g < nseg; ++g) s = s + bs[g * stride];
+    return s;
+}
+__device__ __forceinline__ int fold_blocks(const int* bc, int nseg, int64_t stride) {
+    int s = 0;
+    for (int g = 0; g < nseg; ++g) s += bc[g * stride];
+    return s;
+}
+// the tree of the "larger value, else smaller index" over one (value, index) per thread; an index < 0 is no candidate.  The winner
+// stands in sv[0], sc[0], valid in thread 0.  sv, sc: NT ints each
+template <int NT>
+__device__ __forceinline__ void block_argmax(int value, int index, int* sv, int* sc, int tid) {
+    sv[tid] = value; sc[tid] = index;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int v = sv[tid + s], c = sc[tid + s];
+            if (c >= 0 && (v > sv[tid] || (v == sv[tid] && c < sc[tid]))) { sv[tid] = v; sc[tid] = c; }
+        }
+        __syncthreads();
+    }
 }
 
 }  // namespace rald

@@ -16,6 +16,8 @@
 //   cloud_block_scan  (cloud)             exclusive scan of the block counts in place, the cloud's total
 //   cloud_offsets     one workgroup       out_offsets = exclusive scan of the totals over the batch
 //   cloud_compact     (1024 rows, cloud)  a kept row to out_offsets[b] + its rank
+// and behind it, for the filters that keep labels (cloud_cluster.hip, cloud_plane.hip):
+//   cloud_kept_labels (256 kept rows, cloud)  the label of every kept row, by the row index the compaction left
 // Integer LDS atomics only count digits.  Every loop is bounded by the cloud's length (<= max_per_sample, a host value), by the batch
 // or by 256.  A cloud's span is clamped into [0, n_total] before anything is addressed, so device offsets of any value reach neither
 // past `points` nor past the scratch; a row index read from the scratch is clamped into the cloud before it addresses anything.
@@ -392,6 +394,19 @@ __global__ __launch_bounds__(CLOUD_SEG) void cloud_compact(CompactArgs a) {
     if (a.out_index) a.out_index[vo] = j;
 }
 
+__global__ __launch_bounds__(VOX_KT) void cloud_kept_labels(RaggedCloud c, const int64_t* out_offsets, const int64_t* kept,
+                                                            const int32_t* labels, int32_t* out_labels) {
+    const int b = blockIdx.y;
+    int64_t row0;
+    const int n = ragged_span(c, b, row0);
+    const int64_t j = (int64_t)blockIdx.x * VOX_KT + threadIdx.x;
+    const int64_t o0 = out_offsets[b];
+    if (j >= n || j >= out_offsets[b + 1] - o0) return;
+    const int64_t vo = o0 + j;
+    if (vo < 0 || vo >= c.n_total) return;                   // cannot happen with offsets that do not overlap
+    out_labels[vo] = labels[row0 + rad_clamp(kept[vo], (int64_t)n)];
+}
+
 }  // namespace
 
 void block_scan_layout(BlockScan& sc, const RaggedCloud& c, Carver& s) {
@@ -412,6 +427,12 @@ void compact_rows_ragged(const RaggedCloud& c, BlockScan sc, const int32_t* keep
     hipLaunchKernelGGL(cloud_flags, by_seg, dim3(CLOUD_SEG), 0, st, a);
     block_scan_launch(c, sc, st);
     hipLaunchKernelGGL(cloud_compact, by_seg, dim3(CLOUD_SEG), 0, st, a);
+}
+
+void cloud_kept_labels_ragged(const RaggedCloud& c, const int64_t* out_offsets, const int64_t* kept, const int32_t* labels, int32_t* out_labels,
+                              hipStream_t st) {
+    const dim3 by_row((unsigned)((c.max_per_sample + VOX_KT - 1) / VOX_KT), c.batch);
+    hipLaunchKernelGGL(cloud_kept_labels, by_row, dim3(VOX_KT), 0, st, c, out_offsets, kept, labels, out_labels);
 }
 
 }  // namespace rald

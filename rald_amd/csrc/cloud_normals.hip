@@ -139,40 +139,32 @@ __device__ __forceinline__ int64_t nc_span(const int64_t* off, int f, int64_t bo
     return len > 0 ? len : 0;
 }
 
-__global__ __launch_bounds__(KNN_SEG) void nc_block_sums(NcArgs a) {
+__global__ __launch_bounds__(CLOUD_SEG) void nc_block_sums(NcArgs a) {
 #pragma clang fp contract(off)
-    __shared__ double v[KNN_SEG];
-    __shared__ int sh[KNN_SEG / 64];
+    __shared__ double v[CLOUD_SEG];
+    __shared__ int sh[CLOUD_SEG / 64];
     const int f = blockIdx.y, tid = threadIdx.x;
     int64_t a0, b0;
     const int64_t na = nc_span(a.a_off, f, a.max_a, a.ta, a0), nb = nc_span(a.b_off, f, a.max_b, a.tb, b0);
-    const int64_t j = (int64_t)blockIdx.x * KNN_SEG + tid;
-    if ((int64_t)blockIdx.x * KNN_SEG >= na) return;         // the whole workgroup
+    const int64_t j = (int64_t)blockIdx.x * CLOUD_SEG + tid;
+    if ((int64_t)blockIdx.x * CLOUD_SEG >= na) return;       // the whole workgroup
     bool counts = false;
     double x = 0.0;                                          // a row that does not count, and the padding: +0.0
     if (j < na && nb > 0) {
-        int64_t r = a.idx[a0 + j];
-        r = r < 0 ? 0 : (r < nb ? r : nb - 1);
+        const int64_t r = rad_clamp(a.idx[a0 + j], nb);
         const float* p = a.na + (a0 + j) * 3;
         const float* q = a.nb + (b0 + r) * 3;
         const float px = p[0], py = p[1], pz = p[2], qx = q[0], qy = q[1], qz = q[2];
         counts = nc_usable(px, py, pz) && nc_usable(qx, qy, qz);
         if (counts) x = fabs(((double)px * (double)qx + (double)py * (double)qy) + (double)pz * (double)qz);
     }
-    v[tid] = x;
-    const unsigned long long bm = __ballot(counts);
-    if ((tid & 63) == 0) sh[tid >> 6] = __popcll(bm);
-    __syncthreads();
-    for (int h = KNN_SEG / 2; h >= 1; h >>= 1) {
-        if (tid < h) v[tid] += v[tid + h];
-        __syncthreads();
-    }
+    int total;
+    block_rank<CLOUD_SEG>(counts, sh, tid, &total);
+    const double sum = block_tree_sum<CLOUD_SEG>(x, v, tid);
     if (tid == 0) {
-        int s = 0;
-        for (int w = 0; w < KNN_SEG / 64; ++w) s += sh[w];
         const int64_t at = ((int64_t)a.dir * a.batch + f) * a.nseg_max + blockIdx.x;
-        a.bsum[at] = v[0];
-        a.bcnt[at] = s;
+        a.bsum[at] = sum;
+        a.bcnt[at] = total;
     }
 }
 
@@ -186,14 +178,10 @@ __global__ __launch_bounds__(64) void nc_cloud(NcArgs a, double* out_nc, int64_t
     double nc[2];
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
-        const int64_t nseg = (len[d] + KNN_SEG - 1) / KNN_SEG;     // <= nseg_max: len <= the side's bound
-        double s = 0.0;
-        int64_t cnt = 0;
-        for (int64_t gk = 0; gk < nseg; ++gk) {
-            const int64_t at = ((int64_t)d * a.batch + f) * a.nseg_max + gk;
-            s += a.bsum[at];
-            cnt += a.bcnt[at];
-        }
+        const int nseg = (int)((len[d] + CLOUD_SEG - 1) / CLOUD_SEG);   // <= nseg_max: len <= the side's bound < 2^31
+        const int64_t at = ((int64_t)d * a.batch + f) * a.nseg_max;
+        const double s = fold_blocks(a.bsum + at, nseg, 1);
+        const int cnt = fold_blocks(a.bcnt + at, nseg, 1);  // <= len
         nc[d] = cnt > 0 ? s / (double)cnt : (double)NAN;
         out_counts[f * 2 + d] = cnt;
         out_nc[f * 3 + d] = nc[d];
@@ -210,7 +198,7 @@ struct NcScratch { int64_t* idx; double* bsum; int* bcnt; char* nn; int64_t nn_b
 int64_t nc_layout(NcScratch& w, NcArgs& a, Carver& s, int B, int64_t tp, int64_t tg, int64_t max_pred, int64_t max_gt) {
     const int64_t w0 = cloud_nn_scratch_bytes(B, max_pred, max_gt, 0), w1 = cloud_nn_scratch_bytes(B, max_gt, max_pred, 0);
     if (w0 < 0 || w1 < 0) return -1;
-    a.nseg_max = ((max_pred > max_gt ? max_pred : max_gt) + KNN_SEG - 1) / KNN_SEG;
+    a.nseg_max = ((max_pred > max_gt ? max_pred : max_gt) + CLOUD_SEG - 1) / CLOUD_SEG;
     w.idx = s.take<int64_t>(tp > tg ? tp : tg);
     w.bsum = s.take<double>(2 * (int64_t)B * a.nseg_max);
     w.bcnt = s.take<int>(2 * (int64_t)B * a.nseg_max);
@@ -280,7 +268,7 @@ int normal_consistency_ragged(const float* pred, const float* pred_normals, cons
         a.ta = dir ? n_gt_total : n_pred_total; a.tb = dir ? n_pred_total : n_gt_total;
         if (a.max_a == 0 || a.ta == 0) continue;             // no row on this side: nc_cloud reads no block of it
         RALD_TRY(cloud_nn_ragged(dir ? gt : pred, a.a_off, dir ? pred : gt, a.b_off, B, a.max_a, a.max_b, 0, nullptr, w.idx, w.nn, w.nn_bytes, st));
-        hipLaunchKernelGGL(nc_block_sums, dim3((unsigned)((a.max_a + KNN_SEG - 1) / KNN_SEG), B), dim3(KNN_SEG), 0, st, a);
+        hipLaunchKernelGGL(nc_block_sums, dim3((unsigned)((a.max_a + CLOUD_SEG - 1) / CLOUD_SEG), B), dim3(CLOUD_SEG), 0, st, a);
     }
     a.a_off = pred_off; a.b_off = gt_off; a.max_a = max_pred; a.max_b = max_gt; a.ta = n_pred_total; a.tb = n_gt_total;
     hipLaunchKernelGGL(nc_cloud, dim3((B + 63) / 64), dim3(64), 0, st, a, out_nc, out_counts);

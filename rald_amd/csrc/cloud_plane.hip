@@ -60,7 +60,7 @@ struct PlaneArgs {
     double* bsum; int* bcnt;                                 // [batch][nseg_max][6], [batch][nseg_max]
     double* fit;                                             // [batch][8] the centroid, the plane, the count
     int32_t* labels; double* planes; int32_t* nplanes; int32_t* inliers; int32_t* bests;   // the outputs, or scratch
-    int64_t* kept; int32_t* out_labels;                      // the filter: the kept rows' indices and labels
+    int64_t* kept;                                           // the filter: the kept rows' indices
     BlockScan fs;
 };
 
@@ -193,34 +193,12 @@ __global__ __launch_bounds__(PLN_T) void pln_argmax(PlaneArgs a) {
         const int v = a.hyp[at * 2 + 1].w != 0.f ? a.score[at] : -1;
         if (v > bv) { bv = v; bc = h; }
     }
-    sv[tid] = bv; sc[tid] = bc;
-    __syncthreads();
-    for (int s = PLN_T / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            const int v = sv[tid + s], c = sc[tid + s];
-            if (c >= 0 && (v > sv[tid] || (v == sv[tid] && c < sc[tid]))) { sv[tid] = v; sc[tid] = c; }
-        }
-        __syncthreads();
-    }
+    block_argmax<PLN_T>(bv, bc, sv, sc, tid);
     if (tid == 0) {
         const bool found = sc[0] >= 0 && sv[0] >= a.min_inliers;
         a.best[b] = found ? sc[0] : -1;
         a.bscore[b] = found ? sv[0] : 0;
     }
-}
-
-// the fixed sum shape inside a block: a halving tree over the workgroup's 1024 values; every thread of the workgroup calls it
-__device__ __forceinline__ double pln_tree(double x, double* v, int tid) {
-#pragma clang fp contract(off)
-    v[tid] = x;
-    __syncthreads();
-    for (int h = CLOUD_SEG / 2; h >= 1; h >>= 1) {
-        if (tid < h) v[tid] += v[tid + h];
-        __syncthreads();
-    }
-    const double r = v[0];
-    __syncthreads();
-    return r;
 }
 
 __global__ __launch_bounds__(CLOUD_SEG) void pln_mark(PlaneArgs a, int stage) {
@@ -247,8 +225,9 @@ __global__ __launch_bounds__(CLOUD_SEG) void pln_mark(PlaneArgs a, int stage) {
         flag = on && pln_s2(A, P0, px, py, pz) <= A.w;
         if (on) a.inl[l0 + q] = flag;
         if (!a.refine) return;
-        const double sx = pln_tree(flag ? (double)px : 0.0, v, tid), sy = pln_tree(flag ? (double)py : 0.0, v, tid),
-                     sz = pln_tree(flag ? (double)pz : 0.0, v, tid);
+        const double sx = block_tree_sum<CLOUD_SEG>(flag ? (double)px : 0.0, v, tid),
+                     sy = block_tree_sum<CLOUD_SEG>(flag ? (double)py : 0.0, v, tid),
+                     sz = block_tree_sum<CLOUD_SEG>(flag ? (double)pz : 0.0, v, tid);
         if (tid == 0) { bs[0] = sx; bs[1] = sy; bs[2] = sz; }
     } else if (stage == 1) {
         flag = on && a.inl[l0 + q];
@@ -256,7 +235,7 @@ __global__ __launch_bounds__(CLOUD_SEG) void pln_mark(PlaneArgs a, int stage) {
         const double e[6] = {dx * dx, dx * dy, dx * dz, dy * dy, dy * dz, dz * dz};
         double s[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) s[k] = pln_tree(flag ? e[k] : 0.0, v, tid);
+        for (int k = 0; k < 6; ++k) s[k] = block_tree_sum<CLOUD_SEG>(flag ? e[k] : 0.0, v, tid);
         if (tid == 0) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) bs[k] = s[k];
@@ -313,17 +292,14 @@ __global__ __launch_bounds__(64) void pln_fit(PlaneArgs a, int stage) {
         pln_plane(a, f, nx / len, ny / len, nz / len);
         pln_commit(a, b, f, a.bscore[b], best);
     } else if (stage == 0) {
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        int cnt = 0;
-        for (int g = 0; g < nseg; ++g) { sx += bs[g * 6]; sy += bs[g * 6 + 1]; sz += bs[g * 6 + 2]; cnt += bc[g]; }
-        const double mm = (double)cnt;                       // >= min_inliers >= 3
-        f[0] = sx / mm; f[1] = sy / mm; f[2] = sz / mm; f[7] = mm;
-    } else if (stage == 1) {
-        double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int g = 0; g < nseg; ++g) {
+        const double mm = (double)fold_blocks(bc, nseg, 1);  // >= min_inliers >= 3
 #pragma unroll
-            for (int k = 0; k < 6; ++k) s[k] += bs[g * 6 + k];
-        }
+        for (int k = 0; k < 3; ++k) f[k] = fold_blocks(bs + k, nseg, 6) / mm;
+        f[7] = mm;
+    } else if (stage == 1) {
+        double s[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s[k] = fold_blocks(bs + k, nseg, 6);
         const double mm = f[7];
         double a00 = s[0] / mm, a01 = s[1] / mm, a02 = s[2] / mm, a11 = s[3] / mm, a12 = s[4] / mm, a22 = s[5] / mm;
         double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
@@ -339,9 +315,7 @@ __global__ __launch_bounds__(64) void pln_fit(PlaneArgs a, int stage) {
         const double len = __dsqrt_rn((v00 * v00 + v10 * v10) + v20 * v20);
         pln_plane(a, f, v00 / len, v10 / len, v20 / len);
     } else {
-        int cnt = 0;
-        for (int g = 0; g < nseg; ++g) cnt += bc[g];
-        pln_commit(a, b, f, cnt, best);
+        pln_commit(a, b, f, fold_blocks(bc, nseg, 1), best);
     }
 }
 
@@ -353,8 +327,7 @@ __global__ __launch_bounds__(PLN_T) void pln_label(PlaneArgs a) {
     const int m = pln_live(a, b, n, l0);
     const int64_t q = (int64_t)blockIdx.x * PLN_T + threadIdx.x;
     if (q >= m || !a.inl[l0 + q]) return;
-    const int64_t r = a.li[l0 + q];
-    const int64_t g = row0 + (r < 0 ? 0 : (r < n ? r : n - 1));
+    const int64_t g = row0 + rad_clamp(a.li[l0 + q], (int64_t)n);
     a.labels[g] = a.round;
     a.live[g] = 0;
 }
@@ -367,20 +340,6 @@ __global__ __launch_bounds__(PLN_T) void pln_keep(PlaneArgs a) {
     if (j >= n) return;
     const int label = a.labels[row0 + j];
     a.live[row0 + j] = a.keep_planes ? label >= 0 : label == -1;
-}
-
-// behind the filter's compaction: the label of every kept row, by the row index the compaction left
-__global__ __launch_bounds__(PLN_T) void pln_kept_labels(PlaneArgs a) {
-    const int b = blockIdx.y;
-    int64_t row0;
-    const int n = ragged_span(a.c, b, row0);
-    const int64_t j = (int64_t)blockIdx.x * PLN_T + threadIdx.x;
-    const int64_t o0 = a.fs.out_offsets[b];
-    if (j >= n || j >= a.fs.out_offsets[b + 1] - o0) return;
-    const int64_t vo = o0 + j;
-    if (vo < 0 || vo >= a.c.n_total) return;                 // cannot happen with offsets that do not overlap
-    const int64_t r = a.kept[vo];
-    a.out_labels[vo] = a.labels[row0 + (r < 0 ? 0 : (r < n ? r : n - 1))];
 }
 
 // the scratch, described once; a.c, a.H and a.K are set
@@ -492,13 +451,12 @@ int plane_filter_ragged(const RaggedCloud& c, float threshold, int num_hypothese
     RALD_TRY(pln_segment("plane_filter_ragged", a, c, threshold, num_hypotheses, max_planes, min_inliers, refine, seed, view3_host, nullptr,
                          out_planes, out_num_planes, nullptr, nullptr, scratch, scratch_bytes, st));
     a.keep_planes = keep_planes != 0;
-    a.out_labels = out_labels;
     if (out_index) a.kept = out_index;
     a.fs.out_offsets = out_offsets;
     const dim3 by_row((unsigned)((c.max_per_sample + PLN_T - 1) / PLN_T), c.batch);
     hipLaunchKernelGGL(pln_keep, by_row, dim3(PLN_T), 0, st, a);
     compact_rows_ragged(c, a.fs, a.live, 1, out_points, a.kept, st);
-    hipLaunchKernelGGL(pln_kept_labels, by_row, dim3(PLN_T), 0, st, a);
+    cloud_kept_labels_ragged(c, out_offsets, a.kept, a.labels, out_labels, st);
     RALD_HIP(hipGetLastError());
     return 0;
 }

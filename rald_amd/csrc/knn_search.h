@@ -11,7 +11,6 @@ namespace rald {
 namespace {
 
 constexpr int KNN_T = 128;                                   // sorted positions per workgroup of a search kernel
-constexpr int KNN_SEG = 1024;                                // rows per block of the fixed sum shape
 constexpr int KNN_AHEAD = 4;                                 // rows of a key interval whose loads are issued together
 constexpr int KNN_PASSES = 40;                               // boxes per lane: the own cell, <= 32 doublings, two boxes by the rule
 

@@ -5,7 +5,7 @@
 //   knn              slot s of row i holds the s-th candidate, -1 / +inf from `found` on
 //   m[i]             float64: sum over the slots in order of sqrt((double)d2) / found; +inf with found = 0, NaN outside
 //   filter           keep row i iff found >= 1 and m[i] <= thr = mu + std_ratio * sigma, mu and sigma over the rows with found >= 1,
-//                    their sums in one fixed shape: 1024-row blocks in row order, a halving tree inside a block, the blocks left to right
+//                    their sums in the fixed sum shape (cloud_index.h: block_tree_sum, fold_blocks)
 // The index is cloud_index_build's (cell key, row) order and its sorted copy of the rows (cloud_index.h).  Launches behind it, all on
 // one stream, none waits on another workgroup, no atomics:
 //   knn_search       (128 sorted positions, cloud)  knn_search_lane of knn_search.h (cloud_normals.hip ends the same search in its own
@@ -58,15 +58,15 @@ __global__ __launch_bounds__(KNN_T) void knn_search(KnnArgs a) {
 }
 
 // ---- the filter's statistics in the fixed sum shape, over row order
-__global__ __launch_bounds__(KNN_SEG) void knn_block_sums(KnnArgs a, int pass) {
+__global__ __launch_bounds__(CLOUD_SEG) void knn_block_sums(KnnArgs a, int pass) {
 #pragma clang fp contract(off)
-    __shared__ double v[KNN_SEG];
-    __shared__ int sh[KNN_SEG / 64];
+    __shared__ double v[CLOUD_SEG];
+    __shared__ int sh[CLOUD_SEG / 64];
     const int b = blockIdx.y, tid = threadIdx.x;
     int64_t row0;
     const int n = ragged_span(a.c, b, row0);
-    const int64_t j = (int64_t)blockIdx.x * KNN_SEG + tid;
-    if ((int64_t)blockIdx.x * KNN_SEG >= n) return;          // the whole workgroup
+    const int64_t j = (int64_t)blockIdx.x * CLOUD_SEG + tid;
+    if ((int64_t)blockIdx.x * CLOUD_SEG >= n) return;        // the whole workgroup
     const bool counts = j < n && a.found[row0 + j] >= 1;
     double x = 0.0;                                          // a row that does not count, and the padding: +0.0
     if (counts) {
@@ -76,19 +76,12 @@ __global__ __launch_bounds__(KNN_SEG) void knn_block_sums(KnnArgs a, int pass) {
             x = d * d;
         }
     }
-    v[tid] = x;
-    const unsigned long long bm = __ballot(counts);
-    if ((tid & 63) == 0) sh[tid >> 6] = __popcll(bm);
-    __syncthreads();
-    for (int h = KNN_SEG / 2; h >= 1; h >>= 1) {
-        if (tid < h) v[tid] += v[tid + h];
-        __syncthreads();
-    }
+    int total;
+    block_rank<CLOUD_SEG>(counts, sh, tid, &total);
+    const double sum = block_tree_sum<CLOUD_SEG>(x, v, tid);
     if (tid == 0) {
-        int s = 0;
-        for (int w = 0; w < KNN_SEG / 64; ++w) s += sh[w];
-        a.bsum[(int64_t)b * a.nseg_max + blockIdx.x] = v[0];
-        if (!pass) a.bcnt[(int64_t)b * a.nseg_max + blockIdx.x] = s;
+        a.bsum[(int64_t)b * a.nseg_max + blockIdx.x] = sum;
+        if (!pass) a.bcnt[(int64_t)b * a.nseg_max + blockIdx.x] = total;
     }
 }
 
@@ -98,13 +91,11 @@ __global__ __launch_bounds__(64) void knn_cloud_stats(KnnArgs a, int pass) {
     if (b >= a.c.batch) return;
     int64_t row0;
     const int n = ragged_span(a.c, b, row0);
-    const int nseg = (n + KNN_SEG - 1) / KNN_SEG;
+    const int nseg = (n + CLOUD_SEG - 1) / CLOUD_SEG;
     double* st = a.stats + b * 4;
-    double s = 0.0;
-    for (int gk = 0; gk < nseg; ++gk) s += a.bsum[(int64_t)b * a.nseg_max + gk];
+    const double s = fold_blocks(a.bsum + (int64_t)b * a.nseg_max, nseg, 1);
     if (!pass) {
-        int64_t nf = 0;
-        for (int gk = 0; gk < nseg; ++gk) nf += a.bcnt[(int64_t)b * a.nseg_max + gk];
+        const int nf = fold_blocks(a.bcnt + (int64_t)b * a.nseg_max, nseg, 1);   // <= n
         st[3] = (double)nf;
         st[0] = nf > 0 ? s / (double)nf : (double)NAN;
         return;
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(256) void knn_flags(KnnArgs a) {
 
 void stat_layout(KnnArgs& a, CloudIndex& ix, Carver& s, int64_t chunk) {
     knn_layout(a, ix, s, chunk);
-    a.nseg_max = (a.c.max_per_sample + KNN_SEG - 1) / KNN_SEG;
+    a.nseg_max = (a.c.max_per_sample + CLOUD_SEG - 1) / CLOUD_SEG;
     a.mean = s.take<double>(a.c.n_total);
     a.found = s.take<int32_t>(a.c.n_total);
     block_scan_layout(a.sc, a.c, s);
@@ -189,7 +180,7 @@ int statistical_filter_ragged(const RaggedCloud& c, const GridSpec& grid, int k,
                      statistical_scratch_bytes(c.batch, c.n_total, c.max_per_sample, chunk), out_mean, scratch, scratch_bytes, chunk, st));
     const dim3 by_seg((unsigned)a.nseg_max, c.batch);
     for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(knn_block_sums, by_seg, dim3(KNN_SEG), 0, st, a, pass);
+        hipLaunchKernelGGL(knn_block_sums, by_seg, dim3(CLOUD_SEG), 0, st, a, pass);
         hipLaunchKernelGGL(knn_cloud_stats, dim3((c.batch + 63) / 64), dim3(64), 0, st, a, pass);
     }
     hipLaunchKernelGGL(knn_flags, dim3((unsigned)((c.max_per_sample + 255) / 256), c.batch), dim3(256), 0, st, a);

@@ -258,6 +258,39 @@ def test_capped_count_equals_the_radius_count():
         assert np.array_equal(rad, ref) and np.array_equal(clu, ref) and np.array_equal(rad, clu)
 
 
+# ---- 7. the largest cluster: ties past the argmax's 256 threads ------------------------------------------------------------------------------
+def _pairs_cloud(triples):
+    """300 groups of rows, group i at x = i, its rows 2^-6 apart: pairs, and triples for the groups named.  Group i is cluster i: the
+    clusters are numbered by their smallest row, and the groups stand in row order."""
+    step = F32(2.0 ** -6)
+    rows = []
+    for i in range(300):
+        rows += [(i, 0, 0), (i + step, 0, 0)] + ([(i, step, 0)] if i in triples else [])
+    return np.array(rows, F32)
+
+
+@gpu
+def test_largest_cluster_ties_beyond_one_stride_of_the_argmax():
+    """clu_argmax gives thread t the clusters t, t + 256, ..: cluster 260 is thread 4's second.  All 300 clusters of size 2: cluster 0
+    (every comparison of block_argmax's tree is a tie).  Cluster 260 alone of size 3: it wins from the second stride.  Clusters 4 and
+    260 of size 3: thread 4 must keep the earlier one.  The properties are asserted of the reference first, then kept rows, index and
+    labels are compared with it by equality."""
+    from rald_amd.postprocess import voxel_grid
+    eps = 2.0 ** -4
+    grid = voxel_grid((-1, -1, -1), (301, 1, 1), eps)
+    for triples, winner, first_row in (((), 0, 0), ((260,), 260, 520), ((4, 260), 4, 8)):
+        p = _pairs_cloud(triples)
+        n, size = len(p), 3 if triples else 2
+        assert n == 600 + len(triples)
+        ref = REF.cluster_ragged(p, [0, n], grid, eps, 1, n)
+        sizes = ref["sizes"][:300].tolist()
+        assert ref["num_clusters"].tolist() == [300] and sizes == [3 if i in triples else 2 for i in range(300)]
+        assert ref["labels"][first_row] == winner and (ref["labels"][first_row:first_row + size] == winner).all()
+        want = REF.filter_ragged(p, [0, n], grid, eps, 1, 1, n, largest_only=True, labelled=ref)
+        assert want["index"].tolist() == list(range(first_row, first_row + size)) and want["labels"].tolist() == [winner] * size
+        _check_filter(_routes(p, [0, n], grid, eps, 1, n, keep=(1, 1)), want, 1)
+
+
 # ---- the Python layer ------------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_python_layer():

@@ -167,7 +167,9 @@ def test_few_and_bad_rows():
 @gpu
 @pytest.mark.parametrize("n", (1023, 1024, 1025, 2049))
 def test_sum_shape_boundaries(n):
-    """Source lengths around the block of 1024 of the fixed sum shape, against a target that needs three sort chunks of 1024."""
+    """Source lengths around CLOUD_SEG = 1024, the block of the fixed sum shape, against a target that needs three sort chunks of 1024.
+    icp_sums and icp_solve are the hand-scheduled instance of that shape (two tree levels in registers, sixteen block sums in flight);
+    every other user calls block_tree_sum and fold_blocks of cloud_index.h.  This test pins the hand-scheduled one to the same bits."""
     _case(f"length_{n}", chunk=1024)
     _case(f"length_{n}")
 

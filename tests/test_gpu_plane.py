@@ -145,6 +145,34 @@ def test_tie():
     assert ref["inliers"].tolist() == [[300]] and ref["best"].tolist() == [[0]]
 
 
+def _late_tie_cloud(seed=45):
+    """40 distinct sites of the lattice (0 .. 31)^2 * 2^-3 in z = 0 and 300 rows uniform in [0, 4]^3 with z >= 0.5, in random order:
+    only a hypothesis drawn wholly inside the plane scores 40, about 2048 (40 / 340)^3 = 3 of 2048."""
+    rs = np.random.RandomState(seed)
+    sites = rs.choice(32 * 32, 40, replace=False)
+    plane = np.stack([sites // 32, sites % 32, np.zeros(40)], 1).astype(F32) * F32(0.125)
+    rest = rs.uniform(0.0, 4.0, size=(300, 3))
+    rest[:, 2] = rs.uniform(0.5, 4.0, size=300)
+    p = np.concatenate([plane, rest.astype(F32)]).astype(F32)
+    return p[rs.permutation(len(p))]
+
+
+@gpu
+def test_tie_with_the_winner_beyond_the_first_stride_of_the_argmax():
+    """pln_argmax gives thread t the hypotheses t, t + 256, ..  With seed 0 the reference's scores tie at 40 in the hypotheses 650, 1486
+    and 1566: the winner is thread 138's third, and the tie 1566 stands at thread 30, which the tree of block_argmax meets first.
+    Both properties are asserted of the reference, then labels, planes (by bits), inliers and best are compared with it."""
+    p = _late_tie_cloud()
+    kw = dict(t=REF.T_SLAB, H=2048, K=1, min_inliers=30, refine=False, seed=0)
+    score = REF.scores_of(p, REF.hypotheses(p, 0, kw["H"], kw["seed"], kw["t"]))          # every row is usable: the live rows are p
+    tied = np.nonzero(score == score.max())[0]
+    ref = REF.segment_ragged(p, [0, len(p)], max_per_sample=len(p), **kw)
+    assert score.max() == 40 and ref["best"].tolist() == [[int(tied[0])]] and ref["inliers"].tolist() == [[40]]
+    assert tied[0] >= 256 and len(tied) >= 2 and (tied[1:] % 256 < tied[0] % 256).any()
+    assert (ref["labels"] == np.where(p[:, 2] == 0, 0, -1)).all()
+    _check_segment(_run(p, [0, len(p)], len(p), **kw), ref)
+
+
 @gpu
 @pytest.mark.parametrize("order", ("built", "reversed", "shuffled"))
 def test_faces(order):
