@@ -663,18 +663,28 @@ def op_ae_enc_qproj(xin: Optional[torch.Tensor], X0: torch.Tensor, x: torch.Tens
                                      rows, M, dim, _stream()))
 
 
+def _decode_tables(x, gamma, beta, t2aug, l_img, basis, queries=None):
+    """the checks and conversions op_ae_decode, op_ae_decode_grad and op_ae_cast_rays share -> (x, gamma, beta, t2aug, basis) contiguous
+    fp32 and (B, M, dim); `queries`, when given, is held to the device with the tables (before any shape is looked at)"""
+    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis"), (queries, "queries")):
+        if t is not None:
+            _need_cuda(t, what)
+    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
+    x, gamma, beta, t2aug, basis = (_f32c(t) for t in (x, gamma, beta, t2aug, basis))
+    B, M, dim = x.shape
+    assert t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim and basis.shape == (3, 24)
+    return x, gamma, beta, t2aug, basis, (B, M, dim)
+
+
 def op_ae_decode(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2aug: torch.Tensor, l_img: torch.Tensor, basis: torch.Tensor,
                  c0: float, queries: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The streaming query decoder on caller-made tables (rald_amd/csrc/ae_decode.hip): x fp32 [B,M,dim] (output of the latent stack),
     gamma / beta [dim] (norm_context), t2aug fp32 [dim,64] and l_img [64*64] fp16 (or its bits as int16) as rald_op_ae_decode_tables writes
     them, basis [3,24], queries fp32 [B,Q,3] -> logits fp32 [B,Q], written to `out` (B*Q contiguous floats) when it is given."""
-    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis"), (queries, "queries")):
-        _need_cuda(t, what)
-    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
-    x, gamma, beta, t2aug, basis, queries = (_f32c(t) for t in (x, gamma, beta, t2aug, basis, queries))
-    (B, M, dim), Q = x.shape, queries.shape[1]
-    assert queries.shape[0] == B and queries.shape[2] == 3 and t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim
-    assert basis.shape == (3, 24)
+    x, gamma, beta, t2aug, basis, (B, M, dim) = _decode_tables(x, gamma, beta, t2aug, l_img, basis, queries)
+    queries = _f32c(queries)
+    Q = queries.shape[1]
+    assert queries.shape[0] == B and queries.shape[2] == 3
     if out is None:
         out = torch.empty(B, Q, device=x.device, dtype=torch.float32)
     assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() == B * Q
@@ -691,12 +701,9 @@ def op_ae_decode_grad(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, 
     """The gradient decoder on caller-made tables (rald_op_ae_decode_grad; arguments as op_ae_decode): queries [B,Q,3], or with
     `offsets` (int64 [B+1] on the device) [T,3] concatenated and max_per_sample the host bound of the longest segment.  Writes the
     caller's buffers: out (one float per query), grad and, when given, projected (three per query)."""
-    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis"), (queries, "queries")):
-        _need_cuda(t, what)
-    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
-    x, gamma, beta, t2aug, basis, queries = (_f32c(t) for t in (x, gamma, beta, t2aug, basis, queries))
-    B, M, dim = x.shape
-    assert queries.shape[-1] == 3 and t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim and basis.shape == (3, 24)
+    x, gamma, beta, t2aug, basis, (B, M, dim) = _decode_tables(x, gamma, beta, t2aug, l_img, basis, queries)
+    queries = _f32c(queries)
+    assert queries.shape[-1] == 3
     if offsets is None:
         assert queries.dim() == 3 and queries.shape[0] == B
         n, total = queries.shape[1], B * queries.shape[1]
@@ -742,12 +749,7 @@ def op_ae_cast_rays(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, t2
     holding [R,3] (ray_batch_stride 0) or [B,R,3] (3 * R) in the caller's buffers, out_t / out_logit fp32 and out_step int32 of B * R
     elements, out_points None or fp32 of 3 * B * R; n_rays = R (default: out_step's elements / B).  What the entry checks is not checked
     here (any pointer may be None): -> its status (0 = done), the message in rald_last_error."""
-    for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (t2aug, "t2aug"), (l_img, "l_img"), (basis, "basis")):
-        _need_cuda(t, what)
-    assert l_img.dtype in (torch.float16, torch.int16) and l_img.numel() == 64 * 64 and l_img.is_contiguous()
-    x, gamma, beta, t2aug, basis = (_f32c(t) for t in (x, gamma, beta, t2aug, basis))
-    B, M, dim = x.shape
-    assert t2aug.shape == (dim, 64) and gamma.numel() == dim and beta.numel() == dim and basis.shape == (3, 24)
+    x, gamma, beta, t2aug, basis, (B, M, dim) = _decode_tables(x, gamma, beta, t2aug, l_img, basis)
     R = int(n_rays) if n_rays is not None else out_step.numel() // B
     for t, dt, k in ((origins, torch.float32, None), (dirs, torch.float32, None), (out_t, torch.float32, 1), (out_logit, torch.float32, 1),
                      (out_step, torch.int32, 1), (out_points, torch.float32, 3)):
@@ -809,9 +811,7 @@ class AeHandle(_Handle):
         _need_cuda(queries, "queries")
         queries = _f32c(queries)
         B, Q, _ = queries.shape
-        if ctx.dtype != torch.uint8 or not ctx.is_cuda or ctx.numel() != lib().rald_ae_ctx_bytes(self._h, B):
-            raise RuntimeError(f"decoder context of {ctx.numel()} bytes does not belong to a batch of {B}: decode_latents(z) and the queries "
-                               "must have the same batch size")
+        self._check_ctx(ctx, B, "queries")
         out = torch.empty(B, Q, device=queries.device, dtype=torch.float32)
         check(lib().rald_ae_decode_queries(self._h, ctx.data_ptr(), queries.data_ptr(), B, Q, out.data_ptr(), _stream()))
         return out
@@ -822,9 +822,7 @@ class AeHandle(_Handle):
         _need_cuda(queries, "queries")
         queries = _f32c(queries).reshape(-1, 3)
         B = _ragged_batch(offsets, "offsets")
-        if ctx.dtype != torch.uint8 or not ctx.is_cuda or ctx.numel() != lib().rald_ae_ctx_bytes(self._h, B):
-            raise RuntimeError(f"decoder context of {ctx.numel()} bytes does not belong to a batch of {B}: decode_latents(z) and the offsets "
-                               "must have the same batch size")
+        self._check_ctx(ctx, B, "offsets")
         out = torch.empty(queries.shape[0], device=queries.device, dtype=torch.float32)
         check(lib().rald_ae_decode_queries_ragged(self._h, ctx.data_ptr(), queries.data_ptr(), offsets.data_ptr(), B, int(max_per_sample),
                                                   out.data_ptr(), _stream()))

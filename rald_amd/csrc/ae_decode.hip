@@ -40,14 +40,11 @@
 #include <cmath>
 #include <vector>
 
+#include "ae_decode_core.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace rald {
-
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 // slot of reference feature f (0..23 sin, 24..47 cos, 48..50 xyz), see the header
 static inline int slot_of_feature(int f) {
@@ -55,12 +52,6 @@ static inline int slot_of_feature(int f) {
     if (f < 48) { const int e = f - 24; return 16 * (e >> 3) + 8 + (e & 7); }
     return 48 + (f - 48);
 }
-constexpr int SLOT_ONE = 51;      // (s=3, h=0, j=3): 1.0 -> h0_hi ; j=4 (slot 52): 1.0 -> h0_lo
-constexpr int SLOT_STD = 53;      // j=5,6,7 (slots 53,54,55): std_hi, std_lo, std_hi -> hb_hi, hb_hi, hb_lo
-constexpr int SLOT_U = 63;        // column of the projection that carries u (its feature slot is always zero)
-
-// byte offset of element (row, k) in a [rows][64] fp16 image with 128-byte rows, 16-byte chunks XOR-swizzled by the row
-__host__ __device__ static inline int img_off(int row, int k) { return row * 128 + (((k >> 3) ^ (row & 7)) << 4) + (k & 7) * 2; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // host: weight-only tables (double precision)
@@ -242,11 +233,7 @@ struct DecodeArgs {
 template <bool DIAG, int NW, bool RAGGED>
 __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a, const int64_t* __restrict__ offsets) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int M = a.M;
-    unsigned char* s_h = smem;                                   // M * 128
-    unsigned char* s_l = smem + (size_t)M * 128;                 // 8192
-    float* s_u = reinterpret_cast<float*>(s_l + 8192);           // M + 4
-    float* s_basis = s_u + M + 4;                                // 72 (+ pad)
+    const DecoderLds c = decoder_lds(smem, a.M);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -259,157 +246,45 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_stream_kernel(DecodeArgs a,
         // loads the context; a descending or negative pair of offsets decodes nothing
         if (first < 0 || seg <= 0 || (int64_t)blockIdx.x * NW * 64 >= seg) return;
     }
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(a.ctx + (int64_t)b * a.ctx_stride);
-        uint4* dst = reinterpret_cast<uint4*>(s_h);
-        const int n16 = M * 8;                                   // image
-        for (int i = tid; i < n16; i += NW * 64) dst[i] = src[i];
-        const uint4* su = src + n16;                             // u | inv_scale
-        uint4* du = reinterpret_cast<uint4*>(s_u);
-        for (int i = tid; i < M / 4 + 1; i += NW * 64) du[i] = su[i];
-        const uint4* sl = reinterpret_cast<const uint4*>(a.l_img);
-        uint4* dl = reinterpret_cast<uint4*>(s_l);
-        for (int i = tid; i < 512; i += NW * 64) dl[i] = sl[i];
-        if (tid < 72) s_basis[tid] = a.basis[tid] * 0.15915494309189535f;      // radians -> revolutions (v_sin_f32 takes revolutions)
-    }
+    stage_context<NW * 64>(c, a.ctx + (int64_t)b * a.ctx_stride, a.l_img, a.basis, tid);
     __syncthreads();
-    const float inv_scale = s_u[M];
+    const float inv_scale = c.u[c.M];
     const int r = lane & 31, h = lane >> 5;
+    const DecoderLane ln = {r, h, h ? 0.25f : 0.0f};
     const int64_t Q = RAGGED ? seg : a.Q;
     const float* qin = a.queries + (RAGGED ? first : (int64_t)b * a.Q) * 3;
     float* qout = a.out + (RAGGED ? first : (int64_t)b * a.Q);
     const int64_t nchunks = (Q + 63) / 64;
-    const float quarter = h ? 0.25f : 0.0f;                       // cos(t) = sin(t + 1/4 revolution)
 
     for (int64_t chunk = (int64_t)blockIdx.x * NW + wave; chunk < nchunks; chunk += (int64_t)gridDim.x * NW) {
-        f16x8 bq[2][4];
-        float rq[2];                                              // rstd_q / scale
+        float pt[2][3];
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             int64_t q = chunk * 64 + qb * 32 + r;
             q = q < Q ? q : Q - 1;
-            const float x = qin[q * 3 + 0], y = qin[q * 3 + 1], z = qin[q * 3 + 2];
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                f16x8 f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int e = 8 * s + j;
-                    float p;
-                    if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
-                    else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
-                    p += quarter;
-                    p = __builtin_amdgcn_fractf(p);
-                    f[j] = (f16)__builtin_amdgcn_sinf(p);
-                }
-                bq[qb][s] = f;
-            }
-            f16x8 f;
-            f[0] = (f16)(h ? 0.f : x); f[1] = (f16)(h ? 0.f : y); f[2] = (f16)(h ? 0.f : z);
-            f[3] = (f16)(h ? 0.f : 1.f); f[4] = f[3];
-            f[5] = (f16)0.f; f[6] = (f16)0.f; f[7] = (f16)0.f;
-            bq[qb][3] = f;
+            pt[qb][0] = qin[q * 3 + 0]; pt[qb][1] = qin[q * 3 + 1]; pt[qb][2] = qin[q * 3 + 2];
         }
-        // ---- LayerNorm statistics of the query embedding: var_q = |L.f~|^2 (two 32-row tiles x 4 k-steps)
+        float dsum[2], nsum[2];
+        chunk_sums<DIAG>(c, ln, pt, a.eps, inv_scale, dsum, nsum);
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
-            float ss = 0.f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                f32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-                const int row = 32 * t + r;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const f16x8 la = *reinterpret_cast<const f16x8*>(s_l + row * 128 + (((2 * s + h) ^ (row & 7)) << 4));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(la, bq[qb][s], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int i = 0; i < 16; ++i) ss = fmaf(acc[i], acc[i], ss);
-            }
-            ss += __shfl_xor(ss, 32, 64);
-            const float var = ss + a.eps;
-            const float rstd = rsqrtf(var);
-            const float sd = var * rstd;                           // sqrt(var + eps)
-            const f16 sd_hi = (f16)sd;
-            const f16 sd_lo = (f16)(sd - (float)sd_hi);
-            f16x8 f = bq[qb][3];
-            f[5] = h ? (f16)0.f : sd_hi; f[6] = h ? (f16)0.f : sd_lo; f[7] = h ? (f16)0.f : sd_hi;
-            bq[qb][3] = f;
-            rq[qb] = rstd * inv_scale;
-        }
-        // ---- scores + online softmax over the latents
-        float m[2] = {-INFINITY, -INFINITY}, den[2] = {0.f, 0.f}, num[2] = {0.f, 0.f};
-        const int ntile = M >> 5;
-        for (int t = 0; t < ntile; ++t) {
-            const int row = 32 * t + r;
-            f16x8 fa[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(s_h + row * 128 + (((2 * s + h) ^ (row & 7)) << 4));
-            float4 uv[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) uv[g] = *reinterpret_cast<const float4*>(s_u + 32 * t + 8 * g + 4 * h);
-#pragma unroll
-            for (int qb = 0; qb < 2; ++qb) {
-                f32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bq[qb][s], acc, 0, 0, 0);
-                float tm = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-#pragma unroll
-                for (int i = 4; i < 16; i += 4) tm = fmaxf(tm, fmaxf(fmaxf(acc[i], acc[i + 1]), fmaxf(acc[i + 2], acc[i + 3])));
-                const float vm = tm * rq[qb];
-                if (__any(vm > m[qb] + 8.0f)) {                    // lazy running maximum: p stays <= 2^8
-                    const float mn = fmaxf(m[qb], vm);
-                    const float alpha = __builtin_amdgcn_exp2f(m[qb] - mn);
-                    den[qb] *= alpha; num[qb] *= alpha;
-                    m[qb] = mn;
-                }
-                const float nm = -m[qb];
-                float d0 = 0.f, d1 = 0.f, n0 = 0.f, n1 = 0.f;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float p0 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 0], rq[qb], nm));
-                    const float p1 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 1], rq[qb], nm));
-                    const float p2 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 2], rq[qb], nm));
-                    const float p3 = __builtin_amdgcn_exp2f(fmaf(acc[4 * g + 3], rq[qb], nm));
-                    d0 += p0; d1 += p1; d0 += p2; d1 += p3;
-                    n0 = fmaf(p0, uv[g].x, n0); n1 = fmaf(p1, uv[g].y, n1); n0 = fmaf(p2, uv[g].z, n0); n1 = fmaf(p3, uv[g].w, n1);
-                }
-                den[qb] += d0 + d1;
-                num[qb] += n0 + n1;
-            }
-        }
-        // ---- merge the two lane halves of each query and store
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            const float mo = __shfl_xor(m[qb], 32, 64), dn = __shfl_xor(den[qb], 32, 64), nn = __shfl_xor(num[qb], 32, 64);
-            const float mm = fmaxf(m[qb], mo);
-            const float wa = __builtin_amdgcn_exp2f(m[qb] - mm), wb = __builtin_amdgcn_exp2f(mo - mm);
-            const float dsum = den[qb] * wa + dn * wb, nsum = num[qb] * wa + nn * wb;
             const int64_t q = chunk * 64 + qb * 32 + r;
-            if (h == 0 && q < Q) qout[q] = nsum / dsum + a.c0;
+            if (h == 0 && q < Q) qout[q] = nsum[qb] / dsum[qb] + a.c0;
         }
     }
 }
 
 // longest = the queries of one sample (dense) or a host upper bound of the longest segment (ragged): it sizes the grid
 template <bool DIAG, bool RAGGED>
-static int launch_decode(const DecodeArgs& a, const int64_t* offsets, int B, int64_t longest, size_t smem, hipStream_t st) {
+static int launch_decode(const DecodeArgs& a, const int64_t* offsets, int B, int64_t longest, hipStream_t st) {
     constexpr int NW = 12;                                         // waves per workgroup (the measured best of 8, 12 and 16)
     auto kern = ae_decode_stream_kernel<DIAG, NW, RAGGED>;
     static bool attr_set = false;
     if (!attr_set) {
-        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 * 128 + 8192 + (1024 + 4 + 76) * 4));
+        RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)decoder_smem_bytes(DECODER_MAX_LATENTS)));
         attr_set = true;
     }
-    const int64_t nchunks = (longest + 63) / 64;
-    int64_t per_sample = (nchunks + NW - 1) / NW;                  // workgroups that have at least one chunk per wave
-    const int64_t cap = B >= 256 ? 1 : 256 / B;                    // about one workgroup per CU over the whole batch
-    if (per_sample > cap) per_sample = cap;
-    hipLaunchKernelGGL(kern, dim3((unsigned)per_sample, (unsigned)B), dim3(NW * 64), smem, st, a, offsets);
+    hipLaunchKernelGGL(kern, dim3(decoder_grid_x(longest, NW, B), (unsigned)B), dim3(NW * 64), decoder_smem_bytes(a.M), st, a, offsets);
     RALD_HIP(hipGetLastError());
     return 0;
 }
@@ -422,8 +297,7 @@ int ae_decode_stream(const void* ctx, const unsigned short* l_img, const float* 
     DecodeArgs a;
     a.ctx = (const unsigned char*)ctx; a.ctx_stride = ae_ctx_stride(M); a.l_img = l_img; a.queries = queries; a.out = out; a.basis = basis;
     a.Q = Q; a.M = M; a.c0 = c0; a.eps = 1e-5f;
-    const size_t smem = (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76) * 4;
-    return basis_diag ? launch_decode<true, false>(a, nullptr, B, Q, smem, st) : launch_decode<false, false>(a, nullptr, B, Q, smem, st);
+    return basis_diag ? launch_decode<true, false>(a, nullptr, B, Q, st) : launch_decode<false, false>(a, nullptr, B, Q, st);
 }
 
 // the same decoder on ragged query sets: queries [T][3] / out [T] concatenated over the samples, offsets [B + 1] on the device (sample b owns
@@ -440,8 +314,7 @@ int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const 
     DecodeArgs a;
     a.ctx = (const unsigned char*)ctx; a.ctx_stride = ae_ctx_stride(M); a.l_img = l_img; a.queries = queries; a.out = out; a.basis = basis;
     a.Q = 0; a.M = M; a.c0 = c0; a.eps = 1e-5f;
-    const size_t smem = (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76) * 4;
-    return basis_diag ? launch_decode<true, true>(a, offsets, B, max_per_sample, smem, st) : launch_decode<false, true>(a, offsets, B, max_per_sample, smem, st);
+    return basis_diag ? launch_decode<true, true>(a, offsets, B, max_per_sample, st) : launch_decode<false, true>(a, offsets, B, max_per_sample, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -452,8 +325,11 @@ int ae_decode_stream_ragged(const void* ctx, const unsigned short* l_img, const 
 //
 //     grad = ln2 [ rstd D^T G  -  rstd^3 (sum_l a_l A_l) D~^T L^T L f~ ],      G = sum_l a_l H_l
 //
-// Two passes over the score tiles per 64-query chunk.  Pass 1 is ae_decode_stream_kernel's own statement sequence (same features, same
-// variance, same lazily rescaled softmax, same merge of the lane halves): the logit is that kernel's, bit for bit, for the same segment.
+// Two passes over the score tiles per 64-query chunk.  Pass 1 is ae_decode_stream_kernel's statement sequence on one 32-query
+// half (same features, same variance, same lazily rescaled softmax), written out here: staging, the feature phase and the merge of the
+// lane halves are the same functions that kernel calls (ae_decode_core.h), but as calls to its feature, variance and score stages, or
+// to the score tile alone, pass 1 and pass 2 cost this kernel registers.  The logit is that kernel's, bit for bit,
+// for the same segment (tested, and recorded in tests/golden/g2x_decode_bits.npz).
 // Pass 2 recomputes each score tile, forms a_l from the final maximum, denominator and ubar, and feeds it - the latents sit on the
 // accumulator registers, the queries on the lanes, which is the MFMA B-operand layout up to a fixed order of the contraction index -
 // into a second product G^T[k,q] += H~^T[k,l] a[l,q].  Its A operand is a transposed copy of the image, built once per workgroup in
@@ -497,17 +373,16 @@ __device__ __forceinline__ void newton_step(float x, float y, float z, float log
 
 constexpr int GRAD_NW = 8;
 __host__ __device__ static inline int ht_row_bytes(int M) { return 2 * M + 16; }
-static inline size_t grad_smem_bytes(int M) { return (size_t)M * 128 + 8192 + (size_t)(M + 4 + 76 + 76) * 4 + (size_t)64 * ht_row_bytes(M); }
+static inline size_t grad_smem_bytes(int M) { return decoder_smem_bytes(M) + 76 * 4 + (size_t)64 * ht_row_bytes(M); }
 
 template <bool DIAG, int NW, bool RAGGED>
 __global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGradArgs ga, const int64_t* __restrict__ offsets) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const DecodeArgs& a = ga.d;
     const int M = a.M;
-    unsigned char* s_h = smem;                                   // M * 128
-    unsigned char* s_l = smem + (size_t)M * 128;                 // 8192
-    float* s_u = reinterpret_cast<float*>(s_l + 8192);           // M + 4
-    float* s_basis = s_u + M + 4;                                // 72 (+ pad): revolutions
+    const DecoderLds lds = decoder_lds(smem, M);                 // the plain layout, then what this kernel adds
+    unsigned char *s_h = lds.h, *s_l = lds.l;
+    float *s_u = lds.u, *s_basis = lds.basis;                    // basis in revolutions
     float* s_brad = s_basis + 76;                                // 72 (+ pad): radians, the factor of D
     unsigned char* s_ht = reinterpret_cast<unsigned char*>(s_brad + 76);     // 64 rows of 2M + 16 bytes
     const int RS = ht_row_bytes(M);
@@ -521,23 +396,7 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGr
         seg = offsets[b + 1] - first;
         if (first < 0 || seg <= 0 || (int64_t)blockIdx.x * NW * 64 >= seg) return;
     }
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(a.ctx + (int64_t)b * a.ctx_stride);
-        uint4* dst = reinterpret_cast<uint4*>(s_h);
-        const int n16 = M * 8;                                   // image
-        for (int i = tid; i < n16; i += NW * 64) dst[i] = src[i];
-        const uint4* su = src + n16;                             // u | inv_scale
-        uint4* du = reinterpret_cast<uint4*>(s_u);
-        for (int i = tid; i < M / 4 + 1; i += NW * 64) du[i] = su[i];
-        const uint4* sl = reinterpret_cast<const uint4*>(a.l_img);
-        uint4* dl = reinterpret_cast<uint4*>(s_l);
-        for (int i = tid; i < 512; i += NW * 64) dl[i] = sl[i];
-        if (tid < 72) {
-            const float bv = a.basis[tid];
-            s_basis[tid] = bv * 0.15915494309189535f;            // radians -> revolutions (v_sin_f32 takes revolutions)
-            s_brad[tid] = bv;
-        }
-    }
+    stage_context<NW * 64>(lds, a.ctx + (int64_t)b * a.ctx_stride, a.l_img, a.basis, tid, s_brad);
     __syncthreads();
     {
         // transposed image in the second product's contraction order (see above)
@@ -593,9 +452,7 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGr
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int e = 8 * s + j;
-                    float p;
-                    if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
-                    else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
+                    float p = feature_phase<DIAG>(s_basis, s, e, x, y, z);
                     p += quarter;
                     p = __builtin_amdgcn_fractf(p);
                     f[j] = (f16)__builtin_amdgcn_sinf(p);
@@ -641,9 +498,7 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGr
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const int e = 8 * s + j;
-                        float p;
-                        if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
-                        else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
+                        float p = feature_phase<DIAG>(s_basis, s, e, x, y, z);
                         p += quarter + 0.25f;
                         dq[s][j] = (f16)(__builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p)) * s_brad[24 * ax + e]);
                     }
@@ -720,10 +575,8 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGr
                 num += n0 + n1;
             }
             // ---- merge the two lane halves of the query; both halves go on with the h = 0 lane's numbers (the ones that are stored)
-            const float mo = __shfl_xor(m, 32, 64), dn = __shfl_xor(den, 32, 64), nn = __shfl_xor(num, 32, 64);
-            const float mm = fmaxf(m, mo);
-            const float wa = __builtin_amdgcn_exp2f(m - mm), wb = __builtin_amdgcn_exp2f(mo - mm);
-            const float dsum = den * wa + dn * wb, nsum = num * wa + nn * wb;
+            float mm, dsum, nsum;
+            merge_lane_halves(m, den, num, mm, dsum, nsum);
             const float logit = nsum / dsum + a.c0;
             const float ub = __shfl(nsum / dsum, r, 64);
             const float cs = a_scale / __shfl(dsum, r, 64);
@@ -777,9 +630,7 @@ __global__ __launch_bounds__(NW * 64) void ae_decode_grad_stream_kernel(DecodeGr
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     const int e = 8 * s + 4 * h + jj;
-                    float p;
-                    if (DIAG) p = (s == 0 ? x : (s == 1 ? y : z)) * s_basis[24 * s + e];
-                    else p = fmaf(z, s_basis[48 + e], fmaf(y, s_basis[24 + e], x * s_basis[e]));
+                    float p = feature_phase<DIAG>(s_basis, s, e, x, y, z);
                     const float sn = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p));
                     const float cn = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p + 0.25f));
                     const float Gs = G[s >> 1][8 * (s & 1) + jj], Gc = G[s >> 1][8 * (s & 1) + 4 + jj];
@@ -826,11 +677,7 @@ static int launch_decode_grad(const DecodeGradArgs& a, const int64_t* offsets, i
         RALD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_smem_bytes(AE_DECODE_GRAD_MAX_LATENTS)));
         attr_set = true;
     }
-    const int64_t nchunks = (longest + 63) / 64;
-    int64_t per_sample = (nchunks + NW - 1) / NW;                  // workgroups that have at least one chunk per wave
-    const int64_t cap = B >= 256 ? 1 : 256 / B;                    // about one workgroup per CU over the whole batch
-    if (per_sample > cap) per_sample = cap;
-    hipLaunchKernelGGL(kern, dim3((unsigned)per_sample, (unsigned)B), dim3(NW * 64), grad_smem_bytes(a.d.M), st, a, offsets);
+    hipLaunchKernelGGL(kern, dim3(decoder_grid_x(longest, NW, B), (unsigned)B), dim3(NW * 64), grad_smem_bytes(a.d.M), st, a, offsets);
     RALD_HIP(hipGetLastError());
     return 0;
 }
