@@ -1008,6 +1008,14 @@ int rald_op_conv3d_wgrad(const void* dy_bf16, const void* x_bf16, float* dW, flo
  * full resolution, whose atomics scatter over the parameter's tap-innermost layout. */
 int64_t rald_op_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2);
 int64_t rald_op_conv3d_wgrad_workspace_bytes(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad);
+/* Which kernel rald_op_conv3d_wgrad runs a shape on and how it cuts the voxels: the plan function of the launch itself (pure host arithmetic,
+ * no HIP call, works where no GPU is visible).  Returns 1 for the line-staged kernel (stride 1 / pad 1, or stride 2 / pad 0 on even dims; channel
+ * counts multiples of 64, output width a power of two in 4..64, whole 64-voxel steps) and 0 for the generic row-contracting kernel (narrow
+ * for Cout <= 64).  *ranges_out (nullable) = the voxel ranges that do work (one slab each in the workspace form); *per_range_out (nullable) =
+ * the 64-voxel steps of one range (line) or its rows (generic; for Cout > 64 the workspace form's - the atomic form cuts finer).
+ * -1 (and rald_last_error) for a shape rald_op_conv3d_wgrad refuses. */
+int rald_op_conv3d_wgrad_route(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad,
+                               int32_t* ranges_out, int32_t* per_range_out);
 /* conv_in (one input channel) weight gradient, first half: the 27-neighbourhood of channel 0 of cube [B][D][H][W][cube_ch] fp32 per voxel as one
  * bf16 row of 32 (taps kd*9 + kh*3 + kw, zero outside the volume, 5 zero pads); dW = rald_op_gemm_tn(dy, patches). */
 int rald_op_patches27(const float* cube, int32_t cube_ch, void* out_bf16, int32_t B, int32_t D, int32_t H, int32_t W, void* stream);

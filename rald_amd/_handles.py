@@ -482,6 +482,16 @@ def op_conv3d_route(B: int, ID: int, IH: int, IW: int, Cin: int, Cout: int, stri
     return CONV_ENGINES[e], splits.value
 
 
+def op_conv3d_wgrad_route(B: int, ID: int, IH: int, IW: int, Cin: int, Cout: int, stride: int = 1, pad: int = 1):
+    """(kernel "line" | "generic", voxel ranges that do work, 64-voxel steps (line) or rows (generic) per range) of a Conv3d weight gradient:
+    the plan op_conv3d_wgrad's launch itself uses (host arithmetic, needs no GPU)."""
+    ranges, per = C.c_int32(0), C.c_int32(0)
+    e = lib().rald_op_conv3d_wgrad_route(B, ID, IH, IW, Cin, Cout, stride, pad, C.addressof(ranges), C.addressof(per))
+    if e < 0:
+        check(1)
+    return ("generic", "line")[e], ranges.value, per.value
+
+
 def op_conv3d_full(x16: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, B: int, ID: int, IH: int, IW: int, Cin: int, Cout: int,
                    out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
                    gn_part: Optional[torch.Tensor] = None, split_ws: Optional[torch.Tensor] = None, allow_split: int = 0, stride: int = 1,

@@ -919,6 +919,15 @@ int64_t rald_op_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2) { ret
 int64_t rald_op_conv3d_wgrad_workspace_bytes(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad) {
     return 4 * conv3d_wgrad_workspace_floats(B, ID, IH, IW, Cin, Cout, stride, pad);
 }
+int rald_op_conv3d_wgrad_route(int32_t B, int32_t ID, int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t stride, int32_t pad, int32_t* ranges_out,
+                               int32_t* per_range_out) {
+    int ranges = 0, per_range = 0;
+    const int r = conv3d_wgrad_route(B, ID, IH, IW, Cin, Cout, stride, pad, &ranges, &per_range);
+    if (r < 0) set_error("rald_op_conv3d_wgrad_route: not a shape rald_op_conv3d_wgrad takes (Cin % 8, Cout % 8, stride 1|2, pad >= 0, < 2^31 output voxels)");
+    if (ranges_out) *ranges_out = ranges;
+    if (per_range_out) *per_range_out = per_range;
+    return r;
+}
 int rald_op_patches27(const float* cube, int32_t cube_ch, void* out_bf16, int32_t B, int32_t D, int32_t H, int32_t W, void* stream) {
     return patches27(cube, cube_ch, (bf16*)out_bf16, B, D, H, W, (hipStream_t)stream);
 }

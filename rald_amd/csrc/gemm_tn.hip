@@ -475,7 +475,7 @@ int gemm_tn(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, float* C, in
 // workgroup in 12 288 atomics whose 64 lanes hit 64 different cache lines (the parameter layout puts the 27 taps innermost), which at
 // 32 x 16 x 8 voxels was 93 % of the launch (928 -> 70 us without them).  null = the atomic form.
 namespace {
-struct WgradPlan { bool line; int splits, used, steps_per_split, nsteps, tiles, lw, lh, ld; };
+struct WgradPlan { bool line; int splits, used, steps_per_split, nsteps, tiles, lw, lh, ld, rows; };      // rows: per range of the generic kernel
 int lg2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
 WgradPlan wgrad_plan(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad) {
     WgradPlan p = {};
@@ -504,8 +504,7 @@ WgradPlan wgrad_plan(int B, int ID, int IH, int IW, int Cin, int Cout, int strid
         p.used = cdiv(p.nsteps, p.steps_per_split);
         p.splits = (int)round_up(p.used, 8);                     // (ranges past the last step return at once)
     } else {
-        int rows;
-        tn_ranges(B * OD * OH * OW, Cout, 27 * Cin, rows, p.used, p.splits, Cout > 64);
+        tn_ranges(B * OD * OH * OW, Cout, 27 * Cin, p.rows, p.used, p.splits, Cout > 64);
     }
     return p;
 }
@@ -519,9 +518,23 @@ int64_t conv3d_wgrad_workspace_floats(int B, int ID, int IH, int IW, int Cin, in
     return (int64_t)p.used * ((int64_t)Cout * 27 * Cin + Cout);
 }
 
+// What wgrad_plan answers for a shape conv3d_wgrad_tn takes (its own shape checks, no pointer): 1 line kernel / 0 generic kernel, the voxel
+// ranges that do work and the 64-voxel steps (line) or rows (generic) of one range; -1 for a shape it refuses.  No HIP call.
+int conv3d_wgrad_route(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad, int* ranges, int* per_range) {
+    if (!(B >= 1 && ID >= 1 && IH >= 1 && IW >= 1 && (stride == 1 || stride == 2) && pad >= 0 && Cin >= 8 && Cout >= 8 && Cin % 8 == 0 && Cout % 8 == 0))
+        return -1;
+    const int64_t M = (int64_t)B * (ID / stride) * (IH / stride) * (IW / stride);
+    if (!(M >= 1 && M < ((int64_t)1 << 31) && (int64_t)B * ID * IH * IW * Cin < ((int64_t)1 << 40))) return -1;
+    const WgradPlan p = wgrad_plan(B, ID, IH, IW, Cin, Cout, stride, pad);
+    *ranges = p.used;
+    *per_range = p.line ? p.steps_per_split : p.rows;
+    return p.line ? 1 : 0;
+}
+
 int conv3d_wgrad_tn(const bf16* dy, const bf16* x, float* dW, float* dbias, int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad,
                     hipStream_t st, float* workspace, int64_t workspace_floats) {
-    RALD_CHECK(dy && x && dW && B >= 1 && ID >= 1 && IH >= 1 && IW >= 1 && (stride == 1 || stride == 2) && pad >= 0, "conv3d_wgrad_tn: bad arguments");
+    RALD_CHECK(dy && x && dW && B >= 1 && ID >= 1 && IH >= 1 && IW >= 1 && (stride == 1 || stride == 2) && pad >= 0,
+               "conv3d_wgrad_tn: bad arguments (null pointer, empty volume, stride 1 or 2 only, pad >= 0)");
     RALD_CHECK(Cin % 8 == 0 && Cout % 8 == 0, "conv3d_wgrad_tn: channel counts must be multiples of 8");
     RALD_CHECK((uintptr_t)dy % 16 == 0 && (uintptr_t)x % 16 == 0, "conv3d_wgrad_tn: 16-byte alignment");
     const int OD = ID / stride, OH = IH / stride, OW = IW / stride;

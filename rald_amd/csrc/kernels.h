@@ -106,6 +106,8 @@ int64_t gemm_tn_workspace_floats(int M, int N1, int N2);
 int conv3d_wgrad_tn(const bf16* dy, const bf16* x, float* dW, float* dbias, int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad,
                     hipStream_t st, float* workspace = nullptr, int64_t workspace_floats = 0);
 int64_t conv3d_wgrad_workspace_floats(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad);
+// the plan conv3d_wgrad_tn launches with (pure host arithmetic): 1 line kernel, 0 generic kernel, -1 a refused shape
+int conv3d_wgrad_route(int B, int ID, int IH, int IW, int Cin, int Cout, int stride, int pad, int* ranges, int* per_range);
 
 // ---------------------------------------------------------------- norm.hip
 // out_bf16[m][c] = LN(x[m])[c] * (add_one + g[s][c]) + b[s][c],  s = (m / rows_per_group) * gstride
